@@ -10,7 +10,10 @@ reference als_CP.cxx:215-303) of the order-4 s=200 R=10 CP problem of BASELINE.j
 region. With N > 1 the SAME tensor is block-partitioned along its leading mode over the N ranks
 (strong scaling), one process per GPU, factor-matrix partials reduce-scattered over RCCL.
 
-One JSON line is printed by rank 0; see DESIGN.md "Measurement" for every field.
+One JSON line is printed by rank 0; see DESIGN.md "Measurement" for every field. `--steps K` is the
+number of timed sweeps and `ms_per_step` the milliseconds one of them took. `--dump-outputs DIR` writes
+what the timed sweeps computed as DIR/<name>.npy (the inputs are seeded: two builds compare output
+for output).
 """
 import argparse
 import json
@@ -312,6 +315,21 @@ def live_pmc_traffic(args, timeout_s=240):
            f"k_scan_suffix*: fetch {got['FETCH_SIZE'][0]:.4e} B (FETCH_SIZE KiB x 2, gfx950) + write "
            f"{got['WRITE_SIZE'][0]:.4e} B")
     return got["FETCH_SIZE"][0] + got["WRITE_SIZE"][0], src
+
+
+def dump_outputs(path, W, gradW, gradnorm, residual):
+    """`--dump-outputs DIR`: what the timed sweeps computed, as a caller of the session receives it —
+    the factor matrices W<i> (s_i x R), their gradients gradW<i> and the scalars gradnorm / residual —
+    as DIR/<name>.npy in fp64 (the engine's factor math is fp64 whatever the tensor's storage type;
+    at most sum(s_i) x R x 16 bytes, 1.2 MB for the largest workload)"""
+    import numpy as np
+    arrays = {f"W{i}": w for i, w in enumerate(W)}
+    arrays.update({f"gradW{i}": g for i, g in enumerate(gradW)})
+    arrays.update(gradnorm=np.float64(gradnorm), residual=np.float64(residual))
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _replayed_traffic(key):
@@ -699,6 +717,8 @@ def real_shape_main(args):
         ctx.profile_enable(0)
         del os.environ["PPALS_TRACE_STEPS"]
         launches, scan_ms, scan_bytes = ctx.profile_read(0)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, *cp.get_factors(with_grad=True), cp.gradnorm(), cp.residual())
         out["value"] = args.steps / el
         out["ms_per_step"] = 1e3 * el / args.steps
         out["schedule"] = cp.schedule
@@ -820,7 +840,12 @@ def main():
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)  # live_pmc_traffic's child runs
     ap.add_argument("--no-pmc", action="store_true",
                     help="do not count HBM bytes with rocprofv3 --pmc child passes (roofline.traffic = null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (factor matrices, their "
+                         "gradients, gradient norm, residual) as DIR/<name>.npy, fp64; same inputs every run")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.workload in REAL_SHAPES:
         real_shape_main(args)
@@ -1020,6 +1045,11 @@ def main():
         placement = {"error": str(e)}
     gradnorm = cp.gradnorm()
     resid = cp.residual()
+    if args.dump_outputs:
+        # (every rank: gathering the row-blocked gradients is a collective at N > 1; rank 0 writes)
+        W_out, gradW_out = cp.get_factors(with_grad=True)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, W_out, gradW_out, gradnorm, resid)
     vnorm = V.norm()
     # untimed breakdown pass: a few more sweeps with every bracketed kernel under events (each
     # event pair idles the stream for ~10 us, which is why the timed region brackets scans only)

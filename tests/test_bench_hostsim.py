@@ -23,7 +23,7 @@ def free_port():
 
 
 @pytest.mark.parametrize("world", [2, 3, 8])
-def test_bench_multi_rank_path_on_the_host_stand_in(world):
+def test_bench_multi_rank_path_on_the_host_stand_in(world, tmp_path):
     import hostsim_util
     hostsim_util.load()  # build once, before the ranks race for it
     port = free_port()
@@ -35,7 +35,8 @@ def test_bench_multi_rank_path_on_the_host_stand_in(world):
                    PPALS_BENCH_BACKEND="hostsim")
         procs.append(subprocess.Popen(
             [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3",
-             "--warmup", "1", "--workload", workload, "--dtype", "f64", "--no-cpu-baseline"],
+             "--warmup", "1", "--workload", workload, "--dtype", "f64", "--no-cpu-baseline",
+             "--dump-outputs", str(tmp_path / "multi")],
             env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = []
     for p in procs:
@@ -73,9 +74,63 @@ def test_bench_multi_rank_path_on_the_host_stand_in(world):
     env.pop("RANK", None), env.pop("WORLD_SIZE", None)
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3",
                           "--warmup", "1", "--workload", workload, "--dtype", "f64",
-                          "--no-cpu-baseline", "--no-config-records"], env=env, capture_output=True,
+                          "--no-cpu-baseline", "--no-config-records", "--dump-outputs", str(tmp_path / "one")],
+                         env=env, capture_output=True,
                          text=True, timeout=300)
     assert one.returncode == 0, one.stderr[-3000:]
     d1 = json.loads([ln for ln in one.stdout.splitlines() if ln.startswith("{")][0])
     assert abs(d1["final_gradnorm"] - d["final_gradnorm"]) < 1e-8 * d1["final_gradnorm"]
     assert abs(d1["final_rel_residual"] - d["final_rel_residual"]) < 1e-9
+    # --dump-outputs: the sharded run hands back the same full factors and gradients as one rank
+    import numpy as np
+    names = sorted(os.listdir(tmp_path / "one"))
+    assert len(names) == 10 and sorted(os.listdir(tmp_path / "multi")) == names
+    for n in names:
+        a, b = np.load(tmp_path / "multi" / n), np.load(tmp_path / "one" / n)
+        assert a.shape == b.shape and np.linalg.norm(a - b) <= 1e-9 * np.linalg.norm(b), n
+
+
+def _bench_dump(out_dir, steps, warmup):
+    env = dict(os.environ, PPALS_BENCH_BACKEND="hostsim", OMP_NUM_THREADS="2")
+    env.pop("RANK", None), env.pop("WORLD_SIZE", None)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                        "--warmup", str(warmup), "--workload", "cp4_s12_r3", "--dtype", "f64",
+                        "--no-cpu-baseline", "--no-config-records", "--dump-outputs", str(out_dir)],
+                       env=env, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    return json.loads(lines[0])
+
+
+def test_bench_dump_outputs_are_the_timed_sweeps(tmp_path):
+    """--dump-outputs DIR: the factors, gradients, gradient norm and residual after exactly
+    warmup + steps sweeps from the seeded start (the fp64 oracle's iterates), the same on every run;
+    --steps is the number of timed sweeps and ms_per_step the time of one"""
+    import numpy as np
+    import oracle_lib as O
+    import hostsim_util
+    hostsim_util.load()
+    lens, R, steps, warmup = [12, 12, 12, 12], 3, 3, 1
+    d = _bench_dump(tmp_path / "a", steps, warmup)
+    assert d["steps"] == steps and d["warmup"] == warmup and d["ms_per_step"] > 0
+    assert abs(d["ms_per_step"] * d["value"] - 1e3) < 1e-6 * 1e3
+    names = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert names == sorted([f"W{i}.npy" for i in range(4)] + [f"gradW{i}.npy" for i in range(4)]
+                           + ["gradnorm.npy", "residual.npy"])
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    V = O.build_V(O.init_factors(lens, R, 1000))
+    _, _, W_ref, G_ref = O.als_cp_dt(V, O.init_factors(lens, R, 2000), O.init_factors(lens, R, 3000),
+                                     tol=0.0, maxiter=warmup + steps - 1, resprint=10 ** 9)
+    for i in range(4):
+        assert got[f"W{i}"].shape == (lens[i], R)
+        assert np.linalg.norm(got[f"W{i}"] - W_ref[i]) < 1e-9 * np.linalg.norm(W_ref[i])
+        assert np.linalg.norm(got[f"gradW{i}"] - G_ref[i]) < 1e-9 * np.linalg.norm(G_ref[i])
+    assert abs(float(got["gradnorm"]) - d["final_gradnorm"]) <= 1e-12 * d["final_gradnorm"]
+    assert abs(float(got["residual"]) - O.residual(V, W_ref)) < 1e-9 * np.linalg.norm(V)
+    # the same arguments give the same outputs
+    _bench_dump(tmp_path / "b", steps, warmup)
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "b" / n), got[n[:-4]]), n
