@@ -103,6 +103,35 @@ int ppals_tensor_upload(ppals_tensor *t, const double *host_full);
 /* the reverse (the commented-out V.write_dense_to_file, test_ALS.cxx:347): this rank's leading-mode
  * rows, widened to fp64, into their places of the FULL host tensor; other ranks' rows untouched */
 int ppals_tensor_download(ppals_tensor *t, double *host_full);
+
+/* ---- the tensor from and to DEVICE memory (a torch.Tensor in HBM, say) ----
+ * A view is a box of the GLOBAL tensor, box_lo[i] <= index_i < box_lo[i] + box_len[i] (NULL/NULL: the
+ * whole tensor), whose element (j_0, ..., j_{N-1}) (box-relative) is at ptr + sum_i j_i * strides[i]
+ * elements; strides >= 0 (0: broadcast), NULL = dense over the box, first index fastest (a C-contiguous
+ * torch tensor has the REVERSED strides). Each rank copies the part of the box in its own leading-mode
+ * rows and touches nothing else. `stream` is the hipStream_t the caller works on (NULL: the null
+ * stream): the copy starts after the work already queued there, and work queued there later runs
+ * after it; the host does not block. Every bad argument is refused before anything is launched. */
+#define PPALS_F16 2  /* element types of an import source / export destination only: */
+#define PPALS_BF16 3 /* a tensor is still stored as PPALS_F32 or PPALS_F64            */
+/* Copy the view at src (type F32, F64, F16 or BF16, on the context's device) into the tensor,
+ * converting to its storage type on the device (f16/bf16/f32 -> f64 exact; f64 -> f32 rounds to
+ * nearest even, bit-identical to ppals_tensor_upload). Bumps the generation like an upload. */
+int ppals_tensor_import_device(ppals_tensor *t, const void *src, int src_dtype, const int64_t *box_lo,
+                               const int64_t *box_len, const int64_t *strides, void *stream);
+/* The reverse: this rank's rows of the box into the view at dst (type F32 or F64). The destination
+ * must not overlap itself: no zero stride on an extent > 1, and with the modes of extent > 1 sorted
+ * by stride, each stride beyond the last element of the modes before it. */
+int ppals_tensor_export_device(ppals_tensor *t, void *dst, int dst_dtype, const int64_t *box_lo,
+                               const int64_t *box_len, const int64_t *strides, void *stream);
+/* Every check the two calls make, pointer queries included, and no launch: returns PPALS_OK or the
+ * error the call would return, with ppals_last_error() saying why. direction 0 = import, 1 = export.
+ * The pointer must be device memory of the context's device (not host, pinned host or managed
+ * memory) and the view's byte span (sum_i (len_i - 1) * stride_i + 1) * elem_size must lie inside
+ * the allocation that holds it. */
+int ppals_tensor_check_device_view(ppals_tensor *t, int direction, const void *ptr, int dtype,
+                                   const int64_t *box_lo, const int64_t *box_len,
+                                   const int64_t *strides);
 int ppals_tensor_norm(ppals_tensor *t, double *out); /* V.norm2(), test_ALS.cxx:328 */
 /* same counter-based generator for host-side factor initialisation (W.fill_random(0,1)) */
 void ppals_fill_uniform_host(double *out, int64_t n, uint64_t seed, uint64_t offset, double lo,

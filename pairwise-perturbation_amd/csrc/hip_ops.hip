@@ -18,6 +18,7 @@
 #include "kernels_scan.hip.h"
 #include "kernels_small.hip.h"
 #include "kernels_eig.hip.h"
+#include "kernels_io.hip.h"
 
 namespace ppals {
 #define HIP_CHECK(expr)                                                                       \
@@ -166,6 +167,8 @@ class HipOps : public Ops {
       if (kv.second.Q) hipFree(kv.second.Q);
     if (st2_) hipStreamDestroy(st2_);
     if (handover_) hipFree(handover_);
+    if (io_ev_in_) hipEventDestroy(io_ev_in_);
+    if (io_ev_out_) hipEventDestroy(io_ev_out_);
     hipStreamDestroy(st_);
   }
 
@@ -460,6 +463,110 @@ class HipOps : public Ops {
     }
     free(stage);
   }
+
+  // ------------------------------------------------------------------ device views
+  bool device_ptr_info(const void *p, PtrInfo *out, std::string *why) override {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+      (void)hipGetLastError();
+      *why = "unknown to the HIP runtime";
+      return false;
+    }
+    out->device = at.device;
+    out->is_device = at.type == hipMemoryTypeDevice && !at.isManaged && at.device == dev_;
+    if (!out->is_device) {
+      *why = at.isManaged || at.type == hipMemoryTypeManaged || at.type == hipMemoryTypeUnified
+                 ? "managed memory"
+             : at.type == hipMemoryTypeHost ? "host memory"
+             : at.device != dev_ ? "memory of device " + std::to_string(at.device) + ", the context is on " +
+                                       std::to_string(dev_)
+                                 : "not device memory";
+      return true;
+    }
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+      (void)hipGetLastError();
+      *why = "no allocation holds the pointer";
+      out->is_device = false;
+      return false;
+    }
+    out->base = (uint64_t)(uintptr_t)base;
+    out->size = size;
+    return true;
+  }
+
+  template <bool IMP, typename S, typename D>
+  void io_launch(const ViewPlan &p, const S *src, D *dst) {
+    if (p.kind == DV_STREAM) {
+      bool vec = p.vs[0] == 1 && p.rs[0] == 1 && (uintptr_t)src % (4 * sizeof(S)) == 0 &&
+                 (uintptr_t)dst % (4 * sizeof(D)) == 0;
+      if (p.nd > 1) {
+        vec = vec && p.n[0] % 4 == 0;
+        for (int m = 1; m < p.nd; m++) vec = vec && p.vs[m] % 4 == 0 && p.rs[m] % 4 == 0;
+      }
+      const int g = grid_for(vec ? (p.count + 3) / 4 : p.count, 256, 16384);
+      if (vec)
+        hipLaunchKernelGGL((k_io_stream<IMP, true, S, D>), dim3(g), dim3(256), 0, st_, src, dst, p);
+      else
+        hipLaunchKernelGGL((k_io_stream<IMP, false, S, D>), dim3(g), dim3(256), 0, st_, src, dst, p);
+    } else if (p.kind == DV_TILE) {
+      int64_t FA, tA, tB, tiles;
+      dv_tile_grid(p, &FA, &tA, &tB, &tiles);
+      const int g = (int)std::min<int64_t>(tiles, 16384);
+      hipLaunchKernelGGL((k_io_tile<IMP, S, D>), dim3(g), dim3(256), 0, st_, src, dst, p, FA, tA, tB,
+                         tiles, p.rs[p.fk]);
+    } else {
+      hipLaunchKernelGGL((k_io_gather<IMP, S, D>), dim3(grid_for(p.count, 256, 16384)), dim3(256), 0,
+                         st_, src, dst, p);
+    }
+    HIP_CHECK(hipGetLastError());
+  }
+  template <typename R>
+  void io_import(const ViewPlan &p, const void *view, int vdt, R *V) {
+    const char *s = (const char *)view;
+    switch (vdt) {
+      case DV_F32: io_launch<true>(p, (const float *)s + p.voff, V + p.roff); break;
+      case DV_F64: io_launch<true>(p, (const double *)s + p.voff, V + p.roff); break;
+      case DV_F16: io_launch<true>(p, (const _Float16 *)s + p.voff, V + p.roff); break;
+      case DV_BF16: io_launch<true>(p, (const io_bf16 *)s + p.voff, V + p.roff); break;
+      default: throw std::runtime_error("ppals: bad view dtype");
+    }
+  }
+  template <typename R>
+  void io_export(const ViewPlan &p, void *view, int vdt, const R *V) {
+    if (vdt == DV_F32)
+      io_launch<false>(p, V + p.roff, (float *)view + p.voff);
+    else if (vdt == DV_F64)
+      io_launch<false>(p, V + p.roff, (double *)view + p.voff);
+    else
+      throw std::runtime_error("ppals: bad view dtype");
+  }
+  void copy_view(const ViewPlan &p, int dir, void *view, int vdt, void *V, int dt,
+                 void *caller_stream) override {
+    HIP_CHECK(hipSetDevice(dev_));
+    if (!io_ev_in_) {
+      HIP_CHECK(hipEventCreateWithFlags(&io_ev_in_, hipEventDisableTiming));
+      HIP_CHECK(hipEventCreateWithFlags(&io_ev_out_, hipEventDisableTiming));
+    }
+    hipStream_t cs = (hipStream_t)caller_stream;
+    HIP_CHECK(hipEventRecord(io_ev_in_, cs));  // the view is ready once the caller's work so far is done
+    HIP_CHECK(hipStreamWaitEvent(st_, io_ev_in_, 0));
+    if (dir == DV_IMPORT) {
+      if (dt == F32)
+        io_import(p, view, vdt, (float *)V);
+      else
+        io_import(p, view, vdt, (double *)V);
+    } else {
+      if (dt == F32)
+        io_export(p, view, vdt, (const float *)V);
+      else
+        io_export(p, view, vdt, (const double *)V);
+    }
+    HIP_CHECK(hipEventRecord(io_ev_out_, st_));  // and the caller's later work waits for the copy
+    HIP_CHECK(hipStreamWaitEvent(cs, io_ev_out_, 0));
+  }
+  hipEvent_t io_ev_in_ = nullptr, io_ev_out_ = nullptr;
 
   void *try_alloc(size_t bytes) override {
     void *p = nullptr;

@@ -10,6 +10,9 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "device_view.h"
+#include "preload_policy.h"
+
 namespace ppals {
 
 enum DType { F32 = 0, F64 = 1 };
@@ -119,6 +122,27 @@ class Ops {
   virtual void scan_store_mode(int mode) { (void)mode; }
   // free device memory in bytes, (size_t)-1: unknown / unlimited
   virtual size_t mem_available() { return (size_t)-1; }
+
+  // ---- strided device views (ppals_tensor_import_device / _export_device, device_view.h) ----
+  // What the runtime knows of a pointer. is_device: device memory of this Ops' device (not host,
+  // pinned host or managed memory); [base, base + size): the allocation holding it. false: the
+  // runtime does not know the pointer at all (*why says so).
+  struct PtrInfo {
+    bool is_device = false;
+    int device = -1;
+    uint64_t base = 0, size = 0;
+  };
+  virtual bool device_ptr_info(const void * /*p*/, PtrInfo * /*out*/, std::string * /*why*/) {
+    throw Unsupported("ppals: this back end has no device views");
+  }
+  // Copy what `plan` (dv_plan) describes between the view at `view` (element type vdt, offset by
+  // plan.voff) and the shard V (element type dt, offset by plan.roff): dir DV_IMPORT writes the
+  // shard, DV_EXPORT the view. Ordered after the work queued on `caller_stream` so far, and work
+  // queued there later runs after the copy; the host does not block.
+  virtual void copy_view(const ViewPlan & /*plan*/, int /*dir*/, void * /*view*/, int /*vdt*/,
+                         void * /*V*/, int /*dt*/, void * /*caller_stream*/) {
+    throw Unsupported("ppals: this back end has no device views");
+  }
 
   // ---- Khatri-Rao product, plain: out[j + J*c] = prod_f W_f[j_f + ld_f*(col0+c)], fp64 ----
   virtual void krp(double *out, const FactorRef *f, int nf, int col0, int ncols) = 0;

@@ -265,6 +265,65 @@ int ppals_tensor_norm(ppals_tensor *t, double *out) {
   API_END(PPALS_ERR_HIP)
 }
 
+// ------------------------------------------------------------------ device views
+// every check of ppals_tensor_check_device_view; on success *a holds the resolved view
+static int check_view(ppals_tensor *t, int dir, const void *ptr, int dtype, const int64_t *box_lo,
+                      const int64_t *box_len, const int64_t *strides, ViewArgs *a) {
+  const char *what = dir == DV_EXPORT ? "ppals_tensor_export_device: " : "ppals_tensor_import_device: ";
+  if (!t || !t->ctx || !ptr) return fail(PPALS_ERR_ARG, "NULL tensor or pointer");
+  std::string err;
+  if (!dv_check_args(dir, t->d.order, t->d.glens, dtype, box_lo, box_len, strides, a, &err)) {
+    g_err = what + err;
+    return PPALS_ERR_ARG;
+  }
+  Ops::PtrInfo info;
+  if (!t->ctx->ops->device_ptr_info(ptr, &info, &err) || !info.is_device) {
+    g_err = std::string(what) + "the pointer is not device memory of the context's device (" +
+            (err.empty() ? "host, pinned host or managed memory" : err) +
+            "); a torch tensor must live on that device, and torch must be imported before "
+            "libppals is loaded so that both share one HIP runtime";
+    return PPALS_ERR_ARG;
+  }
+  if (!dv_in_allocation((uint64_t)(uintptr_t)ptr, a->span, info.base, info.size)) {
+    g_err = std::string(what) + "the view spans " + std::to_string(a->span) +
+            " bytes from the pointer, past the end of its allocation (" + std::to_string(info.size) +
+            " bytes, the pointer at offset " + std::to_string((uint64_t)(uintptr_t)ptr - info.base) + ")";
+    return PPALS_ERR_ARG;
+  }
+  return PPALS_OK;
+}
+static int copy_device_view(ppals_tensor *t, int dir, void *ptr, int dtype, const int64_t *box_lo,
+                            const int64_t *box_len, const int64_t *strides, void *stream) {
+  ViewArgs a;
+  const int rc = check_view(t, dir, ptr, dtype, box_lo, box_len, strides, &a);
+  if (rc != PPALS_OK) return rc;
+  const ViewPlan p = dv_plan(a, t->d.glens, t->d.row0, t->d.llens[0]);
+  if (dir == DV_IMPORT) t->generation++;
+  if (p.kind != DV_EMPTY) t->ctx->ops->copy_view(p, dir, ptr, dtype, t->d.data, t->d.dtype, stream);
+  return PPALS_OK;
+}
+int ppals_tensor_check_device_view(ppals_tensor *t, int direction, const void *ptr, int dtype,
+                                   const int64_t *box_lo, const int64_t *box_len,
+                                   const int64_t *strides) {
+  API_BEGIN
+  ViewArgs a;
+  return check_view(t, direction, ptr, dtype, box_lo, box_len, strides, &a);
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_tensor_import_device(ppals_tensor *t, const void *src, int src_dtype, const int64_t *box_lo,
+                               const int64_t *box_len, const int64_t *strides, void *stream) {
+  API_BEGIN
+  return copy_device_view(t, DV_IMPORT, const_cast<void *>(src), src_dtype, box_lo, box_len,
+                          strides, stream);
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_tensor_export_device(ppals_tensor *t, void *dst, int dst_dtype, const int64_t *box_lo,
+                               const int64_t *box_len, const int64_t *strides, void *stream) {
+  API_BEGIN
+  return copy_device_view(t, DV_EXPORT, dst, dst_dtype, box_lo, box_len, strides, stream);
+  API_END(PPALS_ERR_HIP)
+}
+
 static inline uint64_t sm64(uint64_t x) {
   x += 0x9E3779B97F4A7C15ull;
   x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;

@@ -17,6 +17,7 @@ import weakref
 import numpy as np
 
 F32, F64 = 0, 1
+F16, BF16 = 2, 3  # element types of a device view only (import source / export destination)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIBPATH = os.environ.get("PPALS_LIB", os.path.join(os.path.dirname(_HERE), "lib", "libppals.so"))
 _lib = None
@@ -43,7 +44,8 @@ EXPORTS = [
     "ppals_ctx_sync", "ppals_profile_enable", "ppals_profile_read", "ppals_profile_reset",
     "ppals_tensor_create", "ppals_tensor_destroy", "ppals_tensor_local_rows",
     "ppals_tensor_fill_cp", "ppals_tensor_fill_uniform", "ppals_tensor_upload",
-    "ppals_tensor_download",
+    "ppals_tensor_download", "ppals_tensor_import_device", "ppals_tensor_export_device",
+    "ppals_tensor_check_device_view",
     "ppals_tensor_fill_laplacian", "ppals_tensor_fill_collinear", "ppals_collinear_factors",
     "ppals_tensor_norm", "ppals_fill_uniform_host", "ppals_tree_node", "ppals_mttkrp",
     "ppals_pp_operator", "ppals_cp_residual", "ppals_cp_gram_system", "ppals_cp_create",
@@ -85,6 +87,13 @@ def _check(rc, allow_bool=False):
 
 def _dp(a):
     return a.ctypes.data_as(c_dp)
+
+
+def _torch():
+    """torch, imported on first use only: `import ppals` works without it. It must have been imported
+    before libppals was loaded for the two to share one HIP runtime (and so one view of pointers)."""
+    import torch
+    return torch
 
 
 def flat(Ws):
@@ -131,6 +140,7 @@ class Context:
     """replaces CTF::World (test_ALS.cxx:200): one per process, one GPU"""
 
     def __init__(self, device=0):
+        self.device = device
         self._h = C.c_void_p()
         self._children = weakref.WeakSet()  # tensors / sessions that must die before the context
         _check(lib().ppals_ctx_create(C.byref(self._h), device))
@@ -228,6 +238,87 @@ class Tensor:
         """the tensor as fp64, first index fastest (this rank's rows; zeros elsewhere)"""
         out = np.zeros(self.lens, dtype=np.float64, order="F")
         _check(lib().ppals_tensor_download(self._h, _dp(out)))
+        return out
+
+    # ---- device views: torch tensors (or any device pointer) in and out, no host round trip ----
+    def _box(self, shape, lo):
+        n = len(self.lens)
+        if len(shape) != n:
+            raise PpalsError(f"the view has {len(shape)} modes, the tensor {n}")
+        lo = [0] * n if lo is None else [int(x) for x in lo]
+        return (C.c_int64 * n)(*lo), (C.c_int64 * n)(*[int(x) for x in shape])
+
+    def check_view(self, direction, ptr, dtype, shape, strides, lo=None):
+        """ppals_tensor_check_device_view: PPALS_OK (0) or the error code the copy would return; the
+        message is ppals_last_error(). direction 0 = import, 1 = export."""
+        blo, blen = self._box(shape, lo)
+        st = (C.c_int64 * len(self.lens))(*[int(x) for x in strides])
+        return lib().ppals_tensor_check_device_view(self._h, int(direction), C.c_void_p(int(ptr)),
+                                                    int(dtype), blo, blen, st)
+
+    def import_device(self, ptr, dtype, shape, strides, lo=None, stream=0):
+        """raw ppals_tensor_import_device: element (j_0, ...) of the box at lo is at
+        ptr + sum_i j_i * strides[i] elements of type dtype (F32 / F64 / F16 / BF16)"""
+        blo, blen = self._box(shape, lo)
+        st = (C.c_int64 * len(self.lens))(*[int(x) for x in strides])
+        _check(lib().ppals_tensor_import_device(self._h, C.c_void_p(int(ptr)), int(dtype), blo, blen,
+                                                st, C.c_void_p(int(stream or 0))))
+        return self
+
+    def export_device(self, ptr, dtype, shape, strides, lo=None, stream=0):
+        """raw ppals_tensor_export_device: this rank's rows of the box into the view (F32 / F64)"""
+        blo, blen = self._box(shape, lo)
+        st = (C.c_int64 * len(self.lens))(*[int(x) for x in strides])
+        _check(lib().ppals_tensor_export_device(self._h, C.c_void_p(int(ptr)), int(dtype), blo, blen,
+                                                st, C.c_void_p(int(stream or 0))))
+        return self
+
+    def _torch_view(self, x, dtypes):
+        torch = _torch()
+        if x.dtype not in dtypes:
+            raise PpalsError(f"torch dtype {x.dtype} is not one of {sorted(map(str, dtypes))}")
+        if x.device.type != "cuda" or x.device.index != self.ctx.device:
+            raise PpalsError(f"the torch tensor is on {x.device}, the context on cuda:{self.ctx.device}")
+        code = {torch.float32: F32, torch.float64: F64, torch.float16: F16, torch.bfloat16: BF16}
+        return x.data_ptr(), code[x.dtype], tuple(x.shape), x.stride()
+
+    @staticmethod
+    def _stream(stream):
+        if stream is None:
+            return _torch().cuda.current_stream().cuda_stream
+        return getattr(stream, "cuda_stream", stream)
+
+    @classmethod
+    def from_torch(cls, ctx, x, dtype=None):
+        """a tensor with lens = x.shape (mode i = dim i) holding x: stored as F64 for a float64 x,
+        as F32 otherwise, unless dtype says. Under P > 1 ranks each rank copies its own rows of x."""
+        torch = _torch()
+        if dtype is None:
+            dtype = F64 if x.dtype == torch.float64 else F32
+        return cls(ctx, list(x.shape), dtype).import_torch(x)
+
+    def import_torch(self, x, lo=None, stream=None):
+        """copy the torch tensor x (any strides, f16 / bf16 / f32 / f64, on the context's device) into
+        the box of the tensor at lo (default: the origin), ordered on `stream` (default: torch's
+        current stream); the host does not wait"""
+        torch = _torch()
+        ptr, code, shape, strides = self._torch_view(
+            x, (torch.float32, torch.float64, torch.float16, torch.bfloat16))
+        return self.import_device(ptr, code, shape, strides, lo, self._stream(stream))
+
+    def export_torch(self, out, lo=None, stream=None):
+        """this rank's rows of the box at lo (shape out.shape) into the torch tensor out (f32 / f64,
+        any strides that do not overlap); other elements of out are left alone"""
+        torch = _torch()
+        ptr, code, shape, strides = self._torch_view(out, (torch.float32, torch.float64))
+        return self.export_device(ptr, code, shape, strides, lo, self._stream(stream))
+
+    def to_torch(self, dtype=None):
+        """the tensor as a new torch tensor on the context's device (this rank's rows; zeros
+        elsewhere), ordered on torch's current stream"""
+        torch = _torch()
+        out = torch.zeros(self.lens, dtype=dtype or torch.float32, device=f"cuda:{self.ctx.device}")
+        self.export_torch(out)
         return out
 
     def norm(self):
