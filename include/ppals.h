@@ -8,8 +8,9 @@
  * Conventions (identical to the reference's CTF objects):
  *   - tensors are dense, FIRST INDEX FASTEST: V[i0 + lens[0]*(i1 + lens[1]*(i2 + ...))]
  *   - factor matrix W_i is lens[i] x R, column-major; `Wflat` = W_0,...,W_{N-1} concatenated, fp64
- *   - the tensor lives in HBM as fp32 (PPALS_F32) or fp64 (PPALS_F64); all factor-matrix, Gram,
- *     solve and norm arithmetic is fp64 in both modes
+ *   - the tensor lives in HBM as fp32 (PPALS_F32), fp64 (PPALS_F64) or bf16 (PPALS_BF16, CP only);
+ *     all factor-matrix, Gram, solve and norm arithmetic is fp64 in every mode, and what is computed
+ *     from a bf16 tensor is held in fp32 or fp64
  *   - multi-GPU: one process per GPU; the tensor is block-partitioned along its LEADING mode
  *     (rank p owns rows [p*ceil(s0/P), ...)), factor matrices are replicated
  *
@@ -112,11 +113,15 @@ int ppals_tensor_download(ppals_tensor *t, double *host_full);
  * rows and touches nothing else. `stream` is the hipStream_t the caller works on (NULL: the null
  * stream): the copy starts after the work already queued there, and work queued there later runs
  * after it; the host does not block. Every bad argument is refused before anything is launched. */
-#define PPALS_F16 2  /* element types of an import source / export destination only: */
-#define PPALS_BF16 3 /* a tensor is still stored as PPALS_F32 or PPALS_F64            */
+#define PPALS_F16 2  /* an import source only                                              */
+#define PPALS_BF16 3 /* an import source, or a tensor's storage (ppals_tensor_create):     */
+/* values stored as torch rounds float64 to bfloat16 (fp64 -> fp32 -> bf16, each round-to-nearest-even);
+ * every tensor entry point and every CP session takes such a tensor, ppals_tucker_create refuses it
+ * with PPALS_ERR_UNSUPPORTED. A back end that cannot hold bf16 refuses it at creation, likewise. */
 /* Copy the view at src (type F32, F64, F16 or BF16, on the context's device) into the tensor,
  * converting to its storage type on the device (f16/bf16/f32 -> f64 exact; f64 -> f32 rounds to
- * nearest even, bit-identical to ppals_tensor_upload). Bumps the generation like an upload. */
+ * nearest even, bit-identical to ppals_tensor_upload; into bf16 storage a bf16 view copies bit for bit
+ * and wider views round as above). Bumps the generation like an upload. */
 int ppals_tensor_import_device(ppals_tensor *t, const void *src, int src_dtype, const int64_t *box_lo,
                                const int64_t *box_len, const int64_t *strides, void *stream);
 /* The reverse: this rank's rows of the box into the view at dst (type F32 or F64). The destination

@@ -43,6 +43,9 @@ int tensor_create(Ops &ops, Comm &comm, int order, const int64_t *glens, int dty
     *err = "tensor order must be in [2, 8]";
     return -1;
   }
+  if (!ops.supports_storage(dtype))
+    throw Unsupported(dtype == BF16 ? "ppals: this back end cannot store a bf16 tensor"
+                                    : "ppals: this back end cannot store this tensor type");
   TensorDesc t;
   t.order = order;
   t.dtype = dtype;
@@ -1059,7 +1062,7 @@ void CpEngine::ms_place_release_unchosen() {
 size_t CpEngine::ms_X_bytes(int first, int k) const {
   int64_t J = 1;
   for (int q = 0; q < k; q++) J *= ext((first + q) % N_);
-  return (size_t)(V_.nloc / J) * R_ * dtype_size(V_.dtype);
+  return (size_t)(V_.nloc / J) * R_ * dtype_size(work_dt(V_.dtype));
 }
 
 // Allocation of one of the session's large buffers. The optional resident layouts (the padded
@@ -1149,7 +1152,7 @@ void CpEngine::ms_start_step(int first) {
     f.push_back(fref(m, W_.data()));  // storage order: first listed = fastest
     mask |= 1u << m;
   }
-  ms_X_.dt = V_.dtype;
+  ms_X_.dt = work_dt(V_.dtype);
   ms_X_.contracted = mask;
   if ((size_t)L * T * R_ * dtype_size(ms_X_.dt) != xbytes)
     throw std::runtime_error("ppals: internal error (first-level intermediate size)");
@@ -1399,7 +1402,7 @@ void CpEngine::lr_step_begin(int left, bool reuse, int r) {
     f.ld = V_.glens[left];
     ops_.scan_contract(pl.lay->ptr, V_.dtype, pl.L, ext(left), pl.T, &f, 1, r, lr_T_, F64, pl.Lc, n,
                        pl.pad);
-    ops_.lowrank_accumulate(lr_cache_[left], V_.dtype, n, R_, lr_T_, r, lr_small_);
+    ops_.lowrank_accumulate(lr_cache_[left], work_dt(V_.dtype), n, R_, lr_T_, r, lr_small_);
     ms_X_ = lr_desc_[left];
     ms_X_.buf = lr_cache_[left];
     ms_X_.valid = true;
@@ -1908,7 +1911,7 @@ const CpEngine::PPOp &CpEngine::pp_get(const std::string &seq) {
     op.modes = pl.kept;
     op.elems = L * T;
     // (at order 3 a level-1 result already IS a pair operator: those stay fp64 like all the others)
-    op.dt = (pp_fast_ && N_ > 3) ? V_.dtype : F64;
+    op.dt = (pp_fast_ && N_ > 3) ? work_dt(V_.dtype) : F64;
     if (pp_fast_ && N_ > 3 && schedule_ == 1 && ms_k_ == 1 && ms_root_ == mode && ms_X_.valid &&
         ms_X_.dt == op.dt && !pp_no_borrow_) {
       // The exact sweep that ended just now left its first-level intermediate X = V x_mode W_mode

@@ -10,6 +10,7 @@
 #include <stdexcept>
 #include <string>
 #include <map>
+#include <type_traits>
 #include <vector>
 
 #include "hip_ops.h"
@@ -19,6 +20,7 @@
 #include "kernels_small.hip.h"
 #include "kernels_eig.hip.h"
 #include "kernels_io.hip.h"
+#include "kernels_bf16.hip.h"
 
 namespace ppals {
 #define HIP_CHECK(expr)                                                                       \
@@ -199,6 +201,7 @@ class HipOps : public Ops {
   void sync() override { HIP_CHECK(hipStreamSynchronize(st_)); }
   void *stream() override { return (void *)st_; }
   void bind() override { HIP_CHECK(hipSetDevice(dev_)); }
+  bool supports_storage(int dt) override { return dt == F32 || dt == F64 || dt == BF16; }
 
   // ------------------------------------------------------------------ generation / norms
   void fill_uniform(void *V, int dt, int64_t l0, int64_t g0, int64_t row0, int64_t rest,
@@ -207,6 +210,9 @@ class HipOps : public Ops {
     int g = grid_for(n, 256, 16384);
     if (dt == F32)
       hipLaunchKernelGGL(k_fill_uniform<float>, dim3(g), dim3(256), 0, st_, (float *)V, l0, g0,
+                         row0, rest, seed, lo, hi);
+    else if (dt == BF16)
+      hipLaunchKernelGGL(k_fill_uniform<bf16s>, dim3(g), dim3(256), 0, st_, (bf16s *)V, l0, g0,
                          row0, rest, seed, lo, hi);
     else
       hipLaunchKernelGGL(k_fill_uniform<double>, dim3(g), dim3(256), 0, st_, (double *)V, l0, g0,
@@ -220,6 +226,9 @@ class HipOps : public Ops {
     if (dt == F32)
       hipLaunchKernelGGL(k_fill_laplacian<float>, dim3(g), dim3(256), 0, st_, (float *)V, l0, g0,
                          row0, rest, ndigits, s);
+    else if (dt == BF16)
+      hipLaunchKernelGGL(k_fill_laplacian<bf16s>, dim3(g), dim3(256), 0, st_, (bf16s *)V, l0, g0,
+                         row0, rest, ndigits, s);
     else
       hipLaunchKernelGGL(k_fill_laplacian<double>, dim3(g), dim3(256), 0, st_, (double *)V, l0, g0,
                          row0, rest, ndigits, s);
@@ -230,6 +239,9 @@ class HipOps : public Ops {
     int g = grid_for(l0 * rest, 256, 16384);
     if (dt == F32)
       hipLaunchKernelGGL((k_uniform_noise<float, 0>), dim3(g), dim3(256), 0, st_, (float *)V, l0,
+                         g0, row0, rest, seed, lo, hi, alpha, (double *)nullptr);
+    else if (dt == BF16)
+      hipLaunchKernelGGL((k_uniform_noise<bf16s, 0>), dim3(g), dim3(256), 0, st_, (bf16s *)V, l0,
                          g0, row0, rest, seed, lo, hi, alpha, (double *)nullptr);
     else
       hipLaunchKernelGGL((k_uniform_noise<double, 0>), dim3(g), dim3(256), 0, st_, (double *)V, l0,
@@ -365,9 +377,12 @@ class HipOps : public Ops {
   template <typename TV, int MODE>
   void rank_stream(void *V, int64_t M, int64_t K, const double *Q, const double *P, int R,
                    double *out) {
-    if (rank_mfma<TV, MODE>(V, M, K, Q, P, R, out)) return;
-    if constexpr (MODE != 2)
-      if (rank_split<TV, MODE>(V, M, K, Q, P, R, out)) return;
+    // (a bf16 tensor: the per-element kernels below, whose fp64 model is rounded once per element)
+    if constexpr (!std::is_same<TV, bf16s>::value) {
+      if (rank_mfma<TV, MODE>(V, M, K, Q, P, R, out)) return;
+      if constexpr (MODE != 2)
+        if (rank_split<TV, MODE>(V, M, K, Q, P, R, out)) return;
+    }
     int kch = 32;
     while ((K + kch - 1) / kch > 65535) kch *= 2;
     dim3 grid((unsigned)((M + 255) / 256), (unsigned)((K + kch - 1) / kch));
@@ -397,6 +412,8 @@ class HipOps : public Ops {
                  int R) override {
     if (dt == F32)
       rank_stream<float, 0>(V, M, K, Q, P, R, nullptr);
+    else if (dt == BF16)
+      rank_stream<bf16s, 0>(V, M, K, Q, P, R, nullptr);
     else
       rank_stream<double, 0>(V, M, K, Q, P, R, nullptr);
   }
@@ -407,11 +424,15 @@ class HipOps : public Ops {
     if (Q == nullptr) {
       if (dt == F32)
         rank_stream<float, 2>(v, M, K, nullptr, nullptr, 0, out);
+      else if (dt == BF16)
+        rank_stream<bf16s, 2>(v, M, K, nullptr, nullptr, 0, out);
       else
         rank_stream<double, 2>(v, M, K, nullptr, nullptr, 0, out);
     } else {
       if (dt == F32)
         rank_stream<float, 1>(v, M, K, Q, P, R, out);
+      else if (dt == BF16)
+        rank_stream<bf16s, 1>(v, M, K, Q, P, R, out);
       else
         rank_stream<double, 1>(v, M, K, Q, P, R, out);
     }
@@ -433,6 +454,9 @@ class HipOps : public Ops {
       if (dt == F32)
         hipLaunchKernelGGL(k_convert_rows<float>, dim3(grid_for(n, 256)), dim3(256), 0, st_,
                            (float *)V + c0 * l0, stage, n);
+      else if (dt == BF16)
+        hipLaunchKernelGGL(k_convert_rows<bf16s>, dim3(grid_for(n, 256)), dim3(256), 0, st_,
+                           (bf16s *)V + c0 * l0, stage, n);
       else
         hipLaunchKernelGGL(k_convert_rows<double>, dim3(grid_for(n, 256)), dim3(256), 0, st_,
                            (double *)V + c0 * l0, stage, n);
@@ -452,6 +476,9 @@ class HipOps : public Ops {
       if (dt == F32)
         hipLaunchKernelGGL(k_widen_rows<float>, dim3(grid_for(n, 256)), dim3(256), 0, st_, stage,
                            (const float *)V + c0 * l0, n);
+      else if (dt == BF16)
+        hipLaunchKernelGGL(k_widen_rows<bf16s>, dim3(grid_for(n, 256)), dim3(256), 0, st_, stage,
+                           (const bf16s *)V + c0 * l0, n);
       else
         hipLaunchKernelGGL(k_widen_rows<double>, dim3(grid_for(n, 256)), dim3(256), 0, st_, stage,
                            (const double *)V + c0 * l0, n);
@@ -555,11 +582,15 @@ class HipOps : public Ops {
     if (dir == DV_IMPORT) {
       if (dt == F32)
         io_import(p, view, vdt, (float *)V);
+      else if (dt == BF16)
+        io_import(p, view, vdt, (bf16s *)V);
       else
         io_import(p, view, vdt, (double *)V);
     } else {
       if (dt == F32)
         io_export(p, view, vdt, (const float *)V);
+      else if (dt == BF16)
+        io_export(p, view, vdt, (const bf16s *)V);
       else
         io_export(p, view, vdt, (const double *)V);
     }
@@ -594,6 +625,9 @@ class HipOps : public Ops {
     if (dt == F32)
       hipLaunchKernelGGL(k_unpack_shards<float>, dim3(g), dim3(256), 0, st_, (const char *)stage,
                          s0, rest, blk, P, chunk_bytes, (float *)full);
+    else if (dt == BF16)
+      hipLaunchKernelGGL(k_unpack_shards<bf16s>, dim3(g), dim3(256), 0, st_, (const char *)stage,
+                         s0, rest, blk, P, chunk_bytes, (bf16s *)full);
     else
       hipLaunchKernelGGL(k_unpack_shards<double>, dim3(g), dim3(256), 0, st_, (const char *)stage,
                          s0, rest, blk, P, chunk_bytes, (double *)full);
@@ -614,6 +648,9 @@ class HipOps : public Ops {
       if (dt == F32)
         hipLaunchKernelGGL(k_transpose<float>, dim3((unsigned)nb, nby), dim3(256), 0, st_,
                            (const float *)s, rows, cols, (float *)d);
+      else if (dt == BF16)
+        hipLaunchKernelGGL(k_transpose<bf16s>, dim3((unsigned)nb, nby), dim3(256), 0, st_,
+                           (const bf16s *)s, rows, cols, (bf16s *)d);
       else
         hipLaunchKernelGGL(k_transpose<double>, dim3((unsigned)nb, nby), dim3(256), 0, st_,
                            (const double *)s, rows, cols, (double *)d);
@@ -1035,13 +1072,104 @@ class HipOps : public Ops {
   }
   int scan_tail_occ_[4] = {0, 0, 0, 0};
   bool scan_tail_on_ = true;  // PPALS_SCAN_TAIL=0: no tail mode (A/B)
+  // Scans of a bf16 tensor (kernels_bf16.hip.h): passes of up to 16 result columns; row-aligned suffix
+  // and batched forms on the bf16 matrix cores, every other shape on the per-row fp64 kernels.
+  void scan_bf16(const uint16_t *V, int64_t L, int64_t J, int64_t T, const FactorRef *f, int nf, int R,
+                 double *out, int64_t out_tstride, int64_t out_rstride, int out32, RowPad pad) {
+    int64_t Jk;
+    const KrpArgs a = krp_args(f, nf, &Jk);
+    if (Jk != J) throw std::runtime_error("ppals: scan factor extents do not match the tensor");
+    const bool aligned_base = (((uintptr_t)V) & 15) == 0;
+    const int64_t nblk64 = (J + BF16_KB - 1) / BF16_KB;
+    const int64_t n_mtiles64 = (L + 511) / 512;
+    const bool mfma_ok = L > 1 && aligned_base && L % 8 == 0 && nblk64 * BF16_MAX_NT * 3 * 1024 < 2000000000ll &&
+                         n_mtiles64 * T <= 0x7fffffff;
+    const bool big = (double)BF16_KB * L * 2.0 >= 2.0e9;  // a k-block past 32-bit buffer offsets
+    const double bytes_v = (double)L * J * T * 2.0;
+    for (int col0 = 0; col0 < R; col0 += 16 * BF16_MAX_NT) {
+      const int ncols = std::min(16 * BF16_MAX_NT, R - col0);
+      double *o = out32 ? (double *)((float *)out + (int64_t)col0 * out_rstride) : out + (int64_t)col0 * out_rstride;
+      prof_begin(0, bytes_v + (double)L * T * ncols * (out32 ? 4.0 : 8.0));
+      if (mfma_ok) {
+        const int NT = (ncols + 15) / 16;
+        const int nblk = (int)nblk64;
+        uint16_t *P = (uint16_t *)ensure(ws_pack_, ws_pack_sz_, (size_t)nblk * NT * 3 * 1024);
+        hipLaunchKernelGGL(k_krp_pack_bf16, dim3(grid_for((int64_t)nblk * NT * 512, 256)), dim3(256), 0, st_, P,
+                           nblk, NT, a, J, col0, ncols);
+        HIP_CHECK(hipGetLastError());
+        // K-split when the row tiles cannot fill the chip (a tree node of few rows and a long reduction:
+        // order 4 at s = 200 keeps 40000 rows = 79 tiles; order 3 keeps s rows = 1 tile): the fp32
+        // launcher's rule (scan_t), each split at least 16 k-blocks; partial sums through the slab
+        const int64_t M = L;
+        int nsplit = 1;
+        if (T == 1 && n_mtiles64 < (int64_t)ncu_ * 8)
+          nsplit = (int)std::min<int64_t>(((int64_t)ncu_ * 8 + n_mtiles64 - 1) / n_mtiles64,
+                                          std::max(1, nblk / 16));
+        else if (T > 1 && n_mtiles64 * T < ncu_ && (double)M * T * ncols * nblk / 4 * 8.0 < 64e6)
+          nsplit = (int)std::min<int64_t>(((int64_t)ncu_ * 2 + n_mtiles64 * T - 1) / (n_mtiles64 * T),
+                                          std::max(1, nblk / 4));
+        if (nsplit < 1) nsplit = 1;
+        const int per = (nblk + nsplit - 1) / nsplit;
+        nsplit = (nblk + per - 1) / per;
+        if (n_mtiles64 * nsplit * T > 0x7fffffff) throw std::runtime_error("ppals: scan grid too large");
+        double *dst = o;
+        int dst32 = out32;
+        int64_t dst_ns = out_rstride, dst_ss = 0, dst_bs = out_tstride, k_ld = pad.ld, k_valid = pad.valid;
+        if (nsplit > 1) {
+          dst32 = 0;
+          dst = (double *)ensure(ws_slab_, ws_slab_sz_, sizeof(double) * nsplit * ncols * M * T);
+          dst_ns = M;
+          dst_ss = (int64_t)ncols * M * T;
+          dst_bs = (int64_t)ncols * M;
+          k_ld = k_valid = 0;
+        }
+        const dim3 grid((unsigned)(n_mtiles64 * nsplit * T));
+        // non-temporal result stores: the fp32 kernels' rule (scan_t) — the engine's choice, else by size
+        const bool nts = nsplit == 1 && (scan_nt_mode_ < 0 ? (double)L * T * ncols * (out32 ? 4.0 : 8.0) >=
+                                                                 192.0 * 1048576.0
+                                                           : scan_nt_mode_ == 1);
+#define PPALS_BF16_SCAN(NTSv, BIGv)                                                                         \
+  hipLaunchKernelGGL((k_scan_suffix_bf16<BF16_MAX_NT, NTSv, BIGv>), grid, dim3(256), 0, st_, V, L, J, P,         \
+                     (int)n_mtiles64, nsplit, per, nblk, dst, dst_ns, dst_ss, dst_bs, ncols, dst32, k_ld, k_valid)
+        if (big) {
+          if (nts) PPALS_BF16_SCAN(true, true);
+          else PPALS_BF16_SCAN(false, true);
+        } else {
+          if (nts) PPALS_BF16_SCAN(true, false);
+          else PPALS_BF16_SCAN(false, false);
+        }
+#undef PPALS_BF16_SCAN
+        if (nsplit > 1) {
+          HIP_CHECK(hipGetLastError());
+          hipLaunchKernelGGL(k_slab_reduce, dim3(grid_for(M * ncols, 256), (unsigned)T), dim3(256), 0, st_, dst,
+                             nsplit, dst_ss, M, ncols, o, (int64_t)1, out_rstride, out32, pad.ld, pad.valid,
+                             dst_bs, out_tstride);
+        }
+      } else {
+        double *B = (double *)ensure(ws_krp_, ws_krp_sz_, sizeof(double) * (size_t)J * ncols);
+        krp(B, f, nf, col0, ncols);
+        if (L == 1)
+          hipLaunchKernelGGL(k_scan_bf16_prefix<16 * BF16_MAX_NT>, dim3((unsigned)std::min<int64_t>((T + 3) / 4, 65536)),
+                             dim3(256), 0,
+                             st_, V, J, T, B, ncols, o, out_tstride, out_rstride, out32);
+        else
+          hipLaunchKernelGGL(k_scan_bf16_rows<16 * BF16_MAX_NT>, dim3(grid_for(L * T, 256, 16384)), dim3(256), 0,
+                             st_, V, L, J, T, B, ncols, o, out_tstride, out_rstride, out32, pad.ld, pad.valid);
+      }
+      prof_end();
+      HIP_CHECK(hipGetLastError());
+    }
+  }
   using Ops::scan_contract;
   void scan_contract(const void *V, int dt, int64_t L, int64_t J, int64_t T, const FactorRef *f,
                      int nf, int R, void *out, int out_dt, int64_t out_tstride,
                      int64_t out_rstride, RowPad pad) override {
     RoctxRange roctx_("K1/K2/K8/K11 tensor scan");
     const int out32 = out_dt == F32 ? 1 : 0;
-    if (dt == F32)
+    if (dt == BF16)
+      scan_bf16((const uint16_t *)V, L, J, T, f, nf, R, (double *)out, out_tstride, out_rstride, out32,
+                pad);
+    else if (dt == F32)
       scan_t<float>((const float *)V, L, J, T, f, nf, R, (double *)out, out_tstride, out_rstride,
                     out32, pad);
     else
@@ -1116,6 +1244,9 @@ class HipOps : public Ops {
     if (dt == F32)
       hipLaunchKernelGGL(k_transpose_pad<float>, dim3((unsigned)nb), dim3(256), 0, st_,
                          (const float *)src, rows, cols, blk, ld, (float *)dst);
+    else if (dt == BF16)
+      hipLaunchKernelGGL(k_transpose_pad<bf16s>, dim3((unsigned)nb), dim3(256), 0, st_,
+                         (const bf16s *)src, rows, cols, blk, ld, (bf16s *)dst);
     else
       hipLaunchKernelGGL(k_transpose_pad<double>, dim3((unsigned)nb), dim3(256), 0, st_,
                          (const double *)src, rows, cols, blk, ld, (double *)dst);

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "bf16.h"
 #include "device_view.h"
 
 namespace ppals {
@@ -25,6 +26,18 @@ __device__ __forceinline__ float io_cvt<float, io_bf16>(io_bf16 x) {
 template <>
 __device__ __forceinline__ double io_cvt<double, io_bf16>(io_bf16 x) {
   return (double)__uint_as_float((uint32_t)x.u << 16);
+}
+
+// bf16 storage (PPALS_BF16): a bf16 view copies bit for bit, f16 goes through its exact fp32 value
+template <>
+__device__ __forceinline__ bf16s io_cvt<bf16s, io_bf16>(io_bf16 x) {
+  bf16s r;
+  r.u = x.u;
+  return r;
+}
+template <>
+__device__ __forceinline__ bf16s io_cvt<bf16s, _Float16>(_Float16 x) {
+  return bf16s((float)x);
 }
 
 template <typename T>

@@ -10,13 +10,19 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "bf16.h"
 #include "device_view.h"
 #include "preload_policy.h"
 
 namespace ppals {
 
-enum DType { F32 = 0, F64 = 1 };
-inline size_t dtype_size(int dt) { return dt == F32 ? 4 : 8; }
+// BF16 (= PPALS_BF16) is a storage type of the resident tensor only: everything computed from it
+// (tree nodes, the multi-sweep intermediate, PP operators, caches) is held in work_dt(BF16) = F32
+// or wider. F16 (= PPALS_F16) is never a storage type.
+enum DType { F32 = 0, F64 = 1, BF16 = 3 };
+inline size_t dtype_size(int dt) { return dt == F32 ? 4 : (dt == BF16 ? 2 : 8); }
+// the precision of an intermediate "in the tensor's own precision"
+inline int work_dt(int storage) { return storage == BF16 ? F32 : storage; }
 
 // row blocks of a padded layout: `ld` stored rows per block, the first `valid` of them real
 struct RowPad {
@@ -61,6 +67,8 @@ class Ops {
   virtual void sync() = 0;
   virtual void *stream() { return nullptr; }
   virtual void bind() {}  // make this Ops' device current on the calling thread
+  // whether the tensor kernels of this back end can hold a tensor stored as `dt`
+  virtual bool supports_storage(int dt) { return dt == F32 || dt == F64; }
 
   // ---- tensor generation / norms ----
   // V[e_local] = lo + (hi-lo)*u01(seed, global linear index); local shard = rows [row0,row0+l0)

@@ -165,7 +165,7 @@ int ppals_profile_reset(ppals_ctx *ctx) {
 int ppals_tensor_create(ppals_ctx *ctx, int order, const int64_t *global_lens, int dtype,
                         ppals_tensor **out) {
   if (!ctx || !global_lens || !out) return fail(PPALS_ERR_ARG, "NULL argument");
-  if (dtype != PPALS_F32 && dtype != PPALS_F64) return fail(PPALS_ERR_ARG, "bad dtype");
+  if (dtype != PPALS_F32 && dtype != PPALS_F64 && dtype != PPALS_BF16) return fail(PPALS_ERR_ARG, "bad dtype");
   API_BEGIN
   std::unique_ptr<ppals_tensor> t(new ppals_tensor);
   t->ctx = ctx;
@@ -517,6 +517,9 @@ int ppals_cpd_als_lr(ppals_cp *s, int optimizer, int update_rank, int randomsvd,
 // ------------------------------------------------------------------ Tucker
 int ppals_tucker_create(ppals_ctx *ctx, ppals_tensor *V, const int *ranks, ppals_tucker **out) {
   if (!ctx || !V || !ranks || !out) return fail(PPALS_ERR_ARG, "NULL argument");
+  if (V->d.dtype == PPALS_BF16)
+    return fail(PPALS_ERR_UNSUPPORTED,
+                "ppals_tucker_create: Tucker / HOSVD do not take a bf16 tensor (store it as F32 or F64)");
   API_BEGIN
   std::unique_ptr<ppals_tucker> s(new ppals_tucker);
   s->ctx = ctx;

@@ -17,7 +17,7 @@ import weakref
 import numpy as np
 
 F32, F64 = 0, 1
-F16, BF16 = 2, 3  # element types of a device view only (import source / export destination)
+F16, BF16 = 2, 3  # F16: a device view only; BF16: a view, or the tensor's storage (CP only)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIBPATH = os.environ.get("PPALS_LIB", os.path.join(os.path.dirname(_HERE), "lib", "libppals.so"))
 _lib = None
@@ -291,7 +291,9 @@ class Tensor:
     @classmethod
     def from_torch(cls, ctx, x, dtype=None):
         """a tensor with lens = x.shape (mode i = dim i) holding x: stored as F64 for a float64 x,
-        as F32 otherwise, unless dtype says. Under P > 1 ranks each rank copies its own rows of x."""
+        as F32 otherwise (a bfloat16 x too), unless dtype says (BF16: a bfloat16 x is copied bit for
+        bit, wider types are rounded as x.to(torch.bfloat16) rounds them). Under P > 1 ranks each
+        rank copies its own rows of x."""
         torch = _torch()
         if dtype is None:
             dtype = F64 if x.dtype == torch.float64 else F32
