@@ -19,9 +19,9 @@
 // the redundant fused update for small messages, reduce-scatter / row-block solve / all-gather
 // otherwise (mode_update).
 #include "engine.h"
+#include "run_report.h"
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -31,10 +31,6 @@
 #include <stdexcept>
 
 namespace ppals {
-
-static double now() {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 // ============================================================================ tensor helpers
 int tensor_create(Ops &ops, Comm &comm, int order, const int64_t *glens, int dtype,
@@ -1708,7 +1704,7 @@ int CpEngine::run_class(int kind, const CpOpts &o, double *sweeps_out, int *iter
     pcsv = &csv;
     if (!o.bench) csv << "[dim],[iter],[gradnorm],[tol],[pp_update],[diffV],[dtime]\n";
   }
-  st_time_ = now();
+  double st_time = now();
   int iters = 0, next_mode = 0;
   bool first_subtree = true;
   double sweeps = 0, projnorm = 0, diffV = 1000.;
@@ -1719,8 +1715,8 @@ int CpEngine::run_class(int kind, const CpOpts &o, double *sweeps_out, int *iter
       const double st_time1 = now();
       projnorm = gradnorm();
       diffV = residual();
-      st_time_ += now() - st_time1;
-      const double dtime = now() - st_time_;
+      st_time += now() - st_time1;
+      const double dtime = now() - st_time;
       if (rank_ == 0) {
         if (!o.bench) {
           if (o.verbose) {
@@ -1740,7 +1736,7 @@ int CpEngine::run_class(int kind, const CpOpts &o, double *sweeps_out, int *iter
           if (pcsv) (*pcsv) << "[DTtime]" << "," << dtime << "\n";
         }
       }
-      if (agree(projnorm < o.tol || now() - st_time_ > o.timelimit)) break;
+      if (agree(projnorm < o.tol || now() - st_time > o.timelimit)) break;
     }
     int count;
     double frac;
@@ -1771,7 +1767,7 @@ int CpEngine::run_class(int kind, const CpOpts &o, double *sweeps_out, int *iter
   ops_.sync();
   if (rank_ == 0 && o.verbose) {
     printf("\nIters = %d Final proj-grad norm %E \n", iters, projnorm);
-    printf("tf took %lf seconds\n", now() - st_time_);
+    printf("tf took %lf seconds\n", now() - st_time);
   }
   if (pcsv) csv.close();
   if (sweeps_out) *sweeps_out = sweeps;
@@ -2167,196 +2163,107 @@ void CpEngine::sweep_pp(double lambda, double ratio) {
 }
 
 // ---------------------------------------------------------------------------- drivers
-static void csv_row(std::ofstream *csv, int64_t dim, int iter, double gradnorm, double tol, int pp,
-                    double diffV, double dtime) {
-  if (!csv) return;
-  (*csv) << dim << "," << iter << "," << gradnorm << "," << tol << "," << pp << "," << diffV << ","
-         << dtime << "\n";
-  if (iter % 100 == 0 && iter != 0) (*csv) << std::endl;  // als_CP.cxx:199-201
-}
-
-// print block: als_CP.cxx:166-213 / :457-498 / :697-752. Its own duration is subtracted from the
-// elapsed time exactly as the reference does (st_time += ...).
-bool CpEngine::print_block(const CpOpts &o, int iter, int pp_flag, double &projnorm, double &diffV,
-                           std::ofstream *csv) {
+// print block: als_CP.cxx:166-213 / :457-498 / :697-752; bench: pp_bench's timings instead of the
+// row (als_CP.cxx:203-209 / :735-748)
+bool CpEngine::print_block(RunReport &rep, const CpOpts &o, int iter, int pp_flag, double &projnorm,
+                           bool bench) {
   ops_.sync();  // the sweeps enqueued so far belong to [dtime]
-  const double st_time1 = now();
-  projnorm = gradnorm();
-  diffV = residual();
-  st_time_ += now() - st_time1;
-  const double dtime = now() - st_time_;
-  if (rank_ == 0) {
-    if (o.verbose) {
-      std::cout.precision(13);
-      std::cout << "  [dim]=  " << V_.glens[0] << "  [iter]=  " << iter << "  [gradnorm]  "
-                << projnorm << "  [tol]  " << o.tol << "  [pp_update]  " << pp_flag
-                << "  [diffV]  " << diffV << "  [dtime]  " << dtime << "\n";
-    }
-    csv_row(csv, V_.glens[0], iter, projnorm, o.tol, pp_flag, diffV, dtime);
-  }
-  return agree((projnorm < o.tol) || (now() - st_time_ > o.timelimit));
+  double diffV = 0;
+  rep.off_clock([&] {
+    projnorm = gradnorm();
+    diffV = residual();
+  });
+  if (!bench)
+    rep.row(iter, projnorm, pp_flag, diffV);
+  else if (pp_flag)
+    rep.pp_bench_time(iter, o.maxiter);
+  else if (iter != 0)
+    rep.dt_bench_time();
+  return agree(projnorm < o.tol || rep.elapsed() > o.timelimit);
 }
 
 int CpEngine::run_dt(const CpOpts &o, int *iters) {
-  std::ofstream csv;
-  std::ofstream *pcsv = nullptr;
-  if (rank_ == 0 && !o.csv_path.empty()) {
-    csv.open(o.csv_path, o.csv_append ? std::ios::app : std::ios::out);
-    pcsv = &csv;
-    if (!o.bench) csv << "[dim],[iter],[gradnorm],[tol],[pp_update],[diffV],[dtime]\n";
-  }
-  st_time_ = now();
-  double projnorm = 0, diffV = 1000;
+  RunReport rep(o, rank_ == 0, V_.glens[0], "gradnorm");
+  double projnorm = 0;
   int iter;
   for (iter = 0; iter <= o.maxiter; iter++) {
     if (iter % o.resprint == 0 || iter == o.maxiter) {
-      if (!o.bench) {
-        if (print_block(o, iter, 0, projnorm, diffV, pcsv)) break;
-      } else {
-        // pp_bench mode (als_CP.cxx:203-209): only the elapsed time of the sweep is reported
-        ops_.sync();
-        const double st_time1 = now();
-        projnorm = gradnorm();
-        diffV = residual();
-        st_time_ += now() - st_time1;
-        const double dtime = now() - st_time_;
-        if (rank_ == 0 && iter != 0) {
-          if (o.verbose) std::cout << "  [dimension tree step time]  " << dtime << "\n";
-          if (pcsv) (*pcsv) << "[DTtime]" << "," << dtime << "\n";
-        }
-        if (agree(projnorm < o.tol || now() - st_time_ > o.timelimit)) break;
-      }
+      if (print_block(rep, o, iter, 0, projnorm, o.bench)) break;
     }
     sweep_dt(o.lambda);
-    if (iter % 10 == 0 && rank_ == 0 && o.verbose) printf(".");
+    rep.dot(iter);
   }
   ops_.sync();
-  if (rank_ == 0 && o.verbose) {
-    printf("\nIter = %d Final proj-grad norm %E \n", iter, projnorm);
-    printf("tf took %lf seconds\n", now() - st_time_);
-  }
-  if (pcsv) csv.close();
+  rep.finish(iter, "proj-grad", projnorm);
   if (iters) *iters = iter;
   return iter == o.maxiter + 1 ? 0 : 1;
 }
 
-// ||dW_i||^2 and ||W_i||^2 for all modes. dt_phase: dW = W - W_prev, W_prev = W (als_CP.cxx:594-
+// ||dW_i|| and ||W_i|| for all modes. dt_phase: dW = W - W_prev, W_prev = W (als_CP.cxx:594-
 // 603); otherwise dW as left by the PP updates (als_CP.cxx:659-663).
-void CpEngine::read_norms(bool dt_phase, std::vector<double> &nd, std::vector<double> &nw) {
+ModeNorms CpEngine::read_norms(bool dt_phase) {
   int64_t n[MAX_ORDER];
   for (int i = 0; i < N_; i++) n[i] = V_.glens[i] * R_;
-  if (dt_phase)
-    ops_.diff_norms(W_.data(), Wprev_.data(), n, N_, 1, dW_.data(), 1, scal_);
-  else
-    ops_.diff_norms(W_.data(), nullptr, n, N_, 0, dW_.data(), 0, scal_);
-  double h[2 * MAX_ORDER];
-  ops_.d2h(h, scal_, sizeof(double) * 2 * N_);
-  nd.resize(N_);
-  nw.resize(N_);
-  for (int i = 0; i < N_; i++) {
-    nd[i] = std::sqrt(h[2 * i]);
-    nw[i] = std::sqrt(h[2 * i + 1]);
-  }
+  ops_.diff_norms(W_.data(), dt_phase ? Wprev_.data() : nullptr, n, N_, dt_phase, dW_.data(),
+                  dt_phase, scal_);
+  return ModeNorms(ops_, scal_, N_);
 }
 
-double CpEngine::dt_sub(const CpOpts &o, double &projnorm, int &iter, std::ofstream *csv) {
-  double diffV = 1000;
+void CpEngine::dt_sub(RunReport &rep, const CpOpts &o, double &projnorm, int &iter) {
   for (int i = 0; i < N_; i++)  // W_prev starts at zero (als_CP.cxx:428-431)
     ops_.zero(Wprev_[i], sizeof(double) * V_.glens[i] * R_);
-  std::vector<double> nd, nw;
   for (; iter <= o.maxiter; iter++) {
     if (iter % o.resprint == 0 || iter == o.maxiter) {
-      if (print_block(o, iter, 0, projnorm, diffV, csv)) break;
+      if (print_block(rep, o, iter, 0, projnorm, false)) break;
     }
     sweep_dt(o.lambda);
-    read_norms(true, nd, nw);
-    int num_dw_break = 0;
-    for (int i = 0; i < N_; i++)
-      if (std::fabs(nd[i] / nw[i]) < o.tol_init) num_dw_break++;
-    if (num_dw_break == N_) return diffV;  // iter is NOT incremented (als_CP.cxx:604-605)
-    if (iter % 10 == 0 && rank_ == 0 && o.verbose) printf(".");
+    // iter is NOT incremented (als_CP.cxx:604-605)
+    if (read_norms(true).count(o.tol_init, false) == N_) return;
+    rep.dot(iter);
   }
-  return diffV;
 }
 
-double CpEngine::pp_sub(const CpOpts &o, double &projnorm, int &iter, std::ofstream *csv) {
+// the restart point of a PP phase (als_CP.cxx:672-694): W_init = W, dW = 0, fresh operators
+void CpEngine::pp_restart() {
+  for (int j = 0; j < N_; j++) {
+    size_t n = sizeof(double) * V_.glens[j] * R_;
+    ops_.d2d(Winit_[j], W_[j], n);
+    ops_.zero(dW_[j], n);
+  }
+  pp_build_all();
+}
+
+void CpEngine::pp_sub(RunReport &rep, const CpOpts &o, double &projnorm, int &iter) {
   const int init_iter = iter;
-  double diffV = 1000;
-  double dtime_first = 0;
-  std::vector<double> nd, nw;
+  rep.start_pp_phase();  // (bench: a phase restarted after 15 sweeps is called again)
   for (; iter <= o.maxiter; iter++) {
     int num_dw_break = 0;
     if (!o.bench) {
-      if (iter == init_iter || dist_ || !pp_norms_) {
-        read_norms(false, nd, nw);  // dW as the exact phase left it
-      } else {  // left behind by the launches of the previous approximate sweep
-        double h[2 * MAX_ORDER];
-        ops_.d2h(h, pp_norms_, sizeof(double) * 2 * N_);
-        nd.resize(N_);
-        nw.resize(N_);
-        for (int i = 0; i < N_; i++) {
-          nd[i] = std::sqrt(h[2 * i]);
-          nw[i] = std::sqrt(h[2 * i + 1]);
-        }
-      }
-      for (int i = 0; i < N_; i++)
-        if (std::fabs(nd[i] / nw[i]) > o.tol_init) num_dw_break++;
+      // dW as the exact phase left it, later as the launches of the previous approximate sweep did
+      const bool fused = iter != init_iter && !dist_ && pp_norms_;
+      const ModeNorms m = fused ? ModeNorms(ops_, pp_norms_, N_) : read_norms(false);
+      num_dw_break = m.count(o.tol_init, true);
     }
     if ((iter - init_iter) % 15 == 0 || num_dw_break > 0) {
-      if (num_dw_break > 0 || iter != init_iter) return diffV;
-      for (int j = 0; j < N_; j++) {  // W_init = W, dW = 0 (als_CP.cxx:672-675)
-        size_t n = sizeof(double) * V_.glens[j] * R_;
-        ops_.d2d(Winit_[j], W_[j], n);
-        ops_.zero(dW_[j], n);
-      }
-      pp_build_all();
+      if (num_dw_break > 0 || iter != init_iter) return;
+      pp_restart();
     }
     if (iter % o.resprint == 0 || iter == o.maxiter || iter == init_iter) {
-      if (!o.bench) {
-        if (print_block(o, iter, 1, projnorm, diffV, csv)) break;
-      } else {
-        // pp_bench mode (als_CP.cxx:735-748)
-        ops_.sync();
-        const double st_time1 = now();
-        projnorm = gradnorm();
-        diffV = residual();
-        st_time_ += now() - st_time1;
-        const double dtime = now() - st_time_;
-        if (iter != o.maxiter) {
-          dtime_first = dtime;
-          st_time_ = now();
-        } else {
-          dtime_first = dtime_first + dtime;
-          if (rank_ == 0) {
-            if (o.verbose) {
-              std::cout << "  [PP first time]  " << dtime_first << "\n";
-              std::cout << "  [PP second time]  " << dtime << "\n";
-            }
-            if (csv) {
-              (*csv) << "  [PPfirst]  " << "," << dtime_first << "\n";
-              (*csv) << "  [PPsecond]  " << "," << dtime << "\n";
-            }
-          }
-        }
-        if (agree(projnorm < o.tol || now() - st_time_ > o.timelimit)) break;
-      }
+      if (print_block(rep, o, iter, 1, projnorm, o.bench)) break;
     }
     sweep_pp(o.lambda, o.ratio_step);
-    if (iter % 10 == 0 && rank_ == 0 && o.verbose) printf(".");
+    rep.dot(iter);
   }
   if (o.bench) iter++;
-  return diffV;
 }
 
 // alsCP_PP_partupdate_sub (als_CP.cxx:852-1073): PP phase that updates only the modes with the
 // largest relative MTTKRP perturbation ||dM_i|| / ||M_i|| and propagates every update to the other
 // modes' dM through the cached pair operators. Sharded: dM_i (i != 0) is a partial sum, completed
 // on a copy for its norm; M_i is completed in place by its own mode update.
-double CpEngine::pp_partupdate_sub(const CpOpts &o, double &projnorm, int &iter,
-                                   std::ofstream *csv) {
+void CpEngine::pp_partupdate_sub(RunReport &rep, const CpOpts &o, double &projnorm, int &iter) {
   const int init_iter = iter;
-  double diffV = 1000;
-  std::vector<double> nd, nw, relpert(N_, 0.0);
+  std::vector<double> relpert(N_, 0.0);
   for (int i = 0; i < N_; i++) {
     size_t n = sizeof(double) * V_.glens[i] * R_;
     ops_.zero(dM_[i], n);
@@ -2364,21 +2271,14 @@ double CpEngine::pp_partupdate_sub(const CpOpts &o, double &projnorm, int &iter,
   }
   const int update_size = (int)(N_ * o.update_percentage);
   for (; iter <= o.maxiter; iter++) {
-    int num_dw_break = 0;
-    read_norms(false, nd, nw);
-    for (int i = 0; i < N_; i++)
-      if (std::fabs(nd[i] / nw[i]) > o.tol_init) num_dw_break++;
+    const int num_dw_break = read_norms(false).count(o.tol_init, true);
     if ((iter - init_iter) % 15 == 0 || num_dw_break > 0) {
-      if (num_dw_break > 0 || iter != init_iter) return diffV;
-      for (int j = 0; j < N_; j++) {
-        size_t n = sizeof(double) * V_.glens[j] * R_;
-        ops_.d2d(Winit_[j], W_[j], n);
-        ops_.zero(dW_[j], n);
-      }
-      pp_build_all();
+      if (num_dw_break > 0 || iter != init_iter) return;
+      pp_restart();
     }
     if (iter % o.resprint == 0 || iter == o.maxiter || iter == init_iter) {
-      if (print_block(o, iter, 1, projnorm, diffV, csv)) break;
+      // (rows under o.bench too: -pp 2 has no bench form)
+      if (print_block(rep, o, iter, 1, projnorm, false)) break;
     }
     // sort_indexes (als_CP.cxx:835-843): descending, ties keep index order
     std::vector<int> idx(N_);
@@ -2416,14 +2316,12 @@ double CpEngine::pp_partupdate_sub(const CpOpts &o, double &projnorm, int &iter,
     }
     // the sharded mode holds complete ROWS: its two sums of squares add up over the ranks
     if (dist_) comm_.allreduce_sum(scal_, 2);
-    double h[2 * MAX_ORDER];
-    ops_.d2h(h, scal_, sizeof(double) * 2 * N_);
-    for (int i = 0; i < N_; i++) relpert[i] = std::sqrt(h[2 * i]) / std::sqrt(h[2 * i + 1]);
+    const ModeNorms m(ops_, scal_, N_);  // ||dM_i||, ||M_i||
+    for (int i = 0; i < N_; i++) relpert[i] = m.d[i] / m.w[i];
     normalize();
     grad_from_sweep_ = true;
-    if (iter % 10 == 0 && rank_ == 0 && o.verbose) printf(".");
+    rep.dot(iter);
   }
-  return diffV;
 }
 
 int CpEngine::run_pp(const CpOpts &o, int *iters) { return run_pp_common(o, iters, false); }
@@ -2439,13 +2337,6 @@ int CpEngine::run_pp_partupdate(const CpOpts &o, int *iters) {
 }
 
 int CpEngine::run_pp_common(const CpOpts &o, int *iters, bool partupdate) {
-  std::ofstream csv;
-  std::ofstream *pcsv = nullptr;
-  if (rank_ == 0 && !o.csv_path.empty()) {
-    csv.open(o.csv_path, o.csv_append ? std::ios::app : std::ios::out);
-    pcsv = &csv;
-    if (!o.bench) csv << "[dim],[iter],[gradnorm],[tol],[pp_update],[diffV],[dtime]\n";
-  }
   if (partupdate && rank_ == 0 && o.verbose) std::cout << "alsCP_PP_partupdate starts. " << std::endl;
   for (int i = 0; i < N_; i++) {
     size_t n = sizeof(double) * V_.glens[i] * R_;
@@ -2456,30 +2347,26 @@ int CpEngine::run_pp_common(const CpOpts &o, int *iters, bool partupdate) {
     if (partupdate && !Mm_[i]) Mm_[i] = (double *)ops_.alloc(n);
     ops_.zero(dW_[i], n);
   }
-  st_time_ = now();
+  RunReport rep(o, rank_ == 0, V_.glens[0], "gradnorm");
   int iter = 0;
   double gradnorm_v = 10.;
   while (gradnorm_v > o.tol && iter <= o.maxiter) {
     if (!o.bench) {
-      if (rank_ == 0 && o.verbose) printf("DT starts from %d\n", iter);
-      dt_sub(o, gradnorm_v, iter, pcsv);
+      rep.starts("DT", iter);
+      dt_sub(rep, o, gradnorm_v, iter);
     }
-    if (rank_ == 0 && o.verbose) printf("pairwise perturbation starts from %d\n", iter);
+    rep.starts("pairwise perturbation", iter);
     if (partupdate)
-      pp_partupdate_sub(o, gradnorm_v, iter, pcsv);
+      pp_partupdate_sub(rep, o, gradnorm_v, iter);
     else
-      pp_sub(o, gradnorm_v, iter, pcsv);
+      pp_sub(rep, o, gradnorm_v, iter);
     // deviation from the reference: a timelimit hit terminates instead of looping forever
     // (als_CP.cxx:1105 with breaks at :496 and :750)
-    if (agree(now() - st_time_ > o.timelimit)) break;
+    if (agree(rep.elapsed() > o.timelimit)) break;
   }
   ops_.sync();
   pp_clear();
-  if (rank_ == 0 && o.verbose) {
-    printf("\nIter = %d Final grad norm %E \n", iter, gradnorm_v);
-    printf("tf took %lf seconds\n", now() - st_time_);
-  }
-  if (pcsv) csv.close();
+  rep.finish(iter, "grad", gradnorm_v);
   if (iters) *iters = iter;
   return iter == o.maxiter + 1 ? 0 : 1;
 }

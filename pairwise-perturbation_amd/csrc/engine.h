@@ -65,6 +65,9 @@ struct CpOpts {
   bool verbose = false;
 };
 
+class RunReport;
+struct ModeNorms;
+
 class CpEngine {
  public:
   CpEngine(Ops &ops, Comm &comm, const TensorDesc &V, int R);
@@ -279,12 +282,14 @@ class CpEngine {
   void sweep_pp(double lambda, double ratio);
   double allreduce_scalar(double x);
   bool agree(bool local);
-  void read_norms(bool dt_phase, std::vector<double> &nd, std::vector<double> &nw);
-  bool print_block(const CpOpts &o, int iter, int pp_flag, double &projnorm, double &diffV,
-                   std::ofstream *csv);
-  double dt_sub(const CpOpts &o, double &projnorm, int &iter, std::ofstream *csv);
-  double pp_sub(const CpOpts &o, double &projnorm, int &iter, std::ofstream *csv);
-  double pp_partupdate_sub(const CpOpts &o, double &projnorm, int &iter, std::ofstream *csv);
+  // the drivers (their console lines, CSV and clock: run_report.h)
+  ModeNorms read_norms(bool dt_phase);
+  bool print_block(RunReport &rep, const CpOpts &o, int iter, int pp_flag, double &projnorm,
+                   bool bench);
+  void dt_sub(RunReport &rep, const CpOpts &o, double &projnorm, int &iter);
+  void pp_restart();
+  void pp_sub(RunReport &rep, const CpOpts &o, double &projnorm, int &iter);
+  void pp_partupdate_sub(RunReport &rep, const CpOpts &o, double &projnorm, int &iter);
   int run_pp_common(const CpOpts &o, int *iters, bool partupdate);
 
   Ops &ops_;
@@ -340,7 +345,6 @@ class CpEngine {
   std::map<std::string, PPOp> pp_;
   bool grad_from_sweep_ = false;
   double init_gradnorm_ = 0;
-  double st_time_ = 0;
 };
 
 }  // namespace ppals

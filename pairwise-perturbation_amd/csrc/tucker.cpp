@@ -10,21 +10,14 @@
 // Order generalisation as for CP: a node is "first level" iff its parent is the root, which is
 // the reference's length test for N = 4,6,7,8 and defines N = 3 (BASELINE config 5).
 #include "tucker.h"
+#include "run_report.h"
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
-#include <fstream>
-#include <iostream>
 #include <stdexcept>
 
 namespace ppals {
-
-static double now() {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 TuckerEngine::TuckerEngine(Ops &ops, Comm &comm, const TensorDesc &V, const int *ranks)
     : ops_(ops), comm_(comm), V_(V), N_(V.order) {
@@ -816,58 +809,21 @@ double TuckerEngine::residual() {
 }
 
 int TuckerEngine::run_dt(const CpOpts &o, int *iters) {
-  std::ofstream csv;
-  std::ofstream *pcsv = nullptr;
-  if (rank_ == 0 && !o.csv_path.empty()) {
-    csv.open(o.csv_path, o.csv_append ? std::ios::app : std::ios::out);
-    pcsv = &csv;
-    if (!o.bench) csv << "[dim],[iter],[diffnorm],[tol],[pp_update],[diffV],[dtime]\n";
-  }
-  const bool talk = o.verbose && rank_ == 0;
-  double st_time = now();
+  RunReport rep(o, rank_ == 0, V_.glens[0], "diffnorm");
   ensure_core();
   ops_.d2d(core_prev_, core_, sizeof(double) * ncore_);  // Tensor<> core_prev(core)
-  double diffnorm = 1000, diffnorm_V = 1000;
+  double diffnorm = 1000;
   int iter;
   for (iter = 0; iter <= o.maxiter; iter++) {
     if ((iter % o.resprint == 0 && iter != 0) || iter == 1 || iter == o.maxiter) {
-      settle_all();
-      ops_.sync();
-      const double st_time1 = now();
-      compute_core_full();  // TTMc(core, V, W, -1)
-      diffnorm = core_norm();
-      diffnorm_V = residual();
-      st_time += now() - st_time1;
-      const double dtime = now() - st_time;
-      if (!o.bench) {
-        if (talk) {
-          std::cout.precision(13);
-          std::cout << "  [dim]=  " << V_.glens[0] << "  [iter]=  " << iter << "  [diffnorm]  "
-                    << diffnorm << "  [tol]  " << o.tol << "  [pp_update]  " << 0 << "  [diffV]  "
-                    << diffnorm_V << "  [dtime]  " << dtime << "\n";
-        }
-        if (pcsv) {
-          (*pcsv) << V_.glens[0] << "," << iter << "," << diffnorm << "," << o.tol << "," << 0
-                  << "," << diffnorm_V << "," << dtime << "\n";
-          if (iter % 100 == 0 && iter != 0) (*pcsv) << std::endl;
-        }
-      } else {
-        if (talk) std::cout << "  [dimension tree step time]  " << dtime << "\n";
-        if (pcsv) (*pcsv) << "[DTtime]" << "," << dtime << "\n";
-      }
-      if (agree(diffnorm < o.tol || now() - st_time > o.timelimit)) break;
-      ops_.d2d(core_prev_, core_, sizeof(double) * ncore_);
+      if (print_block(rep, o, iter, 0, diffnorm, false)) break;
     }
     sweep_dt();
-    if (iter % 10 == 0 && talk) printf(".");
+    rep.dot(iter);
   }
   settle_all();
   ops_.sync();
-  if (talk) {
-    printf("\nIter = %d Final Diff norm %E \n", iter, diffnorm);
-    printf("tf took %lf seconds\n", now() - st_time);
-  }
-  if (pcsv) csv.close();
+  rep.finish(iter, "Diff", diffnorm);
   if (iters) *iters = iter;
   return iter == o.maxiter + 1 ? 0 : 1;
 }
@@ -981,88 +937,61 @@ void TuckerEngine::sweep_pp() {
                 core_);
 }
 
-bool TuckerEngine::print_block(const CpOpts &o, int iter, int pp_flag, double &diffnorm,
-                               double &diffV, std::ofstream *csv, double &st_time,
-                               bool stop_at_maxiter) {
+// print block (als_Tucker.cxx:288-338 / :521-564 / :764-822); bench: pp_bench's timings instead of
+// the row. (pp_bench's PP phase has no deferred eigen-step to settle: run_pp settled them all.)
+bool TuckerEngine::print_block(RunReport &rep, const CpOpts &o, int iter, int pp_flag,
+                               double &diffnorm, bool stop_at_maxiter) {
   settle_all();
   ops_.sync();
-  const double st_time1 = now();
-  compute_core_full();
-  diffnorm = core_norm();
-  diffV = residual();
-  st_time += now() - st_time1;
-  const double dtime = now() - st_time;
-  if (rank_ == 0) {
-    if (o.verbose) {
-      std::cout.precision(13);
-      std::cout << "  [dim]=  " << V_.glens[0] << "  [iter]=  " << iter << "  [diffnorm]  "
-                << diffnorm << "  [tol]  " << o.tol << "  [pp_update]  " << pp_flag
-                << "  [diffV]  " << diffV << "  [dtime]  " << dtime << "\n";
-    }
-    if (csv) {
-      (*csv) << V_.glens[0] << "," << iter << "," << diffnorm << "," << o.tol << "," << pp_flag
-             << "," << diffV << "," << dtime << "\n";
-      if (iter % 100 == 0 && iter != 0) (*csv) << std::endl;
-    }
-  }
-  if (agree(diffnorm < o.tol || now() - st_time > o.timelimit ||
+  double diffV = 0;
+  rep.off_clock([&] {
+    compute_core_full();  // TTMc(core, V, W, -1)
+    diffnorm = core_norm();
+    diffV = residual();
+  });
+  if (!o.bench)
+    rep.row(iter, diffnorm, pp_flag, diffV);
+  else if (pp_flag)
+    rep.pp_bench_time(iter, o.maxiter);
+  else
+    rep.dt_bench_time();
+  if (agree(diffnorm < o.tol || rep.elapsed() > o.timelimit ||
             (stop_at_maxiter && iter == o.maxiter)))
     return true;
   ops_.d2d(core_prev_, core_, sizeof(double) * ncore_);
   return false;
 }
 
-void TuckerEngine::read_norms(bool dt_phase, std::vector<double> &nd, std::vector<double> &nw) {
+ModeNorms TuckerEngine::read_norms(bool dt_phase) {
   int64_t n[MAX_ORDER];
   for (int i = 0; i < N_; i++) n[i] = V_.glens[i] * r_[i];
-  if (dt_phase)
-    ops_.diff_norms(W_.data(), Wprev_.data(), n, N_, 1, dW_.data(), 1, scal_ + 8);
-  else
-    ops_.diff_norms(W_.data(), nullptr, n, N_, 0, dW_.data(), 0, scal_ + 8);
-  double h[2 * MAX_ORDER];
-  ops_.d2h(h, scal_ + 8, sizeof(double) * 2 * N_);
-  nd.resize(N_);
-  nw.resize(N_);
-  for (int i = 0; i < N_; i++) {
-    nd[i] = std::sqrt(h[2 * i]);
-    nw[i] = std::sqrt(h[2 * i + 1]);
-  }
+  ops_.diff_norms(W_.data(), dt_phase ? Wprev_.data() : nullptr, n, N_, dt_phase, dW_.data(),
+                  dt_phase, scal_ + 8);
+  return ModeNorms(ops_, scal_ + 8, N_);
 }
 
 // alsTucker_DT_sub (als_Tucker.cxx:476-669)
-void TuckerEngine::dt_sub(const CpOpts &o, double tol_init, double &diffnorm, int &iter,
-                          std::ofstream *csv, double &st_time) {
-  double diffV = 1000;
+void TuckerEngine::dt_sub(RunReport &rep, const CpOpts &o, double tol_init, double &diffnorm,
+                          int &iter) {
   for (int i = 0; i < N_; i++) ops_.zero(Wprev_[i], sizeof(double) * V_.glens[i] * r_[i]);
-  std::vector<double> nd, nw;
   for (; iter <= o.maxiter; iter++) {
     if ((iter % o.resprint == 0 && iter != 0) || iter == 1 || iter == o.maxiter) {
-      if (print_block(o, iter, 0, diffnorm, diffV, csv, st_time, false)) break;
+      if (print_block(rep, o, iter, 0, diffnorm, false)) break;
     }
     sweep_body(&Wprev_);
-    read_norms(true, nd, nw);
-    int num_dw_break = 0;
-    for (int i = 0; i < N_; i++)
-      if (std::fabs(nd[i] / nw[i]) < tol_init) num_dw_break++;
-    if (num_dw_break == N_) return;
-    if (iter % 10 == 0 && rank_ == 0 && o.verbose) printf(".");
+    if (read_norms(true).count(tol_init, false) == N_) return;
+    rep.dot(iter);
   }
 }
 
 // alsTucker_PP_sub (als_Tucker.cxx:679-896); o.bench: pp_bench's form (:722-730 no restart test,
 // :799-814 [PPfirst]/[PPsecond], :892-893 iter++ on exit)
-void TuckerEngine::pp_sub(const CpOpts &o, double tol_init, double &diffnorm, int &iter,
-                          std::ofstream *csv, double &st_time) {
+void TuckerEngine::pp_sub(RunReport &rep, const CpOpts &o, double tol_init, double &diffnorm,
+                          int &iter) {
   const int init_iter = iter;
-  double diffV = 1000, dtime_first = 0;
-  std::vector<double> nd, nw;
+  rep.start_pp_phase();
   for (; iter <= o.maxiter; iter++) {
-    int num_dw_break = 0;
-    if (!o.bench) {
-      read_norms(false, nd, nw);
-      for (int i = 0; i < N_; i++)
-        if (std::fabs(nd[i] / nw[i]) > tol_init) num_dw_break++;
-    }
+    const int num_dw_break = o.bench ? 0 : read_norms(false).count(tol_init, true);
     if (iter == init_iter || num_dw_break > 0) {
       if (num_dw_break > 0) return;
       for (int j = 0; j < N_; j++) {
@@ -1077,35 +1006,7 @@ void TuckerEngine::pp_sub(const CpOpts &o, double tol_init, double &diffnorm, in
     }
     if ((iter % o.resprint == 0 && iter != 0) || iter == 1 || iter == o.maxiter ||
         iter == init_iter) {
-      if (!o.bench) {
-        if (print_block(o, iter, 1, diffnorm, diffV, csv, st_time, true)) break;
-      } else {
-        ops_.sync();
-        const double st_time1 = now();
-        compute_core_full();
-        diffnorm = core_norm();
-        diffV = residual();
-        st_time += now() - st_time1;
-        const double dtime = now() - st_time;
-        if (iter != o.maxiter) {
-          dtime_first = dtime;
-          st_time = now();
-        } else {
-          dtime_first = dtime_first + dtime;
-          if (rank_ == 0) {
-            if (o.verbose) {
-              std::cout << "  [PP first time]  " << dtime_first << "\n";
-              std::cout << "  [PP second time]  " << dtime << "\n";
-            }
-            if (csv) {
-              (*csv) << "  [PPfirst]  " << "," << dtime_first << "\n";
-              (*csv) << "  [PPsecond]  " << "," << dtime << "\n";
-            }
-          }
-        }
-        if (agree(diffnorm < o.tol || now() - st_time > o.timelimit || iter == o.maxiter)) break;
-        ops_.d2d(core_prev_, core_, sizeof(double) * ncore_);
-      }
+      if (print_block(rep, o, iter, 1, diffnorm, true)) break;
     }
     sweep_pp();
   }
@@ -1115,13 +1016,6 @@ void TuckerEngine::pp_sub(const CpOpts &o, double tol_init, double &diffnorm, in
 int TuckerEngine::run_pp(const CpOpts &o, int *iters) {
   finalize_rotations();  // the PP phases difference the eigenvectors themselves
   for (int i = 0; i < N_; i++) ops_.eig_lazy(eig_base_ + i, false);
-  std::ofstream csv;
-  std::ofstream *pcsv = nullptr;
-  if (rank_ == 0 && !o.csv_path.empty()) {
-    csv.open(o.csv_path, o.csv_append ? std::ios::app : std::ios::out);
-    pcsv = &csv;
-    if (!o.bench) csv << "[dim],[iter],[diffnorm],[tol],[pp_update],[diffV],[dtime]\n";
-  }
   if (Wprev_.empty()) {
     for (int i = 0; i < N_; i++) {
       size_t n = sizeof(double) * V_.glens[i] * r_[i];
@@ -1131,28 +1025,24 @@ int TuckerEngine::run_pp(const CpOpts &o, int *iters) {
     }
   }
   for (int i = 0; i < N_; i++) ops_.zero(dW_[i], sizeof(double) * V_.glens[i] * r_[i]);
-  double st_time = now();
+  RunReport rep(o, rank_ == 0, V_.glens[0], "diffnorm");
   int iter = 0;
   ops_.d2d(core_prev_, core_, sizeof(double) * ncore_);  // Tensor<> core_prev(core)
   double diffnorm = 10.;
   double tol_init = o.tol_init;
   while (diffnorm > o.tol && iter <= o.maxiter) {
     if (!o.bench) {
-      if (rank_ == 0 && o.verbose) printf("DT starts from %d\n", iter);
-      dt_sub(o, tol_init, diffnorm, iter, pcsv, st_time);
+      rep.starts("DT", iter);
+      dt_sub(rep, o, tol_init, diffnorm, iter);
     }
-    if (rank_ == 0 && o.verbose) printf("pairwise perturbation starts from %d\n", iter);
-    pp_sub(o, tol_init, diffnorm, iter, pcsv, st_time);
+    rep.starts("pairwise perturbation", iter);
+    pp_sub(rep, o, tol_init, diffnorm, iter);
     if (tol_init > 5e-3) tol_init *= 0.9;  // als_Tucker.cxx:947-948
-    if (agree(now() - st_time > o.timelimit)) break;
+    if (agree(rep.elapsed() > o.timelimit)) break;
   }
   ops_.sync();
   pp_clear();
-  if (rank_ == 0 && o.verbose) {
-    printf("\nIter = %d Final Diff norm %E \n", iter, diffnorm);
-    printf("tf took %lf seconds\n", now() - st_time);
-  }
-  if (pcsv) csv.close();
+  rep.finish(iter, "Diff", diffnorm);
   if (iters) *iters = iter;
   return iter == o.maxiter + 1 ? 0 : 1;
 }

@@ -1,6 +1,5 @@
 // tucker.h — HOOI sweep engine for Tucker decomposition (als_Tucker.cxx) over abstract ops.
 #pragma once
-#include <fstream>
 #include <map>
 #include <string>
 #include <vector>
@@ -129,13 +128,11 @@ class TuckerEngine {
   void settle_all();        // before anything derived from the factors is read
   void rollback_and_redo();
   void sweep_pp();
-  bool print_block(const CpOpts &o, int iter, int pp_flag, double &diffnorm, double &diffV,
-                   std::ofstream *csv, double &st_time, bool stop_at_maxiter);
-  void read_norms(bool dt_phase, std::vector<double> &nd, std::vector<double> &nw);
-  void dt_sub(const CpOpts &o, double tol_init, double &diffnorm, int &iter, std::ofstream *csv,
-              double &st_time);
-  void pp_sub(const CpOpts &o, double tol_init, double &diffnorm, int &iter, std::ofstream *csv,
-              double &st_time);
+  bool print_block(RunReport &rep, const CpOpts &o, int iter, int pp_flag, double &diffnorm,
+                   bool stop_at_maxiter);
+  ModeNorms read_norms(bool dt_phase);
+  void dt_sub(RunReport &rep, const CpOpts &o, double tol_init, double &diffnorm, int &iter);
+  void pp_sub(RunReport &rep, const CpOpts &o, double tol_init, double &diffnorm, int &iter);
   double *Yfull_ = nullptr, *gather_ = nullptr;
   int64_t yfull_cap_ = 0, gather_cap_ = 0;
 };

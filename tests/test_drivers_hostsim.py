@@ -1,6 +1,7 @@
 """CPU runs of the DRIVER tests (tests/test_gpu_driver.py): the product's bin/test_ALS, bin/pp_bench
 and bin/run sources linked against the host stand-in (tests/hostsim) — flag parsing, echo block,
-CSV, the V/W file exchange and the `-tensor o*` path, pp_bench's line format, against the oracle.
+CSV, the V/W file exchange and the `-tensor o*` path, pp_bench's line format, against the oracle;
+the console transcripts line by line.
 They say nothing about the HIP kernels; `-m gpu` runs the same tests on the real binaries."""
 import os
 import subprocess
@@ -33,6 +34,8 @@ test_cfg1_cli_matches_oracle = D.test_cfg1_cli_matches_oracle
 test_file_exchange_and_o_path = D.test_file_exchange_and_o_path
 test_o_path_rejects_short_file = D.test_o_path_rejects_short_file
 test_pp_bench_tucker_lines = D.test_pp_bench_tucker_lines
+test_test_ALS_console_transcript = D.test_test_ALS_console_transcript
+test_pp_bench_console_transcript = D.test_pp_bench_console_transcript
 
 # the plug-in point for reference-made fixtures (tests/test_ctf_fixtures.py), on the host stand-in
 import test_ctf_fixtures as CF  # noqa: E402

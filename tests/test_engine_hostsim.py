@@ -57,6 +57,7 @@ test_class_api_low_rank_optimizers = G.test_class_api_low_rank_optimizers
 test_class_api_low_rank_optimizers_randomsvd = G.test_class_api_low_rank_optimizers_randomsvd
 test_tensor_refill_while_session_alive = G.test_tensor_refill_while_session_alive
 test_bench_mode_matches_oracle = G.test_bench_mode_matches_oracle
+test_bench_mode_ppfirst_starts_at_zero_in_every_pp_phase = G.test_bench_mode_ppfirst_starts_at_zero_in_every_pp_phase
 test_long_run_factor_parity = G.test_long_run_factor_parity
 test_rank_stream_on_matrix_cores = G.test_rank_stream_on_matrix_cores
 

@@ -934,6 +934,29 @@ def test_bench_mode_matches_oracle(pp, ctx, lens, R, maxiter, resprint, tmp_path
     t.close()
 
 
+def test_bench_mode_ppfirst_starts_at_zero_in_every_pp_phase(pp, ctx, tmp_path):
+    """bench-mode PP restarts after 15 sweeps (als_CP.cxx:667-697) without iter++, so alsCP_PP calls
+    the PP phase again from iter 15. Its [PPfirst] bookkeeping (dtime_first, als_CP.cxx:627) starts
+    at 0 in that phase too: with maxiter 15 the second phase reports at once, and [PPfirst] equals
+    [PPsecond] bit for bit."""
+    lens, R = [10, 10, 10, 10], 3
+    V, W = problem(lens, R, 6, "r")
+    G = O.init_factors(lens, R, 96)
+    t = pp.Tensor(ctx, lens, 1).upload(V)
+    s = pp.CP(ctx, t, R)
+    s.set_factors(W, G)
+    c_got, c_ref = str(tmp_path / "got.csv"), str(tmp_path / "ref.csv")
+    kw = dict(tol=0.0, maxiter=15, resprint=1)
+    rc, it = s.run_pp(tol_init=0.05, csv=c_got, csv_append=1, bench=1, **kw)
+    rc_ref, it_ref, _, _ = O.als_cp_pp(V, W, G, tol_init=0.05, csv=c_ref, bench=1, **kw)
+    assert (rc, it) == (rc_ref, it_ref)
+    assert _bench_lines(c_got) == _bench_lines(c_ref) == ["  [PPfirst]  ", "  [PPsecond]  "]
+    first, second = (ln.split(",")[1] for ln in open(c_got).read().splitlines() if ln.strip())
+    assert first == second, (first, second)
+    s.close()
+    t.close()
+
+
 @pytest.mark.parametrize("lens,R", [([20, 20, 20, 20], 5), ([24, 18, 16], 4)])
 @pytest.mark.parametrize("dtype", [0, 1])
 def test_long_run_factor_parity(pp, ctx, lens, R, dtype):

@@ -2,6 +2,7 @@
 (test_ALS.cxx:64-217), CSV format, and numeric agreement of the whole run with the oracle driven
 from the same counter-based initialisation."""
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -380,3 +381,135 @@ def test_pp_bench_tucker_lines(BIN, tmp_path):
     assert sum(ln.startswith("  [PPsecond]  ,") for ln in text) == 3
     assert out.count("pairwise perturbation starts from 0") == 3
     assert out.count("Iter = 2 Final Diff norm") == 6   # DT: loop end at maxiter+1; PP: iter++ on exit
+
+
+# ---------------------------------------------------------------------------- console transcript
+# The drivers' console output pinned line by line (als_CP.cxx / als_Tucker.cxx cout/printf). Every
+# line after the echo block must have one of the shapes below exactly; each is reduced to a token
+# ("3/1": the row of iteration 3 in a PP phase, leading "." the progress dots printed before it,
+# "_" an empty line) and the token sequence is compared with the expected one. Only the timing
+# numbers are free. A row carries its metric, tol and diffV at cout precision 13 and has a CSV twin
+# at the default precision 6; the closing line repeats the last row's metric in %E.
+_ROW = re.compile(r"  \[dim\]=  (\d+)  \[iter\]=  (\d+)  \[(gradnorm|diffnorm)\]  (\S+)  \[tol\]  (\S+)"
+                  r"  \[pp_update\]  ([01])  \[diffV\]  (\S+)  \[dtime\]  (\S+)")
+_LINES = [(re.compile(r), tok) for r, tok in [
+    (r"DT starts from (\d+)", "DT@{}"),
+    (r"pairwise perturbation starts from (\d+)", "PP@{}"),
+    (r"alsCP_PP_partupdate starts. ", "partupdate"),
+    (r"new round", "round"),
+    (r"(\d+)", "m{}"),
+    (r"tf took \d+\.\d{6} seconds", "tf"),
+    (r"experiment took \d+\.\d{6} seconds", "exp"),
+]]
+_END = re.compile(r"Iter = (\d+) Final (proj-grad|grad|Diff) norm (-?\d\.\d{6}E[+-]\d\d+) ")
+_BENCH = re.compile(r"  \[(dimension tree step|PP first|PP second) time\]  (\S+)")
+
+
+def _sig_digits(t):
+    return len(re.sub(r"e.*|[^0-9]", "", t).lstrip("0"))
+
+
+def _transcript(lines, csv_path=None, metric=None):
+    """tokens of the console lines; checks every row's metric label (gradnorm / diffnorm), its CSV
+    twin (csv_path) and the closing line's norm against the last row"""
+    toks, rows, ends = [], [], []
+    for ln in lines:
+        body = ln.lstrip(".")
+        dots = "." * (len(ln) - len(body))
+        m = _ROW.fullmatch(body)
+        if m:
+            dim, it, label, g, tol, pp, dv, dt = m.groups()
+            assert label == metric, ln
+            for t in (g, tol, dv):
+                assert t == format(float(t), ".13g"), ln
+            assert max(_sig_digits(g), _sig_digits(dv)) >= 10, ln              # precision 13
+            assert _sig_digits(dt) <= 13 and float(dt) >= 0, ln
+            rows.append((dim, int(it), g, tol, pp, dv))
+            toks.append(f"{dots}{it}/{pp}")
+            continue
+        m = _END.fullmatch(body)
+        if m:
+            ends.append((m.group(2), m.group(3)))
+            toks.append(f"{dots}end@{m.group(1)}:{m.group(2)}")
+            continue
+        m = _BENCH.fullmatch(body)
+        if m:
+            assert _sig_digits(m.group(2)) <= 6 and float(m.group(2)) > 0, ln   # cout precision 6
+            toks.append(dots + {"dimension tree step": "dt", "PP first": "first",
+                                "PP second": "second"}[m.group(1)])
+            continue
+        for rx, tok in _LINES:
+            m = rx.fullmatch(body)
+            if m:
+                toks.append(dots + tok.format(*m.groups()))
+                break
+        else:
+            assert body == "", f"unexpected console line {ln!r}"
+            toks.append(dots or "_")
+    if csv_path is not None:
+        text = open(csv_path).read().splitlines()
+        want = [f"[dim],[iter],[{metric}],[tol],[pp_update],[diffV],[dtime]"]
+        for dim, it, g, tol, pp, dv in rows:
+            want.append(",".join([dim, str(it)] + [format(float(v), ".6g") for v in (g, tol)] +
+                                 [pp, format(float(dv), ".6g")]))
+            if it % 100 == 0 and it != 0:
+                want.append("")
+        assert [ln.rsplit(",", 1)[0] if ln and i else ln for i, ln in enumerate(text)] == want
+    if rows:
+        assert ends[-1][1] == "%E" % float(rows[-1][2])
+    return " ".join(toks)
+
+
+_CP = ["-model", "CP", "-tensor", "r", "-dim", "4", "-size", "10", "-rank", "3"]
+_TK = ["-model", "Tucker", "-tensor", "r2", "-dim", "3", "-size", "12", "-rank", "3"]
+
+
+@pytest.mark.parametrize("args,want", [
+    (_CP + ["-pp", "0", "-maxiter", "12", "-resprint", "1"],
+     "0/0 .1/0 2/0 3/0 4/0 5/0 6/0 7/0 8/0 9/0 10/0 .11/0 12/0 _ end@13:proj-grad tf exp"),
+    (_CP + ["-pp", "0", "-maxiter", "100", "-resprint", "25"],
+     "0/0 ...25/0 ..50/0 ...75/0 ..100/0 . end@101:proj-grad tf exp"),
+    (_CP + ["-pp", "1", "-maxiter", "20", "-resprint", "1", "-pp_res_tol", "0.1"],
+     "DT@0 0/0 .1/0 2/0 3/0 PP@3 3/1 4/1 DT@5 5/0 6/0 PP@6 6/1 7/1 8/1 9/1 10/1 .11/1 "
+     "DT@12 12/0 13/0 PP@13 13/1 14/1 15/1 16/1 17/1 18/1 19/1 20/1 . end@21:grad tf exp"),
+    (_CP + ["-pp", "1", "-maxiter", "30", "-resprint", "4", "-pp_res_tol", "0.1"],
+     "DT@0 0/0 .PP@3 3/1 4/1 DT@5 PP@6 6/1 8/1 .DT@12 12/0 PP@13 13/1 16/1 20/1 .24/1 "
+     "DT@26 PP@27 27/1 28/1 30/1 . end@31:grad tf exp"),
+    (_CP + ["-pp", "2", "-update_percentage_pp", "0.5", "-maxiter", "14", "-resprint", "1",
+            "-pp_res_tol", "0.1"],
+     "partupdate DT@0 0/0 .1/0 2/0 3/0 PP@3 3/1 round m0 m1 4/1 round m2 m3 5/1 round m0 "
+     "m1 6/1 round m0 m3 DT@7 7/0 8/0 PP@8 8/1 round m0 m1 9/1 round m2 m3 10/1 round m0 "
+     "m1 .11/1 round m2 m0 12/1 round m3 m2 DT@13 13/0 14/0 PP@14 14/1 round m0 m1 _ "
+     "end@15:grad tf exp"),
+    (_TK + ["-pp", "0", "-maxiter", "12", "-resprint", "1"],
+     ".1/0 2/0 3/0 4/0 5/0 6/0 7/0 8/0 9/0 10/0 .11/0 12/0 _ end@13:Diff tf exp"),
+    (_TK + ["-pp", "1", "-maxiter", "14", "-resprint", "4", "-pp_res_tol", "0.1"],
+     "DT@0 .1/0 PP@3 3/1 4/1 DT@7 8/0 PP@8 8/1 DT@12 12/0 PP@13 13/1 14/1 DT@14 14/0 PP@15 "
+     "_ end@15:Diff tf exp"),
+], ids=["cp_dt", "cp_dt_resprint25", "cp_pp", "cp_pp_resprint4", "cp_partupdate", "tucker_dt",
+        "tucker_pp_resprint4"])
+def test_test_ALS_console_transcript(BIN, tmp_path, args, want):
+    csv = str(tmp_path / "o.csv")
+    lines = run([os.path.join(BIN, "test_ALS")] + args + ["-filename", csv]).splitlines()
+    assert lines[7].startswith("Vnorm= ")
+    metric = "gradnorm" if args[1] == "CP" else "diffnorm"
+    assert _transcript(lines[8:], csv, metric) == want
+
+
+@pytest.mark.parametrize("args,want", [
+    (_CP + ["-maxiter", "2"],
+     ".dt _ end@2:proj-grad tf .dt _ end@2:proj-grad tf PP@0 .first second _ end@3:grad tf "
+     "PP@0 .first second _ end@3:grad tf exp"),
+    (_TK + ["-maxiter", "2"],
+     ".dt _ end@2:Diff tf .dt _ end@2:Diff tf PP@0 first second _ end@2:Diff tf PP@0 first "
+     "second _ end@2:Diff tf exp"),
+], ids=["cp", "tucker"])
+def test_pp_bench_console_transcript(BIN, tmp_path, args, want):
+    csv = str(tmp_path / "b.csv")
+    lines = run([os.path.join(BIN, "pp_bench")] + args + ["-filename", csv]).splitlines()
+    assert lines[5].startswith("  timelimit=  ")
+    assert _transcript(lines[6:]) == want
+    text = open(csv).read().splitlines()
+    masked = [ln.split(",")[0] + ",t" if "," in ln and i else ln for i, ln in enumerate(text)]
+    assert masked == (["[timetype],[dtime]"] + ["[DTtime],t"] * 2 + [""] +
+                      ["  [PPfirst]  ,t", "  [PPsecond]  ,t"] * 2 + [""])
