@@ -1390,22 +1390,23 @@ class HipOps : public Ops {
                            S, Sinv, work, status);
       HIP_CHECK(hipGetLastError());
       // a non-positive pivot (S not positive definite: a rank above a mode extent, collinear
-      // columns) leaves NaNs in Sinv: take the reference's route instead, the untruncated inverse
-      // through a full eigen-decomposition.
+      // columns, a negative lambda) leaves NaNs in Sinv: take the reference's route instead, the
+      // untruncated inverse through a full eigen- or singular value decomposition.
       // Up to 128 columns that route is two CONDITIONAL launches on the stream — the one-workgroup
-      // one-sided Jacobi of S and Z diag(1/w) Z^T, both returning at once unless the elimination set
-      // its status word — so a mode update above 64 columns holds no host synchronisation any more
-      // (round 6: four read-backs per sweep were 40 us of idle stream each, and milliseconds each
-      // whenever the host's cores were busy). PPALS_FORCE_EIGINV=2 runs the two launches ungated (tests).
+      // one-sided Jacobi of S (S V = W = U Sigma) and V Sigma^-2 W^T, both returning at once unless
+      // the elimination set its status word — so a mode update above 64 columns holds no host
+      // synchronisation any more (round 6: four read-backs per sweep were 40 us of idle stream each,
+      // and milliseconds each whenever the host's cores were busy). PPALS_FORCE_EIGINV=2 runs the two
+      // launches ungated (tests).
       if (R <= kJacobiBigMax && force_eiginv_ != 1) {
-        double *fb = (double *)ensure(ws_gsfb_, ws_gsfb_sz_, sizeof(double) * (2 * (size_t)R * R + R));
-        double *Vt = fb, *Yz = Vt + (size_t)R * R, *wv = Yz + (size_t)R * R;
+        double *fb = (double *)ensure(ws_gsfb_, ws_gsfb_sz_, sizeof(double) * (3 * (size_t)R * R + R));
+        double *Vt = fb, *Yz = Vt + (size_t)R * R, *Wc = Yz + (size_t)R * R, *wv = Wc + (size_t)R * R;
         const int *gate = force_eiginv_ == 2 ? nullptr : status;
         const size_t lds_j = sizeof(double) * ((size_t)R * (R + 1) + 256) + sizeof(int) * 256;
         hipLaunchKernelGGL(k_jacobi_onesided, dim3(1), dim3(1024), lds_j, st_, (const double *)S, R, Vt, Yz, wv,
-                           (double *)nullptr, gate);
-        hipLaunchKernelGGL(k_eig_inverse, dim3(grid_for((int64_t)R * R, 256)), dim3(256), 0, st_,
-                           (const double *)Yz, (const double *)wv, R, Sinv, gate);
+                           (double *)nullptr, gate, Wc);
+        hipLaunchKernelGGL(k_svd_inverse, dim3(grid_for((int64_t)R * R, 256)), dim3(256), 0, st_,
+                           (const double *)Vt, (const double *)Wc, R, Sinv, gate);
         HIP_CHECK(hipGetLastError());
         return;
       }

@@ -1777,24 +1777,31 @@ __global__ __launch_bounds__(1024) void k_rr_small(const double *__restrict__ H,
   }
 }
 
-// Eigen-decomposition of a symmetric positive semi-definite H of 64 < n <= kJacobiBigMax rows (the
-// Rayleigh-Ritz matrix of a Tucker mode whose core rank exceeds 64: the reference's own data sets
-// run ranks 70 and 100, test_ALS.cxx:366-379) by ONE workgroup: one-sided (Hestenes) Jacobi. The
+// Eigen-decomposition of a symmetric H of 64 < n <= kJacobiBigMax rows (the Rayleigh-Ritz matrix
+// of a Tucker mode whose core rank exceeds 64: the reference's own data sets run ranks 70 and 100,
+// test_ALS.cxx:366-379; the R x R normal equations above 64 columns when S is not positive
+// definite) by ONE workgroup: one-sided (Hestenes) Jacobi. The
 // two-sided block Jacobi of the small modes keeps A and Q twice in LDS (4 n^2 doubles: 64 rows at
 // most); here only W = H V lives in LDS (n (n + 1) doubles, 129 KB at n = 128) and V — the product
 // of the rotations, L2-resident — in global memory: a round rotates n / 2 disjoint column pairs of
-// W (and V) so that the columns of W become orthogonal; at convergence W = V Lambda: the columns
-// of V are the eigenvectors, the column norms of W the eigenvalues. Sixteen threads per pair (their
+// W (and V) so that the columns of W become orthogonal; at convergence W = H V = U Sigma, the SVD
+// H = U Sigma V^T. For a positive semi-definite H (the Tucker callers) U = V: the columns of V are the
+// eigenvectors, the column norms of W the eigenvalues. For an indefinite H the column norms are
+// |eigenvalues| (their signs are lost) and, where two eigenvalues share a magnitude, V need not hold
+// eigenvectors at all: such a caller takes the converged W (Wout) and forms what it needs from the
+// SVD instead (k_svd_inverse). Sixteen threads per pair (their
 // three inner products meet by lane shuffles inside the 16-lane group), one barrier per round,
 // round-robin pairing (circle method), <= 40 sweeps; a sweep without a rotation ends it.
-//   Y (n x n) = eigenvectors, column k for the k-th largest eigenvalue; ev / ev_host: eigenvalues.
+//   Y (n x n) = eigenvectors, column k for the k-th largest eigenvalue; ev / ev_host: eigenvalues;
+//   V (n x n) the rotations and Wout (n x n, optional) the converged W, both in the unranked order.
 // dynamic LDS: n (n + 1) doubles + 256 doubles + 256 ints.
 constexpr int kJacobiBigMax = 128;
 __global__ __launch_bounds__(1024) void k_jacobi_onesided(const double *__restrict__ H, int n,
                                                           double *__restrict__ V, double *__restrict__ Y,
                                                           double *__restrict__ ev,
                                                           double *__restrict__ ev_host,
-                                                          const int *__restrict__ gate = nullptr) {
+                                                          const int *__restrict__ gate = nullptr,
+                                                          double *__restrict__ Wout = nullptr) {
   // (gate: the launch is a conditional one — it does nothing unless *gate is set; the R x R normal
   // equations' eigen-route, wanted only when the elimination met a non-positive pivot)
   if (gate && *gate == 0) return;
@@ -1871,7 +1878,8 @@ __global__ __launch_bounds__(1024) void k_jacobi_onesided(const double *__restri
     __syncthreads();
     if (!rotated) break;
   }
-  // eigenvalues = column norms of W (H is positive semi-definite), ranked descending
+  // singular values = column norms of W (the eigenvalues when H is positive semi-definite), ranked
+  // descending
   for (int k = tid >> 4; k < n; k += nthr >> 4) {
     double a = 0;
     for (int i = gl; i < n; i += 16) a += W[k * ld + i] * W[k * ld + i];
@@ -1896,6 +1904,36 @@ __global__ __launch_bounds__(1024) void k_jacobi_onesided(const double *__restri
   for (int e = tid; e < n * n; e += nthr) {
     const int i = e % n, k = e / n;
     Y[i + n * k] = V[i + n * ord[k]];
+    if (Wout) Wout[i + n * k] = W[k * ld + i];
+  }
+}
+
+// Sinv = V diag(1 / sigma_k^2) W^T from the converged one-sided Jacobi of a symmetric S
+// (k_jacobi_onesided: W = S V with orthogonal columns, sigma_k = ||W[:, k]||, V and W in the same
+// column order). S = W V^T = U Sigma V^T with U = W Sigma^-1, so this IS the reference's untruncated
+// V diag(1/sigma) U^T (common.cxx:717-722) — for an indefinite S too, where the column norms alone
+// lose the eigenvalues' signs. Both triangles are formed from the same products and averaged, so
+// the result is symmetric bit for bit (as the elimination routes' is). R <= kJacobiBigMax.
+__global__ __launch_bounds__(256) void k_svd_inverse(const double *__restrict__ V,
+                                                     const double *__restrict__ W, int R,
+                                                     double *__restrict__ Sinv,
+                                                     const int *__restrict__ gate = nullptr) {
+  if (gate && *gate == 0) return;  // (conditional launch: see k_jacobi_onesided)
+  __shared__ double rs[kJacobiBigMax];  // 1 / sigma_k^2
+  for (int k = threadIdx.x; k < R; k += blockDim.x) {
+    double a = 0;
+    for (int i = 0; i < R; i++) a += W[i + (int64_t)R * k] * W[i + (int64_t)R * k];
+    rs[k] = 1.0 / a;
+  }
+  __syncthreads();
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < R * R; e += gridDim.x * blockDim.x) {
+    const int i = e % R, j = e / R;
+    double x = 0, y = 0;
+    for (int k = 0; k < R; k++) {
+      x += V[i + (int64_t)R * k] * rs[k] * W[j + (int64_t)R * k];
+      y += V[j + (int64_t)R * k] * rs[k] * W[i + (int64_t)R * k];
+    }
+    Sinv[e] = 0.5 * (x + y);
   }
 }
 

@@ -1364,8 +1364,9 @@ __global__ __launch_bounds__(1024) void k_gram_system_mfma(const double *__restr
   }
 }
 // Sinv = Z diag(1/w) Z^T from the eigen-decomposition S = Z diag(w) Z^T (Z column-major, w any
-// order): for symmetric S this IS the reference's untruncated V diag(1/sigma) U^T
-// (common.cxx:717-722) — the defined answer when S is not positive definite
+// order, with their signs: dsyevd's eigenvalues, not the column norms of a one-sided Jacobi): for
+// symmetric S this IS the reference's untruncated V diag(1/sigma) U^T (common.cxx:717-722) — the
+// defined answer when S is not positive definite
 __global__ void k_eig_inverse(const double *__restrict__ Z, const double *__restrict__ w, int R,
                               double *__restrict__ Sinv, const int *__restrict__ gate = nullptr) {
   if (gate && *gate == 0) return;  // (conditional launch: see k_jacobi_onesided)

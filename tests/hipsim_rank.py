@@ -12,7 +12,7 @@ tests/rank_structured.py at BASELINE's full size).
                  allows 6 processes on its card; world 8 needs this):
                                   python hipsim_rank.py <case> --threads P
 
-cases: cp_mid, cp_plans, tucker_mid, cfg4 (BASELINE configs[3] at full size, P = 8: 8 x (12.8 GB
+cases: cp_mid, cp_plans, cp_lam, cp_lam_neg (lambda > 0, lambda < 0 at R = 80), tucker_mid, cfg4 (BASELINE configs[3] at full size, P = 8: 8 x (12.8 GB
 shard + its second layout) on one MI355X), cfg5 (configs[4], Tucker s = 400), tiny (the hostsim
 cases of tests/hostsim_rank.py over the HIP kernels; process mode only)."""
 import argparse
@@ -90,11 +90,12 @@ def nonempty(lens, P):
 
 
 # ------------------------------------------------------------------------------------------------
-def cp_cases(pp, ctx, w, rank, shapes, pp_driver=True):
+def cp_cases(pp, ctx, w, rank, shapes, pp_driver=True, lam=None, K=3):
     """CP on mid-size shapes (the real scan kernels: persistent one-tile, two n-tiles, fp64, the
     second resident layout, padded layouts where the strides ask for them): MTTKRP of every mode,
     residual, exact sweeps under both schedules with factors AND gradients, the PP driver, `-pp 2`
-    — on both collective plans — against the unsharded oracle."""
+    — on both collective plans — against the unsharded oracle. lam(V, W, G) -> (lambda, kappa):
+    the regularisation of every run and the condition of its systems (fp64 bars grow with it)."""
     P = w.size
     for case_no, (lens, R, dtype) in enumerate(shapes):
         lens = nonempty(lens, P)
@@ -104,18 +105,18 @@ def cp_cases(pp, ctx, w, rank, shapes, pp_driver=True):
             V = O.build_V(O.init_factors(lens, R, 1234))
             W = O.init_factors(lens, R, 4321)
             G = O.init_factors(lens, R, 99)
-            K = 3
-            _, _, W_ref, G_ref = O.als_cp_dt(V, W, G, tol=0.0, maxiter=K - 1, resprint=1000)
+            lm, kappa = lam(V, W, G) if lam else (0.0, 1.0)
+            _, _, W_ref, G_ref = O.als_cp_dt(V, W, G, tol=0.0, maxiter=K - 1, lam=lm, resprint=1000)
             M_ref = [O.mttkrp(V, W, m, 0) for m in range(N)]
             Vn = np.linalg.norm(V)
-            kw = dict(tol=1e-6 * Vn, tol_init=0.1, maxiter=24, resprint=1000)
+            kw = dict(tol=1e-6 * Vn, tol_init=0.1, maxiter=24, resprint=1000, lam=lm)
             pp_ref = O.als_cp_pp(V, W, G, **kw)[1:3] if pp_driver else None
-            kw2 = dict(tol=1e-6 * Vn, tol_init=0.1, maxiter=16, resprint=1000)
+            kw2 = dict(tol=1e-6 * Vn, tol_init=0.1, maxiter=16, resprint=1000, lam=lm)
             pu_ref = (O.als_cp_pp_partupdate(V, W, G, update_percentage=0.5, **kw2)[1:3]
                       if pp_driver and dtype == 1 else None)
             return dict(V=V, W=W, G=G, K=K, W_ref=W_ref, G_ref=G_ref, M_ref=M_ref, Vn=Vn, kw=kw,
                         kw2=kw2, pp_ref=pp_ref, pu_ref=pu_ref, res0=O.residual(V, W),
-                        res_ref=O.residual(V, W_ref))
+                        res_ref=O.residual(V, W_ref), lam=lm, kappa=kappa)
 
         pr = w.once(rank, ("cp", case_no), problem)
         V, W, G, K = pr["V"], pr["W"], pr["G"], pr["K"]
@@ -125,7 +126,7 @@ def cp_cases(pp, ctx, w, rank, shapes, pp_driver=True):
         assert lo == rank * blk and n == min(blk, lens[0] - lo), (lo, n, blk)
         assert abs(t.norm() - pr["Vn"]) < 1e-6 * pr["Vn"]
         ktol = 1e-10 if dtype == 1 else 2e-6
-        ftol = 1e-8 if dtype == 1 else 1e-5
+        ftol = max(1e-8, 1e-11 * pr["kappa"]) if dtype == 1 else 1e-5
         for plan in ("0", str(1 << 20)):   # reduce-scatter + all-gather / one all-reduce
             w.setenv(rank, "PPALS_COMM_SMALL_BYTES", plan)
             for schedule in ("msdt", "dt"):
@@ -138,7 +139,7 @@ def cp_cases(pp, ctx, w, rank, shapes, pp_driver=True):
                         assert e < ktol, (lens, plan, m, e)
                     assert abs(s.residual() - pr["res0"]) < 1e-5 * pr["res0"]
                 before = dict(w.calls_of(rank))
-                s.sweeps_dt(K)
+                s.sweeps_dt(K, pr["lam"])
                 after = w.calls_of(rank)
                 if plan == "0":   # every mode: reduce-scatter (not the partitioned one) + all-gather
                     assert after["rs"] - before["rs"] == K * (N - 1), (before, after)
@@ -323,6 +324,8 @@ def cfg5_full(pp, ctx, w, rank, s=400, r=20):
 CP_MID = [([96, 64, 48, 40], 10, 0), ([100, 56, 48, 36], 8, 1), ([160, 120, 96], 16, 1),
           ([80, 64, 48, 40], 20, 0), ([18, 12, 10, 8, 8, 6], 4, 1)]
 CP_PLANS = [([64, 64, 64, 64], 10, 0), ([48, 40, 36, 50], 6, 1)]
+CP_LAM = [([100, 56, 48, 36], 8, 1)]                               # lambda > 0
+CP_LAM_NEG = [([90, 85, 82], 80, 1)]   # lambda < 0 above 64 columns: the fallback on every shard
 CP_SMALL = [([12, 8, 6, 5], 3, 1), ([10, 9, 7], 4, 0)]            # CPU rehearsal of the script
 TUCKER_SMALL = [([10, 9, 8], [3, 2, 3], 1)]
 TUCKER_MID = [([96, 80, 72], [8, 6, 7], 1), ([72, 48, 40, 36], [4, 3, 4, 3], 0),
@@ -336,6 +339,11 @@ def run_case(case, pp, ctx, w, rank):
         cp_cases(pp, ctx, w, rank, CP_PLANS, pp_driver=False)
     elif case == "tucker_mid":
         tucker_cases(pp, ctx, w, rank, TUCKER_MID)
+    elif case == "cp_lam":
+        cp_cases(pp, ctx, w, rank, CP_LAM, lam=lambda V, W, G: (
+            0.05 * np.trace(O.gram_hadamard(W, 0)) / W[0].shape[1], 1.0))
+    elif case == "cp_lam_neg":
+        cp_cases(pp, ctx, w, rank, CP_LAM_NEG, pp_driver=False, lam=negative_lambda, K=1)
     elif case == "cp_small":
         cp_cases(pp, ctx, w, rank, CP_SMALL)
     elif case == "tucker_small":
@@ -357,6 +365,18 @@ def run_case(case, pp, ctx, w, rank):
         hostsim_rank.rs_unequal_cases(pp, ctx, rank, w.size, w.calls_of(rank), hostsim_rank.relerr)
     else:
         raise SystemExit(f"unknown case {case}")
+
+
+def negative_lambda(V, W, G):
+    """a lambda < 0 that leaves mode 0's S indefinite and every S of one sweep non-singular, and
+    the condition of those systems (tests/test_gpu_normal_equations.py)"""
+    import test_gpu_normal_equations as GN
+    lm = GN.negative_lambda(V, W)
+    ev = [np.linalg.eigvalsh(S) for S in GN.replay_systems(V, W, lm)]
+    assert np.min(ev[0]) < 0 < np.max(ev[0]), ev[0]
+    ratio = min(np.min(np.abs(x)) / np.max(np.abs(x)) for x in ev)
+    assert ratio >= 1e-6, ratio
+    return lm, 1.0 / ratio
 
 
 def one_rank(case, pp, w, rank):

@@ -74,6 +74,13 @@ test_tall_unfolding_thin_route_matches_oracle = GT.test_tall_unfolding_thin_rout
 test_tall_unfolding_rank_deficient_falls_back = GT.test_tall_unfolding_rank_deficient_falls_back
 test_chain_order_of_the_first_level_products = GT.test_chain_order_of_the_first_level_products
 
+import test_gpu_normal_equations as GN  # noqa: E402
+
+test_gram_system_lambda_and_indefinite = GN.test_gram_system_lambda_and_indefinite
+test_sweeps_with_lambda = GN.test_sweeps_with_lambda
+test_drivers_with_lambda = GN.test_drivers_with_lambda
+test_class_api_with_lambda = GN.test_class_api_with_lambda
+
 
 def test_context_destroyed_before_its_children(pp):
     """a garbage-collected binding (or an exception on the way out) may destroy the context while

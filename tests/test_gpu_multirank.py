@@ -103,6 +103,18 @@ def test_cp_dt_pp_sharded_processes(world):
     run_processes("cp_mid", world)
 
 
+def test_cp_lambda_sharded_processes():
+    """lambda > 0 through the sharded sweeps, the PP driver and `-pp 2` (the blocked update over the
+    gathered row blocks), P = 2"""
+    run_processes("cp_lam", 2)
+
+
+def test_cp_negative_lambda_above_64_sharded_processes():
+    """lambda < 0 at R = 80, P = 2: S indefinite, the conditional non-positive-pivot fallback on
+    every shard"""
+    run_processes("cp_lam_neg", 2)
+
+
 @pytest.mark.parametrize("world", [2, 4])
 def test_tucker_sharded_processes(world):
     """Tucker HOSVD + alsTucker_DT + TTMc + alsTucker_PP with modes above 64 rows"""

@@ -94,6 +94,32 @@ def test_gram_solve_normalize():
                        rtol=1e-12)
 
 
+@pytest.mark.parametrize("R", [1, 3, 64, 65, 127, 140])
+@pytest.mark.parametrize("kind", ["one_negative", "pm_pairs", "half_negative"])
+def test_svd_solve_inverts_indefinite_systems(R, kind):
+    """O.svd_solve(I, S) is S^-1 for a symmetric indefinite S too — ± pairs of equal magnitude
+    included, where S's singular vectors are not its eigenvectors. The GPU solver tests
+    (tests/test_gpu_normal_equations.py) take it as their reference."""
+    rng = np.random.default_rng(R)
+    Q, _ = np.linalg.qr(rng.standard_normal((R, R)))
+    if kind == "one_negative":
+        w = np.concatenate([[-1.0], np.linspace(1.0, 8.0, R - 1)])
+    elif kind == "pm_pairs":
+        m = np.linspace(0.3, 0.9, R // 2)
+        w = np.concatenate([m, -m, [0.5] * (R % 2)])
+    else:
+        w = np.linspace(1.0, 1e3, R) * np.where(np.arange(R) % 2, -1.0, 1.0)
+    S = (Q * w) @ Q.T
+    S = 0.5 * (S + S.T)
+    assert np.sum(np.linalg.eigvalsh(S) < 0) == np.sum(w < 0)
+    want = np.linalg.inv(S)
+    cond = np.linalg.cond(S)
+    assert np.linalg.norm(O.svd_solve(np.eye(R), S) - want) < 1e-12 * cond * np.linalg.norm(want)
+    M = rng.standard_normal((7, R))
+    X = O.svd_solve(M, S)
+    assert np.linalg.norm(X @ S - M) < 1e-12 * cond * np.linalg.norm(M)
+
+
 def test_svd():
     A = O.fill_uniform(12 * 5, 11, lo=-1, hi=1).reshape((12, 5), order="F")
     U, s, Vm = O.svd(A)

@@ -15,11 +15,27 @@ def _problem(lens, R, seed):
 
 @pytest.mark.parametrize("lens,R", [([8, 7, 6, 5], 3), ([9, 8, 7], 2), ([5, 4, 4, 3, 4], 2)])
 def test_dt_driver(lens, R, tmp_path):
+    _dt_driver(lens, R, 0.0, tmp_path)
+
+
+@pytest.mark.parametrize("lam", [0.3])
+@pytest.mark.parametrize("lens,R", [([8, 7, 6, 5], 3), ([9, 8, 7], 2), ([5, 4, 4, 3, 4], 2)])
+def test_dt_driver_with_lambda(lens, R, lam, tmp_path):
+    """the regularised normal equations S + lam I (als_CP.cxx:288-292): the GPU
+    tests with lam != 0 (tests/test_gpu_normal_equations.py) take the oracle as their reference"""
+    _dt_driver(lens, R, lam, tmp_path)
+    V, W, G = _problem(lens, R, 1)
+    W_0 = O.als_cp_dt(V, W, G, tol=0.0, maxiter=3, resprint=1000)[2]
+    W_l = O.als_cp_dt(V, W, G, tol=0.0, maxiter=3, lam=lam, resprint=1000)[2]
+    assert max(np.linalg.norm(a - b) / np.linalg.norm(b) for a, b in zip(W_l, W_0)) > 1e-4
+
+
+def _dt_driver(lens, R, lam, tmp_path):
     V, W, G = _problem(lens, R, 1)
     csv = str(tmp_path / "dt.csv")
-    _, it_o, W_o, G_o = O.als_cp_dt(V, W, G, tol=1e-9 * np.linalg.norm(V), maxiter=25, csv=csv,
-                                    resprint=5)
-    it_n, W_n, G_n, rows_n = NR.als_cp_dt(V, W, G, 1e-9 * np.linalg.norm(V), 25, resprint=5)
+    _, it_o, W_o, G_o = O.als_cp_dt(V, W, G, tol=1e-9 * np.linalg.norm(V), maxiter=25, lam=lam,
+                                    csv=csv, resprint=5)
+    it_n, W_n, G_n, rows_n = NR.als_cp_dt(V, W, G, 1e-9 * np.linalg.norm(V), 25, lam=lam, resprint=5)
     _, rows_o = O.read_csv(csv)
     assert it_o == it_n
     assert [(int(r[1]), int(r[4])) for r in rows_o] == [(r[0], r[1]) for r in rows_n]
