@@ -44,6 +44,32 @@ static inline int grid_for(int64_t n, int block, int cap = 4096) {
   return (int)g;
 }
 
+// A reduction over n units (k-blocks, columns) in the `want` splits a launcher asks for (at least 1):
+// per = units per split, at least min_per and rounded up to a multiple of align; nsplit = the splits
+// that leaves non-empty.
+struct KSplit {
+  int nsplit;
+  int64_t per;
+};
+static inline KSplit k_split(int64_t n, int64_t want, int64_t min_per = 1, int64_t align = 1) {
+  want = std::max<int64_t>(want, 1);
+  int64_t per = std::max((n + want - 1) / want, min_per);
+  per = (per + align - 1) / align * align;
+  return {(int)((n + per - 1) / per), per};
+}
+
+// Compile-time dispatch of a launch: f(std::integral_constant) for the first of Vs equal to v, or for
+// the last of Vs when none is. Instantiates f for exactly the listed values.
+template <auto V, auto... Vs, typename T, typename F>
+static inline void dispatch(T v, F &&f) {
+  if constexpr (sizeof...(Vs) == 0)
+    f(std::integral_constant<decltype(V), V>());
+  else if (v == V)
+    f(std::integral_constant<decltype(V), V>());
+  else
+    dispatch<Vs...>(v, f);
+}
+
 // The vendor eigensolver libraries, process-wide. See hip_preload_eigensolver (hip_ops.h).
 struct EigLibs {
   void *blas = nullptr, *solver = nullptr;
@@ -272,10 +298,9 @@ class HipOps : public Ops {
     // enough workgroups to fill the chip several times, chunks of >= 8 column blocks
     // (workgroups per CU x 4 .. 128 instead of 16: 1.60-1.73 ms for the whole [diffV] call at cfg2,
     // 1.61 at 16 — tools/k10_probe.py, profiles/r03z_k10_geometry.txt: the geometry is not the lever)
-    int nchunk = (int)std::min<int64_t>(nkb, std::max<int64_t>(1, ((int64_t)ncu_ * 16 + n_mtiles - 1) / n_mtiles));
-    int per = (nkb + nchunk - 1) / nchunk;
-    per = std::max(per, std::min(nkb, 8));
-    nchunk = (nkb + per - 1) / per;
+    const KSplit ks = k_split(nkb, std::min<int64_t>(nkb, ((int64_t)ncu_ * 16 + n_mtiles - 1) / n_mtiles),
+                              std::min(nkb, 8));
+    const int nchunk = ks.nsplit, per = (int)ks.per;
     if (n_mtiles > 0x7fffffff || nchunk > 65535) return false;
     // residual: a remainder of 1 or 2 ranks goes to the vector pipe instead of a padded matrix-core
     // step (kernels_scan.hip.h, REM), its P columns in LDS — if a chunk's share of them fits
@@ -300,16 +325,14 @@ class HipOps : public Ops {
     bool done = false;
     if constexpr (MODE == 1) {
       if (rem) {
-#define PPALS_RANK_REM(MRB, RM)                                                                        \
-  hipLaunchKernelGGL((k_rank_mfma<TV, 1, MRB, RM>), grid, dim3(256), lds_rem, st_, (TV *)V, M, K, Q, Ppk, R, \
-                     RB, per, nkb, part, P)
-        if (RB <= 2) {
-          if (rem == 1) PPALS_RANK_REM(2, 1);
-          else PPALS_RANK_REM(2, 2);
-        } else {
-          PPALS_RANK_REM(4, 1);
-        }
-#undef PPALS_RANK_REM
+        auto launch_rem = [&](auto mrb, auto rm) {
+          hipLaunchKernelGGL((k_rank_mfma<TV, 1, mrb, rm>), grid, dim3(256), lds_rem, st_, (TV *)V, M, K, Q, Ppk,
+                             R, RB, per, nkb, part, P);
+        };
+        if (RB <= 2)
+          dispatch<1, 2>(rem, [&](auto rm) { launch_rem(std::integral_constant<int, 2>(), rm); });
+        else
+          launch_rem(std::integral_constant<int, 4>(), std::integral_constant<int, 1>());
         done = true;
       }
     }
@@ -347,10 +370,9 @@ class HipOps : public Ops {
     hipLaunchKernelGGL(k_rank_pack, dim3(grid_for((int64_t)nkb * RB * 64, 256)), dim3(256), 0, st_, P,
                        K, R, RB, nkb, Ppk);
     const int64_t n_mtiles = (M + 16 * VEC - 1) / (16 * VEC);
-    int nchunk = (int)std::min<int64_t>(nkb, std::max<int64_t>(1, ((int64_t)ncu_ * 8 + n_mtiles - 1) / n_mtiles));
-    int per = (nkb + nchunk - 1) / nchunk;
-    per = std::max(per, std::min(nkb, 8));
-    nchunk = (nkb + per - 1) / per;
+    const KSplit ks = k_split(nkb, std::min<int64_t>(nkb, ((int64_t)ncu_ * 8 + n_mtiles - 1) / n_mtiles),
+                              std::min(nkb, 8));
+    const int nchunk = ks.nsplit, per = (int)ks.per;
     if (n_mtiles > 0x7fffffff || nchunk > 65535) return false;
     dim3 grid((unsigned)n_mtiles, (unsigned)nchunk);
     const int64_t npart = (int64_t)n_mtiles * nchunk;
@@ -730,13 +752,14 @@ class HipOps : public Ops {
         const int64_t M = J, K = T;
         const bool al = aligned_base && (M % VEC == 0);
         const int64_t ncolgrp = (K + 63) / 64;
-        int nsplit = 1;
+        int want = 1;
         const int target = ncu_ * 4;
-        if (ncolgrp < target) nsplit = (int)std::min<int64_t>((target + ncolgrp - 1) / ncolgrp,
-                                                              std::max(1, nblk / 64));
-        if (nsplit < 1) nsplit = 1;
-        const int per = (nblk + nsplit - 1) / nsplit;
-        nsplit = (nblk + per - 1) / per;
+        if (ncolgrp < target) want = (int)std::min<int64_t>((target + ncolgrp - 1) / ncolgrp,
+                                                            std::max(1, nblk / 64));
+        const KSplit ks = k_split(nblk, want);
+        const int nsplit = ks.nsplit, per = (int)ks.per;
+        // (the slab of a k-split prefix scan is [split][ncols][K], its rows contiguous, where the
+        // result's rows are out_tstride apart: not the suffix form of pass_dst)
         double *dst = o;
         int dst32 = out32;
         int64_t dst_ks = out_tstride, dst_ns = out_rstride, dst_ss = 0;
@@ -750,89 +773,43 @@ class HipOps : public Ops {
         dim3 grid((unsigned)ncolgrp, (unsigned)nsplit);
         dim3 grid_il((unsigned)((K + 15) / 16), (unsigned)nsplit);  // interleaved-waves variant
         prof_begin(0, bytes);
-#define LAUNCH_PREFIX(NTv, ALv)                                                               \
-  hipLaunchKernelGGL((k_scan_prefix<TV, NTv, ALv, 4>), grid, dim3(256), 0, st_, V, M, K, P, per, \
-                     nblk, dst, dst_ks, dst_ns, dst_ss, ncols, dst32)
-#define LAUNCH_PREFIX_FAST(NTv)                                                               \
-  hipLaunchKernelGGL((k_scan_prefix_fast<TV, NTv, 12>), grid_il, dim3(256), 0, st_, V, M, K, P, per, \
-                     nblk, dst, dst_ks, dst_ns, dst_ss, ncols, dst32)
-        if (al && M >= VEC) {
-          if (NT == 1) LAUNCH_PREFIX_FAST(1);
-          else if (NT == 2) LAUNCH_PREFIX_FAST(2);
-          else if (NT == 3) LAUNCH_PREFIX_FAST(3);
-          else LAUNCH_PREFIX_FAST(4);
-        } else if (al) {
-          if (NT == 1) LAUNCH_PREFIX(1, true);
-          else if (NT == 2) LAUNCH_PREFIX(2, true);
-          else if (NT == 3) LAUNCH_PREFIX(3, true);
-          else LAUNCH_PREFIX(4, true);
-        } else {
-          if (NT == 1) LAUNCH_PREFIX(1, false);
-          else if (NT == 2) LAUNCH_PREFIX(2, false);
-          else if (NT == 3) LAUNCH_PREFIX(3, false);
-          else LAUNCH_PREFIX(4, false);
-        }
-#undef LAUNCH_PREFIX
-#undef LAUNCH_PREFIX_FAST
+        dispatch<1, 2, 3, 4>(NT, [&](auto nt) {
+          if (al && M >= VEC)
+            hipLaunchKernelGGL((k_scan_prefix_fast<TV, nt, 12>), grid_il, dim3(256), 0, st_, V, M, K, P, per,
+                               nblk, dst, dst_ks, dst_ns, dst_ss, ncols, dst32);
+          else
+            dispatch<true, false>(al, [&](auto alv) {
+              hipLaunchKernelGGL((k_scan_prefix<TV, nt, alv, 4>), grid, dim3(256), 0, st_, V, M, K, P, per,
+                                 nblk, dst, dst_ks, dst_ns, dst_ss, ncols, dst32);
+            });
+        });
         prof_end();
         HIP_CHECK(hipGetLastError());
-        if (nsplit > 1) {
-          hipLaunchKernelGGL(k_slab_reduce, dim3(grid_for(K * ncols, 256)), dim3(256), 0, st_, dst,
-                             nsplit, dst_ss, K, ncols, o, out_tstride, out_rstride, out32,
-                             (int64_t)0, (int64_t)0);
-          HIP_CHECK(hipGetLastError());
-        }
+        slab_combine(nsplit, dst, dst_ss, K, ncols, o, out_tstride, out_rstride, out32);
       } else {
         // out[l + L*t + rs*n] = sum_j V[l + L*(j + J*t)] * B[j,n]   (M = L rows kept, K = J)
         const int64_t M = L, K = J;
         const bool al = aligned_base && (M % VEC == 0);
         const int64_t n_mtiles64 = (M + 64 * VEC - 1) / (64 * VEC);
         const int n_mtiles = (int)n_mtiles64;
-        int nsplit = 1;
+        int want = 1;
         const int target = ncu_ * 8;
         if (T == 1 && n_mtiles < target)
-          nsplit = (int)std::min<int64_t>((target + n_mtiles - 1) / n_mtiles,
-                                          std::max(1, nblk / 32));
+          want = (int)std::min<int64_t>((target + n_mtiles - 1) / n_mtiles,
+                                        std::max(1, nblk / 32));
         // a batched scan of a small tensor (the second-level mode products of a Tucker sweep:
         // 400 x 400 x 20 -> 2 row tiles x 20 batches = 40 workgroups, 29 us for 25.6 MB): K-split
         // down to 4 column blocks per workgroup until there are two workgroups per CU
         else if (T > 1 && n_mtiles64 * T < ncu_ && (double)M * T * ncols * nblk / 4 * 8.0 < 64e6)
-          nsplit = (int)std::min<int64_t>(((int64_t)ncu_ * 2 + n_mtiles64 * T - 1) / (n_mtiles64 * T),
-                                          std::max(1, nblk / 4));
-        if (nsplit < 1) nsplit = 1;
-        const int per = (nblk + nsplit - 1) / nsplit;
-        nsplit = (nblk + per - 1) / per;
-        double *dst = o;
-        int dst32 = out32;
-        int64_t dst_ns = out_rstride, dst_ss = 0, dst_bs = out_tstride;
-        if (nsplit > 1) {
-          dst32 = 0;
-          dst = (double *)ensure(ws_slab_, ws_slab_sz_, sizeof(double) * nsplit * ncols * M * T);
-          dst_ns = M;
-          dst_ss = (int64_t)ncols * M * T;
-          dst_bs = (int64_t)ncols * M;
-        }
+          want = (int)std::min<int64_t>(((int64_t)ncu_ * 2 + n_mtiles64 * T - 1) / (n_mtiles64 * T),
+                                        std::max(1, nblk / 4));
+        const KSplit ks = k_split(nblk, want);
+        const int nsplit = ks.nsplit, per = (int)ks.per;
+        const PassDst d = pass_dst(nsplit, M, T, ncols, o, out32, out_rstride, out_tstride, pad);
         const int64_t nblocks = (int64_t)n_mtiles * nsplit * T;
         if (nblocks > 0x7fffffff) throw std::runtime_error("ppals: scan grid too large");
         dim3 grid((unsigned)nblocks);
         prof_begin(0, bytes);
-        // padded layout: the kernel compacts the rows as it stores them — unless the partial sums
-        // of several k-splits go through the slab, which k_slab_reduce compacts
-        const int64_t k_ld = nsplit > 1 ? 0 : pad.ld, k_valid = nsplit > 1 ? 0 : pad.valid;
-#define LAUNCH_SUFFIX(NTv, ALv)                                                                  \
-  hipLaunchKernelGGL((k_scan_suffix<TV, NTv, ALv>), grid, dim3(256), 0, st_, V, M, K, M * K, P, \
-                     n_mtiles, nsplit, per, nblk, dst, dst_ns, dst_ss, dst_bs, ncols, dst32, k_ld, \
-                     k_valid)
-#define LAUNCH_SUFFIX_FAST_O(NTv, OPTv)                                                             \
-  hipLaunchKernelGGL((k_scan_suffix_fast<TV, NTv, OPTv>), grid, dim3(256), 0, st_, V, M, K, M * K, P, \
-                     n_mtiles, nsplit, per, nblk, dst, dst_ns, dst_ss, dst_bs, ncols, dst32, k_ld,    \
-                     k_valid)
-#define LAUNCH_SUFFIX_FAST(NTv)   \
-  if (nt_store) {                 \
-    LAUNCH_SUFFIX_FAST_O(NTv, 5); \
-  } else {                        \
-    LAUNCH_SUFFIX_FAST_O(NTv, 1); \
-  }
         // persistent launch: ncu*40 workgroups (measured best of 3..40 per CU), each walks over its tiles
         // (fewer tiles than that: every workgroup would take exactly ONE tile and the launch loses what the
         // persistent form is for — the P = 8 shard of cfg2, 3906 tiles: 6 workgroups per CU walking 2.5
@@ -840,34 +817,13 @@ class HipOps : public Ops {
         const int64_t pgrid = nblocks < (int64_t)ncu_ * persist_mult_ ? (int64_t)ncu_ * std::min(persist_mult_, 6)
                                                                        : (int64_t)ncu_ * persist_mult_;
         dim3 grid_p((unsigned)std::min<int64_t>(nblocks, pgrid));
-#define LAUNCH_SUFFIX_BUF_O(NTv, OPTv)                                                                \
-  hipLaunchKernelGGL((k_scan_suffix_buf<TV, NTv, OPTv>), grid_p, dim3(256), 0, st_, V, M, K, M * K, P, \
-                     n_mtiles, nsplit, per, nblk, dst, dst_ns, dst_ss, dst_bs, ncols, dst32, nblocks,  \
-                     k_ld, k_valid)
-        // A result too large for the 256 MB Infinity Cache is stored non-temporally: the stream of
-        // ordinary stores costs the scan 0.2 ms per 320 MB (cfg2) next to its 6.4 GB of reads, the
-        // non-temporal one 0.1 ms (tools/place6_bench, profiles/r03q_place6_nt.txt: 1.09-1.10 ms
-        // against 1.19-1.20 ms per launch for the same source and result buffers), and what reads
-        // the result next streams it from HBM either way. Not on every pair of buffers, though: in one
-        // process (r03q_place6_nt_same_process.txt) 1.21 -> 1.06 ms for some, +1 % for others — so
-        // the engine's online placement choice tries both kinds for the first-level intermediate
-        // (scan_store_mode); this rule is for every other large result.
-        constexpr double nt_min_bytes = 192.0 * 1048576.0;
-        bool nt_store =
-            nsplit == 1 && (scan_nt_mode_ < 0 ? (double)M * T * ncols * (dst32 ? 4.0 : 8.0) >= nt_min_bytes
-                                              : scan_nt_mode_ == 1);
+        bool nts = nt_store(nsplit, (double)M * T * ncols * (d.out32 ? 4.0 : 8.0));
         // (Measured and rejected, tools/runs/r03_u.sh: second-level sums in fp32 for short
         // reductions — 16 NT registers fewer, the two-tile global-load kernel 174 -> 130 registers and
         // 2 -> 3 waves per SIMD, the one-tile buffer kernel 3 -> 4 waves: cfg4 36.0 / 36.7 -> 33.0 /
         // 33.6 sweeps/s, cfg2 no gain. More waves in flight make the mixed read/write stream worse.
         // Fewer do not help either: 64 KB of dynamic LDS per workgroup (2 instead of 3 workgroups per
         // CU) x 6..40 workgroups per CU in the persistent grid: profiles/r03v_occupancy_sweep.txt.)
-#define LAUNCH_SUFFIX_BUF(NTv)           \
-  if (nt_store) {                        \
-    LAUNCH_SUFFIX_BUF_O(NTv, 5);         \
-  } else {                               \
-    LAUNCH_SUFFIX_BUF_O(NTv, 1);         \
-  }
         // buffer-load variant: needs 32-bit byte offsets inside one 16-column block
         const bool buf_ok = (16.0 * (double)M * sizeof(TV) < 2.0e9) && (pack_bytes < 2000000000ull);
         // Which KERNEL runs must not depend on the store kind: the engine's placement exploration tries
@@ -877,9 +833,9 @@ class HipOps : public Ops {
         // the stores are ordinary whatever was asked for.
         const bool takes_buf = al && M >= VEC && buf_ok && (NT == 1 || sizeof(TV) == 8) &&
                                !(sizeof(TV) == 8 && nsplit > 1);
-        const bool takes_tail = !takes_buf && al && M >= VEC && T == 1 && nsplit == 1 && NT <= 2 && k_ld == 0 &&
-                                scan_tail_split<TV>(NT, n_mtiles) >= 0;
-        if (takes_tail) nt_store = false;
+        const bool takes_tail = !takes_buf && al && M >= VEC && T == 1 && nsplit == 1 && NT <= 2 &&
+                                d.row_ld == 0 && scan_tail_split<TV>(NT, n_mtiles) >= 0;
+        if (takes_tail) nts = false;
         // (measured: with NT >= 2 the fp32 build of the buffer variant drops to 2 waves/SIMD and
         // loses to the global-load kernel, so it is used for one n-tile / fp64 storage only)
         // (and: K-split scans of an fp64 tensor — few, long work items of half-size blocks — run
@@ -888,17 +844,7 @@ class HipOps : public Ops {
         // cfg5, 625 tiles, 73 us — is a round and a quarter at 2 waves per SIMD; handing it to the
         // register-lean persistent form with 3 waves, k_scan_suffix_lean<2,4,0,3>, was measured:
         // 40 HOOI sweeps 0.0446 / 0.0443 s against 0.0442 / 0.0441 s. Not kept.)
-        if (takes_buf) {
-          if (NT == 1) {
-            LAUNCH_SUFFIX_BUF(1)
-          } else if (NT == 2) {
-            LAUNCH_SUFFIX_BUF(2)
-          } else if (NT == 3) {
-            LAUNCH_SUFFIX_BUF(3)
-          } else {
-            LAUNCH_SUFFIX_BUF(4)
-          }
-        } else if (takes_tail) {
+        if (takes_tail) {
           // a round and a bit of resident workgroups (cfg5's 625 tiles on 512 slots: 0.49 of the HBM
           // peak): the tiles of the last, partial round as four quarter-length work items each
           // (kernels_scan.hip.h, TAIL MODE)
@@ -906,50 +852,37 @@ class HipOps : public Ops {
           const int64_t strips = ((M + 16 * VEC - 1) / (16 * VEC)) - (int64_t)tail_from * 4;
           dim3 grid_t((unsigned)(tail_from + strips));
           const size_t lds_t = sizeof(double) * 3 * (size_t)(VEC * NT * 4) * 64;
-#define LAUNCH_SUFFIX_TAIL(NTv)                                                                            \
-  hipLaunchKernelGGL((k_scan_suffix_fast<TV, NTv, 9>), grid_t, dim3(256), lds_t, st_, V, M, K, M * K, P,   \
-                     n_mtiles, nsplit, per, nblk, dst, dst_ns, dst_ss, dst_bs, ncols, dst32, (int64_t)0,   \
-                     (int64_t)0, tail_from)
-          if (NT == 1) {
-            LAUNCH_SUFFIX_TAIL(1);
-          } else {
-            LAUNCH_SUFFIX_TAIL(2);
-          }
-#undef LAUNCH_SUFFIX_TAIL
-        } else if (al && M >= VEC) {
-          if (NT == 1) {
-            LAUNCH_SUFFIX_FAST(1)
-          } else if (NT == 2) {
-            LAUNCH_SUFFIX_FAST(2)
-          } else if (NT == 3) {
-            LAUNCH_SUFFIX_FAST(3)
-          } else {
-            LAUNCH_SUFFIX_FAST(4)
-          }
-        } else if (al) {
-          if (NT == 1) LAUNCH_SUFFIX(1, true);
-          else if (NT == 2) LAUNCH_SUFFIX(2, true);
-          else if (NT == 3) LAUNCH_SUFFIX(3, true);
-          else LAUNCH_SUFFIX(4, true);
+          dispatch<1, 2>(NT, [&](auto nt) {
+            hipLaunchKernelGGL((k_scan_suffix_fast<TV, nt, 9>), grid_t, dim3(256), lds_t, st_, V, M, K, M * K, P,
+                               n_mtiles, nsplit, per, nblk, d.p, d.nstride, d.split_stride, d.batch_stride, ncols,
+                               d.out32, (int64_t)0, (int64_t)0, tail_from);
+          });
         } else {
-          if (NT == 1) LAUNCH_SUFFIX(1, false);
-          else if (NT == 2) LAUNCH_SUFFIX(2, false);
-          else if (NT == 3) LAUNCH_SUFFIX(3, false);
-          else LAUNCH_SUFFIX(4, false);
+          dispatch<1, 2, 3, 4>(NT, [&](auto nt) {
+            if (takes_buf)
+              dispatch<5, 1>(nts ? 5 : 1, [&](auto opt) {
+                hipLaunchKernelGGL((k_scan_suffix_buf<TV, nt, opt>), grid_p, dim3(256), 0, st_, V, M, K, M * K, P,
+                                   n_mtiles, nsplit, per, nblk, d.p, d.nstride, d.split_stride, d.batch_stride,
+                                   ncols, d.out32, nblocks, d.row_ld, d.row_valid);
+              });
+            else if (al && M >= VEC)
+              dispatch<5, 1>(nts ? 5 : 1, [&](auto opt) {
+                hipLaunchKernelGGL((k_scan_suffix_fast<TV, nt, opt>), grid, dim3(256), 0, st_, V, M, K, M * K, P,
+                                   n_mtiles, nsplit, per, nblk, d.p, d.nstride, d.split_stride, d.batch_stride,
+                                   ncols, d.out32, d.row_ld, d.row_valid);
+              });
+            else
+              dispatch<true, false>(al, [&](auto alv) {
+                hipLaunchKernelGGL((k_scan_suffix<TV, nt, alv>), grid, dim3(256), 0, st_, V, M, K, M * K, P,
+                                   n_mtiles, nsplit, per, nblk, d.p, d.nstride, d.split_stride, d.batch_stride,
+                                   ncols, d.out32, d.row_ld, d.row_valid);
+              });
+          });
         }
-#undef LAUNCH_SUFFIX
-#undef LAUNCH_SUFFIX_FAST
-#undef LAUNCH_SUFFIX_FAST_O
-#undef LAUNCH_SUFFIX_BUF
-#undef LAUNCH_SUFFIX_BUF_O
         prof_end();
         HIP_CHECK(hipGetLastError());
-        if (nsplit > 1) {
-          hipLaunchKernelGGL(k_slab_reduce, dim3(grid_for(M * ncols, 256), (unsigned)T), dim3(256), 0,
-                             st_, dst, nsplit, dst_ss, M, ncols, o, (int64_t)1, out_rstride, out32,
-                             pad.ld, pad.valid, dst_bs, out_tstride);
-          HIP_CHECK(hipGetLastError());
-        }
+        slab_combine(nsplit, d.p, d.split_stride, M, ncols, o, 1, out_rstride, out32, pad, T, d.batch_stride,
+                     out_tstride);
       }
     }
   }
@@ -975,22 +908,11 @@ class HipOps : public Ops {
     // k-split: the launch is MFMA-bound, so what counts is how evenly its workgroups fill the resident
     // slots (a partial last round idles the matrix cores): take the split whose number of rounds is
     // closest below a whole number, a little in favour of fewer splits (slab traffic, the combine)
-    int &occ = wide_occ_[NT - 1];
-    if (occ == 0) {
-      int nb = 0;
-      hipError_t e = hipErrorUnknown;
-      switch (NT) {
-        case 5: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k_scan_wide<5, 1>, 512, 0); break;
-        case 6: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k_scan_wide<6, 1>, 512, 0); break;
-        case 7: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k_scan_wide<7, 1>, 512, 0); break;
-        default: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k_scan_wide<8, 1>, 512, 0); break;
-      }
-      if (e != hipSuccess) (void)hipGetLastError();
-      occ = (e == hipSuccess && nb > 0) ? nb : 2;
-    }
-    const double slots = (double)ncu_ * occ;
+    const void *kernel = nullptr;
+    dispatch<5, 6, 7, 8>(NT, [&](auto nt) { kernel = (const void *)k_scan_wide<nt, 1>; });
+    const double slots = (double)ncu_ * occupancy(wide_occ_[NT - 1], kernel, 512, 0, 2);
     const int64_t tiles = n_mtiles64 * T;
-    int nsplit = 1;
+    int want = 1;
     if ((double)tiles < 8.0 * slots) {
       double best = -1.0;
       const int ns_max = (int)std::min<int64_t>(24, std::max(1, nblk / 16));
@@ -999,45 +921,26 @@ class HipOps : public Ops {
         const double score = rounds / std::ceil(rounds) - 0.004 * ns;
         if (score > best) {
           best = score;
-          nsplit = ns;
+          want = ns;
         }
       }
     }
-    const int per = (nblk + nsplit - 1) / nsplit;
-    nsplit = (nblk + per - 1) / per;
-    double *dst = o;
-    int dst32 = out32;
-    int64_t dst_ns = out_rstride, dst_ss = 0, dst_bs = out_tstride;
-    if (nsplit > 1) {
-      dst32 = 0;
-      dst = (double *)ensure(ws_slab_, ws_slab_sz_, sizeof(double) * nsplit * ncols * M * T);
-      dst_ns = M;
-      dst_ss = (int64_t)ncols * M * T;
-      dst_bs = (int64_t)ncols * M;
-    }
+    const KSplit ks = k_split(nblk, want);
+    const int nsplit = ks.nsplit, per = (int)ks.per;
+    const PassDst d = pass_dst(nsplit, M, T, ncols, o, out32, out_rstride, out_tstride, pad);
     const int64_t nblocks = (int64_t)n_mtiles * nsplit * T;
     if (nblocks > 0x7fffffff) throw std::runtime_error("ppals: scan grid too large");
-    const int64_t k_ld = nsplit > 1 ? 0 : pad.ld, k_valid = nsplit > 1 ? 0 : pad.valid;
     const double bytes = (double)L * (double)J * (double)T * 4.0 + (double)L * (double)T * ncols * (out32 ? 4.0 : 8.0);
     prof_begin(0, bytes);
-#define LAUNCH_WIDE(NTv)                                                                                  \
-  hipLaunchKernelGGL((k_scan_wide<NTv, 1>), dim3((unsigned)nblocks), dim3(512), 0, st_, V, M, K, M * K, P, \
-                     n_mtiles, nsplit, per, nblk, dst, dst_ns, dst_ss, dst_bs, ncols, dst32, k_ld, k_valid)
-    switch (NT) {
-      case 5: LAUNCH_WIDE(5); break;
-      case 6: LAUNCH_WIDE(6); break;
-      case 7: LAUNCH_WIDE(7); break;
-      default: LAUNCH_WIDE(8); break;
-    }
-#undef LAUNCH_WIDE
+    dispatch<5, 6, 7, 8>(NT, [&](auto nt) {
+      hipLaunchKernelGGL((k_scan_wide<nt, 1>), dim3((unsigned)nblocks), dim3(512), 0, st_, V, M, K, M * K, P,
+                         n_mtiles, nsplit, per, nblk, d.p, d.nstride, d.split_stride, d.batch_stride, ncols, d.out32,
+                         d.row_ld, d.row_valid);
+    });
     prof_end();
     HIP_CHECK(hipGetLastError());
-    if (nsplit > 1) {
-      hipLaunchKernelGGL(k_slab_reduce, dim3(grid_for(M * ncols, 256), (unsigned)T), dim3(256), 0, st_, dst,
-                         nsplit, dst_ss, M, ncols, o, (int64_t)1, out_rstride, out32, pad.ld, pad.valid,
-                         dst_bs, out_tstride);
-      HIP_CHECK(hipGetLastError());
-    }
+    slab_combine(nsplit, d.p, d.split_stride, M, ncols, o, 1, out_rstride, out32, pad, T, d.batch_stride,
+                 out_tstride);
   }
   int gj_scalar_ = 0;  // PPALS_GJ_SCALAR=1: the scalar in-LDS sweeps for 64 < R <= 128 (A/B, tests)
   bool wide_enabled_ = true;  // PPALS_SCAN_WIDE=0: chunks of 64 columns (A/B, tests)
@@ -1049,20 +952,12 @@ class HipOps : public Ops {
   template <typename TV>
   int scan_tail_split(int NT, int n_mtiles) {
     constexpr int VEC = ScanTraits<TV>::VEC;
-    int &per_cu = scan_tail_occ_[(sizeof(TV) == 8 ? 2 : 0) + (NT - 1)];
     if (!scan_tail_on_) return -1;
-    if (per_cu == 0) {
-      const size_t lds_t = sizeof(double) * 3 * (size_t)(VEC * NT * 4) * 64;
-      int nb = 0;
-      hipError_t e = NT == 1
-          ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k_scan_suffix_fast<TV, 1, 9>, 256, lds_t)
-          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k_scan_suffix_fast<TV, 2, 9>, 256, lds_t);
-      if (e != hipSuccess) {
-        (void)hipGetLastError();
-        nb = 0;
-      }
-      per_cu = nb > 0 ? nb : -1;
-    }
+    const size_t lds_t = sizeof(double) * 3 * (size_t)(VEC * NT * 4) * 64;
+    const int per_cu = occupancy(scan_tail_occ_[(sizeof(TV) == 8 ? 2 : 0) + (NT - 1)],
+                                 NT == 1 ? (const void *)k_scan_suffix_fast<TV, 1, 9>
+                                         : (const void *)k_scan_suffix_fast<TV, 2, 9>,
+                                 256, lds_t, -1);
     if (per_cu < 0) return -1;
     const int slots = ncu_ * per_cu;
     if (n_mtiles <= slots || n_mtiles > 4 * slots) return -1;
@@ -1101,50 +996,29 @@ class HipOps : public Ops {
         // order 4 at s = 200 keeps 40000 rows = 79 tiles; order 3 keeps s rows = 1 tile): the fp32
         // launcher's rule (scan_t), each split at least 16 k-blocks; partial sums through the slab
         const int64_t M = L;
-        int nsplit = 1;
+        int want = 1;
         if (T == 1 && n_mtiles64 < (int64_t)ncu_ * 8)
-          nsplit = (int)std::min<int64_t>(((int64_t)ncu_ * 8 + n_mtiles64 - 1) / n_mtiles64,
-                                          std::max(1, nblk / 16));
+          want = (int)std::min<int64_t>(((int64_t)ncu_ * 8 + n_mtiles64 - 1) / n_mtiles64,
+                                        std::max(1, nblk / 16));
         else if (T > 1 && n_mtiles64 * T < ncu_ && (double)M * T * ncols * nblk / 4 * 8.0 < 64e6)
-          nsplit = (int)std::min<int64_t>(((int64_t)ncu_ * 2 + n_mtiles64 * T - 1) / (n_mtiles64 * T),
-                                          std::max(1, nblk / 4));
-        if (nsplit < 1) nsplit = 1;
-        const int per = (nblk + nsplit - 1) / nsplit;
-        nsplit = (nblk + per - 1) / per;
+          want = (int)std::min<int64_t>(((int64_t)ncu_ * 2 + n_mtiles64 * T - 1) / (n_mtiles64 * T),
+                                        std::max(1, nblk / 4));
+        const KSplit ks = k_split(nblk, want);
+        const int nsplit = ks.nsplit, per = (int)ks.per;
         if (n_mtiles64 * nsplit * T > 0x7fffffff) throw std::runtime_error("ppals: scan grid too large");
-        double *dst = o;
-        int dst32 = out32;
-        int64_t dst_ns = out_rstride, dst_ss = 0, dst_bs = out_tstride, k_ld = pad.ld, k_valid = pad.valid;
-        if (nsplit > 1) {
-          dst32 = 0;
-          dst = (double *)ensure(ws_slab_, ws_slab_sz_, sizeof(double) * nsplit * ncols * M * T);
-          dst_ns = M;
-          dst_ss = (int64_t)ncols * M * T;
-          dst_bs = (int64_t)ncols * M;
-          k_ld = k_valid = 0;
-        }
+        const PassDst d = pass_dst(nsplit, M, T, ncols, o, out32, out_rstride, out_tstride, pad);
         const dim3 grid((unsigned)(n_mtiles64 * nsplit * T));
-        // non-temporal result stores: the fp32 kernels' rule (scan_t) — the engine's choice, else by size
-        const bool nts = nsplit == 1 && (scan_nt_mode_ < 0 ? (double)L * T * ncols * (out32 ? 4.0 : 8.0) >=
-                                                                 192.0 * 1048576.0
-                                                           : scan_nt_mode_ == 1);
-#define PPALS_BF16_SCAN(NTSv, BIGv)                                                                         \
-  hipLaunchKernelGGL((k_scan_suffix_bf16<BF16_MAX_NT, NTSv, BIGv>), grid, dim3(256), 0, st_, V, L, J, P,         \
-                     (int)n_mtiles64, nsplit, per, nblk, dst, dst_ns, dst_ss, dst_bs, ncols, dst32, k_ld, k_valid)
-        if (big) {
-          if (nts) PPALS_BF16_SCAN(true, true);
-          else PPALS_BF16_SCAN(false, true);
-        } else {
-          if (nts) PPALS_BF16_SCAN(true, false);
-          else PPALS_BF16_SCAN(false, false);
-        }
-#undef PPALS_BF16_SCAN
-        if (nsplit > 1) {
-          HIP_CHECK(hipGetLastError());
-          hipLaunchKernelGGL(k_slab_reduce, dim3(grid_for(M * ncols, 256), (unsigned)T), dim3(256), 0, st_, dst,
-                             nsplit, dst_ss, M, ncols, o, (int64_t)1, out_rstride, out32, pad.ld, pad.valid,
-                             dst_bs, out_tstride);
-        }
+        const bool nts = nt_store(nsplit, (double)L * T * ncols * (out32 ? 4.0 : 8.0));
+        dispatch<true, false>(nts, [&](auto ntsv) {
+          dispatch<true, false>(big, [&](auto bigv) {
+            hipLaunchKernelGGL((k_scan_suffix_bf16<BF16_MAX_NT, ntsv, bigv>), grid, dim3(256), 0, st_, V, L, J, P,
+                               (int)n_mtiles64, nsplit, per, nblk, d.p, d.nstride, d.split_stride, d.batch_stride,
+                               ncols, d.out32, d.row_ld, d.row_valid);
+          });
+        });
+        HIP_CHECK(hipGetLastError());
+        slab_combine(nsplit, d.p, d.split_stride, M, ncols, o, 1, out_rstride, out32, pad, T, d.batch_stride,
+                     out_tstride);
       } else {
         double *B = (double *)ensure(ws_krp_, ws_krp_sz_, sizeof(double) * (size_t)J * ncols);
         krp(B, f, nf, col0, ncols);
@@ -1189,15 +1063,15 @@ class HipOps : public Ops {
       const int nt = Kc <= 16 ? 1 : (Kc <= 32 ? 2 : 4);
       dim3 grid((unsigned)((L + 15) / 16), (unsigned)((Kc + 16 * nt - 1) / (16 * nt)), (unsigned)T);
       prof_begin(1, bytes);
-#define PPALS_MPS(TA_, NT_)                                                                               \
-  hipLaunchKernelGGL((k_mode_product_small<TA_, NT_>), grid, dim3(512), 0, st_, (const TA_ *)X, (int)L, (int)J, W, \
-                     ldw, Kc, out)
-      if (dt == F32) {
-        if (nt == 1) PPALS_MPS(float, 1); else if (nt == 2) PPALS_MPS(float, 2); else PPALS_MPS(float, 4);
-      } else {
-        if (nt == 1) PPALS_MPS(double, 1); else if (nt == 2) PPALS_MPS(double, 2); else PPALS_MPS(double, 4);
-      }
-#undef PPALS_MPS
+      dispatch<1, 2, 4>(nt, [&](auto ntv) {
+        auto launch = [&](auto ta) {
+          using TA = decltype(ta);
+          hipLaunchKernelGGL((k_mode_product_small<TA, ntv>), grid, dim3(512), 0, st_, (const TA *)X, (int)L,
+                             (int)J, W, ldw, Kc, out);
+        };
+        if (dt == F32) launch(float());
+        else launch(double());
+      });
       prof_end();
       HIP_CHECK(hipGetLastError());
       return;
@@ -1214,15 +1088,15 @@ class HipOps : public Ops {
     const int nt = Kc <= 16 ? 1 : (Kc <= 32 ? 2 : 4);
     dim3 grid((unsigned)((S + 15) / 16), (unsigned)((Kc + 16 * nt - 1) / (16 * nt)), (unsigned)T);
     prof_begin(1, bytes);
-#define PPALS_MPL(TA_, NT_)                                                                               \
-  hipLaunchKernelGGL((k_mode_product_lead<TA_, NT_>), grid, dim3(512), 0, st_, (const TA_ *)X, (int)J, (int)S, W,  \
-                     ldw, Kc, out)
-    if (dt == F32) {
-      if (nt == 1) PPALS_MPL(float, 1); else if (nt == 2) PPALS_MPL(float, 2); else PPALS_MPL(float, 4);
-    } else {
-      if (nt == 1) PPALS_MPL(double, 1); else if (nt == 2) PPALS_MPL(double, 2); else PPALS_MPL(double, 4);
-    }
-#undef PPALS_MPL
+    dispatch<1, 2, 4>(nt, [&](auto ntv) {
+      auto launch = [&](auto ta) {
+        using TA = decltype(ta);
+        hipLaunchKernelGGL((k_mode_product_lead<TA, ntv>), grid, dim3(512), 0, st_, (const TA *)X, (int)J, (int)S,
+                           W, ldw, Kc, out);
+      };
+      if (dt == F32) launch(float());
+      else launch(double());
+    });
     prof_end();
     HIP_CHECK(hipGetLastError());
     return true;
@@ -1711,35 +1585,27 @@ class HipOps : public Ops {
       // (three workgroups per CU are resident — 134 registers, 40 KB of LDS —: the split is rounded DOWN
       // so that tiles x splits fit one round; rounded up, cfg5's 28 x 28 = 784 workgroups ran as 768 +
       // 16, i.e. two rounds: 1.10 ms per Gram)
-      int nsplit = (int)std::min<int64_t>(std::max<int64_t>(1, ((int64_t)ncu_ * 3) / ntri),
-                                          std::max<int64_t>(1, C / 1024));
-      nsplit = std::min(nsplit, 512);
-      int64_t per = ((C + nsplit - 1) / nsplit + 31) / 32 * 32;
-      nsplit = (int)((C + per - 1) / per);
-      double *dst = nsplit > 1 ? (double *)ensure(ws_slab_, ws_slab_sz_, sizeof(double) * nsplit * J * J) : G;
+      const int want = (int)std::min<int64_t>(std::max<int64_t>(1, ((int64_t)ncu_ * 3) / ntri),
+                                              std::max<int64_t>(1, C / 1024));
+      const KSplit ks = k_split(C, std::min(want, 512), 1, 32);
+      double *dst = pass_dst(ks.nsplit, J * J, 1, 1, G, 0, 0, 0, RowPad()).p;
       prof_begin(1, (double)C * J * dtype_size(dt));
-      hipLaunchKernelGGL(k_unfold_syrk_f32, dim3((unsigned)ntri, 1, (unsigned)nsplit), dim3(256), 0, st_,
-                         (const float *)X, L, J, T, per, dst);
+      hipLaunchKernelGGL(k_unfold_syrk_f32, dim3((unsigned)ntri, 1, (unsigned)ks.nsplit), dim3(256), 0, st_,
+                         (const float *)X, L, J, T, ks.per, dst);
       prof_end();
       HIP_CHECK(hipGetLastError());
-      if (nsplit > 1) {
-        hipLaunchKernelGGL(k_slab_reduce, dim3(grid_for(J * J, 256)), dim3(256), 0, st_, dst, nsplit,
-                           J * J, J * J, 1, G, (int64_t)1, (int64_t)0, 0, (int64_t)0, (int64_t)0);
-        HIP_CHECK(hipGetLastError());
-      }
+      slab_combine(ks.nsplit, dst, J * J, J * J, 1, G, 1, 0, 0);
       return;
     }
     const int tiles = (int)((J + 31) / 32);
-    int nsplit = 1;
-    const int64_t want = (int64_t)ncu_ * 4;
-    if ((int64_t)tiles * tiles < want) nsplit = (int)std::min<int64_t>(
-        (want + (int64_t)tiles * tiles - 1) / ((int64_t)tiles * tiles), std::max<int64_t>(1, C / 256));
-    nsplit = std::max(1, std::min(nsplit, 1024));
-    int64_t per = (C + nsplit - 1) / nsplit;
-    per = (per + 31) / 32 * 32;
-    nsplit = (int)((C + per - 1) / per);
-    double *dst = G;
-    if (nsplit > 1) dst = (double *)ensure(ws_slab_, ws_slab_sz_, sizeof(double) * nsplit * J * J);
+    int want = 1;
+    const int64_t target = (int64_t)ncu_ * 4;
+    if ((int64_t)tiles * tiles < target) want = (int)std::min<int64_t>(
+        (target + (int64_t)tiles * tiles - 1) / ((int64_t)tiles * tiles), std::max<int64_t>(1, C / 256));
+    const KSplit ks = k_split(C, std::min(want, 1024), 1, 32);
+    const int nsplit = ks.nsplit;
+    const int64_t per = ks.per;
+    double *dst = pass_dst(nsplit, J * J, 1, 1, G, 0, 0, 0, RowPad()).p;
     dim3 grid(tiles, tiles, nsplit);
     prof_begin(1, (double)C * J * dtype_size(dt));
     if (J >= 16) {  // matrix cores (K13); tiny modes: the VALU tile kernel
@@ -1757,11 +1623,7 @@ class HipOps : public Ops {
                          T, per, dst);
     prof_end();
     HIP_CHECK(hipGetLastError());
-    if (nsplit > 1) {
-      hipLaunchKernelGGL(k_slab_reduce, dim3(grid_for(J * J, 256)), dim3(256), 0, st_, dst, nsplit,
-                         J * J, J * J, 1, G, (int64_t)1, (int64_t)0, 0, (int64_t)0, (int64_t)0);
-      HIP_CHECK(hipGetLastError());
-    }
+    slab_combine(nsplit, dst, J * J, J * J, 1, G, 1, 0, 0);
   }
   // Leading eigenvectors of the s x s Gram (the reference's MTM.svd(U,S,VT,rank),
   // als_Tucker.cxx:20,402). SURVEY.md §2.1 K12 allows the vendor symmetric eigensolver here:
@@ -3381,6 +3243,54 @@ class HipOps : public Ops {
     return p;
   }
   double *small(int n) { return (double *)ensure(ws_small_, ws_small_sz_, sizeof(double) * n); }
+
+  // Where a pass of nsplit k-splits writes its ncols x M result (T batches): the output o itself, or
+  // for nsplit > 1 the fp64 slab [split][batch][ncols][M] that slab_combine sums into o. A padded
+  // layout's rows are compacted by whichever kernel stores to o: the pass, or the combine.
+  struct PassDst {
+    double *p;
+    int out32;
+    int64_t nstride, split_stride, batch_stride, row_ld, row_valid;
+  };
+  PassDst pass_dst(int nsplit, int64_t M, int64_t T, int ncols, double *o, int out32, int64_t out_rstride,
+                   int64_t out_tstride, RowPad pad) {
+    if (nsplit == 1) return {o, out32, out_rstride, 0, out_tstride, pad.ld, pad.valid};
+    double *slab = (double *)ensure(ws_slab_, ws_slab_sz_, sizeof(double) * nsplit * ncols * M * T);
+    return {slab, 0, M, (int64_t)ncols * M * T, (int64_t)ncols * M, 0, 0};
+  }
+  // k_slab_reduce: the sum of the nsplit partial results in the slab, into out (nothing to do for one split)
+  void slab_combine(int nsplit, const double *slab, int64_t split_stride, int64_t M, int ncols, double *out,
+                    int64_t out_mstride, int64_t out_rstride, int out32, RowPad pad = RowPad(), int64_t T = 1,
+                    int64_t slab_bstride = 0, int64_t out_bstride = 0) {
+    if (nsplit == 1) return;
+    hipLaunchKernelGGL(k_slab_reduce, dim3(grid_for(M * ncols, 256), (unsigned)T), dim3(256), 0, st_, slab, nsplit,
+                       split_stride, M, ncols, out, out_mstride, out_rstride, out32, pad.ld, pad.valid, slab_bstride,
+                       out_bstride);
+    HIP_CHECK(hipGetLastError());
+  }
+  // A result too large for the 256 MB Infinity Cache is stored non-temporally: the stream of
+  // ordinary stores costs the scan 0.2 ms per 320 MB (cfg2) next to its 6.4 GB of reads, the
+  // non-temporal one 0.1 ms (tools/place6_bench, profiles/r03q_place6_nt.txt: 1.09-1.10 ms
+  // against 1.19-1.20 ms per launch for the same source and result buffers), and what reads
+  // the result next streams it from HBM either way. Not on every pair of buffers, though: in one
+  // process (r03q_place6_nt_same_process.txt) 1.21 -> 1.06 ms for some, +1 % for others — so
+  // the engine's online placement choice tries both kinds for the first-level intermediate
+  // (scan_store_mode); this rule is for every other large result. A k-split pass writes the slab.
+  static constexpr double kNtMinBytes = 192.0 * 1048576.0;
+  bool nt_store(int nsplit, double result_bytes) const {
+    return nsplit == 1 && (scan_nt_mode_ < 0 ? result_bytes >= kNtMinBytes : scan_nt_mode_ == 1);
+  }
+  // resident workgroups per CU of a kernel, asked of the runtime once and kept in `cached`
+  // (`fallback` when the runtime has no answer)
+  static int occupancy(int &cached, const void *kernel, int block, size_t lds, int fallback) {
+    if (cached == 0) {
+      int nb = 0;
+      const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, block, lds);
+      if (e != hipSuccess) (void)hipGetLastError();
+      cached = (e == hipSuccess && nb > 0) ? nb : fallback;
+    }
+    return cached;
+  }
 
   int dev_ = 0, ncu_ = 256, force_jacobi_ = 0, persist_mult_ = 40;
   int eig_debug_ = 0;

@@ -673,17 +673,6 @@ __global__ void k_handover_probe(unsigned long long *flag, unsigned long long se
   }
 }
 
-// X = (G - sigma I) / rho   (J x J)
-__global__ void k_shift_scale(const double *__restrict__ G, int64_t J, double sigma, double inv_rho,
-                              double *__restrict__ X) {
-  const int64_t total = J * J;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
-       e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t i = e % J, j = e / J;
-    X[e] = (G[e] - (i == j ? sigma : 0.0)) * inv_rho;
-  }
-}
-
 // X = G - sum_{d < m} (lam[d] - tau) q_d q_d^T - sigma I   (deflation of the dominant eigenpairs:
 // their eigenvalues are moved down to tau, everything else is untouched), partial[blk] = the
 // block's share of ||X||_F^2. Q: J x m column-major.
@@ -1054,14 +1043,6 @@ __global__ void k_right_mult(const double *__restrict__ Z, int64_t rows, int r,
     for (int p = 0; p < r; p++) acc += Z[i + rows * p] * sT[p + r * q];
     out[e] = acc;
   }
-}
-
-// Z = 0.5 * (Omega + XO)   (projector applied to the previous basis)
-__global__ void k_half_sum(const double *__restrict__ a, const double *__restrict__ b, int64_t n,
-                           double *__restrict__ out) {
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n;
-       e += (int64_t)gridDim.x * blockDim.x)
-    out[e] = 0.5 * (a[e] + b[e]);
 }
 
 // ---------------------------------------------------------------------------------------------
