@@ -14,6 +14,10 @@ One JSON line is printed by rank 0; see DESIGN.md "Measurement" for every field.
 number of timed sweeps and `ms_per_step` the milliseconds one of them took. `--dump-outputs DIR` writes
 what the timed sweeps computed as DIR/<name>.npy (the inputs are seeded: two builds compare output
 for output).
+
+A plain run sets up, warms up, times the K sweeps and prints the headline; everything measured beside
+it (counted HBM traffic, the untimed kernel breakdown, other schedules, precisions and configs, the
+sharded records at N > 1, the CPU baseline) runs only with `--full`.
 """
 import argparse
 import json
@@ -833,13 +837,19 @@ def main():
                     help="storage type of the tensor in HBM (all factor math is fp64)")
     ap.add_argument("--schedule", default=None, choices=["dt", "msdt"],
                     help="sweep schedule (default: the engine's, msdt); same ALS iterates either way")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, also measure the counted HBM traffic, the kernel breakdown, the "
+                         "sub_records (other schedule, precision and configs; sharded records at N > 1) and "
+                         "the CPU baseline; a plain run measures the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-config-records", action="store_true",
-                    help="skip the cfg3 (PP) / cfg4 (s=400) / cfg5 (Tucker) sub_records (N = 1) and the sharded "
-                         "cfg4 / cfg5 sub_records (N > 1)")
+                    help="with --full: skip the cfg3 (PP) / cfg4 (s=400) / cfg5 (Tucker) sub_records (N = 1) and "
+                         "the sharded cfg4 / cfg5 sub_records (N > 1); with --workload coil100|timelapse: skip "
+                         "the PP and Tucker sub_records")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)  # live_pmc_traffic's child runs
     ap.add_argument("--no-pmc", action="store_true",
-                    help="do not count HBM bytes with rocprofv3 --pmc child passes (roofline.traffic = null)")
+                    help="with --full: do not count HBM bytes with rocprofv3 --pmc child passes "
+                         "(roofline.traffic = null)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last of them computed (factor matrices, their "
                          "gradients, gradient norm, residual) as DIR/<name>.npy, fp64; same inputs every run")
@@ -857,13 +867,15 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
 
     # HBM traffic of the scan kernel, counted by child passes under rocprofv3 --pmc BEFORE this
-    # process initialises the GPU (N = 1, the real engine only)
+    # process initialises the GPU (--full, N = 1, the real engine only)
     live_traffic, live_traffic_src = None, "not collected"
     # (never from inside a profiled run: a profiler's preloaded library has initialised the GPU
     # already and its environment would be inherited by the children)
     profiled = ("rocprof" in os.environ.get("LD_PRELOAD", "").lower()
                 or any(k.startswith(("ROCPROF", "ROCP_", "ROCPROFILER")) for k in os.environ))
-    if profiled:
+    if not args.full:
+        live_traffic_src = "not collected: counted with --full"
+    elif profiled:
         live_traffic_src = "not collected: this run is itself under a profiler"
     elif (world == 1 and not args.no_pmc and os.environ.get("PPALS_BENCH_BACKEND") != "hostsim"
             and os.environ.get("PPALS_FORCE_COMM", "0") != "1"):
@@ -882,13 +894,13 @@ def main():
     else:
         import ppals
     dev = "cpu" if hostsim else "cuda"
-    config_records = (int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_config_records
+    config_records = (args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_config_records
                       and args.workload == "cp4_s200_r10" and args.dtype == "f32"
                       and not args.schedule)
-    # N > 1: the sharded records of configs[3] / configs[4] (the driver's scaling runs use the default flags)
+    # N > 1: the sharded records of configs[3] / configs[4]
     # (PPALS_FORCE_COMM=1: the same records on a one-rank communicator — the rehearsal on a 1-GPU box)
     sharded_records = ((int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("PPALS_FORCE_COMM", "0") == "1")
-                       and not args.no_config_records
+                       and args.full and not args.no_config_records
                        and not args.schedule
                        and ((args.workload == "cp4_s200_r10" and args.dtype == "f32") or hostsim))
     if (config_records or sharded_records) and not hostsim:
@@ -1051,23 +1063,25 @@ def main():
         if rank == 0:
             dump_outputs(args.dump_outputs, W_out, gradW_out, gradnorm, resid)
     vnorm = V.norm()
-    # untimed breakdown pass: a few more sweeps with every bracketed kernel under events (each
-    # event pair idles the stream for ~10 us, which is why the timed region brackets scans only)
-    extra = 6
-    ctx.profile_reset()
-    ctx.profile_enable(2)
-    cp.sweeps_dt(extra)
-    barrier()
-    ctx.profile_enable(0)
-    _, other_ms, _ = ctx.profile_read(1)
-    other_ms_per_step = other_ms / extra
+    other_ms_per_step = None
+    if args.full:
+        # untimed breakdown pass: a few more sweeps with every bracketed kernel under events (each
+        # event pair idles the stream for ~10 us, which is why the timed region brackets scans only)
+        extra = 6
+        ctx.profile_reset()
+        ctx.profile_enable(2)
+        cp.sweeps_dt(extra)
+        barrier()
+        ctx.profile_enable(0)
+        _, other_ms, _ = ctx.profile_read(1)
+        other_ms_per_step = other_ms / extra
 
-    # ---- sub-records beside the headline (same JSON line, never `value`): the reference's own
+    # ---- sub-records beside the headline (--full; same JSON line, never `value`): the reference's own
     # two-scan schedule (SURVEY §8d counts ITS bytes: 2 s^4 sizeof per sweep) and the reference's
     # own precision (fp64 storage) at N = 1; the other shard plan at N > 1
     sub = {}
     sub_steps = max(4, min(args.steps, 10))
-    if world == 1 and not args.schedule and not args.workload.startswith("cp4_s400"):
+    if args.full and world == 1 and not args.schedule and not args.workload.startswith("cp4_s400"):
         other = "dt" if schedule == "msdt" else "msdt"
         cp.set_schedule(other)
         r = measure(cp, sub_steps, 2)
@@ -1076,7 +1090,7 @@ def main():
         r["mttkrp_tflops"] = r["sweep_flops"] * r["value"] / 1e12
         sub[f"{other}_schedule_{args.dtype}"] = r
         cp.set_schedule(schedule)
-    if world == 1 and not args.schedule and schedule == "msdt":
+    if args.full and world == 1 and not args.schedule and schedule == "msdt":
         # the SAME measurement in this process with the placement measurement switched off
         # (PPALS_PLACE_TUNE is read when a session is created): does the set-up's choice of result
         # blocks / offsets / store kinds pay on THIS box?
@@ -1098,7 +1112,7 @@ def main():
             del os.environ["PPALS_PLACE_TUNE"]
         else:
             os.environ["PPALS_PLACE_TUNE"] = old
-    if world == 1 and not args.schedule:
+    if args.full and world == 1 and not args.schedule:
         # cold (first sweep) beside the steady state — a fresh session on the resident
         # tensor: session creation (second resident layout, workspaces), then the very first exact sweep
         try:
@@ -1120,7 +1134,7 @@ def main():
             cpc.close()
         except Exception as e:  # reported, never required
             sub["cold"] = {"error": str(e)}
-    if world == 1 and not args.schedule and schedule == "msdt" and not hostsim:
+    if args.full and world == 1 and not args.schedule and schedule == "msdt" and not hostsim:
         # wall time from session creation to 250 sweeps done (the reference's scripts run 250,
         # script/script_synthetic.py:18) with the online placement choice and without, same tensor,
         # same process, alternating, the faster of two runs each
@@ -1150,7 +1164,7 @@ def main():
                         "sweeps), untuned = PPALS_PLACE_TUNE=0"}
         except Exception as e:
             sub["time_to_250_sweeps"] = {"error": str(e)}
-    if world > 1:
+    if args.full and world > 1:
         # the plan north_star names (reduce-scatter of the s x R partials + row-block solve +
         # all-gather) beside the default for these message sizes (one all-reduce + redundant fused
         # update): PPALS_COMM_SMALL_BYTES moves the switch, read when a session is created
@@ -1217,7 +1231,7 @@ def main():
         except Exception as e:  # reported, never required
             sub["rank100"] = {"error": str(e)}
     V.close()
-    if world == 1 and args.dtype == "f32" and not args.schedule and args.workload == "cp4_s200_r10":
+    if args.full and world == 1 and args.dtype == "f32" and not args.schedule and args.workload == "cp4_s200_r10":
         V64 = ppals.Tensor(ctx, lens, ppals.F64).fill_cp(Wtrue)
         cp64 = ppals.CP(ctx, V64, R)
         r = measure(cp64, sub_steps, 2)
@@ -1337,7 +1351,7 @@ def main():
         out["timed_region_ns"] = head.get("timed_region_ns")
         if sub:
             out["sub_records"] = sub
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(lens, R)
             except Exception as e:  # the baseline is reported, never required

@@ -1,5 +1,5 @@
 """bench.py's own N > 1 code path on the CPU: the process group, the communicator-id hand-over,
-init_comm, measure() with its barrier / max-over-ranks, and the reduce-scatter sub-record — two ranks
+init_comm, measure() with its barrier / max-over-ranks, and (`--full`) the sub-records — two ranks
 over gloo and the engine's host stand-in (PPALS_BENCH_BACKEND=hostsim). What the driver's 8-GPU run
 executes for the first time on hardware is executed here first (TEST INFRASTRUCTURE: the numbers
 mean nothing)."""
@@ -35,7 +35,7 @@ def test_bench_multi_rank_path_on_the_host_stand_in(world, tmp_path):
                    PPALS_BENCH_BACKEND="hostsim")
         procs.append(subprocess.Popen(
             [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3",
-             "--warmup", "1", "--workload", workload, "--dtype", "f64", "--no-cpu-baseline",
+             "--warmup", "1", "--workload", workload, "--dtype", "f64", "--full", "--no-cpu-baseline",
              "--dump-outputs", str(tmp_path / "multi")],
             env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = []
@@ -90,17 +90,38 @@ def test_bench_multi_rank_path_on_the_host_stand_in(world, tmp_path):
         assert a.shape == b.shape and np.linalg.norm(a - b) <= 1e-9 * np.linalg.norm(b), n
 
 
-def _bench_dump(out_dir, steps, warmup):
+def _bench_dump(out_dir, steps, warmup, flags=("--no-cpu-baseline", "--no-config-records")):
     env = dict(os.environ, PPALS_BENCH_BACKEND="hostsim", OMP_NUM_THREADS="2")
     env.pop("RANK", None), env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
                         "--warmup", str(warmup), "--workload", "cp4_s12_r3", "--dtype", "f64",
-                        "--no-cpu-baseline", "--no-config-records", "--dump-outputs", str(out_dir)],
+                        *flags, "--dump-outputs", str(out_dir)],
                        env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout
     return json.loads(lines[0])
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """a plain run measures the headline and nothing beside it; --full adds the sub-records and leaves
+    the headline's iterates and dumped outputs as they are"""
+    import numpy as np
+    import hostsim_util
+    hostsim_util.load()
+    plain = _bench_dump(tmp_path / "plain", 3, 1, flags=())
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in plain, key
+    assert plain["steps"] == 3 and plain["warmup"] == 1 and plain["value"] > 0
+    assert "sub_records" not in plain and "cpu_baseline" not in plain
+    full = _bench_dump(tmp_path / "full", 3, 1, flags=("--full", "--no-cpu-baseline"))
+    assert full["sub_records"]["dt_schedule_f64"]["value"] > 0 and "cold" in full["sub_records"]
+    assert full["final_gradnorm"] == plain["final_gradnorm"]
+    assert full["final_rel_residual"] == plain["final_rel_residual"]
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert len(names) == 10 and sorted(os.listdir(tmp_path / "full")) == names
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "full" / n), np.load(tmp_path / "plain" / n)), n
 
 
 def test_bench_dump_outputs_are_the_timed_sweeps(tmp_path):

@@ -8,7 +8,7 @@ CFG5="-model Tucker -tensor r2 -dim 3 -size 400 -rank 20 -pp 0 -maxiter 40 -prec
 T=r05Z
 tools/gpu_steps.sh \
  "${T}_tests|1100|python -m pytest tests -m gpu -x -q --durations=8" \
- "${T}_bench|600|python bench.py --gpus 1 --steps 20 --warmup 3" \
+ "${T}_bench|600|python bench.py --gpus 1 --steps 20 --warmup 3 --full" \
  "${T}_prof_bench|600|$RP -d gpurun_out/${T}_prof_bench -o p -- python3 bench.py --gpus 1 --steps 20 --warmup 3 --no-config-records --no-pmc" \
  "${T}_prof_cfg5|300|$RP -d gpurun_out/${T}_prof_cfg5 -o p -- $B/test_ALS $CFG5 -filename gpurun_out/${T}_cfg5_tucker_prof.csv" \
  "${T}_cfg5|200|$B/test_ALS $CFG5 -filename gpurun_out/${T}_cfg5_tucker.csv" \

@@ -9,7 +9,7 @@ CFG5="-model Tucker -tensor r2 -dim 3 -size 400 -rank 20 -pp 0 -maxiter 40 -prec
 T=${1:-r06Z}
 tools/gpu_steps.sh \
  "${T}_tests|1100|PPALS_MULTIRANK_LOG=gpurun_out/${T}_multirank python -m pytest tests -m gpu -x -q --durations=8" \
- "${T}_bench|600|python bench.py --gpus 1 --steps 20 --warmup 3" \
+ "${T}_bench|600|python bench.py --gpus 1 --steps 20 --warmup 3 --full" \
  "${T}_prof_bench|600|$RP -d gpurun_out/${T}_prof_bench -o p -- python3 bench.py --gpus 1 --steps 20 --warmup 3 --no-config-records --no-pmc" \
  "${T}_prof_cfg4|400|$RP -d gpurun_out/${T}_prof_cfg4 -o p -- python3 tools/runs/r06_rank100.py 20 400 4" \
  "${T}_prof_r100|300|$RP -d gpurun_out/${T}_prof_r100 -o p -- python3 tools/runs/r06_rank100.py 100 200 6" \

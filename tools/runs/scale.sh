@@ -6,8 +6,8 @@
 #   usage: tools/runs/scale.sh [outdir]            (from the repository root)
 # Every line of <outdir>/scale_*.jsonl is one bench.py JSON record: `value` = sweeps/s of the WHOLE
 # job (strong scaling: same tensor, leading-mode shards), `rccl_ranks` = the communicator size the
-# engine reports, `sub_records.reduce_scatter_plan` = the reduce-scatter / all-gather plan beside
-# the default (one all-reduce per mode below 1 MiB).
+# engine reports, `sub_records.reduce_scatter_plan` (N > 1, `--full`) = the reduce-scatter /
+# all-gather plan beside the default (one all-reduce per mode below 1 MiB).
 set -u
 OUT=${1:-gpurun_out/scale}
 mkdir -p "$OUT"
@@ -21,7 +21,7 @@ for WL in cp4_s200_r10 cp4_s400_r20; do
         | tee -a "$OUT/scale_$WL.jsonl"
     else
       python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \
-        --master-port $PORT bench.py --gpus $N --steps 20 --warmup 5 --workload $WL --no-cpu-baseline \
+        --master-port $PORT bench.py --gpus $N --steps 20 --warmup 5 --workload $WL --full --no-cpu-baseline \
         | tee -a "$OUT/scale_$WL.jsonl"
       PORT=$((PORT + 1))
     fi
