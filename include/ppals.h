@@ -258,6 +258,33 @@ int ppals_tucker_dt(ppals_tucker *s, const ppals_cp_opts *o, int *iters);
 /* alsTucker_PP (als_Tucker.h:89-91, als_Tucker.cxx:906-962); o->tol_init = -pp_res_tol */
 int ppals_tucker_pp(ppals_tucker *s, const ppals_cp_opts *o, int *iters);
 
+/* ---- a fitted model and its residual into DEVICE memory (TensorLy's cp_to_tensor / tucker_to_tensor)
+ * The view is exactly that of ppals_tensor_export_device: a box of the GLOBAL tensor, strides >= 0 in
+ * elements (NULL: dense over the box, first index fastest), destination type F32 or F64; every check
+ * of that call (ppals_tensor_check_device_view, direction export, the same messages) and a bad `what`
+ * are refused with PPALS_ERR_ARG before anything is launched. Each rank writes the part of the box in
+ * its own leading-mode rows and leaves every other element alone. The stores are ordered after the
+ * work queued on `stream` so far, and work queued there later runs after them; the host does not
+ * block. Every element is the fp64 model (products and sums on the fp64 matrix cores) rounded once to
+ * the destination type; PPALS_RESIDUAL subtracts it, in fp64, from V as stored (the bf16 / fp32 / fp64
+ * values the session works on) before that one rounding.
+ *   CP: the model [[W_0, ..., W_{N-1}]] of the current factors: the one whose distance from V
+ *       ppals_cp_residual returns (the exported residual's Frobenius norm equals it up to rounding).
+ *   Tucker: core x_0 W_0 ... x_{N-1} W_{N-1} of exactly the factors and core ppals_tucker_get_factors
+ *       would return now: deferred eigen-checks are settled and pending rotations applied first, by the
+ *       same path get_factors takes (and with the same effect on the session as that call).
+ * Nothing else of the session changes: no cache is dropped and no sweep is added, so later sweeps give
+ * bit for bit the factors they give without the export (for Tucker: with a get_factors call in its place).
+ * The session keeps the export's operand buffers (CP: the two Khatri-Rao products of the box; Tucker:
+ * the transposed factors and up to 2 x 256 MB of chain buffers) for its next export. */
+#define PPALS_MODEL 0    /* the model: CP [[W_0..W_{N-1}]], Tucker core x_0 W_0 ... x_{N-1} W_{N-1} */
+#define PPALS_RESIDUAL 1 /* V - model, V as stored                                                */
+int ppals_cp_export_model_device(ppals_cp *s, int what, void *dst, int dst_dtype, const int64_t *box_lo,
+                                 const int64_t *box_len, const int64_t *strides, void *stream);
+int ppals_tucker_export_model_device(ppals_tucker *s, int what, void *dst, int dst_dtype,
+                                     const int64_t *box_lo, const int64_t *box_len,
+                                     const int64_t *strides, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

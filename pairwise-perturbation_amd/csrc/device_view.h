@@ -231,4 +231,72 @@ DV_HD inline void dv_tile_grid(const ViewPlan &p, int64_t *FA, int64_t *tA, int6
   *tiles = *tA * *tB * nb;
 }
 
+// ---- a decomposition's model stored through a view (ppals_cp/tucker_export_model_device,
+// kernels_model.hip.h). The box of a checked export view cut to this rank's rows: per mode its global
+// lo / extent, view and shard strides, and the offsets of its first element from the view pointer and
+// from the shard's start. false: this rank writes nothing.
+struct ModelBox {
+  int order = 0;
+  int64_t lo[DV_MAX_ORDER] = {}, len[DV_MAX_ORDER] = {}, vs[DV_MAX_ORDER] = {}, rs[DV_MAX_ORDER] = {};
+  int64_t voff = 0, roff = 0;
+};
+inline bool dv_model_box(const ViewArgs &a, const int64_t *glens, int64_t row0, int64_t l0,
+                         ModelBox *b) {
+  const int64_t r_lo = std::max(a.lo[0], row0), r_hi = std::min(a.lo[0] + a.len[0], row0 + l0);
+  if (r_hi <= r_lo) return false;
+  b->order = a.order;
+  b->voff = (r_lo - a.lo[0]) * a.stride[0];
+  b->roff = r_lo - row0;
+  for (int i = 0; i < a.order; i++) {
+    if (a.len[i] == 0) return false;
+    b->lo[i] = i == 0 ? r_lo : a.lo[i];
+    b->len[i] = i == 0 ? r_hi - r_lo : a.len[i];
+    b->vs[i] = a.stride[i];
+    b->rs[i] = i == 0 ? 1 : b->rs[i - 1] * (i == 1 ? l0 : glens[i - 1]);
+    if (i > 0) b->roff += a.lo[i] * b->rs[i];
+  }
+  return true;
+}
+// modes of the box flattened into one index, the first listed fastest
+struct ModelGroup {
+  int n = 0;
+  int64_t count = 1;
+  int64_t len[DV_MAX_ORDER] = {}, vs[DV_MAX_ORDER] = {}, rs[DV_MAX_ORDER] = {};
+  int mode[DV_MAX_ORDER] = {};
+  void add(const ModelBox &b, int m) {
+    mode[n] = m;
+    len[n] = b.len[m];
+    vs[n] = b.vs[m];
+    rs[n] = b.rs[m];
+    count *= b.len[m];
+    n++;
+  }
+  // the offset of flat index i is i itself (under view strides vs, or shard strides rs)
+  static bool unit(int n, const int64_t *len, const int64_t *st) {
+    int64_t want = 1;
+    for (int i = 0; i < n; i++) {
+      if (len[i] > 1 && st[i] != want) return false;
+      want *= len[i];
+    }
+    return true;
+  }
+  bool view_unit() const { return unit(n, len, vs); }
+  bool shard_unit() const { return unit(n, len, rs); }
+};
+// dst[voff + offA(a) + offB(b)] = sum_k Q[a + ldq*k] * P[(b % pL) + pLK*(b / pL) + pL*k] (the residual:
+// V[roff + rA(a) + rB(b)] minus the sum), a over group A (the view's fast side), b over group B
+struct ModelPlan {
+  ModelGroup ga, gb;
+  int64_t voff = 0, roff = 0;
+  int64_t ldq = 0, pL = 1, pLK = 0;
+};
+// The second pass of the two-pass residual, view -= model: "V" is the view itself (its offsets in place
+// of the shard's), after the tensor export has filled it.
+inline ModelPlan dv_model_rmw(ModelPlan mp) {
+  for (int i = 0; i < mp.ga.n; i++) mp.ga.rs[i] = mp.ga.vs[i];
+  for (int i = 0; i < mp.gb.n; i++) mp.gb.rs[i] = mp.gb.vs[i];
+  mp.roff = mp.voff;
+  return mp;
+}
+
 }  // namespace ppals

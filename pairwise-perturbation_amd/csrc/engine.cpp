@@ -234,6 +234,7 @@ CpEngine::CpEngine(Ops &ops, Comm &comm, const TensorDesc &V, int R)
     : ops_(ops), comm_(comm), V_(V), N_(V.order), R_(R), P_(comm.size()), rank_(comm.rank()) {
   dist_ = P_ > 1 || (force_comm_path() && !comm.is_self());
   if (R <= 0) throw std::runtime_error("ppals: rank must be positive");
+  residual_form_ = residual_form_env();
   W_.resize(N_);
   gradW_.resize(N_);
   Wprev_.assign(N_, nullptr);
@@ -347,6 +348,8 @@ CpEngine::~CpEngine() {
   ops_.free(test_blkbuf_);
   ops_.free(Mbuf_);
   ops_.free(Qbuf_);
+  ops_.free(xq_);
+  ops_.free(xp_);
   ops_.free(Pbuf_);
   for (auto &l : lay_)
     if (l.owned) ops_.free(l.ptr);
@@ -1812,6 +1815,89 @@ double CpEngine::residual() {
   double h = 0;
   ops_.d2h(&h, scal_, sizeof(double));
   return std::sqrt(h);
+}
+
+int residual_form_env() {
+  const char *v = getenv("PPALS_MODEL_RESIDUAL");
+  if (!v || !*v || !strcmp(v, "fused")) return RESIDUAL_FUSED;
+  if (!strcmp(v, "two_pass")) return RESIDUAL_TWO_PASS;
+  throw std::runtime_error("ppals: PPALS_MODEL_RESIDUAL must be fused or two_pass");
+}
+
+void model_export_run(Ops &ops, ModelExportCall &c, const ModelPlan &mp, const double *Q, const double *P,
+                      int K) {
+  const TensorDesc &V = *c.V;
+  bool two = false;
+  if (c.residual) {
+    const bool exact = V.dtype != F64 || c.a->dtype == DV_F64;  // the export into the view rounds nothing
+    two = exact && c.form == RESIDUAL_TWO_PASS;
+  }
+  if (!two) {
+    ops.model_to_view(mp, Q, P, K, c.residual, c.dst, c.a->dtype, V.data, V.dtype, c.stream);
+    return;
+  }
+  if (!c.exported) {
+    const ViewPlan p = dv_plan(*c.a, V.glens, V.row0, V.llens[0]);
+    if (p.kind != DV_EMPTY) ops.copy_view(p, DV_EXPORT, c.dst, c.a->dtype, V.data, V.dtype, c.stream);
+    c.exported = true;
+  }
+  ops.model_to_view(dv_model_rmw(mp), Q, P, K, true, c.dst, c.a->dtype, c.dst, c.a->dtype, c.stream);
+}
+
+// The model through a view: [[W]] is symmetric in how the modes are grouped, so the
+// grouping follows the VIEW. Group A = the view's fastest modes (by stride) until A reaches the square
+// root of the box, group B = the rest in the shard's order (a residual's V reads run along it when A is
+// not the shard's fast side); Q and P are their Khatri-Rao products, and the kernel stores Q P^T with the
+// lane index along the view's unit-stride run.
+void CpEngine::export_model(const ViewArgs &a, void *dst, bool residual, void *stream) {
+  ModelBox bx;
+  if (!dv_model_box(a, V_.glens, V_.row0, V_.llens[0], &bx)) return;
+  int ord[MAX_ORDER], n = 0;
+  int64_t total = 1;
+  for (int m = 0; m < N_; m++) {
+    total *= bx.len[m];
+    if (bx.len[m] > 1) ord[n++] = m;
+  }
+  std::stable_sort(ord, ord + n, [&](int x, int y) { return bx.vs[x] < bx.vs[y]; });
+  ModelPlan mp;
+  bool inA[MAX_ORDER] = {};
+  for (int i = 0; i < n && (mp.ga.count < 64 || mp.ga.count * mp.ga.count < total); i++) {
+    mp.ga.add(bx, ord[i]);
+    inA[ord[i]] = true;
+  }
+  for (int m = 0; m < N_; m++)
+    if (!inA[m]) mp.gb.add(bx, m);
+  auto refs = [&](const ModelGroup &g, FactorRef *f) {
+    for (int i = 0; i < g.n; i++) {
+      const int m = g.mode[i];
+      f[i].ptr = W_[m] + bx.lo[m];
+      f[i].rows = bx.len[m];
+      f[i].ld = V_.glens[m];
+    }
+  };
+  const int64_t A = mp.ga.count, B = mp.gb.count;
+  if (A * R_ > xq_cap_) {
+    ops_.free(xq_);
+    xq_ = (double *)ops_.alloc(sizeof(double) * A * R_);
+    xq_cap_ = A * R_;
+  }
+  if (B * R_ > xp_cap_) {
+    ops_.free(xp_);
+    xp_ = (double *)ops_.alloc(sizeof(double) * B * R_);
+    xp_cap_ = B * R_;
+  }
+  FactorRef fa[MAX_ORDER], fb[MAX_ORDER];
+  refs(mp.ga, fa);
+  refs(mp.gb, fb);
+  ops_.krp(xq_, fa, mp.ga.n, 0, R_);
+  ops_.krp(xp_, fb, mp.gb.n, 0, R_);
+  mp.voff = bx.voff;
+  mp.roff = bx.roff;
+  mp.ldq = A;
+  mp.pL = B;
+  mp.pLK = 0;
+  ModelExportCall c{&a, &V_, dst, residual, residual_form_, false, stream};
+  model_export_run(ops_, c, mp, xq_, xp_, R_);
 }
 
 // ---------------------------------------------------------------------------- kernel-level access

@@ -35,6 +35,27 @@ inline bool force_comm_path() {
   return v && atoi(v) != 0;
 }
 
+// How a model export forms V - model (ppals_cp/tucker_export_model_device). Fused (the default): V is
+// read inside the model kernel. Two passes: the tensor export into the destination, then destination -=
+// model — possible only where that export rounds nothing (F32 / BF16 storage, or F64 into F64; else the
+// fused form runs). Measured at the headline extents the fused form wins every case;
+// PPALS_MODEL_RESIDUAL=two_pass keeps the other one reachable for that A/B. Read at session creation.
+enum ResidualForm { RESIDUAL_FUSED = 0, RESIDUAL_TWO_PASS = 1 };
+int residual_form_env();
+// the model (or the residual) of the plan through the view: picks the residual's form, and for two
+// passes runs the tensor export of the whole view `a` first (the plan may be one slab of it)
+struct ModelExportCall {
+  const ViewArgs *a;
+  const TensorDesc *V;
+  void *dst;
+  bool residual;
+  int form;          // ResidualForm
+  bool exported = false;  // two passes: the view already holds V
+  void *stream;
+};
+void model_export_run(Ops &ops, ModelExportCall &c, const ModelPlan &mp, const double *Q, const double *P,
+                      int K);
+
 int tensor_create(Ops &ops, Comm &comm, int order, const int64_t *glens, int dtype,
                   TensorDesc *out, std::string *err);
 void tensor_fill_cp(Ops &ops, const TensorDesc &V, int R, const double *Wtrue_flat);
@@ -97,6 +118,10 @@ class CpEngine {
   void sweep_dt(double lambda);
   double gradnorm();  // sqrt(sum_i ||grad_W[i]||^2), als_CP.cxx:174-181; synchronises
   double residual();  // ||V - [[W]]||_F, als_CP.cxx:183-187; synchronises
+  // the model [[W]] (residual: V - [[W]], V as stored) into this rank's rows of a checked export view
+  // (ppals_cp_export_model_device); reads the session, changes nothing of it
+  void export_model(const ViewArgs &a, void *dst, bool residual, void *stream);
+  const TensorDesc &tensor() const { return V_; }
 
   // kernel-level access for parity tests
   int64_t tree_node(const std::string &key, double *out_host);
@@ -305,6 +330,9 @@ class CpEngine {
   double *sendbuf_ = nullptr, *recvbuf_ = nullptr, *gatherbuf_ = nullptr;
   double *Mbuf_ = nullptr;    // PP: M_i^0 + corrections
   double *Qbuf_ = nullptr, *Pbuf_ = nullptr;  // residual KRP operands
+  double *xq_ = nullptr, *xp_ = nullptr;      // model export KRP operands (grow-only, kept)
+  int64_t xq_cap_ = 0, xp_cap_ = 0;
+  int residual_form_ = RESIDUAL_FUSED;        // PPALS_MODEL_RESIDUAL
   // Resident storage orders of the local tensor that the scans may read. [0] is the tensor itself.
   // [1] (if built) lists the right-half modes first, so that contractions of left-half modes are
   // row-contiguous suffix scans too. When the tensor's column strides are not multiples of 128 B

@@ -20,6 +20,7 @@
 #include "kernels_small.hip.h"
 #include "kernels_eig.hip.h"
 #include "kernels_io.hip.h"
+#include "kernels_model.hip.h"
 #include "kernels_bf16.hip.h"
 
 namespace ppals {
@@ -170,6 +171,7 @@ class HipOps : public Ops {
     }
     if (ws_mttv_) hipFree(ws_mttv_);
     if (ws_pack_) hipFree(ws_pack_);
+    if (ws_mv_) hipFree(ws_mv_);
     if (ws_slab_) hipFree(ws_slab_);
     if (ws_krp_) hipFree(ws_krp_);
     if (ws_part_) hipFree(ws_part_);
@@ -620,6 +622,72 @@ class HipOps : public Ops {
     HIP_CHECK(hipStreamWaitEvent(cs, io_ev_out_, 0));
   }
   hipEvent_t io_ev_in_ = nullptr, io_ev_out_ = nullptr;
+
+  // ------------------------------------------------------------------ model through a view
+  template <typename D, typename TV, bool RES>
+  void mv_launch(dim3 grid, D *dst, const TV *V, const double *Q, const double *P, int K,
+                 const ModelPlan &mp, const int64_t *tab, int flags) {
+    const int64_t A = mp.ga.count, B = mp.gb.count;
+    const int64_t *tav = tab, *tar = tab + A, *tbv = tab + 2 * A, *tbr = tab + 2 * A + B;
+    if (K <= 16)
+      hipLaunchKernelGGL((k_model_view<D, TV, RES, 4>), grid, dim3(256), 0, st_, dst, V, Q, P, K, mp,
+                         tav, tar, tbv, tbr, flags);
+    else
+      hipLaunchKernelGGL((k_model_view<D, TV, RES, 16>), grid, dim3(256), 0, st_, dst, V, Q, P, K, mp,
+                         tav, tar, tbv, tbr, flags);
+  }
+  template <typename D>
+  void mv_dispatch(dim3 grid, D *dst, const void *V, int dt, const double *Q, const double *P, int K,
+                   bool residual, const ModelPlan &mp, const int64_t *tab, int flags) {
+    if (!residual)
+      mv_launch<D, float, false>(grid, dst, nullptr, Q, P, K, mp, tab, flags);
+    else if (dt == F32)
+      mv_launch<D, float, true>(grid, dst, (const float *)V, Q, P, K, mp, tab, flags);
+    else if (dt == BF16)
+      mv_launch<D, bf16s, true>(grid, dst, (const bf16s *)V, Q, P, K, mp, tab, flags);
+    else
+      mv_launch<D, double, true>(grid, dst, (const double *)V, Q, P, K, mp, tab, flags);
+  }
+  void model_to_view(const ModelPlan &mp, const double *Q, const double *P, int K, bool residual,
+                     void *view, int vdt, const void *V, int dt, void *caller_stream) override {
+    HIP_CHECK(hipSetDevice(dev_));
+    const int64_t A = mp.ga.count, B = mp.gb.count;
+    if (A <= 0 || B <= 0) return;
+    if (K < 1) throw std::runtime_error("ppals: model_to_view needs K >= 1");
+    if (vdt != DV_F32 && vdt != DV_F64) throw std::runtime_error("ppals: bad model view dtype");
+    const int64_t ntA = (A + MV_TILE - 1) / MV_TILE, ntB = (B + MV_TILE - 1) / MV_TILE;
+    if (ntA > 0x7fffffff) throw std::runtime_error("ppals: model view too wide");
+    // the offset tables of both groups, built on the engine stream (nothing of the caller's is read)
+    int64_t *tab = (int64_t *)ensure(ws_mv_, ws_mv_sz_, sizeof(int64_t) * 2 * (size_t)(A + B));
+    hipLaunchKernelGGL(k_model_offsets, dim3(grid_for(A, 256)), dim3(256), 0, st_, mp.ga, tab, tab + A);
+    hipLaunchKernelGGL(k_model_offsets, dim3(grid_for(B, 256)), dim3(256), 0, st_, mp.gb, tab + 2 * A,
+                       tab + 2 * A + B);
+    HIP_CHECK(hipGetLastError());
+    const int vw = vdt == DV_F32 ? 4 : 2;
+    const bool a_unit = mp.ga.view_unit();
+    bool vec = a_unit && A % vw == 0 && mp.voff % vw == 0 &&
+               ((uintptr_t)view) % 16 == 0;
+    for (int i = 0; i < mp.gb.n; i++)
+      if (mp.gb.len[i] > 1 && mp.gb.vs[i] % vw != 0) vec = false;
+    const int flags = (a_unit ? 1 : 0) | (vec ? 2 : 0) | (mp.ga.shard_unit() ? 4 : 0);
+    // a chip's worth of workgroups; each walks its share of the b tiles with its Q rows in registers
+    const int64_t want = std::max<int64_t>(1, ((int64_t)ncu_ * 8 + ntA - 1) / ntA);
+    const dim3 grid((unsigned)ntA, (unsigned)std::min<int64_t>(std::min<int64_t>(want, ntB), 65535));
+    if (!io_ev_in_) {
+      HIP_CHECK(hipEventCreateWithFlags(&io_ev_in_, hipEventDisableTiming));
+      HIP_CHECK(hipEventCreateWithFlags(&io_ev_out_, hipEventDisableTiming));
+    }
+    hipStream_t cs = (hipStream_t)caller_stream;
+    HIP_CHECK(hipEventRecord(io_ev_in_, cs));  // the view is the caller's once its work so far is done
+    HIP_CHECK(hipStreamWaitEvent(st_, io_ev_in_, 0));
+    if (vdt == DV_F32)
+      mv_dispatch<float>(grid, (float *)view, V, dt, Q, P, K, residual, mp, tab, flags);
+    else
+      mv_dispatch<double>(grid, (double *)view, V, dt, Q, P, K, residual, mp, tab, flags);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(io_ev_out_, st_));  // and the caller's later work waits for the stores
+    HIP_CHECK(hipStreamWaitEvent(cs, io_ev_out_, 0));
+  }
 
   void *try_alloc(size_t bytes) override {
     void *p = nullptr;
@@ -3325,6 +3393,8 @@ class HipOps : public Ops {
   hipStream_t st_ = nullptr;
   hipStream_t st2_ = nullptr;  // the Jacobi of a lazy eigen-step (created on first use)
   void *ws_mttv_ = nullptr;  // partial sums of a j-split k_mttv_l
+  void *ws_mv_ = nullptr;    // offset tables of model_to_view
+  size_t ws_mv_sz_ = 0;
   size_t ws_mttv_sz_ = 0;
   void *ws_pack_ = nullptr, *ws_slab_ = nullptr, *ws_krp_ = nullptr, *ws_part_ = nullptr,
        *ws_small_ = nullptr, *ws_big_ = nullptr, *ws_big2_ = nullptr;

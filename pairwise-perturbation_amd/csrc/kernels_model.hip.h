@@ -1,0 +1,214 @@
+// kernels_model.hip.h — a decomposition's model, or its residual V - model, stored through a strided
+// device view (ppals_cp_export_model_device / ppals_tucker_export_model_device, include/ppals.h).
+//
+// One kernel family: a thin-K product stored through a view (ModelPlan, device_view.h):
+//   dst[voff + offA(a) + offB(b)] = sum_k Q[a + ldq*k] * P[(b % pL) + pLK*(b / pL) + pL*k]
+// or, for the residual, V[roff + rA(a) + rB(b)] minus that sum, V the resident shard as stored.
+// The products and sums are fp64 on v_mfma_f64_16x16x4_f64 and each element is rounded once to the
+// destination type. A is the view's fast side: its modes are the view's unit-stride run, so a wave's
+// stores walk consecutive addresses.
+//
+// Tiling: a workgroup owns 64 values of a (its Q rows stay in registers when K <= 4 * MAXRB) and walks
+// 64 x 64 tiles along b. Wave w multiplies b rows [16w, 16w + 16) of the tile against the 4 column
+// blocks of 16 a: the f64 MFMA layout (A operand = P: row lane&15, k lane>>4; B operand = Q: k lane>>4,
+// column lane&15; D: column lane&15, row (lane>>4) + 4 reg) puts the lane's results at
+// (b = 16w + (lane>>4) + 4 reg, a = 16t + lane&15). The tile goes through LDS ([b][a], fp64, padded
+// row) and leaves with the lane index along a: 16-byte stores when the view allows them. The residual
+// reads V along a when the shard is contiguous there, otherwise along b (lane index along b, into the
+// LDS image) before the store pass — the two sides of the tile are then each accessed coalesced.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+#include "bf16.h"
+#include "device_view.h"
+
+namespace ppals {
+
+typedef double mv_f64x4 __attribute__((ext_vector_type(4)));
+
+constexpr int MV_TILE = 64;
+
+// ov[i] / orr[i] = view / shard offset of flat index i of a mode group (first listed mode fastest)
+__global__ __launch_bounds__(256) void k_model_offsets(ModelGroup g, int64_t *__restrict__ ov,
+                                                       int64_t *__restrict__ orr) {
+  const int64_t nth = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < g.count; e += nth) {
+    int64_t idx = e, v = 0, r = 0;
+#pragma unroll
+    for (int m = 0; m < DV_MAX_ORDER; m++)
+      if (m < g.n) {
+        const int64_t q = idx / g.len[m], c = idx - q * g.len[m];
+        v += c * g.vs[m];
+        r += c * g.rs[m];
+        idx = q;
+      }
+    ov[e] = v;
+    orr[e] = r;
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ double mv_load(const T *p) {
+  return (double)*p;
+}
+template <>
+__device__ __forceinline__ double mv_load<bf16s>(const bf16s *p) {
+  return (double)__uint_as_float((uint32_t)p->u << 16);
+}
+
+template <typename T>
+struct alignas(16) mv_vec {
+  T v[16 / sizeof(T)];
+};
+
+// D: destination element type (float / double); TV: the shard's storage type (read by the residual
+// only); RES: the residual; MAXRB: 4-wide contraction steps held in registers (more: Q is reloaded per
+// chunk of MAXRB steps). flags: bit 0 the view is unit-stride over A (offA(a) = a); bit 1 16-byte
+// stores (bit 0, and A, voff and every offB a multiple of the vector, dst aligned); bit 2 the shard is
+// contiguous over A (rA(a) = a: the residual reads V in the store pass). V may be dst itself (the second
+// pass of the two-pass residual, dst -= model: shard offsets = view offsets): every element is read and
+// then written by the same thread, or read before and written after a barrier.
+template <typename D, typename TV, bool RES, int MAXRB>
+__global__ __launch_bounds__(256) void k_model_view(D *dst, const TV *V,
+                                                    const double *__restrict__ Q,
+                                                    const double *__restrict__ P, int K, ModelPlan mp,
+                                                    const int64_t *__restrict__ tav,
+                                                    const int64_t *__restrict__ tar,
+                                                    const int64_t *__restrict__ tbv,
+                                                    const int64_t *__restrict__ tbr, int flags) {
+  __shared__ double img[MV_TILE][MV_TILE + 1];
+  __shared__ int64_t sav[MV_TILE], sar[MV_TILE], sbv[MV_TILE], sbr[MV_TILE];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane >> 4, j16 = lane & 15;
+  const int64_t A = mp.ga.count, B = mp.gb.count, a0 = (int64_t)blockIdx.x * MV_TILE;
+  const int na = (int)min((int64_t)MV_TILE, A - a0);
+  const int RB = (K + 3) / 4;
+  const bool a_unit = flags & 1, vec_st = flags & 2, v_along_a = flags & 4;
+  const int64_t nbt = (B + MV_TILE - 1) / MV_TILE;
+
+  // q[t][rb] = Q[a0 + 16t + j16, 4 (c0 + rb) + g] of the rank chunk that starts at step c0 (0 outside)
+  double q[4][MAXRB];
+#define PPALS_MV_LOAD_Q(c0_)                                                     \
+  _Pragma("unroll") for (int t = 0; t < 4; t++) {                                \
+    const int64_t a_ = a0 + 16 * t + j16;                                        \
+    _Pragma("unroll") for (int rb = 0; rb < MAXRB; rb++) {                       \
+      const int k_ = 4 * ((c0_) + rb) + g;                                       \
+      q[t][rb] = (a_ < A && k_ < K) ? Q[a_ + mp.ldq * (int64_t)k_] : 0.0;        \
+    }                                                                            \
+  }
+  if (RB <= MAXRB) PPALS_MV_LOAD_Q(0);
+  if (threadIdx.x < MV_TILE) {
+    const int i = threadIdx.x;
+    sav[i] = i < na ? tav[a0 + i] : 0;
+    sar[i] = i < na ? tar[a0 + i] : 0;
+  }
+  // pn[rb] = P[b, 4 rb + g] of this lane's row b = 16 wave + j16 of tile tb_ (0 outside); loaded a tile
+  // ahead, with the tile's b offsets (threads 64..127), so that their latency hides behind a tile's work
+#define PPALS_MV_LOAD_P(tb_, c0_, pn_)                                                   \
+  {                                                                                      \
+    const int64_t b_ = (tb_) * MV_TILE + 16 * wave + j16;                                \
+    const bool ok_ = (tb_) < nbt && b_ < B;                                              \
+    const int64_t q_ = ok_ ? b_ / mp.pL : 0;                                             \
+    const double *pr_ = P + (ok_ ? (b_ - q_ * mp.pL) + mp.pLK * q_ : 0);                 \
+    _Pragma("unroll") for (int rb = 0; rb < MAXRB; rb++) {                               \
+      const int k_ = 4 * ((c0_) + rb) + g;                                               \
+      pn_[rb] = (ok_ && k_ < K) ? pr_[mp.pL * (int64_t)k_] : 0.0;                        \
+    }                                                                                    \
+  }
+  double pn[MAXRB];
+  int64_t nbv = 0, nbr = 0;
+  const int ib = (int)threadIdx.x - MV_TILE;  // threads 64..127: the b offsets
+  auto load_b = [&](int64_t tb_) {
+    const int64_t bb = tb_ * MV_TILE + ib;
+    const bool ok = ib >= 0 && ib < MV_TILE && tb_ < nbt && bb < B;
+    nbv = ok ? tbv[bb] : 0;
+    nbr = ok ? tbr[bb] : 0;
+  };
+  if (RB <= MAXRB) PPALS_MV_LOAD_P((int64_t)blockIdx.y, 0, pn);
+  load_b(blockIdx.y);
+
+  for (int64_t tb = blockIdx.y; tb < nbt; tb += gridDim.y) {
+    const int64_t b0 = tb * MV_TILE;
+    const int nb = (int)min((int64_t)MV_TILE, B - b0);
+    if (ib >= 0 && ib < MV_TILE) {
+      sbv[ib] = nbv;
+      sbr[ib] = nbr;
+    }
+    load_b(tb + gridDim.y);
+    mv_f64x4 d[4];
+#pragma unroll
+    for (int t = 0; t < 4; t++) d[t] = mv_f64x4{0.0, 0.0, 0.0, 0.0};
+    if (RB <= MAXRB) {
+      double pa[MAXRB];
+#pragma unroll
+      for (int rb = 0; rb < MAXRB; rb++) pa[rb] = pn[rb];
+      PPALS_MV_LOAD_P(tb + gridDim.y, 0, pn);
+#pragma unroll
+      for (int rb = 0; rb < MAXRB; rb++) {
+        if (rb < RB) {
+#pragma unroll
+          for (int t = 0; t < 4; t++)
+            d[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[rb], q[t][rb], d[t], 0, 0, 0);
+        }
+      }
+    } else {  // more rank steps than registers: Q and P chunk by chunk
+      for (int c0 = 0; c0 < RB; c0 += MAXRB) {
+        PPALS_MV_LOAD_Q(c0);
+        double pa[MAXRB];
+        PPALS_MV_LOAD_P(tb, c0, pa);
+#pragma unroll
+        for (int rb = 0; rb < MAXRB; rb++) {
+          if (c0 + rb < RB) {
+#pragma unroll
+            for (int t = 0; t < 4; t++)
+              d[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[rb], q[t][rb], d[t], 0, 0, 0);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < 4; t++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) img[16 * wave + g + 4 * r][16 * t + j16] = d[t][r];
+    __syncthreads();
+    if (RES && !v_along_a) {  // V - model with the lane index along b
+      for (int i = 0; i < MV_TILE / 4; i++) {
+        const int al = wave + 4 * i, bl = lane;
+        if (al < na && bl < nb) img[bl][al] = mv_load(V + (mp.roff + sar[al] + sbr[bl])) - img[bl][al];
+      }
+      __syncthreads();
+    }
+    // the store pass, lane index along a
+    if (vec_st) {
+      constexpr int VW = 16 / sizeof(D), TPR = MV_TILE / VW, RPP = 256 / TPR;
+      const int al = (threadIdx.x % TPR) * VW;
+      for (int bl = threadIdx.x / TPR; bl < nb; bl += RPP) {
+        if (al < na) {
+          mv_vec<D> o;
+#pragma unroll
+          for (int e = 0; e < VW; e++) {
+            double x = img[bl][al + e];
+            if (RES && v_along_a) x = mv_load(V + (mp.roff + sbr[bl] + a0 + al + e)) - x;
+            o.v[e] = (D)x;
+          }
+          *reinterpret_cast<mv_vec<D> *>(dst + (mp.voff + sbv[bl] + a0 + al)) = o;
+        }
+      }
+    } else {
+      const int al = lane;
+      for (int bl = wave; bl < nb; bl += 4) {
+        if (al < na) {
+          double x = img[bl][al];
+          if (RES && v_along_a) x = mv_load(V + (mp.roff + sbr[bl] + sar[al])) - x;
+          dst[mp.voff + sbv[bl] + (a_unit ? a0 + al : sav[al])] = (D)x;
+        }
+      }
+    }
+    __syncthreads();  // the image and the b offsets are rewritten by the next tile
+  }
+#undef PPALS_MV_LOAD_Q
+#undef PPALS_MV_LOAD_P
+}
+
+}  // namespace ppals

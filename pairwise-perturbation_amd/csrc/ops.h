@@ -151,6 +151,15 @@ class Ops {
                          void * /*V*/, int /*dt*/, void * /*caller_stream*/) {
     throw Unsupported("ppals: this back end has no device views");
   }
+  // A thin-K product stored through a view (the model export, device_view.h ModelPlan):
+  //   view[voff + offA(a) + offB(b)] = sum_{k<K} Q[a + ldq*k] * P[(b % pL) + pLK*(b / pL) + pL*k]
+  // in fp64, rounded once to vdt (F32 / F64). residual: V[roff + rA(a) + rB(b)] - the sum instead, V
+  // the shard (storage type dt). Ordered on `caller_stream` as copy_view; the host does not block.
+  virtual void model_to_view(const ModelPlan & /*mp*/, const double * /*Q*/, const double * /*P*/,
+                             int /*K*/, bool /*residual*/, void * /*view*/, int /*vdt*/,
+                             const void * /*V*/, int /*dt*/, void * /*caller_stream*/) {
+    throw Unsupported("ppals: this back end has no device views");
+  }
 
   // ---- Khatri-Rao product, plain: out[j + J*c] = prod_f W_f[j_f + ld_f*(col0+c)], fp64 ----
   virtual void krp(double *out, const FactorRef *f, int nf, int col0, int ncols) = 0;

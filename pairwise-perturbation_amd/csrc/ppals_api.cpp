@@ -267,17 +267,17 @@ int ppals_tensor_norm(ppals_tensor *t, double *out) {
 
 // ------------------------------------------------------------------ device views
 // every check of ppals_tensor_check_device_view; on success *a holds the resolved view
-static int check_view(ppals_tensor *t, int dir, const void *ptr, int dtype, const int64_t *box_lo,
-                      const int64_t *box_len, const int64_t *strides, ViewArgs *a) {
-  const char *what = dir == DV_EXPORT ? "ppals_tensor_export_device: " : "ppals_tensor_import_device: ";
-  if (!t || !t->ctx || !ptr) return fail(PPALS_ERR_ARG, "NULL tensor or pointer");
+// (`what` names the entry point in the messages; the model exports check their views here too)
+static int check_desc_view(ppals_ctx *ctx, const TensorDesc &d, const char *what, int dir,
+                           const void *ptr, int dtype, const int64_t *box_lo, const int64_t *box_len,
+                           const int64_t *strides, ViewArgs *a) {
   std::string err;
-  if (!dv_check_args(dir, t->d.order, t->d.glens, dtype, box_lo, box_len, strides, a, &err)) {
+  if (!dv_check_args(dir, d.order, d.glens, dtype, box_lo, box_len, strides, a, &err)) {
     g_err = what + err;
     return PPALS_ERR_ARG;
   }
   Ops::PtrInfo info;
-  if (!t->ctx->ops->device_ptr_info(ptr, &info, &err) || !info.is_device) {
+  if (!ctx->ops->device_ptr_info(ptr, &info, &err) || !info.is_device) {
     g_err = std::string(what) + "the pointer is not device memory of the context's device (" +
             (err.empty() ? "host, pinned host or managed memory" : err) +
             "); a torch tensor must live on that device, and torch must be imported before "
@@ -291,6 +291,13 @@ static int check_view(ppals_tensor *t, int dir, const void *ptr, int dtype, cons
     return PPALS_ERR_ARG;
   }
   return PPALS_OK;
+}
+static int check_view(ppals_tensor *t, int dir, const void *ptr, int dtype, const int64_t *box_lo,
+                      const int64_t *box_len, const int64_t *strides, ViewArgs *a) {
+  if (!t || !t->ctx || !ptr) return fail(PPALS_ERR_ARG, "NULL tensor or pointer");
+  return check_desc_view(t->ctx, t->d,
+                         dir == DV_EXPORT ? "ppals_tensor_export_device: " : "ppals_tensor_import_device: ",
+                         dir, ptr, dtype, box_lo, box_len, strides, a);
 }
 static int copy_device_view(ppals_tensor *t, int dir, void *ptr, int dtype, const int64_t *box_lo,
                             const int64_t *box_len, const int64_t *strides, void *stream) {
@@ -416,6 +423,42 @@ int ppals_cp_residual(ppals_cp *s, double *out) {
   if (!s || !s->eng || !out) return fail(PPALS_ERR_ARG, "NULL argument");
   API_BEGIN
   *out = s->eng->residual();
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+// the model exports: every check of ppals_tensor_export_device and of `what`, nothing launched
+static int check_model_view(ppals_ctx *ctx, const TensorDesc &d, const char *what, int kind, void *dst,
+                            int dst_dtype, const int64_t *box_lo, const int64_t *box_len,
+                            const int64_t *strides, ViewArgs *a) {
+  if (!dst) return fail(PPALS_ERR_ARG, "NULL pointer");
+  if (kind != PPALS_MODEL && kind != PPALS_RESIDUAL) {
+    g_err = std::string(what) + "`what` must be PPALS_MODEL (0) or PPALS_RESIDUAL (1)";
+    return PPALS_ERR_ARG;
+  }
+  return check_desc_view(ctx, d, what, DV_EXPORT, dst, dst_dtype, box_lo, box_len, strides, a);
+}
+int ppals_cp_export_model_device(ppals_cp *s, int what, void *dst, int dst_dtype, const int64_t *box_lo,
+                                 const int64_t *box_len, const int64_t *strides, void *stream) {
+  if (!s || !s->eng) return fail(PPALS_ERR_ARG, "NULL session");
+  API_BEGIN
+  ViewArgs a;
+  const int rc = check_model_view(s->ctx, s->eng->tensor(), "ppals_cp_export_model_device: ", what, dst,
+                                  dst_dtype, box_lo, box_len, strides, &a);
+  if (rc != PPALS_OK) return rc;
+  s->eng->export_model(a, dst, what == PPALS_RESIDUAL, stream);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_tucker_export_model_device(ppals_tucker *s, int what, void *dst, int dst_dtype,
+                                     const int64_t *box_lo, const int64_t *box_len,
+                                     const int64_t *strides, void *stream) {
+  if (!s || !s->eng) return fail(PPALS_ERR_ARG, "NULL session");
+  API_BEGIN
+  ViewArgs a;
+  const int rc = check_model_view(s->ctx, s->eng->tensor(), "ppals_tucker_export_model_device: ", what,
+                                  dst, dst_dtype, box_lo, box_len, strides, &a);
+  if (rc != PPALS_OK) return rc;
+  s->eng->export_model(a, dst, what == PPALS_RESIDUAL, stream);
   return PPALS_OK;
   API_END(PPALS_ERR_HIP)
 }

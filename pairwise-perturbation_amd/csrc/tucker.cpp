@@ -24,6 +24,7 @@ TuckerEngine::TuckerEngine(Ops &ops, Comm &comm, const TensorDesc &V, const int 
   P_ = comm.size();
   dist_ = P_ > 1 || (force_comm_path() && !comm.is_self());
   rank_ = comm.rank();
+  residual_form_ = residual_form_env();
   eig_base_ = ops_.eig_session_new();  // this session's warm-start slots: base + {i, 8 + i, 16 + i}
   // (the back end sets up what lazy eigen-steps need now, not inside the first sweep)
   if (!dist_)
@@ -168,6 +169,9 @@ TuckerEngine::~TuckerEngine() {
   ops_.free(Yacc_);
   ops_.free(chain_[0]);
   ops_.free(chain_[1]);
+  ops_.free(xwt_);
+  ops_.free(xz_[0]);
+  ops_.free(xz_[1]);
   ops_.free(VT_);
   ops_.free(VT2_);
   ops_.free(ms3_X_);
@@ -560,6 +564,100 @@ void TuckerEngine::get_factors(double *Wflat, double *core) {
     }
   }
   if (core) ops_.d2h(core, core_, sizeof(double) * ncore_);
+}
+
+// The model through a view: f = the view's unit-stride mode (its smallest stride),
+// Z = core x_{i != f} W_i (the box's rows of each W_i) in fp64 by the mode products of the sweeps, and the
+// kernel stores W_f Z^T with the lane index along mode f. Z and the intermediates of its chain stay within
+// two buffers of 256 MB: the box is cut into slabs along the view's slowest mode s, which the chain
+// expands first, so that every intermediate scales with the slab (a single row of s that alone needs
+// more gets buffers of its size). The buffers and the transposed factors are kept for the session's
+// next export (freeing them would wait for the device).
+void TuckerEngine::export_model(const ViewArgs &a, void *dst, bool residual, void *stream) {
+  finalize_rotations();  // (the path of get_factors: deferred checks settled, pending rotations applied)
+  ModelBox bx;
+  if (!dv_model_box(a, V_.glens, V_.row0, V_.llens[0], &bx)) return;
+  int f = -1, s = -1;
+  for (int m = 0; m < N_; m++)
+    if (bx.len[m] > 1 && (f < 0 || bx.vs[m] < bx.vs[f])) f = m;
+  if (f < 0) f = 0;
+  for (int m = 0; m < N_; m++)
+    if (m != f && bx.len[m] > 1 && (s < 0 || bx.vs[m] > bx.vs[s])) s = m;
+  std::vector<int> chain;
+  if (s >= 0) chain.push_back(s);
+  for (int m = 0; m < N_; m++)
+    if (m != f && m != s) chain.push_back(m);
+  // W_m^T (r_m x s_m) of the chain's modes, at offsets in mode order (mode f's slot stays unused)
+  int64_t nwt = 0;
+  for (int m = 0; m < N_; m++) nwt += V_.glens[m] * r_[m];
+  if (nwt > xwt_cap_) {
+    ops_.free(xwt_);
+    xwt_ = (double *)ops_.alloc(sizeof(double) * nwt);
+    xwt_cap_ = nwt;
+  }
+  int64_t off = 0;
+  for (int m = 0; m < N_; off += V_.glens[m] * r_[m], m++)
+    if (m != f) ops_.transpose2d(W_[m], F64, V_.glens[m], r_[m], xwt_ + off);
+  // the largest intermediate of the chain per row of the slab mode, and the slab that fits
+  constexpr int64_t budget = int64_t(1) << 25;  // doubles per buffer (256 MB)
+  std::vector<int64_t> dims(r_.begin(), r_.end());
+  int64_t unit = 1;
+  for (int m : chain) {
+    dims[m] = m == s ? 1 : bx.len[m];
+    int64_t e = 1;
+    for (int q = 0; q < N_; q++) e *= dims[q];
+    unit = std::max(unit, e);
+  }
+  const int64_t ns = s >= 0 ? bx.len[s] : 1;
+  const int64_t cs = std::max<int64_t>(1, std::min(ns, budget / unit));
+  if (unit * cs > xz_cap_) {
+    ops_.free(xz_[0]);
+    ops_.free(xz_[1]);
+    xz_[0] = (double *)ops_.alloc(sizeof(double) * unit * cs);
+    xz_[1] = (double *)ops_.alloc(sizeof(double) * unit * cs);
+    xz_cap_ = unit * cs;
+  }
+  ModelExportCall call{&a, &V_, dst, residual, residual_form_, false, stream};
+  for (int64_t c = 0; c < ns; c += cs) {
+    ModelBox sb = bx;
+    if (s >= 0) {
+      sb.lo[s] += c;
+      sb.len[s] = std::min(cs, ns - c);
+      sb.voff += c * bx.vs[s];
+      sb.roff += c * bx.rs[s];
+    }
+    export_slab(sb, f, chain, call);
+  }
+}
+
+void TuckerEngine::export_slab(const ModelBox &bx, int f, const std::vector<int> &chain,
+                               ModelExportCall &call) {
+  std::vector<int64_t> dims(r_.begin(), r_.end()), wtoff(N_, 0);
+  for (int m = 1; m < N_; m++) wtoff[m] = wtoff[m - 1] + V_.glens[m - 1] * r_[m - 1];
+  const double *cur = core_;
+  int pi = 0;
+  for (int m : chain) {  // expansion of mode m: out[l, a, t] = sum_k cur[l, k, t] * W_m[lo_m + a, k]
+    int64_t L = 1, T = 1;
+    for (int q = 0; q < m; q++) L *= dims[q];
+    for (int q = m + 1; q < N_; q++) T *= dims[q];
+    ops_.ttm_keep(cur, F64, L, r_[m], T, xwt_ + wtoff[m] + r_[m] * bx.lo[m], r_[m], (int)bx.len[m],
+                  xz_[pi]);
+    dims[m] = bx.len[m];
+    cur = xz_[pi];
+    pi ^= 1;
+  }
+  // Z = cur: [modes before f | r_f | modes after f]; P[b, k] with b over the modes other than f
+  ModelPlan mp;
+  mp.ga.add(bx, f);
+  for (int m = 0; m < N_; m++)
+    if (m != f) mp.gb.add(bx, m);
+  mp.voff = bx.voff;
+  mp.roff = bx.roff;
+  mp.ldq = V_.glens[f];
+  mp.pL = 1;
+  for (int q = 0; q < f; q++) mp.pL *= bx.len[q];
+  mp.pLK = mp.pL * r_[f];
+  model_export_run(ops_, call, mp, W_[f] + bx.lo[f], cur, r_[f]);
 }
 
 // hosvd (als_Tucker.cxx:12-70): W_i = leading eigenvectors of the Gram of the mode-i unfolding of

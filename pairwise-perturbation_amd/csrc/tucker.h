@@ -20,6 +20,10 @@ class TuckerEngine {
   void sweep_dt();                       // als_Tucker.cxx:340-408
   void settle() { settle_all(); }        // every eigen-step behind the current factors is a checked one
   int rollbacks() const { return defer_rollbacks_; }
+  // core x_i W_i (residual: V - that, V as stored) into this rank's rows of a checked export view
+  // (ppals_tucker_export_model_device), from the factors and core get_factors would return
+  void export_model(const ViewArgs &a, void *dst, bool residual, void *stream);
+  const TensorDesc &tensor() const { return V_; }
   int run_dt(const CpOpts &o, int *iters);  // alsTucker_DT, als_Tucker.cxx:240-424
   int run_pp(const CpOpts &o, int *iters);  // alsTucker_PP, als_Tucker.cxx:906-962
 
@@ -133,6 +137,12 @@ class TuckerEngine {
   ModeNorms read_norms(bool dt_phase);
   void dt_sub(RunReport &rep, const CpOpts &o, double tol_init, double &diffnorm, int &iter);
   void pp_sub(RunReport &rep, const CpOpts &o, double tol_init, double &diffnorm, int &iter);
+  // model export: the transposed factors and the ping-pong buffers of Z = core x_{i != f} W_i
+  void export_slab(const ModelBox &bx, int f, const std::vector<int> &chain, ModelExportCall &call);
+  // (kept for the session's next export: freeing them would wait for the device)
+  double *xwt_ = nullptr, *xz_[2] = {nullptr, nullptr};
+  int residual_form_ = RESIDUAL_FUSED;  // PPALS_MODEL_RESIDUAL
+  int64_t xwt_cap_ = 0, xz_cap_ = 0;
   double *Yfull_ = nullptr, *gather_ = nullptr;
   int64_t yfull_cap_ = 0, gather_cap_ = 0;
 };

@@ -56,8 +56,9 @@ EXPORTS = [
     "ppals_tucker_destroy", "ppals_tucker_set_factors", "ppals_tucker_get_factors",
     "ppals_tucker_set_core",
     "ppals_tucker_hosvd", "ppals_tucker_ttmc", "ppals_tucker_sweeps_dt", "ppals_tucker_dt",
-    "ppals_tucker_pp",
+    "ppals_tucker_pp", "ppals_cp_export_model_device", "ppals_tucker_export_model_device",
 ]
+MODEL, RESIDUAL = 0, 1  # PPALS_MODEL / PPALS_RESIDUAL
 
 
 def lib(path=None):
@@ -346,8 +347,40 @@ def _opts(tol=0.0, timelimit=5e3, maxiter=0, lam=0.0, resprint=10, bench=0, tol_
                  csv.encode() if csv else None, csv_append, verbose, update_percentage)
 
 
-class CP:
+class _ModelExport:
+    """the fitted model (or V - model) into device memory; the session's class names the entry point"""
+    _export_fn = None
+
+    def export_model_device(self, ptr, dtype, shape, strides, lo=None, residual=False, stream=0):
+        """raw ppals_*_export_model_device: this rank's rows of the box at lo of the model (residual:
+        V - model) into the view at ptr (F32 / F64, strides in elements)"""
+        blo, blen = Tensor._box(self, shape, lo)
+        st = (C.c_int64 * len(self.lens))(*[int(x) for x in strides])
+        _check(getattr(lib(), self._export_fn)(self._h, RESIDUAL if residual else MODEL,
+                                               C.c_void_p(int(ptr)), int(dtype), blo, blen, st,
+                                               C.c_void_p(int(stream or 0))))
+        return self
+
+    def export_model_torch(self, out, residual=False, lo=None, stream=None):
+        """the model (residual: V - model) of the box at lo (shape out.shape) into the torch tensor out
+        (f32 / f64, any strides that do not overlap), this rank's rows, ordered on `stream` (default:
+        torch's current stream); other elements of out are left alone and the host does not wait"""
+        torch = _torch()
+        ptr, code, shape, strides = self.V._torch_view(out, (torch.float32, torch.float64))
+        return self.export_model_device(ptr, code, shape, strides, lo, residual, Tensor._stream(stream))
+
+    def model_to_torch(self, dtype=None, residual=False):
+        """the model (residual: V - model) as a new torch tensor on the context's device (this rank's
+        rows; zeros elsewhere), ordered on torch's current stream"""
+        torch = _torch()
+        out = torch.zeros(self.lens, dtype=dtype or torch.float32, device=f"cuda:{self.ctx.device}")
+        self.export_model_torch(out, residual=residual)
+        return out
+
+
+class CP(_ModelExport):
     """a CP-ALS session: factors, Grams and dimension-tree caches resident in HBM"""
+    _export_fn = "ppals_cp_export_model_device"
 
     def __init__(self, ctx, V, R):
         self.ctx, self.V, self.R = ctx, V, R
@@ -482,7 +515,9 @@ class CP:
             pass
 
 
-class Tucker:
+class Tucker(_ModelExport):
+    _export_fn = "ppals_tucker_export_model_device"
+
     def __init__(self, ctx, V, ranks):
         self.ctx, self.V = ctx, V
         self.lens, self.ranks = V.lens, [int(r) for r in ranks]
