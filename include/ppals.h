@@ -40,6 +40,7 @@ extern "C" {
 typedef struct ppals_ctx ppals_ctx;       /* device, stream, workspaces, communicator */
 typedef struct ppals_tensor ppals_tensor; /* the (local shard of the) dense input tensor in HBM */
 typedef struct ppals_cp ppals_cp;         /* a CP-ALS session: factors, Grams, tree caches in HBM */
+typedef struct ppals_cp_multi ppals_cp_multi; /* several CP-ALS starts sharing the tensor scans */
 typedef struct ppals_tucker ppals_tucker; /* a Tucker-HOOI session */
 
 const char *ppals_last_error(void);
@@ -238,6 +239,45 @@ int ppals_cpd_als(ppals_cp *s, int optimizer, const ppals_cp_opts *o, double *sw
 #define PPALS_OPT_MSDT_LR 4
 int ppals_cpd_als_lr(ppals_cp *s, int optimizer, int update_rank, int randomsvd,
                      const ppals_cp_opts *o, double *sweeps, int *iters);
+
+/* ---- multi-start CP sessions (no counterpart in the reference, whose job scripts loop over seeds) ----
+ * CP-ALS finds local minima, so one runs several initialisations and keeps the best. A multi-start
+ * session sweeps `nstarts` independent rank-R models of ONE tensor together: every contraction of a
+ * sweep (the tensor scans above all: HBM-bound, 5 flop/B at R = 10) runs once on nstarts * R columns,
+ * and only the R x R normal equations are solved start by start — all of them in one launch. Start b
+ * evolves exactly as an ordinary session does under ppals_cpd_als with PPALS_OPT_SIMPLE from the same
+ * factors: cyclic mode updates 0..N-1, no Normalize (one scalar per mode would couple the starts).
+ * nstarts in [1, 32], R * nstarts <= 128, any storage type a CP session takes (a bf16 tensor is
+ * scanned in passes of 16 columns, so above 16 columns it gains nothing over separate sessions);
+ * one rank only: a context with more ranks gets PPALS_ERR_UNSUPPORTED. Every bad argument is refused
+ * with PPALS_ERR_ARG and a message before anything is launched. */
+#define PPALS_MULTI_MAX_STARTS 32
+#define PPALS_MULTI_MAX_COLUMNS 128
+int ppals_cp_multi_create(ppals_ctx *ctx, ppals_tensor *V, int R, int nstarts, ppals_cp_multi **out);
+void ppals_cp_multi_destroy(ppals_cp_multi *s);
+/* one start's factors (and gradients) in the Wflat layout of ppals_cp_set_factors; start = -1: all
+ * starts, one such block after the other */
+int ppals_cp_multi_set_factors(ppals_cp_multi *s, int start, const double *Wflat,
+                               const double *gradWflat /*may be NULL*/);
+int ppals_cp_multi_get_factors(ppals_cp_multi *s, int start, double *Wflat /*may be NULL*/,
+                               double *gradWflat /*may be NULL*/);
+/* as ppals_cp_set_schedule (default PPALS_SCHEDULE_MSDT) */
+int ppals_cp_multi_set_schedule(ppals_cp_multi *s, int schedule);
+/* n sweeps of N mode updates each, enqueued asynchronously like ppals_cp_sweeps_dt */
+int ppals_cp_multi_sweeps(ppals_cp_multi *s, int n, double lambda);
+/* out[nstarts]: per start what ppals_cp_residual / ppals_cp_gradnorm return for that model (the
+ * residuals take one streaming pass over the tensor per start) */
+int ppals_cp_multi_residuals(ppals_cp_multi *s, double *out);
+int ppals_cp_multi_gradnorms(ppals_cp_multi *s, double *out);
+/* Sweeps until o->maxiter sweeps, o->timelimit seconds, or the gradient norm of the best start (the
+ * one with the smallest residual) is below o->tol; looks every o->resprint sweeps. Uses tol,
+ * timelimit, maxiter, lambda and resprint of the options and ignores the rest. *sweeps = sweeps run,
+ * *best = the best start at the last look. Returns 1 if it stopped before maxiter, 0 if not. */
+int ppals_cp_multi_run(ppals_cp_multi *s, const ppals_cp_opts *o, int *sweeps, int *best);
+/* Start `start`'s factors and gradients, device to device, into an ordinary session of the same
+ * context, tensor and R; on `dst` the effect is that of ppals_cp_set_factors (caches dropped, Grams
+ * refreshed): the winner goes on there with Normalize, PP, the drivers and the model export. */
+int ppals_cp_multi_take(ppals_cp_multi *s, int start, ppals_cp *dst);
 
 /* ---- Tucker sessions (als_Tucker.h) ---- */
 int ppals_tucker_create(ppals_ctx *ctx, ppals_tensor *V, const int *ranks, ppals_tucker **out);

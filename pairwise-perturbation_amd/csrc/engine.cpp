@@ -230,10 +230,13 @@ double tensor_norm(Ops &ops, Comm &comm, const TensorDesc &V) {
 }
 
 // ============================================================================ CpEngine
-CpEngine::CpEngine(Ops &ops, Comm &comm, const TensorDesc &V, int R)
-    : ops_(ops), comm_(comm), V_(V), N_(V.order), R_(R), P_(comm.size()), rank_(comm.rank()) {
+CpEngine::CpEngine(Ops &ops, Comm &comm, const TensorDesc &V, int R, int nstarts, bool multi)
+    : ops_(ops), comm_(comm), V_(V), N_(V.order), R_(R * nstarts), P_(comm.size()), rank_(comm.rank()),
+      K_(nstarts), Rs_(R), multi_(multi || nstarts > 1) {
   dist_ = P_ > 1 || (force_comm_path() && !comm.is_self());
   if (R <= 0) throw std::runtime_error("ppals: rank must be positive");
+  if (nstarts <= 0) throw std::runtime_error("ppals: the number of starts must be positive");
+  if (multi_ && dist_) throw Unsupported("ppals: a multi-start session runs on one rank");
   residual_form_ = residual_form_env();
   W_.resize(N_);
   gradW_.resize(N_);
@@ -254,9 +257,9 @@ CpEngine::CpEngine(Ops &ops, Comm &comm, const TensorDesc &V, int R)
   G_ = (double *)ops_.alloc(sizeof(double) * N_ * R_ * R_);
   S_ = (double *)ops_.alloc(sizeof(double) * R_ * R_);
   Sinv_ = (double *)ops_.alloc(sizeof(double) * R_ * R_);
-  gradsq_ = (double *)ops_.alloc(sizeof(double) * MAX_ORDER);
+  gradsq_ = (double *)ops_.alloc(sizeof(double) * MAX_ORDER * K_);
   scal_ = (double *)ops_.alloc(sizeof(double) * 4 * MAX_ORDER);
-  ops_.zero(gradsq_, sizeof(double) * MAX_ORDER);
+  ops_.zero(gradsq_, sizeof(double) * MAX_ORDER * K_);
   if (dist_) {
     size_t n = sizeof(double) * (size_t)maxblk_ * P_ * R_;
     sendbuf_ = (double *)ops_.alloc(n);
@@ -626,11 +629,18 @@ void CpEngine::compute_node(int idx) {
 }
 
 void CpEngine::refresh_grams() {
+  if (multi_) {  // the diagonal blocks only: Gram (start b, mode i) at G_ + (b N + i) Rs^2
+    for (int i = 0; i < N_; i++)
+      ops_.gram_batched(W_[i], V_.glens[i], V_.glens[i], Rs_, K_, G_ + (size_t)i * Rs_ * Rs_,
+                        (int64_t)N_ * Rs_ * Rs_);
+    return;
+  }
   for (int i = 0; i < N_; i++)
     ops_.gram(W_[i], V_.glens[i], V_.glens[i], R_, G_ + (size_t)i * R_ * R_);
 }
 
 void CpEngine::set_factors(const double *Wflat, const double *gradWflat) {
+  if (multi_) throw std::logic_error("ppals: a multi-start session takes its factors start by start");
   const double *w = Wflat, *g = gradWflat;
   double gs = 0, gsi[MAX_ORDER] = {0};
   for (int i = 0; i < N_; i++) {
@@ -657,7 +667,129 @@ void CpEngine::set_factors(const double *Wflat, const double *gradWflat) {
   ms_invalidate();
 }
 
+// ---------------------------------------------------------------------------- multi-start sessions
+// One start's factors are the column block [b Rs, (b+1) Rs) of every W_[i]: s_i * Rs contiguous doubles.
+void CpEngine::set_factors_start(int start, const double *Wflat, const double *gradWflat) {
+  if (!multi_) throw std::logic_error("ppals: not a multi-start session");
+  if (start < -1 || start >= K_) throw std::runtime_error("ppals: start out of range");
+  const double *w = Wflat, *g = gradWflat;
+  const int b0 = start < 0 ? 0 : start, b1 = start < 0 ? K_ : start + 1;
+  for (int b = b0; b < b1; b++)
+    for (int i = 0; i < N_; i++) {
+      const size_t n = (size_t)V_.glens[i] * Rs_;
+      ops_.h2d(W_[i] + (size_t)b * n, w, n * sizeof(double));
+      w += n;
+      // ||grad_W[i]||^2 of the caller's gradients, as set_factors keeps it (0 without gradients)
+      double gsq = 0;
+      if (g) {
+        ops_.h2d(gradW_[i] + (size_t)b * n, g, n * sizeof(double));
+        for (size_t e = 0; e < n; e++) gsq += g[e] * g[e];
+        g += n;
+      }
+      ops_.h2d(gradsq_ + (size_t)i * K_ + b, &gsq, sizeof(double));
+    }
+  refresh_grams();
+  for (auto &n : nodes_) n.valid = false;
+  ms_invalidate();
+}
+
+void CpEngine::get_factors_start(int start, double *Wflat, double *gradWflat) {
+  if (!multi_) throw std::logic_error("ppals: not a multi-start session");
+  if (start < -1 || start >= K_) throw std::runtime_error("ppals: start out of range");
+  double *w = Wflat, *g = gradWflat;
+  const int b0 = start < 0 ? 0 : start, b1 = start < 0 ? K_ : start + 1;
+  for (int b = b0; b < b1; b++)
+    for (int i = 0; i < N_; i++) {
+      const size_t n = (size_t)V_.glens[i] * Rs_;
+      if (w) {
+        ops_.d2h(w, W_[i] + (size_t)b * n, n * sizeof(double));
+        w += n;
+      }
+      if (g) {
+        ops_.d2h(g, gradW_[i] + (size_t)b * n, n * sizeof(double));
+        g += n;
+      }
+    }
+}
+
+void CpEngine::gradnorms(double *out) {
+  if (!multi_) throw std::logic_error("ppals: not a multi-start session");
+  std::vector<double> h((size_t)N_ * K_);
+  ops_.d2h(h.data(), gradsq_, sizeof(double) * h.size());
+  for (int b = 0; b < K_; b++) {
+    double sum = 0;
+    for (int i = 0; i < N_; i++) sum += h[(size_t)i * K_ + b];
+    out[b] = std::sqrt(sum);
+  }
+}
+
+// one streaming pass over the tensor per start (off the sweep path)
+void CpEngine::residuals(double *out) {
+  if (!multi_) throw std::logic_error("ppals: not a multi-start session");
+  int64_t M, K;
+  split_sizes(V_, &M, &K);
+  if (!Qbuf_) Qbuf_ = (double *)ops_.alloc(sizeof(double) * M * R_);
+  if (!Pbuf_) Pbuf_ = (double *)ops_.alloc(sizeof(double) * K * R_);
+  std::vector<double *> Wb(N_);
+  for (int b = 0; b < K_; b++) {
+    for (int i = 0; i < N_; i++) Wb[i] = W_[i] + (size_t)b * V_.glens[i] * Rs_;
+    split_krp(ops_, V_, Rs_, Wb.data(), Qbuf_, Pbuf_, &M, &K);
+    ops_.residual_sq(V_.data, V_.dtype, M, K, Qbuf_, Pbuf_, Rs_, scal_);
+    double h = 0;
+    ops_.d2h(&h, scal_, sizeof(double));
+    out[b] = std::sqrt(h);
+  }
+}
+
+int CpEngine::run_multi(const CpOpts &o, int *sweeps_out, int *best_out) {
+  if (!multi_) throw std::logic_error("ppals: not a multi-start session");
+  const double t0 = now();
+  std::vector<double> gn(K_), res(K_);
+  int sweeps = 0, best = 0;
+  bool stopped = false;
+  for (;;) {
+    if (sweeps % o.resprint == 0 || sweeps >= o.maxiter) {
+      gradnorms(gn.data());
+      residuals(res.data());
+      best = (int)(std::min_element(res.begin(), res.end()) - res.begin());
+      if (o.verbose)
+        std::printf("  [sweeps]=  %d  [best]  %d  [gradnorm]  %.13g  [residual]  %.13g  [dtime]  %g\n", sweeps,
+                    best, gn[best], res[best], now() - t0);
+      stopped = gn[best] < o.tol || now() - t0 > o.timelimit;
+      if (stopped || sweeps >= o.maxiter) break;
+    }
+    update_modes(0, N_, o.lambda);
+    sweeps++;
+  }
+  ops_.sync();
+  if (sweeps_out) *sweeps_out = sweeps;
+  if (best_out) *best_out = best;
+  return stopped && sweeps < o.maxiter ? 1 : 0;
+}
+
+void CpEngine::take_from(CpEngine &src, int start) {
+  if (multi_ || dist_) throw std::logic_error("ppals: the destination must be an ordinary one-rank session");
+  if (!src.multi_ || start < 0 || start >= src.K_ || src.Rs_ != R_ || src.N_ != N_ ||
+      src.V_.data != V_.data)
+    throw std::runtime_error("ppals: take: sessions do not match");
+  for (int i = 0; i < N_; i++) {
+    const size_t n = (size_t)V_.glens[i] * R_;
+    ops_.d2d(W_[i], src.W_[i] + (size_t)start * n, n * sizeof(double));
+    ops_.d2d(gradW_[i], src.gradW_[i] + (size_t)start * n, n * sizeof(double));
+    ops_.d2d(gradsq_ + i, src.gradsq_ + (size_t)i * src.K_ + start, sizeof(double));
+  }
+  // (gradnorm() reads the copied per-mode sums: the same number set_factors would have formed on the
+  // host from these gradients, with no read-back here)
+  for (int i = 0; i < MAX_ORDER; i++) grad_replicated_[i] = true;
+  grad_from_sweep_ = true;
+  refresh_grams();
+  for (auto &n : nodes_) n.valid = false;
+  ms_invalidate();
+  pp_clear();
+}
+
 void CpEngine::get_factors(double *Wflat, double *gradWflat) {
+  if (multi_) throw std::logic_error("ppals: a multi-start session hands out its factors start by start");
   double *w = Wflat, *g = gradWflat;
   for (int i = 0; i < N_; i++) {
     size_t n = (size_t)V_.glens[i] * R_;
@@ -684,6 +816,12 @@ void CpEngine::get_factors(double *Wflat, double *gradWflat) {
 void CpEngine::mode_update(int i, const double *M, int64_t ldm, double lambda, bool pp,
                            double ratio) {
   const int64_t s = V_.glens[i];
+  if (multi_) {  // block-diagonal over starts: one batched update, every start its own system
+    if (pp) throw std::logic_error("ppals: no PP update in a multi-start session");
+    ops_.cp_mode_update_batched(G_, N_, i, Rs_, K_, lambda, M, ldm, W_[i], s, gradW_[i], s, s,
+                                gradsq_ + (size_t)i * K_, S_, Sinv_);
+    return;
+  }
   double *Gi = G_ + (size_t)i * R_ * R_;
   if (!dist_) {
     if (test_blocks_ > 1 && s % test_blocks_ == 0 && !pp) {
@@ -794,6 +932,8 @@ unsigned CpEngine::ms_collect_scales(unsigned *masks, unsigned *fresh, int skip_
 }
 
 void CpEngine::normalize() {
+  // (one scalar per mode over the whole factor matrix: it would couple the starts)
+  if (multi_) throw std::logic_error("ppals: no Normalize in a multi-start session");
   int64_t rows[MAX_ORDER];
   for (int i = 0; i < N_; i++) rows[i] = V_.glens[i];
   unsigned masks[32] = {0}, fresh = 0;
@@ -1238,13 +1378,13 @@ void CpEngine::ms_mode_update(int i, double lambda, bool last_of_sweep) {
   const int leaf = ms_leaf_[pos];
   // (S and S^-1 of this update depend on the other modes' Grams only: the contraction launched
   // next may prepare them on the side)
-  ops_.arm_gram_system(G_, N_, i, R_, lambda, S_, Sinv_);
+  if (!multi_) ops_.arm_gram_system(G_, N_, i, R_, lambda, S_, Sinv_);
   ms_compute(leaf);
   ms_norm_fused_ = false;
   // the sweep's Normalize at the tail of its last update launch, with the pending scales of the cached
   // tensors that outlive the update (everything valid now but the leaf it consumes) — where the update
   // is the fused launch: one rank, or the one-all-reduce plan of a sharded session (never mode 0's)
-  if (last_of_sweep && (!dist_ || (i != 0 && (int64_t)sizeof(double) * V_.glens[i] * R_ <= small_msg_bytes_))) {
+  if (last_of_sweep && !multi_ && (!dist_ || (i != 0 && (int64_t)sizeof(double) * V_.glens[i] * R_ <= small_msg_bytes_))) {
     int64_t rows[MAX_ORDER];
     for (int q = 0; q < N_; q++) rows[q] = V_.glens[q];
     // (asked first with no cached tensors — a back end that cannot fold it must not see them marked)

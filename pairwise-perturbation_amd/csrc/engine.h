@@ -91,7 +91,10 @@ struct ModeNorms;
 
 class CpEngine {
  public:
-  CpEngine(Ops &ops, Comm &comm, const TensorDesc &V, int R);
+  // nstarts > 1 (or multi): a multi-start session — `nstarts` independent rank-R models share every
+  // contraction of the sweep. The factor matrices hold nstarts * R columns, start-major (start b owns
+  // columns [b R, (b+1) R)); only the R x R normal equations know about starts. One rank only.
+  CpEngine(Ops &ops, Comm &comm, const TensorDesc &V, int R, int nstarts = 1, bool multi = false);
   ~CpEngine();
 
   void set_factors(const double *Wflat, const double *gradWflat);
@@ -137,6 +140,21 @@ class CpEngine {
   int run_class(int kind, const CpOpts &o, double *sweeps, int *iters);
   void update_modes(int first, int count, double lambda);
 
+
+  // ---- multi-start sessions (start = -1: every start, concatenated start-major) ----
+  bool is_multi() const { return multi_; }
+  int nstarts() const { return K_; }
+  int start_rank() const { return Rs_; }
+  void set_factors_start(int start, const double *Wflat, const double *gradWflat);
+  void get_factors_start(int start, double *Wflat, double *gradWflat);
+  void gradnorms(double *out);  // [nstarts], each what gradnorm() of a session of that start returns
+  void residuals(double *out);  // [nstarts], each ||V - [[W_b]]||_F; synchronises
+  // start `start` of the multi session `src` (same tensor, same R) becomes this ordinary session's
+  // factors and gradients, device to device; otherwise the effect of set_factors
+  void take_from(CpEngine &src, int start);
+  // sweeps until maxiter / timelimit / the best start's gradient norm < tol (looked at every resprint
+  // sweeps); returns 1 if it stopped before maxiter sweeps
+  int run_multi(const CpOpts &o, int *sweeps, int *best);
 
   int order() const { return N_; }
   int rank_r() const { return R_; }
@@ -321,6 +339,11 @@ class CpEngine {
   Comm &comm_;
   TensorDesc V_;
   int N_, R_, P_, rank_;
+  // multi-start: K_ starts of Rs_ columns each, R_ = K_ * Rs_. G_ then holds, start by start, the N
+  // Grams (Rs_ x Rs_) of that start — the blocks between starts are never formed —, S_ / Sinv_ one
+  // system per start, gradsq_ K_ sums per mode (gradsq_[mode * K_ + start])
+  int K_ = 1, Rs_ = 0;
+  bool multi_ = false;
   bool dist_ = false;  // take the collective code paths (P_ > 1, or PPALS_FORCE_COMM=1 for tests)
   std::vector<double *> W_, gradW_, Wprev_, Winit_, dW_, dM_, Mm_;
   double *G_ = nullptr;       // N Gram matrices, R*R each

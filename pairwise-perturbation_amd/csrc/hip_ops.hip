@@ -121,6 +121,10 @@ class HipOps : public Ops {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
     HIP_CHECK(hipFuncSetAttribute((const void *)k_cp_mode_update<true, true>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_cp_mode_update_batched<false, false>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_cp_mode_update_batched<true, true>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
     if (const char *v = getenv("PPALS_FORCE_JACOBI")) force_jacobi_ = atoi(v);
     if (const char *v = getenv("PPALS_EIG_FAST")) {
       eig_fast_ = atoi(v);  // 0: always the full solver; 2: warm steps as usual, cold starts on the full solver
@@ -1448,6 +1452,46 @@ class HipOps : public Ops {
                          R, lambda, M, ldm, W, ldw, grad, ldg, rows, gradsq, Winit, ldi, dW, ldd, ratio,
                          S, Sinv, dwsq, presolved);
     }
+    HIP_CHECK(hipGetLastError());
+  }
+  // The mode updates of all starts of a multi-start session in ONE launch: a 1024-thread workgroup per
+  // start (nstarts <= 32 of them on 256 CUs: every workgroup has a CU and its LDS to itself, none waits
+  // for another). The same routes as cp_mode_update: the staged launch where M and W of ONE start fit
+  // the LDS, the unstaged one for short long modes, start by start through the unfused routes otherwise.
+  void cp_mode_update_batched(double *Gall, int N, int mode, int R, int nstarts, double lambda,
+                              const double *M, int64_t ldm, double *W, int64_t ldw, double *grad,
+                              int64_t ldg, int64_t rows, double *gradsq, double *S, double *Sinv) override {
+    RoctxRange roctx_("K4-K6 mode update (batched over starts)");
+    const size_t lds = sizeof(double) * (32 + 2 * (size_t)R * R + 2 * (size_t)R * (R + 1) + 64) +
+                       sizeof(int) * 64;
+    const size_t stage = 2 * sizeof(double) * (size_t)rows * R;
+    const bool staged = lds + stage <= 150 * 1024;
+    if (R > 64 || force_jacobi_ || nstarts < 1 || (double)rows * R >= 2.0e9 ||
+        (!staged && (int64_t)rows * R > kUpdateRowParallelFrom)) {
+      // (bracketed start by start: the profile's launch count shows which route a session took)
+      for (int b = 0; b < nstarts; b++) {
+        const size_t rr = (size_t)R * R;
+        prof_begin(1, 0.0);
+        cp_mode_update(Gall + b * N * rr, N, mode, R, lambda, M + (size_t)b * R * ldm, ldm,
+                       W + (size_t)b * R * ldw, ldw, grad + (size_t)b * R * ldg, ldg, rows, gradsq + b, nullptr,
+                       rows, nullptr, rows, 1.0, S ? S + b * rr : nullptr, Sinv ? Sinv + b * rr : nullptr,
+                       nullptr);
+        prof_end();
+      }
+      return;
+    }
+    if (norm_armed_) throw std::logic_error("ppals: armed Normalize in front of a batched mode update");
+    sys_ready_ = false;
+    sys_armed_ = false;
+    prof_begin(1, 0.0);
+    if (staged)
+      hipLaunchKernelGGL((k_cp_mode_update_batched<true, true>), dim3((unsigned)nstarts), dim3(1024),
+                         lds + stage, st_, Gall, N, mode, R, lambda, M, ldm, W, ldw, grad, ldg, rows, gradsq,
+                         S, Sinv);
+    else
+      hipLaunchKernelGGL((k_cp_mode_update_batched<false, false>), dim3((unsigned)nstarts), dim3(1024), lds,
+                         st_, Gall, N, mode, R, lambda, M, ldm, W, ldw, grad, ldg, rows, gradsq, S, Sinv);
+    prof_end();
     HIP_CHECK(hipGetLastError());
   }
   bool arm_normalize(double *const *W, const int64_t *rows, int N, int R, double *Gall, int mode,

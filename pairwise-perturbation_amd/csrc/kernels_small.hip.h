@@ -1501,14 +1501,17 @@ __device__ unsigned long long g_update_stamps[16];
 #else
 #define PPALS_STAMP(i)
 #endif
-template <bool STAGE, bool MF = false>
-__global__ __launch_bounds__(1024) void k_cp_mode_update(
+// The body of the launch, for ONE workgroup: k_cp_mode_update runs it once, k_cp_mode_update_batched
+// once per start of a multi-start session (each workgroup on its own column block and Grams).
+// NORM: the launch may carry the sweep's Normalize (nrm.on); a batched launch never does.
+template <bool STAGE, bool MF, bool NORM>
+__device__ __forceinline__ void cp_mode_update_body(
     double *__restrict__ Gall, int N, int mode, int R, double lambda, const double *__restrict__ M,
     int64_t ldm, double *W, int64_t ldw, double *__restrict__ grad, int64_t ldg, int64_t rows,
     double *__restrict__ gradsq, const double *__restrict__ Winit, int64_t ldi,
     double *__restrict__ dW, int64_t ldd, double ratio, double *__restrict__ S_out,
-    double *__restrict__ Sinv_out, double *__restrict__ dwsq, int presolved = 0,
-    NormArgs nrm = NormArgs(), int mblk = 0) {
+    double *__restrict__ Sinv_out, double *__restrict__ dwsq, int presolved, const NormArgs &nrm,
+    int mblk) {
   // mblk > 0 (STAGE only): M is handed over in ROW BLOCKS of mblk rows, block p at p * mblk * R with
   // leading dimension mblk — the receive buffer of an all-gather of the ranks' row blocks, read as
   // it arrives (no unpack launch in front of the update)
@@ -1764,7 +1767,7 @@ __global__ __launch_bounds__(1024) void k_cp_mode_update(
   }
   }
   PPALS_STAMP(6);  // Gram pairs of this wave done
-  if constexpr (STAGE) {
+  if constexpr (STAGE && NORM) {
     if (nrm.on) {  // (block-uniform) Normalize, common.cxx:644-689, on all N factors
       __threadfence();
       __syncthreads();
@@ -1805,6 +1808,34 @@ __global__ __launch_bounds__(1024) void k_cp_mode_update(
       }
     }
   }
+}
+template <bool STAGE, bool MF = false>
+__global__ __launch_bounds__(1024) void k_cp_mode_update(
+    double *__restrict__ Gall, int N, int mode, int R, double lambda, const double *__restrict__ M,
+    int64_t ldm, double *W, int64_t ldw, double *__restrict__ grad, int64_t ldg, int64_t rows,
+    double *__restrict__ gradsq, const double *__restrict__ Winit, int64_t ldi,
+    double *__restrict__ dW, int64_t ldd, double ratio, double *__restrict__ S_out,
+    double *__restrict__ Sinv_out, double *__restrict__ dwsq, int presolved = 0,
+    NormArgs nrm = NormArgs(), int mblk = 0) {
+  cp_mode_update_body<STAGE, MF, true>(Gall, N, mode, R, lambda, M, ldm, W, ldw, grad, ldg, rows, gradsq, Winit,
+                                 ldi, dW, ldd, ratio, S_out, Sinv_out, dwsq, presolved, nrm, mblk);
+}
+// Multi-start sessions: workgroup b is the whole mode update of start b — its Hadamard system out of
+// its own N Grams (Gall + b N R^2), the inverse (the Jacobi fallback decided by that workgroup alone: a
+// start whose system is not positive definite does not touch the others), gradient, solve and Gram
+// refresh on columns [b R, (b+1) R) of M, W and grad. gridDim.x = number of starts, no workgroup waits
+// for another, so K updates cost the latency of one. S_out / Sinv_out: one R x R system per start.
+template <bool STAGE, bool MF = false>
+__global__ __launch_bounds__(1024) void k_cp_mode_update_batched(
+    double *__restrict__ Gall, int N, int mode, int R, double lambda, const double *__restrict__ M,
+    int64_t ldm, double *W, int64_t ldw, double *__restrict__ grad, int64_t ldg, int64_t rows,
+    double *__restrict__ gradsq, double *__restrict__ S_out, double *__restrict__ Sinv_out) {
+  const int64_t b = blockIdx.x;
+  const int64_t c0 = b * R, rr = (int64_t)R * R;
+  cp_mode_update_body<STAGE, MF, false>(Gall + b * N * rr, N, mode, R, lambda, M + c0 * ldm, ldm, W + c0 * ldw, ldw,
+                                 grad + c0 * ldg, ldg, rows, gradsq + b, nullptr, 0, nullptr, 0, 1.0,
+                                 S_out ? S_out + b * rr : nullptr, Sinv_out ? Sinv_out + b * rr : nullptr,
+                                 nullptr, 0, NormArgs(), 0);
 }
 
 // ------------------------------------------------------------------ Normalize (K7)

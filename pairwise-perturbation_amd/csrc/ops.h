@@ -283,6 +283,25 @@ class Ops {
     gram(W, rows, ldw, R, Gall + (size_t)mode * R * R);
     if (dwsq && Winit) sumsq(dW, rows * R, dwsq);
   }
+  // `nstarts` independent mode updates of rank R in one call (multi-start sessions): M, W and grad hold
+  // nstarts * R columns, start b owns columns [b R, (b+1) R); Gall holds, start by start, the N Grams
+  // (R x R) of that start; S / Sinv one R x R system per start; gradsq[b] = ||grad_b||^2. Nothing
+  // couples two starts. Back ends may run all of them in one launch.
+  virtual void cp_mode_update_batched(double *Gall, int N, int mode, int R, int nstarts, double lambda,
+                                      const double *M, int64_t ldm, double *W, int64_t ldw,
+                                      double *grad, int64_t ldg, int64_t rows, double *gradsq,
+                                      double *S, double *Sinv) {
+    for (int b = 0; b < nstarts; b++)
+      cp_mode_update(Gall + (size_t)b * N * R * R, N, mode, R, lambda, M + (size_t)b * R * ldm, ldm,
+                     W + (size_t)b * R * ldw, ldw, grad + (size_t)b * R * ldg, ldg, rows, gradsq + b,
+                     nullptr, rows, nullptr, rows, 1.0, S ? S + (size_t)b * R * R : nullptr,
+                     Sinv ? Sinv + (size_t)b * R * R : nullptr);
+  }
+  // G_b = W_b^T W_b of the same column blocks: G + b * gstride, b < nstarts
+  virtual void gram_batched(const double *W, int64_t rows, int64_t ld, int R, int nstarts, double *G,
+                            int64_t gstride) {
+    for (int b = 0; b < nstarts; b++) gram(W + (size_t)b * R * ld, rows, ld, R, G + (size_t)b * gstride);
+  }
   // The same with M handed over in ROW BLOCKS (the receive buffer of an all-gather of the ranks' row
   // blocks: block p = rows [p*blk, (p+1)*blk) stored at Mblk + p*blk*R with leading dimension blk,
   // blk * P == rows). A back end may read the blocks as they are; the default re-assembles them in

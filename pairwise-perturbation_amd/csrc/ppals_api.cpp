@@ -28,6 +28,7 @@ struct ppals_ctx {
   // down whatever is still alive itself and leaves the orphaned handles DEAD (eng / data null):
   // destroying them later is a no-op, using them an error — never a use-after-free of the device.
   std::set<ppals_cp *> cps;
+  std::set<ppals_cp_multi *> multis;
   std::set<ppals_tucker *> tks;
   std::set<ppals_tensor *> tensors;
 };
@@ -39,6 +40,10 @@ struct ppals_tensor {
 struct ppals_cp {
   ppals_ctx *ctx;
   CpEngine *eng;
+};
+struct ppals_cp_multi {
+  ppals_ctx *ctx;
+  CpEngine *eng;  // nstarts * R columns, start-major (engine.h)
 };
 struct ppals_tucker {
   ppals_ctx *ctx;
@@ -90,6 +95,11 @@ int ppals_ctx_create(ppals_ctx **out, int device) {
 void ppals_ctx_destroy(ppals_ctx *ctx) {
   if (!ctx) return;
   for (ppals_cp *s : ctx->cps) {
+    delete s->eng;
+    s->eng = nullptr;
+    s->ctx = nullptr;
+  }
+  for (ppals_cp_multi *s : ctx->multis) {
     delete s->eng;
     s->eng = nullptr;
     s->ctx = nullptr;
@@ -554,6 +564,106 @@ int ppals_cpd_als_lr(ppals_cp *s, int optimizer, int update_rank, int randomsvd,
   c.update_rank = update_rank;
   c.randomsvd = randomsvd;
   return s->eng->run_class(optimizer, c, sweeps, iters);
+  API_END(PPALS_ERR_HIP)
+}
+
+// ------------------------------------------------------------------ multi-start CP
+int ppals_cp_multi_create(ppals_ctx *ctx, ppals_tensor *V, int R, int nstarts, ppals_cp_multi **out) {
+  if (!ctx || !V || !out) return fail(PPALS_ERR_ARG, "NULL argument");
+  *out = nullptr;
+  if (V->ctx != ctx || !V->d.data) return fail(PPALS_ERR_ARG, "the tensor belongs to another context");
+  if (R <= 0) return fail(PPALS_ERR_ARG, "rank must be positive");
+  if (nstarts < 1 || nstarts > PPALS_MULTI_MAX_STARTS)
+    return fail(PPALS_ERR_ARG, "nstarts must be in [1, 32]");
+  if ((int64_t)R * nstarts > PPALS_MULTI_MAX_COLUMNS)
+    return fail(PPALS_ERR_ARG, "R * nstarts must not exceed 128");
+  if (ctx->c().size() > 1)
+    return fail(PPALS_ERR_UNSUPPORTED, "a multi-start session runs on one rank (sharded multi-start is not implemented)");
+  API_BEGIN
+  std::unique_ptr<ppals_cp_multi> s(new ppals_cp_multi);
+  s->ctx = ctx;
+  s->eng = new CpEngine(*ctx->ops, ctx->c(), V->d, R, nstarts, true);
+  ctx->multis.insert(s.get());
+  *out = s.release();
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+void ppals_cp_multi_destroy(ppals_cp_multi *s) {
+  if (!s) return;
+  delete s->eng;
+  if (s->ctx) s->ctx->multis.erase(s);
+  delete s;
+}
+static int check_start(const ppals_cp_multi *s, int start, bool all_ok) {
+  if (!s || !s->eng) return fail(PPALS_ERR_ARG, "NULL session");
+  if (start >= s->eng->nstarts() || start < (all_ok ? -1 : 0))
+    return fail(PPALS_ERR_ARG, all_ok ? "start must be in [0, nstarts) or -1" : "start must be in [0, nstarts)");
+  return PPALS_OK;
+}
+int ppals_cp_multi_set_factors(ppals_cp_multi *s, int start, const double *Wflat, const double *gradWflat) {
+  if (int rc = check_start(s, start, true)) return rc;
+  if (!Wflat) return fail(PPALS_ERR_ARG, "NULL argument");
+  API_BEGIN
+  s->eng->set_factors_start(start, Wflat, gradWflat);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_cp_multi_get_factors(ppals_cp_multi *s, int start, double *Wflat, double *gradWflat) {
+  if (int rc = check_start(s, start, true)) return rc;
+  API_BEGIN
+  s->eng->get_factors_start(start, Wflat, gradWflat);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_cp_multi_set_schedule(ppals_cp_multi *s, int schedule) {
+  if (!s || !s->eng) return fail(PPALS_ERR_ARG, "NULL session");
+  if (schedule != PPALS_SCHEDULE_DT && schedule != PPALS_SCHEDULE_MSDT)
+    return fail(PPALS_ERR_ARG, "schedule must be PPALS_SCHEDULE_DT or PPALS_SCHEDULE_MSDT");
+  API_BEGIN
+  s->eng->set_schedule(schedule);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_cp_multi_sweeps(ppals_cp_multi *s, int n, double lambda) {
+  if (!s || !s->eng) return fail(PPALS_ERR_ARG, "NULL session");
+  if (n < 0) return fail(PPALS_ERR_ARG, "the number of sweeps must not be negative");
+  API_BEGIN
+  for (int i = 0; i < n; i++) s->eng->update_modes(0, s->eng->order(), lambda);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_cp_multi_residuals(ppals_cp_multi *s, double *out) {
+  if (!s || !s->eng || !out) return fail(PPALS_ERR_ARG, "NULL argument");
+  API_BEGIN
+  s->eng->residuals(out);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_cp_multi_gradnorms(ppals_cp_multi *s, double *out) {
+  if (!s || !s->eng || !out) return fail(PPALS_ERR_ARG, "NULL argument");
+  API_BEGIN
+  s->eng->gradnorms(out);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_cp_multi_run(ppals_cp_multi *s, const ppals_cp_opts *o, int *sweeps, int *best) {
+  if (!s || !s->eng || !o) return fail(PPALS_ERR_ARG, "NULL argument");
+  if (o->maxiter < 0) return fail(PPALS_ERR_ARG, "maxiter must not be negative");
+  API_BEGIN
+  return s->eng->run_multi(to_opts(o), sweeps, best);
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_cp_multi_take(ppals_cp_multi *s, int start, ppals_cp *dst) {
+  if (int rc = check_start(s, start, false)) return rc;
+  if (!dst || !dst->eng) return fail(PPALS_ERR_ARG, "NULL destination session");
+  if (dst->ctx != s->ctx) return fail(PPALS_ERR_ARG, "the destination session belongs to another context");
+  if (dst->eng->tensor().data != s->eng->tensor().data)
+    return fail(PPALS_ERR_ARG, "the destination session is on another tensor");
+  if (dst->eng->rank_r() != s->eng->start_rank())
+    return fail(PPALS_ERR_ARG, "the destination session has another rank R");
+  API_BEGIN
+  dst->eng->take_from(*s->eng, start);
+  return PPALS_OK;
   API_END(PPALS_ERR_HIP)
 }
 

@@ -57,6 +57,10 @@ EXPORTS = [
     "ppals_tucker_set_core",
     "ppals_tucker_hosvd", "ppals_tucker_ttmc", "ppals_tucker_sweeps_dt", "ppals_tucker_dt",
     "ppals_tucker_pp", "ppals_cp_export_model_device", "ppals_tucker_export_model_device",
+    "ppals_cp_multi_create", "ppals_cp_multi_destroy", "ppals_cp_multi_set_factors",
+    "ppals_cp_multi_get_factors", "ppals_cp_multi_set_schedule", "ppals_cp_multi_sweeps",
+    "ppals_cp_multi_residuals", "ppals_cp_multi_gradnorms", "ppals_cp_multi_run",
+    "ppals_cp_multi_take",
 ]
 MODEL, RESIDUAL = 0, 1  # PPALS_MODEL / PPALS_RESIDUAL
 
@@ -506,6 +510,88 @@ class CP(_ModelExport):
     def close(self):
         if self._h:
             lib().ppals_cp_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CPMulti:
+    """K independent rank-R CP-ALS starts of one tensor that share every tensor scan (ppals_cp_multi):
+    start b evolves as an ordinary CP session does under cpd_als(0, ...) from the same factors. No
+    Normalize, PP or drivers here: take() the winner into a CP session and go on there."""
+
+    def __init__(self, ctx, V, R, nstarts):
+        self.ctx, self.V, self.R, self.nstarts = ctx, V, int(R), int(nstarts)
+        self.lens = V.lens
+        self._h = C.c_void_p()
+        _check(lib().ppals_cp_multi_create(ctx._h, V._h, int(R), int(nstarts), C.byref(self._h)))
+        ctx._children.add(self)
+
+    def _n(self):
+        return sum(s * self.R for s in self.lens)
+
+    def set_factors(self, start, Ws, gradWs=None):
+        """one start's factors (list of (s_i, R) arrays); start = -1: Ws (and gradWs) are lists of
+        nstarts such lists"""
+        if start == -1:
+            wf = np.concatenate([flat(W) for W in Ws])
+            gf = np.concatenate([flat(G) for G in gradWs]) if gradWs is not None else None
+        else:
+            wf = flat(Ws)
+            gf = flat(gradWs) if gradWs is not None else None
+        _check(lib().ppals_cp_multi_set_factors(self._h, int(start), _dp(wf),
+                                                _dp(gf) if gf is not None else None))
+
+    def get_factors(self, start, with_grad=False):
+        k = self.nstarts if start == -1 else 1
+        n = self._n()
+        wf = np.empty(n * k)
+        gf = np.empty(n * k) if with_grad else None
+        _check(lib().ppals_cp_multi_get_factors(self._h, int(start), _dp(wf),
+                                                _dp(gf) if with_grad else None))
+        ranks = [self.R] * len(self.lens)
+        W = [unflat(wf[b * n:(b + 1) * n], self.lens, ranks) for b in range(k)]
+        G = [unflat(gf[b * n:(b + 1) * n], self.lens, ranks) for b in range(k)] if with_grad else None
+        if start != -1:
+            W, G = W[0], (G[0] if with_grad else None)
+        return (W, G) if with_grad else W
+
+    def set_schedule(self, schedule):
+        code = {"dt": 0, "msdt": 1}[schedule] if isinstance(schedule, str) else int(schedule)
+        _check(lib().ppals_cp_multi_set_schedule(self._h, code))
+
+    def sweeps(self, n, lam=0.0):
+        _check(lib().ppals_cp_multi_sweeps(self._h, int(n), C.c_double(lam)))
+
+    def residuals(self):
+        out = np.empty(self.nstarts)
+        _check(lib().ppals_cp_multi_residuals(self._h, _dp(out)))
+        return out
+
+    def gradnorms(self):
+        out = np.empty(self.nstarts)
+        _check(lib().ppals_cp_multi_gradnorms(self._h, _dp(out)))
+        return out
+
+    def run(self, **kw):
+        """returns (rc, sweeps, best): rc 1 if it stopped on tol / timelimit before maxiter sweeps"""
+        o = _opts(**kw)
+        sw, best = C.c_int(0), C.c_int(0)
+        rc = _check(lib().ppals_cp_multi_run(self._h, C.byref(o), C.byref(sw), C.byref(best)))
+        return rc, sw.value, best.value
+
+    def take(self, start, dst):
+        """start's factors and gradients into the CP session dst (same tensor, same R), on the device"""
+        _check(lib().ppals_cp_multi_take(self._h, int(start), dst._h))
+        return dst
+
+    def close(self):
+        if self._h:
+            lib().ppals_cp_multi_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
