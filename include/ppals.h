@@ -325,6 +325,43 @@ int ppals_tucker_export_model_device(ppals_tucker *s, int what, void *dst, int d
                                      const int64_t *box_lo, const int64_t *box_len,
                                      const int64_t *strides, void *stream);
 
+/* ---- CP with missing entries (TensorLy's parafac(mask=...)): imputation and an EM driver ----
+ * The mask is a view exactly as in ppals_tensor_import_device, of one byte per element (PPALS_U8: a
+ * torch.bool or torch.uint8 tensor): a box of the GLOBAL tensor, strides >= 0 in elements (= bytes; 0
+ * broadcasts one mask slice over a mode, i.e. whole fibres missing), NULL strides = dense over the box,
+ * first index fastest. A byte of 0 says the element is MISSING, anything else that it is observed. */
+#define PPALS_U8 4 /* element type of a mask view only: one byte per element, 0 = missing, anything else = observed */
+/* Overwrite the MISSING entries of the session's tensor with the session's current CP model: for every
+ * element of the box in this rank's leading-mode rows a non-zero mask byte leaves the element bit for
+ * bit as it is, a zero byte replaces it with the fp64 model [[W_0..W_{N-1}]] of the current factors
+ * (products and sums on the fp64 matrix cores) rounded once to the storage type, as
+ * ppals_tensor_import_device rounds an fp64 source. Elements outside the box and other ranks' rows are
+ * untouched; V is not even read unless the residual is wanted.
+ *   observed_sq == NULL: the host does not block; ordered on `stream` as the model export is.
+ *   observed_sq != NULL: *observed_sq = sum of (V - model)^2 over the OBSERVED elements of the box, V as
+ *     stored, differences and sum in fp64, summed over all ranks (one scalar all-reduce) in a fixed
+ *     order (the same state gives the same bits); the call returns when the sum is on the host.
+ * The call bumps the tensor's generation like an import: every session on the tensor, this one included,
+ * rebuilds its second layout and drops tree nodes, the multi-sweep intermediate and PP operators at its
+ * next read. The session's factors, Grams and gradients do not change. Every check
+ * ppals_tensor_check_device_view makes of an import source is made of the mask, as a view of PPALS_U8,
+ * before anything is launched: PPALS_ERR_ARG and a message that starts with "ppals_cp_impute_device: ".
+ * (PPALS_U8 is a mask's type only: the tensor import and ppals_tensor_check_device_view refuse it.) */
+int ppals_cp_impute_device(ppals_cp *s, const void *mask, const int64_t *box_lo, const int64_t *box_len,
+                           const int64_t *strides, void *stream, double *observed_sq /* may be NULL */);
+/* EM for CP with missing entries: repeat { impute; inner_sweeps exact sweeps } — iteration k is an
+ * imputation followed by ppals_cp_sweeps_dt(inner_sweeps, o->lambda). The observed residual
+ * sqrt(observed_sq) is read at the imputation of iterations 0, resprint, 2 resprint, ... (the others
+ * never block). The loop stops at the first of: a look that finds the observed residual <= o->tol;
+ * o->maxiter iterations; o->timelimit seconds (checked at the looks, agreed across ranks). Uses tol,
+ * timelimit, maxiter, lambda and resprint of the options and ignores the rest; inner_sweeps >= 1. On
+ * the way out one last imputation with the residual runs (unless the stopping look just did), so the
+ * tensor's missing entries and *observed_res belong to the returned factors. *iters = iterations run.
+ * Returns 1 if it stopped on tol, 0 otherwise, <0 on error. The mask must stay unchanged meanwhile. */
+int ppals_cp_em(ppals_cp *s, const void *mask, const int64_t *box_lo, const int64_t *box_len,
+                const int64_t *strides, void *stream, const ppals_cp_opts *o, int inner_sweeps,
+                int *iters, double *observed_res);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,15 +23,16 @@
 namespace ppals {
 
 constexpr int DV_MAX_ORDER = 8;  // = PPALS_MAX_ORDER
-// element types of a view (the PPALS_F32 / F64 / F16 / BF16 codes)
-enum ViewDType { DV_F32 = 0, DV_F64 = 1, DV_F16 = 2, DV_BF16 = 3 };
+// element types of a view (the PPALS_F32 / F64 / F16 / BF16 / U8 codes); U8: the bytes of a mask view
+// (ppals_cp_impute_device, dv_check_args with mask = true), never a source or destination of tensor values
+enum ViewDType { DV_F32 = 0, DV_F64 = 1, DV_F16 = 2, DV_BF16 = 3, DV_U8 = 4 };
 enum ViewDir { DV_IMPORT = 0, DV_EXPORT = 1 };
 // (a) streaming copy-convert along a mode that is unit-stride in the view and fastest in the shard,
 // (b) 64 x 64 LDS tiles between the shard's fastest modes and the view's unit-stride mode,
 // (c) per-element gather (the view has no unit-stride mode: correct, not fast)
 enum ViewKind { DV_EMPTY = 0, DV_STREAM = 1, DV_TILE = 2, DV_GATHER = 3 };
 
-inline int dv_elem_size(int dt) { return dt == DV_F32 ? 4 : dt == DV_F64 ? 8 : 2; }
+inline int dv_elem_size(int dt) { return dt == DV_F32 ? 4 : dt == DV_F64 ? 8 : dt == DV_U8 ? 1 : 2; }
 inline bool dv_dtype_ok(int dir, int dt) {
   return dt == DV_F32 || dt == DV_F64 || (dir == DV_IMPORT && (dt == DV_F16 || dt == DV_BF16));
 }
@@ -96,11 +97,14 @@ struct ViewArgs {
 
 // Every check that needs no pointer query. box_lo / box_len NULL: the whole tensor; strides NULL:
 // dense over the box, first index fastest. false: *err says why (the C ABI returns PPALS_ERR_ARG).
+// mask: the view is the mask of an imputation, read like an import source, its only type DV_U8.
 inline bool dv_check_args(int dir, int order, const int64_t *glens, int dtype, const int64_t *box_lo,
                           const int64_t *box_len, const int64_t *strides, ViewArgs *a,
-                          std::string *err) {
+                          std::string *err, bool mask = false) {
   if (dir != DV_IMPORT && dir != DV_EXPORT) return *err = "direction must be 0 (import) or 1 (export)", false;
-  if (!dv_dtype_ok(dir, dtype))
+  if (mask) {
+    if (dir != DV_IMPORT || dtype != DV_U8) return *err = "a mask view is read, as PPALS_U8", false;
+  } else if (!dv_dtype_ok(dir, dtype))
     return *err = dir == DV_IMPORT ? "bad source dtype (PPALS_F32, F64, F16 or BF16)"
                                    : "bad destination dtype (PPALS_F32 or F64)",
            false;
@@ -290,6 +294,15 @@ struct ModelPlan {
   int64_t voff = 0, roff = 0;
   int64_t ldq = 0, pL = 1, pLK = 0;
 };
+// The imputation (ppals_cp_impute_device, Ops::model_impute): the stores go to the SHARD, predicated on
+// the bytes of a mask view, so the two sides change places for the kernel: its "view" is the shard
+// (group A along the shard's fast side) and the side it reads, coalesced or through LDS, is the mask.
+inline ModelPlan dv_model_swapped(ModelPlan mp) {
+  for (int i = 0; i < mp.ga.n; i++) std::swap(mp.ga.rs[i], mp.ga.vs[i]);
+  for (int i = 0; i < mp.gb.n; i++) std::swap(mp.gb.rs[i], mp.gb.vs[i]);
+  std::swap(mp.roff, mp.voff);
+  return mp;
+}
 // The second pass of the two-pass residual, view -= model: "V" is the view itself (its offsets in place
 // of the shard's), after the tensor export has filled it.
 inline ModelPlan dv_model_rmw(ModelPlan mp) {

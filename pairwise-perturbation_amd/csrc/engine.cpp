@@ -1984,29 +1984,10 @@ void model_export_run(Ops &ops, ModelExportCall &c, const ModelPlan &mp, const d
   ops.model_to_view(dv_model_rmw(mp), Q, P, K, true, c.dst, c.a->dtype, c.dst, c.a->dtype, c.stream);
 }
 
-// The model through a view (DESIGN.md §2): [[W]] is symmetric in how the modes are grouped, so the
-// grouping follows the VIEW. Group A = the view's fastest modes (by stride) until A reaches the square
-// root of the box, group B = the rest in the shard's order (a residual's V reads run along it when A is
-// not the shard's fast side); Q and P are their Khatri-Rao products, and the kernel stores Q P^T with the
-// lane index along the view's unit-stride run.
-void CpEngine::export_model(const ViewArgs &a, void *dst, bool residual, void *stream) {
-  ModelBox bx;
-  if (!dv_model_box(a, V_.glens, V_.row0, V_.llens[0], &bx)) return;
-  int ord[MAX_ORDER], n = 0;
-  int64_t total = 1;
-  for (int m = 0; m < N_; m++) {
-    total *= bx.len[m];
-    if (bx.len[m] > 1) ord[n++] = m;
-  }
-  std::stable_sort(ord, ord + n, [&](int x, int y) { return bx.vs[x] < bx.vs[y]; });
-  ModelPlan mp;
-  bool inA[MAX_ORDER] = {};
-  for (int i = 0; i < n && (mp.ga.count < 64 || mp.ga.count * mp.ga.count < total); i++) {
-    mp.ga.add(bx, ord[i]);
-    inA[ord[i]] = true;
-  }
-  for (int m = 0; m < N_; m++)
-    if (!inA[m]) mp.gb.add(bx, m);
+// The operands of a grouped plan (groups A and B chosen, box cut): xq_ / xp_ = the Khatri-Rao products
+// of the box rows of the groups' factors (grow-only buffers kept by the session), and the plan's offsets
+// and leading dimensions. Shared by the model export and the imputation, which differ in the grouping.
+void CpEngine::model_operands(const ModelBox &bx, ModelPlan &mp) {
   auto refs = [&](const ModelGroup &g, FactorRef *f) {
     for (int i = 0; i < g.n; i++) {
       const int m = g.mode[i];
@@ -2036,8 +2017,95 @@ void CpEngine::export_model(const ViewArgs &a, void *dst, bool residual, void *s
   mp.ldq = A;
   mp.pL = B;
   mp.pLK = 0;
+}
+
+// The model through a view (DESIGN.md §2): [[W]] is symmetric in how the modes are grouped, so the
+// grouping follows the VIEW. Group A = the view's fastest modes (by stride) until A reaches the square
+// root of the box, group B = the rest in the shard's order (a residual's V reads run along it when A is
+// not the shard's fast side); Q and P are their Khatri-Rao products, and the kernel stores Q P^T with the
+// lane index along the view's unit-stride run.
+void CpEngine::export_model(const ViewArgs &a, void *dst, bool residual, void *stream) {
+  ModelBox bx;
+  if (!dv_model_box(a, V_.glens, V_.row0, V_.llens[0], &bx)) return;
+  int ord[MAX_ORDER], n = 0;
+  int64_t total = 1;
+  for (int m = 0; m < N_; m++) {
+    total *= bx.len[m];
+    if (bx.len[m] > 1) ord[n++] = m;
+  }
+  std::stable_sort(ord, ord + n, [&](int x, int y) { return bx.vs[x] < bx.vs[y]; });
+  ModelPlan mp;
+  bool inA[MAX_ORDER] = {};
+  for (int i = 0; i < n && (mp.ga.count < 64 || mp.ga.count * mp.ga.count < total); i++) {
+    mp.ga.add(bx, ord[i]);
+    inA[ord[i]] = true;
+  }
+  for (int m = 0; m < N_; m++)
+    if (!inA[m]) mp.gb.add(bx, m);
+  model_operands(bx, mp);
   ModelExportCall c{&a, &V_, dst, residual, residual_form_, false, stream};
   model_export_run(ops_, c, mp, xq_, xp_, R_);
+}
+
+// The imputation: the stores go to the shard, so here the grouping follows the SHARD.
+// Group A = the shard's fastest modes (its own order) until A reaches the square root of the box: the
+// lane index of the store pass runs along it, and so do the V reads of the observed residual. Group B =
+// the rest, a mode in which the mask is unit-stride first: when the mask is not contiguous along A its
+// bytes, 1 B per element, are the side read along b through LDS.
+void CpEngine::impute(const ViewArgs &a, const void *mask, void *stream, double *observed_sq) {
+  if (multi_) throw std::logic_error("ppals: a multi-start session does not impute (take the winner first)");
+  ModelBox bx;
+  if (dv_model_box(a, V_.glens, V_.row0, V_.llens[0], &bx)) {
+    ModelPlan mp;
+    int64_t total = 1;
+    for (int m = 0; m < N_; m++) total *= bx.len[m];
+    bool inA[MAX_ORDER] = {};
+    for (int m = 0; m < N_ && (mp.ga.count < 64 || mp.ga.count * mp.ga.count < total); m++)
+      if (bx.len[m] > 1) {
+        mp.ga.add(bx, m);
+        inA[m] = true;
+      }
+    int first = -1;
+    for (int m = 0; m < N_ && first < 0; m++)
+      if (!inA[m] && bx.len[m] > 1 && bx.vs[m] == 1) first = m;
+    if (first >= 0) mp.gb.add(bx, first);
+    for (int m = 0; m < N_; m++)
+      if (!inA[m] && m != first) mp.gb.add(bx, m);
+    model_operands(bx, mp);
+    ops_.model_impute(mp, xq_, xp_, R_, mask, V_.data, V_.dtype, observed_sq ? scal_ : nullptr, stream);
+    // the contents changed with that launch: every session on the tensor, this one too, rebuilds what
+    // it derived at its next read (a rank none of whose rows lie in the box has changed nothing)
+    if (V_.generation) ++*V_.generation;
+  } else if (observed_sq) {
+    ops_.zero(scal_, sizeof(double));  // none of the box in this rank's rows
+  }
+  if (!observed_sq) return;
+  if (dist_) comm_.allreduce_sum(scal_, 1);
+  ops_.d2h(observed_sq, scal_, sizeof(double));
+}
+
+int CpEngine::run_em(const ViewArgs &a, const void *mask, void *stream, const CpOpts &o, int inner_sweeps,
+                     int *iters, double *observed_res) {
+  const double t0 = now();
+  double sq = 0;
+  int k = 0;
+  bool on_tol = false, fresh = false;  // fresh: the tensor and sq belong to the current factors
+  while (k < o.maxiter) {
+    const bool look = k % o.resprint == 0;
+    impute(a, mask, stream, look ? &sq : nullptr);
+    fresh = look;
+    if (look) {
+      on_tol = std::sqrt(sq) <= o.tol;
+      if (on_tol || agree(now() - t0 > o.timelimit)) break;
+    }
+    for (int i = 0; i < inner_sweeps; i++) sweep_dt(o.lambda);
+    fresh = false;
+    k++;
+  }
+  if (!fresh) impute(a, mask, stream, &sq);
+  if (iters) *iters = k;
+  if (observed_res) *observed_res = std::sqrt(sq);
+  return on_tol ? 1 : 0;
 }
 
 // ---------------------------------------------------------------------------- kernel-level access

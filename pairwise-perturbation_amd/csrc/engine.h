@@ -20,10 +20,10 @@ struct TensorDesc {
   int dtype = F32;
   void *data = nullptr;
   int64_t nloc = 0;
-  // bumped by every fill / upload of the tensor (owned by the ppals_tensor handle; nullptr: the
+  // bumped by every fill / upload / imputation of the tensor (owned by the ppals_tensor handle; nullptr: the
   // contents never change). Sessions compare it with the generation their derived data (second
   // resident layout, cached contractions) was built from and rebuild when it moved.
-  const uint64_t *generation = nullptr;
+  uint64_t *generation = nullptr;
 };
 
 // leading-mode block partition shared by the tensor shard and the factor-matrix row blocks
@@ -124,6 +124,17 @@ class CpEngine {
   // the model [[W]] (residual: V - [[W]], V as stored) into this rank's rows of a checked export view
   // (ppals_cp_export_model_device); reads the session, changes nothing of it
   void export_model(const ViewArgs &a, void *dst, bool residual, void *stream);
+  // The missing entries (mask byte 0) of this rank's rows of a checked U8 import view `a` at `mask`
+  // become the model [[W]], rounded once to the storage type; everything else of the tensor stays bit
+  // for bit (ppals_cp_impute_device). Bumps the tensor's generation; the session's factors, Grams and
+  // gradients do not change. observed_sq == nullptr: asynchronous; otherwise *observed_sq = the sum of
+  // (V - model)^2 over the observed entries of the box, all ranks, and the call waits for it.
+  void impute(const ViewArgs &a, const void *mask, void *stream, double *observed_sq);
+  // EM with missing entries (ppals_cp_em): repeat { impute; inner_sweeps exact sweeps }, the observed
+  // residual looked at every o.resprint iterations; one last impute with the residual on the way out.
+  // Returns 1 if a look found the residual <= o.tol.
+  int run_em(const ViewArgs &a, const void *mask, void *stream, const CpOpts &o, int inner_sweeps,
+             int *iters, double *observed_res);
   const TensorDesc &tensor() const { return V_; }
 
   // kernel-level access for parity tests
@@ -386,6 +397,7 @@ class CpEngine {
   };
   bool plan_scan(int first, int k, bool natural_only, ScanPlan &plan);
   void check_tensor_generation();
+  void model_operands(const ModelBox &bx, ModelPlan &mp);  // xq_ / xp_ and the offsets of a grouped plan
   // s x R partials up to this size use one all-reduce + redundant update instead of
   // reduce-scatter + row-block update + all-gather (PPALS_COMM_SMALL_BYTES overrides)
   int64_t small_msg_bytes_ = 1 << 20;

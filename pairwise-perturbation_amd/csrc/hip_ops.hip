@@ -628,29 +628,29 @@ class HipOps : public Ops {
   hipEvent_t io_ev_in_ = nullptr, io_ev_out_ = nullptr;
 
   // ------------------------------------------------------------------ model through a view
-  template <typename D, typename TV, bool RES>
+  template <typename D, typename TV, int MODE>
   void mv_launch(dim3 grid, D *dst, const TV *V, const double *Q, const double *P, int K,
-                 const ModelPlan &mp, const int64_t *tab, int flags) {
+                 const ModelPlan &mp, const int64_t *tab, int flags, double *part = nullptr) {
     const int64_t A = mp.ga.count, B = mp.gb.count;
     const int64_t *tav = tab, *tar = tab + A, *tbv = tab + 2 * A, *tbr = tab + 2 * A + B;
     if (K <= 16)
-      hipLaunchKernelGGL((k_model_view<D, TV, RES, 4>), grid, dim3(256), 0, st_, dst, V, Q, P, K, mp,
-                         tav, tar, tbv, tbr, flags);
+      hipLaunchKernelGGL((k_model_view<D, TV, MODE, 4>), grid, dim3(256), 0, st_, dst, V, Q, P, K, mp,
+                         tav, tar, tbv, tbr, flags, part);
     else
-      hipLaunchKernelGGL((k_model_view<D, TV, RES, 16>), grid, dim3(256), 0, st_, dst, V, Q, P, K, mp,
-                         tav, tar, tbv, tbr, flags);
+      hipLaunchKernelGGL((k_model_view<D, TV, MODE, 16>), grid, dim3(256), 0, st_, dst, V, Q, P, K, mp,
+                         tav, tar, tbv, tbr, flags, part);
   }
   template <typename D>
   void mv_dispatch(dim3 grid, D *dst, const void *V, int dt, const double *Q, const double *P, int K,
                    bool residual, const ModelPlan &mp, const int64_t *tab, int flags) {
     if (!residual)
-      mv_launch<D, float, false>(grid, dst, nullptr, Q, P, K, mp, tab, flags);
+      mv_launch<D, float, MV_MODEL>(grid, dst, nullptr, Q, P, K, mp, tab, flags);
     else if (dt == F32)
-      mv_launch<D, float, true>(grid, dst, (const float *)V, Q, P, K, mp, tab, flags);
+      mv_launch<D, float, MV_RESIDUAL>(grid, dst, (const float *)V, Q, P, K, mp, tab, flags);
     else if (dt == BF16)
-      mv_launch<D, bf16s, true>(grid, dst, (const bf16s *)V, Q, P, K, mp, tab, flags);
+      mv_launch<D, bf16s, MV_RESIDUAL>(grid, dst, (const bf16s *)V, Q, P, K, mp, tab, flags);
     else
-      mv_launch<D, double, true>(grid, dst, (const double *)V, Q, P, K, mp, tab, flags);
+      mv_launch<D, double, MV_RESIDUAL>(grid, dst, (const double *)V, Q, P, K, mp, tab, flags);
   }
   void model_to_view(const ModelPlan &mp, const double *Q, const double *P, int K, bool residual,
                      void *view, int vdt, const void *V, int dt, void *caller_stream) override {
@@ -659,14 +659,8 @@ class HipOps : public Ops {
     if (A <= 0 || B <= 0) return;
     if (K < 1) throw std::runtime_error("ppals: model_to_view needs K >= 1");
     if (vdt != DV_F32 && vdt != DV_F64) throw std::runtime_error("ppals: bad model view dtype");
-    const int64_t ntA = (A + MV_TILE - 1) / MV_TILE, ntB = (B + MV_TILE - 1) / MV_TILE;
-    if (ntA > 0x7fffffff) throw std::runtime_error("ppals: model view too wide");
-    // the offset tables of both groups, built on the engine stream (nothing of the caller's is read)
-    int64_t *tab = (int64_t *)ensure(ws_mv_, ws_mv_sz_, sizeof(int64_t) * 2 * (size_t)(A + B));
-    hipLaunchKernelGGL(k_model_offsets, dim3(grid_for(A, 256)), dim3(256), 0, st_, mp.ga, tab, tab + A);
-    hipLaunchKernelGGL(k_model_offsets, dim3(grid_for(B, 256)), dim3(256), 0, st_, mp.gb, tab + 2 * A,
-                       tab + 2 * A + B);
-    HIP_CHECK(hipGetLastError());
+    dim3 grid;
+    const int64_t *tab = mv_tables(mp, &grid);
     const int vw = vdt == DV_F32 ? 4 : 2;
     const bool a_unit = mp.ga.view_unit();
     bool vec = a_unit && A % vw == 0 && mp.voff % vw == 0 &&
@@ -674,9 +668,6 @@ class HipOps : public Ops {
     for (int i = 0; i < mp.gb.n; i++)
       if (mp.gb.len[i] > 1 && mp.gb.vs[i] % vw != 0) vec = false;
     const int flags = (a_unit ? 1 : 0) | (vec ? 2 : 0) | (mp.ga.shard_unit() ? 4 : 0);
-    // a chip's worth of workgroups; each walks its share of the b tiles with its Q rows in registers
-    const int64_t want = std::max<int64_t>(1, ((int64_t)ncu_ * 8 + ntA - 1) / ntA);
-    const dim3 grid((unsigned)ntA, (unsigned)std::min<int64_t>(std::min<int64_t>(want, ntB), 65535));
     if (!io_ev_in_) {
       HIP_CHECK(hipEventCreateWithFlags(&io_ev_in_, hipEventDisableTiming));
       HIP_CHECK(hipEventCreateWithFlags(&io_ev_out_, hipEventDisableTiming));
@@ -691,6 +682,69 @@ class HipOps : public Ops {
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventRecord(io_ev_out_, st_));  // and the caller's later work waits for the stores
     HIP_CHECK(hipStreamWaitEvent(cs, io_ev_out_, 0));
+  }
+
+  // the offset tables of both groups of a plan, built on the engine stream (nothing of the caller's is
+  // read), and a chip's worth of workgroups, each walking its share of the b tiles
+  const int64_t *mv_tables(const ModelPlan &mp, dim3 *grid) {
+    const int64_t A = mp.ga.count, B = mp.gb.count;
+    const int64_t ntA = (A + MV_TILE - 1) / MV_TILE, ntB = (B + MV_TILE - 1) / MV_TILE;
+    if (ntA > 0x7fffffff) throw std::runtime_error("ppals: model view too wide");
+    int64_t *tab = (int64_t *)ensure(ws_mv_, ws_mv_sz_, sizeof(int64_t) * 2 * (size_t)(A + B));
+    hipLaunchKernelGGL(k_model_offsets, dim3(grid_for(A, 256)), dim3(256), 0, st_, mp.ga, tab, tab + A);
+    hipLaunchKernelGGL(k_model_offsets, dim3(grid_for(B, 256)), dim3(256), 0, st_, mp.gb, tab + 2 * A,
+                       tab + 2 * A + B);
+    HIP_CHECK(hipGetLastError());
+    const int64_t want = std::max<int64_t>(1, ((int64_t)ncu_ * 8 + ntA - 1) / ntA);
+    *grid = dim3((unsigned)ntA, (unsigned)std::min<int64_t>(std::min<int64_t>(want, ntB), 65535));
+    return tab;
+  }
+  template <typename T>
+  void impute_launch(dim3 grid, T *V, const uint8_t *mask, const double *Q, const double *P, int K,
+                     const ModelPlan &mp, const int64_t *tab, int flags, double *part) {
+    if (part)
+      mv_launch<T, uint8_t, MV_IMPUTE_SQ>(grid, V, mask, Q, P, K, mp, tab, flags, part);
+    else
+      mv_launch<T, uint8_t, MV_IMPUTE>(grid, V, mask, Q, P, K, mp, tab, flags);
+  }
+  void model_impute(const ModelPlan &plan, const double *Q, const double *P, int K, const void *mask,
+                    void *V, int dt, double *sumsq, void *caller_stream) override {
+    HIP_CHECK(hipSetDevice(dev_));
+    const int64_t A = plan.ga.count, B = plan.gb.count;
+    if (A <= 0 || B <= 0) {
+      if (sumsq) zero(sumsq, sizeof(double));
+      return;
+    }
+    if (K < 1) throw std::runtime_error("ppals: model_impute needs K >= 1");
+    const ModelPlan mp = dv_model_swapped(plan);  // the kernel's "view" is the shard, its "V" the mask
+    dim3 grid;
+    const int64_t *tab = mv_tables(mp, &grid);
+    const int64_t npart = (int64_t)grid.x * grid.y;
+    if (sumsq && npart > 0x7fffffff) throw std::runtime_error("ppals: model view too wide");
+    double *part = sumsq ? (double *)ensure(ws_part_, ws_part_sz_, sizeof(double) * npart) : nullptr;
+    // bit 0: the shard is unit-stride over A; bit 2: the mask is (its bytes are read in the store pass)
+    const int flags = (mp.ga.view_unit() ? 1 : 0) | (mp.ga.shard_unit() ? 4 : 0);
+    if (!io_ev_in_) {
+      HIP_CHECK(hipEventCreateWithFlags(&io_ev_in_, hipEventDisableTiming));
+      HIP_CHECK(hipEventCreateWithFlags(&io_ev_out_, hipEventDisableTiming));
+    }
+    hipStream_t cs = (hipStream_t)caller_stream;
+    HIP_CHECK(hipEventRecord(io_ev_in_, cs));  // the mask is ready once the caller's work so far is done
+    HIP_CHECK(hipStreamWaitEvent(st_, io_ev_in_, 0));
+    const uint8_t *m = (const uint8_t *)mask;
+    if (dt == F32)
+      impute_launch(grid, (float *)V, m, Q, P, K, mp, tab, flags, part);
+    else if (dt == BF16)
+      impute_launch(grid, (bf16s *)V, m, Q, P, K, mp, tab, flags, part);
+    else
+      impute_launch(grid, (double *)V, m, Q, P, K, mp, tab, flags, part);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(io_ev_out_, st_));  // and the caller may change the mask after the reads
+    HIP_CHECK(hipStreamWaitEvent(cs, io_ev_out_, 0));
+    if (sumsq) {
+      hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(1024), 0, st_, part, (int)npart, sumsq);
+      HIP_CHECK(hipGetLastError());
+    }
   }
 
   void *try_alloc(size_t bytes) override {

@@ -16,18 +16,32 @@
 // row) and leaves with the lane index along a: 16-byte stores when the view allows them. The residual
 // reads V along a when the shard is contiguous there, otherwise along b (lane index along b, into the
 // LDS image) before the store pass — the two sides of the tile are then each accessed coalesced.
+//
+// The impute modes (ppals_cp_impute_device) turn the kernel round: dst is the resident shard itself
+// (group A along the SHARD's fast side, the plan of dv_model_swapped) and the side read beside it is a
+// mask view of one byte per element. The store pass keeps the lane index along a and stores the model,
+// rounded once to the storage type, where the mask byte is 0: one plain vector store per lane under the
+// lane's own predicate, nothing else of the shard is written. The mask bytes come in along a when the
+// mask is unit-stride there, otherwise along b through a byte image in LDS (as the residual reads V).
+// With the observed residual wanted, a lane whose byte is non-zero reads V instead and adds
+// (V - model)^2 to its sum; the workgroup's sum goes to part[workgroup] and k_sum_partials adds those in
+// a fixed order.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
 #include "bf16.h"
 #include "device_view.h"
+#include "kernels_small.hip.h"  // block_sum (hip_ops.hip includes ops.h ahead of the kernel headers)
 
 namespace ppals {
 
 typedef double mv_f64x4 __attribute__((ext_vector_type(4)));
 
 constexpr int MV_TILE = 64;
+// what k_model_view stores: the model, V - model, or the model into the shard where a mask byte is 0
+// (MV_IMPUTE_SQ: and the sum of (V - model)^2 over the other elements)
+enum { MV_MODEL = 0, MV_RESIDUAL = 1, MV_IMPUTE = 2, MV_IMPUTE_SQ = 3 };
 
 // ov[i] / orr[i] = view / shard offset of flat index i of a mode group (first listed mode fastest)
 __global__ __launch_bounds__(256) void k_model_offsets(ModelGroup g, int64_t *__restrict__ ov,
@@ -62,22 +76,31 @@ struct alignas(16) mv_vec {
   T v[16 / sizeof(T)];
 };
 
-// D: destination element type (float / double); TV: the shard's storage type (read by the residual
-// only); RES: the residual; MAXRB: 4-wide contraction steps held in registers (more: Q is reloaded per
-// chunk of MAXRB steps). flags: bit 0 the view is unit-stride over A (offA(a) = a); bit 1 16-byte
-// stores (bit 0, and A, voff and every offB a multiple of the vector, dst aligned); bit 2 the shard is
-// contiguous over A (rA(a) = a: the residual reads V in the store pass). V may be dst itself (the second
-// pass of the two-pass residual, dst -= model: shard offsets = view offsets): every element is read and
-// then written by the same thread, or read before and written after a barrier.
-template <typename D, typename TV, bool RES, int MAXRB>
-__global__ __launch_bounds__(256) void k_model_view(D *dst, const TV *V,
-                                                    const double *__restrict__ Q,
-                                                    const double *__restrict__ P, int K, ModelPlan mp,
-                                                    const int64_t *__restrict__ tav,
-                                                    const int64_t *__restrict__ tar,
-                                                    const int64_t *__restrict__ tbv,
-                                                    const int64_t *__restrict__ tbr, int flags) {
+// The export modes (MV_MODEL, MV_RESIDUAL). D: destination element type (float / double); TV: the
+// shard's storage type (read by the residual only); MAXRB: 4-wide contraction steps held in registers
+// (more: Q is reloaded per chunk of MAXRB steps). flags: bit 0 the view is unit-stride over A
+// (offA(a) = a); bit 1 16-byte stores (bit 0, and A, voff and every offB a multiple of the vector, dst
+// aligned); bit 2 the shard is contiguous over A (rA(a) = a: the residual reads V in the store pass). V
+// may be dst itself (the second pass of the two-pass residual, dst -= model: shard offsets = view
+// offsets): every element is read and then written by the same thread, or read before and written
+// after a barrier.
+//
+// The impute modes (MV_IMPUTE, MV_IMPUTE_SQ) run on the plan of dv_model_swapped, so every name above
+// keeps its place and changes its tenant: dst (type D) is the shard, V (TV = uint8_t) the mask, the
+// "view" offsets (tav, tbv, voff, bit 0) are the shard's and the "shard" offsets (tar, tbr, roff, bit 2)
+// the mask's; bit 1 is never set. part: one sum per workgroup, MV_IMPUTE_SQ only.
+// With Q in registers (MAXRB = 4) the impute modes ask for two waves per SIMD, as the export modes get
+// unasked; without the bound the compiler went past 256 registers (one wave per SIMD, one workgroup
+// per CU). MAXRB = 16 (R > 16) spills in every mode, the export's included.
+template <typename D, typename TV, int MODE, int MAXRB>
+__global__ __launch_bounds__(256, (MODE >= MV_IMPUTE && MAXRB <= 4) ? 2 : 1) void k_model_view(
+    D *dst, const TV *V, const double *__restrict__ Q, const double *__restrict__ P, int K, ModelPlan mp,
+    const int64_t *__restrict__ tav, const int64_t *__restrict__ tar, const int64_t *__restrict__ tbv,
+    const int64_t *__restrict__ tbr, int flags, double *__restrict__ part) {
+  constexpr bool RES = MODE == MV_RESIDUAL, IMP = MODE == MV_IMPUTE || MODE == MV_IMPUTE_SQ;
   __shared__ double img[MV_TILE][MV_TILE + 1];
+  __shared__ uint8_t mimg[IMP ? MV_TILE : 1][IMP ? MV_TILE + 4 : 1];
+  double acc = 0.0;  // MV_IMPUTE_SQ: this thread's share of the observed residual
   __shared__ int64_t sav[MV_TILE], sar[MV_TILE], sbv[MV_TILE], sbr[MV_TILE];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = lane >> 4, j16 = lane & 15;
@@ -180,7 +203,53 @@ __global__ __launch_bounds__(256) void k_model_view(D *dst, const TV *V,
       __syncthreads();
     }
     // the store pass, lane index along a
-    if (vec_st) {
+    if constexpr (IMP) {
+      // Every load of a pass is issued before anything depends on one (a rejected element reads the
+      // tile's first, which exists): a load behind a branch, or behind a store it might alias, would
+      // wait out one memory latency per row, 16 of them per tile.
+      constexpr int NR = MV_TILE / 4;
+      const int64_t m0 = mp.roff + sar[0] + sbr[0];
+      if (!v_along_a) {  // the mask bytes with the lane index along b
+        uint8_t mb[NR];
+#pragma unroll
+        for (int i = 0; i < NR; i++) {
+          const int al = wave + 4 * i;
+          mb[i] = V[(al < na && lane < nb) ? mp.roff + sar[al] + sbr[lane] : m0];
+        }
+#pragma unroll
+        for (int i = 0; i < NR; i++) mimg[lane][wave + 4 * i] = mb[i];
+        __syncthreads();
+      }
+      const int al = lane;
+      const int64_t oa = a_unit ? a0 + al : sav[al < na ? al : 0];
+      const int64_t o0 = mp.voff + sbv[0] + (a_unit ? a0 : sav[0]);
+      // (in two halves of 8 rows: 16 rows of addresses and values in flight cost the second wave per SIMD)
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        constexpr int NH = NR / 2;
+        uint8_t m[NH];
+        D v[NH];
+#pragma unroll
+        for (int i = 0; i < NH; i++) {
+          const int bl = wave + 4 * (NH * h + i);
+          const bool ok = al < na && bl < nb;
+          m[i] = v_along_a ? V[ok ? mp.roff + sbr[bl] + sar[al] : m0] : mimg[bl][al];
+          if (MODE == MV_IMPUTE_SQ) v[i] = dst[ok ? mp.voff + sbv[bl] + oa : o0];
+        }
+#pragma unroll
+        for (int i = 0; i < NH; i++) {
+          const int bl = wave + 4 * (NH * h + i);
+          if (al < na && bl < nb) {
+            if (m[i] == 0) {
+              dst[mp.voff + sbv[bl] + oa] = (D)img[bl][al];
+            } else if (MODE == MV_IMPUTE_SQ) {
+              const double r = mv_load(&v[i]) - img[bl][al];
+              acc += r * r;
+            }
+          }
+        }
+      }
+    } else if (vec_st) {
       constexpr int VW = 16 / sizeof(D), TPR = MV_TILE / VW, RPP = 256 / TPR;
       const int al = (threadIdx.x % TPR) * VW;
       for (int bl = threadIdx.x / TPR; bl < nb; bl += RPP) {
@@ -206,6 +275,10 @@ __global__ __launch_bounds__(256) void k_model_view(D *dst, const TV *V,
       }
     }
     __syncthreads();  // the image and the b offsets are rewritten by the next tile
+  }
+  if constexpr (MODE == MV_IMPUTE_SQ) {
+    acc = block_sum(acc, &img[0][0]);
+    if (threadIdx.x == 0) part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = acc;
   }
 #undef PPALS_MV_LOAD_Q
 #undef PPALS_MV_LOAD_P

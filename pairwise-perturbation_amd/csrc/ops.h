@@ -160,6 +160,17 @@ class Ops {
                              const void * /*V*/, int /*dt*/, void * /*caller_stream*/) {
     throw Unsupported("ppals: this back end has no device views");
   }
+  // The imputation (ppals_cp_impute_device): where the byte of the mask view is 0,
+  //   V[roff + rA(a) + rB(b)] = the sum above, in fp64, rounded once to the storage type dt,
+  // and every other element of the shard V stays as it is. Here group A follows the SHARD's fast side and
+  // the view of the plan (vs, voff) is the mask, one byte per element. sumsq (device scalar, may be
+  // nullptr): the sum of (V - that sum)^2 over the elements whose byte is not 0, V as stored, formed in
+  // fp64 and added up in a fixed order. Ordered on `caller_stream` as copy_view; the host does not block.
+  virtual void model_impute(const ModelPlan & /*mp*/, const double * /*Q*/, const double * /*P*/,
+                            int /*K*/, const void * /*mask*/, void * /*V*/, int /*dt*/,
+                            double * /*sumsq*/, void * /*caller_stream*/) {
+    throw Unsupported("ppals: this back end has no device views");
+  }
 
   // ---- Khatri-Rao product, plain: out[j + J*c] = prod_f W_f[j_f + ld_f*(col0+c)], fp64 ----
   virtual void krp(double *out, const FactorRef *f, int nf, int col0, int ncols) = 0;

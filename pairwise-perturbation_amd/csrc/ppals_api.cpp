@@ -280,9 +280,9 @@ int ppals_tensor_norm(ppals_tensor *t, double *out) {
 // (`what` names the entry point in the messages; the model exports check their views here too)
 static int check_desc_view(ppals_ctx *ctx, const TensorDesc &d, const char *what, int dir,
                            const void *ptr, int dtype, const int64_t *box_lo, const int64_t *box_len,
-                           const int64_t *strides, ViewArgs *a) {
+                           const int64_t *strides, ViewArgs *a, bool mask = false) {
   std::string err;
-  if (!dv_check_args(dir, d.order, d.glens, dtype, box_lo, box_len, strides, a, &err)) {
+  if (!dv_check_args(dir, d.order, d.glens, dtype, box_lo, box_len, strides, a, &err, mask)) {
     g_err = what + err;
     return PPALS_ERR_ARG;
   }
@@ -472,6 +472,28 @@ int ppals_tucker_export_model_device(ppals_tucker *s, int what, void *dst, int d
   return PPALS_OK;
   API_END(PPALS_ERR_HIP)
 }
+// the mask of an imputation: every check ppals_tensor_check_device_view makes of an import source, for a
+// view of PPALS_U8 (a type the tensor import itself goes on refusing)
+static int check_mask_view(ppals_cp *s, const char *what, const void *mask, const int64_t *box_lo,
+                           const int64_t *box_len, const int64_t *strides, ViewArgs *a) {
+  if (!s || !s->eng || !s->ctx) return fail(PPALS_ERR_ARG, "NULL session");
+  if (!mask) {
+    g_err = std::string(what) + "the mask pointer is NULL";
+    return PPALS_ERR_ARG;
+  }
+  return check_desc_view(s->ctx, s->eng->tensor(), what, DV_IMPORT, mask, DV_U8, box_lo, box_len,
+                         strides, a, true);
+}
+int ppals_cp_impute_device(ppals_cp *s, const void *mask, const int64_t *box_lo, const int64_t *box_len,
+                           const int64_t *strides, void *stream, double *observed_sq) {
+  API_BEGIN
+  ViewArgs a;
+  const int rc = check_mask_view(s, "ppals_cp_impute_device: ", mask, box_lo, box_len, strides, &a);
+  if (rc != PPALS_OK) return rc;
+  s->eng->impute(a, mask, stream, observed_sq);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
 int ppals_tree_node(ppals_cp *s, const char *key, double *out, int64_t *n) {
   if (!s || !s->eng || !key) return fail(PPALS_ERR_ARG, "NULL argument");
   API_BEGIN
@@ -564,6 +586,20 @@ int ppals_cpd_als_lr(ppals_cp *s, int optimizer, int update_rank, int randomsvd,
   c.update_rank = update_rank;
   c.randomsvd = randomsvd;
   return s->eng->run_class(optimizer, c, sweeps, iters);
+  API_END(PPALS_ERR_HIP)
+}
+
+int ppals_cp_em(ppals_cp *s, const void *mask, const int64_t *box_lo, const int64_t *box_len,
+                const int64_t *strides, void *stream, const ppals_cp_opts *o, int inner_sweeps,
+                int *iters, double *observed_res) {
+  API_BEGIN
+  if (!o) return fail(PPALS_ERR_ARG, "ppals_cp_em: NULL options");
+  if (inner_sweeps < 1) return fail(PPALS_ERR_ARG, "ppals_cp_em: inner_sweeps must be at least 1");
+  if (o->maxiter < 0) return fail(PPALS_ERR_ARG, "ppals_cp_em: maxiter must not be negative");
+  ViewArgs a;
+  const int rc = check_mask_view(s, "ppals_cp_em: ", mask, box_lo, box_len, strides, &a);
+  if (rc != PPALS_OK) return rc;
+  return s->eng->run_em(a, mask, stream, to_opts(o), inner_sweeps, iters, observed_res);
   API_END(PPALS_ERR_HIP)
 }
 
