@@ -896,6 +896,10 @@ class HipOps : public Ops {
           dst_ns = K;
           dst_ss = (int64_t)ncols * K;
         }
+        if (al && M >= VEC)
+          route("scan.%s.prefix.fast nt=%d nsplit=%d out32=%d", tname<TV>(), NT, nsplit, out32);
+        else
+          route("scan.%s.prefix.generic al=%d nt=%d nsplit=%d out32=%d", tname<TV>(), al ? 1 : 0, NT, nsplit, out32);
         dim3 grid((unsigned)ncolgrp, (unsigned)nsplit);
         dim3 grid_il((unsigned)((K + 15) / 16), (unsigned)nsplit);  // interleaved-waves variant
         prof_begin(0, bytes);
@@ -970,6 +974,14 @@ class HipOps : public Ops {
         // cfg5, 625 tiles, 73 us — is a round and a quarter at 2 waves per SIMD; handing it to the
         // register-lean persistent form with 3 waves, k_scan_suffix_lean<2,4,0,3>, was measured:
         // 40 HOOI sweeps 0.0446 / 0.0443 s against 0.0442 / 0.0441 s. Not kept.)
+        if (takes_tail)
+          route("scan.%s.suffix.tail nt=%d from=%d", tname<TV>(), NT, scan_tail_split<TV>(NT, n_mtiles));
+        else if (takes_buf || (al && M >= VEC))
+          route("scan.%s.suffix.%s nt=%d nsplit=%d nts=%d pad=%d out32=%d", tname<TV>(), takes_buf ? "buf" : "fast",
+                NT, nsplit, nts ? 1 : 0, pad.ld ? 1 : 0, out32);
+        else
+          route("scan.%s.suffix.generic al=%d nt=%d nsplit=%d pad=%d out32=%d", tname<TV>(), al ? 1 : 0, NT, nsplit,
+                pad.ld ? 1 : 0, out32);
         if (takes_tail) {
           // a round and a bit of resident workgroups (cfg5's 625 tiles on 512 slots: 0.49 of the HBM
           // peak): the tiles of the last, partial round as four quarter-length work items each
@@ -1057,6 +1069,7 @@ class HipOps : public Ops {
     const int64_t nblocks = (int64_t)n_mtiles * nsplit * T;
     if (nblocks > 0x7fffffff) throw std::runtime_error("ppals: scan grid too large");
     const double bytes = (double)L * (double)J * (double)T * 4.0 + (double)L * (double)T * ncols * (out32 ? 4.0 : 8.0);
+    route("scan.f32.wide nt=%d nsplit=%d pad=%d out32=%d", NT, nsplit, pad.ld ? 1 : 0, out32);
     prof_begin(0, bytes);
     dispatch<5, 6, 7, 8>(NT, [&](auto nt) {
       hipLaunchKernelGGL((k_scan_wide<nt, 1>), dim3((unsigned)nblocks), dim3(512), 0, st_, V, M, K, M * K, P,
@@ -1135,6 +1148,7 @@ class HipOps : public Ops {
         const PassDst d = pass_dst(nsplit, M, T, ncols, o, out32, out_rstride, out_tstride, pad);
         const dim3 grid((unsigned)(n_mtiles64 * nsplit * T));
         const bool nts = nt_store(nsplit, (double)L * T * ncols * (out32 ? 4.0 : 8.0));
+        route("scan.bf16.mfma nsplit=%d nts=%d pad=%d out32=%d", nsplit, nts ? 1 : 0, pad.ld ? 1 : 0, out32);
         dispatch<true, false>(nts, [&](auto ntsv) {
           dispatch<true, false>(big, [&](auto bigv) {
             hipLaunchKernelGGL((k_scan_suffix_bf16<BF16_MAX_NT, ntsv, bigv>), grid, dim3(256), 0, st_, V, L, J, P,
@@ -1148,6 +1162,7 @@ class HipOps : public Ops {
       } else {
         double *B = (double *)ensure(ws_krp_, ws_krp_sz_, sizeof(double) * (size_t)J * ncols);
         krp(B, f, nf, col0, ncols);
+        route("%s", L == 1 ? "scan.bf16.prefix" : "scan.bf16.rows");
         if (L == 1)
           hipLaunchKernelGGL(k_scan_bf16_prefix<16 * BF16_MAX_NT>, dim3((unsigned)std::min<int64_t>((T + 3) / 4, 65536)),
                              dim3(256), 0,
@@ -1187,6 +1202,7 @@ class HipOps : public Ops {
         (double)ldw * Kc < 4e9) {
       RoctxRange roctx_("K11 mode product (batched thin GEMM)");
       const int nt = Kc <= 16 ? 1 : (Kc <= 32 ? 2 : 4);
+      route("ttm_keep.gemm nt=%d", nt);
       dim3 grid((unsigned)((L + 15) / 16), (unsigned)((Kc + 16 * nt - 1) / (16 * nt)), (unsigned)T);
       prof_begin(1, bytes);
       dispatch<1, 2, 4>(nt, [&](auto ntv) {
@@ -1202,16 +1218,20 @@ class HipOps : public Ops {
       HIP_CHECK(hipGetLastError());
       return;
     }
+    route("%s", "ttm_keep.scan");
     Ops::ttm_keep(X, dt, L, J, T, W, ldw, Kc, out);
   }
   bool ttm_lead_front(const void *X, int dt, int64_t J, int64_t S, int64_t T, const double *W, int64_t ldw,
                       int Kc, double *out) override {
     const double bytes = (double)J * S * T * dtype_size(dt);
     if (!(S >= 16 && J >= 16 && Kc <= 64 && bytes <= 64e6 && (double)J * S < 2e9 && T <= 65535 &&
-          (double)ldw * Kc < 4e9))
+          (double)ldw * Kc < 4e9)) {
+      route("%s", "ttm_lead.refused");
       return false;
+    }
     RoctxRange roctx_("K11 leading-mode product (batched thin GEMM)");
     const int nt = Kc <= 16 ? 1 : (Kc <= 32 ? 2 : 4);
+    route("ttm_lead.gemm nt=%d", nt);
     dim3 grid((unsigned)((S + 15) / 16), (unsigned)((Kc + 16 * nt - 1) / (16 * nt)), (unsigned)T);
     prof_begin(1, bytes);
     dispatch<1, 2, 4>(nt, [&](auto ntv) {
@@ -1272,6 +1292,7 @@ class HipOps : public Ops {
     if (L == 1) {
       int64_t nw = ((T + 3) / 4) * R;
       int g = grid_for(nw * 64, 256, 16384);
+      route("mttv.%s.1 extra=%d", tname<TX>(), extra);
       hipLaunchKernelGGL(k_mttv_1<TX>, dim3(g + extra), dim3(256), lds, st_, X, J, T, R, B, ldb, out, rs,
                          accumulate, scale, sys);
     } else if (L % VL == 0 && L >= 16 * VL && ((uintptr_t)X & 15) == 0 &&
@@ -1279,12 +1300,14 @@ class HipOps : public Ops {
       // streaming regime: enough (l-tile, t, r) waves to fill the chip on their own
       int64_t nb = ((L + 64 * VL - 1) / (64 * VL)) * T * R;
       int g = (int)std::min<int64_t>(nb, 1 << 20);
+      route("mttv.%s.vec extra=%d", tname<TX>(), extra);
       hipLaunchKernelGGL(k_mttv_vec<TX>, dim3(g + extra), dim3(64), lds, st_, X, L, J, T, R, B, ldb, out,
                          rs, accumulate, scale, sys);
     } else if (L < 64 && L * J <= 2048 && T * R >= 2048) {
       // a short plane per (t, r) and many of them: one wave each, no workgroup barrier (k_mttv_s)
       const int64_t nwaves = T * R;
       int g = (int)std::min<int64_t>((nwaves + 3) / 4, 16384);
+      route("mttv.%s.s extra=%d", tname<TX>(), extra);
       hipLaunchKernelGGL(k_mttv_s<TX>, dim3(g + extra), dim3(256), lds, st_, X, (int)L, J, T, R, B, ldb, out,
                          rs, accumulate, scale, sys);
     } else {
@@ -1299,12 +1322,14 @@ class HipOps : public Ops {
         double *partial = (double *)ensure(ws_mttv_, ws_mttv_sz_, sizeof(double) * (size_t)jsplit * L * T * R);
         const int64_t nbs = nb * jsplit;
         int g = (int)std::min<int64_t>(nbs, 32768);
+        route("mttv.%s.l4 jsplit=%d extra=%d", tname<TX>(), jsplit, extra);
         hipLaunchKernelGGL((k_mttv_l<TX, 4>), dim3(g + extra), dim3(256), lds, st_, X, L, J, T, R, B, ldb,
                            out, rs, accumulate, scale, sys, jsplit, jchunk, partial);
         hipLaunchKernelGGL(k_mttv_combine, dim3(grid_for(L * T * R, 256, 1024)), dim3(256), 0, st_, partial,
                            jsplit, L * T, R, out, rs, accumulate, scale);
       } else {
         int g = (int)std::min<int64_t>(nb, 32768);
+        route("mttv.%s.%s jsplit=1 extra=%d", tname<TX>(), nb * 4 < 1024 ? "l16" : "l4", extra);
         if (nb * 4 < 1024)  // few blocks: split the j loop 16 ways instead of 4
           hipLaunchKernelGGL((k_mttv_l<TX, 16>), dim3(g + extra), dim3(1024), lds, st_, X, L, J, T, R, B,
                              ldb, out, rs, accumulate, scale, sys);
@@ -1613,6 +1638,7 @@ class HipOps : public Ops {
       grid.x += 1;
       lds = sizeof(double) * (2 * (size_t)R * (R + 1) + 64) + sizeof(int) * 64;
     }
+    route("pp_correct terms=%d extra=%d", nterms, sys.Gall ? 1 : 0);
     prof_begin(1, 0.0);
     hipLaunchKernelGGL(k_pp_correct, grid, dim3(256), lds, st_, M0, rows, R, tm, M, sys);
     prof_end();
@@ -3409,6 +3435,18 @@ class HipOps : public Ops {
     return p;
   }
   double *small(int n) { return (double *)ensure(ws_small_, ws_small_sz_, sizeof(double) * n); }
+  // one tag of the route log (ops.h); nothing is formatted while no log is attached
+  template <typename... A>
+  void route(const char *fmt, A... a) {
+    if (!route_log) return;
+    char buf[160];
+    snprintf(buf, sizeof(buf), fmt, a...);
+    route_log->emplace_back(buf);
+  }
+  template <typename T>
+  static constexpr const char *tname() {
+    return sizeof(T) == 8 ? "f64" : "f32";
+  }
 
   // Where a pass of nsplit k-splits writes its ncols x M result (T batches): the output o itself, or
   // for nsplit > 1 the fp64 slab [split][batch][ncols][M] that slab_combine sums into o. A padded

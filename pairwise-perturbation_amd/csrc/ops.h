@@ -9,6 +9,8 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <string>
+#include <vector>
 
 #include "bf16.h"
 #include "device_view.h"
@@ -431,6 +433,10 @@ class Ops {
   virtual void profile_enable(int /*level*/) {}
   virtual void profile_collect() {}
   ProfileSlot prof[2];
+  // Route log (tests): when set, the product back end appends one short tag per kernel decision of
+  // the contraction launchers (tensor scans, mttv, the thin-GEMM mode products, pp_correct) — the kernel
+  // family and the facts that chose it. Null: nothing is formatted. The host stand-in logs nothing.
+  std::vector<std::string> *route_log = nullptr;
 };
 
 class Comm {

@@ -34,6 +34,7 @@ inline double u01(uint64_t seed, uint64_t idx) {
   return (double)(h >> 11) * (1.0 / 9007199254740992.0);
 }
 inline double ld(const void *V, int dt, int64_t e) {
+  if (dt == BF16) return (double)bf16_bits_to_float(((const uint16_t *)V)[e]);  // (op-level tests only)
   return dt == F32 ? (double)((const float *)V)[e] : ((const double *)V)[e];
 }
 inline void st(void *V, int dt, int64_t e, double v) {

@@ -1,0 +1,157 @@
+// ops_shim.cpp — TEST INFRASTRUCTURE: a C surface over ppals::Ops for the op-level tests of the
+// contraction kernels (tests/contraction_cases.py). One source, two libraries: linked against the
+// product's libppals.so it reaches the HIP kernels as compiled there, linked against the host stand-in
+// it reaches HostOps. No HIP code and no HIP calls here: every device action goes through the Ops.
+// Every function returns 0, or -1 after an exception whose text shim_error() then returns (the
+// launchers' own refusals — "padded rows inconsistent" — arrive that way).
+#include <cstring>
+#include <exception>
+#include <string>
+#include <vector>
+
+#include "backend.h"
+
+using namespace ppals;
+
+namespace {
+struct Shim {
+  Ops *ops = nullptr;
+  std::vector<std::string> log;
+  std::string err, joined;
+};
+std::string g_create_err;
+
+template <typename F>
+int guarded(Shim *s, F &&f) {
+  try {
+    s->ops->bind();
+    f();
+    return 0;
+  } catch (const std::exception &e) {
+    s->err = e.what();
+  } catch (...) {
+    s->err = "unknown exception";
+  }
+  return -1;
+}
+std::vector<FactorRef> factors(const double *const *ptr, const int64_t *rows, const int64_t *ld, int nf) {
+  std::vector<FactorRef> f((size_t)nf);
+  for (int i = 0; i < nf; i++) f[i] = FactorRef{ptr[i], rows[i], ld[i]};
+  return f;
+}
+}  // namespace
+
+extern "C" {
+const char *shim_backend() { return backend_name(); }
+void *shim_create(int device) {
+  Shim *s = new Shim;
+  try {
+    s->ops = backend_make_ops(device);
+    return s;
+  } catch (const std::exception &e) {
+    g_create_err = e.what();
+  } catch (...) {
+    g_create_err = "unknown exception";
+  }
+  delete s;
+  return nullptr;
+}
+const char *shim_create_error() { return g_create_err.c_str(); }
+void shim_destroy(void *h) {
+  Shim *s = (Shim *)h;
+  if (!s) return;
+  try {
+    delete s->ops;
+  } catch (...) {
+  }
+  delete s;
+}
+const char *shim_error(void *h) { return ((Shim *)h)->err.c_str(); }
+
+int shim_alloc(void *h, size_t bytes, void **out) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { *out = s->ops->alloc(bytes); });
+}
+int shim_free(void *h, void *p) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->free(p); });
+}
+int shim_h2d(void *h, void *dst, const void *src, size_t bytes) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->h2d(dst, src, bytes); });
+}
+int shim_d2h(void *h, void *dst, const void *src, size_t bytes) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->d2h(dst, src, bytes); });
+}
+int shim_sync(void *h) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->sync(); });
+}
+int shim_scan_store_mode(void *h, int mode) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->scan_store_mode(mode); });
+}
+
+int shim_scan_contract(void *h, const void *V, int dt, int64_t L, int64_t J, int64_t T, const double *const *fptr,
+                       const int64_t *frows, const int64_t *fld, int nf, int R, void *out, int out_dt,
+                       int64_t out_tstride, int64_t out_rstride, int64_t pad_ld, int64_t pad_valid) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] {
+    const std::vector<FactorRef> f = factors(fptr, frows, fld, nf);
+    RowPad pad;
+    pad.ld = pad_ld;
+    pad.valid = pad_valid;
+    s->ops->scan_contract(V, dt, L, J, T, f.data(), nf, R, out, out_dt, out_tstride, out_rstride, pad);
+  });
+}
+int shim_mttv(void *h, const void *X, int xdt, int64_t L, int64_t J, int64_t T, const double *const *fptr,
+              const int64_t *frows, const int64_t *fld, int nf, int R, double *out, int64_t out_rstride,
+              int accumulate, const double *out_scale) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] {
+    const std::vector<FactorRef> f = factors(fptr, frows, fld, nf);
+    s->ops->mttv(X, xdt, L, J, T, f.data(), nf, R, out, out_rstride, accumulate, out_scale);
+  });
+}
+int shim_ttm_keep(void *h, const void *X, int dt, int64_t L, int64_t J, int64_t T, const double *W, int64_t ldw,
+                  int Kc, double *out) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->ttm_keep(X, dt, L, J, T, W, ldw, Kc, out); });
+}
+int shim_ttm_lead_front(void *h, const void *X, int dt, int64_t J, int64_t S, int64_t T, const double *W,
+                        int64_t ldw, int Kc, double *out, int *taken) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { *taken = s->ops->ttm_lead_front(X, dt, J, S, T, W, ldw, Kc, out) ? 1 : 0; });
+}
+int shim_pp_correct(void *h, const double *M0, int64_t rows, int R, const double *const *T, const int64_t *ny,
+                    const int *keep_first, const double *const *dW, const int64_t *lddw, int nterms, double *M) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] {
+    std::vector<PPTerm> tm((size_t)nterms);
+    for (int t = 0; t < nterms; t++) tm[t] = PPTerm{T[t], ny[t], keep_first[t], dW[t], lddw[t]};
+    s->ops->pp_correct(M0, rows, R, tm.data(), nterms, M);
+  });
+}
+int shim_arm_gram_system(void *h, const double *Gall, int N, int mode, int R, double lambda, double *S,
+                         double *Sinv) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->arm_gram_system(Gall, N, mode, R, lambda, S, Sinv); });
+}
+
+// the route log (ops.h): attach (on != 0) or detach, read as one newline-joined string, clear
+void shim_route_attach(void *h, int on) {
+  Shim *s = (Shim *)h;
+  s->ops->route_log = on ? &s->log : nullptr;
+}
+const char *shim_route_read(void *h) {
+  Shim *s = (Shim *)h;
+  s->joined.clear();
+  for (const std::string &t : s->log) {
+    if (!s->joined.empty()) s->joined += '\n';
+    s->joined += t;
+  }
+  return s->joined.c_str();
+}
+void shim_route_clear(void *h) { ((Shim *)h)->log.clear(); }
+}

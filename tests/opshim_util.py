@@ -1,0 +1,159 @@
+"""Loads tests/opshim (TEST INFRASTRUCTURE: a C surface over ppals::Ops, see ops_shim.cpp) through ctypes:
+kind "hip" is the product's Ops over the HIP kernels of libppals.so, kind "host" the host stand-in. Neither
+needs torch; the library is built on first use, as hipsim_util.load does."""
+import ctypes as C
+import glob
+import os
+import subprocess
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DIR = os.path.join(ROOT, "tests", "opshim")
+F32, F64, BF16 = 0, 1, 3
+_libs = {}
+
+_P, _I64, _I = C.c_void_p, C.c_int64, C.c_int
+_SIGS = {
+    "shim_alloc": [_P, C.c_size_t, C.POINTER(_P)],
+    "shim_free": [_P, _P],
+    "shim_h2d": [_P, _P, _P, C.c_size_t],
+    "shim_d2h": [_P, _P, _P, C.c_size_t],
+    "shim_sync": [_P],
+    "shim_scan_store_mode": [_P, _I],
+    "shim_scan_contract": [_P, _P, _I, _I64, _I64, _I64, C.POINTER(_P), C.POINTER(_I64), C.POINTER(_I64), _I, _I,
+                           _P, _I, _I64, _I64, _I64, _I64],
+    "shim_mttv": [_P, _P, _I, _I64, _I64, _I64, C.POINTER(_P), C.POINTER(_I64), C.POINTER(_I64), _I, _I, _P, _I64,
+                  _I, _P],
+    "shim_ttm_keep": [_P, _P, _I, _I64, _I64, _I64, _P, _I64, _I, _P],
+    "shim_ttm_lead_front": [_P, _P, _I, _I64, _I64, _I64, _P, _I64, _I, _P, C.POINTER(_I)],
+    "shim_pp_correct": [_P, _P, _I64, _I, C.POINTER(_P), C.POINTER(_I64), C.POINTER(_I), C.POINTER(_P),
+                        C.POINTER(_I64), _I, _P],
+    "shim_arm_gram_system": [_P, _P, _I, _I, _I, C.c_double, _P, _P],
+}
+
+
+def load(kind, make=True):
+    if kind not in _libs:
+        path = os.path.join(DIR, "build", f"libopshim_{kind}.so")
+        if make or not os.path.exists(path):
+            subprocess.check_call(["make", "-s", "-C", DIR, kind])
+        lib = C.CDLL(path)
+        for name, args in _SIGS.items():
+            f = getattr(lib, name)
+            f.argtypes, f.restype = args, _I
+        lib.shim_create.argtypes, lib.shim_create.restype = [_I], _P
+        lib.shim_destroy.argtypes, lib.shim_destroy.restype = [_P], None
+        lib.shim_route_attach.argtypes, lib.shim_route_attach.restype = [_P, _I], None
+        lib.shim_route_clear.argtypes, lib.shim_route_clear.restype = [_P], None
+        for name in ("shim_error", "shim_route_read"):
+            getattr(lib, name).argtypes, getattr(lib, name).restype = [_P], C.c_char_p
+        for name in ("shim_backend", "shim_create_error"):
+            getattr(lib, name).argtypes, getattr(lib, name).restype = [], C.c_char_p
+        _libs[kind] = lib
+    return _libs[kind]
+
+
+class ShimError(RuntimeError):
+    """an exception of the back end, caught in the shim"""
+
+
+def _arr(ctype, vals):
+    return (ctype * max(1, len(vals)))(*vals)
+
+
+class Shim:
+    """One Ops of the back end `kind`, with its route log attached."""
+
+    def __init__(self, kind, device=0):
+        self.kind, self.lib = kind, load(kind)
+        self.h = self.lib.shim_create(device)
+        if not self.h:
+            raise ShimError(self.lib.shim_create_error().decode())
+        self.lib.shim_route_attach(self.h, 1)
+
+    def close(self):
+        if self.h:
+            self.lib.shim_destroy(self.h)
+            self.h = None
+
+    def _ck(self, rc):
+        if rc != 0:
+            raise ShimError(self.lib.shim_error(self.h).decode())
+
+    # ---- memory: device pointers are plain integers
+    def alloc(self, nbytes):
+        p = _P()
+        self._ck(self.lib.shim_alloc(self.h, nbytes, C.byref(p)))
+        return p.value
+
+    def free(self, p):
+        self._ck(self.lib.shim_free(self.h, p))
+
+    def h2d(self, dst, a):
+        a = np.ascontiguousarray(a)
+        self._ck(self.lib.shim_h2d(self.h, dst, a.ctypes.data, a.nbytes))
+
+    def d2h(self, src, nbytes):
+        out = np.empty(nbytes, np.uint8)
+        self._ck(self.lib.shim_d2h(self.h, out.ctypes.data, src, nbytes))
+        return out
+
+    def sync(self):
+        self._ck(self.lib.shim_sync(self.h))
+
+    # ---- the route log
+    def route_take(self):
+        tags = self.lib.shim_route_read(self.h).decode()
+        self.lib.shim_route_clear(self.h)
+        return tags.split("\n") if tags else []
+
+    # ---- the ops; factors: list of (device pointer, rows, ld)
+    def scan_store_mode(self, mode):
+        self._ck(self.lib.shim_scan_store_mode(self.h, mode))
+
+    @staticmethod
+    def _factors(factors):
+        return (_arr(_P, [f[0] for f in factors]), _arr(_I64, [f[1] for f in factors]),
+                _arr(_I64, [f[2] for f in factors]), len(factors))
+
+    def scan_contract(self, V, dt, L, J, T, factors, R, out, out_dt, ts, rs, pad=(0, 0)):
+        self._ck(self.lib.shim_scan_contract(self.h, V, dt, L, J, T, *self._factors(factors), R, out, out_dt, ts, rs,
+                                             pad[0], pad[1]))
+
+    def mttv(self, X, xdt, L, J, T, factors, R, out, rs, accumulate, out_scale):
+        self._ck(self.lib.shim_mttv(self.h, X, xdt, L, J, T, *self._factors(factors), R, out, rs, accumulate,
+                                    out_scale))
+
+    def ttm_keep(self, X, dt, L, J, T, W, ldw, Kc, out):
+        self._ck(self.lib.shim_ttm_keep(self.h, X, dt, L, J, T, W, ldw, Kc, out))
+
+    def ttm_lead_front(self, X, dt, J, S, T, W, ldw, Kc, out):
+        taken = _I(0)
+        self._ck(self.lib.shim_ttm_lead_front(self.h, X, dt, J, S, T, W, ldw, Kc, out, C.byref(taken)))
+        return bool(taken.value)
+
+    def pp_correct(self, M0, rows, R, terms, M):
+        """terms: list of (T pointer, ny, keep_first, dW pointer, lddw)"""
+        self._ck(self.lib.shim_pp_correct(self.h, M0, rows, R, _arr(_P, [t[0] for t in terms]),
+                                          _arr(_I64, [t[1] for t in terms]), _arr(_I, [t[2] for t in terms]),
+                                          _arr(_P, [t[3] for t in terms]), _arr(_I64, [t[4] for t in terms]),
+                                          len(terms), M))
+
+    def arm_gram_system(self, Gall, N, mode, R, lam, S, Sinv):
+        self._ck(self.lib.shim_arm_gram_system(self.h, Gall, N, mode, R, lam, S, Sinv))
+
+
+def compute_units():
+    """The compute-unit count of the first GPU in the KFD topology (what the launchers' device-dependent
+    rules see as multiProcessorCount), or None where there is no such node."""
+    for path in sorted(glob.glob("/sys/class/kfd/kfd/topology/nodes/*/properties")):
+        try:
+            with open(path) as f:
+                props = dict(line.split()[:2] for line in f if len(line.split()) >= 2)
+            simd, per = int(props.get("simd_count", 0)), int(props.get("simd_per_cu", 0))
+        except (OSError, ValueError):
+            continue
+        if simd > 0 and per > 0:
+            return simd // per
+    return None
