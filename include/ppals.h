@@ -171,6 +171,23 @@ int ppals_cp_get_factors(ppals_cp *s, double *Wflat, double *gradWflat /*may be 
 #define PPALS_SCHEDULE_MSDT 1
 int ppals_cp_set_schedule(ppals_cp *s, int schedule);
 int ppals_cp_get_schedule(const ppals_cp *s);
+/* Non-negative CP. With the flag on, every mode update of the session is one pass of Cichocki-Phan
+ * HALS instead of the solve of the normal equations: with M the mode's MTTKRP and S the Hadamard
+ * product of the other modes' Grams + lambda I, for every row x and r = 0 .. R-1 in this order
+ *   w[x,r] <- max(PPALS_NN_FLOOR, w[x,r] + (M[x,r] - sum_q w[x,q] S[q,r]) / S[r,r])
+ * (fp64; the sum takes the row's entries already updated; a column whose S[r,r] is not a positive
+ * finite number stays). The floor is not zero, so no column can die under Normalize, which scales
+ * columns by positive numbers and so keeps the constraint. grad_W, gradnorm and the residual keep
+ * their meaning. The tensor scans, both schedules and the drivers built on exact sweeps
+ * (ppals_cp_sweeps_dt, ppals_cp_dt, ppals_cpd_als, ppals_cp_em) run unchanged on top.
+ * PPALS_ERR_UNSUPPORTED, before anything is launched: turning the flag on in a context of more than one
+ * rank or at R > 64, and on a non-negative session ppals_cp_pp, ppals_cp_pp_partupdate,
+ * ppals_cpd_als_lr and ppals_cp_multi_take. PPALS_ERR_ARG: factors with a negative or non-finite entry
+ * — those already set when the flag is turned on (the flag then stays off), and those handed to
+ * ppals_cp_set_factors later. ppals_cp_get_nonneg: 1 / 0, PPALS_ERR_ARG for a NULL session. */
+#define PPALS_NN_FLOOR 1e-16
+int ppals_cp_set_nonneg(ppals_cp *s, int on);
+int ppals_cp_get_nonneg(const ppals_cp *s);
 /* Where the multi-sweep schedule's first-level intermediates lie (no counterpart in the reference:
  * CTF places its own buffers). The choice is made ONLINE: the first ~20 visits of a root run the
  * sweep's own scan at a different offset / store kind of the result, timed on the stream; then the

@@ -667,6 +667,29 @@ void CpEngine::set_factors(const double *Wflat, const double *gradWflat) {
   ms_invalidate();
 }
 
+// The session's mode updates become HALS passes (Ops::cp_mode_update_nn). Everything that cannot run
+// that way is refused here, before anything is launched, and leaves the flag as it was.
+void CpEngine::set_nonneg(bool on) {
+  if (on) {
+    if (multi_) throw Unsupported("ppals: a multi-start session has no non-negative update");
+    if (P_ > 1 || dist_) throw Unsupported("ppals: a non-negative session runs on one rank");
+    if (R_ > 64) throw Unsupported("ppals: a non-negative session supports R <= 64");
+    if (test_blocks_ > 1)
+      throw Unsupported("ppals: PPALS_TEST_BLOCKED_UPDATE has no non-negative update");
+  }
+  nonneg_ = on;
+}
+
+bool CpEngine::factors_nonneg() {
+  for (int i = 0; i < N_; i++) {
+    std::vector<double> h((size_t)V_.glens[i] * R_);
+    ops_.d2h(h.data(), W_[i], sizeof(double) * h.size());
+    for (double v : h)
+      if (!(v >= 0) || !std::isfinite(v)) return false;
+  }
+  return true;
+}
+
 // ---------------------------------------------------------------------------- multi-start sessions
 // One start's factors are the column block [b Rs, (b+1) Rs) of every W_[i]: s_i * Rs contiguous doubles.
 void CpEngine::set_factors_start(int start, const double *Wflat, const double *gradWflat) {
@@ -769,6 +792,7 @@ int CpEngine::run_multi(const CpOpts &o, int *sweeps_out, int *best_out) {
 
 void CpEngine::take_from(CpEngine &src, int start) {
   if (multi_ || dist_) throw std::logic_error("ppals: the destination must be an ordinary one-rank session");
+  if (nonneg_) throw Unsupported("ppals: a non-negative session does not take a multi-start's factors");
   if (!src.multi_ || start < 0 || start >= src.K_ || src.Rs_ != R_ || src.N_ != N_ ||
       src.V_.data != V_.data)
     throw std::runtime_error("ppals: take: sessions do not match");
@@ -823,6 +847,11 @@ void CpEngine::mode_update(int i, const double *M, int64_t ldm, double lambda, b
     return;
   }
   double *Gi = G_ + (size_t)i * R_ * R_;
+  if (nonneg_) {  // one HALS pass in place of the solve (set_nonneg admits one-rank sessions only)
+    if (pp || dist_) throw std::logic_error("ppals: a non-negative session updates exactly, on one rank");
+    ops_.cp_mode_update_nn(G_, N_, i, R_, lambda, M, ldm, W_[i], s, gradW_[i], s, s, gradsq_ + i, S_);
+    return;
+  }
   if (!dist_) {
     if (test_blocks_ > 1 && s % test_blocks_ == 0 && !pp) {
       // test hook (PPALS_TEST_BLOCKED_UPDATE=P, one rank): the update reads its M in P row blocks, as the
@@ -1378,13 +1407,13 @@ void CpEngine::ms_mode_update(int i, double lambda, bool last_of_sweep) {
   const int leaf = ms_leaf_[pos];
   // (S and S^-1 of this update depend on the other modes' Grams only: the contraction launched
   // next may prepare them on the side)
-  if (!multi_) ops_.arm_gram_system(G_, N_, i, R_, lambda, S_, Sinv_);
+  if (!multi_ && !nonneg_) ops_.arm_gram_system(G_, N_, i, R_, lambda, S_, Sinv_);
   ms_compute(leaf);
   ms_norm_fused_ = false;
   // the sweep's Normalize at the tail of its last update launch, with the pending scales of the cached
   // tensors that outlive the update (everything valid now but the leaf it consumes) — where the update
   // is the fused launch: one rank, or the one-all-reduce plan of a sharded session (never mode 0's)
-  if (last_of_sweep && !multi_ && (!dist_ || (i != 0 && (int64_t)sizeof(double) * V_.glens[i] * R_ <= small_msg_bytes_))) {
+  if (last_of_sweep && !multi_ && !nonneg_ && (!dist_ || (i != 0 && (int64_t)sizeof(double) * V_.glens[i] * R_ <= small_msg_bytes_))) {
     int64_t rows[MAX_ORDER];
     for (int q = 0; q < N_; q++) rows[q] = V_.glens[q];
     // (asked first with no cached tensors — a back end that cannot fold it must not see them marked)
@@ -1467,7 +1496,7 @@ void CpEngine::sweep_dt(double lambda) {
   for (int i = 0; i < N_; i++) {
     compute_node(leaf_[i]);
     const Node &lf = nodes_[leaf_[i]];
-    if (i == N_ - 1 && !dist_) {  // Normalize at the tail of the sweep's last update launch
+    if (i == N_ - 1 && !dist_ && !nonneg_) {  // Normalize at the tail of the sweep's last update launch
       int64_t rows[MAX_ORDER];
       for (int q = 0; q < N_; q++) rows[q] = V_.glens[q];
       norm_fused = ops_.arm_normalize(W_.data(), rows, N_, R_, G_, i, nullptr);
@@ -1755,6 +1784,7 @@ void CpEngine::lr_mode_update(int i, double lambda, int r, const double *base) {
 int CpEngine::run_class(int kind, const CpOpts &o, double *sweeps_out, int *iters_out) {
   if (kind < 0 || kind > 4) throw std::runtime_error("ppals: unknown class-API optimizer");
   const bool lr = kind >= 3;
+  if (lr && nonneg_) throw Unsupported("ppals: a non-negative session has no low-rank-update optimizer");
   if (lr) {
     if (dist_) throw std::runtime_error("ppals: the low-rank-update optimizers run on one GPU");
     if (N_ < 3) throw std::runtime_error("ppals: the low-rank-update optimizers need order >= 3");
@@ -2413,6 +2443,8 @@ int64_t CpEngine::pp_operator(const std::string &contracted, double *out_host) {
 // first-order corrections, ONE for the whole mode update (which also leaves ||dW_i||^2); the
 // Normalize launch leaves ||W_i||^2: the restart test of the next iteration costs no launch.
 void CpEngine::sweep_pp(double lambda, double ratio) {
+  // (the armed S / Normalize below are consumed by cp_mode_update, which a non-negative session never calls)
+  if (nonneg_) throw Unsupported("ppals: a non-negative session has no pairwise-perturbation sweep");
   ms_invalidate();  // PP moves the factors without touching the multi-sweep cache
   if (!Mbuf_) Mbuf_ = (double *)ops_.alloc(sizeof(double) * (size_t)maxs_ * R_);
   if (!pp_norms_) {
@@ -2631,6 +2663,7 @@ int CpEngine::run_pp_partupdate(const CpOpts &o, int *iters) {
 }
 
 int CpEngine::run_pp_common(const CpOpts &o, int *iters, bool partupdate) {
+  if (nonneg_) throw Unsupported("ppals: a non-negative session has no pairwise-perturbation driver");
   if (partupdate && rank_ == 0 && o.verbose) std::cout << "alsCP_PP_partupdate starts. " << std::endl;
   for (int i = 0; i < N_; i++) {
     size_t n = sizeof(double) * V_.glens[i] * R_;

@@ -99,6 +99,12 @@ class CpEngine {
 
   void set_factors(const double *Wflat, const double *gradWflat);
   void set_schedule(int schedule);
+  // Non-negative CP: every mode update is one HALS pass (Ops::cp_mode_update_nn) instead of the solve.
+  // Exact sweeps and what is built on them (run_dt, run_class 0-2, run_em) work unchanged; PP, the
+  // low-rank optimizers, multi-start, more than one rank and R > 64 throw Unsupported.
+  void set_nonneg(bool on);
+  bool nonneg() const { return nonneg_; }
+  bool factors_nonneg();  // downloads the factors: every entry finite and >= 0
   int schedule() const { return schedule_; }
   // one JSON object: where the online placement choice put every root's first-level intermediate
   // (block, offset, store kind, fastest / slowest sample, settled or still exploring)
@@ -355,6 +361,7 @@ class CpEngine {
   // system per start, gradsq_ K_ sums per mode (gradsq_[mode * K_ + start])
   int K_ = 1, Rs_ = 0;
   bool multi_ = false;
+  bool nonneg_ = false;  // set_nonneg
   bool dist_ = false;  // take the collective code paths (P_ > 1, or PPALS_FORCE_COMM=1 for tests)
   std::vector<double *> W_, gradW_, Wprev_, Winit_, dW_, dM_, Mm_;
   double *G_ = nullptr;       // N Gram matrices, R*R each

@@ -18,6 +18,7 @@
 #include "preload_policy.h"
 #include "kernels_scan.hip.h"
 #include "kernels_small.hip.h"
+#include "kernels_nn.hip.h"
 #include "kernels_eig.hip.h"
 #include "kernels_io.hip.h"
 #include "kernels_model.hip.h"
@@ -1532,6 +1533,31 @@ class HipOps : public Ops {
                          S, Sinv, dwsq, presolved);
     }
     HIP_CHECK(hipGetLastError());
+  }
+  // The non-negative (HALS) mode update (kernels_nn.hip.h): rows over one-wave workgroups of 64, the
+  // tiles' partial sums of grad^2 added by k_sum_partials, the Gram refresh by the gram op — three
+  // short launches, each a fixed summation order.
+  void cp_mode_update_nn(double *Gall, int N, int mode, int R, double lambda, const double *M, int64_t ldm,
+                         double *W, int64_t ldw, double *grad, int64_t ldg, int64_t rows, double *gradsq,
+                         double *S) override {
+    RoctxRange roctx_("K4-K6 mode update (non-negative)");
+    if (R > 64) throw Unsupported("ppals: the non-negative mode update supports R <= 64");
+    if (sys_armed_ || sys_ready_ || norm_armed_)
+      throw std::logic_error("ppals: armed S / Normalize in front of a non-negative mode update");
+    if (rows <= 0) {
+      HIP_CHECK(hipMemsetAsync(gradsq, 0, sizeof(double), st_));
+      gram(W, rows, ldw, R, Gall + (size_t)mode * R * R);
+      return;
+    }
+    const int64_t nb = (rows + 63) / 64;
+    if (nb > (int64_t)1 << 30) throw std::runtime_error("ppals: mode too long for the non-negative update");
+    double *part = (double *)ensure(ws_big2_, ws_big2_sz_, sizeof(double) * (size_t)nb);
+    const size_t lds = sizeof(double) * ((size_t)R * R + 64 * (size_t)R);
+    hipLaunchKernelGGL(k_cp_update_nn, dim3((unsigned)nb), dim3(64), lds, st_, Gall, N, mode, R, lambda, M,
+                       ldm, W, ldw, grad, ldg, rows, part, S, kNnFloor);
+    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(1024), 0, st_, part, (int)nb, gradsq);
+    HIP_CHECK(hipGetLastError());
+    gram(W, rows, ldw, R, Gall + (size_t)mode * R * R);
   }
   // The mode updates of all starts of a multi-start session in ONE launch: a 1024-thread workgroup per
   // start (nstarts <= 32 of them on 256 CUs: every workgroup has a CU and its LDS to itself, none waits

@@ -1,0 +1,68 @@
+// kernels_nn.hip.h — the non-negative (HALS) mode update of a CP session (Ops::cp_mode_update_nn).
+// hadamard_entry, wave_sum and k_sum_partials come from kernels_small.hip.h.
+#pragma once
+#include "kernels_small.hip.h"
+
+namespace ppals {
+
+// One pass of Cichocki-Phan HALS over the rows of one mode, fp64. A workgroup is ONE wave and owns a
+// tile of 64 rows, a lane one row. Every workgroup forms S = Hadamard of the other modes' Grams
+// + lambda I in LDS itself (N R^2 reads out of L2: nothing beside a launch), so no launch precedes this one.
+//
+// The lane's row lives in LDS, not in registers: sW[q * 64 + lane], so the 64 lanes of a read hit 64
+// consecutive doubles (no bank conflict) and the rolled loops index it by q. A register array would
+// need both loops unrolled — 2 * 64 * 64 multiply-adds of straight-line code at R = 64, more than
+// the instruction cache — and one instantiation per rank bound. S[q, r] is the same address for
+// every lane: an LDS broadcast. LDS: (R^2 + 64 R) doubles = 64 KB at R = 64, two workgroups per CU.
+//
+//   grad[x, r] = -M[x, r] + sum_q w_old[x, q] S[q, r]                       (pre-update row)
+//   w[x, r]   <- max(nn_floor, w[x, r] + (M[x, r] - sum_q w[x, q] S[q, r]) / S[r, r])   r = 0 .. R-1
+// (the second sum sees the entries already updated, q < r); a column whose S[r, r] is not a positive
+// finite number stays. A lane reads and writes its own row of W only, so W is updated in place.
+// gradsq_part[workgroup] = the tile's sum of grad^2, lanes added in the fixed order of wave_sum;
+// k_sum_partials adds the tiles. Workgroup 0 stores S when asked.
+__global__ __launch_bounds__(64) void k_cp_update_nn(
+    const double *__restrict__ Gall, int N, int mode, int R, double lambda,
+    const double *__restrict__ M, int64_t ldm, double *__restrict__ W, int64_t ldw,
+    double *__restrict__ grad, int64_t ldg, int64_t rows, double *__restrict__ gradsq_part,
+    double *__restrict__ S_out, double nn_floor) {
+  extern __shared__ double lds[];
+  double *sS = lds;           // R x R, column-major (symmetric)
+  double *sW = lds + R * R;   // R x 64: the tile's rows, column q of lane l at q * 64 + l
+  const int lane = threadIdx.x;
+  for (int e = lane; e < R * R; e += 64) {
+    const double v = hadamard_entry(Gall, N, mode, R, lambda, e);
+    sS[e] = v;
+    if (S_out && blockIdx.x == 0) S_out[e] = v;
+  }
+  const int64_t x = (int64_t)blockIdx.x * 64 + lane;
+  const bool live = x < rows;
+  for (int q = 0; q < R; q++) sW[q * 64 + lane] = live ? W[x + ldw * q] : 0.0;
+  __syncthreads();
+  double gs = 0;
+  if (live) {
+    for (int r = 0; r < R; r++) {
+      const double *sc = sS + r * R;
+      double acc = 0;
+      for (int q = 0; q < R; q++) acc += sW[q * 64 + lane] * sc[q];
+      const double gv = -M[x + ldm * r] + acc;
+      grad[x + ldg * r] = gv;
+      gs += gv * gv;
+    }
+    for (int r = 0; r < R; r++) {
+      const double *sc = sS + r * R;
+      const double d = sc[r];
+      if (!(d > 0.0) || d > 1.79769313486231570e308) continue;
+      double acc = 0;
+      for (int q = 0; q < R; q++) acc += sW[q * 64 + lane] * sc[q];
+      const double v = sW[r * 64 + lane] + (M[x + ldm * r] - acc) / d;
+      const double w = v > nn_floor ? v : nn_floor;
+      sW[r * 64 + lane] = w;
+      W[x + ldw * r] = w;
+    }
+  }
+  gs = wave_sum(gs);
+  if (lane == 0) gradsq_part[blockIdx.x] = gs;
+}
+
+}  // namespace ppals

@@ -32,6 +32,9 @@ struct RowPad {
 };
 
 constexpr int MAX_ORDER = 8;
+// the floor of a non-negative factor entry (PPALS_NN_FLOOR of the C ABI): not zero, so that no column
+// can die and make Normalize divide by zero
+constexpr double kNnFloor = 1e-16;
 
 // a factor-matrix operand of a Khatri-Rao product: `rows` rows starting at `ptr`, leading dim ld
 struct FactorRef {
@@ -309,6 +312,58 @@ class Ops {
                      W + (size_t)b * R * ldw, ldw, grad + (size_t)b * R * ldg, ldg, rows, gradsq + b,
                      nullptr, rows, nullptr, rows, 1.0, S ? S + (size_t)b * R * R : nullptr,
                      Sinv ? Sinv + (size_t)b * R * R : nullptr);
+  }
+  // One whole single-rank NON-NEGATIVE mode update (one pass of Cichocki-Phan HALS, fp64): with
+  // S = Hadamard_{j != mode} G_j + lambda I, for every row x on its own and r = 0 .. R-1 in this order
+  //   w[x,r] <- max(nn_floor, w[x,r] + (M[x,r] - sum_q w[x,q] S[q,r]) / S[r,r])
+  // the sum taking the row's entries already updated for q < r; a column whose S[r,r] is not a positive
+  // finite number stays as it is. grad = -M + W_old S with the pre-update W, *gradsq = sum grad^2, the
+  // Gram of the new W into Gall[mode]; S (device, R x R, may be nullptr) receives the system. R <= 64.
+  // This default is built from d2h / h2d and a host loop; the product back end overrides it.
+  virtual void cp_mode_update_nn(double *Gall, int N, int mode, int R, double lambda, const double *M,
+                                 int64_t ldm, double *W, int64_t ldw, double *grad, int64_t ldg,
+                                 int64_t rows, double *gradsq, double *S) {
+    const double nn_floor = kNnFloor;
+    if (R > 64) throw Unsupported("ppals: the non-negative mode update supports R <= 64");
+    const size_t RR = (size_t)R * R;
+    std::vector<double> g((size_t)N * RR), s(RR, 1.0), m((size_t)ldm * (R - 1) + rows),
+        w((size_t)ldw * (R - 1) + rows), gr((size_t)ldg * (R - 1) + rows);
+    d2h(g.data(), Gall, sizeof(double) * g.size());
+    d2h(m.data(), M, sizeof(double) * m.size());
+    d2h(w.data(), W, sizeof(double) * w.size());
+    d2h(gr.data(), grad, sizeof(double) * gr.size());
+    for (size_t e = 0; e < RR; e++) {  // the index order of gram_system (als_CP.cxx:219-232)
+      bool first = true;
+      for (int ii = 0; ii < N - 1; ii++) {
+        const double gv = g[(size_t)(ii == mode ? N - 1 : ii) * RR + e];
+        s[e] = first ? gv : s[e] * gv;
+        first = false;
+      }
+      if (e % R == e / R) s[e] += lambda;
+    }
+    double gs = 0;
+    for (int r = 0; r < R; r++)
+      for (int64_t x = 0; x < rows; x++) {
+        double acc = 0;
+        for (int q = 0; q < R; q++) acc += w[x + ldw * q] * s[q + (size_t)R * r];
+        const double gv = -m[x + ldm * r] + acc;
+        gr[x + ldg * r] = gv;
+        gs += gv * gv;
+      }
+    for (int64_t x = 0; x < rows; x++)
+      for (int r = 0; r < R; r++) {
+        const double d = s[r + (size_t)R * r];
+        if (!(d > 0) || d > 1.79769313486231570e308) continue;
+        double acc = 0;
+        for (int q = 0; q < R; q++) acc += w[x + ldw * q] * s[q + (size_t)R * r];
+        const double v = w[x + ldw * r] + (m[x + ldm * r] - acc) / d;
+        w[x + ldw * r] = v > nn_floor ? v : nn_floor;  // (a NaN lands on the floor)
+      }
+    h2d(W, w.data(), sizeof(double) * w.size());
+    h2d(grad, gr.data(), sizeof(double) * gr.size());
+    h2d(gradsq, &gs, sizeof(double));
+    if (S) h2d(S, s.data(), sizeof(double) * RR);
+    gram(W, rows, ldw, R, Gall + (size_t)mode * RR);
   }
   // G_b = W_b^T W_b of the same column blocks: G + b * gstride, b < nstarts
   virtual void gram_batched(const double *W, int64_t rows, int64_t ld, int R, int nstarts, double *G,

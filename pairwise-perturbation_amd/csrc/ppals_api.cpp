@@ -1,6 +1,7 @@
 // ppals_api.cpp — the C ABI declared in include/ppals.h: thin, exception-free glue between plain
 // pointers/sizes and the engine. The backend (device ops + communicator) comes from backend.h:
 // libppals.so links the HIP/RCCL backend; there is no other backend in the product.
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -375,9 +376,17 @@ void ppals_cp_destroy(ppals_cp *s) {
   if (s->ctx) s->ctx->cps.erase(s);
   delete s;
 }
+static_assert(PPALS_NN_FLOOR == ppals::kNnFloor, "the ABI's floor is the one the update applies");
 int ppals_cp_set_factors(ppals_cp *s, const double *Wflat, const double *gradWflat) {
   if (!s || !s->eng || !Wflat) return fail(PPALS_ERR_ARG, "NULL argument");
   API_BEGIN
+  if (s->eng->nonneg()) {  // Wflat is on the host: looked at here, before anything is uploaded
+    size_t n = 0;
+    for (int i = 0; i < s->eng->order(); i++) n += (size_t)s->eng->tensor().glens[i] * s->eng->rank_r();
+    for (size_t e = 0; e < n; e++)
+      if (!(Wflat[e] >= 0) || !std::isfinite(Wflat[e]))
+        return fail(PPALS_ERR_ARG, "ppals_cp_set_factors: a non-negative session takes finite factors >= 0");
+  }
   s->eng->set_factors(Wflat, gradWflat);
   return PPALS_OK;
   API_END(PPALS_ERR_HIP)
@@ -399,6 +408,19 @@ int ppals_cp_set_schedule(ppals_cp *s, int schedule) {
   API_END(PPALS_ERR_HIP)
 }
 int ppals_cp_get_schedule(const ppals_cp *s) { return s && s->eng ? s->eng->schedule() : PPALS_ERR_ARG; }
+int ppals_cp_set_nonneg(ppals_cp *s, int on) {
+  if (!s || !s->eng) return fail(PPALS_ERR_ARG, "NULL session");
+  API_BEGIN
+  const bool was = s->eng->nonneg();
+  s->eng->set_nonneg(on != 0);
+  if (on && !was && !s->eng->factors_nonneg()) {
+    s->eng->set_nonneg(false);
+    return fail(PPALS_ERR_ARG, "ppals_cp_set_nonneg: the session's factors have a negative or non-finite entry");
+  }
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_cp_get_nonneg(const ppals_cp *s) { return s && s->eng ? (s->eng->nonneg() ? 1 : 0) : PPALS_ERR_ARG; }
 int ppals_cp_placement_report(const ppals_cp *s, char *buf, int cap) {
   if (!s || !s->eng || !buf || cap <= 0) return fail(PPALS_ERR_ARG, "NULL argument");
   API_BEGIN

@@ -62,6 +62,7 @@ EXPORTS = [
     "ppals_cp_multi_get_factors", "ppals_cp_multi_set_schedule", "ppals_cp_multi_sweeps",
     "ppals_cp_multi_residuals", "ppals_cp_multi_gradnorms", "ppals_cp_multi_run",
     "ppals_cp_multi_take", "ppals_cp_impute_device", "ppals_cp_em",
+    "ppals_cp_set_nonneg", "ppals_cp_get_nonneg",
 ]
 MODEL, RESIDUAL = 0, 1  # PPALS_MODEL / PPALS_RESIDUAL
 
@@ -417,6 +418,16 @@ class CP(_ModelExport):
     @property
     def schedule(self):
         return {0: "dt", 1: "msdt"}[_check(lib().ppals_cp_get_schedule(self._h))]
+
+    def set_nonneg(self, on=True):
+        """non-negative CP: every mode update becomes one HALS pass (entries >= PPALS_NN_FLOOR).
+        Exact sweeps, run_dt, cpd_als and run_em work on top; PP, the low-rank optimizers, CPMulti.take,
+        more than one rank and R > 64 are refused, as are factors with a negative or non-finite entry."""
+        _check(lib().ppals_cp_set_nonneg(self._h, 1 if on else 0))
+
+    @property
+    def nonneg(self):
+        return bool(_check(lib().ppals_cp_get_nonneg(self._h)))
 
     def placement_report(self):
         """where the online placement choice put each root's first-level intermediate (dict)"""
