@@ -182,7 +182,9 @@ int ppals_cp_get_schedule(const ppals_cp *s);
  * (ppals_cp_sweeps_dt, ppals_cp_dt, ppals_cpd_als, ppals_cp_em) run unchanged on top.
  * PPALS_ERR_UNSUPPORTED, before anything is launched: turning the flag on in a context of more than one
  * rank or at R > 64, and on a non-negative session ppals_cp_pp, ppals_cp_pp_partupdate,
- * ppals_cpd_als_lr and ppals_cp_multi_take. PPALS_ERR_ARG: factors with a negative or non-finite entry
+ * ppals_cpd_als_lr and ppals_cp_multi_take from an UNCONSTRAINED multi-start session (whose factors may
+ * be negative; a non-negative multi-start session, ppals_cp_multi_set_nonneg below, hands its starts to
+ * any ordinary session). PPALS_ERR_ARG: factors with a negative or non-finite entry
  * — those already set when the flag is turned on (the flag then stays off), and those handed to
  * ppals_cp_set_factors later. ppals_cp_get_nonneg: 1 / 0, PPALS_ERR_ARG for a NULL session. */
 #define PPALS_NN_FLOOR 1e-16
@@ -293,8 +295,22 @@ int ppals_cp_multi_gradnorms(ppals_cp_multi *s, double *out);
 int ppals_cp_multi_run(ppals_cp_multi *s, const ppals_cp_opts *o, int *sweeps, int *best);
 /* Start `start`'s factors and gradients, device to device, into an ordinary session of the same
  * context, tensor and R; on `dst` the effect is that of ppals_cp_set_factors (caches dropped, Grams
- * refreshed): the winner goes on there with Normalize, PP, the drivers and the model export. */
+ * refreshed): the winner goes on there with Normalize, PP, the drivers and the model export.
+ * A non-negative `dst` (ppals_cp_set_nonneg) takes from a non-negative multi-start session only: from
+ * an unconstrained one the call is refused with PPALS_ERR_UNSUPPORTED. An ordinary `dst` takes from both. */
 int ppals_cp_multi_take(ppals_cp_multi *s, int start, ppals_cp *dst);
+/* Non-negative multi-start sessions. With the flag on, every start updates by the HALS pass of
+ * ppals_cp_set_nonneg, all starts in one batched update per mode on the unchanged shared tensor scans:
+ * start b evolves exactly as an ordinary non-negative session does under ppals_cpd_als with
+ * PPALS_OPT_SIMPLE from the same factors (cyclic modes 0..N-1, no Normalize, S that start's Hadamard of
+ * Grams + lambda I, grad from the pre-update row, entries >= PPALS_NN_FLOOR). Sweeps, run, residuals,
+ * gradnorms, the schedules and get_factors run unchanged on top. PPALS_ERR_UNSUPPORTED, before anything
+ * is launched: R > 64 (possible at nstarts == 1 only) and PPALS_TEST_BLOCKED_UPDATE. PPALS_ERR_ARG:
+ * factors of any start with a negative or non-finite entry — those already set when the flag is turned
+ * on (the flag then stays off), and those handed to ppals_cp_multi_set_factors later (the host buffer
+ * is looked at before anything is uploaded). ppals_cp_multi_get_nonneg: 1 / 0, PPALS_ERR_ARG for NULL. */
+int ppals_cp_multi_set_nonneg(ppals_cp_multi *s, int on);
+int ppals_cp_multi_get_nonneg(const ppals_cp_multi *s);
 
 /* ---- Tucker sessions (als_Tucker.h) ---- */
 int ppals_tucker_create(ppals_ctx *ctx, ppals_tensor *V, const int *ranks, ppals_tucker **out);

@@ -667,13 +667,13 @@ void CpEngine::set_factors(const double *Wflat, const double *gradWflat) {
   ms_invalidate();
 }
 
-// The session's mode updates become HALS passes (Ops::cp_mode_update_nn). Everything that cannot run
-// that way is refused here, before anything is launched, and leaves the flag as it was.
+// The session's mode updates become HALS passes (Ops::cp_mode_update_nn; every start of a multi-start
+// session: Ops::cp_mode_update_nn_batched). Everything that cannot run that way is refused here, before
+// anything is launched, and leaves the flag as it was.
 void CpEngine::set_nonneg(bool on) {
   if (on) {
-    if (multi_) throw Unsupported("ppals: a multi-start session has no non-negative update");
     if (P_ > 1 || dist_) throw Unsupported("ppals: a non-negative session runs on one rank");
-    if (R_ > 64) throw Unsupported("ppals: a non-negative session supports R <= 64");
+    if (Rs_ > 64) throw Unsupported("ppals: a non-negative session supports R <= 64");
     if (test_blocks_ > 1)
       throw Unsupported("ppals: PPALS_TEST_BLOCKED_UPDATE has no non-negative update");
   }
@@ -681,7 +681,7 @@ void CpEngine::set_nonneg(bool on) {
 }
 
 bool CpEngine::factors_nonneg() {
-  for (int i = 0; i < N_; i++) {
+  for (int i = 0; i < N_; i++) {  // (R_ columns: all starts of a multi-start session)
     std::vector<double> h((size_t)V_.glens[i] * R_);
     ops_.d2h(h.data(), W_[i], sizeof(double) * h.size());
     for (double v : h)
@@ -792,7 +792,9 @@ int CpEngine::run_multi(const CpOpts &o, int *sweeps_out, int *best_out) {
 
 void CpEngine::take_from(CpEngine &src, int start) {
   if (multi_ || dist_) throw std::logic_error("ppals: the destination must be an ordinary one-rank session");
-  if (nonneg_) throw Unsupported("ppals: a non-negative session does not take a multi-start's factors");
+  // (a non-negative multi-start session's factors are >= the floor by construction)
+  if (nonneg_ && !src.nonneg_)
+    throw Unsupported("ppals: a non-negative session does not take an unconstrained multi-start's factors");
   if (!src.multi_ || start < 0 || start >= src.K_ || src.Rs_ != R_ || src.N_ != N_ ||
       src.V_.data != V_.data)
     throw std::runtime_error("ppals: take: sessions do not match");
@@ -842,6 +844,11 @@ void CpEngine::mode_update(int i, const double *M, int64_t ldm, double lambda, b
   const int64_t s = V_.glens[i];
   if (multi_) {  // block-diagonal over starts: one batched update, every start its own system
     if (pp) throw std::logic_error("ppals: no PP update in a multi-start session");
+    if (nonneg_) {  // one HALS pass per start, all starts in one batched update
+      ops_.cp_mode_update_nn_batched(G_, N_, i, Rs_, K_, lambda, M, ldm, W_[i], s, gradW_[i], s, s,
+                                     gradsq_ + (size_t)i * K_, S_);
+      return;
+    }
     ops_.cp_mode_update_batched(G_, N_, i, Rs_, K_, lambda, M, ldm, W_[i], s, gradW_[i], s, s,
                                 gradsq_ + (size_t)i * K_, S_, Sinv_);
     return;

@@ -99,12 +99,13 @@ class CpEngine {
 
   void set_factors(const double *Wflat, const double *gradWflat);
   void set_schedule(int schedule);
-  // Non-negative CP: every mode update is one HALS pass (Ops::cp_mode_update_nn) instead of the solve.
-  // Exact sweeps and what is built on them (run_dt, run_class 0-2, run_em) work unchanged; PP, the
-  // low-rank optimizers, multi-start, more than one rank and R > 64 throw Unsupported.
+  // Non-negative CP: every mode update is one HALS pass (Ops::cp_mode_update_nn; all starts of a
+  // multi-start session in one Ops::cp_mode_update_nn_batched) instead of the solve.
+  // Exact sweeps and what is built on them (run_dt, run_class 0-2, run_em, run_multi) work unchanged; PP,
+  // the low-rank optimizers, more than one rank and R > 64 per start throw Unsupported.
   void set_nonneg(bool on);
   bool nonneg() const { return nonneg_; }
-  bool factors_nonneg();  // downloads the factors: every entry finite and >= 0
+  bool factors_nonneg();  // downloads the factors (of all starts): every entry finite and >= 0
   int schedule() const { return schedule_; }
   // one JSON object: where the online placement choice put every root's first-level intermediate
   // (block, offset, store kind, fastest / slowest sample, settled or still exploring)

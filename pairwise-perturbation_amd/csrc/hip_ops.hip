@@ -1559,6 +1559,35 @@ class HipOps : public Ops {
     HIP_CHECK(hipGetLastError());
     gram(W, rows, ldw, R, Gall + (size_t)mode * R * R);
   }
+  // The non-negative mode updates of all starts of a multi-start session in TWO launches whatever the
+  // number of starts: the row kernel on a grid of (row tiles x starts), then one workgroup per start that
+  // adds the start's tile sums and refreshes its Gram. Bracketed as cp_mode_update_batched is.
+  void cp_mode_update_nn_batched(double *Gall, int N, int mode, int R, int nstarts, double lambda,
+                                 const double *M, int64_t ldm, double *W, int64_t ldw, double *grad,
+                                 int64_t ldg, int64_t rows, double *gradsq, double *S) override {
+    RoctxRange roctx_("K4-K6 mode update (non-negative, batched over starts)");
+    if (R > 64) throw Unsupported("ppals: the non-negative mode update supports R <= 64");
+    if (nstarts < 1 || nstarts > 65535) throw std::runtime_error("ppals: number of starts out of range");
+    if (sys_armed_ || sys_ready_ || norm_armed_)
+      throw std::logic_error("ppals: armed S / Normalize in front of a non-negative mode update");
+    if (rows <= 0) {
+      Ops::cp_mode_update_nn_batched(Gall, N, mode, R, nstarts, lambda, M, ldm, W, ldw, grad, ldg, rows,
+                                     gradsq, S);
+      return;
+    }
+    const int64_t nb = (rows + 63) / 64;
+    if (nb * nstarts > (int64_t)1 << 30)
+      throw std::runtime_error("ppals: mode too long for the non-negative update");
+    double *part = (double *)ensure(ws_big2_, ws_big2_sz_, sizeof(double) * (size_t)nb * nstarts);
+    const size_t lds = sizeof(double) * ((size_t)R * R + 64 * (size_t)R);
+    prof_begin(1, 0.0);
+    hipLaunchKernelGGL(k_cp_update_nn, dim3((unsigned)nb, (unsigned)nstarts), dim3(64), lds, st_, Gall, N,
+                       mode, R, lambda, M, ldm, W, ldw, grad, ldg, rows, part, S, kNnFloor);
+    hipLaunchKernelGGL(k_cp_finish_nn_batched, dim3((unsigned)nstarts), dim3(1024), 0, st_, part, (int)nb,
+                       gradsq, W, ldw, rows, R, N, mode, Gall);
+    prof_end();
+    HIP_CHECK(hipGetLastError());
+  }
   // The mode updates of all starts of a multi-start session in ONE launch: a 1024-thread workgroup per
   // start (nstarts <= 32 of them on 256 CUs: every workgroup has a CU and its LDS to itself, none waits
   // for another). The same routes as cp_mode_update: the staged launch where M and W of ONE start fit

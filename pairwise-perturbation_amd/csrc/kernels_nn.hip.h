@@ -1,5 +1,6 @@
-// kernels_nn.hip.h — the non-negative (HALS) mode update of a CP session (Ops::cp_mode_update_nn).
-// hadamard_entry, wave_sum and k_sum_partials come from kernels_small.hip.h.
+// kernels_nn.hip.h — the non-negative (HALS) mode update of a CP session (Ops::cp_mode_update_nn) and of
+// all starts of a multi-start session (Ops::cp_mode_update_nn_batched).
+// hadamard_entry, wave_sum, block_sum, gram_pairs and k_sum_partials come from kernels_small.hip.h.
 #pragma once
 #include "kernels_small.hip.h"
 
@@ -21,6 +22,11 @@ namespace ppals {
 // finite number stays. A lane reads and writes its own row of W only, so W is updated in place.
 // gradsq_part[workgroup] = the tile's sum of grad^2, lanes added in the fixed order of wave_sum;
 // k_sum_partials adds the tiles. Workgroup 0 stores S when asked.
+//
+// blockIdx.y is the start of a multi-start session (R columns per start, the layout of
+// k_cp_mode_update_batched): start b reads its N Grams at Gall + b N R^2, owns columns [b R, (b+1) R) of M,
+// W and grad, writes its tiles' sums to gradsq_part[b * gridDim.x + tile] and its S to S_out + b R^2.
+// Nothing is shared between two starts. An ordinary session launches gridDim.y == 1: every offset is 0.
 __global__ __launch_bounds__(64) void k_cp_update_nn(
     const double *__restrict__ Gall, int N, int mode, int R, double lambda,
     const double *__restrict__ M, int64_t ldm, double *__restrict__ W, int64_t ldw,
@@ -30,6 +36,13 @@ __global__ __launch_bounds__(64) void k_cp_update_nn(
   double *sS = lds;           // R x R, column-major (symmetric)
   double *sW = lds + R * R;   // R x 64: the tile's rows, column q of lane l at q * 64 + l
   const int lane = threadIdx.x;
+  const int64_t b = blockIdx.y;
+  Gall += b * N * R * R;
+  M += b * R * ldm;
+  W += b * R * ldw;
+  grad += b * R * ldg;
+  gradsq_part += b * gridDim.x;
+  if (S_out) S_out += b * R * R;
   for (int e = lane; e < R * R; e += 64) {
     const double v = hadamard_entry(Gall, N, mode, R, lambda, e);
     sS[e] = v;
@@ -63,6 +76,22 @@ __global__ __launch_bounds__(64) void k_cp_update_nn(
   }
   gs = wave_sum(gs);
   if (lane == 0) gradsq_part[blockIdx.x] = gs;
+}
+
+// What follows the row kernel in a multi-start session, for all starts in ONE launch: workgroup b adds
+// start b's `ntiles` tile sums into gradsq[b] (the order of k_sum_partials) and refreshes start b's Gram
+// of the new W into Gall (the per-pair order of k_gram: 16 waves share the R (R + 1) / 2 pairs).
+__global__ __launch_bounds__(1024) void k_cp_finish_nn_batched(
+    const double *__restrict__ part, int ntiles, double *__restrict__ gradsq, const double *__restrict__ W,
+    int64_t ldw, int64_t rows, int R, int N, int mode, double *__restrict__ Gall) {
+  __shared__ double lds[17];
+  const int64_t b = blockIdx.x;
+  part += b * ntiles;
+  double s = 0;
+  for (int i = threadIdx.x; i < ntiles; i += blockDim.x) s += part[i];
+  s = block_sum(s, lds);
+  if (threadIdx.x == 0) gradsq[b] = s;
+  gram_pairs(W + b * R * ldw, rows, ldw, R, Gall + (b * N + mode) * R * R, threadIdx.x >> 6, blockDim.x >> 6);
 }
 
 }  // namespace ppals

@@ -688,12 +688,11 @@ __global__ void k_scale_update(double *__restrict__ dst, const double *__restric
 }
 
 // ------------------------------------------------------------------ Gram  G = W^T W
-// one wave per (p<=q) pair, lanes stride the rows (coalesced); symmetric fill.
-__global__ void k_gram(const double *__restrict__ W, int64_t rows, int64_t ld, int R,
-                       double *__restrict__ G) {
+// one wave per (p<=q) pair, lanes stride the rows (coalesced); symmetric fill. Wave `wid` of `nw`
+// cooperating waves takes the pairs wid, wid + nw, ...: a pair's sum does not depend on who takes it.
+__device__ inline void gram_pairs(const double *__restrict__ W, int64_t rows, int64_t ld, int R,
+                                  double *__restrict__ G, int wid, int nw) {
   const int lane = threadIdx.x & 63;
-  const int wid = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-  const int nw = (int)(((int64_t)gridDim.x * blockDim.x) >> 6);
   const int npairs = R * (R + 1) / 2;
   for (int e = wid; e < npairs; e += nw) {
     // decode e -> (p,q), p <= q, row-major over the upper triangle
@@ -721,6 +720,11 @@ __global__ void k_gram(const double *__restrict__ W, int64_t rows, int64_t ld, i
       G[q + R * p] = s;
     }
   }
+}
+__global__ void k_gram(const double *__restrict__ W, int64_t rows, int64_t ld, int R,
+                       double *__restrict__ G) {
+  gram_pairs(W, rows, ld, R, G, (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6),
+             (int)(((int64_t)gridDim.x * blockDim.x) >> 6));
 }
 
 // ------------------------------------------------------------------ S and S^{-1}  (K4 + K6a)

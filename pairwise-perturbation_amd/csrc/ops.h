@@ -365,6 +365,19 @@ class Ops {
     if (S) h2d(S, s.data(), sizeof(double) * RR);
     gram(W, rows, ldw, R, Gall + (size_t)mode * RR);
   }
+  // `nstarts` independent non-negative mode updates of rank R in one call (non-negative multi-start
+  // sessions), in the layout of cp_mode_update_batched: start b owns columns [b R, (b+1) R) of M, W and
+  // grad, its N Grams sit at Gall + b N R^2, gradsq[b] = ||grad_b||^2, S (may be nullptr) receives one
+  // R x R system per start. Nothing couples two starts. Back ends may run all of them in one launch.
+  virtual void cp_mode_update_nn_batched(double *Gall, int N, int mode, int R, int nstarts, double lambda,
+                                         const double *M, int64_t ldm, double *W, int64_t ldw,
+                                         double *grad, int64_t ldg, int64_t rows, double *gradsq,
+                                         double *S) {
+    for (int b = 0; b < nstarts; b++)
+      cp_mode_update_nn(Gall + (size_t)b * N * R * R, N, mode, R, lambda, M + (size_t)b * R * ldm, ldm,
+                        W + (size_t)b * R * ldw, ldw, grad + (size_t)b * R * ldg, ldg, rows, gradsq + b,
+                        S ? S + (size_t)b * R * R : nullptr);
+  }
   // G_b = W_b^T W_b of the same column blocks: G + b * gstride, b < nstarts
   virtual void gram_batched(const double *W, int64_t rows, int64_t ld, int R, int nstarts, double *G,
                             int64_t gstride) {

@@ -662,6 +662,14 @@ int ppals_cp_multi_set_factors(ppals_cp_multi *s, int start, const double *Wflat
   if (int rc = check_start(s, start, true)) return rc;
   if (!Wflat) return fail(PPALS_ERR_ARG, "NULL argument");
   API_BEGIN
+  if (s->eng->nonneg()) {  // Wflat is on the host: looked at here, before anything is uploaded
+    size_t n = 0;
+    for (int i = 0; i < s->eng->order(); i++) n += (size_t)s->eng->tensor().glens[i] * s->eng->start_rank();
+    if (start < 0) n *= (size_t)s->eng->nstarts();
+    for (size_t e = 0; e < n; e++)
+      if (!(Wflat[e] >= 0) || !std::isfinite(Wflat[e]))
+        return fail(PPALS_ERR_ARG, "ppals_cp_multi_set_factors: a non-negative session takes finite factors >= 0");
+  }
   s->eng->set_factors_start(start, Wflat, gradWflat);
   return PPALS_OK;
   API_END(PPALS_ERR_HIP)
@@ -689,6 +697,21 @@ int ppals_cp_multi_sweeps(ppals_cp_multi *s, int n, double lambda) {
   for (int i = 0; i < n; i++) s->eng->update_modes(0, s->eng->order(), lambda);
   return PPALS_OK;
   API_END(PPALS_ERR_HIP)
+}
+int ppals_cp_multi_set_nonneg(ppals_cp_multi *s, int on) {
+  if (!s || !s->eng) return fail(PPALS_ERR_ARG, "NULL session");
+  API_BEGIN
+  const bool was = s->eng->nonneg();
+  s->eng->set_nonneg(on != 0);
+  if (on && !was && !s->eng->factors_nonneg()) {
+    s->eng->set_nonneg(false);
+    return fail(PPALS_ERR_ARG, "ppals_cp_multi_set_nonneg: a start's factors have a negative or non-finite entry");
+  }
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_cp_multi_get_nonneg(const ppals_cp_multi *s) {
+  return s && s->eng ? (s->eng->nonneg() ? 1 : 0) : PPALS_ERR_ARG;
 }
 int ppals_cp_multi_residuals(ppals_cp_multi *s, double *out) {
   if (!s || !s->eng || !out) return fail(PPALS_ERR_ARG, "NULL argument");

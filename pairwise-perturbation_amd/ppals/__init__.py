@@ -63,6 +63,7 @@ EXPORTS = [
     "ppals_cp_multi_residuals", "ppals_cp_multi_gradnorms", "ppals_cp_multi_run",
     "ppals_cp_multi_take", "ppals_cp_impute_device", "ppals_cp_em",
     "ppals_cp_set_nonneg", "ppals_cp_get_nonneg",
+    "ppals_cp_multi_set_nonneg", "ppals_cp_multi_get_nonneg",
 ]
 MODEL, RESIDUAL = 0, 1  # PPALS_MODEL / PPALS_RESIDUAL
 
@@ -421,8 +422,9 @@ class CP(_ModelExport):
 
     def set_nonneg(self, on=True):
         """non-negative CP: every mode update becomes one HALS pass (entries >= PPALS_NN_FLOOR).
-        Exact sweeps, run_dt, cpd_als and run_em work on top; PP, the low-rank optimizers, CPMulti.take,
-        more than one rank and R > 64 are refused, as are factors with a negative or non-finite entry."""
+        Exact sweeps, run_dt, cpd_als and run_em work on top; PP, the low-rank optimizers, CPMulti.take
+        from an unconstrained multi-start session, more than one rank and R > 64 are refused, as are
+        factors with a negative or non-finite entry."""
         _check(lib().ppals_cp_set_nonneg(self._h, 1 if on else 0))
 
     @property
@@ -622,6 +624,15 @@ class CPMulti:
     def set_schedule(self, schedule):
         code = {"dt": 0, "msdt": 1}[schedule] if isinstance(schedule, str) else int(schedule)
         _check(lib().ppals_cp_multi_set_schedule(self._h, code))
+
+    def set_nonneg(self, on=True):
+        """non-negative multi-start: every start updates by the HALS pass of CP.set_nonneg, all starts in
+        one batched update per mode. Factors of any start with a negative or non-finite entry are refused."""
+        _check(lib().ppals_cp_multi_set_nonneg(self._h, 1 if on else 0))
+
+    @property
+    def nonneg(self):
+        return bool(_check(lib().ppals_cp_multi_get_nonneg(self._h)))
 
     def sweeps(self, n, lam=0.0):
         _check(lib().ppals_cp_multi_sweeps(self._h, int(n), C.c_double(lam)))
