@@ -1395,6 +1395,7 @@ class HipOps : public Ops {
     if (sys_ready_ && sys_.Gall == Gall && sys_.mode == mode && sys_.S == S && sys_.Sinv == Sinv &&
         sys_.lambda == lambda && sys_R_ == R) {  // prepared on the side of the last contraction
       sys_ready_ = false;
+      route("%s", "gram_system.ready");
       return;
     }
     sys_ready_ = false;
@@ -1405,6 +1406,7 @@ class HipOps : public Ops {
       const size_t RP = ((size_t)R + 15) & ~(size_t)15;
       const size_t LDm = RP + ((34 - (RP & 31)) & 31);
       const size_t lds_mf = sizeof(double) * (LDm * RP + 8 * RP);
+      route("gram_system.%s", lds_mf <= 150 * 1024 && !gj_scalar_ ? "mfma" : lds_gj <= 150 * 1024 ? "lds" : "big");
       if (lds_mf <= 150 * 1024 && !gj_scalar_)   // block sweeps, trailing update on the fp64 matrix cores
         hipLaunchKernelGGL(k_gram_system_mfma, dim3(1), dim3(1024), lds_mf, st_, Gall, N, mode, R,
                            lambda, S, Sinv, status);
@@ -1437,6 +1439,7 @@ class HipOps : public Ops {
         return;
       }
       int bad = 0;
+      route("%s", "gram_system.host_fallback");
       HIP_CHECK(hipMemcpyAsync(&bad, status, sizeof(int), hipMemcpyDeviceToHost, st_));
       HIP_CHECK(hipStreamSynchronize(st_));
       if (bad || force_eiginv_) {
@@ -1454,6 +1457,7 @@ class HipOps : public Ops {
       return;
     }
     size_t lds = sizeof(double) * (2 * (size_t)R * (R + 1) + 64) + sizeof(int) * 64;
+    route("%s", "gram_system.wave");
     hipLaunchKernelGGL(k_gram_system, dim3(1), dim3(64), lds, st_, Gall, N, mode, R, lambda, S,
                        Sinv, force_jacobi_);
     HIP_CHECK(hipGetLastError());
@@ -1468,11 +1472,13 @@ class HipOps : public Ops {
     const size_t stage = 2 * sizeof(double) * (size_t)rows * R;
     if (R > 64 || force_jacobi_ || norm_armed_ || lds + stage > 150 * 1024 || blk * P != rows ||
         blk > 0x7fffffff) {
+      route("%s", "update_blocked.unpack");
       Ops::cp_mode_update_blocked(Gall, N, mode, R, lambda, Mblk, blk, P, scratch, W, ldw, grad, ldg, rows,
                                   gradsq, Winit, ldi, dW, ldd, ratio, S, Sinv);
       return;
     }
     update_mblk_ = (int)blk;
+    route("%s", "update_blocked.direct");
     cp_mode_update(Gall, N, mode, R, lambda, Mblk, rows, W, ldw, grad, ldg, rows, gradsq, Winit, ldi, dW,
                    ldd, ratio, S, Sinv, nullptr);
     update_mblk_ = 0;
@@ -1488,11 +1494,13 @@ class HipOps : public Ops {
                       double ratio, double *S, double *Sinv, double *dwsq) override {
     RoctxRange roctx_("K4-K6 mode update");
     if (R > 64) {  // unfused route: S / S^-1, row-parallel update, Gram refresh
+      route("%s", "update.unfused why=R");
       Ops::cp_mode_update(Gall, N, mode, R, lambda, M, ldm, W, ldw, grad, ldg, rows, gradsq, Winit,
                           ldi, dW, ldd, ratio, S, Sinv, dwsq);
       return;
     }
     if (force_jacobi_) {  // A/B path: the three separate kernels with the Jacobi inverse
+      route("%s", "update.unfused why=jacobi");
       Ops::cp_mode_update(Gall, N, mode, R, lambda, M, ldm, W, ldw, grad, ldg, rows, gradsq, Winit,
                           ldi, dW, ldd, ratio, S, Sinv, dwsq);
       return;
@@ -1505,6 +1513,7 @@ class HipOps : public Ops {
     // workgroup walking rows x R entries out of global memory takes 333 us there: the row-parallel
     // unfused route (S / S^-1, rows over many workgroups, Gram) takes a few short launches instead
     if (lds + stage > 150 * 1024 && (int64_t)rows * R > kUpdateRowParallelFrom && !norm_armed_ && !update_mblk_) {
+      route("%s", "update.unfused why=rows");
       Ops::cp_mode_update(Gall, N, mode, R, lambda, M, ldm, W, ldw, grad, ldg, rows, gradsq, Winit, ldi, dW,
                           ldd, ratio, S, Sinv, dwsq);
       return;
@@ -1523,11 +1532,14 @@ class HipOps : public Ops {
       norm_armed_ = false;
     }
     if (lds + stage <= 150 * 1024) {
+      route("update.staged presolved=%d norm=%d mblk=%d dwsq=%d", presolved, nrm.on ? 1 : 0, update_mblk_ ? 1 : 0,
+            dwsq ? 1 : 0);
       hipLaunchKernelGGL((k_cp_mode_update<true, true>), dim3(1), dim3(1024), lds + stage, st_, Gall, N, mode,
                          R, lambda, M, ldm, W, ldw, grad, ldg, rows, gradsq, Winit, ldi, dW, ldd, ratio, S,
                          Sinv, dwsq, presolved, nrm, update_mblk_);
     } else {
       if (update_mblk_) throw std::logic_error("ppals: blocked mode update needs the staged launch");
+      route("update.unstaged presolved=%d", presolved);
       hipLaunchKernelGGL((k_cp_mode_update<false, false>), dim3(1), dim3(1024), lds, st_, Gall, N, mode,
                          R, lambda, M, ldm, W, ldw, grad, ldg, rows, gradsq, Winit, ldi, dW, ldd, ratio,
                          S, Sinv, dwsq, presolved);
@@ -1603,6 +1615,7 @@ class HipOps : public Ops {
     if (R > 64 || force_jacobi_ || nstarts < 1 || (double)rows * R >= 2.0e9 ||
         (!staged && (int64_t)rows * R > kUpdateRowParallelFrom)) {
       // (bracketed start by start: the profile's launch count shows which route a session took)
+      route("%s", "update_batched.loop");
       for (int b = 0; b < nstarts; b++) {
         const size_t rr = (size_t)R * R;
         prof_begin(1, 0.0);
@@ -1618,6 +1631,7 @@ class HipOps : public Ops {
     sys_ready_ = false;
     sys_armed_ = false;
     prof_begin(1, 0.0);
+    route("%s", staged ? "update_batched.staged" : "update_batched.unstaged");
     if (staged)
       hipLaunchKernelGGL((k_cp_mode_update_batched<true, true>), dim3((unsigned)nstarts), dim3(1024),
                          lds + stage, st_, Gall, N, mode, R, lambda, M, ldm, W, ldw, grad, ldg, rows, gradsq,
@@ -1632,12 +1646,18 @@ class HipOps : public Ops {
                      double *wsq, double *ms_dst, const unsigned *masks, unsigned active,
                      unsigned fresh) override {
     norm_armed_ = false;
-    if (R > 64 || force_jacobi_ || N > MAX_ORDER) return false;
+    if (R > 64 || force_jacobi_ || N > MAX_ORDER) {
+      route("%s", "arm_normalize.refused");
+      return false;
+    }
     int64_t tot = 0;
     for (int i = 0; i < N; i++) tot += rows[i] * R;
     const size_t lds = sizeof(double) * (32 + 2 * (size_t)R * R + 2 * (size_t)R * (R + 1) + 64) +
                        sizeof(int) * 64;
-    if (tot > 65536 || lds + 2 * sizeof(double) * (size_t)rows[mode] * R > 150 * 1024) return false;
+    if (tot > 65536 || lds + 2 * sizeof(double) * (size_t)rows[mode] * R > 150 * 1024) {
+      route("%s", "arm_normalize.refused");
+      return false;
+    }
     norm_ = NormArgs();
     norm_.on = 1;
     for (int i = 0; i < N; i++) {
@@ -1655,6 +1675,7 @@ class HipOps : public Ops {
     norm_G_ = Gall;
     (void)small(MAX_ORDER);  // (allocated now: no workspace growth inside the armed launch)
     norm_armed_ = true;
+    route("%s", "arm_normalize.taken");
     return true;
   }
   void arm_gram_system(const double *Gall, int N, int mode, int R, double lambda, double *S,
@@ -1706,12 +1727,14 @@ class HipOps : public Ops {
                  const double *Sinv, double *gradsq, const double *Winit, int64_t ldi, double *dW,
                  int64_t ldd, double ratio) override {
     if (rows <= 0) {  // a rank that owns no rows of this mode (row-block plan): nothing to launch
+      route("%s", "cp_update.empty");
       HIP_CHECK(hipMemsetAsync(gradsq, 0, sizeof(double), st_));
       return;
     }
     if (R > 64 && ldg == rows && ldn == rows && (!Winit || ratio == 1.0) && rows * (int64_t)R < (1 << 30)) {
       // both products on the matrix cores (S and S^-1 are symmetric: they ARE their own
       // transposed operand): grad = W_old S - M, then W = M S^-1 (may alias W_old: stream order)
+      route("cp_update.gemm tail=%d", Winit ? 1 : 0);
       gemm_nt(Wold, ldw, S, R, M, ldm, grad, ldg, (int)rows, R, R, 1.0, -1.0);
       sumsq(grad, rows * R, gradsq);
       gemm_nt(M, ldm, Sinv, R, nullptr, 0, Wnew, ldn, (int)rows, R, R, 1.0, 0.0);
@@ -1726,6 +1749,7 @@ class HipOps : public Ops {
     }
     if (R > 64 || (int64_t)rows * R > kUpdateRowParallelFrom) {
       // several blocks update the rows: W_old is read from a scratch copy so that Wnew may alias it
+      route("%s", "cp_update.rows");
       const int nb = (int)((rows + 63) / 64);
       double *wcopy = (double *)ensure(ws_big2_, ws_big2_sz_,
                                        sizeof(double) * ((size_t)rows * R + (size_t)nb));
@@ -1739,12 +1763,14 @@ class HipOps : public Ops {
       return;
     }
     size_t lds = sizeof(double) * (32 + 2 * (size_t)R * R);
+    route("%s", "cp_update.one");
     hipLaunchKernelGGL(k_cp_update, dim3(1), dim3(1024), lds, st_, M, ldm, Wold, ldw, Wnew, ldn,
                        grad, ldg, rows, R, S, Sinv, gradsq, Winit, ldi, dW, ldd, ratio);
     HIP_CHECK(hipGetLastError());
   }
   void normalize(double *const *W, const int64_t *rows, int N, int R, double *Gall) override {
     double *scales = small(MAX_ORDER);
+    route("%s", "normalize.grid");
     hipLaunchKernelGGL(k_norm_scales, dim3(1), dim3(1024), 0, st_, Gall, N, R, scales);
     HIP_CHECK(hipGetLastError());
     PtrsN w;
@@ -1775,6 +1801,7 @@ class HipOps : public Ops {
     }
     ScaleMasks sm;
     for (int k = 0; k < 32; k++) sm.m[k] = masks ? masks[k] : 0u;
+    route("%s", "normalize.fused");
     hipLaunchKernelGGL(k_normalize_fused, dim3(1), dim3(1024), 0, st_, Gall, N, R, w,
                        small(MAX_ORDER), active ? ms_dst : nullptr, sm, active, fresh, wsq);
     HIP_CHECK(hipGetLastError());

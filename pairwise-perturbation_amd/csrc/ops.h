@@ -293,11 +293,21 @@ class Ops {
                               int64_t rows, double *gradsq, const double *Winit, int64_t ldi,
                               double *dW, int64_t ldd, double ratio, double *S, double *Sinv,
                               double *dwsq = nullptr) {
+    // S / Sinv not wanted: the separate launches still pass them on. (An allocation and a free that
+    // waits for the stream, per call: this keeps the contract above, it is not meant for a hot path —
+    // the engine always passes both.)
+    double *tmp = nullptr;
+    if (!S || !Sinv) {
+      tmp = (double *)alloc(sizeof(double) * 2 * (size_t)R * R);
+      if (!S) S = tmp;
+      if (!Sinv) Sinv = tmp + (size_t)R * R;
+    }
     gram_system(Gall, N, mode, R, lambda, S, Sinv);
     cp_update(M, ldm, W, ldw, W, ldw, grad, ldg, rows, R, S, Sinv, gradsq, Winit, ldi, dW, ldd,
               ratio);
     gram(W, rows, ldw, R, Gall + (size_t)mode * R * R);
     if (dwsq && Winit) sumsq(dW, rows * R, dwsq);
+    if (tmp) free(tmp);  // (free waits for the launches above)
   }
   // `nstarts` independent mode updates of rank R in one call (multi-start sessions): M, W and grad hold
   // nstarts * R columns, start b owns columns [b R, (b+1) R); Gall holds, start by start, the N Grams
@@ -502,7 +512,8 @@ class Ops {
   virtual void profile_collect() {}
   ProfileSlot prof[2];
   // Route log (tests): when set, the product back end appends one short tag per kernel decision of
-  // the contraction launchers (tensor scans, mttv, the thin-GEMM mode products, pp_correct) — the kernel
+  // the contraction launchers (tensor scans, mttv, the thin-GEMM mode products, pp_correct) and of the
+  // launchers of the R x R side (mode updates, cp_update, gram_system, Normalize) — the kernel
   // family and the facts that chose it. Null: nothing is formatted. The host stand-in logs nothing.
   std::vector<std::string> *route_log = nullptr;
 };

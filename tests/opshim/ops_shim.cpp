@@ -1,7 +1,7 @@
 // ops_shim.cpp — TEST INFRASTRUCTURE: a C surface over ppals::Ops for the op-level tests of the
-// contraction kernels (tests/contraction_cases.py). One source, two libraries: linked against the
-// product's libppals.so it reaches the HIP kernels as compiled there, linked against the host stand-in
-// it reaches HostOps. No HIP code and no HIP calls here: every device action goes through the Ops.
+// contraction kernels (tests/contraction_cases.py) and of the mode-update side
+// (tests/update_cases.py). One source, two libraries: linked against the product's libppals.so it
+// reaches the HIP kernels as compiled there, linked against the host stand-in it reaches HostOps. No HIP code and no HIP calls here: every device action goes through the Ops.
 // Every function returns 0, or -1 after an exception whose text shim_error() then returns (the
 // launchers' own refusals — "padded rows inconsistent" — arrive that way).
 #include <cstring>
@@ -137,6 +137,107 @@ int shim_arm_gram_system(void *h, const double *Gall, int N, int mode, int R, do
                          double *Sinv) {
   Shim *s = (Shim *)h;
   return guarded(s, [&] { s->ops->arm_gram_system(Gall, N, mode, R, lambda, S, Sinv); });
+}
+
+// ---- the mode-update, Normalize and factor-side ops (tests/update_cases.py) ----
+int shim_gram(void *h, const double *W, int64_t rows, int64_t ld, int R, double *G) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->gram(W, rows, ld, R, G); });
+}
+int shim_gram_batched(void *h, const double *W, int64_t rows, int64_t ld, int R, int nstarts, double *G,
+                      int64_t gstride) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->gram_batched(W, rows, ld, R, nstarts, G, gstride); });
+}
+int shim_gram_system(void *h, const double *Gall, int N, int mode, int R, double lambda, double *S, double *Sinv) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->gram_system(Gall, N, mode, R, lambda, S, Sinv); });
+}
+int shim_cp_update(void *h, const double *M, int64_t ldm, const double *Wold, int64_t ldw, double *Wnew, int64_t ldn,
+                   double *grad, int64_t ldg, int64_t rows, int R, const double *S, const double *Sinv, double *gradsq,
+                   const double *Winit, int64_t ldi, double *dW, int64_t ldd, double ratio) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] {
+    s->ops->cp_update(M, ldm, Wold, ldw, Wnew, ldn, grad, ldg, rows, R, S, Sinv, gradsq, Winit, ldi, dW, ldd, ratio);
+  });
+}
+int shim_cp_mode_update(void *h, double *Gall, int N, int mode, int R, double lambda, const double *M, int64_t ldm,
+                        double *W, int64_t ldw, double *grad, int64_t ldg, int64_t rows, double *gradsq,
+                        const double *Winit, int64_t ldi, double *dW, int64_t ldd, double ratio, double *S,
+                        double *Sinv, double *dwsq) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] {
+    s->ops->cp_mode_update(Gall, N, mode, R, lambda, M, ldm, W, ldw, grad, ldg, rows, gradsq, Winit, ldi, dW, ldd,
+                           ratio, S, Sinv, dwsq);
+  });
+}
+int shim_cp_mode_update_batched(void *h, double *Gall, int N, int mode, int R, int nstarts, double lambda,
+                                const double *M, int64_t ldm, double *W, int64_t ldw, double *grad, int64_t ldg,
+                                int64_t rows, double *gradsq, double *S, double *Sinv) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] {
+    s->ops->cp_mode_update_batched(Gall, N, mode, R, nstarts, lambda, M, ldm, W, ldw, grad, ldg, rows, gradsq, S,
+                                   Sinv);
+  });
+}
+int shim_cp_mode_update_blocked(void *h, double *Gall, int N, int mode, int R, double lambda, const double *Mblk,
+                                int64_t blk, int P, double *scratch, double *W, int64_t ldw, double *grad,
+                                int64_t ldg, int64_t rows, double *gradsq, const double *Winit, int64_t ldi,
+                                double *dW, int64_t ldd, double ratio, double *S, double *Sinv) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] {
+    s->ops->cp_mode_update_blocked(Gall, N, mode, R, lambda, Mblk, blk, P, scratch, W, ldw, grad, ldg, rows, gradsq,
+                                   Winit, ldi, dW, ldd, ratio, S, Sinv);
+  });
+}
+int shim_arm_normalize(void *h, double *const *W, const int64_t *rows, int N, int R, double *Gall, int mode,
+                       double *wsq, double *ms_dst, const unsigned *masks, unsigned active, unsigned fresh,
+                       int *taken) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] {
+    *taken = s->ops->arm_normalize(W, rows, N, R, Gall, mode, wsq, ms_dst, masks, active, fresh) ? 1 : 0;
+  });
+}
+int shim_normalize(void *h, double *const *W, const int64_t *rows, int N, int R, double *Gall) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->normalize(W, rows, N, R, Gall); });
+}
+int shim_normalize_ms(void *h, double *const *W, const int64_t *rows, int N, int R, double *Gall, double *ms_dst,
+                      const unsigned *masks, unsigned active, unsigned fresh, double *wsq) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->normalize_ms(W, rows, N, R, Gall, ms_dst, masks, active, fresh, wsq); });
+}
+int shim_normalize_scales(void *h, const double **out) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { *out = s->ops->normalize_scales(); });
+}
+int shim_diff_norms(void *h, double *const *A, double *const *B, const int64_t *n, int N, int store_diff,
+                    double *const *D, int update_prev, double *out) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->diff_norms(A, B, n, N, store_diff, D, update_prev, out); });
+}
+int shim_pack_blocks(void *h, const double *nat, int64_t rows, int64_t ld, int R, int64_t blk, int P,
+                     double *blocked) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->pack_blocks(nat, rows, ld, R, blk, P, blocked); });
+}
+int shim_unpack_blocks(void *h, const double *blocked, int64_t rows, int64_t ld, int R, int64_t blk, int P,
+                       double *nat) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->unpack_blocks(blocked, rows, ld, R, blk, P, nat); });
+}
+int shim_sumsq(void *h, const double *x, int64_t n, double *out) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->sumsq(x, n, out); });
+}
+int shim_scale_update(void *h, double *dst, const double *scales, unsigned mask, int set_one) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->scale_update(dst, scales, mask, set_one); });
+}
+int shim_scale_update_many(void *h, double *dst, const double *scales, const unsigned *masks, unsigned active,
+                           unsigned fresh) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->scale_update_many(dst, scales, masks, active, fresh); });
 }
 
 // the route log (ops.h): attach (on != 0) or detach, read as one newline-joined string, clear

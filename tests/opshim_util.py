@@ -13,7 +13,7 @@ DIR = os.path.join(ROOT, "tests", "opshim")
 F32, F64, BF16 = 0, 1, 3
 _libs = {}
 
-_P, _I64, _I = C.c_void_p, C.c_int64, C.c_int
+_P, _I64, _I, _U, _D = C.c_void_p, C.c_int64, C.c_int, C.c_uint, C.c_double
 _SIGS = {
     "shim_alloc": [_P, C.c_size_t, C.POINTER(_P)],
     "shim_free": [_P, _P],
@@ -30,6 +30,26 @@ _SIGS = {
     "shim_pp_correct": [_P, _P, _I64, _I, C.POINTER(_P), C.POINTER(_I64), C.POINTER(_I), C.POINTER(_P),
                         C.POINTER(_I64), _I, _P],
     "shim_arm_gram_system": [_P, _P, _I, _I, _I, C.c_double, _P, _P],
+    "shim_gram": [_P, _P, _I64, _I64, _I, _P],
+    "shim_gram_batched": [_P, _P, _I64, _I64, _I, _I, _P, _I64],
+    "shim_gram_system": [_P, _P, _I, _I, _I, _D, _P, _P],
+    "shim_cp_update": [_P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I, _P, _P, _P, _P, _I64, _P, _I64, _D],
+    "shim_cp_mode_update": [_P, _P, _I, _I, _I, _D, _P, _I64, _P, _I64, _P, _I64, _I64, _P, _P, _I64, _P, _I64, _D,
+                            _P, _P, _P],
+    "shim_cp_mode_update_batched": [_P, _P, _I, _I, _I, _I, _D, _P, _I64, _P, _I64, _P, _I64, _I64, _P, _P, _P],
+    "shim_cp_mode_update_blocked": [_P, _P, _I, _I, _I, _D, _P, _I64, _I, _P, _P, _I64, _P, _I64, _I64, _P, _P, _I64,
+                                    _P, _I64, _D, _P, _P],
+    "shim_arm_normalize": [_P, C.POINTER(_P), C.POINTER(_I64), _I, _I, _P, _I, _P, _P, C.POINTER(_U), _U, _U,
+                           C.POINTER(_I)],
+    "shim_normalize": [_P, C.POINTER(_P), C.POINTER(_I64), _I, _I, _P],
+    "shim_normalize_ms": [_P, C.POINTER(_P), C.POINTER(_I64), _I, _I, _P, _P, C.POINTER(_U), _U, _U, _P],
+    "shim_normalize_scales": [_P, C.POINTER(_P)],
+    "shim_diff_norms": [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_I64), _I, _I, C.POINTER(_P), _I, _P],
+    "shim_pack_blocks": [_P, _P, _I64, _I64, _I, _I64, _I, _P],
+    "shim_unpack_blocks": [_P, _P, _I64, _I64, _I, _I64, _I, _P],
+    "shim_sumsq": [_P, _P, _I64, _P],
+    "shim_scale_update": [_P, _P, _P, _U, _I],
+    "shim_scale_update_many": [_P, _P, _P, C.POINTER(_U), _U, _U],
 }
 
 
@@ -142,6 +162,79 @@ class Shim:
 
     def arm_gram_system(self, Gall, N, mode, R, lam, S, Sinv):
         self._ck(self.lib.shim_arm_gram_system(self.h, Gall, N, mode, R, lam, S, Sinv))
+
+    # ---- the mode-update, Normalize and factor-side ops (0 / None: a null pointer)
+    def gram(self, W, rows, ld, R, G):
+        self._ck(self.lib.shim_gram(self.h, W, rows, ld, R, G))
+
+    def gram_batched(self, W, rows, ld, R, nstarts, G, gstride):
+        self._ck(self.lib.shim_gram_batched(self.h, W, rows, ld, R, nstarts, G, gstride))
+
+    def gram_system(self, Gall, N, mode, R, lam, S, Sinv):
+        self._ck(self.lib.shim_gram_system(self.h, Gall, N, mode, R, lam, S, Sinv))
+
+    def cp_update(self, M, ldm, Wold, ldw, Wnew, ldn, grad, ldg, rows, R, S, Sinv, gradsq, Winit, ldi, dW, ldd,
+                  ratio):
+        self._ck(self.lib.shim_cp_update(self.h, M, ldm, Wold, ldw, Wnew, ldn, grad, ldg, rows, R, S, Sinv, gradsq,
+                                         Winit, ldi, dW, ldd, ratio))
+
+    def cp_mode_update(self, Gall, N, mode, R, lam, M, ldm, W, ldw, grad, ldg, rows, gradsq, Winit, ldi, dW, ldd,
+                       ratio, S, Sinv, dwsq):
+        self._ck(self.lib.shim_cp_mode_update(self.h, Gall, N, mode, R, lam, M, ldm, W, ldw, grad, ldg, rows, gradsq,
+                                              Winit, ldi, dW, ldd, ratio, S, Sinv, dwsq))
+
+    def cp_mode_update_batched(self, Gall, N, mode, R, nstarts, lam, M, ldm, W, ldw, grad, ldg, rows, gradsq, S,
+                               Sinv):
+        self._ck(self.lib.shim_cp_mode_update_batched(self.h, Gall, N, mode, R, nstarts, lam, M, ldm, W, ldw, grad,
+                                                      ldg, rows, gradsq, S, Sinv))
+
+    def cp_mode_update_blocked(self, Gall, N, mode, R, lam, Mblk, blk, P, scratch, W, ldw, grad, ldg, rows, gradsq,
+                               Winit, ldi, dW, ldd, ratio, S, Sinv):
+        self._ck(self.lib.shim_cp_mode_update_blocked(self.h, Gall, N, mode, R, lam, Mblk, blk, P, scratch, W, ldw,
+                                                      grad, ldg, rows, gradsq, Winit, ldi, dW, ldd, ratio, S, Sinv))
+
+    @staticmethod
+    def _masks(masks):
+        return _arr(_U, list(masks) + [0] * (32 - len(masks))) if masks is not None else None
+
+    def arm_normalize(self, W, rows, R, Gall, mode, wsq, ms_dst=None, masks=None, active=0, fresh=0):
+        taken = _I(0)
+        self._ck(self.lib.shim_arm_normalize(self.h, _arr(_P, W), _arr(_I64, rows), len(W), R, Gall, mode, wsq,
+                                             ms_dst, self._masks(masks), active, fresh, C.byref(taken)))
+        return bool(taken.value)
+
+    def normalize(self, W, rows, R, Gall):
+        self._ck(self.lib.shim_normalize(self.h, _arr(_P, W), _arr(_I64, rows), len(W), R, Gall))
+
+    def normalize_ms(self, W, rows, R, Gall, ms_dst, masks, active, fresh, wsq):
+        self._ck(self.lib.shim_normalize_ms(self.h, _arr(_P, W), _arr(_I64, rows), len(W), R, Gall, ms_dst,
+                                            self._masks(masks), active, fresh, wsq))
+
+    def normalize_scales(self):
+        p = _P()
+        self._ck(self.lib.shim_normalize_scales(self.h, C.byref(p)))
+        return p.value
+
+    def diff_norms(self, A, B, n, store_diff, D, update_prev, out):
+        """A, B, D: lists of device pointers (B, D may be None: a null array; an entry may be 0)"""
+        arr = lambda v: _arr(_P, v) if v is not None else None
+        self._ck(self.lib.shim_diff_norms(self.h, arr(A), arr(B), _arr(_I64, n), len(A), store_diff, arr(D),
+                                          update_prev, out))
+
+    def pack_blocks(self, nat, rows, ld, R, blk, P, blocked):
+        self._ck(self.lib.shim_pack_blocks(self.h, nat, rows, ld, R, blk, P, blocked))
+
+    def unpack_blocks(self, blocked, rows, ld, R, blk, P, nat):
+        self._ck(self.lib.shim_unpack_blocks(self.h, blocked, rows, ld, R, blk, P, nat))
+
+    def sumsq(self, x, n, out):
+        self._ck(self.lib.shim_sumsq(self.h, x, n, out))
+
+    def scale_update(self, dst, scales, mask, set_one):
+        self._ck(self.lib.shim_scale_update(self.h, dst, scales, mask, set_one))
+
+    def scale_update_many(self, dst, scales, masks, active, fresh):
+        self._ck(self.lib.shim_scale_update_many(self.h, dst, scales, self._masks(masks), active, fresh))
 
 
 def compute_units():
