@@ -273,9 +273,23 @@ int ppals_cpd_als_lr(ppals_cp *s, int optimizer, int update_rank, int randomsvd,
 #define PPALS_MULTI_MAX_STARTS 32
 #define PPALS_MULTI_MAX_COLUMNS 128
 int ppals_cp_multi_create(ppals_ctx *ctx, ppals_tensor *V, int R, int nstarts, ppals_cp_multi **out);
+/* A rank sweep: a multi-start session whose starts have their own ranks, start b a rank-ranks[b] model —
+ * ranks 2 .. 10 are 54 columns of ONE tensor scan instead of nine sessions' scans. nstarts in [1, 32],
+ * every ranks[b] >= 1, their sum <= 128; a NULL `ranks` and every other bad argument is refused with
+ * PPALS_ERR_ARG and a message before anything is allocated or launched. Everything below works on such
+ * a session start by start with that start's rank: start b evolves as an ordinary rank-ranks[b] session
+ * does; in device memory it owns the columns [off_b, off_b + ranks[b]) of every factor, gradient and
+ * MTTKRP result, off_b = ranks[0] + .. + ranks[b-1]. A session whose ranks are all equal is the session
+ * ppals_cp_multi_create makes, bit for bit. */
+int ppals_cp_multi_create_ranks(ppals_ctx *ctx, ppals_tensor *V, int nstarts, const int *ranks,
+                                ppals_cp_multi **out);
+/* *nstarts and, when ranks != NULL, ranks[0 .. nstarts) of any multi-start session (nstarts times R for
+ * one from ppals_cp_multi_create) */
+int ppals_cp_multi_ranks(const ppals_cp_multi *s, int *nstarts, int *ranks /* may be NULL */);
 void ppals_cp_multi_destroy(ppals_cp_multi *s);
-/* one start's factors (and gradients) in the Wflat layout of ppals_cp_set_factors; start = -1: all
- * starts, one such block after the other */
+/* one start's factors (and gradients) in the Wflat layout of ppals_cp_set_factors for a session of that
+ * start's rank (sum_i s_i * ranks[start] doubles); start = -1: all starts, one such block after the
+ * other, each of its own length */
 int ppals_cp_multi_set_factors(ppals_cp_multi *s, int start, const double *Wflat,
                                const double *gradWflat /*may be NULL*/);
 int ppals_cp_multi_get_factors(ppals_cp_multi *s, int start, double *Wflat /*may be NULL*/,
@@ -291,10 +305,13 @@ int ppals_cp_multi_gradnorms(ppals_cp_multi *s, double *out);
 /* Sweeps until o->maxiter sweeps, o->timelimit seconds, or the gradient norm of the best start (the
  * one with the smallest residual) is below o->tol; looks every o->resprint sweeps. Uses tol,
  * timelimit, maxiter, lambda and resprint of the options and ignores the rest. *sweeps = sweeps run,
- * *best = the best start at the last look. Returns 1 if it stopped before maxiter, 0 if not. */
+ * *best = the best start at the last look. Returns 1 if it stopped before maxiter, 0 if not.
+ * In a session whose ranks DIFFER the smallest residual is almost always the largest rank's, and its
+ * gradient says nothing about the others: there the run stops when the LARGEST gradient norm over all
+ * starts is below o->tol (or on maxiter / timelimit); *best is still the start with the smallest residual. */
 int ppals_cp_multi_run(ppals_cp_multi *s, const ppals_cp_opts *o, int *sweeps, int *best);
 /* Start `start`'s factors and gradients, device to device, into an ordinary session of the same
- * context, tensor and R; on `dst` the effect is that of ppals_cp_set_factors (caches dropped, Grams
+ * context and tensor and of that start's rank (any other rank: PPALS_ERR_ARG, the message names both); on `dst` the effect is that of ppals_cp_set_factors (caches dropped, Grams
  * refreshed): the winner goes on there with Normalize, PP, the drivers and the model export.
  * A non-negative `dst` (ppals_cp_set_nonneg) takes from a non-negative multi-start session only: from
  * an unconstrained one the call is refused with PPALS_ERR_UNSUPPORTED. An ordinary `dst` takes from both. */
@@ -305,7 +322,8 @@ int ppals_cp_multi_take(ppals_cp_multi *s, int start, ppals_cp *dst);
  * PPALS_OPT_SIMPLE from the same factors (cyclic modes 0..N-1, no Normalize, S that start's Hadamard of
  * Grams + lambda I, grad from the pre-update row, entries >= PPALS_NN_FLOOR). Sweeps, run, residuals,
  * gradnorms, the schedules and get_factors run unchanged on top. PPALS_ERR_UNSUPPORTED, before anything
- * is launched: R > 64 (possible at nstarts == 1 only) and PPALS_TEST_BLOCKED_UPDATE. PPALS_ERR_ARG:
+ * is launched: a start of rank > 64 and PPALS_TEST_BLOCKED_UPDATE. Starts of different ranks each take the
+ * HALS pass of their own rank. PPALS_ERR_ARG:
  * factors of any start with a negative or non-finite entry — those already set when the flag is turned
  * on (the flag then stays off), and those handed to ppals_cp_multi_set_factors later (the host buffer
  * is looked at before anything is uploaded). ppals_cp_multi_get_nonneg: 1 / 0, PPALS_ERR_ARG for NULL. */

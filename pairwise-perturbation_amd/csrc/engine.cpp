@@ -230,12 +230,33 @@ double tensor_norm(Ops &ops, Comm &comm, const TensorDesc &V) {
 }
 
 // ============================================================================ CpEngine
-CpEngine::CpEngine(Ops &ops, Comm &comm, const TensorDesc &V, int R, int nstarts, bool multi)
-    : ops_(ops), comm_(comm), V_(V), N_(V.order), R_(R * nstarts), P_(comm.size()), rank_(comm.rank()),
-      K_(nstarts), Rs_(R), multi_(multi || nstarts > 1) {
+// total columns of a session: nstarts * R, or the sum of the starts' own ranks
+static int total_columns(int R, int nstarts, const int *ranks) {
+  if (!ranks) return R * nstarts;
+  int t = 0;
+  for (int b = 0; b < nstarts; b++) t += ranks[b];
+  return t;
+}
+
+CpEngine::CpEngine(Ops &ops, Comm &comm, const TensorDesc &V, int R, int nstarts, bool multi, const int *ranks)
+    : ops_(ops), comm_(comm), V_(V), N_(V.order), R_(total_columns(R, nstarts, ranks)), P_(comm.size()),
+      rank_(comm.rank()), K_(nstarts), Rs_(R), multi_(multi || nstarts > 1 || ranks) {
   dist_ = P_ > 1 || (force_comm_path() && !comm.is_self());
-  if (R <= 0) throw std::runtime_error("ppals: rank must be positive");
   if (nstarts <= 0) throw std::runtime_error("ppals: the number of starts must be positive");
+  if (multi_) {  // the per-start table; equal ranks keep Rs_ and the batched ops (engine.h)
+    if (nstarts > kMaxStarts) throw std::runtime_error("ppals: too many starts");
+    tab_.nstarts = nstarts;
+    Rs_ = 0;
+    for (int b = 0; b < nstarts; b++) {
+      const int rb = ranks ? ranks[b] : R;
+      if (rb <= 0) throw std::runtime_error("ppals: rank must be positive");
+      tab_.col[b + 1] = tab_.col[b] + rb;
+      tab_.sq[b + 1] = tab_.sq[b] + rb * rb;
+      if (rb != tab_.rank(0)) ragged_ = true;
+      Rs_ = std::max(Rs_, rb);
+    }
+  }
+  if (Rs_ <= 0) throw std::runtime_error("ppals: rank must be positive");
   if (multi_ && dist_) throw Unsupported("ppals: a multi-start session runs on one rank");
   residual_form_ = residual_form_env();
   W_.resize(N_);
@@ -254,9 +275,11 @@ CpEngine::CpEngine(Ops &ops, Comm &comm, const TensorDesc &V, int R, int nstarts
     maxs_ = std::max(maxs_, V_.glens[i]);
     maxblk_ = std::max(maxblk_, block_rows(V_.glens[i], P_));
   }
-  G_ = (double *)ops_.alloc(sizeof(double) * N_ * R_ * R_);
-  S_ = (double *)ops_.alloc(sizeof(double) * R_ * R_);
-  Sinv_ = (double *)ops_.alloc(sizeof(double) * R_ * R_);
+  // (a multi-start session keeps the diagonal blocks only: sum_b R_b^2 entries per mode and system)
+  const size_t sys_n = multi_ ? (size_t)tab_.sq[K_] : (size_t)R_ * R_;
+  G_ = (double *)ops_.alloc(sizeof(double) * N_ * sys_n);
+  S_ = (double *)ops_.alloc(sizeof(double) * sys_n);
+  Sinv_ = (double *)ops_.alloc(sizeof(double) * sys_n);
   gradsq_ = (double *)ops_.alloc(sizeof(double) * MAX_ORDER * K_);
   scal_ = (double *)ops_.alloc(sizeof(double) * 4 * MAX_ORDER);
   ops_.zero(gradsq_, sizeof(double) * MAX_ORDER * K_);
@@ -629,6 +652,10 @@ void CpEngine::compute_node(int idx) {
 }
 
 void CpEngine::refresh_grams() {
+  if (multi_ && ragged_) {  // Gram (start b, mode i) at G_ + N sq_b + i R_b^2
+    for (int i = 0; i < N_; i++) ops_.gram_ragged(W_[i], V_.glens[i], V_.glens[i], tab_, N_, i, G_);
+    return;
+  }
   if (multi_) {  // the diagonal blocks only: Gram (start b, mode i) at G_ + (b N + i) Rs^2
     for (int i = 0; i < N_; i++)
       ops_.gram_batched(W_[i], V_.glens[i], V_.glens[i], Rs_, K_, G_ + (size_t)i * Rs_ * Rs_,
@@ -673,7 +700,7 @@ void CpEngine::set_factors(const double *Wflat, const double *gradWflat) {
 void CpEngine::set_nonneg(bool on) {
   if (on) {
     if (P_ > 1 || dist_) throw Unsupported("ppals: a non-negative session runs on one rank");
-    if (Rs_ > 64) throw Unsupported("ppals: a non-negative session supports R <= 64");
+    if (Rs_ > 64) throw Unsupported("ppals: a non-negative session supports R <= 64");  // (the largest start)
     if (test_blocks_ > 1)
       throw Unsupported("ppals: PPALS_TEST_BLOCKED_UPDATE has no non-negative update");
   }
@@ -691,7 +718,7 @@ bool CpEngine::factors_nonneg() {
 }
 
 // ---------------------------------------------------------------------------- multi-start sessions
-// One start's factors are the column block [b Rs, (b+1) Rs) of every W_[i]: s_i * Rs contiguous doubles.
+// One start's factors are the column block [col_b, col_b + R_b) of every W_[i]: s_i * R_b contiguous doubles.
 void CpEngine::set_factors_start(int start, const double *Wflat, const double *gradWflat) {
   if (!multi_) throw std::logic_error("ppals: not a multi-start session");
   if (start < -1 || start >= K_) throw std::runtime_error("ppals: start out of range");
@@ -699,13 +726,13 @@ void CpEngine::set_factors_start(int start, const double *Wflat, const double *g
   const int b0 = start < 0 ? 0 : start, b1 = start < 0 ? K_ : start + 1;
   for (int b = b0; b < b1; b++)
     for (int i = 0; i < N_; i++) {
-      const size_t n = (size_t)V_.glens[i] * Rs_;
-      ops_.h2d(W_[i] + (size_t)b * n, w, n * sizeof(double));
+      const size_t n = (size_t)V_.glens[i] * tab_.rank(b), at = (size_t)V_.glens[i] * tab_.col[b];
+      ops_.h2d(W_[i] + at, w, n * sizeof(double));
       w += n;
       // ||grad_W[i]||^2 of the caller's gradients, as set_factors keeps it (0 without gradients)
       double gsq = 0;
       if (g) {
-        ops_.h2d(gradW_[i] + (size_t)b * n, g, n * sizeof(double));
+        ops_.h2d(gradW_[i] + at, g, n * sizeof(double));
         for (size_t e = 0; e < n; e++) gsq += g[e] * g[e];
         g += n;
       }
@@ -723,13 +750,13 @@ void CpEngine::get_factors_start(int start, double *Wflat, double *gradWflat) {
   const int b0 = start < 0 ? 0 : start, b1 = start < 0 ? K_ : start + 1;
   for (int b = b0; b < b1; b++)
     for (int i = 0; i < N_; i++) {
-      const size_t n = (size_t)V_.glens[i] * Rs_;
+      const size_t n = (size_t)V_.glens[i] * tab_.rank(b), at = (size_t)V_.glens[i] * tab_.col[b];
       if (w) {
-        ops_.d2h(w, W_[i] + (size_t)b * n, n * sizeof(double));
+        ops_.d2h(w, W_[i] + at, n * sizeof(double));
         w += n;
       }
       if (g) {
-        ops_.d2h(g, gradW_[i] + (size_t)b * n, n * sizeof(double));
+        ops_.d2h(g, gradW_[i] + at, n * sizeof(double));
         g += n;
       }
     }
@@ -751,13 +778,14 @@ void CpEngine::residuals(double *out) {
   if (!multi_) throw std::logic_error("ppals: not a multi-start session");
   int64_t M, K;
   split_sizes(V_, &M, &K);
-  if (!Qbuf_) Qbuf_ = (double *)ops_.alloc(sizeof(double) * M * R_);
-  if (!Pbuf_) Pbuf_ = (double *)ops_.alloc(sizeof(double) * K * R_);
+  if (!Qbuf_) Qbuf_ = (double *)ops_.alloc(sizeof(double) * M * Rs_);  // (Rs_: the largest start)
+  if (!Pbuf_) Pbuf_ = (double *)ops_.alloc(sizeof(double) * K * Rs_);
   std::vector<double *> Wb(N_);
   for (int b = 0; b < K_; b++) {
-    for (int i = 0; i < N_; i++) Wb[i] = W_[i] + (size_t)b * V_.glens[i] * Rs_;
-    split_krp(ops_, V_, Rs_, Wb.data(), Qbuf_, Pbuf_, &M, &K);
-    ops_.residual_sq(V_.data, V_.dtype, M, K, Qbuf_, Pbuf_, Rs_, scal_);
+    const int rb = tab_.rank(b);
+    for (int i = 0; i < N_; i++) Wb[i] = W_[i] + (size_t)tab_.col[b] * V_.glens[i];
+    split_krp(ops_, V_, rb, Wb.data(), Qbuf_, Pbuf_, &M, &K);
+    ops_.residual_sq(V_.data, V_.dtype, M, K, Qbuf_, Pbuf_, rb, scal_);
     double h = 0;
     ops_.d2h(&h, scal_, sizeof(double));
     out[b] = std::sqrt(h);
@@ -778,7 +806,10 @@ int CpEngine::run_multi(const CpOpts &o, int *sweeps_out, int *best_out) {
       if (o.verbose)
         std::printf("  [sweeps]=  %d  [best]  %d  [gradnorm]  %.13g  [residual]  %.13g  [dtime]  %g\n", sweeps,
                     best, gn[best], res[best], now() - t0);
-      stopped = gn[best] < o.tol || now() - t0 > o.timelimit;
+      // starts of different ranks: the smallest residual is (almost always) the largest rank, whose
+      // gradient says nothing about the others — the run goes on until every start is below tol
+      const double gstop = ragged_ ? *std::max_element(gn.begin(), gn.end()) : gn[best];
+      stopped = gstop < o.tol || now() - t0 > o.timelimit;
       if (stopped || sweeps >= o.maxiter) break;
     }
     update_modes(0, N_, o.lambda);
@@ -795,13 +826,14 @@ void CpEngine::take_from(CpEngine &src, int start) {
   // (a non-negative multi-start session's factors are >= the floor by construction)
   if (nonneg_ && !src.nonneg_)
     throw Unsupported("ppals: a non-negative session does not take an unconstrained multi-start's factors");
-  if (!src.multi_ || start < 0 || start >= src.K_ || src.Rs_ != R_ || src.N_ != N_ ||
+  if (!src.multi_ || start < 0 || start >= src.K_ || src.tab_.rank(start) != R_ || src.N_ != N_ ||
       src.V_.data != V_.data)
     throw std::runtime_error("ppals: take: sessions do not match");
   for (int i = 0; i < N_; i++) {
     const size_t n = (size_t)V_.glens[i] * R_;
-    ops_.d2d(W_[i], src.W_[i] + (size_t)start * n, n * sizeof(double));
-    ops_.d2d(gradW_[i], src.gradW_[i] + (size_t)start * n, n * sizeof(double));
+    const size_t at = (size_t)V_.glens[i] * src.tab_.col[start];
+    ops_.d2d(W_[i], src.W_[i] + at, n * sizeof(double));
+    ops_.d2d(gradW_[i], src.gradW_[i] + at, n * sizeof(double));
     ops_.d2d(gradsq_ + i, src.gradsq_ + (size_t)i * src.K_ + start, sizeof(double));
   }
   // (gradnorm() reads the copied per-mode sums: the same number set_factors would have formed on the
@@ -844,6 +876,15 @@ void CpEngine::mode_update(int i, const double *M, int64_t ldm, double lambda, b
   const int64_t s = V_.glens[i];
   if (multi_) {  // block-diagonal over starts: one batched update, every start its own system
     if (pp) throw std::logic_error("ppals: no PP update in a multi-start session");
+    if (ragged_) {  // starts of different ranks: the same updates, addressed through the table
+      if (nonneg_)
+        ops_.cp_mode_update_nn_ragged(G_, N_, i, tab_, lambda, M, ldm, W_[i], s, gradW_[i], s, s,
+                                      gradsq_ + (size_t)i * K_, S_);
+      else
+        ops_.cp_mode_update_ragged(G_, N_, i, tab_, lambda, M, ldm, W_[i], s, gradW_[i], s, s,
+                                   gradsq_ + (size_t)i * K_, S_, Sinv_);
+      return;
+    }
     if (nonneg_) {  // one HALS pass per start, all starts in one batched update
       ops_.cp_mode_update_nn_batched(G_, N_, i, Rs_, K_, lambda, M, ldm, W_[i], s, gradW_[i], s, s,
                                      gradsq_ + (size_t)i * K_, S_);

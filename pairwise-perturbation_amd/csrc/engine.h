@@ -94,7 +94,12 @@ class CpEngine {
   // nstarts > 1 (or multi): a multi-start session — `nstarts` independent rank-R models share every
   // contraction of the sweep. The factor matrices hold nstarts * R columns, start-major (start b owns
   // columns [b R, (b+1) R)); only the R x R normal equations know about starts. One rank only.
-  CpEngine(Ops &ops, Comm &comm, const TensorDesc &V, int R, int nstarts = 1, bool multi = false);
+  // ranks != nullptr (a rank sweep): start b is a rank-ranks[b] model and owns the columns
+  // [col_b, col_b + ranks[b]), col_b = sum_{c<b} ranks[c]; R is ignored. Scans, leaves and schedules work on
+  // the R_ columns in total and know nothing of this. A session whose ranks are all equal — however it
+  // was created — takes exactly the batched ops of nstarts x R; only differing ranks take the ragged ops.
+  CpEngine(Ops &ops, Comm &comm, const TensorDesc &V, int R, int nstarts = 1, bool multi = false,
+           const int *ranks = nullptr);
   ~CpEngine();
 
   void set_factors(const double *Wflat, const double *gradWflat);
@@ -162,7 +167,8 @@ class CpEngine {
   // ---- multi-start sessions (start = -1: every start, concatenated start-major) ----
   bool is_multi() const { return multi_; }
   int nstarts() const { return K_; }
-  int start_rank() const { return Rs_; }
+  int start_rank() const { return Rs_; }  // the largest start's rank (every start's, when they are equal)
+  int start_rank(int b) const { return multi_ ? tab_.rank(b) : R_; }
   void set_factors_start(int start, const double *Wflat, const double *gradWflat);
   void get_factors_start(int start, double *Wflat, double *gradWflat);
   void gradnorms(double *out);  // [nstarts], each what gradnorm() of a session of that start returns
@@ -360,7 +366,12 @@ class CpEngine {
   // multi-start: K_ starts of Rs_ columns each, R_ = K_ * Rs_. G_ then holds, start by start, the N
   // Grams (Rs_ x Rs_) of that start — the blocks between starts are never formed —, S_ / Sinv_ one
   // system per start, gradsq_ K_ sums per mode (gradsq_[mode * K_ + start])
+  // tab_ is the per-start table (rank, column offset col_b, system offset sq_b = sum_{c<b} R_c^2 into
+  // S_ / Sinv_, Gram offset N sq_b: start b, mode i at G_ + N sq_b + i R_b^2); equal ranks make it the
+  // arithmetic above, Rs_ the common rank. ragged_: the ranks differ, Rs_ is the largest.
   int K_ = 1, Rs_ = 0;
+  StartTable tab_;
+  bool ragged_ = false;
   bool multi_ = false;
   bool nonneg_ = false;  // set_nonneg
   bool dist_ = false;  // take the collective code paths (P_ > 1, or PPALS_FORCE_COMM=1 for tests)

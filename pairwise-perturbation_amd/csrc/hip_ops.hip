@@ -126,6 +126,10 @@ class HipOps : public Ops {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
     HIP_CHECK(hipFuncSetAttribute((const void *)k_cp_mode_update_batched<true, true>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_cp_mode_update_ragged<false, false>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_cp_mode_update_ragged<true, true>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
     if (const char *v = getenv("PPALS_FORCE_JACOBI")) force_jacobi_ = atoi(v);
     if (const char *v = getenv("PPALS_EIG_FAST")) {
       eig_fast_ = atoi(v);  // 0: always the full solver; 2: warm steps as usual, cold starts on the full solver
@@ -1640,6 +1644,92 @@ class HipOps : public Ops {
       hipLaunchKernelGGL((k_cp_mode_update_batched<false, false>), dim3((unsigned)nstarts), dim3(1024), lds,
                          st_, Gall, N, mode, R, lambda, M, ldm, W, ldw, grad, ldg, rows, gradsq, S, Sinv);
     prof_end();
+    HIP_CHECK(hipGetLastError());
+  }
+  // ---- rank-sweep sessions: the three ops above for starts of different ranks (StartTable) ----
+  // what the table must hold before a kernel indexes by it (the engine builds it; checked all the same)
+  static void check_table(const StartTable &t) {
+    bool ok = t.nstarts >= 1 && t.nstarts <= kMaxStarts && t.col[0] == 0 && t.sq[0] == 0;
+    for (int b = 0; ok && b < t.nstarts; b++)
+      ok = t.rank(b) >= 1 && t.sq[b + 1] == t.sq[b] + t.rank(b) * t.rank(b);
+    if (!ok) throw std::runtime_error("ppals: malformed table of starts");
+  }
+  // One launch, a 1024-thread workgroup per start, each with its own rank (k_cp_mode_update_ragged). The
+  // routes of cp_mode_update_batched, decided ONCE per launch with the largest rank: its LDS sizes the
+  // launch, and a launch is staged only if the largest start's M and W fit.
+  void cp_mode_update_ragged(double *Gall, int N, int mode, const StartTable &t, double lambda, const double *M,
+                             int64_t ldm, double *W, int64_t ldw, double *grad, int64_t ldg, int64_t rows,
+                             double *gradsq, double *S, double *Sinv) override {
+    RoctxRange roctx_("K4-K6 mode update (starts of different ranks)");
+    check_table(t);
+    const int R = t.max_rank();
+    const size_t lds = sizeof(double) * (32 + 2 * (size_t)R * R + 2 * (size_t)R * (R + 1) + 64) +
+                       sizeof(int) * 64;
+    const size_t stage = 2 * sizeof(double) * (size_t)rows * R;
+    const bool staged = lds + stage <= 150 * 1024;
+    if (R > 64 || force_jacobi_ || (double)rows * R >= 2.0e9 ||
+        (!staged && (int64_t)rows * R > kUpdateRowParallelFrom)) {
+      route("%s", "update_ragged.loop");
+      for (int b = 0; b < t.nstarts; b++) {
+        const size_t c0 = (size_t)t.col[b];
+        prof_begin(1, 0.0);
+        cp_mode_update(Gall + (size_t)N * t.sq[b], N, mode, t.rank(b), lambda, M + c0 * ldm, ldm, W + c0 * ldw,
+                       ldw, grad + c0 * ldg, ldg, rows, gradsq + b, nullptr, rows, nullptr, rows, 1.0,
+                       S ? S + t.sq[b] : nullptr, Sinv ? Sinv + t.sq[b] : nullptr, nullptr);
+        prof_end();
+      }
+      return;
+    }
+    if (norm_armed_) throw std::logic_error("ppals: armed Normalize in front of a batched mode update");
+    sys_ready_ = false;
+    sys_armed_ = false;
+    prof_begin(1, 0.0);
+    route("%s", staged ? "update_ragged.staged" : "update_ragged.unstaged");
+    if (staged)
+      hipLaunchKernelGGL((k_cp_mode_update_ragged<true, true>), dim3((unsigned)t.nstarts), dim3(1024),
+                         lds + stage, st_, Gall, N, mode, t, lambda, M, ldm, W, ldw, grad, ldg, rows, gradsq, S,
+                         Sinv);
+    else
+      hipLaunchKernelGGL((k_cp_mode_update_ragged<false, false>), dim3((unsigned)t.nstarts), dim3(1024), lds,
+                         st_, Gall, N, mode, t, lambda, M, ldm, W, ldw, grad, ldg, rows, gradsq, S, Sinv);
+    prof_end();
+    HIP_CHECK(hipGetLastError());
+  }
+  // Two launches whatever the ranks: the row kernel on (row tiles x starts) with the LDS of the largest
+  // rank, then a workgroup per start for its tile sums and its Gram. Bracketed as the batched one is.
+  void cp_mode_update_nn_ragged(double *Gall, int N, int mode, const StartTable &t, double lambda,
+                                const double *M, int64_t ldm, double *W, int64_t ldw, double *grad, int64_t ldg,
+                                int64_t rows, double *gradsq, double *S) override {
+    RoctxRange roctx_("K4-K6 mode update (non-negative, starts of different ranks)");
+    check_table(t);
+    const int R = t.max_rank();
+    if (R > 64) throw Unsupported("ppals: the non-negative mode update supports R <= 64");
+    if (sys_armed_ || sys_ready_ || norm_armed_)
+      throw std::logic_error("ppals: armed S / Normalize in front of a non-negative mode update");
+    if (rows <= 0) {
+      Ops::cp_mode_update_nn_ragged(Gall, N, mode, t, lambda, M, ldm, W, ldw, grad, ldg, rows, gradsq, S);
+      return;
+    }
+    const int64_t nb = (rows + 63) / 64;
+    if (nb * t.nstarts > (int64_t)1 << 30)
+      throw std::runtime_error("ppals: mode too long for the non-negative update");
+    double *part = (double *)ensure(ws_big2_, ws_big2_sz_, sizeof(double) * (size_t)nb * t.nstarts);
+    const size_t lds = sizeof(double) * ((size_t)R * R + 64 * (size_t)R);
+    prof_begin(1, 0.0);
+    hipLaunchKernelGGL(k_cp_update_nn_ragged, dim3((unsigned)nb, (unsigned)t.nstarts), dim3(64), lds, st_, Gall, N,
+                       mode, t, lambda, M, ldm, W, ldw, grad, ldg, rows, part, S, kNnFloor);
+    hipLaunchKernelGGL(k_cp_finish_nn_ragged, dim3((unsigned)t.nstarts), dim3(1024), 0, st_, part, (int)nb,
+                       gradsq, W, ldw, rows, t, N, mode, Gall);
+    prof_end();
+    HIP_CHECK(hipGetLastError());
+  }
+  // one launch, a workgroup per start, every pair's sum that of k_gram
+  void gram_ragged(const double *W, int64_t rows, int64_t ld, const StartTable &t, int N, int mode,
+                   double *Gall) override {
+    RoctxRange roctx_("K4 gram (starts of different ranks)");
+    check_table(t);
+    hipLaunchKernelGGL(k_gram_ragged, dim3((unsigned)t.nstarts), dim3(1024), 0, st_, W, rows, ld, t, N, mode,
+                       Gall);
     HIP_CHECK(hipGetLastError());
   }
   bool arm_normalize(double *const *W, const int64_t *rows, int N, int R, double *Gall, int mode,

@@ -27,7 +27,8 @@ namespace ppals {
 // k_cp_mode_update_batched): start b reads its N Grams at Gall + b N R^2, owns columns [b R, (b+1) R) of M,
 // W and grad, writes its tiles' sums to gradsq_part[b * gridDim.x + tile] and its S to S_out + b R^2.
 // Nothing is shared between two starts. An ordinary session launches gridDim.y == 1: every offset is 0.
-__global__ __launch_bounds__(64) void k_cp_update_nn(
+// (the body, for ONE workgroup on one start's pointers: k_cp_update_nn and k_cp_update_nn_ragged below)
+__device__ __forceinline__ void cp_update_nn_body(
     const double *__restrict__ Gall, int N, int mode, int R, double lambda,
     const double *__restrict__ M, int64_t ldm, double *__restrict__ W, int64_t ldw,
     double *__restrict__ grad, int64_t ldg, int64_t rows, double *__restrict__ gradsq_part,
@@ -36,13 +37,6 @@ __global__ __launch_bounds__(64) void k_cp_update_nn(
   double *sS = lds;           // R x R, column-major (symmetric)
   double *sW = lds + R * R;   // R x 64: the tile's rows, column q of lane l at q * 64 + l
   const int lane = threadIdx.x;
-  const int64_t b = blockIdx.y;
-  Gall += b * N * R * R;
-  M += b * R * ldm;
-  W += b * R * ldw;
-  grad += b * R * ldg;
-  gradsq_part += b * gridDim.x;
-  if (S_out) S_out += b * R * R;
   for (int e = lane; e < R * R; e += 64) {
     const double v = hadamard_entry(Gall, N, mode, R, lambda, e);
     sS[e] = v;
@@ -78,6 +72,31 @@ __global__ __launch_bounds__(64) void k_cp_update_nn(
   if (lane == 0) gradsq_part[blockIdx.x] = gs;
 }
 
+__global__ __launch_bounds__(64) void k_cp_update_nn(
+    const double *__restrict__ Gall, int N, int mode, int R, double lambda,
+    const double *__restrict__ M, int64_t ldm, double *__restrict__ W, int64_t ldw,
+    double *__restrict__ grad, int64_t ldg, int64_t rows, double *__restrict__ gradsq_part,
+    double *__restrict__ S_out, double nn_floor) {
+  const int64_t b = blockIdx.y;
+  cp_update_nn_body(Gall + b * N * R * R, N, mode, R, lambda, M + b * R * ldm, ldm, W + b * R * ldw, ldw,
+                    grad + b * R * ldg, ldg, rows, gradsq_part + b * gridDim.x, S_out ? S_out + b * R * R : nullptr,
+                    nn_floor);
+}
+// Rank-sweep sessions: blockIdx.y is a start of its own rank (StartTable by value, as
+// k_cp_mode_update_ragged): R_b columns from col[b], Grams at Gall + N sq[b], S to S_out + sq[b]. The
+// launch's LDS is sized for the largest rank; a start uses the front of it.
+__global__ __launch_bounds__(64) void k_cp_update_nn_ragged(
+    const double *__restrict__ Gall, int N, int mode, StartTable t, double lambda,
+    const double *__restrict__ M, int64_t ldm, double *__restrict__ W, int64_t ldw,
+    double *__restrict__ grad, int64_t ldg, int64_t rows, double *__restrict__ gradsq_part,
+    double *__restrict__ S_out, double nn_floor) {
+  const int b = blockIdx.y;
+  const int64_t c0 = t.col[b], so = t.sq[b];
+  cp_update_nn_body(Gall + N * so, N, mode, t.col[b + 1] - t.col[b], lambda, M + c0 * ldm, ldm, W + c0 * ldw, ldw,
+                    grad + c0 * ldg, ldg, rows, gradsq_part + (int64_t)b * gridDim.x, S_out ? S_out + so : nullptr,
+                    nn_floor);
+}
+
 // What follows the row kernel in a multi-start session, for all starts in ONE launch: workgroup b adds
 // start b's `ntiles` tile sums into gradsq[b] (the order of k_sum_partials) and refreshes start b's Gram
 // of the new W into Gall (the per-pair order of k_gram: 16 waves share the R (R + 1) / 2 pairs).
@@ -92,6 +111,22 @@ __global__ __launch_bounds__(1024) void k_cp_finish_nn_batched(
   s = block_sum(s, lds);
   if (threadIdx.x == 0) gradsq[b] = s;
   gram_pairs(W + b * R * ldw, rows, ldw, R, Gall + (b * N + mode) * R * R, threadIdx.x >> 6, blockDim.x >> 6);
+}
+
+// The same for starts of different ranks (after k_cp_update_nn_ragged).
+__global__ __launch_bounds__(1024) void k_cp_finish_nn_ragged(
+    const double *__restrict__ part, int ntiles, double *__restrict__ gradsq, const double *__restrict__ W,
+    int64_t ldw, int64_t rows, StartTable t, int N, int mode, double *__restrict__ Gall) {
+  __shared__ double lds[17];
+  const int b = blockIdx.x;
+  const int R = t.col[b + 1] - t.col[b];
+  part += (int64_t)b * ntiles;
+  double s = 0;
+  for (int i = threadIdx.x; i < ntiles; i += blockDim.x) s += part[i];
+  s = block_sum(s, lds);
+  if (threadIdx.x == 0) gradsq[b] = s;
+  gram_pairs(W + (int64_t)t.col[b] * ldw, rows, ldw, R, Gall + (int64_t)N * t.sq[b] + (int64_t)mode * R * R,
+             threadIdx.x >> 6, blockDim.x >> 6);
 }
 
 }  // namespace ppals

@@ -727,6 +727,17 @@ __global__ void k_gram(const double *__restrict__ W, int64_t rows, int64_t ld, i
              (int)(((int64_t)gridDim.x * blockDim.x) >> 6));
 }
 
+// Rank-sweep sessions: the Grams of one mode for starts of different ranks in ONE launch, workgroup b start
+// b's (its 16 waves share the R_b (R_b + 1) / 2 pairs; a pair's sum is that of k_gram), into
+// Gall + N sq[b] + mode R_b^2.
+__global__ __launch_bounds__(1024) void k_gram_ragged(const double *__restrict__ W, int64_t rows, int64_t ld,
+                                                      StartTable t, int N, int mode, double *__restrict__ Gall) {
+  const int b = blockIdx.x;
+  const int R = t.col[b + 1] - t.col[b];
+  gram_pairs(W + (int64_t)t.col[b] * ld, rows, ld, R, Gall + (int64_t)N * t.sq[b] + (int64_t)mode * R * R,
+             threadIdx.x >> 6, blockDim.x >> 6);
+}
+
 // ------------------------------------------------------------------ S and S^{-1}  (K4 + K6a)
 // wave-level ordering point for LDS traffic between lanes of ONE wave (LDS executes a wave's DS
 // instructions in order; this only stops the compiler from moving them)
@@ -1839,6 +1850,26 @@ __global__ __launch_bounds__(1024) void k_cp_mode_update_batched(
   cp_mode_update_body<STAGE, MF, false>(Gall + b * N * rr, N, mode, R, lambda, M + c0 * ldm, ldm, W + c0 * ldw, ldw,
                                  grad + c0 * ldg, ldg, rows, gradsq + b, nullptr, 0, nullptr, 0, 1.0,
                                  S_out ? S_out + b * rr : nullptr, Sinv_out ? Sinv_out + b * rr : nullptr,
+                                 nullptr, 0, NormArgs(), 0);
+}
+
+// Rank-sweep sessions: the same launch for starts of DIFFERENT ranks. The table travels by value in the
+// kernel arguments (blockIdx.x is wave-uniform: its reads are scalar loads of the argument segment);
+// workgroup b runs the body with its own rank R_b = col[b+1] - col[b] on the columns [col[b], col[b+1]),
+// its N Grams at Gall + N sq[b] and its system at S_out / Sinv_out + sq[b]. The dynamic LDS of the launch is
+// sized for the largest rank, the body carves it up by the rank it is given; STAGE is one decision per
+// launch (made with the largest rank). The workgroups cost rows R_b^2 + R_b^3 each and the launch lasts as
+// long as its largest start: with at most 32 workgroups on 256 CUs nothing is gained by balancing them.
+template <bool STAGE, bool MF = false>
+__global__ __launch_bounds__(1024) void k_cp_mode_update_ragged(
+    double *__restrict__ Gall, int N, int mode, StartTable t, double lambda, const double *__restrict__ M,
+    int64_t ldm, double *W, int64_t ldw, double *__restrict__ grad, int64_t ldg, int64_t rows,
+    double *__restrict__ gradsq, double *__restrict__ S_out, double *__restrict__ Sinv_out) {
+  const int b = blockIdx.x;
+  const int64_t c0 = t.col[b], so = t.sq[b];
+  cp_mode_update_body<STAGE, MF, false>(Gall + N * so, N, mode, t.col[b + 1] - t.col[b], lambda, M + c0 * ldm, ldm,
+                                 W + c0 * ldw, ldw, grad + c0 * ldg, ldg, rows, gradsq + b, nullptr, 0, nullptr,
+                                 0, 1.0, S_out ? S_out + so : nullptr, Sinv_out ? Sinv_out + so : nullptr,
                                  nullptr, 0, NormArgs(), 0);
 }
 

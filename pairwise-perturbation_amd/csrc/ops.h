@@ -37,6 +37,22 @@ constexpr int MAX_ORDER = 8;
 constexpr double kNnFloor = 1e-16;
 
 // a factor-matrix operand of a Khatri-Rao product: `rows` rows starting at `ptr`, leading dim ld
+// The starts of a multi-start session whose ranks differ (a rank sweep), handed to the ragged ops — and to
+// their kernels BY VALUE, as a kernel argument: start b has rank col[b+1] - col[b], owns the columns
+// [col[b], col[b+1]) of every factor, gradient and MTTKRP result; sq[b] = sum_{c<b} R_c^2 is its offset into
+// S / Sinv, N * sq[b] the offset of its N Grams.
+constexpr int kMaxStarts = 32;
+struct StartTable {
+  int nstarts = 0;
+  int col[kMaxStarts + 1] = {0};
+  int sq[kMaxStarts + 1] = {0};
+  int rank(int b) const { return col[b + 1] - col[b]; }
+  int max_rank() const {
+    int m = 0;
+    for (int b = 0; b < nstarts; b++) m = rank(b) > m ? rank(b) : m;
+    return m;
+  }
+};
 struct FactorRef {
   const double *ptr;
   int64_t rows;
@@ -392,6 +408,35 @@ class Ops {
   virtual void gram_batched(const double *W, int64_t rows, int64_t ld, int R, int nstarts, double *G,
                             int64_t gstride) {
     for (int b = 0; b < nstarts; b++) gram(W + (size_t)b * R * ld, rows, ld, R, G + (size_t)b * gstride);
+  }
+  // The three ops above for starts of DIFFERENT ranks (rank-sweep sessions, StartTable): start b owns
+  // columns [t.col[b], t.col[b+1]) of M, W and grad, its N Grams (R_b x R_b) sit at Gall + N t.sq[b], its
+  // system at S / Sinv + t.sq[b]; gradsq[b] = ||grad_b||^2. Nothing couples two starts. Back ends may
+  // run all of them in one launch; a session whose ranks are all equal never comes here.
+  virtual void cp_mode_update_ragged(double *Gall, int N, int mode, const StartTable &t, double lambda,
+                                     const double *M, int64_t ldm, double *W, int64_t ldw, double *grad,
+                                     int64_t ldg, int64_t rows, double *gradsq, double *S, double *Sinv) {
+    for (int b = 0; b < t.nstarts; b++)
+      cp_mode_update(Gall + (size_t)N * t.sq[b], N, mode, t.rank(b), lambda, M + (size_t)t.col[b] * ldm, ldm,
+                     W + (size_t)t.col[b] * ldw, ldw, grad + (size_t)t.col[b] * ldg, ldg, rows, gradsq + b,
+                     nullptr, rows, nullptr, rows, 1.0, S ? S + t.sq[b] : nullptr,
+                     Sinv ? Sinv + t.sq[b] : nullptr);
+  }
+  virtual void cp_mode_update_nn_ragged(double *Gall, int N, int mode, const StartTable &t, double lambda,
+                                        const double *M, int64_t ldm, double *W, int64_t ldw, double *grad,
+                                        int64_t ldg, int64_t rows, double *gradsq, double *S) {
+    for (int b = 0; b < t.nstarts; b++)
+      cp_mode_update_nn(Gall + (size_t)N * t.sq[b], N, mode, t.rank(b), lambda, M + (size_t)t.col[b] * ldm,
+                        ldm, W + (size_t)t.col[b] * ldw, ldw, grad + (size_t)t.col[b] * ldg, ldg, rows,
+                        gradsq + b, S ? S + t.sq[b] : nullptr);
+  }
+  // G_b = W_b^T W_b of the same column blocks into the session's Gram store: Gram (start b, mode) at
+  // Gall + N t.sq[b] + mode R_b^2
+  virtual void gram_ragged(const double *W, int64_t rows, int64_t ld, const StartTable &t, int N, int mode,
+                           double *Gall) {
+    for (int b = 0; b < t.nstarts; b++)
+      gram(W + (size_t)t.col[b] * ld, rows, ld, t.rank(b),
+           Gall + (size_t)N * t.sq[b] + (size_t)mode * t.rank(b) * t.rank(b));
   }
   // The same with M handed over in ROW BLOCKS (the receive buffer of an all-gather of the ranks' row
   // blocks: block p = rows [p*blk, (p+1)*blk) stored at Mblk + p*blk*R with leading dimension blk,

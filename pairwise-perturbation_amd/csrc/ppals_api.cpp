@@ -646,6 +646,39 @@ int ppals_cp_multi_create(ppals_ctx *ctx, ppals_tensor *V, int R, int nstarts, p
   return PPALS_OK;
   API_END(PPALS_ERR_HIP)
 }
+int ppals_cp_multi_create_ranks(ppals_ctx *ctx, ppals_tensor *V, int nstarts, const int *ranks,
+                                ppals_cp_multi **out) {
+  if (!ctx || !V || !out) return fail(PPALS_ERR_ARG, "NULL argument");
+  *out = nullptr;
+  if (!ranks) return fail(PPALS_ERR_ARG, "ppals_cp_multi_create_ranks: ranks is NULL");
+  if (V->ctx != ctx || !V->d.data) return fail(PPALS_ERR_ARG, "the tensor belongs to another context");
+  if (nstarts < 1 || nstarts > PPALS_MULTI_MAX_STARTS)
+    return fail(PPALS_ERR_ARG, "nstarts must be in [1, 32]");
+  int64_t total = 0;
+  for (int b = 0; b < nstarts; b++) {
+    if (ranks[b] <= 0) return fail(PPALS_ERR_ARG, "ppals_cp_multi_create_ranks: every rank must be positive");
+    total += ranks[b];
+  }
+  if (total > PPALS_MULTI_MAX_COLUMNS)
+    return fail(PPALS_ERR_ARG, "ppals_cp_multi_create_ranks: the ranks must not add up to more than 128");
+  if (ctx->c().size() > 1)
+    return fail(PPALS_ERR_UNSUPPORTED, "a multi-start session runs on one rank (sharded multi-start is not implemented)");
+  API_BEGIN
+  std::unique_ptr<ppals_cp_multi> s(new ppals_cp_multi);
+  s->ctx = ctx;
+  s->eng = new CpEngine(*ctx->ops, ctx->c(), V->d, 0, nstarts, true, ranks);
+  ctx->multis.insert(s.get());
+  *out = s.release();
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_cp_multi_ranks(const ppals_cp_multi *s, int *nstarts, int *ranks) {
+  if (!s || !s->eng || !nstarts) return fail(PPALS_ERR_ARG, "NULL argument");
+  *nstarts = s->eng->nstarts();
+  if (ranks)
+    for (int b = 0; b < s->eng->nstarts(); b++) ranks[b] = s->eng->start_rank(b);
+  return PPALS_OK;
+}
 void ppals_cp_multi_destroy(ppals_cp_multi *s) {
   if (!s) return;
   delete s->eng;
@@ -663,9 +696,10 @@ int ppals_cp_multi_set_factors(ppals_cp_multi *s, int start, const double *Wflat
   if (!Wflat) return fail(PPALS_ERR_ARG, "NULL argument");
   API_BEGIN
   if (s->eng->nonneg()) {  // Wflat is on the host: looked at here, before anything is uploaded
-    size_t n = 0;
-    for (int i = 0; i < s->eng->order(); i++) n += (size_t)s->eng->tensor().glens[i] * s->eng->start_rank();
-    if (start < 0) n *= (size_t)s->eng->nstarts();
+    size_t n = 0, rows = 0;  // (the blocks of the starts, each of its own length)
+    for (int i = 0; i < s->eng->order(); i++) rows += (size_t)s->eng->tensor().glens[i];
+    for (int b = start < 0 ? 0 : start; b < (start < 0 ? s->eng->nstarts() : start + 1); b++)
+      n += rows * (size_t)s->eng->start_rank(b);
     for (size_t e = 0; e < n; e++)
       if (!(Wflat[e] >= 0) || !std::isfinite(Wflat[e]))
         return fail(PPALS_ERR_ARG, "ppals_cp_multi_set_factors: a non-negative session takes finite factors >= 0");
@@ -740,8 +774,12 @@ int ppals_cp_multi_take(ppals_cp_multi *s, int start, ppals_cp *dst) {
   if (dst->ctx != s->ctx) return fail(PPALS_ERR_ARG, "the destination session belongs to another context");
   if (dst->eng->tensor().data != s->eng->tensor().data)
     return fail(PPALS_ERR_ARG, "the destination session is on another tensor");
-  if (dst->eng->rank_r() != s->eng->start_rank())
-    return fail(PPALS_ERR_ARG, "the destination session has another rank R");
+  if (dst->eng->rank_r() != s->eng->start_rank(start)) {
+    char msg[128];
+    std::snprintf(msg, sizeof(msg), "ppals_cp_multi_take: the destination session has rank %d, the start rank %d",
+                  dst->eng->rank_r(), s->eng->start_rank(start));
+    return fail(PPALS_ERR_ARG, msg);
+  }
   API_BEGIN
   dst->eng->take_from(*s->eng, start);
   return PPALS_OK;

@@ -64,6 +64,7 @@ EXPORTS = [
     "ppals_cp_multi_take", "ppals_cp_impute_device", "ppals_cp_em",
     "ppals_cp_set_nonneg", "ppals_cp_get_nonneg",
     "ppals_cp_multi_set_nonneg", "ppals_cp_multi_get_nonneg",
+    "ppals_cp_multi_create_ranks", "ppals_cp_multi_ranks",
 ]
 MODEL, RESIDUAL = 0, 1  # PPALS_MODEL / PPALS_RESIDUAL
 
@@ -583,17 +584,41 @@ class CP(_ModelExport):
 class CPMulti:
     """K independent rank-R CP-ALS starts of one tensor that share every tensor scan (ppals_cp_multi):
     start b evolves as an ordinary CP session does under cpd_als(0, ...) from the same factors. No
-    Normalize, PP or drivers here: take() the winner into a CP session and go on there."""
+    Normalize, PP or drivers here: take() the winner into a CP session and go on there.
+    CPMulti.with_ranks(ctx, V, ranks) is a rank sweep: start b is a rank-ranks[b] model
+    (ppals_cp_multi_create_ranks). `ranks` lists every start's rank, [R] * nstarts here."""
 
     def __init__(self, ctx, V, R, nstarts):
         self.ctx, self.V, self.R, self.nstarts = ctx, V, int(R), int(nstarts)
         self.lens = V.lens
         self._h = C.c_void_p()
         _check(lib().ppals_cp_multi_create(ctx._h, V._h, int(R), int(nstarts), C.byref(self._h)))
+        self.ranks = self._read_ranks()
         ctx._children.add(self)
 
-    def _n(self):
-        return sum(s * self.R for s in self.lens)
+    @classmethod
+    def with_ranks(cls, ctx, V, ranks):
+        """a session whose starts have their own ranks; R is the common rank, None when they differ"""
+        self = cls.__new__(cls)
+        ranks = [int(r) for r in ranks]
+        self.ctx, self.V, self.nstarts, self.lens = ctx, V, len(ranks), V.lens
+        self.R = ranks[0] if ranks and len(set(ranks)) == 1 else None
+        self._h = C.c_void_p()
+        arr = (C.c_int * max(len(ranks), 1))(*ranks)
+        _check(lib().ppals_cp_multi_create_ranks(ctx._h, V._h, len(ranks), arr, C.byref(self._h)))
+        self.ranks = self._read_ranks()
+        ctx._children.add(self)
+        return self
+
+    def _read_ranks(self):
+        k = C.c_int(0)
+        _check(lib().ppals_cp_multi_ranks(self._h, C.byref(k), None))
+        arr = (C.c_int * k.value)()
+        _check(lib().ppals_cp_multi_ranks(self._h, C.byref(k), arr))
+        return list(arr)
+
+    def _n(self, b):
+        return sum(s * self.ranks[b] for s in self.lens)
 
     def set_factors(self, start, Ws, gradWs=None):
         """one start's factors (list of (s_i, R) arrays); start = -1: Ws (and gradWs) are lists of
@@ -608,15 +633,17 @@ class CPMulti:
                                                 _dp(gf) if gf is not None else None))
 
     def get_factors(self, start, with_grad=False):
-        k = self.nstarts if start == -1 else 1
-        n = self._n()
-        wf = np.empty(n * k)
-        gf = np.empty(n * k) if with_grad else None
+        starts = list(range(self.nstarts)) if start == -1 else [int(start)]
+        starts = [b for b in starts if 0 <= b < self.nstarts]  # (a bad start: the library refuses)
+        at = np.concatenate([[0], np.cumsum([self._n(b) for b in starts])]).astype(int)
+        wf = np.empty(at[-1])
+        gf = np.empty(at[-1]) if with_grad else None
         _check(lib().ppals_cp_multi_get_factors(self._h, int(start), _dp(wf),
                                                 _dp(gf) if with_grad else None))
-        ranks = [self.R] * len(self.lens)
-        W = [unflat(wf[b * n:(b + 1) * n], self.lens, ranks) for b in range(k)]
-        G = [unflat(gf[b * n:(b + 1) * n], self.lens, ranks) for b in range(k)] if with_grad else None
+        cut = lambda f: [unflat(f[at[k]:at[k + 1]], self.lens, [self.ranks[b]] * len(self.lens))
+                         for k, b in enumerate(starts)]
+        W = cut(wf)
+        G = cut(gf) if with_grad else None
         if start != -1:
             W, G = W[0], (G[0] if with_grad else None)
         return (W, G) if with_grad else W
@@ -655,7 +682,7 @@ class CPMulti:
         return rc, sw.value, best.value
 
     def take(self, start, dst):
-        """start's factors and gradients into the CP session dst (same tensor, same R), on the device"""
+        """start's factors and gradients into the CP session dst (same tensor, the start's rank), on the device"""
         _check(lib().ppals_cp_multi_take(self._h, int(start), dst._h))
         return dst
 
