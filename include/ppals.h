@@ -330,6 +330,38 @@ int ppals_cp_multi_take(ppals_cp_multi *s, int start, ppals_cp *dst);
 int ppals_cp_multi_set_nonneg(ppals_cp_multi *s, int on);
 int ppals_cp_multi_get_nonneg(const ppals_cp_multi *s);
 
+/* ---- core consistency diagnostic (CORCONDIA: R. Bro, H. A. L. Kiers, "A new efficient method for
+ * determining the number of components in PARAFAC models", J. Chemometrics 17 (2003) 274-286; no
+ * counterpart in the reference) ----
+ * The residual falls with the rank and cannot choose one; the core consistency drops sharply at the first
+ * rank that over-factors. For a model with the session's current factors W_i (s_i x R, no separate
+ * weights) let P_i = W_i (W_i^T W_i)^-1, the transposed pseudo-inverse (no lambda). The core G has R^N
+ * entries, first index fastest like every tensor here:
+ *   G[r_0,...,r_{N-1}] = sum_{i_0..i_{N-1}} V[i_0,...,i_{N-1}] * prod_k P_k[i_k, r_k]
+ *   cc = 100 * (1 - sum (G - T)^2 / R),      T[r,...,r] = 1 and zero elsewhere
+ * with V as stored (the bf16 / fp32 / fp64 values the session works on). cc is not clamped: it may be
+ * negative. V = [[W]] exactly with factors of full column rank gives G = T and cc = 100.
+ * The call reads the session and changes nothing of it — factors, Grams, gradients, cached contractions
+ * and the tensor's generation stay, and later sweeps give bit for bit the factors they give without it;
+ * its work buffers are its own, grow-only, kept by the session for its next call. Every storage type,
+ * both schedules, non-negative sessions, equal-rank and rank-sweep multi-start sessions. The tensor is
+ * read ONCE, by one scan on the columns of all starts together; the rest works on that scan's result.
+ * A start one of whose Grams W_i^T W_i meets a pivot that is not a positive finite number in the
+ * elimination (a zero column; R > s_i, unless rounding leaves the last pivots tiny and positive: the
+ * figure is then meaningless and huge) gets cc = NaN, and NaN in every entry of its core; the call still
+ * returns PPALS_OK and the other starts are unaffected.
+ * PPALS_ERR_UNSUPPORTED, before anything is launched, the message starting with the function's name: a
+ * context of more than one rank; a start whose R^N exceeds 2^24 entries (128 MB of fp64 core); a start of
+ * rank above 64 (the Grams are inverted in LDS; ranks 65 .. 128 are refused, not routed elsewhere).
+ * PPALS_ERR_ARG: a NULL session, a NULL cc, start out of range. */
+/* *cc = core consistency of the session's current model. core may be NULL. n may be NULL.
+ * *n receives R^N; with core == NULL this is a size query. */
+int ppals_cp_core_consistency(ppals_cp *s, double *cc, double *core, int64_t *n);
+/* cc[nstarts]: one value per start, each with its own rank */
+int ppals_cp_multi_core_consistency(ppals_cp_multi *s, double *cc);
+/* start's core, ranks[start]^N doubles; core == NULL: size query through *n (nothing is launched) */
+int ppals_cp_multi_core(ppals_cp_multi *s, int start, double *core, int64_t *n);
+
 /* ---- Tucker sessions (als_Tucker.h) ---- */
 int ppals_tucker_create(ppals_ctx *ctx, ppals_tensor *V, const int *ranks, ppals_tucker **out);
 void ppals_tucker_destroy(ppals_tucker *s);

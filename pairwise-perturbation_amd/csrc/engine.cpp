@@ -376,6 +376,13 @@ CpEngine::~CpEngine() {
   ops_.free(Qbuf_);
   ops_.free(xq_);
   ops_.free(xp_);
+  for (auto q : cc_P_) ops_.free(q);
+  ops_.free(cc_flag_);
+  ops_.free(cc_out_);
+  ops_.free(cc_Y_.ptr);
+  ops_.free(cc_chain_[0].ptr);
+  ops_.free(cc_chain_[1].ptr);
+  ops_.free(cc_core_.ptr);
   ops_.free(Pbuf_);
   for (auto &l : lay_)
     if (l.owned) ops_.free(l.ptr);
@@ -2184,6 +2191,155 @@ int CpEngine::run_em(const ViewArgs &a, const void *mask, void *stream, const Cp
   if (iters) *iters = k;
   if (observed_res) *observed_res = std::sqrt(sq);
   return on_tol ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------- core consistency
+int64_t CpEngine::core_entries(int start) const {
+  const int64_t R = start_rank(start);
+  int64_t n = 1;
+  for (int i = 0; i < N_ && n <= kCoreMaxEntries; i++) n *= R;
+  return n;
+}
+
+void *CpEngine::cc_reserve(GrowBuf &b, size_t bytes) {
+  if (b.cap < bytes) {
+    ops_.free(b.ptr);  // (waits for what still reads it)
+    b.ptr = nullptr;
+    b.cap = 0;
+    b.ptr = ops_.alloc(bytes);
+    b.cap = bytes;
+  }
+  return b.ptr;
+}
+
+// The diagnostic of engine.h. Launches: one for the pseudo-inverse factors of all modes and starts, ONE tensor
+// scan Y = V x_m P_m on the columns of all selected starts (m: the longest mode a resident layout scans
+// row-contiguously, so Y is as small as it gets), then per start N - 1 mode products on its column block of
+// Y — the kept mode stored slowest first, so every product but the last reads contiguous rows; the last one
+// writes the start's core — and one score launch. Y has the tensor's work type, everything behind it is fp64.
+// The chain's products are booked with the other kernels in the launch profile: the tensor is read once.
+void CpEngine::core_consistency(int only, double *cc_host, double *core_host) {
+  if (P_ > 1) throw Unsupported("ppals: the core consistency runs on one rank");
+  if (N_ < 2) throw Unsupported("ppals: the core consistency needs a tensor of order >= 2");
+  StartTable tab = tab_;
+  if (!multi_) {  // an ordinary session is one start: its Grams lie where the table says
+    tab = StartTable();
+    tab.nstarts = 1;
+    tab.col[1] = R_;
+    tab.sq[1] = R_ * R_;
+  }
+  const int K = tab.nstarts;
+  if (only >= K) throw std::runtime_error("ppals: start out of range");
+  const int b0 = only < 0 ? 0 : only, b1 = only < 0 ? K : only + 1;
+  if (core_host && b1 - b0 != 1) throw std::runtime_error("ppals: a core is read one start at a time");
+  if (tab.max_rank() > Ops::kPinvMaxRank) throw Unsupported("ppals: the core consistency supports ranks <= 64");
+  for (int b = b0; b < b1; b++)
+    if (core_entries(b) > kCoreMaxEntries) throw Unsupported("ppals: the core has more than 2^24 entries");
+  check_tensor_generation();
+  int64_t rows[MAX_ORDER];
+  for (int i = 0; i < N_; i++) rows[i] = V_.glens[i];
+  if (cc_P_.empty()) {
+    cc_P_.assign(N_, nullptr);
+    for (int i = 0; i < N_; i++) cc_P_[i] = (double *)ops_.alloc(sizeof(double) * (size_t)rows[i] * R_);
+    cc_flag_ = (int *)ops_.alloc(sizeof(int) * K);
+    cc_out_ = (double *)ops_.alloc(sizeof(double) * K);
+  }
+  // the contracted mode, before anything is sized (LT = the kept modes' extents)
+  int m = -1;
+  bool m_rows = false;
+  for (int c = 0; c < N_; c++) {
+    ScanPlan pc;
+    if (!plan_scan(c, 1, false, pc)) continue;
+    const bool rc = pc.Lc > 1;
+    if (m < 0 || (rc && !m_rows) || (rc == m_rows && ext(c) >= ext(m))) {
+      m = c;
+      m_rows = rc;
+    }
+  }
+  if (m < 0) throw std::runtime_error("ppals: internal error (no scan for the core consistency)");
+  const int wdt = work_dt(V_.dtype);
+  const int64_t LT = V_.nloc / ext(m);
+  const int cA = tab.col[b0], ncols = tab.col[b1] - cA;
+  size_t chain_max = 0, core_total = 0;
+  ScanPlan pl;
+  plan_scan(m, 1, false, pl);
+  const int nk = (int)pl.kept.size();
+  for (int b = b0; b < b1; b++) {
+    const size_t Rb = (size_t)tab.rank(b);
+    size_t elems = (size_t)LT * Rb;
+    for (int p = nk - 1; p >= 1; p--) {  // (the product of p == 0 writes the core)
+      elems = elems / (size_t)ext(pl.kept[p]) * Rb;
+      chain_max = std::max(chain_max, elems);
+    }
+    core_total += (size_t)core_entries(b);
+  }
+  cc_reserve(cc_Y_, (size_t)LT * ncols * dtype_size(wdt));
+  if (chain_max) cc_reserve(cc_chain_[0], sizeof(double) * chain_max);
+  if (chain_max && nk > 2) cc_reserve(cc_chain_[1], sizeof(double) * chain_max);
+  cc_reserve(cc_core_, sizeof(double) * core_total);
+
+  ops_.zero(cc_flag_, sizeof(int) * K);
+  ops_.cp_pinv_ragged(G_, N_, tab, W_.data(), rows, cc_P_.data(), cc_flag_);
+  {
+    FactorRef f = fref(m, cc_P_.data());
+    f.ptr += (size_t)cA * f.ld;
+    ops_.scan_contract(pl.lay->ptr, V_.dtype, pl.L, pl.J, pl.T, &f, 1, ncols, cc_Y_.ptr, wdt, pl.Lc,
+                       pl.Lc * pl.T, pl.pad);
+  }
+  ops_.scan_profile_slot(1);
+  try {
+    size_t core_off = 0;
+    for (int b = b0; b < b1; b++) {
+      const int Rb = tab.rank(b);
+      double *core = (double *)cc_core_.ptr + core_off;
+      const void *X = (const char *)cc_Y_.ptr + (size_t)(tab.col[b] - cA) * LT * dtype_size(wdt);
+      int xdt = wdt;
+      int64_t tail = Rb;  // what lies behind the mode being contracted: r_m, then the modes already done
+      for (int p = nk - 1; p >= 0; p--) {
+        int64_t L = 1;
+        for (int q = 0; q < p; q++) L *= ext(pl.kept[q]);
+        const int km = pl.kept[p];
+        FactorRef f = fref(km, cc_P_.data());
+        double *out = p == 0 ? core : (double *)cc_chain_[(nk - 1 - p) & 1].ptr;
+        ops_.ttm_keep(X, xdt, L, ext(km), tail, f.ptr + (size_t)tab.col[b] * f.ld, f.ld, Rb, out);
+        tail *= Rb;
+        X = out;
+        xdt = F64;
+      }
+      ops_.core_score(core, Rb, N_, cc_flag_ + b, cc_out_ + b);
+      core_off += (size_t)core_entries(b);
+    }
+  } catch (...) {
+    ops_.scan_profile_slot(0);
+    throw;
+  }
+  ops_.scan_profile_slot(0);
+  ops_.d2h(cc_host, cc_out_ + b0, sizeof(double) * (b1 - b0));  // the flag travels as the NaN of the score
+  if (!core_host) return;
+  // the device holds the core with its indices in the order (kept modes as stored, then m)
+  const int64_t n = core_entries(b0), Rb = tab.rank(b0);
+  bool natural = m == N_ - 1;
+  for (int q = 0; q < nk; q++) natural = natural && pl.kept[q] == q;
+  if (natural) {
+    ops_.d2h(core_host, cc_core_.ptr, sizeof(double) * n);
+    return;
+  }
+  std::vector<double> tmp((size_t)n);
+  ops_.d2h(tmp.data(), cc_core_.ptr, sizeof(double) * n);
+  int64_t stride[MAX_ORDER];  // of the device's q-th index in the caller's layout
+  for (int q = 0; q <= nk; q++) {
+    const int mode = q < nk ? pl.kept[q] : m;
+    stride[q] = 1;
+    for (int i = 0; i < mode; i++) stride[q] *= Rb;
+  }
+  for (int64_t e = 0; e < n; e++) {
+    int64_t rem = e, dst = 0;
+    for (int q = 0; q <= nk; q++) {
+      dst += (rem % Rb) * stride[q];
+      rem /= Rb;
+    }
+    core_host[dst] = tmp[(size_t)e];
+  }
 }
 
 // ---------------------------------------------------------------------------- kernel-level access

@@ -148,6 +148,17 @@ class CpEngine {
   int run_em(const ViewArgs &a, const void *mask, void *stream, const CpOpts &o, int inner_sweeps,
              int *iters, double *observed_res);
   const TensorDesc &tensor() const { return V_; }
+  // The core consistency diagnostic (Bro & Kiers 2003; include/ppals.h): per start b, with
+  // P_i = W_i (W_i^T W_i)^-1 of its current factors, the core G_b = V x_0 P_0^T ... x_{N-1} P_{N-1}^T
+  // (R_b^N entries) and cc_b = 100 (1 - sum (G_b - T)^2 / R_b). `only` = -1: every start (an ordinary
+  // session is one start), cc_host[nstarts]; `only` = b: that start alone, cc_host[1]. core_host (may be
+  // nullptr; one start only): that start's core, first index fastest. The first contraction of all selected
+  // starts is ONE tensor scan; the rest works start by start on its column block of the result. Reads the
+  // session and changes nothing of it: the buffers are the call's own (grow-only, kept). Synchronises.
+  void core_consistency(int only, double *cc_host, double *core_host);
+  // R_b^N of a start, or a number above kCoreMaxEntries when it exceeds that
+  static constexpr int64_t kCoreMaxEntries = (int64_t)1 << 24;
+  int64_t core_entries(int start) const;
 
   // kernel-level access for parity tests
   int64_t tree_node(const std::string &key, double *out_host);
@@ -386,6 +397,17 @@ class CpEngine {
   double *xq_ = nullptr, *xp_ = nullptr;      // model export KRP operands (grow-only, kept)
   int64_t xq_cap_ = 0, xp_cap_ = 0;
   int residual_form_ = RESIDUAL_FUSED;        // PPALS_MODEL_RESIDUAL
+  // core_consistency: the pseudo-inverse factors (laid out like W_), the per-start flag and score, the
+  // first contraction Y, the two chain buffers and the cores (all grow-only, kept for the next call)
+  std::vector<double *> cc_P_;
+  int *cc_flag_ = nullptr;
+  double *cc_out_ = nullptr;
+  struct GrowBuf {
+    void *ptr = nullptr;
+    size_t cap = 0;
+  };
+  GrowBuf cc_Y_, cc_chain_[2], cc_core_;
+  void *cc_reserve(GrowBuf &b, size_t bytes);
   // Resident storage orders of the local tensor that the scans may read. [0] is the tensor itself.
   // [1] (if built) lists the right-half modes first, so that contractions of left-half modes are
   // row-contiguous suffix scans too. When the tensor's column strides are not multiples of 128 B

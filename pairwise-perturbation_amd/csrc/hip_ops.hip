@@ -19,6 +19,7 @@
 #include "kernels_scan.hip.h"
 #include "kernels_small.hip.h"
 #include "kernels_nn.hip.h"
+#include "kernels_corcondia.hip.h"
 #include "kernels_eig.hip.h"
 #include "kernels_io.hip.h"
 #include "kernels_model.hip.h"
@@ -762,6 +763,7 @@ class HipOps : public Ops {
     return p;
   }
   void scan_store_mode(int mode) override { scan_nt_mode_ = mode; }
+  void scan_profile_slot(int slot) override { scan_slot_ = slot == 1 ? 1 : 0; }
   int scan_nt_mode_ = -1;
   size_t mem_available() override {
     size_t fr = 0, tot = 0;
@@ -907,7 +909,7 @@ class HipOps : public Ops {
           route("scan.%s.prefix.generic al=%d nt=%d nsplit=%d out32=%d", tname<TV>(), al ? 1 : 0, NT, nsplit, out32);
         dim3 grid((unsigned)ncolgrp, (unsigned)nsplit);
         dim3 grid_il((unsigned)((K + 15) / 16), (unsigned)nsplit);  // interleaved-waves variant
-        prof_begin(0, bytes);
+        prof_begin(scan_slot_, bytes);
         dispatch<1, 2, 3, 4>(NT, [&](auto nt) {
           if (al && M >= VEC)
             hipLaunchKernelGGL((k_scan_prefix_fast<TV, nt, 12>), grid_il, dim3(256), 0, st_, V, M, K, P, per,
@@ -944,7 +946,7 @@ class HipOps : public Ops {
         const int64_t nblocks = (int64_t)n_mtiles * nsplit * T;
         if (nblocks > 0x7fffffff) throw std::runtime_error("ppals: scan grid too large");
         dim3 grid((unsigned)nblocks);
-        prof_begin(0, bytes);
+        prof_begin(scan_slot_, bytes);
         // persistent launch: ncu*40 workgroups (measured best of 3..40 per CU), each walks over its tiles
         // (fewer tiles than that: every workgroup would take exactly ONE tile and the launch loses what the
         // persistent form is for — the P = 8 shard of cfg2, 3906 tiles: 6 workgroups per CU walking 2.5
@@ -1075,7 +1077,7 @@ class HipOps : public Ops {
     if (nblocks > 0x7fffffff) throw std::runtime_error("ppals: scan grid too large");
     const double bytes = (double)L * (double)J * (double)T * 4.0 + (double)L * (double)T * ncols * (out32 ? 4.0 : 8.0);
     route("scan.f32.wide nt=%d nsplit=%d pad=%d out32=%d", NT, nsplit, pad.ld ? 1 : 0, out32);
-    prof_begin(0, bytes);
+    prof_begin(scan_slot_, bytes);
     dispatch<5, 6, 7, 8>(NT, [&](auto nt) {
       hipLaunchKernelGGL((k_scan_wide<nt, 1>), dim3((unsigned)nblocks), dim3(512), 0, st_, V, M, K, M * K, P,
                          n_mtiles, nsplit, per, nblk, d.p, d.nstride, d.split_stride, d.batch_stride, ncols, d.out32,
@@ -1128,7 +1130,7 @@ class HipOps : public Ops {
     for (int col0 = 0; col0 < R; col0 += 16 * BF16_MAX_NT) {
       const int ncols = std::min(16 * BF16_MAX_NT, R - col0);
       double *o = out32 ? (double *)((float *)out + (int64_t)col0 * out_rstride) : out + (int64_t)col0 * out_rstride;
-      prof_begin(0, bytes_v + (double)L * T * ncols * (out32 ? 4.0 : 8.0));
+      prof_begin(scan_slot_, bytes_v + (double)L * T * ncols * (out32 ? 4.0 : 8.0));
       if (mfma_ok) {
         const int NT = (ncols + 15) / 16;
         const int nblk = (int)nblk64;
@@ -1692,6 +1694,44 @@ class HipOps : public Ops {
     else
       hipLaunchKernelGGL((k_cp_mode_update_ragged<false, false>), dim3((unsigned)t.nstarts), dim3(1024), lds,
                          st_, Gall, N, mode, t, lambda, M, ldm, W, ldw, grad, ldg, rows, gradsq, S, Sinv);
+    prof_end();
+    HIP_CHECK(hipGetLastError());
+  }
+  // One launch for all modes and starts: a grid of (starts x modes x row tiles), each workgroup inverting
+  // its start's Gram of its mode in LDS (k_cp_pinv_ragged). The LDS of the launch is sized for the largest rank.
+  void cp_pinv_ragged(const double *Gall, int N, const StartTable &t, double *const *W, const int64_t *rows,
+                      double *const *P, int *bad) override {
+    RoctxRange roctx_("core consistency: pseudo-inverse factors");
+    check_table(t);
+    const int R = t.max_rank();
+    if (R > kPinvMaxRank) throw Unsupported("ppals: the pseudo-inverse factors support ranks <= 64");
+    if (N < 1 || N > MAX_ORDER) throw std::runtime_error("ppals: cp_pinv_ragged order out of range");
+    PinvArgs a;
+    int64_t maxrows = 1;
+    for (int i = 0; i < MAX_ORDER; i++) {
+      a.w[i] = i < N ? W[i] : nullptr;
+      a.p[i] = i < N ? P[i] : nullptr;
+      a.rows[i] = i < N ? rows[i] : 0;
+      if (i < N) maxrows = std::max(maxrows, rows[i]);
+    }
+    const size_t lds = sizeof(double) * ((size_t)R * R + 2 * (size_t)R);
+    const unsigned ntiles = (unsigned)std::min<int64_t>((maxrows + 255) / 256, 1024);
+    route("pinv_ragged starts=%d rmax=%d tiles=%u", t.nstarts, R, ntiles);
+    prof_begin(1, 0.0);
+    hipLaunchKernelGGL(k_cp_pinv_ragged, dim3((unsigned)t.nstarts, (unsigned)N, ntiles), dim3(256), lds, st_, Gall,
+                       N, t, a, bad);
+    prof_end();
+    HIP_CHECK(hipGetLastError());
+  }
+  void core_score(double *core, int R, int N, const int *bad, double *cc) override {
+    RoctxRange roctx_("core consistency: score");
+    int64_t n = 1, dstride = 0;
+    for (int i = 0; i < N; i++) {
+      dstride += n;
+      n *= R;
+    }
+    prof_begin(1, 8.0 * (double)n);
+    hipLaunchKernelGGL(k_core_score, dim3(1), dim3(1024), 0, st_, core, n, R, dstride, bad, cc);
     prof_end();
     HIP_CHECK(hipGetLastError());
   }
@@ -3709,6 +3749,7 @@ class HipOps : public Ops {
   size_t ws_pack_sz_ = 0, ws_slab_sz_ = 0, ws_krp_sz_ = 0, ws_part_sz_ = 0, ws_small_sz_ = 0,
          ws_big_sz_ = 0, ws_big2_sz_ = 0;
   int profiling_ = 0;
+  int scan_slot_ = 0;  // profile slot of the scans (scan_profile_slot)
   std::vector<Ev> events_;
   size_t nev_ = 0;
   int cur_ = -1;

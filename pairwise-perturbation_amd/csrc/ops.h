@@ -9,6 +9,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -451,6 +452,111 @@ class Ops {
     cp_mode_update(Gall, N, mode, R, lambda, scratch, rows, W, ldw, grad, ldg, rows, gradsq, Winit, ldi,
                    dW, ldd, ratio, S, Sinv);
   }
+  // ---- core consistency (CpEngine::core_consistency) ----
+  // The transposed pseudo-inverses of all modes and starts in one call: for every mode i < N and start b
+  //   P[i][:, col_b .. col_b + R_b) = W[i][:, col_b .. col_b + R_b) * G_{i,b}^{-1}
+  // with G_{i,b} the start's R_b x R_b Gram of that mode as the session keeps it (Gall + N t.sq[b] + i R_b^2),
+  // inverted in fp64 by Gauss-Jordan sweeps without pivoting. W[i] and P[i] are rows[i] x t.col[nstarts],
+  // column-major, leading dimension rows[i]. A start one of whose N Grams meets a pivot that is not a
+  // positive finite number gets bad[b] = 1 (device, int[nstarts], zeroed by the caller) and zeros in that
+  // block of P. Every rank <= kPinvMaxRank.
+  static constexpr int kPinvMaxRank = 64;
+  // This default is the fp64 twin of the product's kernel, built from d2h / h2d and host loops (what the
+  // host stand-in runs, as with cp_mode_update_nn); the product back end overrides it.
+  virtual void cp_pinv_ragged(const double *Gall, int N, const StartTable &t, double *const *W,
+                              const int64_t *rows, double *const *P, int *bad) {
+    if (t.max_rank() > kPinvMaxRank) throw Unsupported("ppals: the pseudo-inverse factors support ranks <= 64");
+    const int K = t.nstarts, C = t.col[K];
+    std::vector<double> g((size_t)N * t.sq[K]);
+    std::vector<int> flag(K);
+    d2h(g.data(), Gall, sizeof(double) * g.size());
+    d2h(flag.data(), bad, sizeof(int) * K);
+    for (int mode = 0; mode < N; mode++) {
+      const int64_t n = rows[mode];
+      std::vector<double> w((size_t)n * C), p((size_t)n * C, 0.0);
+      d2h(w.data(), W[mode], sizeof(double) * w.size());
+      for (int b = 0; b < K; b++) {
+        const int R = t.rank(b);
+        const double *G = g.data() + (size_t)N * t.sq[b] + (size_t)mode * R * R;
+        std::vector<double> A(G, G + (size_t)R * R), prow(R), pcol(R);
+        bool ok = true;
+        for (int k = 0; k < R; k++) {
+          const double pv = A[k + (size_t)R * k];
+          if (!(pv > 0.0) || !(pv <= 1.79769313486231570e308)) {
+            ok = false;
+            break;
+          }
+          for (int q = 0; q < R; q++) {
+            prow[q] = A[k + (size_t)R * q];
+            pcol[q] = A[q + (size_t)R * k];
+          }
+          const double d = 1.0 / pv;
+          for (int j = 0; j < R; j++)
+            for (int i = 0; i < R; i++) {
+              double v;
+              if (i == k)
+                v = (j == k) ? d : prow[j] * d;
+              else if (j == k)
+                v = -pcol[i] * d;
+              else
+                v = A[i + (size_t)R * j] - pcol[i] * (prow[j] * d);
+              A[i + (size_t)R * j] = v;
+            }
+        }
+        if (!ok) {
+          flag[b] = 1;
+          continue;  // (the block of P stays zero)
+        }
+        for (int j = 0; j < R; j++)  // the two triangles differ by rounding only
+          for (int i = 0; i < j; i++) {
+            const double v = 0.5 * (A[i + (size_t)R * j] + A[j + (size_t)R * i]);
+            A[i + (size_t)R * j] = A[j + (size_t)R * i] = v;
+          }
+        const double *wb = w.data() + (size_t)t.col[b] * n;
+        double *pb = p.data() + (size_t)t.col[b] * n;
+        for (int r = 0; r < R; r++)
+          for (int64_t x = 0; x < n; x++) {
+            double acc = 0;
+            for (int q = 0; q < R; q++) acc += wb[x + n * q] * A[q + (size_t)R * r];
+            pb[x + n * r] = acc;
+          }
+      }
+      h2d(P[mode], p.data(), sizeof(double) * p.size());
+    }
+    h2d(bad, flag.data(), sizeof(int) * K);
+  }
+  // The score of one start from its core G (R^N fp64 entries, first index fastest), summed in a fixed order:
+  //   *cc = 100 (1 - sum (G - T)^2 / R),   T[r,...,r] = 1 and zero elsewhere;
+  // *bad != 0 (device): *cc = NaN and every entry of the core becomes NaN.
+  // (the default: the fp64 twin on the host, as above)
+  virtual void core_score(double *core, int R, int N, const int *bad, double *cc) {
+    int64_t n = 1, dstride = 0;
+    for (int i = 0; i < N; i++) {
+      dstride += n;
+      n *= R;
+    }
+    int flag = 0;
+    d2h(&flag, bad, sizeof(int));
+    std::vector<double> g((size_t)n);
+    double out;
+    if (flag) {
+      out = std::numeric_limits<double>::quiet_NaN();
+      g.assign((size_t)n, out);
+      h2d(core, g.data(), sizeof(double) * g.size());
+    } else {
+      d2h(g.data(), core, sizeof(double) * g.size());
+      double s = 0;
+      for (int64_t e = 0; e < n; e++) {
+        const double d = g[(size_t)e] - (e % dstride == 0 ? 1.0 : 0.0);
+        s += d * d;
+      }
+      out = 100.0 * (1.0 - s / (double)R);
+    }
+    h2d(cc, &out, sizeof(double));
+  }
+  // Where the next scan_contract calls are booked in the launch profile: 0 the tensor scans (the default),
+  // 1 the other kernels — for a scan of something that is not the tensor.
+  virtual void scan_profile_slot(int /*slot*/) {}
   // Hint: the next cp_mode_update will be for `mode` with these arguments, and the Grams of the
   // other modes are final NOW — a back end may prepare S / S^-1 on the side of the contraction that
   // is launched next (mttv / pp_correct) instead of at the head of the update launch. Optional.

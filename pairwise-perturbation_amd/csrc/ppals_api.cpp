@@ -786,6 +786,68 @@ int ppals_cp_multi_take(ppals_cp_multi *s, int start, ppals_cp *dst) {
   API_END(PPALS_ERR_HIP)
 }
 
+// ------------------------------------------------------------------ core consistency
+// the refusals the three entry points share, before anything is launched: more than one rank, a core above
+// the cap, a rank above the LDS elimination's (starts [b0, b1) of the session)
+static int check_core_consistency(ppals_ctx *ctx, const CpEngine &e, int b0, int b1, const char *fn) {
+  char msg[192];
+  if (ctx->c().size() > 1) {
+    std::snprintf(msg, sizeof(msg), "%s: the core consistency runs on one rank (no sharded form)", fn);
+    return fail(PPALS_ERR_UNSUPPORTED, msg);
+  }
+  if (e.order() < 2) {
+    std::snprintf(msg, sizeof(msg), "%s: the tensor must have order >= 2", fn);
+    return fail(PPALS_ERR_UNSUPPORTED, msg);
+  }
+  for (int b = b0; b < b1; b++) {
+    if (e.core_entries(b) > CpEngine::kCoreMaxEntries) {
+      std::snprintf(msg, sizeof(msg), "%s: the core of a rank-%d model of order %d has more than 2^24 entries",
+                    fn, e.start_rank(b), e.order());
+      return fail(PPALS_ERR_UNSUPPORTED, msg);
+    }
+    if (e.start_rank(b) > Ops::kPinvMaxRank) {
+      std::snprintf(msg, sizeof(msg), "%s: rank %d is above 64, the largest the pseudo-inverse factors take",
+                    fn, e.start_rank(b));
+      return fail(PPALS_ERR_UNSUPPORTED, msg);
+    }
+  }
+  return PPALS_OK;
+}
+int ppals_cp_core_consistency(ppals_cp *s, double *cc, double *core, int64_t *n) {
+  if (!s || !s->eng) return fail(PPALS_ERR_ARG, "ppals_cp_core_consistency: NULL session");
+  if (!cc) return fail(PPALS_ERR_ARG, "ppals_cp_core_consistency: cc is NULL");
+  if (int rc = check_core_consistency(s->ctx, *s->eng, 0, 1, "ppals_cp_core_consistency")) return rc;
+  API_BEGIN
+  if (n) *n = s->eng->core_entries(0);
+  s->eng->core_consistency(-1, cc, core);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_cp_multi_core_consistency(ppals_cp_multi *s, double *cc) {
+  if (!s || !s->eng) return fail(PPALS_ERR_ARG, "ppals_cp_multi_core_consistency: NULL session");
+  if (!cc) return fail(PPALS_ERR_ARG, "ppals_cp_multi_core_consistency: cc is NULL");
+  if (int rc = check_core_consistency(s->ctx, *s->eng, 0, s->eng->nstarts(), "ppals_cp_multi_core_consistency"))
+    return rc;
+  API_BEGIN
+  s->eng->core_consistency(-1, cc, nullptr);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_cp_multi_core(ppals_cp_multi *s, int start, double *core, int64_t *n) {
+  if (!s || !s->eng) return fail(PPALS_ERR_ARG, "ppals_cp_multi_core: NULL session");
+  if (start < 0 || start >= s->eng->nstarts())
+    return fail(PPALS_ERR_ARG, "ppals_cp_multi_core: start must be in [0, nstarts)");
+  if (!core && !n) return fail(PPALS_ERR_ARG, "ppals_cp_multi_core: core and n are both NULL");
+  if (int rc = check_core_consistency(s->ctx, *s->eng, start, start + 1, "ppals_cp_multi_core")) return rc;
+  API_BEGIN
+  if (n) *n = s->eng->core_entries(start);
+  if (!core) return PPALS_OK;  // the size query
+  double cc = 0;
+  s->eng->core_consistency(start, &cc, core);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+
 // ------------------------------------------------------------------ Tucker
 int ppals_tucker_create(ppals_ctx *ctx, ppals_tensor *V, const int *ranks, ppals_tucker **out) {
   if (!ctx || !V || !ranks || !out) return fail(PPALS_ERR_ARG, "NULL argument");

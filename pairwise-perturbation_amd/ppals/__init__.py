@@ -65,6 +65,7 @@ EXPORTS = [
     "ppals_cp_set_nonneg", "ppals_cp_get_nonneg",
     "ppals_cp_multi_set_nonneg", "ppals_cp_multi_get_nonneg",
     "ppals_cp_multi_create_ranks", "ppals_cp_multi_ranks",
+    "ppals_cp_core_consistency", "ppals_cp_multi_core_consistency", "ppals_cp_multi_core",
 ]
 MODEL, RESIDUAL = 0, 1  # PPALS_MODEL / PPALS_RESIDUAL
 
@@ -459,6 +460,18 @@ class CP(_ModelExport):
         _check(lib().ppals_cp_residual(self._h, C.byref(out)))
         return out.value
 
+    def core_consistency(self, return_core=False):
+        """the core consistency diagnostic (Bro & Kiers 2003) of the current factors, in per cent, not
+        clamped; NaN when a factor has no pseudo-inverse. return_core: (cc, core), the core of shape
+        (R,) * order. Reads the session and changes nothing of it."""
+        cc, n = C.c_double(0), C.c_int64(0)
+        if not return_core:
+            _check(lib().ppals_cp_core_consistency(self._h, C.byref(cc), None, C.byref(n)))
+            return cc.value
+        core = np.empty(int(self.R) ** len(self.lens))
+        _check(lib().ppals_cp_core_consistency(self._h, C.byref(cc), _dp(core), C.byref(n)))
+        return cc.value, core.reshape((self.R,) * len(self.lens), order="F")
+
     def tree_node(self, key, shape=None):
         n = C.c_int64(0)
         _check(lib().ppals_tree_node(self._h, key.encode(), None, C.byref(n)))
@@ -673,6 +686,21 @@ class CPMulti:
         out = np.empty(self.nstarts)
         _check(lib().ppals_cp_multi_gradnorms(self._h, _dp(out)))
         return out
+
+    def core_consistencies(self):
+        """the core consistency of every start (CP.core_consistency), all starts on ONE tensor scan; NaN
+        for a start one of whose factors has no pseudo-inverse"""
+        out = np.empty(self.nstarts)
+        _check(lib().ppals_cp_multi_core_consistency(self._h, _dp(out)))
+        return out
+
+    def core(self, start):
+        """start's core, shape (ranks[start],) * order (all NaN where core_consistencies gives NaN)"""
+        n = C.c_int64(0)
+        _check(lib().ppals_cp_multi_core(self._h, int(start), None, C.byref(n)))
+        out = np.empty(n.value)
+        _check(lib().ppals_cp_multi_core(self._h, int(start), _dp(out), C.byref(n)))
+        return out.reshape((self.ranks[int(start)],) * len(self.lens), order="F")
 
     def run(self, **kw):
         """returns (rc, sweeps, best): rc 1 if it stopped on tol / timelimit before maxiter sweeps"""
