@@ -445,6 +445,41 @@ int ppals_cp_em(ppals_cp *s, const void *mask, const int64_t *box_lo, const int6
                 const int64_t *strides, void *stream, const ppals_cp_opts *o, int inner_sweeps,
                 int *iters, double *observed_res);
 
+/* ---- Tucker with missing entries (TensorLy's tucker(mask=...)): imputation and an EM driver ----
+ * The contracts of ppals_cp_impute_device / ppals_cp_em with a Tucker session in the CP session's place:
+ * the same PPALS_U8 mask view (a box of the GLOBAL tensor, strides >= 0, 0 broadcasts, NULL = dense, a byte
+ * of 0 = MISSING), the same checks before anything is launched (PPALS_ERR_ARG, the message starts with
+ * "ppals_tucker_impute_device: " / "ppals_tucker_em: "), each rank rewriting its own leading-mode rows.
+ * A non-zero mask byte leaves the element bit for bit as it is; a zero byte replaces it with the fp64 model
+ * core x_0 W_0 ... x_{N-1} W_{N-1} (products and sums on the fp64 matrix cores) rounded once to the
+ * storage type (F32 or F64), of exactly the factors and core ppals_tucker_get_factors would return now:
+ * the call first takes the path of ppals_tucker_export_model_device (deferred eigen-checks settled, pending
+ * rotations applied), with the same effect on the session as that call. Unlike the CP call it may
+ * therefore WAIT FOR THE DEVICE even with observed_sq == NULL; the stores themselves are ordered on
+ * `stream` as the model export's are.
+ *   observed_sq != NULL: *observed_sq = sum of (V - model)^2 over the OBSERVED elements of the box, V as
+ *     stored, in fp64, in a fixed order (per-workgroup sums in order, the slabs of a large box in order,
+ *     one scalar all-reduce over the ranks): the same state gives the same bits.
+ * The call bumps the tensor's generation (once, if any of the box lies in this rank's rows): every session
+ * on the tensor rebuilds its other layouts and drops tree nodes, the multi-sweep state and PP operators at
+ * its next read. Factors and core do not change; elements outside the box and other ranks' rows are
+ * untouched. The session keeps the operand buffers it shares with the model export. A REFUSED call (any
+ * PPALS_ERR_ARG above, or PPALS_ERR_UNSUPPORTED on a back end without device views) returns before the
+ * session is touched: nothing is settled, rotated or allocated. */
+int ppals_tucker_impute_device(ppals_tucker *s, const void *mask, const int64_t *box_lo,
+                               const int64_t *box_len, const int64_t *strides, void *stream,
+                               double *observed_sq /* may be NULL */);
+/* EM for Tucker with missing entries: iteration k is an imputation followed by
+ * ppals_tucker_sweeps_dt(inner_sweeps). The looks (iterations 0, resprint, 2 resprint, ...), the stop rules
+ * (observed residual <= o->tol at a look; o->maxiter; o->timelimit, agreed across ranks), the last
+ * imputation on the way out, *iters, *observed_res and the return value are those of ppals_cp_em. Uses
+ * tol, timelimit, maxiter and resprint of the options; lambda has no meaning here and is ignored, like the
+ * rest. inner_sweeps >= 1 (else PPALS_ERR_ARG). The start is the factors and core the session holds at
+ * the call: the usual one is ppals_tucker_hosvd on the tensor with its missing entries set to zero. */
+int ppals_tucker_em(ppals_tucker *s, const void *mask, const int64_t *box_lo, const int64_t *box_len,
+                    const int64_t *strides, void *stream, const ppals_cp_opts *o, int inner_sweeps,
+                    int *iters, double *observed_res);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2157,7 +2157,7 @@ void CpEngine::impute(const ViewArgs &a, const void *mask, void *stream, double 
     for (int m = 0; m < N_; m++)
       if (!inA[m] && m != first) mp.gb.add(bx, m);
     model_operands(bx, mp);
-    ops_.model_impute(mp, xq_, xp_, R_, mask, V_.data, V_.dtype, observed_sq ? scal_ : nullptr, stream);
+    ops_.model_impute(mp, xq_, xp_, R_, false, mask, V_.data, V_.dtype, observed_sq ? scal_ : nullptr, stream);
     // the contents changed with that launch: every session on the tensor, this one too, rebuilds what
     // it derived at its next read (a rank none of whose rows lie in the box has changed nothing)
     if (V_.generation) ++*V_.generation;

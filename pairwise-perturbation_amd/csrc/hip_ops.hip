@@ -165,6 +165,15 @@ class HipOps : public Ops {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
     HIP_CHECK(hipFuncSetAttribute((const void *)k_gram_system_mfma,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024));
+    const int mw_max = (int)mw_lds_bytes(MW_KMAX);
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_model_impute_wide<float, false>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, mw_max));
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_model_impute_wide<float, true>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, mw_max));
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_model_impute_wide<double, false>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, mw_max));
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_model_impute_wide<double, true>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, mw_max));
     if (const char *v = getenv("PPALS_GJ_SCALAR")) gj_scalar_ = atoi(v);
   }
   ~HipOps() override {
@@ -692,7 +701,7 @@ class HipOps : public Ops {
 
   // the offset tables of both groups of a plan, built on the engine stream (nothing of the caller's is
   // read), and a chip's worth of workgroups, each walking its share of the b tiles
-  const int64_t *mv_tables(const ModelPlan &mp, dim3 *grid) {
+  const int64_t *mv_tables(const ModelPlan &mp, dim3 *grid, int wgs_per_cu = 8) {
     const int64_t A = mp.ga.count, B = mp.gb.count;
     const int64_t ntA = (A + MV_TILE - 1) / MV_TILE, ntB = (B + MV_TILE - 1) / MV_TILE;
     if (ntA > 0x7fffffff) throw std::runtime_error("ppals: model view too wide");
@@ -701,20 +710,40 @@ class HipOps : public Ops {
     hipLaunchKernelGGL(k_model_offsets, dim3(grid_for(B, 256)), dim3(256), 0, st_, mp.gb, tab + 2 * A,
                        tab + 2 * A + B);
     HIP_CHECK(hipGetLastError());
-    const int64_t want = std::max<int64_t>(1, ((int64_t)ncu_ * 8 + ntA - 1) / ntA);
+    const int64_t want = std::max<int64_t>(1, ((int64_t)ncu_ * wgs_per_cu + ntA - 1) / ntA);
     *grid = dim3((unsigned)ntA, (unsigned)std::min<int64_t>(std::min<int64_t>(want, ntB), 65535));
     return tab;
   }
+  // Routes of the imputation: K <= 16, or a caller that keeps the route CP sessions have always had
+  // (wide = false): the impute instantiations of k_model_view (MAXRB = 16 above K = 16: it spills).
+  // wide and 16 < K <= MW_KMAX (Tucker sessions: K is the leading core rank): k_model_impute_wide, Q
+  // in LDS. (K > MW_KMAX = 112, which set_factors admits and no sweep does: k_model_view again.)
   template <typename T>
   void impute_launch(dim3 grid, T *V, const uint8_t *mask, const double *Q, const double *P, int K,
-                     const ModelPlan &mp, const int64_t *tab, int flags, double *part) {
-    if (part)
-      mv_launch<T, uint8_t, MV_IMPUTE_SQ>(grid, V, mask, Q, P, K, mp, tab, flags, part);
-    else
-      mv_launch<T, uint8_t, MV_IMPUTE>(grid, V, mask, Q, P, K, mp, tab, flags);
+                     const ModelPlan &mp, const int64_t *tab, int flags, double *part, bool wide) {
+    if (!wide) {
+      if (part)
+        mv_launch<T, uint8_t, MV_IMPUTE_SQ>(grid, V, mask, Q, P, K, mp, tab, flags, part);
+      else
+        mv_launch<T, uint8_t, MV_IMPUTE>(grid, V, mask, Q, P, K, mp, tab, flags);
+      return;
+    }
+    if constexpr (std::is_same<T, bf16s>::value) {
+      throw std::runtime_error("ppals: the wide imputation stores F32 or F64");
+    } else {
+      const int64_t A = mp.ga.count, B = mp.gb.count;
+      const int64_t *tav = tab, *tar = tab + A, *tbv = tab + 2 * A, *tbr = tab + 2 * A + B;
+      const size_t lds = mw_lds_bytes(K);
+      if (part)
+        hipLaunchKernelGGL((k_model_impute_wide<T, true>), grid, dim3(256), lds, st_, V, mask, Q, P, K, mp,
+                           tav, tar, tbv, tbr, flags, part);
+      else
+        hipLaunchKernelGGL((k_model_impute_wide<T, false>), grid, dim3(256), lds, st_, V, mask, Q, P, K, mp,
+                           tav, tar, tbv, tbr, flags, part);
+    }
   }
-  void model_impute(const ModelPlan &plan, const double *Q, const double *P, int K, const void *mask,
-                    void *V, int dt, double *sumsq, void *caller_stream) override {
+  void model_impute(const ModelPlan &plan, const double *Q, const double *P, int K, bool wide_k,
+                    const void *mask, void *V, int dt, double *sumsq, void *caller_stream) override {
     HIP_CHECK(hipSetDevice(dev_));
     const int64_t A = plan.ga.count, B = plan.gb.count;
     if (A <= 0 || B <= 0) {
@@ -722,9 +751,11 @@ class HipOps : public Ops {
       return;
     }
     if (K < 1) throw std::runtime_error("ppals: model_impute needs K >= 1");
+    const bool wide = wide_k && K > 16 && K <= MW_KMAX;
     const ModelPlan mp = dv_model_swapped(plan);  // the kernel's "view" is the shard, its "V" the mask
     dim3 grid;
-    const int64_t *tab = mv_tables(mp, &grid);
+    // (the wide kernel: two rounds of the workgroups its LDS lets a CU hold, so that Q is staged rarely)
+    const int64_t *tab = wide ? mv_tables(mp, &grid, 2 * mw_wgs_per_cu(K)) : mv_tables(mp, &grid);
     const int64_t npart = (int64_t)grid.x * grid.y;
     if (sumsq && npart > 0x7fffffff) throw std::runtime_error("ppals: model view too wide");
     double *part = sumsq ? (double *)ensure(ws_part_, ws_part_sz_, sizeof(double) * npart) : nullptr;
@@ -739,11 +770,11 @@ class HipOps : public Ops {
     HIP_CHECK(hipStreamWaitEvent(st_, io_ev_in_, 0));
     const uint8_t *m = (const uint8_t *)mask;
     if (dt == F32)
-      impute_launch(grid, (float *)V, m, Q, P, K, mp, tab, flags, part);
+      impute_launch(grid, (float *)V, m, Q, P, K, mp, tab, flags, part, wide);
     else if (dt == BF16)
-      impute_launch(grid, (bf16s *)V, m, Q, P, K, mp, tab, flags, part);
+      impute_launch(grid, (bf16s *)V, m, Q, P, K, mp, tab, flags, part, wide);
     else
-      impute_launch(grid, (double *)V, m, Q, P, K, mp, tab, flags, part);
+      impute_launch(grid, (double *)V, m, Q, P, K, mp, tab, flags, part, wide);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventRecord(io_ev_out_, st_));  // and the caller may change the mask after the reads
     HIP_CHECK(hipStreamWaitEvent(cs, io_ev_out_, 0));

@@ -182,14 +182,17 @@ class Ops {
                              const void * /*V*/, int /*dt*/, void * /*caller_stream*/) {
     throw Unsupported("ppals: this back end has no device views");
   }
-  // The imputation (ppals_cp_impute_device): where the byte of the mask view is 0,
+  // The imputation (ppals_cp_impute_device, ppals_tucker_impute_device): where the byte of the mask view is 0,
   //   V[roff + rA(a) + rB(b)] = the sum above, in fp64, rounded once to the storage type dt,
   // and every other element of the shard V stays as it is. Here group A follows the SHARD's fast side and
   // the view of the plan (vs, voff) is the mask, one byte per element. sumsq (device scalar, may be
   // nullptr): the sum of (V - that sum)^2 over the elements whose byte is not 0, V as stored, formed in
   // fp64 and added up in a fixed order. Ordered on `caller_stream` as copy_view; the host does not block.
+  // wide_k: the caller's K is habitually above 16 (a Tucker session's leading core rank, up to 112; dt
+  // F32 or F64): such a K takes the kernel that keeps Q in LDS. false (CP sessions): the routes CP
+  // imputation has always had.
   virtual void model_impute(const ModelPlan & /*mp*/, const double * /*Q*/, const double * /*P*/,
-                            int /*K*/, const void * /*mask*/, void * /*V*/, int /*dt*/,
+                            int /*K*/, bool /*wide_k*/, const void * /*mask*/, void * /*V*/, int /*dt*/,
                             double * /*sumsq*/, void * /*caller_stream*/) {
     throw Unsupported("ppals: this back end has no device views");
   }

@@ -496,21 +496,35 @@ int ppals_tucker_export_model_device(ppals_tucker *s, int what, void *dst, int d
 }
 // the mask of an imputation: every check ppals_tensor_check_device_view makes of an import source, for a
 // view of PPALS_U8 (a type the tensor import itself goes on refusing)
-static int check_mask_view(ppals_cp *s, const char *what, const void *mask, const int64_t *box_lo,
-                           const int64_t *box_len, const int64_t *strides, ViewArgs *a) {
-  if (!s || !s->eng || !s->ctx) return fail(PPALS_ERR_ARG, "NULL session");
+static int check_mask_view(ppals_ctx *ctx, const TensorDesc &d, const char *what, const void *mask,
+                           const int64_t *box_lo, const int64_t *box_len, const int64_t *strides,
+                           ViewArgs *a) {
   if (!mask) {
     g_err = std::string(what) + "the mask pointer is NULL";
     return PPALS_ERR_ARG;
   }
-  return check_desc_view(s->ctx, s->eng->tensor(), what, DV_IMPORT, mask, DV_U8, box_lo, box_len,
-                         strides, a, true);
+  return check_desc_view(ctx, d, what, DV_IMPORT, mask, DV_U8, box_lo, box_len, strides, a, true);
 }
 int ppals_cp_impute_device(ppals_cp *s, const void *mask, const int64_t *box_lo, const int64_t *box_len,
                            const int64_t *strides, void *stream, double *observed_sq) {
+  if (!s || !s->eng || !s->ctx) return fail(PPALS_ERR_ARG, "NULL session");
   API_BEGIN
   ViewArgs a;
-  const int rc = check_mask_view(s, "ppals_cp_impute_device: ", mask, box_lo, box_len, strides, &a);
+  const int rc = check_mask_view(s->ctx, s->eng->tensor(), "ppals_cp_impute_device: ", mask, box_lo, box_len,
+                                 strides, &a);
+  if (rc != PPALS_OK) return rc;
+  s->eng->impute(a, mask, stream, observed_sq);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_tucker_impute_device(ppals_tucker *s, const void *mask, const int64_t *box_lo,
+                               const int64_t *box_len, const int64_t *strides, void *stream,
+                               double *observed_sq) {
+  if (!s || !s->eng || !s->ctx) return fail(PPALS_ERR_ARG, "NULL session");
+  API_BEGIN
+  ViewArgs a;
+  const int rc = check_mask_view(s->ctx, s->eng->tensor(), "ppals_tucker_impute_device: ", mask, box_lo,
+                                 box_len, strides, &a);
   if (rc != PPALS_OK) return rc;
   s->eng->impute(a, mask, stream, observed_sq);
   return PPALS_OK;
@@ -618,8 +632,9 @@ int ppals_cp_em(ppals_cp *s, const void *mask, const int64_t *box_lo, const int6
   if (!o) return fail(PPALS_ERR_ARG, "ppals_cp_em: NULL options");
   if (inner_sweeps < 1) return fail(PPALS_ERR_ARG, "ppals_cp_em: inner_sweeps must be at least 1");
   if (o->maxiter < 0) return fail(PPALS_ERR_ARG, "ppals_cp_em: maxiter must not be negative");
+  if (!s || !s->eng || !s->ctx) return fail(PPALS_ERR_ARG, "NULL session");
   ViewArgs a;
-  const int rc = check_mask_view(s, "ppals_cp_em: ", mask, box_lo, box_len, strides, &a);
+  const int rc = check_mask_view(s->ctx, s->eng->tensor(), "ppals_cp_em: ", mask, box_lo, box_len, strides, &a);
   if (rc != PPALS_OK) return rc;
   return s->eng->run_em(a, mask, stream, to_opts(o), inner_sweeps, iters, observed_res);
   API_END(PPALS_ERR_HIP)
@@ -917,6 +932,22 @@ int ppals_tucker_dt(ppals_tucker *s, const ppals_cp_opts *o, int *iters) {
   if (!s || !s->eng || !o) return fail(PPALS_ERR_ARG, "NULL argument");
   API_BEGIN
   return s->eng->run_dt(to_opts(o), iters);
+  API_END(PPALS_ERR_HIP)
+}
+
+int ppals_tucker_em(ppals_tucker *s, const void *mask, const int64_t *box_lo, const int64_t *box_len,
+                    const int64_t *strides, void *stream, const ppals_cp_opts *o, int inner_sweeps,
+                    int *iters, double *observed_res) {
+  API_BEGIN
+  if (!o) return fail(PPALS_ERR_ARG, "ppals_tucker_em: NULL options");
+  if (inner_sweeps < 1) return fail(PPALS_ERR_ARG, "ppals_tucker_em: inner_sweeps must be at least 1");
+  if (o->maxiter < 0) return fail(PPALS_ERR_ARG, "ppals_tucker_em: maxiter must not be negative");
+  if (!s || !s->eng || !s->ctx) return fail(PPALS_ERR_ARG, "NULL session");
+  ViewArgs a;
+  const int rc = check_mask_view(s->ctx, s->eng->tensor(), "ppals_tucker_em: ", mask, box_lo, box_len, strides,
+                                 &a);
+  if (rc != PPALS_OK) return rc;
+  return s->eng->run_em(a, mask, stream, to_opts(o), inner_sweeps, iters, observed_res);
   API_END(PPALS_ERR_HIP)
 }
 

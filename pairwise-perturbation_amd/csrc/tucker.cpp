@@ -583,6 +583,86 @@ void TuckerEngine::export_model(const ViewArgs &a, void *dst, bool residual, voi
   if (f < 0) f = 0;
   for (int m = 0; m < N_; m++)
     if (m != f && bx.len[m] > 1 && (s < 0 || bx.vs[m] > bx.vs[s])) s = m;
+  ModelExportCall call{&a, &V_, dst, residual, residual_form_, false, stream};
+  model_slabs(bx, f, s, [&](const ModelPlan &mp, const double *Q, const double *Z) {
+    model_export_run(ops_, call, mp, Q, Z, r_[f]);
+  });
+}
+
+// The imputation: the stores go to the shard, so the plan follows the SHARD: f = mode 0,
+// its fast side, is group A alone (the lane index of the store pass, and of the V reads of the observed
+// residual), group B the other modes in the shard's order, which is the order Z has them in, and the
+// slabs are cut along the shard's slowest mode. Per slab one launch of Ops::model_impute with
+// Q = W_0 + lo_0, P = Z and K = r_0, the route that keeps Q in LDS when r_0 > 16. The slabs' sums are
+// added on the host in order, then one scalar all-reduce.
+// On a back end without device views the API's pointer check refuses the call before it gets here.
+void TuckerEngine::impute(const ViewArgs &a, const void *mask, void *stream, double *observed_sq) {
+  finalize_rotations();  // (as export_model: the factors and core get_factors would return now)
+  ModelBox bx;
+  double sq = 0;
+  if (dv_model_box(a, V_.glens, V_.row0, V_.llens[0], &bx)) {
+    int s = -1;
+    for (int m = 1; m < N_; m++)
+      if (bx.len[m] > 1) s = m;
+    // (a slab's sum stays in a device slot of its own until a batch of slots is read in one copy: the host
+    // does not wait between slabs, and adds the sums in slab order)
+    constexpr int kSlots = 48;
+    double *slot = scal_ + 8;
+    int used = 0;
+    auto drain = [&] {
+      double h[kSlots];
+      if (used) ops_.d2h(h, slot, sizeof(double) * used);
+      for (int i = 0; i < used; i++) sq += h[i];
+      used = 0;
+    };
+    model_slabs(bx, 0, s, [&](const ModelPlan &mp, const double *Q, const double *Z) {
+      ops_.model_impute(mp, Q, Z, r_[0], true, mask, V_.data, V_.dtype, observed_sq ? slot + used : nullptr,
+                        stream);
+      if (observed_sq && ++used == kSlots) drain();
+    });
+    drain();
+    // the contents changed: every session on the tensor, this one too, rebuilds what it derived at its
+    // next read (a rank none of whose rows lie in the box has changed nothing)
+    if (V_.generation) ++*V_.generation;
+  }
+  if (!observed_sq) return;
+  if (dist_) {
+    ops_.h2d(scal_ + 8, &sq, sizeof(double));
+    comm_.allreduce_sum(scal_ + 8, 1);
+    ops_.d2h(&sq, scal_ + 8, sizeof(double));
+  }
+  *observed_sq = sq;
+}
+
+// ppals_tucker_em: CpEngine::run_em with HOOI sweeps in place of the CP sweeps (lambda has no meaning here)
+int TuckerEngine::run_em(const ViewArgs &a, const void *mask, void *stream, const CpOpts &o,
+                         int inner_sweeps, int *iters, double *observed_res) {
+  const double t0 = now();
+  double sq = 0;
+  int k = 0;
+  bool on_tol = false, fresh = false;  // fresh: the tensor and sq belong to the current factors
+  while (k < o.maxiter) {
+    const bool look = k % o.resprint == 0;
+    impute(a, mask, stream, look ? &sq : nullptr);
+    fresh = look;
+    if (look) {
+      on_tol = std::sqrt(sq) <= o.tol;
+      if (on_tol || agree(now() - t0 > o.timelimit)) break;
+    }
+    for (int i = 0; i < inner_sweeps; i++) sweep_dt();
+    settle_all();  // (as ppals_tucker_sweeps_dt)
+    fresh = false;
+    k++;
+  }
+  if (!fresh) impute(a, mask, stream, &sq);
+  if (iters) *iters = k;
+  if (observed_res) *observed_res = std::sqrt(sq);
+  return on_tol ? 1 : 0;
+}
+
+// The slabs of box bx for fast mode f, cut along mode s (-1: none): the transposed factors, the chain
+// buffers and, per slab, run(plan, Q = the box's rows of W_f, Z). Shared by the export and the imputation.
+void TuckerEngine::model_slabs(const ModelBox &bx, int f, int s, const SlabRun &run) {
   std::vector<int> chain;
   if (s >= 0) chain.push_back(s);
   for (int m = 0; m < N_; m++)
@@ -617,7 +697,6 @@ void TuckerEngine::export_model(const ViewArgs &a, void *dst, bool residual, voi
     xz_[1] = (double *)ops_.alloc(sizeof(double) * unit * cs);
     xz_cap_ = unit * cs;
   }
-  ModelExportCall call{&a, &V_, dst, residual, residual_form_, false, stream};
   for (int64_t c = 0; c < ns; c += cs) {
     ModelBox sb = bx;
     if (s >= 0) {
@@ -626,12 +705,11 @@ void TuckerEngine::export_model(const ViewArgs &a, void *dst, bool residual, voi
       sb.voff += c * bx.vs[s];
       sb.roff += c * bx.rs[s];
     }
-    export_slab(sb, f, chain, call);
+    export_slab(sb, f, chain, run);
   }
 }
 
-void TuckerEngine::export_slab(const ModelBox &bx, int f, const std::vector<int> &chain,
-                               ModelExportCall &call) {
+void TuckerEngine::export_slab(const ModelBox &bx, int f, const std::vector<int> &chain, const SlabRun &run) {
   std::vector<int64_t> dims(r_.begin(), r_.end()), wtoff(N_, 0);
   for (int m = 1; m < N_; m++) wtoff[m] = wtoff[m - 1] + V_.glens[m - 1] * r_[m - 1];
   const double *cur = core_;
@@ -657,7 +735,7 @@ void TuckerEngine::export_slab(const ModelBox &bx, int f, const std::vector<int>
   mp.pL = 1;
   for (int q = 0; q < f; q++) mp.pL *= bx.len[q];
   mp.pLK = mp.pL * r_[f];
-  model_export_run(ops_, call, mp, W_[f] + bx.lo[f], cur, r_[f]);
+  run(mp, W_[f] + bx.lo[f], cur);
 }
 
 // hosvd (als_Tucker.cxx:12-70): W_i = leading eigenvectors of the Gram of the mode-i unfolding of

@@ -1,5 +1,6 @@
 // tucker.h — HOOI sweep engine for Tucker decomposition (als_Tucker.cxx) over abstract ops.
 #pragma once
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -23,6 +24,15 @@ class TuckerEngine {
   // core x_i W_i (residual: V - that, V as stored) into this rank's rows of a checked export view
   // (ppals_tucker_export_model_device), from the factors and core get_factors would return
   void export_model(const ViewArgs &a, void *dst, bool residual, void *stream);
+  // The missing entries of the tensor (mask byte 0) overwritten with that model, rounded once to the
+  // storage type, the others left bit for bit (ppals_tucker_impute_device); settles the rotations as
+  // export_model does. Bumps the tensor's generation; factors and core do not change. observed_sq != nullptr:
+  // the sum of (V - model)^2 over the observed elements of the box, all ranks (the call then waits for it).
+  void impute(const ViewArgs &a, const void *mask, void *stream, double *observed_sq);
+  // EM with missing entries (ppals_tucker_em): repeat { impute; inner_sweeps HOOI sweeps }, the looks, the
+  // stop rules and the last impute on the way out as CpEngine::run_em. Returns 1 if it stopped on tol.
+  int run_em(const ViewArgs &a, const void *mask, void *stream, const CpOpts &o, int inner_sweeps, int *iters,
+             double *observed_res);
   const TensorDesc &tensor() const { return V_; }
   int run_dt(const CpOpts &o, int *iters);  // alsTucker_DT, als_Tucker.cxx:240-424
   int run_pp(const CpOpts &o, int *iters);  // alsTucker_PP, als_Tucker.cxx:906-962
@@ -137,8 +147,11 @@ class TuckerEngine {
   ModeNorms read_norms(bool dt_phase);
   void dt_sub(RunReport &rep, const CpOpts &o, double tol_init, double &diffnorm, int &iter);
   void pp_sub(RunReport &rep, const CpOpts &o, double tol_init, double &diffnorm, int &iter);
-  // model export: the transposed factors and the ping-pong buffers of Z = core x_{i != f} W_i
-  void export_slab(const ModelBox &bx, int f, const std::vector<int> &chain, ModelExportCall &call);
+  // model export and imputation: the transposed factors and the ping-pong buffers of
+  // Z = core x_{i != f} W_i; run(plan, Q, Z) is what the caller does with a slab
+  using SlabRun = std::function<void(const ModelPlan &, const double *, const double *)>;
+  void model_slabs(const ModelBox &bx, int f, int s, const SlabRun &run);
+  void export_slab(const ModelBox &bx, int f, const std::vector<int> &chain, const SlabRun &run);
   // (kept for the session's next export: freeing them would wait for the device)
   double *xwt_ = nullptr, *xz_[2] = {nullptr, nullptr};
   int residual_form_ = RESIDUAL_FUSED;  // PPALS_MODEL_RESIDUAL

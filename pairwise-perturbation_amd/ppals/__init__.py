@@ -18,7 +18,7 @@ import numpy as np
 
 F32, F64 = 0, 1
 F16, BF16 = 2, 3  # F16: a device view only; BF16: a view, or the tensor's storage (CP only)
-U8 = 4  # a mask view only (CP.impute_device): one byte per element, 0 = missing
+U8 = 4  # a mask view only (CP / Tucker.impute_device): one byte per element, 0 = missing
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIBPATH = os.environ.get("PPALS_LIB", os.path.join(os.path.dirname(_HERE), "lib", "libppals.so"))
 _lib = None
@@ -66,6 +66,7 @@ EXPORTS = [
     "ppals_cp_multi_set_nonneg", "ppals_cp_multi_get_nonneg",
     "ppals_cp_multi_create_ranks", "ppals_cp_multi_ranks",
     "ppals_cp_core_consistency", "ppals_cp_multi_core_consistency", "ppals_cp_multi_core",
+    "ppals_tucker_impute_device", "ppals_tucker_em",
 ]
 MODEL, RESIDUAL = 0, 1  # PPALS_MODEL / PPALS_RESIDUAL
 
@@ -387,9 +388,65 @@ class _ModelExport:
         return out
 
 
-class CP(_ModelExport):
+class _Impute:
+    """missing entries under a mask of one byte per element, 0 = missing; the session's class names the
+    entry points"""
+    _impute_fn = None
+    _em_fn = None
+
+    def _mask_view(self, shape, strides, lo):
+        blo, blen = Tensor._box(self, shape, lo)
+        return blo, blen, (C.c_int64 * len(self.lens))(*[int(x) for x in strides])
+
+    def impute_device(self, ptr, shape, strides, lo=None, stream=0, want_residual=False):
+        """raw ppals_*_impute_device: the tensor's elements whose mask byte (at ptr + sum_i j_i *
+        strides[i], box at lo) is 0 become the current model, the others stay bit for bit. Returns the
+        observed residual norm sqrt(sum over the observed elements of (V - model)^2) if want_residual
+        (the call then waits for it), else None (a CP session's host does not wait; a Tucker session
+        settles its eigen-steps first and may)."""
+        blo, blen, st = self._mask_view(shape, strides, lo)
+        sq = C.c_double(0)
+        _check(getattr(lib(), self._impute_fn)(self._h, C.c_void_p(int(ptr)), blo, blen, st,
+                                               C.c_void_p(int(stream or 0)),
+                                               C.byref(sq) if want_residual else None))
+        return float(np.sqrt(sq.value)) if want_residual else None
+
+    def _torch_mask(self, mask):
+        torch = _torch()
+        if mask.dtype not in (torch.bool, torch.uint8):   # the C ABI takes bytes: nothing there to refuse it
+            raise TypeError(f"the mask's torch dtype {mask.dtype} is not torch.bool or torch.uint8 "
+                            "(one byte per element)")
+        if mask.device.type != "cuda" or mask.device.index != self.ctx.device:
+            raise PpalsError(f"the mask is on {mask.device}, the context on cuda:{self.ctx.device}")
+        return mask.data_ptr(), tuple(mask.shape), mask.stride()
+
+    def impute_torch(self, mask, lo=None, stream=None, want_residual=False):
+        """impute_device with a torch.bool / torch.uint8 mask on the context's device (any strides, 0
+        included: an expanded mask marks whole fibres), False / 0 = missing; the box at lo has the
+        mask's shape. Ordered on `stream` (default: torch's current stream)."""
+        ptr, shape, strides = self._torch_mask(mask)
+        return self.impute_device(ptr, shape, strides, lo, Tensor._stream(stream), want_residual)
+
+    def run_em(self, mask, inner_sweeps=1, lo=None, stream=None, **opts):
+        """ppals_cp_em / ppals_tucker_em: repeat { impute; inner_sweeps exact sweeps } until maxiter
+        iterations, timelimit or an observed residual <= tol (looked at every resprint iterations); uses
+        tol, timelimit, maxiter, resprint and (CP) lam. Returns (stopped on tol, iterations, observed
+        residual norm); the tensor's missing entries then hold the model of the returned factors. A
+        Tucker session starts from the factors and core it holds: usually hosvd() of the zero-filled tensor."""
+        ptr, shape, strides = self._torch_mask(mask)
+        blo, blen, st = self._mask_view(shape, strides, lo)
+        o = _opts(**opts)
+        it, res = C.c_int(0), C.c_double(0)
+        rc = _check(getattr(lib(), self._em_fn)(self._h, C.c_void_p(int(ptr)), blo, blen, st,
+                                                C.c_void_p(int(Tensor._stream(stream) or 0)), C.byref(o),
+                                                int(inner_sweeps), C.byref(it), C.byref(res)))
+        return rc, it.value, res.value
+
+
+class CP(_ModelExport, _Impute):
     """a CP-ALS session: factors, Grams and dimension-tree caches resident in HBM"""
     _export_fn = "ppals_cp_export_model_device"
+    _impute_fn, _em_fn = "ppals_cp_impute_device", "ppals_cp_em"
 
     def __init__(self, ctx, V, R):
         self.ctx, self.V, self.R = ctx, V, R
@@ -535,53 +592,6 @@ class CP(_ModelExport):
         rc = _check(lib().ppals_cp_pp_partupdate(self._h, C.byref(o), C.byref(it)))
         return rc, it.value
 
-    # ---- missing entries: a mask of one byte per element, 0 = missing ----
-    def _mask_view(self, shape, strides, lo):
-        blo, blen = Tensor._box(self, shape, lo)
-        return blo, blen, (C.c_int64 * len(self.lens))(*[int(x) for x in strides])
-
-    def impute_device(self, ptr, shape, strides, lo=None, stream=0, want_residual=False):
-        """raw ppals_cp_impute_device: the tensor's elements whose mask byte (at ptr + sum_i j_i *
-        strides[i], box at lo) is 0 become the current model, the others stay bit for bit. Returns the
-        observed residual norm sqrt(sum over the observed elements of (V - model)^2) if want_residual
-        (the call then waits for it), else None (the host does not wait)."""
-        blo, blen, st = self._mask_view(shape, strides, lo)
-        sq = C.c_double(0)
-        _check(lib().ppals_cp_impute_device(self._h, C.c_void_p(int(ptr)), blo, blen, st,
-                                            C.c_void_p(int(stream or 0)),
-                                            C.byref(sq) if want_residual else None))
-        return float(np.sqrt(sq.value)) if want_residual else None
-
-    def _torch_mask(self, mask):
-        torch = _torch()
-        if mask.dtype not in (torch.bool, torch.uint8):   # the C ABI takes bytes: nothing there to refuse it
-            raise TypeError(f"the mask's torch dtype {mask.dtype} is not torch.bool or torch.uint8 "
-                            "(one byte per element)")
-        if mask.device.type != "cuda" or mask.device.index != self.ctx.device:
-            raise PpalsError(f"the mask is on {mask.device}, the context on cuda:{self.ctx.device}")
-        return mask.data_ptr(), tuple(mask.shape), mask.stride()
-
-    def impute_torch(self, mask, lo=None, stream=None, want_residual=False):
-        """impute_device with a torch.bool / torch.uint8 mask on the context's device (any strides, 0
-        included: an expanded mask marks whole fibres), False / 0 = missing; the box at lo has the
-        mask's shape. Ordered on `stream` (default: torch's current stream)."""
-        ptr, shape, strides = self._torch_mask(mask)
-        return self.impute_device(ptr, shape, strides, lo, Tensor._stream(stream), want_residual)
-
-    def run_em(self, mask, inner_sweeps=1, lo=None, stream=None, **opts):
-        """ppals_cp_em: repeat { impute; inner_sweeps exact sweeps } until maxiter iterations, timelimit
-        or an observed residual <= tol (looked at every resprint iterations); uses tol, timelimit,
-        maxiter, lam and resprint. Returns (stopped on tol, iterations, observed residual norm); the
-        tensor's missing entries then hold the model of the returned factors."""
-        ptr, shape, strides = self._torch_mask(mask)
-        blo, blen, st = self._mask_view(shape, strides, lo)
-        o = _opts(**opts)
-        it, res = C.c_int(0), C.c_double(0)
-        rc = _check(lib().ppals_cp_em(self._h, C.c_void_p(int(ptr)), blo, blen, st,
-                                      C.c_void_p(int(Tensor._stream(stream) or 0)), C.byref(o),
-                                      int(inner_sweeps), C.byref(it), C.byref(res)))
-        return rc, it.value, res.value
-
     def close(self):
         if self._h:
             lib().ppals_cp_destroy(self._h)
@@ -726,8 +736,9 @@ class CPMulti:
             pass
 
 
-class Tucker(_ModelExport):
+class Tucker(_ModelExport, _Impute):
     _export_fn = "ppals_tucker_export_model_device"
+    _impute_fn, _em_fn = "ppals_tucker_impute_device", "ppals_tucker_em"
 
     def __init__(self, ctx, V, ranks):
         self.ctx, self.V = ctx, V
