@@ -362,6 +362,58 @@ int ppals_cp_multi_core_consistency(ppals_cp_multi *s, double *cc);
 /* start's core, ranks[start]^N doubles; core == NULL: size query through *n (nothing is launched) */
 int ppals_cp_multi_core(ppals_cp_multi *s, int start, double *core, int64_t *n);
 
+/* ---- factor match score: Tucker's congruence across starts and between sessions (R. A. Harshman's
+ * split-half validation; tlviz factor_match_score, TensorLy congruence_coefficient; no counterpart in the
+ * reference) ----
+ * Did two fits find the same components? Two column sets are compared: a with columns p < Ca, b with
+ * columns q < Cb, of the same order N and with the same extents in every compared mode. The compared
+ * modes are all modes (skip_mode = -1) or all but skip_mode (0 <= skip_mode < N), in which the extents
+ * may differ: the split mode of a split-half analysis.
+ *   Phi[p,q] = prod over compared modes i of (a_i[:,p] . b_i[:,q]) / (|a_i[:,p]| |b_i[:,q]|)    (signed, fp64)
+ *   w_a[p]   = prod over ALL N modes of |a_i[:,p]|                                             (likewise w_b)
+ * A column whose norm in some compared mode is not a positive finite number gives Phi = 0 in its whole
+ * row or column: Phi is never NaN. The sign is kept: CP's sign indeterminacy flips pairs of modes and
+ * leaves the product unchanged; an odd number of flips is a different component. Phi is stored
+ * column-major, Phi[p + Ca*q]; a multi-start session's columns are those of all its starts, start b owning
+ * [off_b, off_b + ranks[b]) as everywhere else.
+ * The factor match score of a rank-ra model against a rank-rb one, m = min(ra, rb):
+ *   score[p,q] = Phi[p,q]                                                  (flags = 0)
+ *              = Phi[p,q] * (1 - |w_a[p] - w_b[q]| / max(w_a[p], w_b[q]))  (flags & PPALS_FMS_WEIGHTS;
+ *                                                                          0 where the max is not positive finite)
+ *   fms        = (1/m) * max over injective matchings of m pairs of sum score[p, pi(p)]
+ * the exact optimum of the rectangular assignment problem, not a greedy matching. With ranks that differ
+ * it says how well the smaller model's components persist in the larger one.
+ * The calls on sessions are ordered after the work queued on the engine stream and return when the result
+ * is on the host. They read the sessions and change nothing of them — factors, Grams, gradients, cached
+ * contractions and the tensor's generation stay, and later sweeps give bit for bit the factors they give
+ * without the call; the work buffers are the call's own, grow-only, kept by the first session. The tensor
+ * is never read, so the two sessions may sit on different tensors of one context. The same state gives
+ * the same bits on every call (no floating-point atomics; partial sums are added in a fixed order). Every
+ * storage type, both schedules, non-negative sessions. Two kernel launches a call, whatever N, the number of
+ * starts and the extents; one download of at most 128 x 128 doubles; the matching runs on the host.
+ * Refused before anything is launched, the message starting with the function's name — PPALS_ERR_ARG: a
+ * NULL session or output, sessions of different contexts or order, different extents in a compared mode,
+ * skip_mode outside [-1, N), unknown flag bits, fms_between with different numbers of starts;
+ * PPALS_ERR_UNSUPPORTED: a context of more than one rank, a session of more than 128 columns. */
+#define PPALS_FMS_WEIGHTS 1
+/* Host only, no context and no device: the assignment above on score[p + ld*q], p < ra, q < rb.
+ * perm (ra ints, may be NULL): the matched q, or -1 for a p left out when ra > rb; *sum (may be NULL): the
+ * optimal total. O(n^3), deterministic. PPALS_ERR_ARG: score NULL, ra or rb < 1, ld < ra, an entry that is
+ * not finite. */
+int ppals_match_columns(const double *score, int ra, int rb, int ld, int *perm, double *sum);
+/* Phi is Ra x Rb; *n receives Ra*Rb (n may be NULL when Phi is not); Phi == NULL: a size query, nothing
+ * is launched */
+int ppals_cp_congruence(ppals_cp *a, ppals_cp *b, int skip_mode, double *Phi, int64_t *n);
+/* *fms of a against b; perm (Ra ints, may be NULL): the matched column of b, -1 for an unmatched one */
+int ppals_cp_fms(ppals_cp *a, ppals_cp *b, int skip_mode, int flags, double *fms, int *perm);
+/* all columns of all starts of s against those of other (NULL: s with itself): Ca x Cb */
+int ppals_cp_multi_congruence(ppals_cp_multi *s, ppals_cp_multi *other, int skip_mode, double *Phi, int64_t *n);
+/* every pair of starts, each start with its own rank: fms[a + K*b], K = nstarts */
+int ppals_cp_multi_fms(ppals_cp_multi *s, int skip_mode, int flags, double *fms);
+/* fms[k]: start k of a against start k of b (the same number of starts; the ranks may differ) — the
+ * split-half call for two rank-sweep sessions on the halves */
+int ppals_cp_multi_fms_between(ppals_cp_multi *a, ppals_cp_multi *b, int skip_mode, int flags, double *fms);
+
 /* ---- Tucker sessions (als_Tucker.h) ---- */
 int ppals_tucker_create(ppals_ctx *ctx, ppals_tensor *V, const int *ranks, ppals_tucker **out);
 void ppals_tucker_destroy(ppals_tucker *s);

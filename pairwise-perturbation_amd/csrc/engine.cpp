@@ -19,6 +19,7 @@
 // the redundant fused update for small messages, reduce-scatter / row-block solve / all-gather
 // otherwise (mode_update).
 #include "engine.h"
+#include "assignment.h"
 #include "run_report.h"
 
 #include <algorithm>
@@ -383,6 +384,8 @@ CpEngine::~CpEngine() {
   ops_.free(cc_chain_[0].ptr);
   ops_.free(cc_chain_[1].ptr);
   ops_.free(cc_core_.ptr);
+  ops_.free(fms_out_.ptr);
+  ops_.free(fms_work_.ptr);
   ops_.free(Pbuf_);
   for (auto &l : lay_)
     if (l.owned) ops_.free(l.ptr);
@@ -2340,6 +2343,65 @@ void CpEngine::core_consistency(int only, double *cc_host, double *core_host) {
     }
     core_host[dst] = tmp[(size_t)e];
   }
+}
+
+// ---------------------------------------------------------------------------- factor match score
+StartTable CpEngine::start_table() const {
+  if (multi_) return tab_;
+  StartTable t;
+  t.nstarts = 1;
+  t.col[1] = R_;
+  t.sq[1] = R_ * R_;
+  return t;
+}
+
+void CpEngine::congruence(CpEngine &b, int skip_mode, std::vector<double> &out) {
+  if (P_ > 1 || b.P_ > 1) throw Unsupported("ppals: the factor congruence runs on one rank");
+  if (&ops_ != &b.ops_) throw std::runtime_error("ppals: the sessions belong to different contexts");
+  if (N_ != b.N_) throw std::runtime_error("ppals: the sessions differ in order");
+  if (skip_mode < -1 || skip_mode >= N_) throw std::runtime_error("ppals: skip_mode out of range");
+  if (R_ > Ops::kCongruenceMaxCols || b.R_ > Ops::kCongruenceMaxCols)
+    throw Unsupported("ppals: the factor congruence supports at most 128 columns a session");
+  Ops::CongruenceSide sa, sb;
+  unsigned mask = 0;
+  for (int i = 0; i < MAX_ORDER; i++) {
+    const bool in = i < N_;
+    sa.w[i] = in ? W_[i] : nullptr;
+    sb.w[i] = in ? b.W_[i] : nullptr;
+    sa.ld[i] = sa.rows[i] = in ? V_.glens[i] : 0;
+    sb.ld[i] = sb.rows[i] = in ? b.V_.glens[i] : 0;
+    if (in && i != skip_mode) {
+      if (sa.rows[i] != sb.rows[i]) throw std::runtime_error("ppals: the sessions differ in a compared extent");
+      mask |= 1u << i;
+    }
+  }
+  sa.cols = R_;
+  sb.cols = b.R_;
+  const size_t n = (size_t)R_ * b.R_ + (size_t)R_ + (size_t)b.R_;
+  double *dev = (double *)cc_reserve(fms_out_, sizeof(double) * n);
+  const size_t wbytes = ops_.factor_congruence_work(N_, sa, sb);
+  void *work = wbytes ? cc_reserve(fms_work_, wbytes) : nullptr;
+  ops_.factor_congruence(N_, sa, sb, mask, work, dev, dev + (size_t)R_ * b.R_, dev + (size_t)R_ * b.R_ + R_);
+  out.resize(n);
+  ops_.d2h(out.data(), dev, sizeof(double) * n);
+}
+
+void CpEngine::fms_pairs(CpEngine &b, int skip_mode, bool weights, bool pairwise, double *fms, int *perm) {
+  const StartTable ta = start_table(), tb = b.start_table();
+  if (!pairwise && ta.nstarts != tb.nstarts) throw std::runtime_error("ppals: the numbers of starts differ");
+  if (perm && (ta.nstarts != 1 || tb.nstarts != 1))
+    throw std::logic_error("ppals: a matching is handed out for one pair of models");
+  std::vector<double> h;
+  congruence(b, skip_mode, h);
+  const int Ca = R_, Cb = b.R_;
+  const double *Phi = h.data(), *wa = Phi + (size_t)Ca * Cb, *wb = wa + Ca;
+  for (int x = 0; x < ta.nstarts; x++)
+    for (int y = pairwise ? 0 : x; y < (pairwise ? tb.nstarts : x + 1); y++) {
+      double *dst = pairwise ? fms + x + (size_t)ta.nstarts * y : fms + x;
+      if (!fms_from_congruence(Phi + ta.col[x] + (size_t)Ca * tb.col[y], Ca, wa + ta.col[x], wb + tb.col[y],
+                               ta.rank(x), tb.rank(y), weights, perm, dst))
+        throw std::runtime_error("ppals: internal error (a congruence that is not finite)");
+    }
 }
 
 // ---------------------------------------------------------------------------- kernel-level access

@@ -159,6 +159,19 @@ class CpEngine {
   // R_b^N of a start, or a number above kCoreMaxEntries when it exceeds that
   static constexpr int64_t kCoreMaxEntries = (int64_t)1 << 24;
   int64_t core_entries(int start) const;
+  // The factor congruence and the factor match score (include/ppals.h): all columns of this session (side
+  // a: every start of a multi-start session, side by side as the column table says) against all columns
+  // of `b` — another session of the same context and order, or this one. skip_mode = -1 compares every
+  // mode, 0 <= skip_mode < N all but that one. ONE Ops::factor_congruence and one download of
+  // Phi (Ca x Cb), w_a (Ca), w_b (Cb) into `out`, in this order. Reads both sessions and changes nothing of
+  // them; the buffers are the call's own, grow-only, kept by this session. Synchronises.
+  void congruence(CpEngine &b, int skip_mode, std::vector<double> &out);
+  // the scores of starts from one such download, matched on the host (assignment.h), each start with its
+  // own rank. pairwise: fms[a + K * b] for every start a of this session and b of `b` (K = nstarts());
+  // otherwise fms[k] of start k against start k (equal numbers of starts). perm (may be nullptr; ordinary
+  // sessions only): rank_r() ints, the matched column of b or -1.
+  void fms_pairs(CpEngine &b, int skip_mode, bool weights, bool pairwise, double *fms, int *perm);
+  int64_t mode_extent(int i) const { return V_.glens[i]; }
 
   // kernel-level access for parity tests
   int64_t tree_node(const std::string &key, double *out_host);
@@ -407,6 +420,8 @@ class CpEngine {
     size_t cap = 0;
   };
   GrowBuf cc_Y_, cc_chain_[2], cc_core_;
+  GrowBuf fms_out_, fms_work_;  // congruence: Phi | w_a | w_b, and the back end's partial sums
+  StartTable start_table() const;  // tab_, or the one start of an ordinary session
   void *cc_reserve(GrowBuf &b, size_t bytes);
   // Resident storage orders of the local tensor that the scans may read. [0] is the tensor itself.
   // [1] (if built) lists the right-half modes first, so that contractions of left-half modes are

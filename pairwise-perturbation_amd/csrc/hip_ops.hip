@@ -20,6 +20,7 @@
 #include "kernels_small.hip.h"
 #include "kernels_nn.hip.h"
 #include "kernels_corcondia.hip.h"
+#include "kernels_fms.hip.h"
 #include "kernels_eig.hip.h"
 #include "kernels_io.hip.h"
 #include "kernels_model.hip.h"
@@ -175,6 +176,8 @@ class HipOps : public Ops {
     HIP_CHECK(hipFuncSetAttribute((const void *)k_model_impute_wide<double, true>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, mw_max));
     if (const char *v = getenv("PPALS_GJ_SCALAR")) gj_scalar_ = atoi(v);
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_fms_cross, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)fms_lds_bytes(FMS_MAXC, FMS_MAXC, false)));
   }
   ~HipOps() override {
     hipSetDevice(dev_);
@@ -1763,6 +1766,69 @@ class HipOps : public Ops {
     }
     prof_begin(1, 8.0 * (double)n);
     hipLaunchKernelGGL(k_core_score, dim3(1), dim3(1024), 0, st_, core, n, R, dstride, bad, cc);
+    prof_end();
+    HIP_CHECK(hipGetLastError());
+  }
+  // Two launches whatever N, the columns and the extents: k_fms_cross on one workgroup per (mode, slab of
+  // row chunks), k_fms_finish on the partials. The slabs are a function of the extents alone.
+  static void fms_args(int N, const CongruenceSide &a, const CongruenceSide &b, unsigned mask, FmsArgs &A) {
+    if (N < 1 || N > MAX_ORDER) throw std::runtime_error("ppals: factor_congruence order out of range");
+    if (a.cols < 1 || b.cols < 1 || a.cols > kCongruenceMaxCols || b.cols > kCongruenceMaxCols)
+      throw Unsupported("ppals: the factor congruence supports 1 .. 128 columns a side");
+    A = FmsArgs();
+    A.N = N;
+    A.Ca = a.cols;
+    A.Cb = b.cols;
+    A.mask = mask;
+    A.same = a.cols == b.cols;
+    int at = 0;
+    for (int i = 0; i < N; i++) {
+      if (a.rows[i] < 1 || b.rows[i] < 1 || a.ld[i] < a.rows[i] || b.ld[i] < b.rows[i])
+        throw std::runtime_error("ppals: factor_congruence rows / leading dimension out of range");
+      if (((mask >> i) & 1u) && a.rows[i] != b.rows[i])
+        throw std::runtime_error("ppals: factor_congruence extents differ in a compared mode");
+      A.a[i] = a.w[i];
+      A.b[i] = b.w[i];
+      A.lda[i] = a.ld[i];
+      A.ldb[i] = b.ld[i];
+      A.rows_a[i] = a.rows[i];
+      A.rows_b[i] = b.rows[i];
+      A.same = A.same && a.w[i] == b.w[i] && a.ld[i] == b.ld[i] && a.rows[i] == b.rows[i];
+      const int64_t chunks = (std::max(a.rows[i], b.rows[i]) + FMS_CH - 1) / FMS_CH;
+      const int64_t cps = (chunks + FMS_MAXSLAB - 1) / FMS_MAXSLAB;
+      if (cps > 0x7fffffff / FMS_CH) throw std::runtime_error("ppals: factor_congruence extent too large");
+      A.cps[i] = (int)cps;
+      A.slab0[i] = at;
+      at += (int)((chunks + cps - 1) / cps);
+    }
+    for (int i = N; i <= MAX_ORDER; i++) A.slab0[i] = at;
+  }
+  static int fms_pad(int c) { return 16 * ((c + 15) / 16); }
+  size_t factor_congruence_work(int N, const CongruenceSide &a, const CongruenceSide &b) override {
+    FmsArgs A;
+    fms_args(N, a, b, 0u, A);
+    return sizeof(double) * (size_t)A.slab0[N] * (size_t)fms_part_stride(fms_pad(a.cols), fms_pad(b.cols));
+  }
+  void factor_congruence(int N, const CongruenceSide &a, const CongruenceSide &b, unsigned mask, void *work,
+                         double *Phi, double *wa, double *wb) override {
+    RoctxRange roctx_("factor congruence");
+    FmsArgs A;
+    fms_args(N, a, b, mask, A);
+    if (!work) throw std::runtime_error("ppals: factor_congruence without its work buffer");
+    const int cap = fms_pad(a.cols), cbp = fms_pad(b.cols), nslab = A.slab0[N];
+    const size_t lds = fms_lds_bytes(cap, cbp, A.same != 0);
+    double bytes = 0;
+    for (int i = 0; i < N; i++) bytes += 8.0 * ((double)a.rows[i] * a.cols + (A.same ? 0.0 : (double)b.rows[i] * b.cols));
+    const double pbytes = 8.0 * (double)nslab * (double)fms_part_stride(cap, cbp);
+    route("fms.cross slabs=%d ca=%d cb=%d same=%d", nslab, a.cols, b.cols, A.same);
+    prof_begin(1, bytes + pbytes);
+    hipLaunchKernelGGL(k_fms_cross, dim3((unsigned)nslab), dim3(256), lds, st_, A, (double *)work);
+    prof_end();
+    HIP_CHECK(hipGetLastError());
+    const int64_t entries = (int64_t)a.cols * b.cols;
+    const unsigned nfin = (unsigned)std::min<int64_t>((entries + 255) / 256, 64);
+    prof_begin(1, pbytes + 8.0 * (double)entries);
+    hipLaunchKernelGGL(k_fms_finish, dim3(nfin), dim3(256), 0, st_, A, (const double *)work, Phi, wa, wb);
     prof_end();
     HIP_CHECK(hipGetLastError());
   }

@@ -7,6 +7,7 @@
 // with plain host loops + callbacks so the engine's host logic and the multi-rank shard plan can be
 // exercised on a CPU-only box (test infrastructure, never shipped in libppals.so).
 #pragma once
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <limits>
@@ -556,6 +557,71 @@ class Ops {
       out = 100.0 * (1.0 - s / (double)R);
     }
     h2d(cc, &out, sizeof(double));
+  }
+  // ---- factor congruence (CpEngine::congruence; include/ppals.h, "factor match score") ----
+  // Two column sets of the same order N: side a has a.cols columns, its mode-i factor a.w[i] is
+  // a.rows[i] x a.cols, column-major with leading dimension a.ld[i]; side b likewise. At most
+  // kCongruenceMaxCols columns a side. `mask` has bit i set for every COMPARED mode; in those
+  // a.rows[i] == b.rows[i]. Outputs on the device, all fp64:
+  //   Phi[p + a.cols*q] = prod over compared modes of (a_i[:,p] . b_i[:,q]) / (|a_i[:,p]| |b_i[:,q]|),
+  //                       0 when a norm of p or of q in a compared mode is not a positive finite number
+  //   wa[p] = prod over ALL N modes of |a_i[:,p]|, wb[q] likewise (as computed: 0, inf and NaN stay)
+  // `work`: factor_congruence_work(...) bytes of device memory owned by the caller (nullptr when 0).
+  // The same inputs give the same bits: no atomics, partial sums added in a fixed order.
+  static constexpr int kCongruenceMaxCols = 128;
+  struct CongruenceSide {
+    const double *w[MAX_ORDER];
+    int64_t ld[MAX_ORDER], rows[MAX_ORDER];
+    int cols;
+  };
+  virtual size_t factor_congruence_work(int /*N*/, const CongruenceSide & /*a*/, const CongruenceSide & /*b*/) {
+    return 0;
+  }
+  // (the default: the fp64 twin on the host, as above)
+  virtual void factor_congruence(int N, const CongruenceSide &a, const CongruenceSide &b, unsigned mask,
+                                 void * /*work*/, double *Phi, double *wa, double *wb) {
+    if (a.cols < 1 || b.cols < 1 || a.cols > kCongruenceMaxCols || b.cols > kCongruenceMaxCols)
+      throw Unsupported("ppals: the factor congruence supports 1 .. 128 columns a side");
+    const int Ca = a.cols, Cb = b.cols;
+    const double dmax = std::numeric_limits<double>::max();
+    std::vector<double> phi((size_t)Ca * Cb, 1.0), na(Ca, 1.0), nb(Cb, 1.0);
+    std::vector<char> bad_a(Ca, 0), bad_b(Cb, 0);
+    auto fetch = [&](const CongruenceSide &s, int i, std::vector<double> &h) {
+      h.resize((size_t)s.ld[i] * (s.cols - 1) + (size_t)s.rows[i]);
+      d2h(h.data(), s.w[i], sizeof(double) * h.size());
+    };
+    std::vector<double> ha, hb, xa(Ca), xb(Cb);
+    for (int i = 0; i < N; i++) {
+      fetch(a, i, ha);
+      fetch(b, i, hb);
+      const bool compared = (mask >> i) & 1u;
+      auto norms = [&](const CongruenceSide &s, const std::vector<double> &h, std::vector<double> &x,
+                       std::vector<double> &w, std::vector<char> &bad) {
+        for (int c = 0; c < s.cols; c++) {
+          double ss = 0;
+          for (int64_t r = 0; r < s.rows[i]; r++) ss += h[(size_t)(r + s.ld[i] * c)] * h[(size_t)(r + s.ld[i] * c)];
+          x[c] = std::sqrt(ss);
+          w[c] *= x[c];
+          if (compared && (!(x[c] > 0.0) || !(x[c] <= dmax))) bad[c] = 1;
+        }
+      };
+      norms(a, ha, xa, na, bad_a);
+      norms(b, hb, xb, nb, bad_b);
+      if (!compared) continue;
+      for (int q = 0; q < Cb; q++)
+        for (int p = 0; p < Ca; p++) {
+          double dot = 0;
+          for (int64_t r = 0; r < a.rows[i]; r++)
+            dot += ha[(size_t)(r + a.ld[i] * p)] * hb[(size_t)(r + b.ld[i] * q)];
+          phi[p + (size_t)Ca * q] *= (dot / xa[p]) / xb[q];
+        }
+    }
+    for (int q = 0; q < Cb; q++)
+      for (int p = 0; p < Ca; p++)
+        if (bad_a[p] || bad_b[q]) phi[p + (size_t)Ca * q] = 0.0;
+    h2d(Phi, phi.data(), sizeof(double) * phi.size());
+    h2d(wa, na.data(), sizeof(double) * Ca);
+    h2d(wb, nb.data(), sizeof(double) * Cb);
   }
   // Where the next scan_contract calls are booked in the launch profile: 0 the tensor scans (the default),
   // 1 the other kernels — for a scan of something that is not the tensor.

@@ -13,6 +13,7 @@
 #include "backend.h"
 #include "preload_policy.h"
 #include "engine.h"
+#include "assignment.h"
 #include "tucker.h"
 
 using namespace ppals;
@@ -859,6 +860,120 @@ int ppals_cp_multi_core(ppals_cp_multi *s, int start, double *core, int64_t *n) 
   if (!core) return PPALS_OK;  // the size query
   double cc = 0;
   s->eng->core_consistency(start, &cc, core);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+
+// ------------------------------------------------------------------ factor match score
+int ppals_match_columns(const double *score, int ra, int rb, int ld, int *perm, double *sum) {
+  if (!score) return fail(PPALS_ERR_ARG, "ppals_match_columns: score is NULL");
+  if (ra < 1 || rb < 1) return fail(PPALS_ERR_ARG, "ppals_match_columns: ra and rb must be >= 1");
+  if (ld < ra) return fail(PPALS_ERR_ARG, "ppals_match_columns: ld must be >= ra");
+  API_BEGIN
+  if (!match_columns(score, ra, rb, ld, perm, sum))
+    return fail(PPALS_ERR_ARG, "ppals_match_columns: score has an entry that is not finite");
+  return PPALS_OK;
+  API_END(PPALS_ERR_ARG)
+}
+// the refusals the congruence / fms entry points share, before anything is launched
+static int check_congruence(ppals_ctx *ca, const CpEngine *a, ppals_ctx *cb, const CpEngine *b, int skip_mode,
+                            int flags, const char *fn) {
+  char msg[224];
+  if (!a || !b) {
+    std::snprintf(msg, sizeof(msg), "%s: NULL session", fn);
+    return fail(PPALS_ERR_ARG, msg);
+  }
+  if (ca != cb) {
+    std::snprintf(msg, sizeof(msg), "%s: the sessions belong to different contexts", fn);
+    return fail(PPALS_ERR_ARG, msg);
+  }
+  if (a->order() != b->order()) {
+    std::snprintf(msg, sizeof(msg), "%s: the sessions differ in order (%d and %d)", fn, a->order(), b->order());
+    return fail(PPALS_ERR_ARG, msg);
+  }
+  if (skip_mode < -1 || skip_mode >= a->order()) {
+    std::snprintf(msg, sizeof(msg), "%s: skip_mode %d is outside [-1, %d)", fn, skip_mode, a->order());
+    return fail(PPALS_ERR_ARG, msg);
+  }
+  if (flags & ~PPALS_FMS_WEIGHTS) {
+    std::snprintf(msg, sizeof(msg), "%s: unknown flag bits 0x%x", fn, (unsigned)(flags & ~PPALS_FMS_WEIGHTS));
+    return fail(PPALS_ERR_ARG, msg);
+  }
+  for (int i = 0; i < a->order(); i++)
+    if (i != skip_mode && a->mode_extent(i) != b->mode_extent(i)) {
+      std::snprintf(msg, sizeof(msg), "%s: mode %d has extent %lld in the first session and %lld in the second",
+                    fn, i, (long long)a->mode_extent(i), (long long)b->mode_extent(i));
+      return fail(PPALS_ERR_ARG, msg);
+    }
+  if (ca->c().size() > 1) {
+    std::snprintf(msg, sizeof(msg), "%s: the factor match score runs on one rank (no sharded form)", fn);
+    return fail(PPALS_ERR_UNSUPPORTED, msg);
+  }
+  if (a->rank_r() > Ops::kCongruenceMaxCols || b->rank_r() > Ops::kCongruenceMaxCols) {
+    std::snprintf(msg, sizeof(msg), "%s: a session of more than 128 columns", fn);
+    return fail(PPALS_ERR_UNSUPPORTED, msg);
+  }
+  return PPALS_OK;
+}
+static int congruence_call(ppals_ctx *ca, CpEngine *a, ppals_ctx *cb, CpEngine *b, int skip_mode, double *Phi,
+                           int64_t *n, const char *fn) {
+  if (int rc = check_congruence(ca, a, cb, b, skip_mode, 0, fn)) return rc;
+  if (!Phi && !n) {
+    g_err = std::string(fn) + ": Phi and n are both NULL";
+    return PPALS_ERR_ARG;
+  }
+  API_BEGIN
+  const int64_t total = (int64_t)a->rank_r() * b->rank_r();
+  if (n) *n = total;
+  if (!Phi) return PPALS_OK;  // the size query
+  std::vector<double> h;
+  a->congruence(*b, skip_mode, h);
+  std::memcpy(Phi, h.data(), sizeof(double) * (size_t)total);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_cp_congruence(ppals_cp *a, ppals_cp *b, int skip_mode, double *Phi, int64_t *n) {
+  return congruence_call(a ? a->ctx : nullptr, a ? a->eng : nullptr, b ? b->ctx : nullptr, b ? b->eng : nullptr,
+                         skip_mode, Phi, n, "ppals_cp_congruence");
+}
+int ppals_cp_multi_congruence(ppals_cp_multi *s, ppals_cp_multi *other, int skip_mode, double *Phi, int64_t *n) {
+  if (!other) other = s;
+  return congruence_call(s ? s->ctx : nullptr, s ? s->eng : nullptr, other ? other->ctx : nullptr,
+                         other ? other->eng : nullptr, skip_mode, Phi, n, "ppals_cp_multi_congruence");
+}
+int ppals_cp_fms(ppals_cp *a, ppals_cp *b, int skip_mode, int flags, double *fms, int *perm) {
+  if (int rc = check_congruence(a ? a->ctx : nullptr, a ? a->eng : nullptr, b ? b->ctx : nullptr,
+                                b ? b->eng : nullptr, skip_mode, flags, "ppals_cp_fms"))
+    return rc;
+  if (!fms) return fail(PPALS_ERR_ARG, "ppals_cp_fms: fms is NULL");
+  API_BEGIN
+  a->eng->fms_pairs(*b->eng, skip_mode, (flags & PPALS_FMS_WEIGHTS) != 0, false, fms, perm);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_cp_multi_fms(ppals_cp_multi *s, int skip_mode, int flags, double *fms) {
+  if (int rc = check_congruence(s ? s->ctx : nullptr, s ? s->eng : nullptr, s ? s->ctx : nullptr,
+                                s ? s->eng : nullptr, skip_mode, flags, "ppals_cp_multi_fms"))
+    return rc;
+  if (!fms) return fail(PPALS_ERR_ARG, "ppals_cp_multi_fms: fms is NULL");
+  API_BEGIN
+  s->eng->fms_pairs(*s->eng, skip_mode, (flags & PPALS_FMS_WEIGHTS) != 0, true, fms, nullptr);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_cp_multi_fms_between(ppals_cp_multi *a, ppals_cp_multi *b, int skip_mode, int flags, double *fms) {
+  if (int rc = check_congruence(a ? a->ctx : nullptr, a ? a->eng : nullptr, b ? b->ctx : nullptr,
+                                b ? b->eng : nullptr, skip_mode, flags, "ppals_cp_multi_fms_between"))
+    return rc;
+  if (!fms) return fail(PPALS_ERR_ARG, "ppals_cp_multi_fms_between: fms is NULL");
+  if (a->eng->nstarts() != b->eng->nstarts()) {
+    char msg[160];
+    std::snprintf(msg, sizeof(msg), "ppals_cp_multi_fms_between: the sessions have %d and %d starts",
+                  a->eng->nstarts(), b->eng->nstarts());
+    return fail(PPALS_ERR_ARG, msg);
+  }
+  API_BEGIN
+  a->eng->fms_pairs(*b->eng, skip_mode, (flags & PPALS_FMS_WEIGHTS) != 0, false, fms, nullptr);
   return PPALS_OK;
   API_END(PPALS_ERR_HIP)
 }

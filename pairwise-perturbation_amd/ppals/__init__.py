@@ -67,8 +67,11 @@ EXPORTS = [
     "ppals_cp_multi_create_ranks", "ppals_cp_multi_ranks",
     "ppals_cp_core_consistency", "ppals_cp_multi_core_consistency", "ppals_cp_multi_core",
     "ppals_tucker_impute_device", "ppals_tucker_em",
+    "ppals_match_columns", "ppals_cp_congruence", "ppals_cp_fms", "ppals_cp_multi_congruence",
+    "ppals_cp_multi_fms", "ppals_cp_multi_fms_between",
 ]
 MODEL, RESIDUAL = 0, 1  # PPALS_MODEL / PPALS_RESIDUAL
+FMS_WEIGHTS = 1  # PPALS_FMS_WEIGHTS
 
 
 def lib(path=None):
@@ -139,6 +142,24 @@ def collinear_factors(lens, R, col_min=0.5, col_max=0.9, seed=0):
     _check(lib().ppals_collinear_factors(len(lens), arr, R, C.c_double(col_min),
                                          C.c_double(col_max), C.c_uint64(seed), _dp(wf)))
     return unflat(wf, lens, [R] * len(lens))
+
+
+def match_columns(score):
+    """ppals_match_columns: the exact optimum of the rectangular assignment problem on score (ra, rb):
+    (perm, total), perm[p] the column matched to row p or -1 (ra > rb), total the sum of the min(ra, rb)
+    matched entries. Host only: needs no context and no device."""
+    sc = np.asfortranarray(score, dtype=np.float64)
+    if sc.ndim != 2:
+        raise PpalsError("match_columns: score must be a matrix")
+    ra, rb = sc.shape
+    perm = (C.c_int * max(ra, 1))()
+    total = C.c_double(0)
+    _check(lib().ppals_match_columns(_dp(sc), ra, rb, ra, perm, C.byref(total)))
+    return np.array(perm[:ra], dtype=np.int64), total.value
+
+
+def _skip(skip_mode):
+    return -1 if skip_mode is None else int(skip_mode)
 
 
 def preload_eigensolver():
@@ -529,6 +550,25 @@ class CP(_ModelExport, _Impute):
         _check(lib().ppals_cp_core_consistency(self._h, C.byref(cc), _dp(core), C.byref(n)))
         return cc.value, core.reshape((self.R,) * len(self.lens), order="F")
 
+    def congruence(self, other, skip_mode=None):
+        """Phi (R, other.R): the signed product over the compared modes (all, or all but skip_mode) of the
+        cosines between this session's columns and other's (ppals_cp_congruence); 0 in the row / column of
+        a column without a positive finite norm. Reads both sessions and changes nothing of them."""
+        out = np.empty((self.R, other.R), order="F")
+        n = C.c_int64(0)
+        _check(lib().ppals_cp_congruence(self._h, other._h, _skip(skip_mode), _dp(out), C.byref(n)))
+        return out
+
+    def fms(self, other, skip_mode=None, weights=False, return_perm=False):
+        """the factor match score against other (ppals_cp_fms): the mean congruence of the optimally
+        matched min(R, other.R) column pairs; weights: each pair scaled by 1 - |w - w'| / max(w, w') of
+        the components' norm products. return_perm: (fms, perm), perm[p] the matched column of other or -1."""
+        out = C.c_double(0)
+        perm = (C.c_int * self.R)()
+        _check(lib().ppals_cp_fms(self._h, other._h, _skip(skip_mode), FMS_WEIGHTS if weights else 0,
+                                  C.byref(out), perm if return_perm else None))
+        return (out.value, np.array(perm[:], dtype=np.int64)) if return_perm else out.value
+
     def tree_node(self, key, shape=None):
         n = C.c_int64(0)
         _check(lib().ppals_tree_node(self._h, key.encode(), None, C.byref(n)))
@@ -712,6 +752,31 @@ class CPMulti:
         _check(lib().ppals_cp_multi_core(self._h, int(start), _dp(out), C.byref(n)))
         return out.reshape((self.ranks[int(start)],) * len(self.lens), order="F")
 
+    def congruence(self, other=None, skip_mode=None):
+        """Phi (C, C'): all columns of all starts against those of other (None: this session itself), start
+        b owning rows / columns [sum(ranks[:b]), sum(ranks[:b + 1])) (ppals_cp_multi_congruence)"""
+        o = self if other is None else other
+        out = np.empty((sum(self.ranks), sum(o.ranks)), order="F")
+        n = C.c_int64(0)
+        _check(lib().ppals_cp_multi_congruence(self._h, None if other is None else other._h,
+                                               _skip(skip_mode), _dp(out), C.byref(n)))
+        return out
+
+    def fms(self, skip_mode=None, weights=False):
+        """(nstarts, nstarts): the factor match score of every pair of starts, each with its own rank, from
+        one congruence of all columns (ppals_cp_multi_fms)"""
+        out = np.empty((self.nstarts, self.nstarts), order="F")
+        _check(lib().ppals_cp_multi_fms(self._h, _skip(skip_mode), FMS_WEIGHTS if weights else 0, _dp(out)))
+        return out
+
+    def fms_between(self, other, skip_mode=None, weights=False):
+        """(nstarts,): start k against start k of other, a session with as many starts (their ranks and,
+        in skip_mode, the extents may differ): the split-half comparison (ppals_cp_multi_fms_between)"""
+        out = np.empty(self.nstarts)
+        _check(lib().ppals_cp_multi_fms_between(self._h, other._h, _skip(skip_mode),
+                                                FMS_WEIGHTS if weights else 0, _dp(out)))
+        return out
+
     def run(self, **kw):
         """returns (rc, sweeps, best): rc 1 if it stopped on tol / timelimit before maxiter sweeps"""
         o = _opts(**kw)
@@ -801,6 +866,40 @@ class Tucker(_ModelExport, _Impute):
             self.close()
         except Exception:
             pass
+
+
+def split_half(ctx, x, mode, ranks, sweeps, seed=0, dtype=F32, split="interleave"):
+    """Split-half validation (Harshman) of a torch tensor x in HBM: the two halves of x along `mode` —
+    "interleave": the even and the odd indices, "blocks": [0, s // 2) and [s // 2, s) — are imported as
+    strided views (Tensor.from_torch: no copy on the torch side), a CPMulti.with_ranks(ranks) session is
+    created on each, its factors drawn with numpy.random.default_rng(seed).random((s_i, r)) in the order
+    half 0 then half 1, start by start, mode by mode, and swept `sweeps` times. Returns
+    (fms, residuals of half 0, residuals of half 1), fms[k] = the factor match score of the rank-ranks[k]
+    models of the two halves over all modes but `mode` (CPMulti.fms_between)."""
+    mode = int(mode)
+    s = x.shape[mode]
+    if split == "interleave":
+        idx = (slice(0, s, 2), slice(1, s, 2))
+    elif split == "blocks":
+        idx = (slice(0, s // 2), slice(s // 2, s))
+    else:
+        raise PpalsError(f"split_half: split must be 'interleave' or 'blocks', not {split!r}")
+    rng = np.random.default_rng(seed)
+    tensors, sessions = [], []
+    try:
+        for sl in idx:
+            half = x[(slice(None),) * mode + (sl,)]
+            t = Tensor.from_torch(ctx, half, dtype)
+            tensors.append(t)
+            m = CPMulti.with_ranks(ctx, t, ranks)
+            sessions.append(m)
+            m.set_factors(-1, [[rng.random((n, r)) for n in t.lens] for r in m.ranks])
+            m.sweeps(sweeps)
+        fms = sessions[0].fms_between(sessions[1], skip_mode=mode)
+        return fms, sessions[0].residuals(), sessions[1].residuals()
+    finally:
+        for h in sessions + tensors:
+            h.close()
 
 
 # ---- reference-named entry points (als_CP.h / als_Tucker.h), argument order preserved ----
