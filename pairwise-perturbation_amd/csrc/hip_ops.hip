@@ -2072,6 +2072,7 @@ class HipOps : public Ops {
         transpose_batched(X, F64, L, J, T, Ym);
         A = Ym;
       }
+      route("unfold_gram.sym transposed=%d lds=%d", L > 1 ? 1 : 0, (int)J >= sym_lds_min_ ? 1 : 0);
       prof_begin(1, (double)C * J * 8.0);
       sym_product(A, J, A, J, nullptr, 0, G, J, (int)J, (int)C, 1.0, 0.0);
       prof_end();
@@ -2090,6 +2091,7 @@ class HipOps : public Ops {
                                               std::max<int64_t>(1, C / 1024));
       const KSplit ks = k_split(C, std::min(want, 512), 1, 32);
       double *dst = pass_dst(ks.nsplit, J * J, 1, 1, G, 0, 0, 0, RowPad()).p;
+      route("unfold_gram.syrk nsplit=%d", ks.nsplit);
       prof_begin(1, (double)C * J * dtype_size(dt));
       hipLaunchKernelGGL(k_unfold_syrk_f32, dim3((unsigned)ntri, 1, (unsigned)ks.nsplit), dim3(256), 0, st_,
                          (const float *)X, L, J, T, ks.per, dst);
@@ -2108,6 +2110,7 @@ class HipOps : public Ops {
     const int64_t per = ks.per;
     double *dst = pass_dst(nsplit, J * J, 1, 1, G, 0, 0, 0, RowPad()).p;
     dim3 grid(tiles, tiles, nsplit);
+    route("unfold_gram.%s.%s nsplit=%d", J >= 16 ? "mfma" : "valu", dt == F32 ? "f32" : "f64", nsplit);
     prof_begin(1, (double)C * J * dtype_size(dt));
     if (J >= 16) {  // matrix cores (K13); tiny modes: the VALU tile kernel
       if (dt == F32)
@@ -2132,6 +2135,7 @@ class HipOps : public Ops {
   void top_eigvecs(double *G, int64_t J, int rank, double *U) override {
     RoctxRange roctx_("K12 eig (full solver)");
     if (J <= 64) {  // small modes: in-LDS Jacobi, one block
+      route("%s", "eig.full.lds_jacobi");
       launch_top_eig_small(G, (int)J, rank, U, nullptr);
       HIP_CHECK(hipGetLastError());
       return;
@@ -2139,6 +2143,7 @@ class HipOps : public Ops {
     if (J <= kJacobiBigMax) {
       // 64 < J <= 128 (the small side of a tall unfolding at core ranks 70-100, a short mode): the
       // whole eigen-decomposition by the one-workgroup one-sided Jacobi, no vendor library
+      route("%s", "eig.full.onesided_jacobi");
       double *w = (double *)ensure(ws_jac_, ws_jac_sz_, sizeof(double) * (2 * (size_t)J * J + 2 * J));
       double *Vt = w, *Y = Vt + J * J, *evd = Y + J * J, *D = evd + J;
       const size_t lds = sizeof(double) * ((size_t)J * (J + 1) + 256) + sizeof(int) * 256;
@@ -2151,6 +2156,7 @@ class HipOps : public Ops {
       HIP_CHECK(hipGetLastError());
       return;
     }
+    route("%s", "eig.full.dsyevd");
     RocSolver &rs = rocsolver();
     double *D = (double *)ensure(ws_krp_, ws_krp_sz_, sizeof(double) * (2 * J + 2));
     double *E = D + J;
@@ -2297,6 +2303,7 @@ class HipOps : public Ops {
     if (r > 64) {
       // more columns than the one-wave Cholesky holds (core ranks above 48, test_ALS.cxx:366-379):
       // block Gram-Schmidt, 64 columns at a time, in place — its own read-back says whether it held
+      route("chol_qr2.blocks r=%d", r);
       const int st[2] = {orthonormalize(cur, J, r) ? 0 : 1, 0};
       HIP_CHECK(hipMemcpyAsync(status, st, sizeof(int) * std::min(npass, 2), hipMemcpyHostToDevice, st_));
       HIP_CHECK(hipStreamSynchronize(st_));
@@ -2323,6 +2330,7 @@ class HipOps : public Ops {
     if (r <= 0) return true;
     if (r > 2048) throw std::runtime_error("ppals: orthonormalize supports at most 2048 columns");
     const int nblk = (r + 63) / 64;
+    route("orthonormalize nblk=%d", nblk);
     double *w = (double *)ensure(ws_orth_, ws_orth_sz_,
                                  sizeof(double) * ((size_t)rows * 64 + 64 * 64 + (size_t)r * 64) +
                                      sizeof(int) * 2 * 64);
@@ -2398,10 +2406,12 @@ class HipOps : public Ops {
       sm.valid = false;
     }
     if (!sm.valid || ++sm.age >= 64) {
+      route("%s", "eig.small cold=1");
       launch_top_eig_small(G, Ji, Ji, sm.Q, nullptr);
       sm.valid = true;
       sm.age = 0;
     } else {
+      route("%s", "eig.small cold=0");
       double *w = (double *)ensure(ws_eig_, ws_eig_sz_, sizeof(double) * 5 * nJJ);
       double *Qt = w, *C1 = Qt + nJJ, *H = C1 + nJJ, *Y = H + nJJ, *Qn = Y + nJJ;
       transpose2d(sm.Q, F64, J, J, Qt);
@@ -2423,6 +2433,8 @@ class HipOps : public Ops {
     }
     // (up to core rank 112: rank + 16 columns of a wide tail / cold start must fit kEigEvMax)
     if (J <= 64 || rank + 16 > kEigEvMax || rank + 16 >= J || slot < 0 || !eig_fast_) {
+      route("eig.warm.direct why=%s", J <= 64 ? "J" : rank + 16 > kEigEvMax ? "rank_max" : rank + 16 >= J ? "rank_J"
+                                                    : slot < 0 ? "slot" : "fast");
       top_eigvecs(G, J, rank, U);
       return;
     }
@@ -2432,6 +2444,7 @@ class HipOps : public Ops {
     if (es.valid && (es.J != J || es.rank != rank)) es.valid = false;
     if (es.valid && projector_step(es, G, J, rank, U, slot, false)) return;
     if (es.valid) {  // the spectral bound may have been outrun: once more on the measured norm
+      route("%s", "eig.warm.frob_retry");
       eig_frob_once_ = true;
       const bool ok = projector_step(es, G, J, rank, U, slot, false);
       eig_frob_once_ = false;
@@ -2445,16 +2458,25 @@ class HipOps : public Ops {
     // projector step — checked against machine precision, not against an estimated gap — delivers
     // the eigenpairs; the full solver remains the fallback of the fallback
     if (eig_cold_) {
-      if (cold_ritz_state(es, G, J, rank, slot)) {
+      const bool ritz_ok = cold_ritz_state(es, G, J, rank, slot);
+      route("eig.cold.ritz ok=%d", ritz_ok ? 1 : 0);
+      if (ritz_ok) {
         // (long modes: thin products instead of ~46 products of J^3; kColdSubspaceFrom: where a J^3
         // product, 7.4 us at J = 400, stops being cheap against a step of thin products + Rayleigh-Ritz)
-        if (J >= cold_subspace_from_ && cold_subspace(es, G, J, rank, U, slot)) return;
+        if (J >= cold_subspace_from_ && cold_subspace(es, G, J, rank, U, slot)) {
+          route("%s", "eig.cold.subspace");
+          return;
+        }
         if (projector_step(es, G, J, rank, U, slot, true)) return;
       }
       // a flat spectrum around the cut (the Gram of a noise tensor: the HOSVD initialisation), where
       // Ritz values cannot place the shift: place it by COUNTING eigenvalues with the sign iteration
-      if (cold_ok_ && cold_bisect(es, G, J, rank, U, slot)) return;
+      if (cold_ok_ && cold_bisect(es, G, J, rank, U, slot)) {
+        route("%s", "eig.cold.bisect");
+        return;
+      }
     }
+    route("%s", "eig.warm.bootstrap");
     es.valid = false;
     if (eig_debug_)
       fprintf(stderr, "[ppals eig] slot %d J %lld rank %d: full solver (%s)\n", slot, (long long)J, rank,
@@ -2609,7 +2631,10 @@ class HipOps : public Ops {
   }
   int eig_verify(int slot, bool discard) override {
     auto it = eig_state_.find(slot);
-    if (it == eig_state_.end() || !it->second.deferred) return -1;
+    if (it == eig_state_.end() || !it->second.deferred) {
+      route("%s", "eig.verify idle");
+      return -1;
+    }
     EigState &es = it->second;
     es.deferred = false;
     HIP_CHECK(hipEventSynchronize(es.ev_chk));
@@ -2646,8 +2671,10 @@ class HipOps : public Ops {
       es.dom_move = es.dp.m == 1 ? std::sqrt(std::max(0.0, hc[9])) : -1.0;
       es.fast++;
       es.stable++;
+      route("%s", "eig.verify accepted");
       return 0;
     }
+    route("eig.verify %s", discard ? "discarded" : "rejected");
     std::swap(es.Q, es.Qn);  // (the step had put its basis in front)
     es.stable = 0;
     es.dom_move = -1;
@@ -3024,6 +3051,12 @@ class HipOps : public Ops {
     // fused tail: the check sums ride on the LAST step's two products (per-tile partial sums of
     // ||X_prev^2 - I||_F^2 and of trace(X_new), added up by the tail's last kernel)
     const bool fused_tail = m <= 1 && rank + kWide <= 64;
+    // (the step's tag of the route log: what scheduled it and how it ended)
+    auto tag = [&](bool wide, bool lazy, bool defer, bool ok) {
+      route("eig.projector m=%d strict=%d fused_scale=%d fused_tail=%d wide=%d lazy=%d defer_now=%d ok=%d",
+            std::min(m, 2), strict ? 1 : 0, fused_scale ? 1 : 0, fused_tail ? 1 : 0, wide ? 1 : 0, lazy ? 1 : 0,
+            defer ? 1 : 0, ok ? 1 : 0);
+    };
     double *pe2 = (double *)ensure(ws_part2_, ws_part2_sz_, sizeof(double) * (2 * (size_t)ntri + 2 * 256 + 2));
     double *ptr_ = pe2 + ntri;
     auto ns_step = [&](double mu, bool last = false) {
@@ -3108,6 +3141,7 @@ class HipOps : public Ops {
         es.dp.iters = iters;
         es.dp.pow = pow_steps;
         std::swap(es.Q, es.Qn);  // (eig_verify swaps back when the step is not accepted)
+        tag(false, true, true, true);
         return true;
       }
       const double *hc = (const double *)eig_host_, *evn = hc + 16;
@@ -3134,6 +3168,7 @@ class HipOps : public Ops {
         es.dom_move = (m == 1 && fused_scale) ? std::sqrt(std::max(0.0, hc[9])) : -1.0;
         std::swap(es.Q, es.Qn);
         es.fast++;
+        tag(false, true, false, true);
         return true;
       }
       if (lazy_used) {
@@ -3160,6 +3195,7 @@ class HipOps : public Ops {
         else
           HIP_CHECK(hipMemcpyAsync(es.Q, U, sizeof(double) * nJR, hipMemcpyDeviceToDevice, st_));
         es.fast++;
+        tag(false, false, false, true);
         return true;
       }
       const int cwide = (int)std::lround(cnt);
@@ -3190,9 +3226,11 @@ class HipOps : public Ops {
           es.rho_frob = rho_now;
           HIP_CHECK(hipMemcpyAsync(es.Q, U, sizeof(double) * nJR, hipMemcpyDeviceToDevice, st_));
           es.fast++;
+          tag(true, false, false, true);
           return true;
         }
-        break;
+        tag(true, false, false, false);
+        return false;
       }
       if (converged || attempt >= (strict ? 4 : 2)) break;
       // the gap was narrower than estimated: a few more steps, then the tail again
@@ -3205,6 +3243,7 @@ class HipOps : public Ops {
       HIP_CHECK(hipMemsetAsync(status, 0, 2 * sizeof(int), st_));  // (the Cholesky QR of the tail)
     }
     // sigma does not separate `rank` eigenvalues, a lost direction, no convergence
+    tag(false, false, false, false);
     return false;
   }
   // Cold start of a slot: q steps of block subspace iteration from a pseudo-random block of
@@ -3293,9 +3332,12 @@ class HipOps : public Ops {
   // columns. From the Ritz pairs (U, theta) of cold_ritz_state: B = orth(G U theta^-1) — scaled column
   // by column, so the block stays near orthonormal whatever the spread of the spectrum (a mean
   // component 1e6 above the rest included) —, Rayleigh-Ritz on B, residual of the leading `rank` pairs;
-  // accepted at the warm steps' bar (residual <= 1e-9 x the Ritz gap below the rank-th value, or the
-  // rounding floor). The iteration converges like (lambda_{rank+17} / lambda_rank)^k: where the residual
-  // shows that this will not get there within the budget, false — the caller goes on to the projector.
+  // accepted at the bar of every other cold start (residual <= 1e-13 lambda_1 sqrt(rank), the strict
+  // projector step's and cold_bisect's: a cold start has no previous gap to lean on, and the op-level
+  // tests hold all cold routes to that one bar). The iteration converges like
+  // (lambda_{rank+17} / lambda_rank)^k: where the residual shows that this will not get there within
+  // the budget — 40 steps, each two thin products, still a fraction of ONE J^3 product per step on a
+  // long mode —, false: the caller goes on to the projector.
   bool cold_subspace(EigState &es, double *G, int64_t J, int rank, double *U, int slot) {
     const int b = cold_b_, Ji = (int)J;
     if (b <= rank || !cold_Uo_) return false;
@@ -3307,7 +3349,7 @@ class HipOps : public Ops {
     if (Uo != cold_Uo_) return false;  // (the workspace moved: nothing to continue from)
     double *w2 = (double *)ensure(ws_cold2_, ws_cold2_sz_, sizeof(double) * (nJB + 16));
     double *GU = w2, *res_d = GU + nJB;
-    constexpr int kMaxIt = 24;
+    constexpr int kMaxIt = 40;
     double th[kEigEvMax], res_prev = 0;
     for (int it = 0; it < kMaxIt; it++) {
       gemm_nn(G, J, Uo, J, nullptr, 0, Z, J, Ji, b, Ji, 1.0, 0.0);  // G * (Ritz vectors)
@@ -3327,7 +3369,7 @@ class HipOps : public Ops {
       const double res = std::sqrt(res2);
       const bool sane = hs[0] != 1 && hs[1] == 0 && std::isfinite(res) && th[rank - 1] > 0 && th[rank] >= 0;
       const double gap = sane ? th[rank - 1] - th[rank] : 0.0;
-      const double tol = std::max(1e-9 * gap, 1e-13 * th[0]) * std::sqrt((double)rank);
+      const double tol = 1e-13 * th[0] * std::sqrt((double)rank);
       if (eig_debug_)
         fprintf(stderr, "[ppals eig] slot %d J %lld rank %d: cold subspace step %d, Ritz %.4e .. %.4e | %.4e, "
                         "residual %.3e (bar %.3e)\n", slot, (long long)J, rank, it, th[0], th[rank - 1], th[rank],
@@ -3605,6 +3647,7 @@ class HipOps : public Ops {
       throw std::runtime_error("ppals: rows_times_small: the small operand does not fit LDS");
     double *dst = out;
     if (out == A) dst = (double *)ensure(ws_big2_, ws_big2_sz_, sizeof(double) * (size_t)rows * C);
+    route("rows_times_small copy=%d", dst != out ? 1 : 0);
     hipLaunchKernelGGL(k_rows_times_small, dim3(grid_for(rows * C, 256)), dim3(256),
                        sizeof(double) * (size_t)K * C, st_, A, rows, K, B, C, D, dst);
     HIP_CHECK(hipGetLastError());

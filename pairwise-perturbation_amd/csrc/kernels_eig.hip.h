@@ -1882,9 +1882,22 @@ __global__ __launch_bounds__(1024) void k_jacobi_onesided(const double *__restri
   }
   __syncthreads();
   __threadfence_block();
+  // V is a product of some n x sweeps rotations per column, each orthogonal to a few u: the columns' norms drift
+  // by that many roundings (|v^T v - 1| = 1e-13 at n = 128, which alone puts the eigenpair residual of such a
+  // vector at 1e-13 lambda, the bar the projector route's own steps are held to). The eigenvectors handed out
+  // are normalised once more; V itself stays the exact record of the rotations (k_svd_inverse pairs it with W).
+  double *inrm = nrm + kJacobiBigMax;
+  for (int k = tid >> 4; k < n; k += nthr >> 4) {
+    double a = 0;
+    for (int i = gl; i < n; i += 16) a += V[i + n * k] * V[i + n * k];
+#pragma unroll
+    for (int o = 8; o >= 1; o >>= 1) a += __shfl_xor(a, o, 16);
+    if (gl == 0) inrm[k] = a > 0.0 ? 1.0 / sqrt(a) : 1.0;
+  }
+  __syncthreads();
   for (int e = tid; e < n * n; e += nthr) {
     const int i = e % n, k = e / n;
-    Y[i + n * k] = V[i + n * ord[k]];
+    Y[i + n * k] = V[i + n * ord[k]] * inrm[ord[k]];
     if (Wout) Wout[i + n * k] = W[k * ld + i];
   }
 }

@@ -2148,9 +2148,11 @@ __global__ void k_lowrank_accumulate(TV *__restrict__ X, int64_t n, int R, const
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n;
        e += (int64_t)gridDim.x * blockDim.x) {
     for (int c = 0; c < R; c++) {
-      double acc = (double)X[e + n * c];
+      // the update is summed on its own and added once: the error is r u |T||VT| plus one rounding of the
+      // result, whatever the size of X (started from X, every partial sum would round at the size of X)
+      double acc = 0.0;
       for (int k = 0; k < r; k++) acc += T[e + n * k] * sV[k + r * c];
-      X[e + n * c] = (TV)acc;
+      X[e + n * c] = (TV)((double)X[e + n * c] + acc);
     }
   }
 }

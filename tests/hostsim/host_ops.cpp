@@ -38,7 +38,9 @@ inline double ld(const void *V, int dt, int64_t e) {
   return dt == F32 ? (double)((const float *)V)[e] : ((const double *)V)[e];
 }
 inline void st(void *V, int dt, int64_t e, double v) {
-  if (dt == F32)
+  if (dt == BF16) {  // (op-level tests only)
+    ((uint16_t *)V)[e] = bf16_bits_from_double(v);
+  } else if (dt == F32)
     ((float *)V)[e] = (float)v;
   else
     ((double *)V)[e] = v;
@@ -529,9 +531,9 @@ class HostOps : public Ops {
                           const double *VT) override {
     for (int c = 0; c < R; c++)
       for (int64_t e = 0; e < n; e++) {
-        double v = ld(X, xdt, e + n * c);
+        double v = 0;  // (the update is summed on its own: one rounding of X + update, one to storage)
         for (int k = 0; k < r; k++) v += T[e + n * k] * VT[k + (int64_t)r * c];
-        st(X, xdt, e + n * c, v);
+        st(X, xdt, e + n * c, ld(X, xdt, e + n * c) + v);
       }
   }
 };

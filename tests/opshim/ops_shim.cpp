@@ -1,7 +1,9 @@
 // ops_shim.cpp — TEST INFRASTRUCTURE: a C surface over ppals::Ops for the op-level tests of the
-// contraction kernels (tests/contraction_cases.py) and of the mode-update side
-// (tests/update_cases.py). One source, two libraries: linked against the product's libppals.so it
-// reaches the HIP kernels as compiled there, linked against the host stand-in it reaches HostOps. No HIP code and no HIP calls here: every device action goes through the Ops.
+// contraction kernels (tests/contraction_cases.py), of the mode-update side (tests/update_cases.py)
+// and of the Tucker eigen side (tests/tucker_ops_cases.py). One source, two libraries: linked
+// against the product's libppals.so it reaches the HIP kernels as compiled there, linked against
+// the host stand-in it reaches HostOps. No HIP code and no HIP calls here: every device action goes
+// through the Ops.
 // Every function returns 0, or -1 after an exception whose text shim_error() then returns (the
 // launchers' own refusals — "padded rows inconsistent" — arrive that way).
 #include <cstring>
@@ -238,6 +240,89 @@ int shim_scale_update_many(void *h, double *dst, const double *scales, const uns
                            unsigned fresh) {
   Shim *s = (Shim *)h;
   return guarded(s, [&] { s->ops->scale_update_many(dst, scales, masks, active, fresh); });
+}
+
+// ---- the Tucker eigen side and the low-rank factor ops (tests/tucker_ops_cases.py) ----
+int shim_d2d(void *h, void *dst, const void *src, size_t bytes) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->d2d(dst, src, bytes); });
+}
+int shim_unfold_gram(void *h, const void *X, int dt, int64_t L, int64_t J, int64_t T, double *G) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->unfold_gram(X, dt, L, J, T, G); });
+}
+int shim_top_eigvecs(void *h, double *G, int64_t J, int rank, double *U) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->top_eigvecs(G, J, rank, U); });
+}
+int shim_top_eigvecs_warm(void *h, double *G, int64_t J, int rank, double *U, int slot) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->top_eigvecs_warm(G, J, rank, U, slot); });
+}
+int shim_eig_lazy(void *h, int slot, int on) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->eig_lazy(slot, on != 0); });
+}
+int shim_eig_defer(void *h, int slot, int on) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->eig_defer(slot, on != 0); });
+}
+int shim_eig_gram(void *h, int slot, int64_t J, double **out) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { *out = s->ops->eig_gram(slot, J); });
+}
+int shim_eig_deferred(void *h, int slot, int *out) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { *out = s->ops->eig_deferred(slot) ? 1 : 0; });
+}
+int shim_eig_verify(void *h, int slot, int discard, int *out) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { *out = s->ops->eig_verify(slot, discard != 0); });
+}
+int shim_eig_pending_rotation(void *h, int slot, const double **out) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { *out = s->ops->eig_pending_rotation(slot); });
+}
+int shim_eig_rotation_done(void *h, int slot) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->eig_rotation_done(slot); });
+}
+int shim_eig_session_new(void *h, int *out) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { *out = s->ops->eig_session_new(); });
+}
+int shim_eig_session_free(void *h, int base) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->eig_session_free(base); });
+}
+int shim_orthonormalize(void *h, double *U, int64_t rows, int r, int *ok) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { *ok = s->ops->orthonormalize(U, rows, r) ? 1 : 0; });
+}
+int shim_sign_align(void *h, double *W, const double *Wref, int64_t rows, int r) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->sign_align(W, Wref, rows, r); });
+}
+int shim_rows_times_small(void *h, const double *A, int64_t rows, int K, const double *B, int C, const double *D,
+                          double *out) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->rows_times_small(A, rows, K, B, C, D, out); });
+}
+int shim_lowrank_accumulate(void *h, void *X, int xdt, int64_t n, int R, const double *T, int r, const double *VT) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->lowrank_accumulate(X, xdt, n, R, T, r, VT); });
+}
+int shim_add_inplace(void *h, double *dst, const double *src, int64_t n) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->add_inplace(dst, src, n); });
+}
+int shim_transpose2d(void *h, const void *src, int dt, int64_t rows, int64_t cols, void *dst) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->transpose2d(src, dt, rows, cols, dst); });
+}
+int shim_transpose_batched(void *h, const void *src, int dt, int64_t rows, int64_t cols, int64_t batch, void *dst) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->transpose_batched(src, dt, rows, cols, batch, dst); });
 }
 
 // the route log (ops.h): attach (on != 0) or detach, read as one newline-joined string, clear

@@ -50,6 +50,26 @@ _SIGS = {
     "shim_sumsq": [_P, _P, _I64, _P],
     "shim_scale_update": [_P, _P, _P, _U, _I],
     "shim_scale_update_many": [_P, _P, _P, C.POINTER(_U), _U, _U],
+    "shim_d2d": [_P, _P, _P, C.c_size_t],
+    "shim_unfold_gram": [_P, _P, _I, _I64, _I64, _I64, _P],
+    "shim_top_eigvecs": [_P, _P, _I64, _I, _P],
+    "shim_top_eigvecs_warm": [_P, _P, _I64, _I, _P, _I],
+    "shim_eig_lazy": [_P, _I, _I],
+    "shim_eig_defer": [_P, _I, _I],
+    "shim_eig_gram": [_P, _I, _I64, C.POINTER(_P)],
+    "shim_eig_deferred": [_P, _I, C.POINTER(_I)],
+    "shim_eig_verify": [_P, _I, _I, C.POINTER(_I)],
+    "shim_eig_pending_rotation": [_P, _I, C.POINTER(_P)],
+    "shim_eig_rotation_done": [_P, _I],
+    "shim_eig_session_new": [_P, C.POINTER(_I)],
+    "shim_eig_session_free": [_P, _I],
+    "shim_orthonormalize": [_P, _P, _I64, _I, C.POINTER(_I)],
+    "shim_sign_align": [_P, _P, _P, _I64, _I],
+    "shim_rows_times_small": [_P, _P, _I64, _I, _P, _I, _P, _P],
+    "shim_lowrank_accumulate": [_P, _P, _I, _I64, _I, _P, _I, _P],
+    "shim_add_inplace": [_P, _P, _P, _I64],
+    "shim_transpose2d": [_P, _P, _I, _I64, _I64, _P],
+    "shim_transpose_batched": [_P, _P, _I, _I64, _I64, _I64, _P],
 }
 
 
@@ -235,6 +255,77 @@ class Shim:
 
     def scale_update_many(self, dst, scales, masks, active, fresh):
         self._ck(self.lib.shim_scale_update_many(self.h, dst, scales, self._masks(masks), active, fresh))
+
+    # ---- the Tucker eigen side and the low-rank factor ops (tests/tucker_ops_cases.py)
+    def d2d(self, dst, src, nbytes):
+        self._ck(self.lib.shim_d2d(self.h, dst, src, nbytes))
+
+    def unfold_gram(self, X, dt, L, J, T, G):
+        self._ck(self.lib.shim_unfold_gram(self.h, X, dt, L, J, T, G))
+
+    def top_eigvecs(self, G, J, rank, U):
+        self._ck(self.lib.shim_top_eigvecs(self.h, G, J, rank, U))
+
+    def top_eigvecs_warm(self, G, J, rank, U, slot):
+        self._ck(self.lib.shim_top_eigvecs_warm(self.h, G, J, rank, U, slot))
+
+    def eig_lazy(self, slot, on):
+        self._ck(self.lib.shim_eig_lazy(self.h, slot, int(on)))
+
+    def eig_defer(self, slot, on):
+        self._ck(self.lib.shim_eig_defer(self.h, slot, int(on)))
+
+    def _int_out(self, f, *args):
+        v = _I(0)
+        self._ck(f(self.h, *args, C.byref(v)))
+        return v.value
+
+    def _ptr_out(self, f, *args):
+        p = _P()
+        self._ck(f(self.h, *args, C.byref(p)))
+        return p.value
+
+    def eig_gram(self, slot, J):
+        return self._ptr_out(self.lib.shim_eig_gram, slot, J)
+
+    def eig_deferred(self, slot):
+        return bool(self._int_out(self.lib.shim_eig_deferred, slot))
+
+    def eig_verify(self, slot, discard=False):
+        return self._int_out(self.lib.shim_eig_verify, slot, int(discard))
+
+    def eig_pending_rotation(self, slot):
+        return self._ptr_out(self.lib.shim_eig_pending_rotation, slot)
+
+    def eig_rotation_done(self, slot):
+        self._ck(self.lib.shim_eig_rotation_done(self.h, slot))
+
+    def eig_session_new(self):
+        return self._int_out(self.lib.shim_eig_session_new)
+
+    def eig_session_free(self, base):
+        self._ck(self.lib.shim_eig_session_free(self.h, base))
+
+    def orthonormalize(self, U, rows, r):
+        return bool(self._int_out(self.lib.shim_orthonormalize, U, rows, r))
+
+    def sign_align(self, W, Wref, rows, r):
+        self._ck(self.lib.shim_sign_align(self.h, W, Wref, rows, r))
+
+    def rows_times_small(self, A, rows, K, B, Cc, D, out):
+        self._ck(self.lib.shim_rows_times_small(self.h, A, rows, K, B, Cc, D, out))
+
+    def lowrank_accumulate(self, X, xdt, n, R, T, r, VT):
+        self._ck(self.lib.shim_lowrank_accumulate(self.h, X, xdt, n, R, T, r, VT))
+
+    def add_inplace(self, dst, src, n):
+        self._ck(self.lib.shim_add_inplace(self.h, dst, src, n))
+
+    def transpose2d(self, src, dt, rows, cols, dst):
+        self._ck(self.lib.shim_transpose2d(self.h, src, dt, rows, cols, dst))
+
+    def transpose_batched(self, src, dt, rows, cols, batch, dst):
+        self._ck(self.lib.shim_transpose_batched(self.h, src, dt, rows, cols, batch, dst))
 
 
 def compute_units():
