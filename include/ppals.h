@@ -414,6 +414,43 @@ int ppals_cp_multi_fms(ppals_cp_multi *s, int skip_mode, int flags, double *fms)
  * split-half call for two rank-sweep sessions on the halves */
 int ppals_cp_multi_fms_between(ppals_cp_multi *a, ppals_cp_multi *b, int skip_mode, int flags, double *fms);
 
+/* ---- per-slice residuals and leverages: the influence plot (no counterpart in the reference) ----
+ * The third routine validation step of a PARAFAC model (R. Bro, "PARAFAC. Tutorial and applications",
+ * Chemom. Intell. Lab. Syst. 38, 1997, section 7; the N-way toolbox draws it from its `nmodel` residuals and the
+ * loadings' hat matrices): for every mode i and every index x of it, the sum of squared residuals over the
+ * slice x against the leverage of row x of W_i. A slice far up fits badly; one far right dominates the model.
+ * ss, lev: sum_i s_i doubles, mode 0's s_0 values first (the layout of one column of Wflat).
+ *   ss_i[x]  = sum over all elements whose i-th index is x of (V - [[W_0..W_{N-1}]])^2
+ *              V as stored (bf16 / fp32 / fp64), model, differences and sums in fp64. It is exactly the model
+ *              whose distance ppals_cp_residual returns (the same Khatri-Rao operands). *total (may be NULL)
+ *              = the sum over all elements = ppals_cp_residual()^2 up to rounding; every mode's ss_i sums to it.
+ *   lev_i[x] = w^T (W_i^T W_i)^-1 w, w = row x of W_i: the diagonal of the projector onto the column space of
+ *              W_i (in [0,1], summing to R over x for full column rank). No lambda. The Gram is the one the
+ *              session keeps, inverted as for the core consistency: a session ONE of whose N Grams meets a
+ *              pivot that is not a positive finite number gets NaN in EVERY entry of lev, and PPALS_OK.
+ * Both calls are ordered after the work queued on the engine stream and return when the result is on the
+ * host. They read the session and change nothing of it — factors, Grams, gradients, cached contractions, the
+ * multi-sweep intermediate and the tensor's generation stay, and later sweeps give bit for bit the factors
+ * they give without the call. The same state gives the same bits on every call (no floating-point atomics;
+ * partial sums are added in a fixed order). Every storage type, both schedules, non-negative sessions.
+ * Tensor traffic: ppals_cp_slice_residuals reads the tensor exactly ONCE, whatever the order, extents, rank
+ * and storage type — the pass of ppals_cp_residual, keeping the sums over the rows and the columns of its
+ * M x K split (M the product of the first N/2 extents), each then folded onto its modes; nothing of the
+ * tensor's size is materialised. ppals_cp_leverages never reads it.
+ * Work memory: the calls' own, grow-only and kept by the session until it is destroyed — the two marginals
+ * (M + K doubles), the pseudo-inverse factors and the partial sums of the pass, beside the two Khatri-Rao
+ * operands ppals_cp_residual already keeps. The partial sums stay under 256 MB whatever the extents: the row tiles of the pass are walked
+ * in slabs (and one tile's column chunks in slabs, should a single tile not fit) and folded between them as
+ * running sums in tile and chunk order, so the cap changes no bit of the result.
+ * No mask argument: after ppals_cp_impute_device the missing entries equal the model up to one storage
+ * rounding, so their share of a slice sum is rounding-sized.
+ * Refused before anything is launched or allocated, the message starting with the function's name —
+ * PPALS_ERR_ARG: a NULL session, a NULL ss / lev; PPALS_ERR_UNSUPPORTED: a context of more than one rank
+ * (both calls), ppals_cp_leverages at R > 64 (ppals_cp_slice_residuals takes every R). Multi-start and
+ * rank-sweep sessions: ppals_cp_multi_take hands a start to an ordinary session. */
+int ppals_cp_slice_residuals(ppals_cp *s, double *ss, double *total /* may be NULL */);
+int ppals_cp_leverages(ppals_cp *s, double *lev);
+
 /* ---- Tucker sessions (als_Tucker.h) ---- */
 int ppals_tucker_create(ppals_ctx *ctx, ppals_tensor *V, const int *ranks, ppals_tucker **out);
 void ppals_tucker_destroy(ppals_tucker *s);

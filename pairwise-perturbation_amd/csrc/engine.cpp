@@ -260,6 +260,7 @@ CpEngine::CpEngine(Ops &ops, Comm &comm, const TensorDesc &V, int R, int nstarts
   if (Rs_ <= 0) throw std::runtime_error("ppals: rank must be positive");
   if (multi_ && dist_) throw Unsupported("ppals: a multi-start session runs on one rank");
   residual_form_ = residual_form_env();
+  slice_work_cap_ = slice_work_cap_env();
   W_.resize(N_);
   gradW_.resize(N_);
   Wprev_.assign(N_, nullptr);
@@ -384,6 +385,10 @@ CpEngine::~CpEngine() {
   ops_.free(cc_chain_[0].ptr);
   ops_.free(cc_chain_[1].ptr);
   ops_.free(cc_core_.ptr);
+  ops_.free(sl_row_.ptr);
+  ops_.free(sl_col_.ptr);
+  ops_.free(sl_out_.ptr);
+  ops_.free(sl_work_.ptr);
   ops_.free(fms_out_.ptr);
   ops_.free(fms_work_.ptr);
   ops_.free(Pbuf_);
@@ -2343,6 +2348,71 @@ void CpEngine::core_consistency(int only, double *cc_host, double *core_host) {
     }
     core_host[dst] = tmp[(size_t)e];
   }
+}
+
+// ---------------------------------------------------------------------------- influence plot
+size_t slice_work_cap_env() {
+  const char *v = getenv("PPALS_TEST_SLICE_WORK_BYTES");
+  if (!v || !*v) return (size_t)256 << 20;
+  char *end = nullptr;
+  const long long n = strtoll(v, &end, 10);
+  if (*end || n < 1) throw std::runtime_error("ppals: PPALS_TEST_SLICE_WORK_BYTES must be a positive number of bytes");
+  return (size_t)n;
+}
+
+// The model is residual()'s: the same split, the same Khatri-Rao operands in the same buffers.
+void CpEngine::slice_residuals(double *ss_host, double *total_host) {
+  if (P_ > 1) throw Unsupported("ppals: the per-slice residuals run on one rank");
+  if (multi_) throw Unsupported("ppals: the per-slice residuals take an ordinary session");
+  int64_t M, K, nout = 0;
+  split_sizes(V_, &M, &K);
+  for (int i = 0; i < N_; i++) nout += V_.glens[i];
+  if (!Qbuf_) Qbuf_ = (double *)ops_.alloc(sizeof(double) * M * R_);
+  if (!Pbuf_) Pbuf_ = (double *)ops_.alloc(sizeof(double) * K * R_);
+  double *row = (double *)cc_reserve(sl_row_, sizeof(double) * M);
+  double *col = (double *)cc_reserve(sl_col_, sizeof(double) * K);
+  double *out = (double *)cc_reserve(sl_out_, sizeof(double) * (nout + 1));
+  split_krp(ops_, V_, R_, W_.data(), Qbuf_, Pbuf_, &M, &K);
+  ops_.residual_slices(V_.data, V_.dtype, M, K, Qbuf_, Pbuf_, R_, row, col, out + nout, slice_work_cap_, sl_work_.ptr,
+                       sl_work_.cap);
+  const int h = N_ / 2;
+  int64_t left = 0;
+  for (int i = 0; i < h; i++) left += V_.glens[i];
+  if (h > 0) ops_.fold_slice_sums(row, V_.glens, h, out);
+  ops_.fold_slice_sums(col, V_.glens + h, N_ - h, out + left);
+  ops_.d2h(ss_host, out, sizeof(double) * nout);
+  if (total_host) ops_.d2h(total_host, out + nout, sizeof(double));
+}
+
+void CpEngine::leverages(double *lev_host) {
+  if (P_ > 1) throw Unsupported("ppals: the leverages run on one rank");
+  if (multi_) throw Unsupported("ppals: the leverages take an ordinary session");
+  if (R_ > Ops::kPinvMaxRank) throw Unsupported("ppals: the leverages support ranks <= 64");
+  StartTable tab;
+  tab.nstarts = 1;
+  tab.col[1] = R_;
+  tab.sq[1] = R_ * R_;
+  int64_t rows[MAX_ORDER], nout = 0;
+  for (int i = 0; i < N_; i++) nout += (rows[i] = V_.glens[i]);
+  if (cc_P_.empty()) {  // (the buffers of the core consistency: the same pseudo-inverse factors)
+    cc_P_.assign(N_, nullptr);
+    for (int i = 0; i < N_; i++) cc_P_[i] = (double *)ops_.alloc(sizeof(double) * (size_t)rows[i] * R_);
+    cc_flag_ = (int *)ops_.alloc(sizeof(int));
+    cc_out_ = (double *)ops_.alloc(sizeof(double));
+  }
+  double *out = (double *)cc_reserve(sl_out_, sizeof(double) * (nout + 1));
+  ops_.zero(cc_flag_, sizeof(int));
+  ops_.cp_pinv_ragged(G_, N_, tab, W_.data(), rows, cc_P_.data(), cc_flag_);
+  int64_t off = 0;
+  for (int i = 0; i < N_; i++) {
+    ops_.row_dots(cc_P_[i], W_[i], rows[i], R_, rows[i], out + off);
+    off += rows[i];
+  }
+  int bad = 0;
+  ops_.d2h(&bad, cc_flag_, sizeof(int));
+  ops_.d2h(lev_host, out, sizeof(double) * nout);
+  if (bad)  // a Gram without a positive finite pivot: no projector to speak of
+    for (int64_t e = 0; e < nout; e++) lev_host[e] = std::numeric_limits<double>::quiet_NaN();
 }
 
 // ---------------------------------------------------------------------------- factor match score

@@ -42,6 +42,9 @@ inline bool force_comm_path() {
 // PPALS_MODEL_RESIDUAL=two_pass keeps the other one reachable for that A/B. Read at session creation.
 enum ResidualForm { RESIDUAL_FUSED = 0, RESIDUAL_TWO_PASS = 1 };
 int residual_form_env();
+// PPALS_TEST_SLICE_WORK_BYTES=n (tests): the cap of the partial sums of slice_residuals, 256 MB without it —
+// so that small shapes reach the walk in slabs. Read at session creation.
+size_t slice_work_cap_env();
 // the model (or the residual) of the plan through the view: picks the residual's form, and for two
 // passes runs the tensor export of the whole view `a` first (the plan may be one slab of it)
 struct ModelExportCall {
@@ -172,6 +175,18 @@ class CpEngine {
   // sessions only): rank_r() ints, the matched column of b or -1.
   void fms_pairs(CpEngine &b, int skip_mode, bool weights, bool pairwise, double *fms, int *perm);
   int64_t mode_extent(int i) const { return V_.glens[i]; }
+  // The influence plot of an ordinary session (Bro 1997; include/ppals.h). Both lay their N vectors out one
+  // after the other, mode 0's s_0 values first. They read the session and change nothing of it; the buffers
+  // are the calls' own (grow-only, kept). Synchronise. One rank, no multi-start session.
+  //   slice_residuals: ss_i[x] = the sum of (V - [[W]])^2 over the slice x of mode i, of exactly the model
+  //     residual() measures (the same operands); *total_host (may be nullptr) = the sum over everything. ONE
+  //     pass over the tensor (Ops::residual_slices: the sums over the rows and the columns of the M x K
+  //     split), then one fold of each marginal onto its modes (Ops::fold_slice_sums).
+  //   leverages: lev_i[x] = w^T (W_i^T W_i)^-1 w, w = row x of W_i, from the pseudo-inverse factors of the
+  //     core consistency (Ops::cp_pinv_ragged, Ops::row_dots); all NaN when a Gram has no such inverse. The
+  //     tensor is not read.
+  void slice_residuals(double *ss_host, double *total_host);
+  void leverages(double *lev_host);
 
   // kernel-level access for parity tests
   int64_t tree_node(const std::string &key, double *out_host);
@@ -420,6 +435,9 @@ class CpEngine {
     size_t cap = 0;
   };
   GrowBuf cc_Y_, cc_chain_[2], cc_core_;
+  // slice_residuals / leverages: the two marginals, the folded result, the partial sums of the pass
+  GrowBuf sl_row_, sl_col_, sl_out_, sl_work_;
+  size_t slice_work_cap_ = (size_t)256 << 20;  // of the back end's partial sums (PPALS_TEST_SLICE_WORK_BYTES)
   GrowBuf fms_out_, fms_work_;  // congruence: Phi | w_a | w_b, and the back end's partial sums
   StartTable start_table() const;  // tab_, or the one start of an ordinary session
   void *cc_reserve(GrowBuf &b, size_t bytes);

@@ -21,6 +21,7 @@
 #include "kernels_nn.hip.h"
 #include "kernels_corcondia.hip.h"
 #include "kernels_fms.hip.h"
+#include "kernels_slices.hip.h"
 #include "kernels_eig.hip.h"
 #include "kernels_io.hip.h"
 #include "kernels_model.hip.h"
@@ -308,10 +309,13 @@ class HipOps : public Ops {
     HIP_CHECK(hipGetLastError());
   }
 
-  // K10 on the matrix cores (kernels_scan.hip.h: k_rank_mfma); false: shape not covered
-  template <typename TV, int MODE>
-  bool rank_mfma(void *V, int64_t M, int64_t K, const double *Q, const double *P, int R,
-                 double *out) {
+  // the launch geometry of k_rank_mfma (MODE 3 walks the one of MODE 1 in slabs); false: shape not covered
+  struct RankPlan {
+    int nkb, nchunk, per, rem, RB;
+    int64_t n_mtiles;
+  };
+  template <typename TV>
+  bool rank_plan(int mode, const void *V, int64_t M, int64_t K, int R, RankPlan &pl) {
     constexpr int VEC = ScanTraits<TV>::VEC;
     if (R > 32 || M % VEC != 0 || M < VEC || (((uintptr_t)V) & 15) != 0 || K < 1)
       return false;
@@ -331,9 +335,19 @@ class HipOps : public Ops {
     // (measured, tools/k10_probe.py at cfg2, profiles/r04I_k10_probe.txt: R = 10 1.28 -> 1.26 ms, R = 9
     // 1.17 ms, R = 13 1.38 ms against ~1.5 ms with a padded fourth step; two ranks beside three or four
     // steps — R = 14: 1.63 ms, R = 18: 1.78 ms — lose to padding: 2 waves per SIMD)
-    int rem = (MODE == 1 && R > 4 && R <= 17 && (R % 4 == 1 || (R % 4 == 2 && R <= 10))) ? R % 4 : 0;
+    int rem = ((mode == 1 || mode == 3) && R > 4 && R <= 17 && (R % 4 == 1 || (R % 4 == 2 && R <= 10))) ? R % 4 : 0;
     if (sizeof(double) * (size_t)per * 16 * rem > 48 * 1024) rem = 0;
-    const int RB = MODE == 2 ? 1 : (R - rem + 3) / 4;
+    pl = {nkb, nchunk, per, rem, mode == 2 ? 1 : (R - rem + 3) / 4, n_mtiles};
+    return true;
+  }
+  // K10 on the matrix cores (kernels_scan.hip.h: k_rank_mfma); false: shape not covered
+  template <typename TV, int MODE>
+  bool rank_mfma(void *V, int64_t M, int64_t K, const double *Q, const double *P, int R,
+                 double *out) {
+    RankPlan pl;
+    if (!rank_plan<TV>(MODE, V, M, K, R, pl)) return false;
+    const int nkb = pl.nkb, nchunk = pl.nchunk, per = pl.per, rem = pl.rem, RB = pl.RB;
+    const int64_t n_mtiles = pl.n_mtiles;
     double *Ppk = nullptr;
     if (MODE != 2) {
       Ppk = (double *)ensure(ws_pack_, ws_pack_sz_, sizeof(double) * (size_t)nkb * RB * 64);
@@ -482,6 +496,159 @@ class HipOps : public Ops {
       else
         rank_stream<double, 1>(v, M, K, Q, P, R, out);
     }
+  }
+  // ---- the influence plot: the residual's pass keeping its row and column sums (ops.h, residual_slices)
+  // The walk in slabs both routes share. The pass geometry — n_tiles row tiles of rpt rows by nchunk k-chunks of
+  // cpc columns — is fixed by the shape alone; the cap only cuts it into slabs of nt tiles x nc chunks whose
+  // partial sums (8 (nt min(K, nc cpc) + nc nt rpt) bytes, and 1/G of the row part again) fit: whole row tiles
+  // while one fits, otherwise one tile's chunks, in multiples of the row fold's group G. k_slice_group and
+  // k_slice_fold add every slab's partials onto rowsq / colsq in an order of the geometry alone, so the cap
+  // changes no bit. launch(tile0, nt, chunk0, nc, rp_ld, cp_ld, rowpart, colpart) runs the pass of one slab;
+  // each is bracketed in the launch profile with the bytes of its part of the tensor.
+  template <typename F>
+  void slice_slabs(int64_t M, int64_t K, int64_t n_tiles, int64_t rpt, int64_t nchunk, int64_t cpc, size_t elem,
+                   size_t cap, void *&work, size_t &work_bytes, double *rowsq, double *colsq, double *total,
+                   F &&launch) {
+    const int64_t G = (nchunk + 63) / 64;  // chunks per group of the row fold (kernels_slices.hip.h)
+    const int nparts = (int)std::min<int64_t>(1024, (K + 8191) / 8192);  // of the two-level total
+    const int64_t words = (int64_t)(cap / sizeof(double)) - nparts, one = K + (nchunk + (G > 1 ? 64 : 0)) * rpt;
+    int64_t nt = 1, nc = nchunk;
+    if (one <= words)
+      nt = std::min(n_tiles, words / one);
+    else
+      nc = std::min(nchunk, std::max<int64_t>(1, words / ((cpc + 2 * rpt) * G)) * G);
+    const int64_t rp_ld = std::min(M, nt * rpt), cp_ld = std::min(K, nc * cpc), ngs = G > 1 ? (nc + G - 1) / G : 0;
+    const int64_t seg = (K + nparts - 1) / nparts;
+    const size_t need = sizeof(double) * (size_t)((nc + ngs) * rp_ld + nt * cp_ld + nparts);
+    if (need > work_bytes) {  // (the caller's buffer, exactly what is needed: it is held to a cap)
+      free(work);
+      work = nullptr;
+      work_bytes = 0;
+      work = alloc(need);
+      work_bytes = need;
+    }
+    double *rowpart = (double *)work;
+    double *colpart = rowpart + nc * rp_ld, *grp = colpart + nt * cp_ld, *parts = grp + ngs * rp_ld;
+    route("slices_slabs:%lldx%lld", (long long)((n_tiles + nt - 1) / nt), (long long)((nchunk + nc - 1) / nc));
+    for (int64_t t0 = 0; t0 < n_tiles; t0 += nt)
+      for (int64_t c0 = 0; c0 < nchunk; c0 += nc) {
+        const int64_t ntc = std::min(nt, n_tiles - t0), ncc = std::min(nc, nchunk - c0);
+        const int64_t row0 = t0 * rpt, rows = std::min(M - row0, ntc * rpt);
+        const int64_t kc0 = c0 * cpc, kcols = std::min(K - kc0, ncc * cpc);
+        prof_begin(1, (double)rows * (double)kcols * elem);
+        launch(t0, ntc, c0, ncc, rp_ld, cp_ld, rowpart, colpart);
+        prof_end();
+        HIP_CHECK(hipGetLastError());
+        const int64_t ngc = (ncc + G - 1) / G;
+        if (G > 1)
+          hipLaunchKernelGGL(k_slice_group, dim3(grid_for(ngc * rows, 256)), dim3(256), 0, st_, rowpart, ncc, G, rp_ld,
+                             rows, grp);
+        hipLaunchKernelGGL(k_slice_fold, dim3(grid_for(rows + kcols, 256)), dim3(256), 0, st_, G > 1 ? grp : rowpart,
+                           G > 1 ? ngc : ncc, rp_ld, rows, row0, c0 == 0 ? 1 : 0, colpart, ntc, cp_ld, kcols, kc0,
+                           t0 == 0 ? 1 : 0, rowsq, colsq);
+        HIP_CHECK(hipGetLastError());
+      }
+    hipLaunchKernelGGL(k_slice_total_parts, dim3(nparts), dim3(256), 0, st_, colsq, K, seg, parts);
+    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(1024), 0, st_, parts, nparts, total);
+    HIP_CHECK(hipGetLastError());
+  }
+  // the fused route: MODE 3 of k_rank_mfma, on the shapes and with the geometry, the packed P and the REM
+  // remainder of the residual (rank_plan); false: shape not covered
+  template <typename TV>
+  bool slices_mfma(const void *V, int64_t M, int64_t K, const double *Q, const double *P, int R, double *rowsq,
+                   double *colsq, double *total, size_t cap, void *&work, size_t &wb) {
+    constexpr int VEC = ScanTraits<TV>::VEC;
+    RankPlan pl;
+    if (!rank_plan<TV>(3, V, M, K, R, pl)) return false;
+    const int RB = pl.RB, rem = pl.rem, per = pl.per, nkb = pl.nkb;
+    double *Ppk = (double *)ensure(ws_pack_, ws_pack_sz_, sizeof(double) * (size_t)nkb * RB * 64);
+    hipLaunchKernelGGL(k_rank_pack, dim3(grid_for((int64_t)nkb * RB * 64, 256)), dim3(256), 0, st_, P, K, R - rem, RB,
+                       nkb, Ppk);
+    const size_t lds_rem = sizeof(double) * (size_t)per * 16 * rem;
+    route("slices_mfma:%s,R%d,RB%d,rem%d,tiles%lld,chunks%d", tname<TV>(), R, RB, rem, (long long)pl.n_mtiles,
+          pl.nchunk);
+    slice_slabs(M, K, pl.n_mtiles, 64 * VEC, pl.nchunk, (int64_t)per * 16, sizeof(TV), cap, work, wb, rowsq, colsq, total,
+                [&](int64_t t0, int64_t nt, int64_t c0, int64_t nc, int64_t rp_ld, int64_t cp_ld, double *rowpart,
+                    double *colpart) {
+                  const dim3 grid((unsigned)nt, (unsigned)nc);
+                  auto go = [&](auto mrb, auto rm) {
+                    hipLaunchKernelGGL((k_rank_mfma<TV, 3, mrb, rm>), grid, dim3(256), lds_rem, st_, (TV *)V, M, K, Q,
+                                       Ppk, R, RB, per, nkb, rowpart, P, colpart, (int)t0, (int)c0, rp_ld, cp_ld);
+                  };
+                  std::integral_constant<int, 0> none{};
+                  if (rem && RB <= 2)
+                    dispatch<1, 2>(rem, [&](auto rm) { go(std::integral_constant<int, 2>(), rm); });
+                  else if (rem)
+                    go(std::integral_constant<int, 4>(), std::integral_constant<int, 1>());
+                  else if (RB <= 3)
+                    go(std::integral_constant<int, 3>(), none);
+                  else if (RB <= 4)
+                    go(std::integral_constant<int, 4>(), none);
+                  else
+                    go(std::integral_constant<int, 8>(), none);
+                });
+    return true;
+  }
+  // the general route (k_slice_stream): 256-row tiles, enough k-chunks to fill the chip
+  template <typename TV>
+  void slices_stream(const void *V, int64_t M, int64_t K, const double *Q, const double *P, int R, double *rowsq,
+                     double *colsq, double *total, size_t cap, void *&work, size_t &wb) {
+    const int64_t n_tiles = (M + 255) / 256;
+    const int64_t want = std::min<int64_t>((K + kSliceCols - 1) / kSliceCols,
+                                           std::max<int64_t>(1, ((int64_t)ncu_ * 8 + n_tiles - 1) / n_tiles));
+    const KSplit ks = k_split(K, want, 1, kSliceCols);
+    const int64_t kch = ks.per, nchunk = ks.nsplit;
+    route("slices_stream:%s,R%d,tiles%lld,chunks%lld", std::is_same<TV, bf16s>::value ? "bf16" : tname<TV>(), R,
+          (long long)n_tiles, (long long)nchunk);
+    slice_slabs(M, K, n_tiles, 256, nchunk, kch, sizeof(TV), cap, work, wb, rowsq, colsq, total,
+                [&](int64_t t0, int64_t nt, int64_t c0, int64_t nc, int64_t rp_ld, int64_t cp_ld, double *rowpart,
+                    double *colpart) {
+                  const dim3 grid((unsigned)nt, (unsigned)nc);  // (nc <= 8 x the compute units)
+                  auto go = [&](auto rb) {
+                    hipLaunchKernelGGL((k_slice_stream<TV, rb>), grid, dim3(256), 0, st_, (const TV *)V, M, K, Q, P, R,
+                                       kch, t0, c0, rp_ld, cp_ld, rowpart, colpart);
+                  };
+                  if (R <= 16)
+                    go(std::integral_constant<int, 16>());
+                  else if (R <= 64)
+                    go(std::integral_constant<int, 64>());
+                  else
+                    go(std::integral_constant<int, 0>());
+                });
+  }
+  template <typename TV>
+  void slices_any(const void *V, int64_t M, int64_t K, const double *Q, const double *P, int R, double *rowsq,
+                  double *colsq, double *total, size_t cap, void *&work, size_t &wb) {
+    if constexpr (!std::is_same<TV, bf16s>::value)
+      if (slices_mfma<TV>(V, M, K, Q, P, R, rowsq, colsq, total, cap, work, wb)) return;
+    slices_stream<TV>(V, M, K, Q, P, R, rowsq, colsq, total, cap, work, wb);
+  }
+  void residual_slices(const void *V, int dt, int64_t M, int64_t K, const double *Q, const double *P, int R,
+                       double *rowsq, double *colsq, double *total, size_t work_cap_bytes, void *&work,
+                       size_t &work_bytes) override {
+    RoctxRange roctx_("residual stream with slice sums");
+    if (M < 1 || K < 1 || R < 1) throw std::runtime_error("ppals: residual_slices needs M, K, R >= 1");
+    if (dt == F32)
+      slices_any<float>(V, M, K, Q, P, R, rowsq, colsq, total, work_cap_bytes, work, work_bytes);
+    else if (dt == BF16)
+      slices_any<bf16s>(V, M, K, Q, P, R, rowsq, colsq, total, work_cap_bytes, work, work_bytes);
+    else
+      slices_any<double>(V, M, K, Q, P, R, rowsq, colsq, total, work_cap_bytes, work, work_bytes);
+  }
+  void fold_slice_sums(const double *src, const int64_t *lens, int n, double *out) override {
+    if (n < 1 || n > MAX_ORDER) throw std::runtime_error("ppals: fold_slice_sums order out of range");
+    SliceFoldArgs a;
+    int64_t nout = 0;
+    a.n = n;
+    for (int j = 0; j < n; j++) nout += (a.lens[j] = lens[j]);
+    if (nout > 0x7fffffff) throw std::runtime_error("ppals: fold_slice_sums: too many slices");
+    route("fold_slice_sums:n%d", n);
+    hipLaunchKernelGGL(k_fold_slice_sums, dim3((unsigned)nout), dim3(256), 0, st_, src, a, out);
+    HIP_CHECK(hipGetLastError());
+  }
+  void row_dots(const double *P, const double *W, int64_t rows, int R, int64_t ld, double *out) override {
+    hipLaunchKernelGGL(k_row_dots, dim3(grid_for(rows, 256)), dim3(256), 0, st_, P, W, rows, R, ld, out);
+    HIP_CHECK(hipGetLastError());
   }
   void upload_shard(void *V, int dt, const double *host_full, int64_t l0, int64_t g0,
                     int64_t row0, int64_t rest) override {

@@ -1119,6 +1119,8 @@ __global__ __launch_bounds__(256) void k_scan_prefix_fast(
 //   MODE 0  V = vhat                      (build_V, common.cxx:135-197)
 //   MODE 1  partial[wg] = sum (V - vhat)^2   (als_CP.cxx:183-187)
 //   MODE 2  partial[wg] = sum V^2
+//   MODE 3  the residual's pass keeping its row and column sums (Ops::residual_slices; layout of the two
+//           partial arrays: kernels_slices.hip.h), below
 // The model tile comes off the matrix cores in fp64 (v_mfma_f64_16x16x4_f64, contraction over r):
 // fp32 products would carry ~1e-7 of |vhat| and drown a converged residual (~3e-8 of |V| with fp32
 // tensor storage). Tiling = the suffix scan's: a workgroup covers 256 consecutive rows (1 KiB of
@@ -1135,27 +1137,45 @@ __global__ __launch_bounds__(256) void k_scan_prefix_fast(
 // multiply-adds per element on the vector pipe, their P columns waiting in LDS (16 * kb_per_chunk * REM
 // doubles of dynamic LDS), their Q columns in registers: R = 10 is two steps + two ranks instead of three
 // steps (the matrix pipe 0.57 ms instead of 0.86 ms per 6.4 GB). RB counts the matrix-core steps only.
+// MODE 3 is MODE 1 that throws nothing away. A lane owns VEC fixed rows for its whole walk: their sums of e^2 are
+// VEC registers, added over the four 16-lane groups (the lanes j16 + 16 g hold the same rows) at the end and
+// written to partial[chunk][row]. Per column block the lane holds e^2 of its VEC rows for the four columns
+// 16 kb + 4 u + g: the four values go over the 16 lanes of the group by a butterfly that HALVES what travels
+// (xor 8: two values each way, xor 4: one, then xor 2 and xor 1 on the one left — 5 shuffles instead of 16),
+// leaving column u = 2 (bit 3) + (bit 2) of j16 in the lane; a wave parks its 16 column sums of the block in
+// LDS, and every kSliceFlush blocks the four waves' sums are added in wave order and stored to
+// colpart[row tile][column] (two barriers per kSliceFlush blocks; a wave beyond M parks zeros and keeps
+// walking for them). Clamped columns (k >= K) and rows contribute zero and are not stored. The grid is one
+// SLAB of the geometry: row tile tile0 + blockIdx.x, k-chunk chunk0 + blockIdx.y.
+constexpr int kSliceFlush = 8;
+__device__ inline double *slice_col_lds() {
+  __shared__ double cs[4 * kSliceFlush * 16];  // [wave][block since the last flush][column of the block]
+  return cs;
+}
 template <typename TV, int MODE, int MAXRB, int REM = 0>
 __global__ __launch_bounds__(256) void k_rank_mfma(TV *__restrict__ V, int64_t M, int64_t K,
                                                    const double *__restrict__ Q,
                                                    const double *__restrict__ Ppk, int R, int RB,
                                                    int kb_per_chunk, int nkb,
                                                    double *__restrict__ partial,
-                                                   const double *__restrict__ Praw = nullptr) {
+                                                   const double *__restrict__ Praw = nullptr,
+                                                   double *__restrict__ colpart = nullptr, int tile0 = 0,
+                                                   int chunk0 = 0, int64_t rp_ld = 0, int64_t cp_ld = 0) {
   typedef ScanTraits<TV> TR;
   typedef typename TR::vec vec;
   constexpr int VEC = TR::VEC;  // MAXRB: 4-wide contraction steps held in registers (R <= 4*MAXRB)
-  static_assert(REM == 0 || MODE == 1, "the vector-pipe remainder belongs to the residual");
+  constexpr bool SLICES = MODE == 3;
+  static_assert(REM == 0 || MODE == 1 || SLICES, "the vector-pipe remainder belongs to the residual");
   __shared__ double red[4];
   extern __shared__ double rank_ps[];  // REM > 0: P[k, R - REM + t] at [(k - 16 kb0) * REM + t]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = lane >> 4, j16 = lane & 15;
-  const int64_t m0 = ((int64_t)blockIdx.x * 4 + wave) * (16 * VEC);
+  const int64_t m0 = ((int64_t)(blockIdx.x + (SLICES ? tile0 : 0)) * 4 + wave) * (16 * VEC);
   const bool live = m0 < M;  // wave-uniform
   const int64_t m = m0 + (int64_t)VEC * j16;
   const bool row_ok = live && m < M;
   const int64_t m_ld = live ? min(m, M - VEC) : 0;
-  const int kb0 = blockIdx.y * kb_per_chunk, kb1 = min(nkb, kb0 + kb_per_chunk);
+  const int kb0 = (blockIdx.y + (SLICES ? chunk0 : 0)) * kb_per_chunk, kb1 = min(nkb, kb0 + kb_per_chunk);
   double bq[VEC][MAXRB];
   if constexpr (MODE != 2) {
 #pragma unroll
@@ -1179,6 +1199,11 @@ __global__ __launch_bounds__(256) void k_rank_mfma(TV *__restrict__ V, int64_t M
     __syncthreads();
   }
   double acc = 0.0;
+  [[maybe_unused]] double rsum[SLICES ? VEC : 1];  // MODE 3: e^2 of the lane's rows, summed over its columns
+  if constexpr (SLICES) {
+#pragma unroll
+    for (int jj = 0; jj < VEC; jj++) rsum[jj] = 0.0;
+  }
   TV *__restrict__ vp = V + m_ld;
   // register double buffer: the tensor columns and the packed P values of block kb+1 are
   // requested before block kb is multiplied (the last block is simply requested twice)
@@ -1198,7 +1223,75 @@ __global__ __launch_bounds__(256) void k_rank_mfma(TV *__restrict__ V, int64_t M
     }                                                                                         \
   }
   if (live && kb0 < kb1) PPALS_RANK_LOAD(kb0, cv, ca);
-  for (int kb = kb0; kb < kb1 && live; kb++) {
+  for (int kb = kb0; kb < kb1 && (SLICES || live); kb++) {
+    if constexpr (SLICES) {
+      double *cs = slice_col_lds() + (wave * kSliceFlush + (kb - kb0) % kSliceFlush) * 16;
+      if (!live) {  // (wave-uniform) nothing to add, but the flush below reads this wave's slots
+        if (lane < 16) cs[lane] = 0.0;
+      } else {
+        vec nv[4];
+        double na[MAXRB];
+        const int kn = min(kb + 1, kb1 - 1);
+        PPALS_RANK_LOAD(kn, nv, na);
+        double c[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int jp = 0; jp < VEC; jp += 2) {
+          f64x4 d0 = f64x4{0.0, 0.0, 0.0, 0.0}, d1 = d0;
+#pragma unroll
+          for (int rb = 0; rb < MAXRB; rb++) {
+            if (rb < RB) {
+              d0 = __builtin_amdgcn_mfma_f64_16x16x4f64(ca[rb], bq[jp][rb], d0, 0, 0, 0);
+              d1 = __builtin_amdgcn_mfma_f64_16x16x4f64(ca[rb], bq[jp + 1][rb], d1, 0, 0, 0);
+            }
+          }
+#pragma unroll
+          for (int u = 0; u < 4; u++) {
+            const int64_t k = (int64_t)kb * 16 + 4 * u + g;
+            const bool ok = k < K && row_ok;  // beyond K the loads were clamped: excluded here
+            double e0 = (double)cv[u][jp] - d0[u], e1 = (double)cv[u][jp + 1] - d1[u];
+            if constexpr (REM > 0) {
+#pragma unroll
+              for (int t = 0; t < REM; t++) {
+                const double pk = rank_ps[((kb - kb0) * 16 + 4 * u + g) * REM + t];
+                e0 -= qrem[jp][t] * pk;
+                e1 -= qrem[jp + 1][t] * pk;
+              }
+            }
+            e0 = ok ? e0 * e0 : 0.0;
+            e1 = ok ? e1 * e1 : 0.0;
+            rsum[jp] += e0;
+            rsum[jp + 1] += e1;
+            c[u] += e0 + e1;
+          }
+        }
+        // the butterfly over the 16 lanes of the group: first the half of the values that is not the lane's
+        const bool hi = (j16 & 8) != 0, mid = (j16 & 4) != 0;
+        const double keep0 = (hi ? c[2] : c[0]) + __shfl_xor(hi ? c[0] : c[2], 8, 64);
+        const double keep1 = (hi ? c[3] : c[1]) + __shfl_xor(hi ? c[1] : c[3], 8, 64);
+        double col = (mid ? keep1 : keep0) + __shfl_xor(mid ? keep0 : keep1, 4, 64);
+        col += __shfl_xor(col, 2, 64);
+        col += __shfl_xor(col, 1, 64);
+        if ((j16 & 3) == 0) cs[4 * (2 * (int)hi + (int)mid) + g] = col;
+#pragma unroll
+        for (int u = 0; u < 4; u++) cv[u] = nv[u];
+#pragma unroll
+        for (int rb = 0; rb < MAXRB; rb++) ca[rb] = na[rb];
+      }
+      const int nb = (kb - kb0) % kSliceFlush + 1;  // blocks parked since the last flush
+      if (nb == kSliceFlush || kb == kb1 - 1) {     // (uniform over the workgroup)
+        __syncthreads();
+        const double *all = slice_col_lds();
+        const int kbf = kb - (nb - 1);
+        for (int e = threadIdx.x; e < nb * 16; e += blockDim.x) {
+          const int64_t k = (int64_t)kbf * 16 + e;
+          if (k < K)
+            colpart[(int64_t)blockIdx.x * cp_ld + (k - (int64_t)chunk0 * kb_per_chunk * 16)] =
+                ((all[e] + all[kSliceFlush * 16 + e]) + all[2 * kSliceFlush * 16 + e]) + all[3 * kSliceFlush * 16 + e];
+        }
+        __syncthreads();
+      }
+      continue;
+    }
     vec nv[4];
     double na[MAXRB];
     const int kn = min(kb + 1, kb1 - 1);
@@ -1264,7 +1357,16 @@ __global__ __launch_bounds__(256) void k_rank_mfma(TV *__restrict__ V, int64_t M
     for (int rb = 0; rb < MAXRB; rb++) ca[rb] = na[rb];
   }
 #undef PPALS_RANK_LOAD
-  if constexpr (MODE != 0) {
+  if constexpr (SLICES) {
+#pragma unroll
+    for (int jj = 0; jj < VEC; jj++) {
+      double v = rsum[jj];
+      v += __shfl_xor(v, 16, 64);
+      v += __shfl_xor(v, 32, 64);
+      if (g == 0 && row_ok) partial[(int64_t)blockIdx.y * rp_ld + (m - (int64_t)tile0 * (64 * VEC)) + jj] = v;
+    }
+  }
+  if constexpr (MODE == 1 || MODE == 2) {
     acc = [&]() {
       double v = acc;
 #pragma unroll

@@ -623,6 +623,79 @@ class Ops {
     h2d(wa, na.data(), sizeof(double) * Ca);
     h2d(wb, nb.data(), sizeof(double) * Cb);
   }
+  // ---- per-slice residuals and leverages (CpEngine::slice_residuals / leverages; include/ppals.h) ----
+  // The contract of residual_sq (Q != nullptr) with two more outputs, from ONE pass over V: with
+  // e[m,k] = V[m,k] - sum_r Q[m,r] P[k,r] (V as stored, everything else fp64)
+  //   rowsq[m] = sum_k e^2,  colsq[k] = sum_m e^2,  *total = sum_k colsq[k]     (device, fp64)
+  // The same inputs give the same bits: no atomics, partial sums added in a fixed order. A back end's
+  // partial sums live in the CALLER's grow-only buffer `work` of `work_bytes` bytes (nullptr / 0 at first): the
+  // op frees and allocates it anew (free / alloc of this Ops) when it needs more, the caller keeps it for the
+  // next call and frees it in the end. It stays within work_cap_bytes — or what one row tile by one group of
+  // k-chunks needs, if that is more — by walking the pass in slabs; the cap changes no bit of the result.
+  // This default is the fp64 twin of the product's kernels on the host (it needs no partial sums, leaves
+  // `work` alone and ignores the cap), as with cp_pinv_ragged; the product back end overrides it.
+  virtual void residual_slices(const void *V, int dt, int64_t M, int64_t K, const double *Q, const double *P,
+                               int R, double *rowsq, double *colsq, double *total, size_t /*work_cap_bytes*/,
+                               void *& /*work*/, size_t & /*work_bytes*/) {
+    std::vector<char> raw((size_t)M * K * dtype_size(dt));
+    std::vector<double> q((size_t)M * R), p((size_t)K * R), rs((size_t)M, 0.0), cs((size_t)K, 0.0);
+    d2h(raw.data(), V, raw.size());
+    d2h(q.data(), Q, sizeof(double) * q.size());
+    d2h(p.data(), P, sizeof(double) * p.size());
+    double tot = 0;
+    for (int64_t k = 0; k < K; k++) {
+      double c = 0;
+      for (int64_t m = 0; m < M; m++) {
+        const size_t e = (size_t)(m + M * k);
+        double v = 0;
+        for (int r = 0; r < R; r++) v += q[(size_t)(m + M * r)] * p[(size_t)(k + K * r)];
+        const double x = dt == F32    ? (double)((const float *)raw.data())[e]
+                         : dt == BF16 ? (double)bf16_bits_to_float(((const uint16_t *)raw.data())[e])
+                                      : ((const double *)raw.data())[e];
+        const double d = x - v;
+        rs[(size_t)m] += d * d;
+        c += d * d;
+      }
+      cs[(size_t)k] = c;
+      tot += c;
+    }
+    h2d(rowsq, rs.data(), sizeof(double) * rs.size());
+    h2d(colsq, cs.data(), sizeof(double) * cs.size());
+    h2d(total, &tot, sizeof(double));
+  }
+  // A vector indexed by a flattened group of n modes (extents lens[0..n), the first listed fastest; device,
+  // fp64) marginalised onto each of them: out = the n per-mode vectors one after the other,
+  //   out_j[x] = sum of src[e] over every e whose j-th index is x,
+  // in a fixed order. (the default: the host twin, in ascending e)
+  virtual void fold_slice_sums(const double *src, const int64_t *lens, int n, double *out) {
+    int64_t total = 1, nout = 0;
+    for (int j = 0; j < n; j++) {
+      total *= lens[j];
+      nout += lens[j];
+    }
+    std::vector<double> s((size_t)total), o((size_t)nout, 0.0);
+    d2h(s.data(), src, sizeof(double) * s.size());
+    for (int64_t e = 0; e < total; e++) {
+      int64_t rem = e, off = 0;
+      for (int j = 0; j < n; j++) {
+        o[(size_t)(off + rem % lens[j])] += s[(size_t)e];
+        rem /= lens[j];
+        off += lens[j];
+      }
+    }
+    h2d(out, o.data(), sizeof(double) * o.size());
+  }
+  // out[x] = sum_r P[x + ld r] W[x + ld r], x < rows, r ascending (device, fp64): with P = W G^-1 the
+  // leverages diag(W G^-1 W^T). (the default: the host twin)
+  virtual void row_dots(const double *P, const double *W, int64_t rows, int R, int64_t ld, double *out) {
+    const size_t n = (size_t)ld * (R - 1) + (size_t)rows;
+    std::vector<double> p(n), w(n), o((size_t)rows, 0.0);
+    d2h(p.data(), P, sizeof(double) * n);
+    d2h(w.data(), W, sizeof(double) * n);
+    for (int r = 0; r < R; r++)
+      for (int64_t x = 0; x < rows; x++) o[(size_t)x] += p[(size_t)(x + ld * r)] * w[(size_t)(x + ld * r)];
+    h2d(out, o.data(), sizeof(double) * o.size());
+  }
   // Where the next scan_contract calls are booked in the launch profile: 0 the tensor scans (the default),
   // 1 the other kernels — for a scan of something that is not the tensor.
   virtual void scan_profile_slot(int /*slot*/) {}

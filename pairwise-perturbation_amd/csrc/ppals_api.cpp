@@ -978,6 +978,44 @@ int ppals_cp_multi_fms_between(ppals_cp_multi *a, ppals_cp_multi *b, int skip_mo
   API_END(PPALS_ERR_HIP)
 }
 
+// ------------------------------------------------------------------ influence plot
+// the refusals of the two calls, before anything is launched or allocated
+static int check_influence(ppals_cp *s, const void *out, const char *fn, const char *outname, bool pinv) {
+  char msg[192];
+  if (!s || !s->eng) {
+    std::snprintf(msg, sizeof(msg), "%s: NULL session", fn);
+    return fail(PPALS_ERR_ARG, msg);
+  }
+  if (!out) {
+    std::snprintf(msg, sizeof(msg), "%s: %s is NULL", fn, outname);
+    return fail(PPALS_ERR_ARG, msg);
+  }
+  if (s->ctx->c().size() > 1) {
+    std::snprintf(msg, sizeof(msg), "%s: the influence plot runs on one rank (no sharded form)", fn);
+    return fail(PPALS_ERR_UNSUPPORTED, msg);
+  }
+  if (pinv && s->eng->rank_r() > Ops::kPinvMaxRank) {
+    std::snprintf(msg, sizeof(msg), "%s: rank %d is above 64, the largest the pseudo-inverse factors take", fn,
+                  s->eng->rank_r());
+    return fail(PPALS_ERR_UNSUPPORTED, msg);
+  }
+  return PPALS_OK;
+}
+int ppals_cp_slice_residuals(ppals_cp *s, double *ss, double *total) {
+  if (int rc = check_influence(s, ss, "ppals_cp_slice_residuals", "ss", false)) return rc;
+  API_BEGIN
+  s->eng->slice_residuals(ss, total);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_cp_leverages(ppals_cp *s, double *lev) {
+  if (int rc = check_influence(s, lev, "ppals_cp_leverages", "lev", true)) return rc;
+  API_BEGIN
+  s->eng->leverages(lev);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+
 // ------------------------------------------------------------------ Tucker
 int ppals_tucker_create(ppals_ctx *ctx, ppals_tensor *V, const int *ranks, ppals_tucker **out) {
   if (!ctx || !V || !ranks || !out) return fail(PPALS_ERR_ARG, "NULL argument");

@@ -69,6 +69,7 @@ EXPORTS = [
     "ppals_tucker_impute_device", "ppals_tucker_em",
     "ppals_match_columns", "ppals_cp_congruence", "ppals_cp_fms", "ppals_cp_multi_congruence",
     "ppals_cp_multi_fms", "ppals_cp_multi_fms_between",
+    "ppals_cp_slice_residuals", "ppals_cp_leverages",
 ]
 MODEL, RESIDUAL = 0, 1  # PPALS_MODEL / PPALS_RESIDUAL
 FMS_WEIGHTS = 1  # PPALS_FMS_WEIGHTS
@@ -568,6 +569,29 @@ class CP(_ModelExport, _Impute):
         _check(lib().ppals_cp_fms(self._h, other._h, _skip(skip_mode), FMS_WEIGHTS if weights else 0,
                                   C.byref(out), perm if return_perm else None))
         return (out.value, np.array(perm[:], dtype=np.int64)) if return_perm else out.value
+
+    def _per_mode(self, flat_vec):
+        cuts = np.cumsum(self.lens)[:-1]
+        return [v.copy() for v in np.split(flat_vec, cuts)]
+
+    def slice_residuals(self, return_total=False):
+        """the residual side of the influence plot (ppals_cp_slice_residuals): a list of N vectors, entry x
+        of vector i the sum of (V - model)^2 over the slice x of mode i — one pass over the tensor, nothing
+        materialised. return_total: (list, total), total = residual()**2 up to rounding. Reads the session
+        and changes nothing of it."""
+        out = np.empty(sum(self.lens))
+        total = C.c_double(0)
+        _check(lib().ppals_cp_slice_residuals(self._h, _dp(out), C.byref(total)))
+        ss = self._per_mode(out)
+        return (ss, total.value) if return_total else ss
+
+    def leverages(self):
+        """the leverage side (ppals_cp_leverages): a list of N vectors, entry x of vector i the x-th diagonal
+        entry of the projector onto the columns of W_i; all NaN when a factor has no pseudo-inverse. Never
+        reads the tensor."""
+        out = np.empty(sum(self.lens))
+        _check(lib().ppals_cp_leverages(self._h, _dp(out)))
+        return self._per_mode(out)
 
     def tree_node(self, key, shape=None):
         n = C.c_int64(0)
