@@ -360,6 +360,9 @@ class HipOps : public Ops {
     if (MODE != 0) part = (double *)ensure(ws_part_, ws_part_sz_, npart * sizeof(double));
     prof_begin(1, (double)M * K * sizeof(TV));
     const size_t lds_rem = sizeof(double) * (size_t)per * 16 * rem;
+    const bool remk = MODE == 1 && rem != 0;  // the instantiation chosen below
+    route("rank.mfma mode=%d dt=%s R=%d maxrb=%d rem=%d tiles=%lld chunks=%d per=%d", MODE, sname<TV>(), R,
+          remk ? (RB <= 2 ? 2 : 4) : RB <= 3 ? 3 : RB <= 4 ? 4 : 8, remk ? rem : 0, (long long)n_mtiles, nchunk, per);
     bool done = false;
     if constexpr (MODE == 1) {
       if (rem) {
@@ -417,6 +420,8 @@ class HipOps : public Ops {
     double *part = MODE == 1 ? (double *)ensure(ws_part_, ws_part_sz_, npart * sizeof(double)) : nullptr;
     prof_begin(1, (double)M * K * sizeof(TV));
     const int rbw = (RB + 3) / 4;
+    route("rank.split mode=%d dt=%s R=%d maxrbw=%d tiles=%lld chunks=%d per=%d", MODE, sname<TV>(), R,
+          rbw <= 4 ? 4 : rbw <= 8 ? 8 : 16, (long long)n_mtiles, nchunk, per);
     if (rbw <= 4)
       hipLaunchKernelGGL((k_rank_split<TV, MODE, 4>), grid, dim3(256), 0, st_, (TV *)V, M, K, Q, Ppk, R,
                          RB, per, nkb, part);
@@ -450,6 +455,8 @@ class HipOps : public Ops {
     int64_t npart = (int64_t)grid.x * grid.y;
     if (MODE != 0) part = (double *)ensure(ws_part_, ws_part_sz_, npart * sizeof(double));
     TV *v = (TV *)V;
+    route("rank.stream mode=%d dt=%s R=%d rb=%d kch=%d", MODE, sname<TV>(), R,
+          R > 64 ? 0 : R <= 16 ? 16 : R <= 32 ? 32 : 64, kch);
     if (R > 64)
       hipLaunchKernelGGL((k_rank_stream_any<TV, MODE>), grid, dim3(256), 0, st_, v, M, K, Q, P, R,
                          kch, part);
@@ -3965,6 +3972,10 @@ class HipOps : public Ops {
   template <typename T>
   static constexpr const char *tname() {
     return sizeof(T) == 8 ? "f64" : "f32";
+  }
+  template <typename T>
+  static constexpr const char *sname() {  // the storage type of a tensor, bf16 included
+    return std::is_same<T, bf16s>::value ? "bf16" : tname<T>();
   }
 
   // Where a pass of nsplit k-splits writes its ncols x M result (T batches): the output o itself, or

@@ -807,7 +807,8 @@ class Ops {
   // Route log (tests): when set, the product back end appends one short tag per kernel decision of
   // the contraction launchers (tensor scans, mttv, the thin-GEMM mode products, pp_correct) and of the
   // launchers of the R x R side (mode updates, cp_update, gram_system, Normalize) and of the Tucker
-  // eigen side (unfold_gram, top_eigvecs(_warm), eig_verify, orthonormalize, rows_times_small) — the
+  // eigen side (unfold_gram, top_eigvecs(_warm), eig_verify, orthonormalize, rows_times_small) and of
+  // the rank-structured stream (fill_rank, residual_sq: rank.mfma / rank.split / rank.stream) — the
   // kernel family and the facts that chose it. Null: nothing is formatted. The host stand-in logs nothing.
   std::vector<std::string> *route_log = nullptr;
 };

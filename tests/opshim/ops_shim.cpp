@@ -1,9 +1,9 @@
 // ops_shim.cpp — TEST INFRASTRUCTURE: a C surface over ppals::Ops for the op-level tests of the
-// contraction kernels (tests/contraction_cases.py), of the mode-update side (tests/update_cases.py)
-// and of the Tucker eigen side (tests/tucker_ops_cases.py). One source, two libraries: linked
-// against the product's libppals.so it reaches the HIP kernels as compiled there, linked against
-// the host stand-in it reaches HostOps. No HIP code and no HIP calls here: every device action goes
-// through the Ops.
+// contraction kernels (tests/contraction_cases.py), of the mode-update side (tests/update_cases.py),
+// of the Tucker eigen side (tests/tucker_ops_cases.py) and of the tensor streams
+// (tests/stream_cases.py). One source, two libraries: linked against the product's libppals.so it
+// reaches the HIP kernels as compiled there, linked against the host stand-in it reaches HostOps. No
+// HIP code and no HIP calls here: every device action goes through the Ops.
 // Every function returns 0, or -1 after an exception whose text shim_error() then returns (the
 // launchers' own refusals — "padded rows inconsistent" — arrive that way).
 #include <cstring>
@@ -323,6 +323,66 @@ int shim_transpose2d(void *h, const void *src, int dt, int64_t rows, int64_t col
 int shim_transpose_batched(void *h, const void *src, int dt, int64_t rows, int64_t cols, int64_t batch, void *dst) {
   Shim *s = (Shim *)h;
   return guarded(s, [&] { s->ops->transpose_batched(src, dt, rows, cols, batch, dst); });
+}
+
+// ---- the tensor streams: generation, residual, layouts and shards (tests/stream_cases.py) ----
+int shim_fill_uniform(void *h, void *V, int dt, int64_t l0, int64_t g0, int64_t row0, int64_t rest, uint64_t seed,
+                      double lo, double hi) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->fill_uniform(V, dt, l0, g0, row0, rest, seed, lo, hi); });
+}
+int shim_fill_laplacian(void *h, void *V, int dt, int64_t l0, int64_t g0, int64_t row0, int64_t rest, int ndigits,
+                        int sdim) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->fill_laplacian(V, dt, l0, g0, row0, rest, ndigits, sdim); });
+}
+int shim_add_uniform_noise(void *h, void *V, int dt, int64_t l0, int64_t g0, int64_t row0, int64_t rest,
+                           uint64_t seed, double lo, double hi, double alpha) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->add_uniform_noise(V, dt, l0, g0, row0, rest, seed, lo, hi, alpha); });
+}
+int shim_uniform_sumsq(void *h, int64_t l0, int64_t g0, int64_t row0, int64_t rest, uint64_t seed, double lo,
+                       double hi, double *out) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->uniform_sumsq(l0, g0, row0, rest, seed, lo, hi, out); });
+}
+int shim_fill_rank(void *h, void *V, int dt, int64_t M, int64_t K, const double *Q, const double *P, int R) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->fill_rank(V, dt, M, K, Q, P, R); });
+}
+int shim_residual_sq(void *h, const void *V, int dt, int64_t M, int64_t K, const double *Q, const double *P, int R,
+                     double *out) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->residual_sq(V, dt, M, K, Q, P, R, out); });
+}
+// host_full: HOST memory, the full tensor (g0 x rest doubles)
+int shim_upload_shard(void *h, void *V, int dt, const double *host_full, int64_t l0, int64_t g0, int64_t row0,
+                      int64_t rest) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->upload_shard(V, dt, host_full, l0, g0, row0, rest); });
+}
+int shim_download_shard(void *h, const void *V, int dt, double *host_full, int64_t l0, int64_t g0, int64_t row0,
+                        int64_t rest) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->download_shard(V, dt, host_full, l0, g0, row0, rest); });
+}
+int shim_pad_layout(void *h, const void *src, int dt, int64_t rows, int64_t cols, int64_t blk, int64_t ld,
+                    void *dst) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->pad_layout(src, dt, rows, cols, blk, ld, dst); });
+}
+int shim_unpack_shards(void *h, const void *stage, int dt, int64_t s0, int64_t rest, int64_t blk, int P,
+                       int64_t chunk_bytes, void *full) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->unpack_shards(stage, dt, s0, rest, blk, P, chunk_bytes, full); });
+}
+int shim_krp(void *h, double *out, const double *const *fptr, const int64_t *frows, const int64_t *fld, int nf,
+             int col0, int ncols) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] {
+    const std::vector<FactorRef> f = factors(fptr, frows, fld, nf);
+    s->ops->krp(out, f.data(), nf, col0, ncols);
+  });
 }
 
 // the route log (ops.h): attach (on != 0) or detach, read as one newline-joined string, clear

@@ -13,7 +13,7 @@ DIR = os.path.join(ROOT, "tests", "opshim")
 F32, F64, BF16 = 0, 1, 3
 _libs = {}
 
-_P, _I64, _I, _U, _D = C.c_void_p, C.c_int64, C.c_int, C.c_uint, C.c_double
+_P, _I64, _I, _U, _D, _U64 = C.c_void_p, C.c_int64, C.c_int, C.c_uint, C.c_double, C.c_uint64
 _SIGS = {
     "shim_alloc": [_P, C.c_size_t, C.POINTER(_P)],
     "shim_free": [_P, _P],
@@ -70,6 +70,17 @@ _SIGS = {
     "shim_add_inplace": [_P, _P, _P, _I64],
     "shim_transpose2d": [_P, _P, _I, _I64, _I64, _P],
     "shim_transpose_batched": [_P, _P, _I, _I64, _I64, _I64, _P],
+    "shim_fill_uniform": [_P, _P, _I, _I64, _I64, _I64, _I64, _U64, _D, _D],
+    "shim_fill_laplacian": [_P, _P, _I, _I64, _I64, _I64, _I64, _I, _I],
+    "shim_add_uniform_noise": [_P, _P, _I, _I64, _I64, _I64, _I64, _U64, _D, _D, _D],
+    "shim_uniform_sumsq": [_P, _I64, _I64, _I64, _I64, _U64, _D, _D, _P],
+    "shim_fill_rank": [_P, _P, _I, _I64, _I64, _P, _P, _I],
+    "shim_residual_sq": [_P, _P, _I, _I64, _I64, _P, _P, _I, _P],
+    "shim_upload_shard": [_P, _P, _I, _P, _I64, _I64, _I64, _I64],
+    "shim_download_shard": [_P, _P, _I, _P, _I64, _I64, _I64, _I64],
+    "shim_pad_layout": [_P, _P, _I, _I64, _I64, _I64, _I64, _P],
+    "shim_unpack_shards": [_P, _P, _I, _I64, _I64, _I64, _I, _I64, _P],
+    "shim_krp": [_P, _P, C.POINTER(_P), C.POINTER(_I64), C.POINTER(_I64), _I, _I, _I],
 }
 
 
@@ -326,6 +337,43 @@ class Shim:
 
     def transpose_batched(self, src, dt, rows, cols, batch, dst):
         self._ck(self.lib.shim_transpose_batched(self.h, src, dt, rows, cols, batch, dst))
+
+    # ---- the tensor streams: generation, residual, layouts and shards (tests/stream_cases.py)
+    def fill_uniform(self, V, dt, l0, g0, row0, rest, seed, lo, hi):
+        self._ck(self.lib.shim_fill_uniform(self.h, V, dt, l0, g0, row0, rest, seed, lo, hi))
+
+    def fill_laplacian(self, V, dt, l0, g0, row0, rest, ndigits, s):
+        self._ck(self.lib.shim_fill_laplacian(self.h, V, dt, l0, g0, row0, rest, ndigits, s))
+
+    def add_uniform_noise(self, V, dt, l0, g0, row0, rest, seed, lo, hi, alpha):
+        self._ck(self.lib.shim_add_uniform_noise(self.h, V, dt, l0, g0, row0, rest, seed, lo, hi, alpha))
+
+    def uniform_sumsq(self, l0, g0, row0, rest, seed, lo, hi, out):
+        self._ck(self.lib.shim_uniform_sumsq(self.h, l0, g0, row0, rest, seed, lo, hi, out))
+
+    def fill_rank(self, V, dt, M, K, Q, P, R):
+        self._ck(self.lib.shim_fill_rank(self.h, V, dt, M, K, Q, P, R))
+
+    def residual_sq(self, V, dt, M, K, Q, P, R, out):
+        self._ck(self.lib.shim_residual_sq(self.h, V, dt, M, K, Q, P, R, out))
+
+    def upload_shard(self, V, dt, host_full, l0, g0, row0, rest):
+        """host_full: a contiguous float64 numpy array, the full tensor"""
+        assert host_full.dtype == np.float64 and host_full.flags.c_contiguous and host_full.size == g0 * rest
+        self._ck(self.lib.shim_upload_shard(self.h, V, dt, host_full.ctypes.data, l0, g0, row0, rest))
+
+    def download_shard(self, V, dt, host_full, l0, g0, row0, rest):
+        assert host_full.dtype == np.float64 and host_full.flags.c_contiguous and host_full.size == g0 * rest
+        self._ck(self.lib.shim_download_shard(self.h, V, dt, host_full.ctypes.data, l0, g0, row0, rest))
+
+    def pad_layout(self, src, dt, rows, cols, blk, ld, dst):
+        self._ck(self.lib.shim_pad_layout(self.h, src, dt, rows, cols, blk, ld, dst))
+
+    def unpack_shards(self, stage, dt, s0, rest, blk, P, chunk_bytes, full):
+        self._ck(self.lib.shim_unpack_shards(self.h, stage, dt, s0, rest, blk, P, chunk_bytes, full))
+
+    def krp(self, out, factors, col0, ncols):
+        self._ck(self.lib.shim_krp(self.h, out, *self._factors(factors), col0, ncols))
 
 
 def compute_units():
