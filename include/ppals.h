@@ -451,6 +451,51 @@ int ppals_cp_multi_fms_between(ppals_cp_multi *a, ppals_cp_multi *b, int skip_mo
 int ppals_cp_slice_residuals(ppals_cp *s, double *ss, double *total /* may be NULL */);
 int ppals_cp_leverages(ppals_cp *s, double *lev);
 
+/* ---- hold-out rows per start of a multi-start session (resampling over one mode: the jackknife of
+ * J. Riu, R. Bro, "Jack-knife technique for outlier detection and estimation of standard errors in PARAFAC
+ * models", Chemom. Intell. Lab. Syst. 65 (2003) 35-49; segmented leave-samples-out fits; no counterpart in
+ * the reference) ----
+ * A CP fit of the tensor with some slices of mode `mode` (the "samples") deleted is exactly the fit of the
+ * full tensor with the corresponding rows of W_mode held at zero: those rows drop out of every MTTKRP of the
+ * other modes and out of W_mode^T W_mode, and the rows of mode `mode` are updated independently of each
+ * other. So a multi-start session whose starts each hold out their own rows runs nstarts resampled fits on
+ * ONE set of tensor scans, with no reduced tensors and no second resident layouts of them.
+ *   keep[b * s_mode + x] (host, nstarts x s_mode bytes): 0 = start b holds sample x out, anything else = kept.
+ * With a hold-out set, start b evolves as an ordinary session of its rank does under ppals_cpd_als with
+ * PPALS_OPT_SIMPLE on the tensor without the held-out slices of `mode` (a non-negative session: as a
+ * non-negative one does); held-out rows of the factor and of the gradient read back as exactly 0 (they are
+ * exempt from PPALS_NN_FLOOR), so gradnorms are those of the reduced fits. One small launch follows the
+ * update of `mode`; a start that holds nothing out is not touched by it and keeps, bit for bit, what it
+ * has in a session without a hold-out. Tensor scans and their traffic do not change.
+ * ppals_cp_multi_heldout_scores: scores (s_mode x ranks[start] doubles, column-major) holds, for each held-out
+ * row, the row produced by the most recent update of `mode` — the least-squares projection of that sample on
+ * the model of the other modes at that moment, fitted without it (from the HALS row update in a non-negative
+ * session: >= PPALS_NN_FLOOR). Before any update it holds the rows the caller set: ppals_cp_multi_set_factors
+ * and ppals_cp_multi_set_holdout MOVE the held-out rows, as they are at that moment, from the factor into the
+ * scores. Rows of kept samples are 0.
+ * ppals_cp_multi_take_predicted is ppals_cp_multi_take with the sample-mode factor additionally carrying the
+ * scores in the held-out rows: bit for bit W + scores, the rows being disjoint. ppals_cp_slice_residuals on
+ * `dst` then gives, per sample, the fit of the kept samples and the prediction error of the held-out ones.
+ * ppals_cp_multi_take itself is unchanged (zero rows). ppals_cp_multi_residuals keeps its definition: the
+ * model has zero rows there, so a held-out slice x counts with the whole ||V_x||^2. Core consistency,
+ * congruence and the factor match score work unchanged: zero rows contribute nothing to the pseudo-inverse,
+ * so cc is that of the reduced tensor; across starts compare with skip_mode = mode. ppals_cp_multi_run stops
+ * on the LARGEST gradient norm over the starts, as for differing ranks: every start is a fit the caller wants.
+ * ppals_cp_multi_set_holdout with keep == NULL clears the hold-out (mode is ignored): the zero rows stay where
+ * they are until the next update of that mode. Setting it again replaces it; rows that an earlier hold-out
+ * left at zero are moved as the zeros they are. Cached contractions are dropped as by set_factors.
+ * ppals_cp_multi_get_holdout: *mode = the sample mode or -1; keep (may be NULL) receives the table when set.
+ * Hold-out in one mode only; multi-start sessions only (a one-start session is fine).
+ * Refused before anything is launched or allocated, the message starting with the function's name —
+ * PPALS_ERR_ARG: a NULL session, mode outside [0, N), a start with no kept row, start out of range, a NULL
+ * output, scores or take_predicted on a session without a hold-out, a dst that ppals_cp_multi_take refuses
+ * (NULL, another context, another tensor, another rank); PPALS_ERR_UNSUPPORTED: what ppals_cp_multi_take
+ * refuses so (a non-negative dst from an unconstrained session). */
+int ppals_cp_multi_set_holdout(ppals_cp_multi *s, int mode, const uint8_t *keep /* NULL: clear */);
+int ppals_cp_multi_get_holdout(const ppals_cp_multi *s, int *mode, uint8_t *keep /* may be NULL */);
+int ppals_cp_multi_heldout_scores(ppals_cp_multi *s, int start, double *scores);
+int ppals_cp_multi_take_predicted(ppals_cp_multi *s, int start, ppals_cp *dst);
+
 /* ---- Tucker sessions (als_Tucker.h) ---- */
 int ppals_tucker_create(ppals_ctx *ctx, ppals_tensor *V, const int *ranks, ppals_tucker **out);
 void ppals_tucker_destroy(ppals_tucker *s);

@@ -391,6 +391,8 @@ CpEngine::~CpEngine() {
   ops_.free(sl_work_.ptr);
   ops_.free(fms_out_.ptr);
   ops_.free(fms_work_.ptr);
+  ops_.free(hold_keep_dev_);
+  ops_.free(hold_scores_);
   ops_.free(Pbuf_);
   for (auto &l : lay_)
     if (l.owned) ops_.free(l.ptr);
@@ -753,9 +755,72 @@ void CpEngine::set_factors_start(int start, const double *Wflat, const double *g
       }
       ops_.h2d(gradsq_ + (size_t)i * K_ + b, &gsq, sizeof(double));
     }
+  if (hold_mode_ >= 0) {  // the caller's held-out rows of these starts move into the scores
+    unsigned sel = 0;
+    for (int b = b0; b < b1; b++) sel |= 1u << b;
+    hold_apply(sel);
+    if (!g) {  // (no gradients: the sums stay 0, whatever the gradient buffer still holds)
+      const double zero = 0;
+      for (int b = b0; b < b1; b++)
+        if ((hold_mask_ >> b) & 1u) ops_.h2d(gradsq_ + (size_t)hold_mode_ * K_ + b, &zero, sizeof(double));
+    }
+  }
   refresh_grams();
   for (auto &n : nodes_) n.valid = false;
   ms_invalidate();
+}
+
+// ---------------------------------------------------------------------------- hold-out rows per start
+void CpEngine::hold_apply(unsigned starts) {
+  const unsigned sel = hold_mask_ & starts;
+  if (hold_mode_ < 0 || !sel) return;
+  const int64_t s = V_.glens[hold_mode_];
+  ops_.cp_hold_rows(W_[hold_mode_], s, gradW_[hold_mode_], s, hold_scores_, s, s, tab_, hold_keep_dev_, sel, G_, N_,
+                    hold_mode_, gradsq_ + (size_t)hold_mode_ * K_);
+}
+
+void CpEngine::set_holdout(int mode, const uint8_t *keep) {
+  if (!multi_) throw std::logic_error("ppals: not a multi-start session");
+  if (!keep) {  // the zero rows stay until the next update of the mode
+    hold_mode_ = -1;
+    hold_mask_ = 0;
+    hold_keep_.clear();
+    return;
+  }
+  if (mode < 0 || mode >= N_) throw std::runtime_error("ppals: hold-out mode out of range");
+  const int64_t s = V_.glens[mode];
+  unsigned mask = 0;
+  for (int b = 0; b < K_; b++) {
+    int64_t kept = 0;
+    for (int64_t x = 0; x < s; x++) kept += keep[(size_t)b * s + x] != 0;
+    if (kept == 0) throw std::runtime_error("ppals: a start must keep at least one row");
+    if (kept < s) mask |= 1u << b;
+  }
+  if (!hold_keep_dev_ || hold_rows_ != s) {
+    ops_.sync();
+    ops_.free(hold_keep_dev_);
+    ops_.free(hold_scores_);
+    hold_keep_dev_ = nullptr;
+    hold_scores_ = nullptr;
+    hold_keep_dev_ = (uint8_t *)ops_.alloc((size_t)K_ * s);
+    hold_scores_ = (double *)ops_.alloc(sizeof(double) * (size_t)s * R_);
+    hold_rows_ = s;
+  }
+  hold_keep_.assign(keep, keep + (size_t)K_ * s);
+  ops_.h2d(hold_keep_dev_, hold_keep_.data(), hold_keep_.size());
+  ops_.zero(hold_scores_, sizeof(double) * (size_t)s * R_);
+  hold_mode_ = mode;
+  hold_mask_ = mask;
+  hold_apply(~0u);
+  for (auto &n : nodes_) n.valid = false;
+  ms_invalidate();
+}
+
+void CpEngine::heldout_scores(int start, double *out) {
+  if (!multi_ || hold_mode_ < 0) throw std::logic_error("ppals: the session has no hold-out");
+  if (start < 0 || start >= K_) throw std::runtime_error("ppals: start out of range");
+  const int64_t s = V_.glens[hold_mode_];
+  ops_.d2h(out, hold_scores_ + (size_t)s * tab_.col[start], sizeof(double) * (size_t)s * tab_.rank(start));
 }
 
 void CpEngine::get_factors_start(int start, double *Wflat, double *gradWflat) {
@@ -823,7 +888,8 @@ int CpEngine::run_multi(const CpOpts &o, int *sweeps_out, int *best_out) {
                     best, gn[best], res[best], now() - t0);
       // starts of different ranks: the smallest residual is (almost always) the largest rank, whose
       // gradient says nothing about the others — the run goes on until every start is below tol
-      const double gstop = ragged_ ? *std::max_element(gn.begin(), gn.end()) : gn[best];
+      // (a hold-out session likewise: every start is a fit of its own that the caller wants finished)
+      const double gstop = ragged_ || hold_mode_ >= 0 ? *std::max_element(gn.begin(), gn.end()) : gn[best];
       stopped = gstop < o.tol || now() - t0 > o.timelimit;
       if (stopped || sweeps >= o.maxiter) break;
     }
@@ -836,7 +902,7 @@ int CpEngine::run_multi(const CpOpts &o, int *sweeps_out, int *best_out) {
   return stopped && sweeps < o.maxiter ? 1 : 0;
 }
 
-void CpEngine::take_from(CpEngine &src, int start) {
+void CpEngine::take_from(CpEngine &src, int start, bool predicted) {
   if (multi_ || dist_) throw std::logic_error("ppals: the destination must be an ordinary one-rank session");
   // (a non-negative multi-start session's factors are >= the floor by construction)
   if (nonneg_ && !src.nonneg_)
@@ -844,12 +910,17 @@ void CpEngine::take_from(CpEngine &src, int start) {
   if (!src.multi_ || start < 0 || start >= src.K_ || src.tab_.rank(start) != R_ || src.N_ != N_ ||
       src.V_.data != V_.data)
     throw std::runtime_error("ppals: take: sessions do not match");
+  if (predicted && src.hold_mode_ < 0) throw std::runtime_error("ppals: take: the session has no hold-out");
   for (int i = 0; i < N_; i++) {
     const size_t n = (size_t)V_.glens[i] * R_;
     const size_t at = (size_t)V_.glens[i] * src.tab_.col[start];
     ops_.d2d(W_[i], src.W_[i] + at, n * sizeof(double));
     ops_.d2d(gradW_[i], src.gradW_[i] + at, n * sizeof(double));
     ops_.d2d(gradsq_ + i, src.gradsq_ + (size_t)i * src.K_ + start, sizeof(double));
+  }
+  if (predicted) {  // the scores into the (zero) held-out rows: W + scores, the kept rows of the scores are 0
+    const int m = src.hold_mode_;
+    ops_.add_inplace(W_[m], src.hold_scores_ + (size_t)V_.glens[m] * src.tab_.col[start], V_.glens[m] * R_);
   }
   // (gradnorm() reads the copied per-mode sums: the same number set_factors would have formed on the
   // host from these gradients, with no read-back here)
@@ -898,15 +969,16 @@ void CpEngine::mode_update(int i, const double *M, int64_t ldm, double lambda, b
       else
         ops_.cp_mode_update_ragged(G_, N_, i, tab_, lambda, M, ldm, W_[i], s, gradW_[i], s, s,
                                    gradsq_ + (size_t)i * K_, S_, Sinv_);
-      return;
-    }
-    if (nonneg_) {  // one HALS pass per start, all starts in one batched update
+    } else if (nonneg_) {  // one HALS pass per start, all starts in one batched update
       ops_.cp_mode_update_nn_batched(G_, N_, i, Rs_, K_, lambda, M, ldm, W_[i], s, gradW_[i], s, s,
                                      gradsq_ + (size_t)i * K_, S_);
-      return;
+    } else {
+      ops_.cp_mode_update_batched(G_, N_, i, Rs_, K_, lambda, M, ldm, W_[i], s, gradW_[i], s, s,
+                                  gradsq_ + (size_t)i * K_, S_, Sinv_);
     }
-    ops_.cp_mode_update_batched(G_, N_, i, Rs_, K_, lambda, M, ldm, W_[i], s, gradW_[i], s, s,
-                                gradsq_ + (size_t)i * K_, S_, Sinv_);
+    // the sample mode of a hold-out session: the rows just computed for held-out samples are their
+    // predicted scores — moved aside, and zero again before another mode reads the factor
+    if (i == hold_mode_) hold_apply(~0u);
     return;
   }
   double *Gi = G_ + (size_t)i * R_ * R_;

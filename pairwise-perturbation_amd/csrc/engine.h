@@ -214,10 +214,24 @@ class CpEngine {
   void residuals(double *out);  // [nstarts], each ||V - [[W_b]]||_F; synchronises
   // start `start` of the multi session `src` (same tensor, same R) becomes this ordinary session's
   // factors and gradients, device to device; otherwise the effect of set_factors
-  void take_from(CpEngine &src, int start);
+  void take_from(CpEngine &src, int start, bool predicted = false);
   // sweeps until maxiter / timelimit / the best start's gradient norm < tol (looked at every resprint
   // sweeps); returns 1 if it stopped before maxiter sweeps
   int run_multi(const CpOpts &o, int *sweeps, int *best);
+  // Hold-out rows of ONE mode, per start (include/ppals.h): keep[b * s_mode + x] == 0 holds row x of W_mode
+  // out of start b — it is 0 in the factor and the gradient whenever another mode reads them, so start b
+  // evolves as a session on the tensor without those slices does, and what the update of `mode` computes
+  // for the row (its least-squares score under that model) is moved to the scores buffer right behind the
+  // update (Ops::cp_hold_rows: one launch; starts that hold nothing out are not touched). Setting it moves
+  // the rows as they are now and drops the cached contractions; keep == nullptr clears it: the zero rows
+  // stay until the next update of the mode. Every start keeps at least one row (checked).
+  void set_holdout(int mode, const uint8_t *keep);
+  int holdout_mode() const { return hold_mode_; }  // -1: none
+  const std::vector<uint8_t> &holdout_keep() const { return hold_keep_; }
+  void heldout_scores(int start, double *out);  // s_mode x rank(start), column-major; kept rows 0
+  // take_from with the scores added into the held-out rows of the sample mode's factor (W + scores: the rows
+  // are disjoint)
+  void take_predicted_from(CpEngine &src, int start) { take_from(src, start, true); }
 
   int order() const { return N_; }
   int rank_r() const { return R_; }
@@ -413,6 +427,15 @@ class CpEngine {
   bool ragged_ = false;
   bool multi_ = false;
   bool nonneg_ = false;  // set_nonneg
+  // hold-out (set_holdout): the sample mode (-1: none), the keep table on the host and on the device
+  // (K_ x s_mode bytes), bit b set for a start that holds something out, the scores shaped like W_[mode]
+  int hold_mode_ = -1;
+  std::vector<uint8_t> hold_keep_;
+  uint8_t *hold_keep_dev_ = nullptr;
+  unsigned hold_mask_ = 0;
+  double *hold_scores_ = nullptr;
+  int64_t hold_rows_ = 0;  // the extent the two device buffers were allocated for
+  void hold_apply(unsigned starts);  // Ops::cp_hold_rows on the starts of hold_mask_ & starts
   bool dist_ = false;  // take the collective code paths (P_ > 1, or PPALS_FORCE_COMM=1 for tests)
   std::vector<double *> W_, gradW_, Wprev_, Winit_, dW_, dM_, Mm_;
   double *G_ = nullptr;       // N Gram matrices, R*R each

@@ -19,6 +19,7 @@
 #include "kernels_scan.hip.h"
 #include "kernels_small.hip.h"
 #include "kernels_nn.hip.h"
+#include "kernels_holdout.hip.h"
 #include "kernels_corcondia.hip.h"
 #include "kernels_fms.hip.h"
 #include "kernels_slices.hip.h"
@@ -2041,6 +2042,23 @@ class HipOps : public Ops {
     check_table(t);
     hipLaunchKernelGGL(k_gram_ragged, dim3((unsigned)t.nstarts), dim3(1024), 0, st_, W, rows, ld, t, N, mode,
                        Gall);
+    HIP_CHECK(hipGetLastError());
+  }
+  // one launch, a workgroup per start (k_cp_hold_rows); a start that holds nothing out returns at once
+  void cp_hold_rows(double *W, int64_t ldw, double *grad, int64_t ldg, double *scores, int64_t lds, int64_t rows,
+                    const StartTable &t, const uint8_t *keep, unsigned holds, double *Gall, int N, int mode,
+                    double *gradsq) override {
+    RoctxRange roctx_("hold-out rows of the sample mode");
+    check_table(t);
+    if (rows <= 0 || ldw < rows || ldg < rows || lds < rows || mode < 0 || mode >= N || !keep)
+      throw std::runtime_error("ppals: cp_hold_rows arguments out of range");
+    if (t.nstarts < 32) holds &= (1u << t.nstarts) - 1u;
+    if (!holds) return;
+    route("hold_rows starts=%d holds=0x%x", t.nstarts, holds);
+    prof_begin(1, 0.0);
+    hipLaunchKernelGGL(k_cp_hold_rows, dim3((unsigned)t.nstarts), dim3(1024), 0, st_, W, ldw, grad, ldg, scores,
+                       lds, rows, t, keep, holds, N, mode, Gall, gradsq);
+    prof_end();
     HIP_CHECK(hipGetLastError());
   }
   bool arm_normalize(double *const *W, const int64_t *rows, int N, int R, double *Gall, int mode,

@@ -443,6 +443,49 @@ class Ops {
       gram(W + (size_t)t.col[b] * ld, rows, ld, t.rank(b),
            Gall + (size_t)N * t.sq[b] + (size_t)mode * t.rank(b) * t.rank(b));
   }
+  // Hold-out rows of one mode per start (CpEngine::set_holdout; include/ppals.h), after that mode's update:
+  // keep (device, nstarts x rows bytes) has keep[b * rows + x] == 0 where start b holds row x out. For every
+  // start b whose bit of `holds` is set, on its column block [t.col[b], t.col[b + 1]) of W, grad and scores
+  // (all rows x t.col[nstarts], column-major, leading dimensions ldw, ldg, lds):
+  //   held-out x:  scores[x, :] = W[x, :],  W[x, :] = 0,  grad[x, :] = 0;       kept x:  scores[x, :] = 0
+  //   Gall + N t.sq[b] + mode R_b^2 = W_b^T W_b of the zeroed block, gradsq[b] = sum grad_b^2 of the zeroed block
+  // A start whose bit is clear is not touched at all. The same state gives the same bits: no atomics, the
+  // sums added in a fixed order. This default is built from d2h / h2d and a host loop (what the host
+  // stand-in runs, as with cp_mode_update_nn); the product back end overrides it with one launch.
+  virtual void cp_hold_rows(double *W, int64_t ldw, double *grad, int64_t ldg, double *scores, int64_t lds,
+                            int64_t rows, const StartTable &t, const uint8_t *keep, unsigned holds,
+                            double *Gall, int N, int mode, double *gradsq) {
+    if (rows <= 0) return;
+    std::vector<uint8_t> k((size_t)rows);
+    for (int b = 0; b < t.nstarts; b++) {
+      if (!((holds >> b) & 1u)) continue;
+      const int R = t.rank(b);
+      const size_t c0 = (size_t)t.col[b];
+      std::vector<double> w((size_t)ldw * (R - 1) + rows), g((size_t)ldg * (R - 1) + rows),
+          sc((size_t)lds * (R - 1) + rows);
+      d2h(k.data(), keep + (size_t)b * rows, k.size());
+      d2h(w.data(), W + c0 * ldw, sizeof(double) * w.size());
+      d2h(g.data(), grad + c0 * ldg, sizeof(double) * g.size());
+      d2h(sc.data(), scores + c0 * lds, sizeof(double) * sc.size());  // (the gaps of lds > rows go back as they came)
+      double gs = 0;
+      for (int r = 0; r < R; r++)
+        for (int64_t x = 0; x < rows; x++) {
+          if (k[(size_t)x]) {
+            sc[(size_t)(x + lds * r)] = 0.0;
+            gs += g[(size_t)(x + ldg * r)] * g[(size_t)(x + ldg * r)];
+          } else {
+            sc[(size_t)(x + lds * r)] = w[(size_t)(x + ldw * r)];
+            w[(size_t)(x + ldw * r)] = 0.0;
+            g[(size_t)(x + ldg * r)] = 0.0;
+          }
+        }
+      h2d(W + c0 * ldw, w.data(), sizeof(double) * w.size());
+      h2d(grad + c0 * ldg, g.data(), sizeof(double) * g.size());
+      h2d(scores + c0 * lds, sc.data(), sizeof(double) * sc.size());
+      h2d(gradsq + b, &gs, sizeof(double));
+      gram(W + c0 * ldw, rows, ldw, R, Gall + (size_t)N * t.sq[b] + (size_t)mode * R * R);
+    }
+  }
   // The same with M handed over in ROW BLOCKS (the receive buffer of an all-gather of the ranks' row
   // blocks: block p = rows [p*blk, (p+1)*blk) stored at Mblk + p*blk*R with leading dimension blk,
   // blk * P == rows). A back end may read the blocks as they are; the default re-assembles them in

@@ -802,6 +802,71 @@ int ppals_cp_multi_take(ppals_cp_multi *s, int start, ppals_cp *dst) {
   API_END(PPALS_ERR_HIP)
 }
 
+// ------------------------------------------------------------------ hold-out rows per start
+static int fail_fn(int code, const char *fn, const char *what) {
+  g_err = std::string(fn) + ": " + what;
+  return code;
+}
+int ppals_cp_multi_set_holdout(ppals_cp_multi *s, int mode, const uint8_t *keep) {
+  const char *fn = "ppals_cp_multi_set_holdout";
+  if (!s || !s->eng) return fail_fn(PPALS_ERR_ARG, fn, "NULL session");
+  if (keep) {  // (the table is on the host: looked at here, before anything is allocated or launched)
+    if (mode < 0 || mode >= s->eng->order()) return fail_fn(PPALS_ERR_ARG, fn, "mode must be in [0, N)");
+    const int64_t n = s->eng->mode_extent(mode);
+    for (int b = 0; b < s->eng->nstarts(); b++) {
+      bool any = false;
+      for (int64_t x = 0; x < n && !any; x++) any = keep[(size_t)b * n + x] != 0;
+      if (!any) return fail_fn(PPALS_ERR_ARG, fn, "every start must keep at least one row");
+    }
+  }
+  API_BEGIN
+  s->eng->set_holdout(mode, keep);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_cp_multi_get_holdout(const ppals_cp_multi *s, int *mode, uint8_t *keep) {
+  const char *fn = "ppals_cp_multi_get_holdout";
+  if (!s || !s->eng) return fail_fn(PPALS_ERR_ARG, fn, "NULL session");
+  if (!mode) return fail_fn(PPALS_ERR_ARG, fn, "mode is NULL");
+  *mode = s->eng->holdout_mode();
+  if (keep && *mode >= 0) std::memcpy(keep, s->eng->holdout_keep().data(), s->eng->holdout_keep().size());
+  return PPALS_OK;
+}
+int ppals_cp_multi_heldout_scores(ppals_cp_multi *s, int start, double *scores) {
+  const char *fn = "ppals_cp_multi_heldout_scores";
+  if (!s || !s->eng) return fail_fn(PPALS_ERR_ARG, fn, "NULL session");
+  if (start < 0 || start >= s->eng->nstarts()) return fail_fn(PPALS_ERR_ARG, fn, "start must be in [0, nstarts)");
+  if (!scores) return fail_fn(PPALS_ERR_ARG, fn, "scores is NULL");
+  if (s->eng->holdout_mode() < 0) return fail_fn(PPALS_ERR_ARG, fn, "the session has no hold-out");
+  API_BEGIN
+  s->eng->heldout_scores(start, scores);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_cp_multi_take_predicted(ppals_cp_multi *s, int start, ppals_cp *dst) {
+  const char *fn = "ppals_cp_multi_take_predicted";
+  if (!s || !s->eng) return fail_fn(PPALS_ERR_ARG, fn, "NULL session");
+  if (start < 0 || start >= s->eng->nstarts()) return fail_fn(PPALS_ERR_ARG, fn, "start must be in [0, nstarts)");
+  if (!dst || !dst->eng) return fail_fn(PPALS_ERR_ARG, fn, "NULL destination session");
+  if (s->eng->holdout_mode() < 0) return fail_fn(PPALS_ERR_ARG, fn, "the session has no hold-out");
+  if (dst->ctx != s->ctx) return fail_fn(PPALS_ERR_ARG, fn, "the destination session belongs to another context");
+  if (dst->eng->tensor().data != s->eng->tensor().data)
+    return fail_fn(PPALS_ERR_ARG, fn, "the destination session is on another tensor");
+  if (dst->eng->rank_r() != s->eng->start_rank(start)) {
+    char msg[128];
+    std::snprintf(msg, sizeof(msg), "the destination session has rank %d, the start rank %d", dst->eng->rank_r(),
+                  s->eng->start_rank(start));
+    return fail_fn(PPALS_ERR_ARG, fn, msg);
+  }
+  if (dst->eng->nonneg() && !s->eng->nonneg())
+    return fail_fn(PPALS_ERR_UNSUPPORTED, fn,
+                   "a non-negative session does not take an unconstrained multi-start's factors");
+  API_BEGIN
+  dst->eng->take_predicted_from(*s->eng, start);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+
 // ------------------------------------------------------------------ core consistency
 // the refusals the three entry points share, before anything is launched: more than one rank, a core above
 // the cap, a rank above the LDS elimination's (starts [b0, b1) of the session)

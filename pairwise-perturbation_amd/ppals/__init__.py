@@ -70,6 +70,8 @@ EXPORTS = [
     "ppals_match_columns", "ppals_cp_congruence", "ppals_cp_fms", "ppals_cp_multi_congruence",
     "ppals_cp_multi_fms", "ppals_cp_multi_fms_between",
     "ppals_cp_slice_residuals", "ppals_cp_leverages",
+    "ppals_cp_multi_set_holdout", "ppals_cp_multi_get_holdout", "ppals_cp_multi_heldout_scores",
+    "ppals_cp_multi_take_predicted",
 ]
 MODEL, RESIDUAL = 0, 1  # PPALS_MODEL / PPALS_RESIDUAL
 FMS_WEIGHTS = 1  # PPALS_FMS_WEIGHTS
@@ -813,6 +815,55 @@ class CPMulti:
         _check(lib().ppals_cp_multi_take(self._h, int(start), dst._h))
         return dst
 
+    # ---- hold-out rows per start (ppals_cp_multi_set_holdout): resampled fits on the shared scans ----
+    def set_holdout(self, mode, keep):
+        """keep: (nstarts, s_mode) bool array, False = start b holds sample x of `mode` out — start b then
+        evolves as a session on the tensor without those slices does, and heldout_scores(b) carries the
+        held-out samples' predicted scores. None clears the hold-out (mode is ignored)."""
+        if keep is None:
+            _check(lib().ppals_cp_multi_set_holdout(self._h, -1, None))
+            return
+        mode = int(mode)
+        n = self.lens[mode] if 0 <= mode < len(self.lens) else -1   # (a bad mode: the library refuses)
+        k = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+        if n >= 0 and k.shape != (self.nstarts, n):
+            raise PpalsError(f"set_holdout: keep has shape {k.shape}, not {(self.nstarts, n)}")
+        _check(lib().ppals_cp_multi_set_holdout(self._h, mode, k.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    @property
+    def holdout(self):
+        """(mode, keep) of the hold-out, keep an (nstarts, s_mode) bool array; None without one"""
+        mode = C.c_int(-1)
+        _check(lib().ppals_cp_multi_get_holdout(self._h, C.byref(mode), None))
+        if mode.value < 0:
+            return None
+        k = np.zeros((self.nstarts, self.lens[mode.value]), dtype=np.uint8)
+        _check(lib().ppals_cp_multi_get_holdout(self._h, C.byref(mode), k.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return mode.value, k != 0
+
+    def heldout_scores(self, start):
+        """(s_mode, ranks[start]): the held-out samples' rows from the sample mode's most recent update
+        (before any: the rows the caller set); rows of kept samples are 0"""
+        b = int(start)
+        h = self.holdout
+        if h is None or not 0 <= b < self.nstarts:   # (the library refuses both, with its message)
+            _check(lib().ppals_cp_multi_heldout_scores(self._h, b, _dp(np.empty(1))))
+            raise PpalsError("heldout_scores: no hold-out, or start out of range")
+        out = np.empty((self.lens[h[0]], self.ranks[b]), order="F")
+        _check(lib().ppals_cp_multi_heldout_scores(self._h, b, _dp(out)))
+        return out
+
+    def take_predicted(self, start, dst):
+        """take() with the sample-mode factor carrying the predicted scores in the held-out rows (W + scores)"""
+        _check(lib().ppals_cp_multi_take_predicted(self._h, int(start), dst._h))
+        return dst
+
+    def sample_residuals(self, start, dst):
+        """take_predicted(start, dst), then dst.slice_residuals()[mode]: per sample of the hold-out mode the
+        sum of (V - model)^2 over its slice — the fit of a kept sample, the prediction error of a held-out one"""
+        self.take_predicted(start, dst)
+        return dst.slice_residuals()[self.holdout[0]]
+
     def close(self):
         if self._h:
             lib().ppals_cp_multi_destroy(self._h)
@@ -924,6 +975,112 @@ def split_half(ctx, x, mode, ranks, sweeps, seed=0, dtype=F32, split="interleave
     finally:
         for h in sessions + tensors:
             h.close()
+
+
+def holdout_segments(n, K, split="interleave"):
+    """(K, n) bool keep masks of a segmented leave-samples-out scheme over n samples: segment g leaves out
+    the samples x with x % K == g ("interleave") or the g-th of K contiguous blocks ("blocks", sizes as
+    numpy.array_split). Every sample is left out by exactly one segment. Rows for CPMulti.set_holdout."""
+    n, K = int(n), int(K)
+    if K < 1 or K > n:
+        raise PpalsError(f"holdout_segments: K must be in [1, {n}], not {K}")
+    if split == "interleave":
+        seg = np.arange(n) % K
+    elif split == "blocks":
+        seg = np.concatenate([np.full(len(c), g) for g, c in enumerate(np.array_split(np.arange(n), K))])
+    else:
+        raise PpalsError(f"holdout_segments: split must be 'interleave' or 'blocks', not {split!r}")
+    return seg[None, :] != np.arange(K)[:, None]
+
+
+def jackknife(ctx, V, mode, R, segments, sweeps, W0=None, seed=0, split="interleave"):
+    """The segmented jackknife of a rank-R PARAFAC model over the samples of `mode` (Riu & Bro 2003) in ONE
+    multi-start session on the tensor V: start 0 keeps every sample (the reference fit), start g leaves out
+    segment g - 1 of holdout_segments(s_mode, segments, split); all `segments + 1` fits share every tensor
+    scan of the `sweeps` sweeps. All starts begin from the same W0 — a list of (s_i, R) arrays, by default
+    numpy.random.default_rng(seed).random((s_i, R)) mode by mode; a list of segments + 1 such lists gives
+    every start its own. Refused when segments + 1 > 32 or (segments + 1) * R > 128 (CPMulti's limits).
+
+    Each start is then aligned to start 0: its columns are matched to the reference's (match_columns on the
+    absolute congruence over all modes but `mode`), and in each mode other than `mode` each column is scaled
+    to unit norm and given the sign of its dot product with the matched reference column; the product of
+    those signs and norms goes into the sample mode and the predicted scores, so the model is unchanged.
+    Returns a dict:
+      loadings[i]  (segments, s_i, R): the aligned factors (in `mode`: zero rows where a sample was left out)
+      se[i]        (s_i, R), i != mode: the jackknife standard error sqrt((K - 1) / K * sum_g (a_g - mean)^2),
+                   K = segments; None for `mode`
+      reference    start 0's factors in the same normalisation
+      scores       (s_mode, R): each sample's predicted score from the start that left it out
+      fms          (segments,): the factor match score of each start against the reference, `mode` skipped: the
+                   mean absolute congruence of the matched columns (the skipped mode can carry a sign)
+      press        (s_mode,): each sample's prediction error (CPMulti.sample_residuals) from that start
+    Leave-samples-out PRESS projects a sample with its own data and so falls with the rank: it is an outlier
+    diagnostic, not a rank selector. Element-wise cross-validation is what run_em with a mask is for."""
+    mode, R, K = int(mode), int(R), int(segments)
+    N = len(V.lens)
+    if not 0 <= mode < N:
+        raise PpalsError(f"jackknife: mode must be in [0, {N}), not {mode}")
+    if K < 2:
+        raise PpalsError("jackknife: at least 2 segments")
+    if K + 1 > 32 or (K + 1) * R > 128:
+        raise PpalsError(f"jackknife: segments + 1 = {K + 1} starts of rank {R} exceed a multi-start session "
+                         "(32 starts, 128 columns)")
+    n = V.lens[mode]
+    keep = np.vstack([np.ones((1, n), dtype=bool), holdout_segments(n, K, split)])
+    if W0 is None:
+        rng = np.random.default_rng(seed)
+        W0 = [rng.random((s, R)) for s in V.lens]
+    per_start = list(W0) if isinstance(W0[0], (list, tuple)) else [W0] * (K + 1)
+    if len(per_start) != K + 1:
+        raise PpalsError(f"jackknife: W0 lists {len(per_start)} starts, not {K + 1}")
+    m = dst = None
+    try:
+        m = CPMulti(ctx, V, R, K + 1)
+        m.set_holdout(mode, keep)
+        m.set_factors(-1, per_start)
+        m.sweeps(int(sweeps))
+        Ws = m.get_factors(-1)
+        phi = np.abs(m.congruence(skip_mode=mode))
+        held = [m.heldout_scores(g) for g in range(K + 1)]
+        dst = CP(ctx, V, R)
+        press = np.zeros(n)
+        for g in range(1, K + 1):
+            press[~keep[g]] = m.sample_residuals(g, dst)[~keep[g]]
+    finally:
+        for h in (dst, m):
+            if h is not None:
+                h.close()
+
+    def normalised(W, sc, ref):
+        """modes != mode to unit norm (and the sign of <column, ref column> if ref), the rest into `mode`"""
+        W = [w.copy() for w in W]
+        f = np.ones(R)
+        for i in range(N):
+            if i == mode:
+                continue
+            c = np.linalg.norm(W[i], axis=0)
+            if ref is not None:
+                c = c * np.where(np.sum(W[i] * ref[i], axis=0) < 0, -1.0, 1.0)
+            W[i] = W[i] / c
+            f = f * c
+        W[mode] = W[mode] * f
+        return W, sc * f
+
+    ref_raw = Ws[0]
+    loadings = [np.empty((K, s, R)) for s in V.lens]
+    scores, fms = np.zeros((n, R)), np.empty(K)
+    for g in range(1, K + 1):
+        perm, total = match_columns(phi[g * R:(g + 1) * R, :R])   # column p of start g <-> column perm[p] of start 0
+        fms[g - 1] = total / R
+        inv = np.argsort(perm)
+        Wg, sg = normalised([w[:, inv] for w in Ws[g]], held[g][:, inv], ref_raw)
+        for i in range(N):
+            loadings[i][g - 1] = Wg[i]
+        scores[~keep[g]] = sg[~keep[g]]
+    se = [None if i == mode else
+          np.sqrt((K - 1) / K * np.sum((loadings[i] - loadings[i].mean(axis=0)) ** 2, axis=0)) for i in range(N)]
+    reference, _ = normalised(ref_raw, np.zeros((n, R)), None)
+    return dict(loadings=loadings, se=se, reference=reference, scores=scores, fms=fms, press=press)
 
 
 # ---- reference-named entry points (als_CP.h / als_Tucker.h), argument order preserved ----
