@@ -190,6 +190,49 @@ int ppals_cp_get_schedule(const ppals_cp *s);
 #define PPALS_NN_FLOOR 1e-16
 int ppals_cp_set_nonneg(ppals_cp *s, int on);
 int ppals_cp_get_nonneg(const ppals_cp *s);
+/* Per-mode constraints: one kind per mode (kinds[N]), FREE everywhere at first. Throughout, M is the
+ * mode's MTTKRP and S the Hadamard product of the other modes' Grams + lambda I.
+ *   PPALS_MODE_FREE    the solve of the normal equations. A session whose kinds are all FREE is bit for bit
+ *                      a session on which the call was never made.
+ *   PPALS_MODE_NONNEG  one HALS pass, exactly that of ppals_cp_set_nonneg above. A session whose kinds are
+ *                      all NONNEG is bit for bit one with ppals_cp_set_nonneg(s, 1); that call is "all modes
+ *                      NONNEG, or all modes FREE", and ppals_cp_get_nonneg returns 1 only if every mode is.
+ *   PPALS_MODE_FIXED   the factor is never updated: neither the mode's leaf contraction nor an update is
+ *                      launched, the factor and its Gram read back bit for bit as they were set. grad_W of
+ *                      the mode and its share of the gradient norm are zero: zeroed when the mode becomes
+ *                      FIXED, and gradients handed to ppals_cp_set_factors for it are ignored. Cached
+ *                      contractions are not dropped on its account.
+ *   PPALS_MODE_ORTHO   orthonormal columns: W <- M (M^T M)^(-1/2), the orthonormal polar factor of M in fp64,
+ *                      which minimises the mode's least-squares problem under W^T W = I (lambda does not
+ *                      enter it: ||W||^2 is constant). grad = -M + W_old S as for every kind. The Gram of the
+ *                      new W is computed, not assumed to be I. With theta the eigenvalues of M^T M: if any is
+ *                      not a positive finite number, or theta_min <= theta_max * PPALS_ORTHO_MIN_RATIO
+ *                      (u kappa(M)^2 = 2^-13 at that ratio: no polar factor to speak of), the factor stays
+ *                      as it is — for that start, in a multi-start session — and the gradient is still
+ *                      written. Needs s_mode >= R (of every start). The factor need not be orthonormal when
+ *                      it is set: the first update makes it so.
+ * Normalize would rescale a FIXED factor and destroy orthonormal columns: in a session with at least one
+ * FIXED or ORTHO mode the Normalize step of ppals_cp_sweeps_dt and of every driver built on it (ppals_cp_dt,
+ * ppals_cp_em) is skipped — such sweeps are those of ppals_cpd_als. Mixtures of FREE and NONNEG keep it.
+ * grad_W, the gradient norm and the residual keep their definitions; as with NONNEG, the unconstrained
+ * gradient does not vanish at a constrained optimum. The kinds may be changed between calls; factors,
+ * Grams and caches are untouched by the call itself. The read-only diagnostics (core consistency,
+ * congruence and factor match score, slice residuals and leverages, model export, imputation) work
+ * unchanged.
+ * Every refusal happens before anything is launched and leaves the kinds as they were. PPALS_ERR_ARG: a
+ * NULL session or kinds, a kind outside 0..3, ORTHO on a mode shorter than the rank, a mode that becomes
+ * NONNEG while its factor has a negative or non-finite entry (and such a factor in ppals_cp_set_factors
+ * later). PPALS_ERR_UNSUPPORTED: any kind but FREE in a context of more than one rank, with the collective
+ * paths forced or under PPALS_TEST_BLOCKED_UPDATE; NONNEG or ORTHO at R > 64 (FREE and FIXED take any rank);
+ * ppals_cp_pp, ppals_cp_pp_partupdate and ppals_cpd_als_lr on a session with a mode that is not FREE;
+ * ppals_cp_multi_take into a session that is NONNEG in a mode where the multi-start session is not. */
+#define PPALS_MODE_FREE 0
+#define PPALS_MODE_NONNEG 1
+#define PPALS_MODE_FIXED 2
+#define PPALS_MODE_ORTHO 3
+#define PPALS_ORTHO_MIN_RATIO 9.094947017729282379150390625e-13 /* 2^-40 */
+int ppals_cp_set_mode_constraints(ppals_cp *s, const int *kinds /* N */);
+int ppals_cp_get_mode_constraints(const ppals_cp *s, int *kinds /* N */);
 /* Where the multi-sweep schedule's first-level intermediates lie (no counterpart in the reference:
  * CTF places its own buffers). The choice is made ONLINE: the first ~20 visits of a root run the
  * sweep's own scan at a different offset / store kind of the result, timed on the stream; then the
@@ -329,6 +372,14 @@ int ppals_cp_multi_take(ppals_cp_multi *s, int start, ppals_cp *dst);
  * is looked at before anything is uploaded). ppals_cp_multi_get_nonneg: 1 / 0, PPALS_ERR_ARG for NULL. */
 int ppals_cp_multi_set_nonneg(ppals_cp_multi *s, int on);
 int ppals_cp_multi_get_nonneg(const ppals_cp_multi *s);
+/* The per-mode constraints of ppals_cp_set_mode_constraints for a multi-start or rank-sweep session: one
+ * kind per mode, shared by all starts (kinds[N]). Start b evolves exactly as an ordinary session of its
+ * rank with the same kinds does under ppals_cpd_als with PPALS_OPT_SIMPLE; an ORTHO update whose M has no
+ * polar factor leaves that start's factor alone. ORTHO needs s_mode >= the largest start's rank, NONNEG
+ * and ORTHO every start's rank <= 64. PPALS_ERR_UNSUPPORTED in addition: ppals_cp_multi_set_holdout on a
+ * FIXED or ORTHO mode, and making the hold-out mode FIXED or ORTHO. */
+int ppals_cp_multi_set_mode_constraints(ppals_cp_multi *s, const int *kinds /* N: one kind per mode, for all starts */);
+int ppals_cp_multi_get_mode_constraints(const ppals_cp_multi *s, int *kinds /* N */);
 
 /* ---- core consistency diagnostic (CORCONDIA: R. Bro, H. A. L. Kiers, "A new efficient method for
  * determining the number of components in PARAFAC models", J. Chemometrics 17 (2003) 274-286; no

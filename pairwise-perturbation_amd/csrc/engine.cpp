@@ -692,9 +692,11 @@ void CpEngine::set_factors(const double *Wflat, const double *gradWflat) {
     ops_.h2d(W_[i], w, n * sizeof(double));
     w += n;
     if (g) {
-      ops_.h2d(gradW_[i], g, n * sizeof(double));
-      for (size_t e = 0; e < n; e++) gsi[i] += g[e] * g[e];
-      gs += gsi[i];
+      if (kind_[i] != kModeFixed) {  // (a FIXED mode's gradient is zero and stays zero)
+        ops_.h2d(gradW_[i], g, n * sizeof(double));
+        for (size_t e = 0; e < n; e++) gsi[i] += g[e] * g[e];
+        gs += gsi[i];
+      }
       g += n;
     }
   }
@@ -721,11 +723,62 @@ void CpEngine::set_nonneg(bool on) {
     if (test_blocks_ > 1)
       throw Unsupported("ppals: PPALS_TEST_BLOCKED_UPDATE has no non-negative update");
   }
-  nonneg_ = on;
+  for (int i = 0; i < N_; i++) kind_[i] = on ? kModeNonneg : kModeFree;
 }
 
-bool CpEngine::factors_nonneg() {
+int CpEngine::check_mode_kinds(const int *kinds, std::string *why) const {
+  bool nonfree = false, capped = false;
+  for (int i = 0; i < N_; i++) {
+    if (kinds[i] < kModeFree || kinds[i] > kModeOrtho) {
+      *why = "a kind must be PPALS_MODE_FREE, _NONNEG, _FIXED or _ORTHO";
+      return 1;
+    }
+    nonfree = nonfree || kinds[i] != kModeFree;
+    capped = capped || kinds[i] == kModeNonneg || kinds[i] == kModeOrtho;
+    // (Rs_ is the largest start's rank: ORTHO needs s_mode >= R for every start)
+    if (kinds[i] == kModeOrtho && V_.glens[i] < (multi_ ? Rs_ : R_)) {
+      *why = "an orthonormal mode must have at least as many rows as the rank (of every start)";
+      return 1;
+    }
+  }
+  if (!nonfree) return 0;
+  if (P_ > 1 || dist_) {
+    *why = "per-mode constraints run on one rank";
+    return 2;
+  }
+  if (test_blocks_ > 1) {
+    *why = "PPALS_TEST_BLOCKED_UPDATE has no constrained update";
+    return 2;
+  }
+  if (capped && (multi_ ? Rs_ : R_) > 64) {
+    *why = "a non-negative or orthonormal mode supports R <= 64";
+    return 2;
+  }
+  if (hold_mode_ >= 0 && (kinds[hold_mode_] == kModeFixed || kinds[hold_mode_] == kModeOrtho)) {
+    *why = "the hold-out mode cannot be fixed or orthonormal";
+    return 2;
+  }
+  return 0;
+}
+
+void CpEngine::set_mode_kinds(const int *kinds) {
+  std::string why;
+  const int rc = check_mode_kinds(kinds, &why);
+  if (rc == 2) throw Unsupported("ppals: " + why);
+  if (rc) throw std::invalid_argument("ppals: " + why);
+  for (int i = 0; i < N_; i++) {
+    if (kinds[i] == kModeFixed && kind_[i] != kModeFixed) {  // its gradient is zero from here on
+      ops_.zero(gradW_[i], sizeof(double) * (size_t)V_.glens[i] * R_);
+      ops_.zero(gradsq_ + (size_t)i * K_, sizeof(double) * K_);
+      grad_replicated_[i] = true;
+    }
+    kind_[i] = kinds[i];
+  }
+}
+
+bool CpEngine::factors_nonneg(unsigned modes) {
   for (int i = 0; i < N_; i++) {  // (R_ columns: all starts of a multi-start session)
+    if (!((modes >> i) & 1u)) continue;
     std::vector<double> h((size_t)V_.glens[i] * R_);
     ops_.d2h(h.data(), W_[i], sizeof(double) * h.size());
     for (double v : h)
@@ -749,8 +802,10 @@ void CpEngine::set_factors_start(int start, const double *Wflat, const double *g
       // ||grad_W[i]||^2 of the caller's gradients, as set_factors keeps it (0 without gradients)
       double gsq = 0;
       if (g) {
-        ops_.h2d(gradW_[i] + at, g, n * sizeof(double));
-        for (size_t e = 0; e < n; e++) gsq += g[e] * g[e];
+        if (kind_[i] != kModeFixed) {  // (a FIXED mode's gradient is zero and stays zero)
+          ops_.h2d(gradW_[i] + at, g, n * sizeof(double));
+          for (size_t e = 0; e < n; e++) gsq += g[e] * g[e];
+        }
         g += n;
       }
       ops_.h2d(gradsq_ + (size_t)i * K_ + b, &gsq, sizeof(double));
@@ -905,7 +960,7 @@ int CpEngine::run_multi(const CpOpts &o, int *sweeps_out, int *best_out) {
 void CpEngine::take_from(CpEngine &src, int start, bool predicted) {
   if (multi_ || dist_) throw std::logic_error("ppals: the destination must be an ordinary one-rank session");
   // (a non-negative multi-start session's factors are >= the floor by construction)
-  if (nonneg_ && !src.nonneg_)
+  if (!takes_nonneg_from(src))
     throw Unsupported("ppals: a non-negative session does not take an unconstrained multi-start's factors");
   if (!src.multi_ || start < 0 || start >= src.K_ || src.tab_.rank(start) != R_ || src.N_ != N_ ||
       src.V_.data != V_.data)
@@ -917,6 +972,10 @@ void CpEngine::take_from(CpEngine &src, int start, bool predicted) {
     ops_.d2d(W_[i], src.W_[i] + at, n * sizeof(double));
     ops_.d2d(gradW_[i], src.gradW_[i] + at, n * sizeof(double));
     ops_.d2d(gradsq_ + i, src.gradsq_ + (size_t)i * src.K_ + start, sizeof(double));
+    if (kind_[i] == kModeFixed) {  // (a FIXED mode's gradient is zero and stays zero)
+      ops_.zero(gradW_[i], n * sizeof(double));
+      ops_.zero(gradsq_ + i, sizeof(double));
+    }
   }
   if (predicted) {  // the scores into the (zero) held-out rows: W + scores, the kept rows of the scores are 0
     const int m = src.hold_mode_;
@@ -960,16 +1019,25 @@ void CpEngine::get_factors(double *Wflat, double *gradWflat) {
 void CpEngine::mode_update(int i, const double *M, int64_t ldm, double lambda, bool pp,
                            double ratio) {
   const int64_t s = V_.glens[i];
+  const bool hals = kind_[i] == kModeNonneg;  // this mode's update is the HALS pass
+  if (kind_[i] == kModeFixed) throw std::logic_error("ppals: a FIXED mode has no update");
+  if (kind_[i] == kModeOrtho) {  // the polar factor of M, start by start through the table (one start here
+    // when the session is an ordinary one); the hold-out mode is never ORTHO (set_mode_kinds, set_holdout)
+    if (pp || dist_) throw std::logic_error("ppals: an orthonormal mode updates exactly, on one rank");
+    ops_.cp_mode_update_ortho_ragged(G_, N_, i, start_table(), lambda, M, ldm, W_[i], s, gradW_[i], s, s,
+                                     gradsq_ + (size_t)i * K_, S_);
+    return;
+  }
   if (multi_) {  // block-diagonal over starts: one batched update, every start its own system
     if (pp) throw std::logic_error("ppals: no PP update in a multi-start session");
     if (ragged_) {  // starts of different ranks: the same updates, addressed through the table
-      if (nonneg_)
+      if (hals)
         ops_.cp_mode_update_nn_ragged(G_, N_, i, tab_, lambda, M, ldm, W_[i], s, gradW_[i], s, s,
                                       gradsq_ + (size_t)i * K_, S_);
       else
         ops_.cp_mode_update_ragged(G_, N_, i, tab_, lambda, M, ldm, W_[i], s, gradW_[i], s, s,
                                    gradsq_ + (size_t)i * K_, S_, Sinv_);
-    } else if (nonneg_) {  // one HALS pass per start, all starts in one batched update
+    } else if (hals) {  // one HALS pass per start, all starts in one batched update
       ops_.cp_mode_update_nn_batched(G_, N_, i, Rs_, K_, lambda, M, ldm, W_[i], s, gradW_[i], s, s,
                                      gradsq_ + (size_t)i * K_, S_);
     } else {
@@ -982,7 +1050,7 @@ void CpEngine::mode_update(int i, const double *M, int64_t ldm, double lambda, b
     return;
   }
   double *Gi = G_ + (size_t)i * R_ * R_;
-  if (nonneg_) {  // one HALS pass in place of the solve (set_nonneg admits one-rank sessions only)
+  if (hals) {  // one HALS pass in place of the solve (set_nonneg admits one-rank sessions only)
     if (pp || dist_) throw std::logic_error("ppals: a non-negative session updates exactly, on one rank");
     ops_.cp_mode_update_nn(G_, N_, i, R_, lambda, M, ldm, W_[i], s, gradW_[i], s, s, gradsq_ + i, S_);
     return;
@@ -1527,6 +1595,10 @@ void CpEngine::ms_start_step(int first) {
 // set of the running one (its factor was frozen into X), i.e. after N - k updates
 void CpEngine::ms_mode_update(int i, double lambda, bool last_of_sweep) {
   check_tensor_generation();
+  // A FIXED mode: no step is started for it, no leaf contracted, nothing launched. Its factor does not
+  // change, so every cached contraction stays what it was — the step whose root set it belongs to goes
+  // on serving the other modes (see the invalidation below the update).
+  if (kind_[i] == kModeFixed) return;
   if (ms_root_ < 0 || ((i - ms_root_ + N_) % N_) < ms_k_) {
     // the k modes updated last serve the next N - k updates — unless one of them is never a root
     // (ms_excl_: the partitioned mode of a sharded session, whose X would be a PARTIAL sum of full
@@ -1542,13 +1614,14 @@ void CpEngine::ms_mode_update(int i, double lambda, bool last_of_sweep) {
   const int leaf = ms_leaf_[pos];
   // (S and S^-1 of this update depend on the other modes' Grams only: the contraction launched
   // next may prepare them on the side)
-  if (!multi_ && !nonneg_) ops_.arm_gram_system(G_, N_, i, R_, lambda, S_, Sinv_);
+  const bool free_i = kind_[i] == kModeFree;  // the solve: the only update that takes an armed S / Normalize
+  if (!multi_ && free_i) ops_.arm_gram_system(G_, N_, i, R_, lambda, S_, Sinv_);
   ms_compute(leaf);
   ms_norm_fused_ = false;
   // the sweep's Normalize at the tail of its last update launch, with the pending scales of the cached
   // tensors that outlive the update (everything valid now but the leaf it consumes) — where the update
   // is the fused launch: one rank, or the one-all-reduce plan of a sharded session (never mode 0's)
-  if (last_of_sweep && !multi_ && !nonneg_ && (!dist_ || (i != 0 && (int64_t)sizeof(double) * V_.glens[i] * R_ <= small_msg_bytes_))) {
+  if (last_of_sweep && !multi_ && free_i && !skips_normalize() && (!dist_ || (i != 0 && (int64_t)sizeof(double) * V_.glens[i] * R_ <= small_msg_bytes_))) {
     int64_t rows[MAX_ORDER];
     for (int q = 0; q < N_; q++) rows[q] = V_.glens[q];
     // (asked first with no cached tensors — a back end that cannot fold it must not see them marked)
@@ -1560,6 +1633,14 @@ void CpEngine::ms_mode_update(int i, double lambda, bool last_of_sweep) {
   }
   mode_update(i, (const double *)ms_nodes_[leaf].t.buf, ext(i), lambda, false, 1.0);
   ms_nodes_[leaf].t.valid = false;  // a leaf is consumed by its own update
+  // A node that contracted mode i holds the factor from before this update. While every root mode is
+  // updated in its turn, such a node is never asked for again before the next step starts; but a step whose
+  // root modes are FIXED — now, or made so by a later set_mode_kinds, which leaves the caches alone — is not
+  // restarted and goes round its mode list again, and then the node must be rebuilt (from its parent, in the
+  // end from X, which contracted root modes only). So it is marked in every session: the mark costs nothing
+  // where the node is dead anyway, and the kinds may change between any two updates.
+  for (auto &nd : ms_nodes_)
+    if (nd.t.contracted & (1u << i)) nd.t.valid = false;
 }
 
 // dst = src contracted with `mode` (rank index shared), fp64 result; in_scale = pending factor of
@@ -1616,7 +1697,7 @@ void CpEngine::ms_compute(int idx) {
 
 void CpEngine::sweep_msdt(double lambda) {
   for (int i = 0; i < N_; i++) ms_mode_update(i, lambda, i == N_ - 1);
-  if (!ms_norm_fused_) normalize();
+  if (!ms_norm_fused_ && !skips_normalize()) normalize();
   ms_norm_fused_ = false;
   grad_from_sweep_ = true;
 }
@@ -1629,9 +1710,11 @@ void CpEngine::sweep_dt(double lambda) {
   for (auto &n : nodes_) n.valid = false;  // mttkrp_map.clear(), als_CP.cxx:215
   bool norm_fused = false;
   for (int i = 0; i < N_; i++) {
+    if (kind_[i] == kModeFixed) continue;  // neither its leaf contraction nor an update
     compute_node(leaf_[i]);
     const Node &lf = nodes_[leaf_[i]];
-    if (i == N_ - 1 && !dist_ && !nonneg_) {  // Normalize at the tail of the sweep's last update launch
+    // Normalize at the tail of the sweep's last update launch (the solve's: a FREE mode)
+    if (i == N_ - 1 && !dist_ && kind_[i] == kModeFree && !skips_normalize()) {
       int64_t rows[MAX_ORDER];
       for (int q = 0; q < N_; q++) rows[q] = V_.glens[q];
       norm_fused = ops_.arm_normalize(W_.data(), rows, N_, R_, G_, i, nullptr);
@@ -1640,7 +1723,7 @@ void CpEngine::sweep_dt(double lambda) {
     // every cached node that does NOT contain mode i stays valid; nodes containing mode i were
     // built from W_j, j != i only, so they stay valid too until the cache is cleared.
   }
-  if (!norm_fused) normalize();
+  if (!norm_fused && !skips_normalize()) normalize();
   grad_from_sweep_ = true;
 }
 
@@ -1655,6 +1738,7 @@ void CpEngine::update_modes(int first, int count, double lambda) {
     } else {
       if (i == 0 || k == 0)
         for (auto &n : nodes_) n.valid = false;
+      if (kind_[i] == kModeFixed) continue;
       compute_node(leaf_[i]);
       mode_update(i, nodes_[leaf_[i]].buf, ext(i), lambda, false, 1.0);
     }
@@ -1919,7 +2003,8 @@ void CpEngine::lr_mode_update(int i, double lambda, int r, const double *base) {
 int CpEngine::run_class(int kind, const CpOpts &o, double *sweeps_out, int *iters_out) {
   if (kind < 0 || kind > 4) throw std::runtime_error("ppals: unknown class-API optimizer");
   const bool lr = kind >= 3;
-  if (lr && nonneg_) throw Unsupported("ppals: a non-negative session has no low-rank-update optimizer");
+  if (lr && nonneg()) throw Unsupported("ppals: a non-negative session has no low-rank-update optimizer");
+  if (lr && any_nonfree()) throw Unsupported("ppals: a session with constrained modes has no low-rank-update optimizer");
   if (lr) {
     if (dist_) throw std::runtime_error("ppals: the low-rank-update optimizers run on one GPU");
     if (N_ < 3) throw std::runtime_error("ppals: the low-rank-update optimizers need order >= 3");
@@ -2852,7 +2937,8 @@ int64_t CpEngine::pp_operator(const std::string &contracted, double *out_host) {
 // Normalize launch leaves ||W_i||^2: the restart test of the next iteration costs no launch.
 void CpEngine::sweep_pp(double lambda, double ratio) {
   // (the armed S / Normalize below are consumed by cp_mode_update, which a non-negative session never calls)
-  if (nonneg_) throw Unsupported("ppals: a non-negative session has no pairwise-perturbation sweep");
+  if (nonneg()) throw Unsupported("ppals: a non-negative session has no pairwise-perturbation sweep");
+  if (any_nonfree()) throw Unsupported("ppals: a session with constrained modes has no pairwise-perturbation sweep");
   ms_invalidate();  // PP moves the factors without touching the multi-sweep cache
   if (!Mbuf_) Mbuf_ = (double *)ops_.alloc(sizeof(double) * (size_t)maxs_ * R_);
   if (!pp_norms_) {
@@ -3071,7 +3157,8 @@ int CpEngine::run_pp_partupdate(const CpOpts &o, int *iters) {
 }
 
 int CpEngine::run_pp_common(const CpOpts &o, int *iters, bool partupdate) {
-  if (nonneg_) throw Unsupported("ppals: a non-negative session has no pairwise-perturbation driver");
+  if (nonneg()) throw Unsupported("ppals: a non-negative session has no pairwise-perturbation driver");
+  if (any_nonfree()) throw Unsupported("ppals: a session with constrained modes has no pairwise-perturbation driver");
   if (partupdate && rank_ == 0 && o.verbose) std::cout << "alsCP_PP_partupdate starts. " << std::endl;
   for (int i = 0; i < N_; i++) {
     size_t n = sizeof(double) * V_.glens[i] * R_;

@@ -111,9 +111,55 @@ class CpEngine {
   // multi-start session in one Ops::cp_mode_update_nn_batched) instead of the solve.
   // Exact sweeps and what is built on them (run_dt, run_class 0-2, run_em, run_multi) work unchanged; PP,
   // the low-rank optimizers, more than one rank and R > 64 per start throw Unsupported.
-  void set_nonneg(bool on);
-  bool nonneg() const { return nonneg_; }
-  bool factors_nonneg();  // downloads the factors (of all starts): every entry finite and >= 0
+  void set_nonneg(bool on);  // all modes kModeNonneg, or all modes kModeFree
+  bool nonneg() const {      // every mode is kModeNonneg
+    for (int i = 0; i < N_; i++)
+      if (kind_[i] != kModeNonneg) return false;
+    return true;
+  }
+  // downloads the factors (of all starts) of the modes of `modes` (bit i: mode i): every entry finite and >= 0
+  bool factors_nonneg(unsigned modes = ~0u);
+  // Per-mode constraints (include/ppals.h, PPALS_MODE_*): the update of mode i is the solve (kModeFree), one
+  // HALS pass (kModeNonneg), nothing at all (kModeFixed: no leaf contraction either; its gradient is
+  // zeroed here and stays zero) or the orthonormal polar factor of the MTTKRP (kModeOrtho,
+  // Ops::cp_mode_update_ortho_ragged). One kind per mode, shared by all starts of a multi-start session.
+  // Everything that cannot run that way is refused before anything is launched or changed: Unsupported
+  // for more than one rank, the blocked-update test hook, NONNEG / ORTHO at a start rank above 64 and a
+  // FIXED / ORTHO hold-out mode; std::invalid_argument for a kind outside 0..3 and ORTHO on a mode shorter
+  // than a start's rank. Factors, Grams and caches are untouched.
+  void set_mode_kinds(const int *kinds);
+  // the refusals of set_mode_kinds, nothing changed: 0 fine, 1 a bad argument, 2 unsupported; *why says which
+  int check_mode_kinds(const int *kinds, std::string *why) const;
+  // the kinds as they were a moment ago (set_nonneg taken back by the C ABI): no check, nothing zeroed
+  void restore_mode_kinds(const int *kinds) {
+    for (int i = 0; i < N_; i++) kind_[i] = kinds[i];
+  }
+  int mode_kind(int i) const { return kind_[i]; }
+  bool all_free() const { return !any_nonfree(); }
+  bool any_nonfree() const {
+    for (int i = 0; i < N_; i++)
+      if (kind_[i] != kModeFree) return true;
+    return false;
+  }
+  // Normalize would rescale a FIXED factor and destroy orthonormal columns: sweeps of such a session end
+  // without it (a positive scaling keeps FREE and NONNEG)
+  bool skips_normalize() const {
+    for (int i = 0; i < N_; i++)
+      if (kind_[i] == kModeFixed || kind_[i] == kModeOrtho) return true;
+    return false;
+  }
+  // take_from: a mode that is NONNEG here must be NONNEG in the multi-start session `src`
+  bool takes_nonneg_from(const CpEngine &src) const {
+    for (int i = 0; i < N_ && i < src.N_; i++)
+      if (kind_[i] == kModeNonneg && src.kind_[i] != kModeNonneg) return false;
+    return true;
+  }
+  unsigned nonneg_modes() const {
+    unsigned m = 0;
+    for (int i = 0; i < N_; i++)
+      if (kind_[i] == kModeNonneg) m |= 1u << i;
+    return m;
+  }
   int schedule() const { return schedule_; }
   // one JSON object: where the online placement choice put every root's first-level intermediate
   // (block, offset, store kind, fastest / slowest sample, settled or still exploring)
@@ -426,7 +472,12 @@ class CpEngine {
   StartTable tab_;
   bool ragged_ = false;
   bool multi_ = false;
-  bool nonneg_ = false;  // set_nonneg
+  int kind_[MAX_ORDER] = {0};  // set_mode_kinds / set_nonneg: kModeFree everywhere at first
+  bool any_fixed() const {
+    for (int i = 0; i < N_; i++)
+      if (kind_[i] == kModeFixed) return true;
+    return false;
+  }
   // hold-out (set_holdout): the sample mode (-1: none), the keep table on the host and on the device
   // (K_ x s_mode bytes), bit b set for a start that holds something out, the scores shaped like W_[mode]
   int hold_mode_ = -1;

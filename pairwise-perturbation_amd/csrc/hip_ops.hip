@@ -19,6 +19,7 @@
 #include "kernels_scan.hip.h"
 #include "kernels_small.hip.h"
 #include "kernels_nn.hip.h"
+#include "kernels_polar.hip.h"
 #include "kernels_holdout.hip.h"
 #include "kernels_corcondia.hip.h"
 #include "kernels_fms.hip.h"
@@ -180,6 +181,8 @@ class HipOps : public Ops {
     if (const char *v = getenv("PPALS_GJ_SCALAR")) gj_scalar_ = atoi(v);
     HIP_CHECK(hipFuncSetAttribute((const void *)k_fms_cross, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)fms_lds_bytes(FMS_MAXC, FMS_MAXC, false)));
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_polar_factor, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  96 * 1024));  // (67.5 KB at R = 64)
   }
   ~HipOps() override {
     hipSetDevice(dev_);
@@ -2030,6 +2033,47 @@ class HipOps : public Ops {
     prof_begin(1, 0.0);
     hipLaunchKernelGGL(k_cp_update_nn_ragged, dim3((unsigned)nb, (unsigned)t.nstarts), dim3(64), lds, st_, Gall, N,
                        mode, t, lambda, M, ldm, W, ldw, grad, ldg, rows, part, S, kNnFloor);
+    hipLaunchKernelGGL(k_cp_finish_nn_ragged, dim3((unsigned)t.nstarts), dim3(1024), 0, st_, part, (int)nb,
+                       gradsq, W, ldw, rows, t, N, mode, Gall);
+    prof_end();
+    HIP_CHECK(hipGetLastError());
+  }
+  // The orthonormal mode update (kernels_polar.hip.h) in THREE launches whatever the starts, ranks and rows:
+  // a workgroup per start for T = (M^T M)^(-1/2) and the start's status, the row kernel on (row tiles x
+  // starts) for grad, its tile sums and W = M T, then k_cp_finish_nn_ragged for the sums and the Grams. Each
+  // launch is bracketed on its own, so the launch profile counts them. Scratch: T | tile sums | status.
+  void cp_mode_update_ortho_ragged(double *Gall, int N, int mode, const StartTable &t, double lambda,
+                                   const double *M, int64_t ldm, double *W, int64_t ldw, double *grad,
+                                   int64_t ldg, int64_t rows, double *gradsq, double *S) override {
+    RoctxRange roctx_("K4-K6 mode update (orthonormal)");
+    check_table(t);
+    const int R = t.max_rank();
+    if (R > 64) throw Unsupported("ppals: the orthonormal mode update supports R <= 64");
+    if (sys_armed_ || sys_ready_ || norm_armed_)
+      throw std::logic_error("ppals: armed S / Normalize in front of an orthonormal mode update");
+    if (rows <= 0) {
+      Ops::cp_mode_update_ortho_ragged(Gall, N, mode, t, lambda, M, ldm, W, ldw, grad, ldg, rows, gradsq, S);
+      return;
+    }
+    const int64_t nb = (rows + 63) / 64;
+    if (nb * t.nstarts > (int64_t)1 << 30)
+      throw std::runtime_error("ppals: mode too long for the orthonormal update");
+    const size_t nT = (size_t)t.sq[t.nstarts], npart = (size_t)nb * t.nstarts;
+    double *Tm = (double *)ensure(ws_big2_, ws_big2_sz_, sizeof(double) * (nT + npart) + sizeof(int) * kMaxStarts);
+    double *part = Tm + nT;
+    int *status = (int *)(part + npart);
+    const size_t lds1 = sizeof(double) * (2 * (size_t)R * (R + 1) + 64 + 18) + sizeof(int) * 64;
+    const size_t lds2 = sizeof(double) * ((size_t)R * R + 64 * (size_t)R);
+    route("update_ortho R=%d starts=%d tiles=%d", R, t.nstarts, (int)nb);
+    prof_begin(1, 0.0);
+    hipLaunchKernelGGL(k_polar_factor, dim3((unsigned)t.nstarts), dim3(1024), lds1, st_, M, ldm, rows, t,
+                       kOrthoMinRatio, Tm, status);
+    prof_end();
+    prof_begin(1, 0.0);
+    hipLaunchKernelGGL(k_cp_update_ortho_ragged, dim3((unsigned)nb, (unsigned)t.nstarts), dim3(64), lds2, st_, Gall,
+                       N, mode, t, lambda, M, ldm, W, ldw, grad, ldg, rows, part, S, Tm, status);
+    prof_end();
+    prof_begin(1, 0.0);
     hipLaunchKernelGGL(k_cp_finish_nn_ragged, dim3((unsigned)t.nstarts), dim3(1024), 0, st_, part, (int)nb,
                        gradsq, W, ldw, rows, t, N, mode, Gall);
     prof_end();

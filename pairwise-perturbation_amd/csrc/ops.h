@@ -37,6 +37,11 @@ constexpr int MAX_ORDER = 8;
 // the floor of a non-negative factor entry (PPALS_NN_FLOOR of the C ABI): not zero, so that no column
 // can die and make Normalize divide by zero
 constexpr double kNnFloor = 1e-16;
+// the orthonormal mode update leaves a factor as it is when the eigenvalues theta of M^T M have
+// theta_min <= theta_max * 2^-40 (PPALS_ORTHO_MIN_RATIO of the C ABI): u kappa(M)^2 is 2^-13 there
+constexpr double kOrthoMinRatio = 0x1p-40;
+// the kind of a mode's update (PPALS_MODE_* of the C ABI)
+enum ModeKind { kModeFree = 0, kModeNonneg = 1, kModeFixed = 2, kModeOrtho = 3 };
 
 // a factor-matrix operand of a Khatri-Rao product: `rows` rows starting at `ptr`, leading dim ld
 // The starts of a multi-start session whose ranks differ (a rank sweep), handed to the ragged ops — and to
@@ -434,6 +439,126 @@ class Ops {
       cp_mode_update_nn(Gall + (size_t)N * t.sq[b], N, mode, t.rank(b), lambda, M + (size_t)t.col[b] * ldm,
                         ldm, W + (size_t)t.col[b] * ldw, ldw, grad + (size_t)t.col[b] * ldg, ldg, rows,
                         gradsq + b, S ? S + t.sq[b] : nullptr);
+  }
+  // One whole single-rank ORTHONORMAL mode update per start (PPALS_MODE_ORTHO; the layout of the ragged ops
+  // above — an ordinary session is a table of one start): with S = Hadamard_{j != mode} G_j + lambda I,
+  //   grad = -M + W_old S (as for every kind), gradsq[b] = sum grad_b^2,
+  //   W_b <- M_b (M_b^T M_b)^(-1/2) = M_b U diag(theta^-1/2) U^T, the orthonormal polar factor of M_b in fp64
+  //   (M_b^T M_b = U diag(theta) U^T by a cyclic Jacobi) — unless some theta is not a positive finite number
+  //   or theta_min <= theta_max * kOrthoMinRatio: then the start's factor stays as it is,
+  //   the Gram of the (new) W_b into Gall (computed, not assumed to be I); S (may be nullptr) receives the
+  //   systems. lambda enters S, and so the gradient, only. Ranks <= 64; rows may be below a rank (the factor
+  //   then stays: theta has a zero). Nothing couples two starts; the same state gives the same bits.
+  // This default is built from d2h / h2d and a host loop (what the host stand-in runs, as with
+  // cp_mode_update_nn); the product back end overrides it with three launches.
+  virtual void cp_mode_update_ortho_ragged(double *Gall, int N, int mode, const StartTable &t, double lambda,
+                                           const double *M, int64_t ldm, double *W, int64_t ldw, double *grad,
+                                           int64_t ldg, int64_t rows, double *gradsq, double *S) {
+    if (t.max_rank() > 64) throw Unsupported("ppals: the orthonormal mode update supports R <= 64");
+    for (int b = 0; b < t.nstarts; b++) {
+      const int R = t.rank(b);
+      const size_t RR = (size_t)R * R;
+      double *Gb = Gall + (size_t)N * t.sq[b];
+      const double *Mb = M + (size_t)t.col[b] * ldm;
+      double *Wb = W + (size_t)t.col[b] * ldw, *gb = grad + (size_t)t.col[b] * ldg;
+      double gs = 0;
+      if (rows <= 0) {
+        h2d(gradsq + b, &gs, sizeof(double));
+        gram(Wb, rows, ldw, R, Gb + (size_t)mode * RR);
+        continue;
+      }
+      std::vector<double> g((size_t)N * RR), s(RR, 1.0), m((size_t)ldm * (R - 1) + rows),
+          w((size_t)ldw * (R - 1) + rows), gr((size_t)ldg * (R - 1) + rows);
+      d2h(g.data(), Gb, sizeof(double) * g.size());
+      d2h(m.data(), Mb, sizeof(double) * m.size());
+      d2h(w.data(), Wb, sizeof(double) * w.size());
+      d2h(gr.data(), gb, sizeof(double) * gr.size());
+      for (size_t e = 0; e < RR; e++) {  // the index order of gram_system (als_CP.cxx:219-232)
+        bool first = true;
+        for (int ii = 0; ii < N - 1; ii++) {
+          const double gv = g[(size_t)(ii == mode ? N - 1 : ii) * RR + e];
+          s[e] = first ? gv : s[e] * gv;
+          first = false;
+        }
+        if (e % R == e / R) s[e] += lambda;
+      }
+      for (int r = 0; r < R; r++)
+        for (int64_t x = 0; x < rows; x++) {
+          double acc = 0;
+          for (int q = 0; q < R; q++) acc += w[x + ldw * q] * s[q + (size_t)R * r];
+          const double gv = -m[x + ldm * r] + acc;
+          gr[x + ldg * r] = gv;
+          gs += gv * gv;
+        }
+      // C = M^T M, then the cyclic Jacobi C = U diag(theta) U^T (row-cyclic order, plain C++)
+      std::vector<double> c(RR), u(RR, 0.0), tm(RR);
+      for (int p = 0; p < R; p++)
+        for (int q = p; q < R; q++) {
+          double acc = 0;
+          for (int64_t x = 0; x < rows; x++) acc += m[x + ldm * p] * m[x + ldm * q];
+          c[p + (size_t)R * q] = c[q + (size_t)R * p] = acc;
+        }
+      for (int k = 0; k < R; k++) u[k + (size_t)R * k] = 1.0;
+      for (int sweep = 0; sweep < 60; sweep++) {
+        double off = 0, diag = 0;
+        for (int p = 0; p < R; p++)
+          for (int q = 0; q < R; q++) (p == q ? diag : off) += c[p + (size_t)R * q] * c[p + (size_t)R * q];
+        if (!(off > 1e-30 * diag)) break;  // (converged, or NaN: the rule below refuses it)
+        for (int p = 0; p < R; p++)
+          for (int q = p + 1; q < R; q++) {
+            const double apq = c[p + (size_t)R * q];
+            if (apq == 0.0) continue;
+            const double theta = (c[q + (size_t)R * q] - c[p + (size_t)R * p]) / (2.0 * apq);
+            const double tt = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+            const double cc = 1.0 / std::sqrt(tt * tt + 1.0), sn = tt * cc;
+            for (int k = 0; k < R; k++) {  // C <- C J, U <- U J
+              const double akp = c[k + (size_t)R * p], akq = c[k + (size_t)R * q];
+              c[k + (size_t)R * p] = cc * akp - sn * akq;
+              c[k + (size_t)R * q] = sn * akp + cc * akq;
+              const double ukp = u[k + (size_t)R * p], ukq = u[k + (size_t)R * q];
+              u[k + (size_t)R * p] = cc * ukp - sn * ukq;
+              u[k + (size_t)R * q] = sn * ukp + cc * ukq;
+            }
+            for (int k = 0; k < R; k++) {  // C <- J^T C
+              const double apk = c[p + (size_t)R * k], aqk = c[q + (size_t)R * k];
+              c[p + (size_t)R * k] = cc * apk - sn * aqk;
+              c[q + (size_t)R * k] = sn * apk + cc * aqk;
+            }
+          }
+      }
+      double off_end = 0, diag_end = 0;  // (not converged after the last sweep: the factor stays)
+      for (int p = 0; p < R; p++)
+        for (int q = 0; q < R; q++) (p == q ? diag_end : off_end) += c[p + (size_t)R * q] * c[p + (size_t)R * q];
+      bool good = off_end <= 1e-30 * diag_end || off_end == 0.0;
+      double tmin = 1.79769313486231570e308, tmax = 0;
+      for (int k = 0; k < R; k++) {
+        const double th = c[k + (size_t)R * k];
+        if (!(th > 0) || th > 1.79769313486231570e308) good = false;
+        tmin = th < tmin ? th : tmin;
+        tmax = th > tmax ? th : tmax;
+      }
+      if (good && tmin <= tmax * kOrthoMinRatio) good = false;
+      if (good) {
+        for (int i = 0; i < R; i++)
+          for (int j = 0; j < R; j++) {
+            double acc = 0;
+            for (int k = 0; k < R; k++)
+              acc += u[i + (size_t)R * k] * (1.0 / std::sqrt(c[k + (size_t)R * k])) * u[j + (size_t)R * k];
+            tm[i + (size_t)R * j] = acc;
+          }
+        for (int r = 0; r < R; r++)
+          for (int64_t x = 0; x < rows; x++) {
+            double acc = 0;
+            for (int q = 0; q < R; q++) acc += m[x + ldm * q] * tm[q + (size_t)R * r];
+            w[x + ldw * r] = acc;
+          }
+        h2d(Wb, w.data(), sizeof(double) * w.size());
+      }
+      h2d(gb, gr.data(), sizeof(double) * gr.size());
+      h2d(gradsq + b, &gs, sizeof(double));
+      if (S) h2d(S + t.sq[b], s.data(), sizeof(double) * RR);
+      gram(Wb, rows, ldw, R, Gb + (size_t)mode * RR);
+    }
   }
   // G_b = W_b^T W_b of the same column blocks into the session's Gram store: Gram (start b, mode) at
   // Gall + N t.sq[b] + mode R_b^2

@@ -72,6 +72,10 @@ static int fail(int code, const char *msg) {
   g_err = msg;
   return code;
 }
+static int fail_fn(int code, const char *fn, const char *what) {
+  g_err = std::string(fn) + ": " + what;
+  return code;
+}
 
 extern "C" {
 
@@ -381,12 +385,19 @@ static_assert(PPALS_NN_FLOOR == ppals::kNnFloor, "the ABI's floor is the one the
 int ppals_cp_set_factors(ppals_cp *s, const double *Wflat, const double *gradWflat) {
   if (!s || !s->eng || !Wflat) return fail(PPALS_ERR_ARG, "NULL argument");
   API_BEGIN
-  if (s->eng->nonneg()) {  // Wflat is on the host: looked at here, before anything is uploaded
-    size_t n = 0;
-    for (int i = 0; i < s->eng->order(); i++) n += (size_t)s->eng->tensor().glens[i] * s->eng->rank_r();
-    for (size_t e = 0; e < n; e++)
-      if (!(Wflat[e] >= 0) || !std::isfinite(Wflat[e]))
-        return fail(PPALS_ERR_ARG, "ppals_cp_set_factors: a non-negative session takes finite factors >= 0");
+  if (s->eng->nonneg_modes()) {  // Wflat is on the host: looked at here, before anything is uploaded
+    const bool all = s->eng->nonneg();
+    size_t at = 0;
+    for (int i = 0; i < s->eng->order(); i++) {  // (the NONNEG modes' blocks)
+      const size_t n = (size_t)s->eng->tensor().glens[i] * s->eng->rank_r();
+      if (s->eng->mode_kind(i) == ppals::kModeNonneg)
+        for (size_t e = at; e < at + n; e++)
+          if (!(Wflat[e] >= 0) || !std::isfinite(Wflat[e]))
+            return fail(PPALS_ERR_ARG,
+                        all ? "ppals_cp_set_factors: a non-negative session takes finite factors >= 0"
+                            : "ppals_cp_set_factors: a non-negative mode takes a finite factor >= 0");
+      at += n;
+    }
   }
   s->eng->set_factors(Wflat, gradWflat);
   return PPALS_OK;
@@ -413,15 +424,52 @@ int ppals_cp_set_nonneg(ppals_cp *s, int on) {
   if (!s || !s->eng) return fail(PPALS_ERR_ARG, "NULL session");
   API_BEGIN
   const bool was = s->eng->nonneg();
+  int before[ppals::MAX_ORDER];  // (all FREE unless ppals_cp_set_mode_constraints was used)
+  for (int i = 0; i < s->eng->order(); i++) before[i] = s->eng->mode_kind(i);
   s->eng->set_nonneg(on != 0);
   if (on && !was && !s->eng->factors_nonneg()) {
-    s->eng->set_nonneg(false);
+    s->eng->restore_mode_kinds(before);
     return fail(PPALS_ERR_ARG, "ppals_cp_set_nonneg: the session's factors have a negative or non-finite entry");
   }
   return PPALS_OK;
   API_END(PPALS_ERR_HIP)
 }
 int ppals_cp_get_nonneg(const ppals_cp *s) { return s && s->eng ? (s->eng->nonneg() ? 1 : 0) : PPALS_ERR_ARG; }
+static_assert(PPALS_ORTHO_MIN_RATIO == ppals::kOrthoMinRatio, "the ABI's ratio is the one the update applies");
+static_assert(PPALS_MODE_FREE == ppals::kModeFree && PPALS_MODE_NONNEG == ppals::kModeNonneg &&
+                  PPALS_MODE_FIXED == ppals::kModeFixed && PPALS_MODE_ORTHO == ppals::kModeOrtho,
+              "the ABI's kinds are the engine's");
+// (both kinds of session: everything is refused before the engine changes anything)
+static int set_mode_constraints(CpEngine *e, const int *kinds, const char *fn, const char *whose) {
+  if (!e) return fail_fn(PPALS_ERR_ARG, fn, "NULL session");
+  if (!kinds) return fail_fn(PPALS_ERR_ARG, fn, "kinds is NULL");
+  API_BEGIN
+  std::string why;
+  if (const int rc = e->check_mode_kinds(kinds, &why))
+    return fail_fn(rc == 2 ? PPALS_ERR_UNSUPPORTED : PPALS_ERR_ARG, fn, why.c_str());
+  unsigned look = 0;  // modes that become NONNEG: their factors are looked at, as ppals_cp_set_nonneg does
+  for (int i = 0; i < e->order(); i++)
+    if (kinds[i] == PPALS_MODE_NONNEG && e->mode_kind(i) != ppals::kModeNonneg) look |= 1u << i;
+  if (look && !e->factors_nonneg(look))
+    return fail_fn(PPALS_ERR_ARG, fn,
+                   (std::string(whose) + " of a mode that becomes non-negative have a negative or non-finite entry")
+                       .c_str());
+  e->set_mode_kinds(kinds);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+static int get_mode_constraints(const CpEngine *e, int *kinds, const char *fn) {
+  if (!e) return fail_fn(PPALS_ERR_ARG, fn, "NULL session");
+  if (!kinds) return fail_fn(PPALS_ERR_ARG, fn, "kinds is NULL");
+  for (int i = 0; i < e->order(); i++) kinds[i] = e->mode_kind(i);
+  return PPALS_OK;
+}
+int ppals_cp_set_mode_constraints(ppals_cp *s, const int *kinds) {
+  return set_mode_constraints(s ? s->eng : nullptr, kinds, "ppals_cp_set_mode_constraints", "the session's factors");
+}
+int ppals_cp_get_mode_constraints(const ppals_cp *s, int *kinds) {
+  return get_mode_constraints(s ? s->eng : nullptr, kinds, "ppals_cp_get_mode_constraints");
+}
 int ppals_cp_placement_report(const ppals_cp *s, char *buf, int cap) {
   if (!s || !s->eng || !buf || cap <= 0) return fail(PPALS_ERR_ARG, "NULL argument");
   API_BEGIN
@@ -588,8 +636,13 @@ int ppals_cp_dt(ppals_cp *s, const ppals_cp_opts *o, int *iters) {
   return s->eng->run_dt(to_opts(o), iters);
   API_END(PPALS_ERR_HIP)
 }
+// (an all-NONNEG session keeps the engine's own message)
+static bool mixed_constraints(const CpEngine *e) { return e->any_nonfree() && !e->nonneg(); }
 int ppals_cp_pp(ppals_cp *s, const ppals_cp_opts *o, int *iters) {
   if (!s || !s->eng || !o) return fail(PPALS_ERR_ARG, "NULL argument");
+  if (mixed_constraints(s->eng))
+    return fail_fn(PPALS_ERR_UNSUPPORTED, "ppals_cp_pp",
+                   "a session with constrained modes has no pairwise-perturbation driver");
   API_BEGIN
   return s->eng->run_pp(to_opts(o), iters);
   API_END(PPALS_ERR_HIP)
@@ -597,6 +650,9 @@ int ppals_cp_pp(ppals_cp *s, const ppals_cp_opts *o, int *iters) {
 
 int ppals_cp_pp_partupdate(ppals_cp *s, const ppals_cp_opts *o, int *iters) {
   if (!s || !s->eng || !o) return fail(PPALS_ERR_ARG, "NULL argument");
+  if (mixed_constraints(s->eng))
+    return fail_fn(PPALS_ERR_UNSUPPORTED, "ppals_cp_pp_partupdate",
+                   "a session with constrained modes has no pairwise-perturbation driver");
   API_BEGIN
   return s->eng->run_pp_partupdate(to_opts(o), iters);
   API_END(PPALS_ERR_HIP)
@@ -618,6 +674,9 @@ int ppals_cpd_als_lr(ppals_cp *s, int optimizer, int update_rank, int randomsvd,
   if (update_rank < 1 || update_rank > s->eng->rank_r())
     return fail(PPALS_ERR_ARG, "update_rank must be in [1, R]");
   if (randomsvd < 0 || randomsvd > 1) return fail(PPALS_ERR_ARG, "randomsvd must be 0 or 1");
+  if (mixed_constraints(s->eng))
+    return fail_fn(PPALS_ERR_UNSUPPORTED, "ppals_cpd_als_lr",
+                   "a session with constrained modes has no low-rank-update optimizer");
   API_BEGIN
   CpOpts c = to_opts(o);
   c.update_rank = update_rank;
@@ -711,14 +770,20 @@ int ppals_cp_multi_set_factors(ppals_cp_multi *s, int start, const double *Wflat
   if (int rc = check_start(s, start, true)) return rc;
   if (!Wflat) return fail(PPALS_ERR_ARG, "NULL argument");
   API_BEGIN
-  if (s->eng->nonneg()) {  // Wflat is on the host: looked at here, before anything is uploaded
-    size_t n = 0, rows = 0;  // (the blocks of the starts, each of its own length)
-    for (int i = 0; i < s->eng->order(); i++) rows += (size_t)s->eng->tensor().glens[i];
+  if (s->eng->nonneg_modes()) {  // Wflat is on the host: looked at here, before anything is uploaded
+    const bool all = s->eng->nonneg();
+    size_t at = 0;  // (the blocks of the starts, each of its own length; of those the NONNEG modes' blocks)
     for (int b = start < 0 ? 0 : start; b < (start < 0 ? s->eng->nstarts() : start + 1); b++)
-      n += rows * (size_t)s->eng->start_rank(b);
-    for (size_t e = 0; e < n; e++)
-      if (!(Wflat[e] >= 0) || !std::isfinite(Wflat[e]))
-        return fail(PPALS_ERR_ARG, "ppals_cp_multi_set_factors: a non-negative session takes finite factors >= 0");
+      for (int i = 0; i < s->eng->order(); i++) {
+        const size_t n = (size_t)s->eng->tensor().glens[i] * (size_t)s->eng->start_rank(b);
+        if (s->eng->mode_kind(i) == ppals::kModeNonneg)
+          for (size_t e = at; e < at + n; e++)
+            if (!(Wflat[e] >= 0) || !std::isfinite(Wflat[e]))
+              return fail(PPALS_ERR_ARG,
+                          all ? "ppals_cp_multi_set_factors: a non-negative session takes finite factors >= 0"
+                              : "ppals_cp_multi_set_factors: a non-negative mode takes a finite factor >= 0");
+        at += n;
+      }
   }
   s->eng->set_factors_start(start, Wflat, gradWflat);
   return PPALS_OK;
@@ -752,13 +817,22 @@ int ppals_cp_multi_set_nonneg(ppals_cp_multi *s, int on) {
   if (!s || !s->eng) return fail(PPALS_ERR_ARG, "NULL session");
   API_BEGIN
   const bool was = s->eng->nonneg();
+  int before[ppals::MAX_ORDER];  // (all FREE unless ppals_cp_multi_set_mode_constraints was used)
+  for (int i = 0; i < s->eng->order(); i++) before[i] = s->eng->mode_kind(i);
   s->eng->set_nonneg(on != 0);
   if (on && !was && !s->eng->factors_nonneg()) {
-    s->eng->set_nonneg(false);
+    s->eng->restore_mode_kinds(before);
     return fail(PPALS_ERR_ARG, "ppals_cp_multi_set_nonneg: a start's factors have a negative or non-finite entry");
   }
   return PPALS_OK;
   API_END(PPALS_ERR_HIP)
+}
+int ppals_cp_multi_set_mode_constraints(ppals_cp_multi *s, const int *kinds) {
+  return set_mode_constraints(s ? s->eng : nullptr, kinds, "ppals_cp_multi_set_mode_constraints",
+                              "a start's factors");
+}
+int ppals_cp_multi_get_mode_constraints(const ppals_cp_multi *s, int *kinds) {
+  return get_mode_constraints(s ? s->eng : nullptr, kinds, "ppals_cp_multi_get_mode_constraints");
 }
 int ppals_cp_multi_get_nonneg(const ppals_cp_multi *s) {
   return s && s->eng ? (s->eng->nonneg() ? 1 : 0) : PPALS_ERR_ARG;
@@ -796,6 +870,10 @@ int ppals_cp_multi_take(ppals_cp_multi *s, int start, ppals_cp *dst) {
                   dst->eng->rank_r(), s->eng->start_rank(start));
     return fail(PPALS_ERR_ARG, msg);
   }
+  // (a destination that is NONNEG in every mode keeps the engine's own message)
+  if (!dst->eng->nonneg() && !dst->eng->takes_nonneg_from(*s->eng))
+    return fail_fn(PPALS_ERR_UNSUPPORTED, "ppals_cp_multi_take",
+                   "the destination is non-negative in a mode where the multi-start session is not");
   API_BEGIN
   dst->eng->take_from(*s->eng, start);
   return PPALS_OK;
@@ -803,15 +881,13 @@ int ppals_cp_multi_take(ppals_cp_multi *s, int start, ppals_cp *dst) {
 }
 
 // ------------------------------------------------------------------ hold-out rows per start
-static int fail_fn(int code, const char *fn, const char *what) {
-  g_err = std::string(fn) + ": " + what;
-  return code;
-}
 int ppals_cp_multi_set_holdout(ppals_cp_multi *s, int mode, const uint8_t *keep) {
   const char *fn = "ppals_cp_multi_set_holdout";
   if (!s || !s->eng) return fail_fn(PPALS_ERR_ARG, fn, "NULL session");
   if (keep) {  // (the table is on the host: looked at here, before anything is allocated or launched)
     if (mode < 0 || mode >= s->eng->order()) return fail_fn(PPALS_ERR_ARG, fn, "mode must be in [0, N)");
+    if (s->eng->mode_kind(mode) == ppals::kModeFixed || s->eng->mode_kind(mode) == ppals::kModeOrtho)
+      return fail_fn(PPALS_ERR_UNSUPPORTED, fn, "the hold-out mode cannot be fixed or orthonormal");
     const int64_t n = s->eng->mode_extent(mode);
     for (int b = 0; b < s->eng->nstarts(); b++) {
       bool any = false;
@@ -858,7 +934,7 @@ int ppals_cp_multi_take_predicted(ppals_cp_multi *s, int start, ppals_cp *dst) {
                   s->eng->start_rank(start));
     return fail_fn(PPALS_ERR_ARG, fn, msg);
   }
-  if (dst->eng->nonneg() && !s->eng->nonneg())
+  if (!dst->eng->takes_nonneg_from(*s->eng))
     return fail_fn(PPALS_ERR_UNSUPPORTED, fn,
                    "a non-negative session does not take an unconstrained multi-start's factors");
   API_BEGIN

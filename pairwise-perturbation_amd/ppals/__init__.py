@@ -72,9 +72,21 @@ EXPORTS = [
     "ppals_cp_slice_residuals", "ppals_cp_leverages",
     "ppals_cp_multi_set_holdout", "ppals_cp_multi_get_holdout", "ppals_cp_multi_heldout_scores",
     "ppals_cp_multi_take_predicted",
+    "ppals_cp_set_mode_constraints", "ppals_cp_get_mode_constraints",
+    "ppals_cp_multi_set_mode_constraints", "ppals_cp_multi_get_mode_constraints",
 ]
+MODE_FREE, MODE_NONNEG, MODE_FIXED, MODE_ORTHO = 0, 1, 2, 3  # PPALS_MODE_*
+MODE_KINDS = ("free", "nonneg", "fixed", "ortho")
 MODEL, RESIDUAL = 0, 1  # PPALS_MODEL / PPALS_RESIDUAL
 FMS_WEIGHTS = 1  # PPALS_FMS_WEIGHTS
+
+
+def _kinds(kinds, n):
+    """a kind per mode, as ints or as the strings of MODE_KINDS, into a C array of n ints"""
+    kinds = list(kinds)
+    if len(kinds) != n:
+        raise ValueError(f"one kind per mode: {n} expected, {len(kinds)} given")
+    return (C.c_int * n)(*[MODE_KINDS.index(k) if isinstance(k, str) else int(k) for k in kinds])
 
 
 def lib(path=None):
@@ -514,6 +526,19 @@ class CP(_ModelExport, _Impute):
     def nonneg(self):
         return bool(_check(lib().ppals_cp_get_nonneg(self._h)))
 
+    def set_mode_constraints(self, kinds):
+        """one kind per mode, ints (MODE_*) or "free" | "nonneg" | "fixed" | "ortho": the solve, the HALS pass
+        of set_nonneg, no update at all, or orthonormal columns (the polar factor of the mode's MTTKRP). With
+        a fixed or orthonormal mode the sweeps end without Normalize. PP, the low-rank optimizers, more than
+        one rank, and non-negative or orthonormal modes at R > 64 are refused."""
+        _check(lib().ppals_cp_set_mode_constraints(self._h, _kinds(kinds, len(self.lens))))
+
+    @property
+    def mode_constraints(self):
+        out = (C.c_int * len(self.lens))()
+        _check(lib().ppals_cp_get_mode_constraints(self._h, out))
+        return [MODE_KINDS[k] for k in out]
+
     def placement_report(self):
         """where the online placement choice put each root's first-level intermediate (dict)"""
         import json
@@ -750,6 +775,16 @@ class CPMulti:
     def nonneg(self):
         return bool(_check(lib().ppals_cp_multi_get_nonneg(self._h)))
 
+    def set_mode_constraints(self, kinds):
+        """CP.set_mode_constraints for every start: one kind per mode, shared by all starts"""
+        _check(lib().ppals_cp_multi_set_mode_constraints(self._h, _kinds(kinds, len(self.lens))))
+
+    @property
+    def mode_constraints(self):
+        out = (C.c_int * len(self.lens))()
+        _check(lib().ppals_cp_multi_get_mode_constraints(self._h, out))
+        return [MODE_KINDS[k] for k in out]
+
     def sweeps(self, n, lam=0.0):
         _check(lib().ppals_cp_multi_sweeps(self._h, int(n), C.c_double(lam)))
 
@@ -941,6 +976,25 @@ class Tucker(_ModelExport, _Impute):
             self.close()
         except Exception:
             pass
+
+
+def project(ctx, V, mode, W, lam=0.0):
+    """The calibration step: the least-squares scores of the slices of the Tensor V along `mode` under given
+    loadings. W lists one (s_i, R) factor per mode with None at `mode`. A session with every other mode FIXED
+    and zeros in `mode` runs one sweep of cpd_als(0): the MTTKRP of `mode` and the solve of its normal
+    equations (+ lam I), nothing else. Returns the (s_mode, R) scores; closes what it opened."""
+    N = len(V.lens)
+    if len(W) != N or W[mode] is not None or any(w is None for i, w in enumerate(W) if i != mode):
+        raise ValueError("W lists one factor per mode, None at `mode` and only there")
+    R = int(np.shape(W[(mode + 1) % N])[1])
+    s = CP(ctx, V, R)
+    try:
+        s.set_mode_constraints([MODE_FREE if i == mode else MODE_FIXED for i in range(N)])
+        s.set_factors([np.zeros((V.lens[mode], R)) if i == mode else w for i, w in enumerate(W)])
+        s.cpd_als(0, maxiter=0, tol=0.0, lam=lam, resprint=1 << 30)
+        return s.get_factors()[mode]
+    finally:
+        s.close()
 
 
 def split_half(ctx, x, mode, ranks, sweeps, seed=0, dtype=F32, split="interleave"):
