@@ -1783,6 +1783,7 @@ class HipOps : public Ops {
     if (nb > (int64_t)1 << 30) throw std::runtime_error("ppals: mode too long for the non-negative update");
     double *part = (double *)ensure(ws_big2_, ws_big2_sz_, sizeof(double) * (size_t)nb);
     const size_t lds = sizeof(double) * ((size_t)R * R + 64 * (size_t)R);
+    route("update_nn R=%d tiles=%lld", R, (long long)nb);
     hipLaunchKernelGGL(k_cp_update_nn, dim3((unsigned)nb), dim3(64), lds, st_, Gall, N, mode, R, lambda, M,
                        ldm, W, ldw, grad, ldg, rows, part, S, kNnFloor);
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(1024), 0, st_, part, (int)nb, gradsq);
@@ -1810,6 +1811,7 @@ class HipOps : public Ops {
       throw std::runtime_error("ppals: mode too long for the non-negative update");
     double *part = (double *)ensure(ws_big2_, ws_big2_sz_, sizeof(double) * (size_t)nb * nstarts);
     const size_t lds = sizeof(double) * ((size_t)R * R + 64 * (size_t)R);
+    route("update_nn_batched R=%d tiles=%lld starts=%d", R, (long long)nb, nstarts);
     prof_begin(1, 0.0);
     hipLaunchKernelGGL(k_cp_update_nn, dim3((unsigned)nb, (unsigned)nstarts), dim3(64), lds, st_, Gall, N,
                        mode, R, lambda, M, ldm, W, ldw, grad, ldg, rows, part, S, kNnFloor);
@@ -2030,6 +2032,7 @@ class HipOps : public Ops {
       throw std::runtime_error("ppals: mode too long for the non-negative update");
     double *part = (double *)ensure(ws_big2_, ws_big2_sz_, sizeof(double) * (size_t)nb * t.nstarts);
     const size_t lds = sizeof(double) * ((size_t)R * R + 64 * (size_t)R);
+    route("update_nn_ragged rmax=%d tiles=%lld starts=%d", R, (long long)nb, t.nstarts);
     prof_begin(1, 0.0);
     hipLaunchKernelGGL(k_cp_update_nn_ragged, dim3((unsigned)nb, (unsigned)t.nstarts), dim3(64), lds, st_, Gall, N,
                        mode, t, lambda, M, ldm, W, ldw, grad, ldg, rows, part, S, kNnFloor);

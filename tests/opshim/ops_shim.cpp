@@ -1,7 +1,7 @@
 // ops_shim.cpp — TEST INFRASTRUCTURE: a C surface over ppals::Ops for the op-level tests of the
 // contraction kernels (tests/contraction_cases.py), of the mode-update side (tests/update_cases.py),
-// of the Tucker eigen side (tests/tucker_ops_cases.py) and of the tensor streams
-// (tests/stream_cases.py). One source, two libraries: linked against the product's libppals.so it
+// of the Tucker eigen side (tests/tucker_ops_cases.py), of the tensor streams (tests/stream_cases.py)
+// and of the multi-start, constraint and diagnostic ops (tests/multistart_ops_cases.py). One source, two libraries: linked against the product's libppals.so it
 // reaches the HIP kernels as compiled there, linked against the host stand-in it reaches HostOps. No
 // HIP code and no HIP calls here: every device action goes through the Ops.
 // Every function returns 0, or -1 after an exception whose text shim_error() then returns (the
@@ -383,6 +383,114 @@ int shim_krp(void *h, double *out, const double *const *fptr, const int64_t *fro
     const std::vector<FactorRef> f = factors(fptr, frows, fld, nf);
     s->ops->krp(out, f.data(), nf, col0, ncols);
   });
+}
+
+// ---- the multi-start, constraint and diagnostic ops (tests/multistart_ops_cases.py) ----
+// A StartTable crosses as (nstarts, col, sq) and is copied in AS GIVEN (col / sq hold min(max(nstarts, 0), 32)
+// + 1 entries), so that a malformed table reaches the launcher's own check.
+namespace {
+StartTable table(int nstarts, const int *col, const int *sq) {
+  StartTable t;
+  t.nstarts = nstarts;
+  const int n = nstarts < 0 ? 0 : nstarts > kMaxStarts ? kMaxStarts : nstarts;
+  for (int b = 0; b <= n; b++) {
+    t.col[b] = col[b];
+    t.sq[b] = sq[b];
+  }
+  return t;
+}
+Ops::CongruenceSide side(const double *const *w, const int64_t *ld, const int64_t *rows, int cols, int N) {
+  Ops::CongruenceSide s;
+  for (int i = 0; i < MAX_ORDER; i++) {
+    s.w[i] = i < N ? w[i] : nullptr;
+    s.ld[i] = i < N ? ld[i] : 0;
+    s.rows[i] = i < N ? rows[i] : 0;
+  }
+  s.cols = cols;
+  return s;
+}
+}  // namespace
+int shim_cp_mode_update_ragged(void *h, double *Gall, int N, int mode, int nstarts, const int *col, const int *sq,
+                               double lambda, const double *M, int64_t ldm, double *W, int64_t ldw, double *grad,
+                               int64_t ldg, int64_t rows, double *gradsq, double *S, double *Sinv) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] {
+    s->ops->cp_mode_update_ragged(Gall, N, mode, table(nstarts, col, sq), lambda, M, ldm, W, ldw, grad, ldg, rows,
+                                  gradsq, S, Sinv);
+  });
+}
+int shim_gram_ragged(void *h, const double *W, int64_t rows, int64_t ld, int nstarts, const int *col, const int *sq,
+                     int N, int mode, double *Gall) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->gram_ragged(W, rows, ld, table(nstarts, col, sq), N, mode, Gall); });
+}
+int shim_cp_mode_update_nn(void *h, double *Gall, int N, int mode, int R, double lambda, const double *M, int64_t ldm,
+                           double *W, int64_t ldw, double *grad, int64_t ldg, int64_t rows, double *gradsq,
+                           double *S) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] {
+    s->ops->cp_mode_update_nn(Gall, N, mode, R, lambda, M, ldm, W, ldw, grad, ldg, rows, gradsq, S);
+  });
+}
+int shim_cp_mode_update_nn_batched(void *h, double *Gall, int N, int mode, int R, int nstarts, double lambda,
+                                   const double *M, int64_t ldm, double *W, int64_t ldw, double *grad, int64_t ldg,
+                                   int64_t rows, double *gradsq, double *S) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] {
+    s->ops->cp_mode_update_nn_batched(Gall, N, mode, R, nstarts, lambda, M, ldm, W, ldw, grad, ldg, rows, gradsq, S);
+  });
+}
+int shim_cp_mode_update_nn_ragged(void *h, double *Gall, int N, int mode, int nstarts, const int *col, const int *sq,
+                                  double lambda, const double *M, int64_t ldm, double *W, int64_t ldw, double *grad,
+                                  int64_t ldg, int64_t rows, double *gradsq, double *S) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] {
+    s->ops->cp_mode_update_nn_ragged(Gall, N, mode, table(nstarts, col, sq), lambda, M, ldm, W, ldw, grad, ldg, rows,
+                                     gradsq, S);
+  });
+}
+int shim_cp_hold_rows(void *h, double *W, int64_t ldw, double *grad, int64_t ldg, double *scores, int64_t lds,
+                      int64_t rows, int nstarts, const int *col, const int *sq, const uint8_t *keep, unsigned holds,
+                      double *Gall, int N, int mode, double *gradsq) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] {
+    s->ops->cp_hold_rows(W, ldw, grad, ldg, scores, lds, rows, table(nstarts, col, sq), keep, holds, Gall, N, mode,
+                         gradsq);
+  });
+}
+int shim_cp_pinv_ragged(void *h, const double *Gall, int N, int nstarts, const int *col, const int *sq,
+                        double *const *W, const int64_t *rows, double *const *P, int *bad) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->cp_pinv_ragged(Gall, N, table(nstarts, col, sq), W, rows, P, bad); });
+}
+int shim_core_score(void *h, double *core, int R, int N, const int *bad, double *cc) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->core_score(core, R, N, bad, cc); });
+}
+int shim_factor_congruence_work(void *h, int N, const double *const *aw, const int64_t *ald, const int64_t *arows,
+                                int acols, const double *const *bw, const int64_t *bld, const int64_t *brows,
+                                int bcols, int64_t *bytes) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] {
+    *bytes = (int64_t)s->ops->factor_congruence_work(N, side(aw, ald, arows, acols, N), side(bw, bld, brows, bcols, N));
+  });
+}
+int shim_factor_congruence(void *h, int N, const double *const *aw, const int64_t *ald, const int64_t *arows,
+                           int acols, const double *const *bw, const int64_t *bld, const int64_t *brows, int bcols,
+                           unsigned mask, void *work, double *Phi, double *wa, double *wb) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] {
+    s->ops->factor_congruence(N, side(aw, ald, arows, acols, N), side(bw, bld, brows, bcols, N), mask, work, Phi, wa,
+                              wb);
+  });
+}
+int shim_row_dots(void *h, const double *P, const double *W, int64_t rows, int R, int64_t ld, double *out) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->row_dots(P, W, rows, R, ld, out); });
+}
+int shim_fold_slice_sums(void *h, const double *src, const int64_t *lens, int n, double *out) {
+  Shim *s = (Shim *)h;
+  return guarded(s, [&] { s->ops->fold_slice_sums(src, lens, n, out); });
 }
 
 // the route log (ops.h): attach (on != 0) or detach, read as one newline-joined string, clear

@@ -81,6 +81,24 @@ _SIGS = {
     "shim_pad_layout": [_P, _P, _I, _I64, _I64, _I64, _I64, _P],
     "shim_unpack_shards": [_P, _P, _I, _I64, _I64, _I64, _I, _I64, _P],
     "shim_krp": [_P, _P, C.POINTER(_P), C.POINTER(_I64), C.POINTER(_I64), _I, _I, _I],
+    "shim_cp_mode_update_ragged": [_P, _P, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _D, _P, _I64, _P, _I64, _P, _I64,
+                                   _I64, _P, _P, _P],
+    "shim_gram_ragged": [_P, _P, _I64, _I64, _I, C.POINTER(_I), C.POINTER(_I), _I, _I, _P],
+    "shim_cp_mode_update_nn": [_P, _P, _I, _I, _I, _D, _P, _I64, _P, _I64, _P, _I64, _I64, _P, _P],
+    "shim_cp_mode_update_nn_batched": [_P, _P, _I, _I, _I, _I, _D, _P, _I64, _P, _I64, _P, _I64, _I64, _P, _P],
+    "shim_cp_mode_update_nn_ragged": [_P, _P, _I, _I, _I, C.POINTER(_I), C.POINTER(_I), _D, _P, _I64, _P, _I64, _P,
+                                      _I64, _I64, _P, _P],
+    "shim_cp_hold_rows": [_P, _P, _I64, _P, _I64, _P, _I64, _I64, _I, C.POINTER(_I), C.POINTER(_I), _P, _U, _P, _I, _I,
+                          _P],
+    "shim_cp_pinv_ragged": [_P, _P, _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_P), C.POINTER(_I64),
+                            C.POINTER(_P), _P],
+    "shim_core_score": [_P, _P, _I, _I, _P, _P],
+    "shim_factor_congruence_work": [_P, _I, C.POINTER(_P), C.POINTER(_I64), C.POINTER(_I64), _I, C.POINTER(_P),
+                                    C.POINTER(_I64), C.POINTER(_I64), _I, C.POINTER(_I64)],
+    "shim_factor_congruence": [_P, _I, C.POINTER(_P), C.POINTER(_I64), C.POINTER(_I64), _I, C.POINTER(_P),
+                               C.POINTER(_I64), C.POINTER(_I64), _I, _U, _P, _P, _P, _P],
+    "shim_row_dots": [_P, _P, _P, _I64, _I, _I64, _P],
+    "shim_fold_slice_sums": [_P, _P, C.POINTER(_I64), _I, _P],
 }
 
 
@@ -374,6 +392,60 @@ class Shim:
 
     def krp(self, out, factors, col0, ncols):
         self._ck(self.lib.shim_krp(self.h, out, *self._factors(factors), col0, ncols))
+
+    # ---- the multi-start, constraint and diagnostic ops (tests/multistart_ops_cases.py)
+    # table: (nstarts, col, sq), handed on as given; side: (list of pointers, list of ld, list of rows, cols)
+    @staticmethod
+    def _table(t):
+        return t[0], _arr(_I, list(t[1])), _arr(_I, list(t[2]))
+
+    def cp_mode_update_ragged(self, Gall, N, mode, t, lam, M, ldm, W, ldw, grad, ldg, rows, gradsq, S, Sinv):
+        self._ck(self.lib.shim_cp_mode_update_ragged(self.h, Gall, N, mode, *self._table(t), lam, M, ldm, W, ldw, grad,
+                                                     ldg, rows, gradsq, S, Sinv))
+
+    def gram_ragged(self, W, rows, ld, t, N, mode, Gall):
+        self._ck(self.lib.shim_gram_ragged(self.h, W, rows, ld, *self._table(t), N, mode, Gall))
+
+    def cp_mode_update_nn(self, Gall, N, mode, R, lam, M, ldm, W, ldw, grad, ldg, rows, gradsq, S):
+        self._ck(self.lib.shim_cp_mode_update_nn(self.h, Gall, N, mode, R, lam, M, ldm, W, ldw, grad, ldg, rows,
+                                                 gradsq, S))
+
+    def cp_mode_update_nn_batched(self, Gall, N, mode, R, nstarts, lam, M, ldm, W, ldw, grad, ldg, rows, gradsq, S):
+        self._ck(self.lib.shim_cp_mode_update_nn_batched(self.h, Gall, N, mode, R, nstarts, lam, M, ldm, W, ldw, grad,
+                                                         ldg, rows, gradsq, S))
+
+    def cp_mode_update_nn_ragged(self, Gall, N, mode, t, lam, M, ldm, W, ldw, grad, ldg, rows, gradsq, S):
+        self._ck(self.lib.shim_cp_mode_update_nn_ragged(self.h, Gall, N, mode, *self._table(t), lam, M, ldm, W, ldw,
+                                                        grad, ldg, rows, gradsq, S))
+
+    def cp_hold_rows(self, W, ldw, grad, ldg, scores, lds, rows, t, keep, holds, Gall, N, mode, gradsq):
+        self._ck(self.lib.shim_cp_hold_rows(self.h, W, ldw, grad, ldg, scores, lds, rows, *self._table(t), keep, holds,
+                                            Gall, N, mode, gradsq))
+
+    def cp_pinv_ragged(self, Gall, N, t, W, rows, P, bad):
+        self._ck(self.lib.shim_cp_pinv_ragged(self.h, Gall, N, *self._table(t), _arr(_P, W), _arr(_I64, rows),
+                                              _arr(_P, P), bad))
+
+    def core_score(self, core, R, N, bad, cc):
+        self._ck(self.lib.shim_core_score(self.h, core, R, N, bad, cc))
+
+    @staticmethod
+    def _side(s):
+        return _arr(_P, s[0]), _arr(_I64, s[1]), _arr(_I64, s[2]), s[3]
+
+    def factor_congruence_work(self, N, a, b):
+        n = _I64(0)
+        self._ck(self.lib.shim_factor_congruence_work(self.h, N, *self._side(a), *self._side(b), C.byref(n)))
+        return n.value
+
+    def factor_congruence(self, N, a, b, mask, work, Phi, wa, wb):
+        self._ck(self.lib.shim_factor_congruence(self.h, N, *self._side(a), *self._side(b), mask, work, Phi, wa, wb))
+
+    def row_dots(self, P, W, rows, R, ld, out):
+        self._ck(self.lib.shim_row_dots(self.h, P, W, rows, R, ld, out))
+
+    def fold_slice_sums(self, src, lens, out):
+        self._ck(self.lib.shim_fold_slice_sums(self.h, src, _arr(_I64, list(lens)), len(lens), out))
 
 
 def compute_units():
