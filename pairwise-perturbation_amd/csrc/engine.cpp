@@ -297,6 +297,7 @@ CpEngine::CpEngine(Ops &ops, Comm &comm, const TensorDesc &V, int R, int nstarts
   if (const char *e = std::getenv("PPALS_TEST_BLOCKED_UPDATE")) test_blocks_ = std::atoi(e);
   if (N_ < 3) schedule_ = 0;
   if (const char *e = std::getenv("PPALS_PLACE_TUNE")) ms_tune_enabled_ = std::atoi(e) != 0;
+  if (const char *e = std::getenv("PPALS_PACK_LAYOUT")) pack_mode_ = std::atoi(e) == 0 ? 0 : (std::atoi(e) == 1 ? 1 : -1);
   if (N_ >= 3) {  // multi-sweep structures exist for every session so the schedule can be switched
     ms_set_roots(ms_choose_roots());
     ms_scales_ = (double *)ops_.alloc(sizeof(double) * 32);
@@ -329,6 +330,13 @@ CpEngine::CpEngine(Ops &ops, Comm &comm, const TensorDesc &V, int R, int nstarts
       ms_X_alt_ = ops_.try_alloc(xmax + ms_X_slack());
   }
   ensure_transposed();
+  // the packed twins of the multi-sweep roots: set-up as well (several GB each at the headline)
+  if (schedule_ == 1 && N_ >= 3)
+    for (int r = 0; r < N_; r++) {
+      ScanPlan pl;
+      PackedSrc pk;
+      if (!ms_set_excluded(r, ms_k_, ms_excl_) && plan_scan(r, ms_k_, false, pl) && pl.Lc > 1) packed_for(pl, pk);
+    }
   if (place) {
     ms_X_base_ = big_alloc(xmax + ms_X_slack());
     ms_X_cap_ = xmax + ms_X_slack();
@@ -394,6 +402,7 @@ CpEngine::~CpEngine() {
   ops_.free(hold_keep_dev_);
   ops_.free(hold_scores_);
   ops_.free(Pbuf_);
+  packs_release();
   for (auto &l : lay_)
     if (l.owned) ops_.free(l.ptr);
   for (auto &ex : ms_place_)
@@ -432,6 +441,16 @@ void CpEngine::fill_layout(const Layout &l) {
     ops_.transpose2d(V_.data, V_.dtype, rows, cols, l.ptr);
   else
     ops_.pad_layout(V_.data, V_.dtype, rows, cols, l.blk, l.ld, l.ptr);
+}
+
+bool CpEngine::optional_fits(size_t bytes) {
+  const size_t esz = dtype_size(V_.dtype);
+  int64_t min_ext = ext(0);
+  for (int m = 1; m < N_; m++) min_ext = std::min(min_ext, ext(m));
+  const size_t xbytes_max = (size_t)(V_.nloc / std::max<int64_t>(1, min_ext)) * R_ * esz;
+  const size_t reserve = 3 * xbytes_max + ms_X_slack() + ((size_t)1 << 30);
+  const size_t avail = ops_.mem_available();
+  return avail == (size_t)-1 || avail >= bytes + reserve;
 }
 
 void CpEngine::ensure_transposed() {
@@ -485,14 +504,7 @@ void CpEngine::ensure_transposed() {
   // size, tree nodes / pair operators (a few per cent of that) and a margin. (A Tucker session on
   // the same tensor, or a second CP session, may still find the device full: big_alloc then gives
   // the optional copies back.)
-  int64_t min_ext = ext(0);
-  for (int m = 1; m < N_; m++) min_ext = std::min(min_ext, ext(m));
-  const size_t xbytes_max = (size_t)(V_.nloc / std::max<int64_t>(1, min_ext)) * R_ * esz;
-  const size_t reserve = 3 * xbytes_max + ms_X_slack() + ((size_t)1 << 30);
-  auto fits = [&](size_t bytes) {
-    const size_t avail = ops_.mem_available();
-    return avail == (size_t)-1 || avail >= bytes + reserve;
-  };
+  auto fits = [&](size_t bytes) { return optional_fits(bytes); };
   if (!fits(bytes_of(t))) return;
   t.ptr = ops_.try_alloc(bytes_of(t));
   if (!t.ptr) return;
@@ -575,6 +587,101 @@ bool CpEngine::plan_scan(int first, int k, bool natural_only, ScanPlan &plan) {
   return true;
 }
 
+// Packed twins (ops.h PackedSrc, kernels_pack.hip.h): a lossless 3.5-byte-per-element copy of an
+// unpadded fp32 layout in the block order of ONE scan shape, which the one-n-tile scan then reads
+// instead of the layout — the scan is HBM-bound, the tensor does not change between sweeps, and the
+// copy is made once like the second resident layout. Optional like the padded third copy: taken
+// only if it fits behind what the session must still allocate, given back by big_alloc first.
+// Every root of the single-mode multi-sweep schedule has its own scan shape, hence its own twin
+// (order 4, s = 200: four of 5.6 GB beside two layouts of 6.4 GB). All or nothing per twin: one
+// block whose top bytes span 16 values or more (mixed signs, zeros beside large values) and the
+// scan reads the plain layout, as does every launch the packed kernel does not serve (ops.h).
+// PPALS_PACK_LAYOUT=0 never packs, =1 packs whatever the size (tests), default: tensors of at
+// least 100 MB. Sharded, multi-start and rank-sweep sessions do not pack; a session whose tensor
+// keeps being rewritten (masked EM) stops packing at the third rewrite.
+namespace {
+// names the packed twin for the scans inside a scope and takes it back on every way out
+struct PackedScope {
+  Ops &ops;
+  PackedScope(Ops &o, const PackedSrc *pk) : ops(o) { ops.scan_packed_source(pk); }
+  ~PackedScope() { ops.scan_packed_source(nullptr); }
+};
+}  // namespace
+
+void CpEngine::packs_release() {
+  for (auto &t : packs_) {
+    ops_.free(t.data);
+    ops_.free(t.bases);
+  }
+  packs_.clear();
+}
+
+bool CpEngine::pack_fill(PackedTwin &t) {
+  const int spread = ops_.pack_layout(t.src, V_.dtype, t.L, t.J, t.T, t.data, t.bases);
+  if (spread >= 0 && spread < PACK_WINDOW) return true;
+  ops_.free(t.data);
+  ops_.free(t.bases);
+  t.data = t.bases = nullptr;
+  t.bytes = 0;
+  t.reason = spread < 0 ? "scan shape has no packed route"
+                        : "top bytes of a block span " + std::to_string(spread + 1) + " values (window 16)";
+  return false;
+}
+
+const PackedSrc *CpEngine::packed_for(const ScanPlan &pl, PackedSrc &out) {
+  if (pack_off_reason_.empty()) {
+    if (pack_mode_ == 0) pack_off_reason_ = "PPALS_PACK_LAYOUT=0";
+    else if (V_.dtype != F32) pack_off_reason_ = "not eligible: storage is not fp32";
+    else if (R_ > 16) pack_off_reason_ = "not eligible: more than 16 result columns";
+    else if (dist_) pack_off_reason_ = "not eligible: sharded session";
+    else if (multi_) pack_off_reason_ = "not eligible: multi-start session";
+    else if (pack_mode_ != 1 && (double)V_.nloc * 4.0 < 1e8) pack_off_reason_ = "tensor below 100 MB";
+  }
+  if (!pack_off_reason_.empty()) return nullptr;
+  const int li = (int)(pl.lay - lay_.data());
+  PackedTwin *t = nullptr;
+  for (auto &c : packs_)
+    if (c.layout == li && c.L == pl.L && c.J == pl.J && c.T == pl.T) t = &c;
+  if (!t) {
+    PackedTwin n;
+    n.layout = li;
+    n.src = pl.lay->ptr;
+    n.L = pl.L;
+    n.J = pl.J;
+    n.T = pl.T;
+    const size_t db = pack_data_bytes(n.L, n.J, n.T), bb = pack_base_bytes(n.L, n.J, n.T);
+    if (pl.lay->q > 0) {
+      n.reason = "padded layout";
+    } else if (n.L < 4 || n.L % 4) {
+      n.reason = "scan shape has no packed route";  // (no whole lanes of 4 rows)
+    } else if (pack_mode_ != 1 && db + bb >= (size_t)n.L * (size_t)n.J * (size_t)n.T * 4) {
+      n.reason = "row tiles would pad away what packing saves";  // (a batch ends with a whole tile of 256 rows)
+    } else if (!optional_fits(db + bb)) {
+      n.reason = "no room beside what the session still allocates";
+    } else {
+      n.data = ops_.try_alloc(db);
+      n.bases = n.data ? ops_.try_alloc(bb) : nullptr;
+      if (!n.bases) {
+        ops_.free(n.data);
+        n.data = nullptr;
+        n.reason = "allocation failed";
+      } else {
+        n.bytes = db + bb;
+        pack_fill(n);
+      }
+    }
+    packs_.push_back(n);
+    t = &packs_.back();
+  }
+  if (!t->data) return nullptr;
+  out.data = t->data;
+  out.bases = t->bases;
+  out.L = t->L;
+  out.J = t->J;
+  out.T = t->T;
+  return &out;
+}
+
 // The tensor handle stays writable while sessions exist (ppals_tensor_fill_*/upload). Everything
 // a session derived from the old contents — the second resident layout, tree nodes, the
 // multi-sweep intermediate, PP operators — is rebuilt / dropped when the generation moved.
@@ -584,6 +691,24 @@ void CpEngine::check_tensor_generation() {
   tensor_gen_ = *V_.generation;
   for (const auto &l : lay_)
     if (l.owned) fill_layout(l);
+  // packed twins: pre-pass and pack again; a twin that no longer qualifies is dropped, one that was
+  // refused for its values gets another look at its next scan. The third rewrite ends packing.
+  if (++pack_regen_ >= 3) {
+    ops_.sync();
+    packs_release();
+    if (pack_off_reason_.empty()) pack_off_reason_ = "tensor rewritten repeatedly";
+  } else {
+    ops_.sync();
+    for (size_t k = 0; k < packs_.size();) {
+      if (packs_[k].data && pack_fill(packs_[k])) {
+        k++;
+      } else if (packs_[k].data == nullptr && packs_[k].reason.compare(0, 9, "top bytes") != 0) {
+        k++;  // (refused for its shape or for memory: that has not changed)
+      } else {
+        packs_.erase(packs_.begin() + k);
+      }
+    }
+  }
   for (auto &n : nodes_) n.valid = false;
   ms_invalidate();
   pp_clear();
@@ -654,6 +779,8 @@ void CpEngine::compute_node(int idx) {
     } else {
       if (pl.T != 1 || pl.Lc != n.elems || pl.J != J)
         throw std::runtime_error("ppals: internal error (tree node scan shape)");
+      PackedSrc pk_store;
+      PackedScope scope(ops_, packed_for(pl, pk_store));
       ops_.scan_contract(pl.lay->ptr, V_.dtype, pl.L, J, 1, f, nf, R_, n.buf, F64, n.elems, n.elems,
                          pl.pad);
     }
@@ -1462,6 +1589,14 @@ void *CpEngine::big_alloc(size_t bytes) {
       ms_X_alt_ = nullptr;
       continue;
     }
+    bool had_packs = false;
+    for (const auto &t : packs_) had_packs = had_packs || t.data;
+    if (had_packs) {  // the packed twins go first, and for good: a layout serves every scan, a twin one
+      ops_.sync();
+      packs_release();
+      pack_off_reason_ = "given back for a mandatory buffer";
+      continue;
+    }
     if (lay_.size() > 1 && lay_.back().owned) {
       ops_.sync();
       ops_.free(lay_.back().ptr);
@@ -1527,10 +1662,13 @@ void CpEngine::ms_start_step(int first) {
   ms_X_.contracted = mask;
   if ((size_t)L * T * R_ * dtype_size(ms_X_.dt) != xbytes)
     throw std::runtime_error("ppals: internal error (first-level intermediate size)");
+  PackedSrc pk_store;
+  const PackedSrc *pk = pl.Lc > 1 ? packed_for(pl, pk_store) : nullptr;
   auto launch_scan = [&](int blk, int64_t off, int nt) {
     ms_X_.buf = ms_X_override_ ? (char *)ms_X_override_
                                : (char *)(blk == 1 && ms_X_alt_ ? ms_X_alt_ : ms_X_base_) + off;
     ops_.scan_store_mode(nt);
+    PackedScope scope(ops_, pk);
     ops_.scan_contract(src, V_.dtype, pl.L, J, T, f.data(), (int)f.size(), R_, ms_X_.buf, ms_X_.dt,
                        L, L * T, pl.pad);
     ops_.scan_store_mode(-1);
@@ -2897,7 +3035,23 @@ std::string CpEngine::placement_report() const {
     out += buf;
     firstrow = false;
   }
-  out += "]}";
+  out += "]";
+  // packed twins of the layouts, one row per scan shape that asked for one
+  out += ", \"packed\": {\"mode\": ";
+  out += pack_mode_ == 0 ? "\"off\"" : (pack_mode_ == 1 ? "\"on\"" : "\"auto\"");
+  out += ", \"refused\": \"" + pack_off_reason_ + "\", \"packed_scans\": " + std::to_string(ops_.scan_packed_launches()) +
+         ", \"layouts\": [";
+  for (size_t k = 0; k < packs_.size(); k++) {
+    const PackedTwin &t = packs_[k];
+    snprintf(buf, sizeof buf,
+             "%s{\"layout\": \"%s\", \"rows\": %lld, \"reduced\": %lld, \"batches\": %lld, \"packed\": %s, "
+             "\"bytes_per_element\": %.4f, \"reason\": \"%s\"}",
+             k ? ", " : "", t.layout == 0 ? "tensor" : (t.layout == 1 ? "second (transposed) copy" : "padded copy"),
+             (long long)t.L, (long long)t.J, (long long)t.T, t.data ? "true" : "false",
+             t.data ? (double)t.bytes / ((double)t.L * (double)t.J * (double)t.T) : 4.0, t.reason.c_str());
+    out += buf;
+  }
+  out += "]}}";
   return out;
 }
 

@@ -532,6 +532,23 @@ class CpEngine {
     size_t bytes = 0;         // of an owned layout
   };
   std::vector<Layout> lay_;
+  // Packed twins of unpadded fp32 layouts (engine.cpp, packed_for): one per (layout, scan shape)
+  // that asked for one, with the reason where there is no copy
+  struct PackedTwin {
+    int layout = 0;             // index into lay_
+    const void *src = nullptr;  // that layout's elements
+    int64_t L = 0, J = 0, T = 0;
+    void *data = nullptr, *bases = nullptr;
+    size_t bytes = 0;
+    std::string reason;         // why there is no copy ("" while there is one)
+  };
+  std::vector<PackedTwin> packs_;
+  int pack_mode_ = -1;            // PPALS_PACK_LAYOUT: 0 never, 1 whatever the size, -1 auto
+  int pack_regen_ = 0;            // times the tensor changed under this session
+  std::string pack_off_reason_;   // why this session does not pack at all ("" while it may)
+  bool optional_fits(size_t bytes);  // an optional copy of `bytes` fits behind what is still to come
+  bool pack_fill(PackedTwin &t);
+  void packs_release();
   int vt_state_ = 0;          // 0 not tried, 1 second layout built, -1 unavailable (disabled / no memory)
   uint64_t tensor_gen_ = 0;   // generation of the tensor contents the layouts and caches were built from
   void ensure_transposed();   // builds lay_[1] (and [2]) once
@@ -544,6 +561,8 @@ class CpEngine {
     std::vector<int> set, kept;  // contracted / kept modes in storage order
   };
   bool plan_scan(int first, int k, bool natural_only, ScanPlan &plan);
+  // the packed twin of plan.lay for plan's scan shape (built at the first request), nullptr: none
+  const PackedSrc *packed_for(const ScanPlan &pl, PackedSrc &out);
   void check_tensor_generation();
   void model_operands(const ModelBox &bx, ModelPlan &mp);  // xq_ / xp_ and the offsets of a grouped plan
   // s x R partials up to this size use one all-reduce + redundant update instead of

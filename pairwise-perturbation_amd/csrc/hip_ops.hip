@@ -17,6 +17,7 @@
 #include "roctx_ranges.h"
 #include "preload_policy.h"
 #include "kernels_scan.hip.h"
+#include "kernels_pack.hip.h"
 #include "kernels_small.hip.h"
 #include "kernels_nn.hip.h"
 #include "kernels_polar.hip.h"
@@ -198,6 +199,7 @@ class HipOps : public Ops {
     }
     if (ws_mttv_) hipFree(ws_mttv_);
     if (ws_pack_) hipFree(ws_pack_);
+    if (pack_spread_) hipFree(pack_spread_);
     if (ws_mv_) hipFree(ws_mv_);
     if (ws_slab_) hipFree(ws_slab_);
     if (ws_krp_) hipFree(ws_krp_);
@@ -975,6 +977,36 @@ class HipOps : public Ops {
     return p;
   }
   void scan_store_mode(int mode) override { scan_nt_mode_ = mode; }
+  void scan_packed_source(const PackedSrc *pk) override {
+    scan_pk_ = pk ? *pk : PackedSrc();
+  }
+  PackedSrc scan_pk_;
+  int64_t scan_pk_launches_ = 0;
+  int64_t scan_packed_launches() override { return scan_pk_launches_; }
+  int *pack_spread_ = nullptr;  // device word of pack_layout's pre-pass
+  int pack_layout(const void *src, int dt, int64_t L, int64_t J, int64_t T, void *data, void *bases) override {
+    // what the packed scan route itself needs (scan_t): fp32, whole lanes of 4 rows, 16-byte aligned
+    // rows, 32-bit tile ids and block counts
+    const int64_t n_mtiles = (L + 255) / 256, nkb = (J + 15) / 16;
+    if (dt != F32 || L < 4 || L % 4 || J < 1 || T < 1 || (((uintptr_t)src) & 15) || n_mtiles * T > 0x7fffffff ||
+        n_mtiles * T * nkb > 0x7fffffff)
+      return -1;
+    if (!pack_spread_) pack_spread_ = (int *)alloc(sizeof(int));
+    const unsigned nblocks = (unsigned)(n_mtiles * T * nkb);
+    HIP_CHECK(hipMemsetAsync(pack_spread_, 0, sizeof(int), st_));
+    hipLaunchKernelGGL(k_pk_prepass, dim3(nblocks), dim3(256), 0, st_, (const float *)src, L, J, (int)n_mtiles,
+                       (int)nkb, (pk_u32 *)bases, pack_spread_);
+    HIP_CHECK(hipGetLastError());
+    int spread = 0;
+    HIP_CHECK(hipMemcpyAsync(&spread, pack_spread_, sizeof(int), hipMemcpyDeviceToHost, st_));
+    HIP_CHECK(hipStreamSynchronize(st_));
+    if (spread >= PACK_WINDOW) return spread;
+    hipLaunchKernelGGL(k_pk_pack, dim3(nblocks), dim3(256), 0, st_, (const float *)src, L, J, (int)n_mtiles, (int)nkb,
+                       pack_tile_bytes(J), (const pk_u32 *)bases, (char *)data);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(st_));
+    return spread;
+  }
   void scan_profile_slot(int slot) override { scan_slot_ = slot == 1 ? 1 : 0; }
   int scan_nt_mode_ = -1;
   size_t mem_available() override {
@@ -1158,7 +1190,6 @@ class HipOps : public Ops {
         const int64_t nblocks = (int64_t)n_mtiles * nsplit * T;
         if (nblocks > 0x7fffffff) throw std::runtime_error("ppals: scan grid too large");
         dim3 grid((unsigned)nblocks);
-        prof_begin(scan_slot_, bytes);
         // persistent launch: ncu*40 workgroups (measured best of 3..40 per CU), each walks over its tiles
         // (fewer tiles than that: every workgroup would take exactly ONE tile and the launch loses what the
         // persistent form is for — the P = 8 shard of cfg2, 3906 tiles: 6 workgroups per CU walking 2.5
@@ -1185,6 +1216,16 @@ class HipOps : public Ops {
         const bool takes_tail = !takes_buf && al && M >= VEC && T == 1 && nsplit == 1 && NT <= 2 &&
                                 d.row_ld == 0 && scan_tail_split<TV>(NT, n_mtiles) >= 0;
         if (takes_tail) nts = false;
+        // the packed twin of this very scan (Ops::scan_packed_source): the one-n-tile fp32 buffer route,
+        // unpadded and without k-split; the same result bits from 3.5 instead of 4 bytes per element
+        bool takes_pk = false;
+        if constexpr (sizeof(TV) == 4)
+          takes_pk = takes_buf && NT == 1 && nsplit == 1 && d.row_ld == 0 && scan_pk_.data && scan_pk_.L == L &&
+                     scan_pk_.J == J && scan_pk_.T == T;
+        // (the profile counts the bytes the launch addresses: the packed source + the result)
+        prof_begin(scan_slot_, takes_pk ? (double)pack_data_bytes(L, J, T) + (double)pack_base_bytes(L, J, T) +
+                                              (double)L * (double)T * ncols * (out32 ? 4.0 : 8.0)
+                                        : bytes);
         // (measured: with NT >= 2 the fp32 build of the buffer variant drops to 2 waves/SIMD and
         // loses to the global-load kernel, so it is used for one n-tile / fp64 storage only)
         // (and: K-split scans of an fp64 tensor — few, long work items of half-size blocks — run
@@ -1195,6 +1236,8 @@ class HipOps : public Ops {
         // 40 HOOI sweeps 0.0446 / 0.0443 s against 0.0442 / 0.0441 s. Not kept.)
         if (takes_tail)
           route("scan.%s.suffix.tail nt=%d from=%d", tname<TV>(), NT, scan_tail_split<TV>(NT, n_mtiles));
+        else if (takes_pk)
+          route("scan.%s.suffix.pk nt=1 nsplit=1 nts=%d pad=0 out32=%d", tname<TV>(), nts ? 1 : 0, out32);
         else if (takes_buf || (al && M >= VEC))
           route("scan.%s.suffix.%s nt=%d nsplit=%d nts=%d pad=%d out32=%d", tname<TV>(), takes_buf ? "buf" : "fast",
                 NT, nsplit, nts ? 1 : 0, pad.ld ? 1 : 0, out32);
@@ -1213,6 +1256,13 @@ class HipOps : public Ops {
             hipLaunchKernelGGL((k_scan_suffix_fast<TV, nt, 9>), grid_t, dim3(256), lds_t, st_, V, M, K, M * K, P,
                                n_mtiles, nsplit, per, nblk, d.p, d.nstride, d.split_stride, d.batch_stride, ncols,
                                d.out32, (int64_t)0, (int64_t)0, tail_from);
+          });
+        } else if (takes_pk) {
+          scan_pk_launches_++;
+          dispatch<5, 1>(nts ? 5 : 1, [&](auto opt) {
+            hipLaunchKernelGGL((k_scan_suffix_pk<opt>), grid_p, dim3(256), 0, st_, (const char *)scan_pk_.data,
+                               (const unsigned int *)scan_pk_.bases, pack_tile_bytes(J), M, (const float *)P, n_mtiles,
+                               nblk, d.p, d.nstride, d.batch_stride, ncols, d.out32, nblocks);
           });
         } else {
           dispatch<1, 2, 3, 4>(NT, [&](auto nt) {

@@ -26,6 +26,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ops.h"
+
 namespace ppals {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -751,6 +753,200 @@ __global__ __launch_bounds__(256) void k_scan_suffix_buf(
     id = nid;
   }
 #undef PPALS_BUF_LOAD
+}
+
+// ---------------------------------------------------------------------------------------------
+// The PACKED form of k_scan_suffix_buf<float, 1, .>: the tensor is read from its lossless 28-bit twin
+// (kernels_pack.hip.h: 3.5 B per element, block-major in this kernel's own unit) — the scan is
+// HBM-bound, so 12.5 % fewer bytes are 12-19 % less time (profiles/pack_scan_bench.md). Everything
+// else is the plain kernel's: persistent tile walk, next-tile prefetch under the epilogue, register
+// double buffer, MFMA order, FLUSH, epilogue and store kinds; the MFMA operands are the same fp32
+// words, so every result bit is the same. One n-tile, no k-split, unpadded (the launcher routes
+// everything else to the plain kernels).
+// Per block a lane issues four b96 loads (one per k-quad) and one b64 load (its codes), each a
+// contiguous run per wave; the block's base word comes through the scalar cache. After the MFMAs of
+// block i the words of block i+1 are rebuilt — per quad 3 VALU operations for the four top bytes
+// (base + code, one per byte) and 6 byte permutes — where the plain kernel copies its registers.
+// Held at the plain kernel's 3 waves per SIMD (the registers would allow 4, measured 1-2 % slower).
+// OPT bit 0: non-temporal tensor loads, bit 2: non-temporal result stores.
+typedef unsigned int scan_u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int scan_u32x3 __attribute__((ext_vector_type(3)));
+template <int OPT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_scan_suffix_pk(
+    const char *__restrict__ Vp, const unsigned int *__restrict__ bases, int64_t tile_bytes, int64_t M,
+    const float *__restrict__ P, int n_mtiles, int nkb, double *__restrict__ out, int64_t out_nstride,
+    int64_t out_batch_stride, int ncols, int out32, int64_t ntiles) {
+  typedef ScanTraits<float> TR;
+  typedef unsigned int u32;
+  constexpr int VEC = 4, FLUSH = SCAN_FLUSH;
+  constexpr int AUXV = (OPT & 1) ? 2 : 0;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane >> 4, j16 = lane & 15;
+  const int voffP = (int)((g * 16 + j16) * VEC * (int)sizeof(float));
+  const int voffC = wave * 512 + lane * 8;
+  const int voffQ = PACK_CODE_BYTES + wave * 768 + lane * 12;
+  const __amdgpu_buffer_rsrc_t rsrcP = __builtin_amdgcn_make_buffer_rsrc(
+      (void *)P, 0, (int)((int64_t)nkb * (4 * 16 * VEC) * (int64_t)sizeof(float)), 0x00020000);
+
+  struct Tile {
+    int64_t m, obase;
+    bool live;
+  };
+  auto decode = [&](int64_t id, Tile &t) {
+    const unsigned b = (unsigned)id;  // (tile ids fit 31 bits: the launcher checks)
+    const int mtile = (int)(b % (unsigned)n_mtiles);
+    const int64_t batch = b / (unsigned)n_mtiles;
+    const int64_t m0 = ((int64_t)mtile * 4 + wave) * (16 * VEC);
+    t.live = m0 < M;  // wave-uniform
+    t.m = m0 + (int64_t)VEC * j16;
+    t.obase = batch * out_batch_stride;
+  };
+  struct Raw {
+    u32 w[12], c[2], b;
+    f32x4 p;
+  };
+  // the descriptor ends with the tile: the absent quads of a short last block read as zero (their
+  // words then decode to a finite value, and the packed Khatri-Rao operand is zero there)
+#define PPALS_PK_LOAD(tile_, kb_, r_)                                                                 \
+  {                                                                                                   \
+    const int t_ = __builtin_amdgcn_readfirstlane((int)(tile_));                                      \
+    const int k_ = __builtin_amdgcn_readfirstlane((int)(kb_));                                        \
+    const int64_t koff_ = (int64_t)k_ * PACK_BLOCK_BYTES;                                             \
+    const __amdgpu_buffer_rsrc_t rs_ = __builtin_amdgcn_make_buffer_rsrc(                             \
+        (void *)(Vp + (int64_t)t_ * tile_bytes + koff_), 0,                                           \
+        (int)min(tile_bytes - koff_, (int64_t)PACK_BLOCK_BYTES), 0x00020000);                         \
+    _Pragma("unroll") for (int u = 0; u < 4; u++) {                                                   \
+      const scan_u32x3 q_ = __builtin_amdgcn_raw_buffer_load_b96(rs_, voffQ, u * PACK_QUAD_BYTES, AUXV); \
+      r_.w[3 * u] = q_[0];                                                                            \
+      r_.w[3 * u + 1] = q_[1];                                                                        \
+      r_.w[3 * u + 2] = q_[2];                                                                        \
+    }                                                                                                 \
+    const scan_u32x2 c_ = __builtin_amdgcn_raw_buffer_load_b64(rs_, voffC, 0, AUXV);                  \
+    r_.c[0] = c_[0];                                                                                  \
+    r_.c[1] = c_[1];                                                                                  \
+    r_.b = bases[(int64_t)t_ * nkb + k_];                                                             \
+    r_.p = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(                           \
+                                         rsrcP, voffP, k_ * (4 * 16 * VEC) * (int)sizeof(float), 0)); \
+  }
+  // the 16 fp32 words of a block. v_perm_b32(hi, lo, sel): selector bytes 0..3 take lo's bytes,
+  // 4..7 hi's, 0x0c gives zero. (base + code <= 255 in every byte: no carries)
+  auto unpack = [](const Raw &r, f32x4(&v)[4]) {
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const u32 cw = r.c[u >> 1];
+      const u32 T = (((u & 1) ? cw >> 4 : cw) & 0x0f0f0f0fu) + r.b;
+      const u32 w0 = r.w[3 * u], w1 = r.w[3 * u + 1], w2 = r.w[3 * u + 2];
+      v[u][0] = __uint_as_float(__builtin_amdgcn_perm(T, w0, 0x04020100u));
+      v[u][1] = __uint_as_float(__builtin_amdgcn_perm(T, w1, 0x05020100u));
+      v[u][2] = __uint_as_float(__builtin_amdgcn_perm(T, w2, 0x06020100u));
+      v[u][3] = __uint_as_float(__builtin_amdgcn_perm(w1, w0, 0x0c0c0703u) |  // w0.b3, w1.b3, 0, 0
+                                __builtin_amdgcn_perm(T, w2, 0x07030c0cu));   // 0, 0, w2.b3, T.b3
+    }
+  };
+
+  Tile cur, nxt;
+  int64_t id = blockIdx.x;
+  for (; id < ntiles; id += gridDim.x) {  // first live tile of this wave
+    decode(id, cur);
+    if (cur.live) break;
+  }
+  if (id >= ntiles || nkb <= 0) return;
+  f32x4 cv[4], cb;
+  {
+    Raw r0;
+    PPALS_PK_LOAD(id, 0, r0);
+    unpack(r0, cv);
+    cb = r0.p;
+  }
+
+  for (;;) {
+    bool has_next = false;
+    int64_t nid = id + gridDim.x;
+    for (; nid < ntiles; nid += gridDim.x) {
+      decode(nid, nxt);
+      if (nxt.live) {
+        has_next = true;
+        break;
+      }
+    }
+    f32x4 acc[VEC];
+    double acc64[VEC][4];
+#pragma unroll
+    for (int a = 0; a < VEC; a++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        acc[a][r] = 0;
+        acc64[a][r] = 0;
+      }
+    for (int kc = 0; kc < nkb; kc += FLUSH) {
+      const int ke = min(nkb, kc + FLUSH);
+      for (int kb = kc; kb < ke; kb++) {
+        Raw nr;
+        // what to request next: the following block of this tile, else the first block of the
+        // next tile, else (very last block of the wave) this block again
+        const bool same = kb + 1 < nkb;
+        const int64_t pt = (same || !has_next) ? id : nid;
+        const int pk = same ? kb + 1 : (has_next ? 0 : kb);
+        PPALS_PK_LOAD(pt, pk, nr);
+        // (the scheduler must not pull the unpacking, and with it the wait for the loads just
+        // issued, up between the MFMAs: block i+1 stays in flight under all MFMAs of block i)
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < VEC; u++)
+#pragma unroll
+          for (int jj = 0; jj < VEC; jj++) acc[jj] = TR::mfma(cb[u], cv[u][jj], acc[jj]);
+        __builtin_amdgcn_sched_barrier(0);
+        unpack(nr, cv);
+        cb = nr.p;
+      }
+#pragma unroll
+      for (int a = 0; a < VEC; a++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          acc64[a][r] += (double)acc[a][r];
+          acc[a][r] = 0;
+        }
+    }
+    // epilogue: as in k_scan_suffix_buf
+    const ScanRowMap rm = scan_row_map<VEC>(cur.m, M, 0, 0);
+    const bool vec_ok = (((cur.obase | out_nstride | rm.mo) & (VEC - 1)) == 0) && rm.nvalid == VEC;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int n = TR::row(lane, r);
+      if (n < ncols && rm.nvalid > 0) {
+        double val[VEC];
+#pragma unroll
+        for (int jj = 0; jj < VEC; jj++) val[jj] = acc64[jj][r];
+        const int64_t idx = cur.obase + (int64_t)n * out_nstride + rm.mo;
+        if (vec_ok && out32) {
+          f32x4 ov;
+#pragma unroll
+          for (int jj = 0; jj < VEC; jj++) ov[jj] = (float)val[jj];
+          if constexpr (OPT & 4)
+            __builtin_nontemporal_store(ov, reinterpret_cast<f32x4 *>(reinterpret_cast<float *>(out) + idx));
+          else
+            *reinterpret_cast<f32x4 *>(reinterpret_cast<float *>(out) + idx) = ov;
+        } else if (vec_ok) {
+#pragma unroll
+          for (int jj = 0; jj < VEC; jj += 2) {
+            f64x2 ov = {val[jj], val[jj + 1]};
+            if constexpr (OPT & 4)
+              __builtin_nontemporal_store(ov, reinterpret_cast<f64x2 *>(out + idx + jj));
+            else
+              *reinterpret_cast<f64x2 *>(out + idx + jj) = ov;
+          }
+        } else {
+#pragma unroll
+          for (int jj = 0; jj < VEC; jj++)
+            if (jj < rm.nvalid) scan_store(out, idx + jj, val[jj], out32);
+        }
+      }
+    }
+    if (!has_next) break;
+    cur = nxt;
+    id = nid;
+  }
+#undef PPALS_PK_LOAD
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -33,6 +33,28 @@ struct RowPad {
   int64_t ld = 0, valid = 0;  // ld == 0: not padded
 };
 
+// The packed (28 bits per element) twin of a resident fp32 layout for ONE scan shape [L, J, T]
+// (format: kernels_pack.hip.h). A block is 256 rows x 16 reduction indices: a code plane and four
+// k-quads; a short last k-block stores only the quads that reach below J.
+constexpr int PACK_BLOCK_BYTES = 14336, PACK_CODE_BYTES = 2048, PACK_QUAD_BYTES = 3072;
+constexpr int PACK_WINDOW = 16;  // top bytes of a block must span fewer values than this
+struct PackedSrc {
+  const void *data = nullptr;   // the blocks: pack_tile_bytes(J) per (row tile, batch)
+  const void *bases = nullptr;  // one 32-bit word per block
+  int64_t L = 0, J = 0, T = 0;
+};
+inline int64_t pack_tile_bytes(int64_t J) {
+  const int64_t kfull = J / 16, rem = J - kfull * 16;
+  return kfull * PACK_BLOCK_BYTES + (rem ? PACK_CODE_BYTES + (rem + 3) / 4 * PACK_QUAD_BYTES : 0);
+}
+inline int64_t pack_tiles(int64_t L, int64_t T) { return (L + 255) / 256 * T; }
+inline size_t pack_data_bytes(int64_t L, int64_t J, int64_t T) {
+  return (size_t)pack_tiles(L, T) * (size_t)pack_tile_bytes(J);
+}
+inline size_t pack_base_bytes(int64_t L, int64_t J, int64_t T) {
+  return (size_t)pack_tiles(L, T) * (size_t)((J + 15) / 16) * 4;
+}
+
 constexpr int MAX_ORDER = 8;
 // the floor of a non-negative factor entry (PPALS_NN_FLOOR of the C ABI): not zero, so that no column
 // can die and make Normalize divide by zero
@@ -158,6 +180,22 @@ class Ops {
   virtual void scan_store_mode(int mode) { (void)mode; }
   // free device memory in bytes, (size_t)-1: unknown / unlimited
   virtual size_t mem_available() { return (size_t)-1; }
+  // Packed twins of fp32 layouts (PackedSrc). pack_layout fills `data` (pack_data_bytes) and `bases`
+  // (pack_base_bytes) from src viewed as [L, J, T] and returns the largest spread of top bytes in
+  // a block; at PACK_WINDOW or above nothing usable was written (the layout does not qualify).
+  // -1: this back end, or this shape, has no packed scans — such a back end never sees a PackedSrc.
+  // Synchronises.
+  virtual int pack_layout(const void * /*src*/, int /*dt*/, int64_t /*L*/, int64_t /*J*/, int64_t /*T*/,
+                          void * /*data*/, void * /*bases*/) {
+    return -1;
+  }
+  // the packed twin of the tensor the NEXT scan_contract calls read (nullptr: none). A scan whose
+  // shape matches and whose launch is eligible (fp32, at most 16 result columns, the buffer-load
+  // route, unpadded, no k-split) reads the twin instead of V; every other scan reads V. The
+  // results are the same bits either way.
+  virtual void scan_packed_source(const PackedSrc * /*pk*/) {}
+  // launches of the packed scan kernel by this back end so far
+  virtual int64_t scan_packed_launches() { return 0; }
 
   // ---- strided device views (ppals_tensor_import_device / _export_device, device_view.h) ----
   // What the runtime knows of a pointer. is_device: device memory of this Ops' device (not host,
