@@ -139,6 +139,58 @@ int ppals_tensor_check_device_view(ppals_tensor *t, int direction, const void *p
                                    const int64_t *box_lo, const int64_t *box_len,
                                    const int64_t *strides);
 int ppals_tensor_norm(ppals_tensor *t, double *out); /* V.norm2(), test_ALS.cxx:328 */
+
+/* ---- centring and scaling in place: PARAFAC preprocessing (R. Bro, A. K. Smilde, "Centering and scaling in
+ * component analysis", J. Chemometrics 17 (2003) 16-33; `nprocess` of the N-way toolbox; no counterpart in the
+ * reference) ----
+ * A constant offset per fibre is not multilinear: "rank-R model + offsets" is not rank R until it has been
+ * centred ACROSS the right mode; scaling WITHIN a mode gives every slice of that mode unit root mean square.
+ * Throughout, the tensor is viewed as [L, J, T], first index fastest: J = lens[mode], L the product of the
+ * extents before `mode`, T of those after it. A fibre of the mode is the J elements with (l, t) fixed, a slice
+ * x the n = L*T elements with j = x. Offsets are L*T doubles, index l + L*t.
+ * Arithmetic: V is read as stored (bf16, fp32 or fp64), widened to fp64, and the new value is rounded ONCE to
+ * the storage type, as ppals_tensor_import_device rounds an fp64 source. Means and sums of squares are formed
+ * in fp64 in a fixed order: the same state gives the same bits on every call; no floating-point atomics.
+ * shift with alpha = +-1 forms v +- o with one fp64 rounding, so shift(offsets, -1) on a copy of the original
+ * tensor gives, bit for bit, what center stored. scale: a slice whose rms is not a positive finite number is
+ * left bit for bit as it is and its scales[x] reports the value as computed (0, inf or NaN). No other special
+ * cases: a NaN in a fibre makes that fibre NaN.
+ * `where` says where the offsets lie. PPALS_HOST: the call returns when the host buffer is filled (center) or
+ * consumed (shift); it uses a temporary device buffer of L*T doubles, freed before it returns. PPALS_DEVICE: the
+ * pointer must be device memory of the context's device with L*T*8 bytes inside its allocation (the checks and
+ * messages of the device views); the call is ordered on `stream` exactly as ppals_tensor_import_device is and
+ * the host does not block; a back end without device views answers PPALS_ERR_UNSUPPORTED. With offsets == NULL
+ * in center, `where` is ignored and the call does not block. All five calls are ordered after the work already
+ * queued on the engine stream, sweeps a session queued asynchronously included.
+ * center, shift, scale and rescale bump the tensor's generation exactly as an import does: every CP and Tucker
+ * session on the tensor rebuilds its other layouts and packed twins at its next read and drops tree nodes,
+ * multi-sweep state and PP operators; a Tucker session also forgets the warm starts of its eigen-steps, so that
+ * its next hosvd / sweeps are bit for bit those of a new session on the new contents. slice_sumsq reads only
+ * and bumps nothing. A centred fp32 tensor has
+ * blocks of mixed sign: the packed 28-bit twin of the CP scans then no longer qualifies and the session reads
+ * the plain layouts (the 537 instead of the 632 sweeps/s class at the headline shape).
+ * The calls take no mask: centring with missing entries belongs inside the EM loop (Bro & Smilde, section 6)
+ * and is not provided.
+ * Refused before anything is launched or allocated, the tensor's bytes and generation untouched, the message
+ * starting with the function's name — PPALS_ERR_ARG: a NULL tensor or a dead handle, mode outside [0, N), a
+ * NULL ss, factors, or offsets in shift, where outside {0, 1}, a non-finite alpha or factors[x], a device
+ * pointer that fails the checks above; PPALS_ERR_UNSUPPORTED: a context of more than one rank (centring across
+ * the sharded mode needs a collective of L*T values; all five calls refuse alike). */
+#define PPALS_HOST 0
+#define PPALS_DEVICE 1
+/* V[l,j,t] <- V[l,j,t] - mean_j V[l,.,t], for every fibre of `mode`.
+ * offsets (may be NULL) receives the L*T means as fp64, index l + L*t. */
+int ppals_tensor_center(ppals_tensor *t, int mode, double *offsets, int where, void *stream);
+/* V[l,j,t] <- V[l,j,t] + alpha * offsets[l + L*t]. alpha = +1 undoes a centring,
+ * alpha = -1 applies a calibration set's means to new data. */
+int ppals_tensor_shift(ppals_tensor *t, int mode, const double *offsets, int where, double alpha, void *stream);
+/* ss[x] = sum over slice x of V^2, host, lens[mode] doubles. Read-only, no generation bump. */
+int ppals_tensor_slice_sumsq(ppals_tensor *t, int mode, double *ss);
+/* rms[x] = sqrt(ss[x] / n). Slice x is multiplied by 1/rms[x].
+ * scales (host, lens[mode] doubles, may be NULL) receives rms. */
+int ppals_tensor_scale(ppals_tensor *t, int mode, double *scales);
+/* slice x is multiplied by factors[x] (host). Undoes a scaling, or applies a calibration set's scaling. */
+int ppals_tensor_rescale(ppals_tensor *t, int mode, const double *factors);
 /* same counter-based generator for host-side factor initialisation (W.fill_random(0,1)) */
 void ppals_fill_uniform_host(double *out, int64_t n, uint64_t seed, uint64_t offset, double lo,
                              double hi);

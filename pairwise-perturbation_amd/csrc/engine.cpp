@@ -230,6 +230,48 @@ double tensor_norm(Ops &ops, Comm &comm, const TensorDesc &V) {
   return std::sqrt(h);
 }
 
+PrepShape prep_shape(const TensorDesc &V, int mode) {
+  PrepShape s;
+  for (int i = 0; i < mode; i++) s.L *= V.llens[i];
+  s.J = V.llens[mode];
+  for (int i = mode + 1; i < V.order; i++) s.T *= V.llens[i];
+  return s;
+}
+void tensor_center(Ops &ops, const TensorDesc &V, int mode, double *offsets_dev) {
+  const PrepShape s = prep_shape(V, mode);
+  ops.center_fibres(V.data, V.dtype, s.L, s.J, s.T, offsets_dev);
+}
+void tensor_shift(Ops &ops, const TensorDesc &V, int mode, const double *offsets_dev, double alpha) {
+  const PrepShape s = prep_shape(V, mode);
+  ops.shift_fibres(V.data, V.dtype, s.L, s.J, s.T, offsets_dev, alpha);
+}
+void tensor_slice_sumsq(Ops &ops, const TensorDesc &V, int mode, double *ss_host) {
+  const PrepShape s = prep_shape(V, mode);
+  double *d = (double *)ops.alloc(sizeof(double) * s.J);
+  ops.slice_sumsq(V.data, V.dtype, s.L, s.J, s.T, d);
+  ops.d2h(ss_host, d, sizeof(double) * s.J);
+  ops.free(d);
+}
+void tensor_rescale(Ops &ops, const TensorDesc &V, int mode, const double *factors_host) {
+  const PrepShape s = prep_shape(V, mode);
+  double *d = (double *)ops.alloc(sizeof(double) * s.J);
+  ops.h2d(d, factors_host, sizeof(double) * s.J);
+  ops.scale_slices(V.data, V.dtype, s.L, s.J, s.T, d);
+  ops.free(d);  // (waits for the launch)
+}
+void tensor_scale(Ops &ops, const TensorDesc &V, int mode, double *rms_host) {
+  const PrepShape s = prep_shape(V, mode);
+  std::vector<double> ss((size_t)s.J), f((size_t)s.J);
+  tensor_slice_sumsq(ops, V, mode, ss.data());
+  const double n = (double)s.L * (double)s.T;
+  for (int64_t x = 0; x < s.J; x++) {
+    const double rms = std::sqrt(ss[(size_t)x] / n);
+    if (rms_host) rms_host[x] = rms;
+    f[(size_t)x] = rms > 0 && rms <= std::numeric_limits<double>::max() ? 1.0 / rms : 1.0;
+  }
+  tensor_rescale(ops, V, mode, f.data());
+}
+
 // ============================================================================ CpEngine
 // total columns of a session: nstarts * R, or the sum of the starts' own ranks
 static int total_columns(int R, int nstarts, const int *ranks) {

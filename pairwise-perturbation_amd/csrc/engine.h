@@ -24,6 +24,11 @@ struct TensorDesc {
   // contents never change). Sessions compare it with the generation their derived data (second
   // resident layout, cached contractions) was built from and rebuild when it moved.
   uint64_t *generation = nullptr;
+  // bumped, beside the generation, by the calls that preprocess the contents in place (ppals_tensor_center / _shift /
+  // _scale / _rescale): what follows is another data set, not the next iterate of the same one. A Tucker session
+  // then also drops what it learnt from its earlier steps (warm-start slots of its eigen-steps, a multi-sweep
+  // schedule it switched off), so that it goes on as a new session on the new contents would. nullptr: never.
+  uint64_t *prep_epoch = nullptr;
 };
 
 // leading-mode block partition shared by the tensor shard and the factor-matrix row blocks
@@ -73,6 +78,23 @@ void collinear_factors(const int64_t *lens, int N, int R, double col_min, double
 void tensor_fill_collinear(Ops &ops, Comm &comm, const TensorDesc &V, int R, double col_min,
                            double col_max, double ratio_noise, uint64_t seed);
 double tensor_norm(Ops &ops, Comm &comm, const TensorDesc &V);
+// Preprocessing in place (ppals_tensor_center / _shift / _slice_sumsq / _scale / _rescale; one rank): the tensor
+// viewed as [L, J, T] around `mode`, J = lens[mode], L / T the products of the extents before / after it.
+struct PrepShape {
+  int64_t L = 1, J = 1, T = 1;
+};
+PrepShape prep_shape(const TensorDesc &V, int mode);
+// V[l,j,t] -= mean_j V[l,.,t]; offsets (device, L*T doubles, may be nullptr) receives the means
+void tensor_center(Ops &ops, const TensorDesc &V, int mode, double *offsets_dev);
+// V[l,j,t] += alpha * offsets[l + L*t] (device)
+void tensor_shift(Ops &ops, const TensorDesc &V, int mode, const double *offsets_dev, double alpha);
+// ss[x] = sum over slice x of V^2, on the host
+void tensor_slice_sumsq(Ops &ops, const TensorDesc &V, int mode, double *ss_host);
+// slice x multiplied by factors[x] (host)
+void tensor_rescale(Ops &ops, const TensorDesc &V, int mode, const double *factors_host);
+// rms[x] = sqrt(ss[x] / n); slice x multiplied by 1 / rms[x] unless rms[x] is not a positive finite number (the
+// slice then stays bit for bit); rms_host (lens[mode] doubles, may be nullptr) receives rms as computed
+void tensor_scale(Ops &ops, const TensorDesc &V, int mode, double *rms_host);
 
 struct CpOpts {
   double tol = 0, timelimit = 5e3;

@@ -29,6 +29,7 @@
 #include "kernels_io.hip.h"
 #include "kernels_model.hip.h"
 #include "kernels_bf16.hip.h"
+#include "kernels_prep.hip.h"
 
 namespace ppals {
 #define HIP_CHECK(expr)                                                                       \
@@ -179,6 +180,13 @@ class HipOps : public Ops {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, mw_max));
     HIP_CHECK(hipFuncSetAttribute((const void *)k_model_impute_wide<double, true>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, mw_max));
+    // (the on-chip centring tile: 56 KiB of image + 8 KiB of partial sums at VEC = 4 is the whole 64 KiB)
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_prep_rows<float, 4, 16, PREP_CENTER, true>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_prep_rows<bf16s, 4, 16, PREP_CENTER, true>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_prep_rows<double, 2, 16, PREP_CENTER, true>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
     if (const char *v = getenv("PPALS_GJ_SCALAR")) gj_scalar_ = atoi(v);
     HIP_CHECK(hipFuncSetAttribute((const void *)k_fms_cross, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)fms_lds_bytes(FMS_MAXC, FMS_MAXC, false)));
@@ -824,6 +832,146 @@ class HipOps : public Ops {
     HIP_CHECK(hipStreamWaitEvent(cs, io_ev_out_, 0));
   }
   hipEvent_t io_ev_in_ = nullptr, io_ev_out_ = nullptr;
+  void io_events() {
+    HIP_CHECK(hipSetDevice(dev_));
+    if (!io_ev_in_) {
+      HIP_CHECK(hipEventCreateWithFlags(&io_ev_in_, hipEventDisableTiming));
+      HIP_CHECK(hipEventCreateWithFlags(&io_ev_out_, hipEventDisableTiming));
+    }
+  }
+  void join_stream(void *caller_stream) override {
+    io_events();
+    HIP_CHECK(hipEventRecord(io_ev_in_, (hipStream_t)caller_stream));
+    HIP_CHECK(hipStreamWaitEvent(st_, io_ev_in_, 0));
+  }
+  void release_stream(void *caller_stream) override {
+    io_events();
+    HIP_CHECK(hipEventRecord(io_ev_out_, st_));
+    HIP_CHECK(hipStreamWaitEvent((hipStream_t)caller_stream, io_ev_out_, 0));
+  }
+
+  // ------------------------------------------------------------------ preprocessing in place (kernels_prep.hip.h)
+  // The route rule, a plain formula on (dt, L, J) and the base alignment:
+  //   L == 1: lead.runs while a fibre fits the run buffer, J * size <= 48 KiB; lead.long beyond.
+  //   L  > 1: vec = L % VEC == 0 and V aligned to VEC elements (VEC = 4, 2, 4 for f32, f64, bf16); a tile is
+  //           BL = vec ? 16 * VEC : 64 consecutive l; centring keeps the tile on chip (rows.lds) while
+  //           J * BL * size <= 56 KiB and takes two passes (rows.twopass) beyond. shift and scale keep nothing.
+  static int pow2_floor(int64_t x) {
+    int p = 1;
+    while (2 * (int64_t)p <= x) p *= 2;
+    return p;
+  }
+  static int pow2_ceil(int64_t x, int cap) {
+    int p = 1;
+    while (p < x && p < cap) p *= 2;
+    return p;
+  }
+  static const char *prep_name(int mode) { return mode == PREP_CENTER ? "center" : mode == PREP_SHIFT ? "shift" : "scale"; }
+  template <typename TV, int MODE>
+  void prep_lead(TV *V, int64_t J, int64_t T, double *off, const double *fac, double alpha) {
+    const int64_t fib_bytes = J * (int64_t)sizeof(TV);
+    if (fib_bytes > PREP_LEAD_RUN_BYTES) {
+      route("prep.%s.%s.lead.long", prep_name(MODE), sname<TV>());
+      hipLaunchKernelGGL((k_prep_lead_long<TV, MODE>), dim3((unsigned)std::min<int64_t>(T, 16384)), dim3(PREP_THREADS),
+                         8 * PREP_THREADS, st_, V, J, T, off, fac, alpha);
+      return;
+    }
+    // fibres a run: what the buffer holds, fewer while that leaves the device without work (4 runs a CU)
+    int64_t F = std::max<int64_t>(1, PREP_LEAD_RUN_BYTES / fib_bytes);
+    F = std::min(F, std::max<int64_t>(1, (T + 4 * ncu_ - 1) / (4 * (int64_t)ncu_)));
+    const int G = F >= PREP_THREADS ? 1 : std::min(pow2_floor(PREP_THREADS / F), pow2_ceil(J, PREP_THREADS));
+    if (G > 1) F = std::min<int64_t>(F, PREP_THREADS / G);
+    const int64_t nruns = (T + F - 1) / F;
+    const size_t lds = 8 * PREP_THREADS + (size_t)(PrepVec16<TV>::N + F * J) * sizeof(TV);
+    route("prep.%s.%s.lead.runs F=%lld G=%d", prep_name(MODE), sname<TV>(), (long long)F, G);
+    hipLaunchKernelGGL((k_prep_lead<TV, MODE>), dim3((unsigned)std::min<int64_t>(nruns, 16384)), dim3(PREP_THREADS),
+                       (lds + 15) / 16 * 16, st_, V, (int)J, T, (int)F, G, off, fac, alpha);
+  }
+  template <typename TV, int MODE, int VEC, int LX>
+  void prep_rows_launch(TV *V, int64_t L, int64_t J, int64_t T, double *off, const double *fac, double alpha) {
+    constexpr int BL = LX * VEC;
+    const int64_t ntl = (L + BL - 1) / BL;
+    const bool onchip = MODE == PREP_CENTER && J * BL * (int64_t)sizeof(TV) <= PREP_ROWS_TILE_BYTES;
+    const size_t lds = MODE != PREP_CENTER ? 0 : 8 * (size_t)PREP_THREADS * VEC + (onchip ? (size_t)J * BL * sizeof(TV) : 0);
+    const dim3 grid((unsigned)std::min<int64_t>(ntl * T, 16384));
+    route("prep.%s.%s.rows.%s vec=%d", prep_name(MODE), sname<TV>(),
+          MODE != PREP_CENTER ? "stream" : onchip ? "lds" : "twopass", VEC > 1 ? 1 : 0);
+    if (onchip)
+      hipLaunchKernelGGL((k_prep_rows<TV, VEC, LX, MODE, MODE == PREP_CENTER>), grid, dim3(PREP_THREADS), lds, st_, V, L, J,
+                         T, ntl, off, fac, alpha);
+    else
+      hipLaunchKernelGGL((k_prep_rows<TV, VEC, LX, MODE, false>), grid, dim3(PREP_THREADS), lds, st_, V, L, J, T, ntl,
+                         off, fac, alpha);
+  }
+  template <typename TV, int MODE>
+  void prep_typed(TV *V, int64_t L, int64_t J, int64_t T, double *off, const double *fac, double alpha) {
+    if (L * J * T <= 0) return;
+    constexpr int VEC = PrepRowsVec<TV>::N;
+    if (L == 1)
+      prep_lead<TV, MODE>(V, J, T, off, fac, alpha);
+    else if (L % VEC == 0 && (uintptr_t)V % (VEC * sizeof(TV)) == 0)
+      prep_rows_launch<TV, MODE, VEC, 16>(V, L, J, T, off, fac, alpha);
+    else
+      prep_rows_launch<TV, MODE, 1, 64>(V, L, J, T, off, fac, alpha);
+    HIP_CHECK(hipGetLastError());
+  }
+  template <int MODE>
+  void prep_dispatch(void *V, int dt, int64_t L, int64_t J, int64_t T, double *off, const double *fac, double alpha) {
+    if (dt == F32)
+      prep_typed<float, MODE>((float *)V, L, J, T, off, fac, alpha);
+    else if (dt == BF16)
+      prep_typed<bf16s, MODE>((bf16s *)V, L, J, T, off, fac, alpha);
+    else
+      prep_typed<double, MODE>((double *)V, L, J, T, off, fac, alpha);
+  }
+  void center_fibres(void *V, int dt, int64_t L, int64_t J, int64_t T, double *off) override {
+    prep_dispatch<PREP_CENTER>(V, dt, L, J, T, off, nullptr, 0.0);
+  }
+  void shift_fibres(void *V, int dt, int64_t L, int64_t J, int64_t T, const double *off, double alpha) override {
+    prep_dispatch<PREP_SHIFT>(V, dt, L, J, T, const_cast<double *>(off), nullptr, alpha);
+  }
+  void scale_slices(void *V, int dt, int64_t L, int64_t J, int64_t T, const double *fac) override {
+    prep_dispatch<PREP_SCALE>(V, dt, L, J, T, nullptr, fac, 0.0);
+  }
+  // ss[j] from one partial sum per (block, slice), folded in block order. nb blocks a slice: enough for ~8
+  // workgroups a CU, no more than there are rows of t, and nb * J partial sums capped at 64 MB.
+  template <typename TV>
+  void sumsq_typed(const TV *V, int64_t L, int64_t J, int64_t T, double *ss) {
+    constexpr int VEC = PrepVec16<TV>::N;
+    const bool vec = L > 1 && L % VEC == 0 && (uintptr_t)V % 16 == 0;
+    const int X = L == 1 ? pow2_ceil(J, PREP_THREADS) : pow2_ceil(vec ? L / VEC : L, PREP_THREADS);
+    const int Y = PREP_THREADS / X;
+    const int64_t gx = L == 1 ? (J + X - 1) / X : J;
+    int64_t nb = std::max<int64_t>(1, (8 * (int64_t)ncu_ + gx - 1) / gx);
+    nb = std::min(nb, (T + Y - 1) / Y);
+    nb = std::min(nb, std::max<int64_t>(1, ((int64_t)64 << 20) / (8 * J)));
+    nb = std::min<int64_t>(nb, 65535);
+    if (gx > 0x7fffffff) throw Unsupported("ppals: slice_sumsq supports at most 2^31 - 1 slices");
+    double *part = (double *)ensure(ws_part_, ws_part_sz_, sizeof(double) * (size_t)nb * J);
+    const dim3 grid((unsigned)gx, (unsigned)nb);
+    route("prep.sumsq.%s.%s vec=%d X=%d nb=%lld", sname<TV>(), L == 1 ? "lead" : "rows", vec ? 1 : 0, X, (long long)nb);
+    if (L == 1)
+      hipLaunchKernelGGL((k_sumsq_lead<TV>), grid, dim3(PREP_THREADS), 8 * PREP_THREADS, st_, V, J, T, X, part);
+    else if (vec)
+      hipLaunchKernelGGL((k_sumsq_rows<TV, VEC>), grid, dim3(PREP_THREADS), 8 * PREP_THREADS, st_, V, L, J, T, X, part);
+    else
+      hipLaunchKernelGGL((k_sumsq_rows<TV, 1>), grid, dim3(PREP_THREADS), 8 * PREP_THREADS, st_, V, L, J, T, X, part);
+    hipLaunchKernelGGL(k_fold_partials, dim3(grid_for(J, 256)), dim3(256), 0, st_, part, (int)nb, J, ss);
+    HIP_CHECK(hipGetLastError());
+  }
+  void slice_sumsq(const void *V, int dt, int64_t L, int64_t J, int64_t T, double *ss) override {
+    if (J <= 0) return;
+    if (L * T <= 0) {
+      zero(ss, sizeof(double) * J);
+      return;
+    }
+    if (dt == F32)
+      sumsq_typed((const float *)V, L, J, T, ss);
+    else if (dt == BF16)
+      sumsq_typed((const bf16s *)V, L, J, T, ss);
+    else
+      sumsq_typed((const double *)V, L, J, T, ss);
+  }
 
   // ------------------------------------------------------------------ model through a view
   template <typename D, typename TV, int MODE>

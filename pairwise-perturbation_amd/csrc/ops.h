@@ -241,6 +241,97 @@ class Ops {
     throw Unsupported("ppals: this back end has no device views");
   }
 
+  // Order work on the engine stream against a caller's stream, as copy_view does it: join_stream makes the
+  // work queued on the engine stream from now on wait for what `caller_stream` holds so far, release_stream
+  // makes what the caller queues there later wait for the engine stream's work so far. The host does not block.
+  virtual void join_stream(void * /*caller_stream*/) { throw Unsupported("ppals: this back end has no device views"); }
+  virtual void release_stream(void * /*caller_stream*/) {
+    throw Unsupported("ppals: this back end has no device views");
+  }
+
+  // ---- preprocessing in place (ppals_tensor_center / _shift / _slice_sumsq / _scale / _rescale) ----
+  // V (storage type dt) viewed as [L, J, T], first index fastest. Every element is read as stored, widened to
+  // fp64, and the new value rounded once to dt as an import rounds an fp64 source; sums are formed in fp64 in
+  // a fixed order (no atomics). The defaults are the fp64 host twins built from d2h / h2d (what the host
+  // stand-in runs, as with cp_mode_update_nn); the product back end overrides them with its kernels.
+  //   center_fibres: off[l + L*t] = mean_j V[l,j,t] (device, fp64; may be nullptr), V[l,j,t] -= that mean
+  //   shift_fibres:  V[l,j,t] += alpha * off[l + L*t]  (alpha = +-1: one rounding in fp64)
+  //   slice_sumsq:   ss[j] = sum_{l,t} V[l,j,t]^2      (device, fp64)
+  //   scale_slices:  V[l,j,t] *= fac[j]                (device, fp64); a slice with fac[j] == 1.0 is not touched
+  static double prep_load(const void *V, int dt, size_t e) {
+    return dt == F32 ? (double)((const float *)V)[e] : dt == BF16 ? (double)((const bf16s *)V)[e] : ((const double *)V)[e];
+  }
+  static void prep_store(void *V, int dt, size_t e, double x) {
+    if (dt == F32)
+      ((float *)V)[e] = (float)x;
+    else if (dt == BF16)
+      ((bf16s *)V)[e] = bf16s(x);
+    else
+      ((double *)V)[e] = x;
+  }
+  virtual void center_fibres(void *V, int dt, int64_t L, int64_t J, int64_t T, double *off) {
+    const size_t n = (size_t)L * J * T;
+    std::vector<char> h(n * dtype_size(dt));
+    std::vector<double> o((size_t)L * T);
+    d2h(h.data(), V, h.size());
+    for (int64_t t = 0; t < T; t++)
+      for (int64_t l = 0; l < L; l++) {
+        double s = 0;
+        for (int64_t j = 0; j < J; j++) s += prep_load(h.data(), dt, (size_t)(l + L * (j + J * t)));
+        const double m = s / (double)J;
+        o[(size_t)(l + L * t)] = m;
+        for (int64_t j = 0; j < J; j++) {
+          const size_t e = (size_t)(l + L * (j + J * t));
+          prep_store(h.data(), dt, e, prep_load(h.data(), dt, e) - m);
+        }
+      }
+    h2d(V, h.data(), h.size());
+    if (off) h2d(off, o.data(), sizeof(double) * o.size());
+  }
+  virtual void shift_fibres(void *V, int dt, int64_t L, int64_t J, int64_t T, const double *off, double alpha) {
+    const size_t n = (size_t)L * J * T;
+    std::vector<char> h(n * dtype_size(dt));
+    std::vector<double> o((size_t)L * T);
+    d2h(h.data(), V, h.size());
+    d2h(o.data(), off, sizeof(double) * o.size());
+    for (int64_t t = 0; t < T; t++)
+      for (int64_t j = 0; j < J; j++)
+        for (int64_t l = 0; l < L; l++) {
+          const size_t e = (size_t)(l + L * (j + J * t));
+          prep_store(h.data(), dt, e, prep_load(h.data(), dt, e) + alpha * o[(size_t)(l + L * t)]);
+        }
+    h2d(V, h.data(), h.size());
+  }
+  virtual void slice_sumsq(const void *V, int dt, int64_t L, int64_t J, int64_t T, double *ss) {
+    const size_t n = (size_t)L * J * T;
+    std::vector<char> h(n * dtype_size(dt));
+    std::vector<double> s((size_t)J, 0.0);
+    d2h(h.data(), V, h.size());
+    for (int64_t t = 0; t < T; t++)
+      for (int64_t j = 0; j < J; j++)
+        for (int64_t l = 0; l < L; l++) {
+          const double v = prep_load(h.data(), dt, (size_t)(l + L * (j + J * t)));
+          s[(size_t)j] += v * v;
+        }
+    h2d(ss, s.data(), sizeof(double) * s.size());
+  }
+  virtual void scale_slices(void *V, int dt, int64_t L, int64_t J, int64_t T, const double *fac) {
+    const size_t n = (size_t)L * J * T;
+    std::vector<char> h(n * dtype_size(dt));
+    std::vector<double> f((size_t)J);
+    d2h(h.data(), V, h.size());
+    d2h(f.data(), fac, sizeof(double) * f.size());
+    for (int64_t t = 0; t < T; t++)
+      for (int64_t j = 0; j < J; j++) {
+        if (f[(size_t)j] == 1.0) continue;
+        for (int64_t l = 0; l < L; l++) {
+          const size_t e = (size_t)(l + L * (j + J * t));
+          prep_store(h.data(), dt, e, prep_load(h.data(), dt, e) * f[(size_t)j]);
+        }
+      }
+    h2d(V, h.data(), h.size());
+  }
+
   // ---- Khatri-Rao product, plain: out[j + J*c] = prod_f W_f[j_f + ld_f*(col0+c)], fp64 ----
   virtual void krp(double *out, const FactorRef *f, int nf, int col0, int ncols) = 0;
 

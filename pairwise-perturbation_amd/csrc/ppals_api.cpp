@@ -38,6 +38,7 @@ struct ppals_tensor {
   ppals_ctx *ctx;
   TensorDesc d;
   uint64_t generation = 1;  // bumped by every fill / upload; sessions rebuild what they derived
+  uint64_t prep_epoch = 0;  // bumped by center / shift / scale / rescale (TensorDesc::prep_epoch)
 };
 struct ppals_cp {
   ppals_ctx *ctx;
@@ -191,6 +192,7 @@ int ppals_tensor_create(ppals_ctx *ctx, int order, const int64_t *global_lens, i
     return PPALS_ERR_ARG;
   }
   t->d.generation = &t->generation;
+  t->d.prep_epoch = &t->prep_epoch;
   ctx->tensors.insert(t.get());
   *out = t.release();
   return PPALS_OK;
@@ -277,6 +279,141 @@ int ppals_tensor_norm(ppals_tensor *t, double *out) {
   if (!t || !t->ctx || !out) return fail(PPALS_ERR_ARG, "NULL argument");
   API_BEGIN
   *out = tensor_norm(*t->ctx->ops, t->ctx->c(), t->d);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+
+// ------------------------------------------------------------------ preprocessing in place
+// the checks all five calls share; nothing is launched, allocated or bumped before every check has passed
+static int prep_check(ppals_tensor *t, int mode, const char *fn) {
+  if (!t || !t->ctx) return fail_fn(PPALS_ERR_ARG, fn, "NULL tensor or a dead handle");
+  if (mode < 0 || mode >= t->d.order)
+    return fail_fn(PPALS_ERR_ARG, fn, ("mode " + std::to_string(mode) + " is outside [0, " +
+                                       std::to_string(t->d.order) + ")").c_str());
+  if (t->ctx->c().size() > 1)
+    return fail_fn(PPALS_ERR_UNSUPPORTED, fn,
+                   "a context of more than one rank is not supported (centring across the sharded mode needs a "
+                   "collective of the size of the offsets)");
+  return PPALS_OK;
+}
+// the contents change in place: sessions rebuild what they derived, Tucker sessions also forget their history
+static void prep_bump(ppals_tensor *t) {
+  t->generation++;
+  t->prep_epoch++;
+}
+// an offsets buffer in device memory: the checks of the device views on L*T doubles at ptr
+static int prep_check_device(ppals_ctx *ctx, const char *fn, const void *ptr, int64_t count) {
+  Ops::PtrInfo info;
+  std::string err;
+  bool known = false;
+  try {
+    known = ctx->ops->device_ptr_info(ptr, &info, &err);
+  } catch (const ppals::Unsupported &e) {  // a back end without device views
+    return fail_fn(PPALS_ERR_UNSUPPORTED, fn, e.what());
+  }
+  if (!known || !info.is_device)
+    return fail_fn(PPALS_ERR_ARG, fn,
+                   ("the offsets pointer is not device memory of the context's device (" +
+                    (err.empty() ? std::string("host, pinned host or managed memory") : err) +
+                    "); a torch tensor must live on that device, and torch must be imported before libppals is "
+                    "loaded so that both share one HIP runtime").c_str());
+  if ((uintptr_t)ptr % sizeof(double))
+    return fail_fn(PPALS_ERR_ARG, fn, "the offsets pointer is not aligned to 8 bytes");
+  if (!dv_in_allocation((uint64_t)(uintptr_t)ptr, count * (int64_t)sizeof(double), info.base, info.size))
+    return fail_fn(PPALS_ERR_ARG, fn,
+                   ("the offsets span " + std::to_string(count * (int64_t)sizeof(double)) +
+                    " bytes from the pointer, past the end of its allocation (" + std::to_string(info.size) +
+                    " bytes, the pointer at offset " + std::to_string((uint64_t)(uintptr_t)ptr - info.base) + ")").c_str());
+  return PPALS_OK;
+}
+int ppals_tensor_center(ppals_tensor *t, int mode, double *offsets, int where, void *stream) {
+  static const char *fn = "ppals_tensor_center";
+  API_BEGIN
+  int rc = prep_check(t, mode, fn);
+  if (rc != PPALS_OK) return rc;
+  Ops &ops = *t->ctx->ops;
+  if (!offsets) {
+    prep_bump(t);
+    tensor_center(ops, t->d, mode, nullptr);
+    return PPALS_OK;
+  }
+  if (where != PPALS_HOST && where != PPALS_DEVICE) return fail_fn(PPALS_ERR_ARG, fn, "where must be PPALS_HOST or PPALS_DEVICE");
+  const PrepShape s = prep_shape(t->d, mode);
+  if (where == PPALS_DEVICE) {
+    rc = prep_check_device(t->ctx, fn, offsets, s.L * s.T);
+    if (rc != PPALS_OK) return rc;
+    prep_bump(t);
+    ops.join_stream(stream);
+    tensor_center(ops, t->d, mode, offsets);
+    ops.release_stream(stream);
+    return PPALS_OK;
+  }
+  double *tmp = (double *)ops.alloc(sizeof(double) * s.L * s.T);
+  prep_bump(t);
+  tensor_center(ops, t->d, mode, tmp);
+  ops.d2h(offsets, tmp, sizeof(double) * s.L * s.T);
+  ops.free(tmp);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_tensor_shift(ppals_tensor *t, int mode, const double *offsets, int where, double alpha, void *stream) {
+  static const char *fn = "ppals_tensor_shift";
+  API_BEGIN
+  int rc = prep_check(t, mode, fn);
+  if (rc != PPALS_OK) return rc;
+  if (!offsets) return fail_fn(PPALS_ERR_ARG, fn, "offsets is NULL");
+  if (where != PPALS_HOST && where != PPALS_DEVICE) return fail_fn(PPALS_ERR_ARG, fn, "where must be PPALS_HOST or PPALS_DEVICE");
+  if (!std::isfinite(alpha)) return fail_fn(PPALS_ERR_ARG, fn, "alpha is not finite");
+  Ops &ops = *t->ctx->ops;
+  const PrepShape s = prep_shape(t->d, mode);
+  if (where == PPALS_DEVICE) {
+    rc = prep_check_device(t->ctx, fn, offsets, s.L * s.T);
+    if (rc != PPALS_OK) return rc;
+    prep_bump(t);
+    ops.join_stream(stream);
+    tensor_shift(ops, t->d, mode, offsets, alpha);
+    ops.release_stream(stream);
+    return PPALS_OK;
+  }
+  double *tmp = (double *)ops.alloc(sizeof(double) * s.L * s.T);
+  ops.h2d(tmp, offsets, sizeof(double) * s.L * s.T);
+  prep_bump(t);
+  tensor_shift(ops, t->d, mode, tmp, alpha);
+  ops.free(tmp);  // (waits for the launch: the host buffer has been consumed long before)
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_tensor_slice_sumsq(ppals_tensor *t, int mode, double *ss) {
+  static const char *fn = "ppals_tensor_slice_sumsq";
+  API_BEGIN
+  const int rc = prep_check(t, mode, fn);
+  if (rc != PPALS_OK) return rc;
+  if (!ss) return fail_fn(PPALS_ERR_ARG, fn, "ss is NULL");
+  tensor_slice_sumsq(*t->ctx->ops, t->d, mode, ss);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_tensor_scale(ppals_tensor *t, int mode, double *scales) {
+  static const char *fn = "ppals_tensor_scale";
+  API_BEGIN
+  const int rc = prep_check(t, mode, fn);
+  if (rc != PPALS_OK) return rc;
+  prep_bump(t);
+  tensor_scale(*t->ctx->ops, t->d, mode, scales);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_tensor_rescale(ppals_tensor *t, int mode, const double *factors) {
+  static const char *fn = "ppals_tensor_rescale";
+  API_BEGIN
+  const int rc = prep_check(t, mode, fn);
+  if (rc != PPALS_OK) return rc;
+  if (!factors) return fail_fn(PPALS_ERR_ARG, fn, "factors is NULL");
+  for (int64_t x = 0; x < t->d.llens[mode]; x++)
+    if (!std::isfinite(factors[x]))
+      return fail_fn(PPALS_ERR_ARG, fn, ("factors[" + std::to_string(x) + "] is not finite").c_str());
+  prep_bump(t);
+  tensor_rescale(*t->ctx->ops, t->d, mode, factors);
   return PPALS_OK;
   API_END(PPALS_ERR_HIP)
 }

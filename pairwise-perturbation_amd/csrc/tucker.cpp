@@ -77,6 +77,23 @@ TuckerEngine::TuckerEngine(Ops &ops, Comm &comm, const TensorDesc &V, const int 
     }
   }
   if (V_.generation) tensor_gen_ = *V_.generation;
+  if (V_.prep_epoch) prep_epoch_ = *V_.prep_epoch;
+  ms3_created_ = ms3_;
+}
+
+// see tucker.h; called where a session call first comes to read the tensor (hosvd, the sweeps)
+void TuckerEngine::check_prep_epoch() {
+  if (!V_.prep_epoch || *V_.prep_epoch == prep_epoch_) return;
+  prep_epoch_ = *V_.prep_epoch;
+  finalize_rotations();  // (settles deferred steps; a rotation still owed to a factor is applied, not lost)
+  ops_.sync();
+  ops_.eig_session_free(eig_base_);
+  eig_base_ = ops_.eig_session_new();
+  if (!dist_)
+    for (int i = 0; i < N_ && i < MAX_ORDER; i++)
+      if (V_.glens[i] > 64) ops_.eig_lazy(eig_base_ + i, true);
+  ms3_ = ms3_created_;
+  ms3_invalidate();
 }
 
 // The leaf of mode i, [s_i | the other two ranks], from the order-3 multi-sweep schedule; nullptr: the
@@ -741,6 +758,7 @@ void TuckerEngine::export_slab(const ModelBox &bx, int f, const std::vector<int>
 // hosvd (als_Tucker.cxx:12-70): W_i = leading eigenvectors of the Gram of the mode-i unfolding of
 // V (K13), then core = V x_i W_i^T
 void TuckerEngine::hosvd() {
+  check_prep_epoch();
   settle_all();
   ms3_invalidate();
   for (int i = 0; i < N_; i++) {
@@ -818,6 +836,7 @@ void TuckerEngine::sweep_dt() { sweep_body(nullptr); }
 // one HOOI sweep; align_ref != nullptr: column signs aligned with that factor set after every
 // eigen-step (alsTucker_DT_sub, als_Tucker.cxx:632-643)
 void TuckerEngine::sweep_body(const std::vector<double *> *align_ref) {
+  check_prep_epoch();
   const bool may_defer = defer_enabled_ && align_ref == nullptr && !dist_;
   if (!may_defer) settle_all();
   for (auto &n : nodes_) n.valid = false;  // ttmc_map.clear(), als_Tucker.cxx:340

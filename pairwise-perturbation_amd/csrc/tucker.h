@@ -120,6 +120,13 @@ class TuckerEngine {
   }
   uint64_t tensor_gen_ = 0;  // generation of the tensor contents VT_ and the caches were built from
   void check_tensor_generation();
+  // TensorDesc::prep_epoch as this session last saw it. When it has moved (the contents were centred or scaled in
+  // place) the session settles what is pending and then forgets its history — the warm-start slots of its
+  // eigen-steps are drawn anew and the order-3 multi-sweep schedule is back to what the session was created with —
+  // so that its next hosvd / sweeps are, bit for bit, those of a new session on the new contents.
+  uint64_t prep_epoch_ = 0;
+  bool ms3_created_ = false;
+  void check_prep_epoch();
   void *chain_[2] = {nullptr, nullptr};  // ping-pong scratch of the mode-product chains
   size_t chain_cap_[2] = {0, 0};
   int64_t ytmp_cap_ = 0, yacc_cap_ = 0;

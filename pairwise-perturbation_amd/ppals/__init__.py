@@ -74,7 +74,10 @@ EXPORTS = [
     "ppals_cp_multi_take_predicted",
     "ppals_cp_set_mode_constraints", "ppals_cp_get_mode_constraints",
     "ppals_cp_multi_set_mode_constraints", "ppals_cp_multi_get_mode_constraints",
+    "ppals_tensor_center", "ppals_tensor_shift", "ppals_tensor_slice_sumsq", "ppals_tensor_scale",
+    "ppals_tensor_rescale",
 ]
+HOST, DEVICE = 0, 1  # PPALS_HOST / PPALS_DEVICE: where the offsets of Tensor.center / Tensor.shift lie
 MODE_FREE, MODE_NONNEG, MODE_FIXED, MODE_ORTHO = 0, 1, 2, 3  # PPALS_MODE_*
 MODE_KINDS = ("free", "nonneg", "fixed", "ortho")
 MODEL, RESIDUAL = 0, 1  # PPALS_MODEL / PPALS_RESIDUAL
@@ -375,6 +378,91 @@ class Tensor:
         _check(lib().ppals_tensor_norm(self._h, C.byref(out)))
         return out.value
 
+    # ---- centring and scaling in place (include/ppals.h, "PARAFAC preprocessing") ----
+    def _prep_shape(self, mode):
+        """(L, J, T) around `mode`, and the offsets' shape: the tensor's with shape[mode] = 1. A mode out of
+        range gives sizes of 1: the library is the one that refuses it."""
+        n = len(self.lens)
+        if not 0 <= mode < n:
+            return 1, 1, 1, [1] * n
+        L = int(np.prod(self.lens[:mode], dtype=np.int64))
+        T = int(np.prod(self.lens[mode + 1:], dtype=np.int64))
+        return L, self.lens[mode], T, self.lens[:mode] + [1] + self.lens[mode + 1:]
+
+    def center(self, mode, offsets=None, stream=None):
+        """V <- V - its mean over `mode`, fibre by fibre. offsets: None (nothing is returned and the host does
+        not wait), "numpy" (the means as an fp64 array of the tensor's shape with shape[mode] = 1) or "torch"
+        (the same as a float64 torch tensor on the context's device, ordered on `stream`, default torch's
+        current stream; the host does not wait)."""
+        mode = int(mode)
+        L, _, T, shape = self._prep_shape(mode)
+        if offsets is None:
+            _check(lib().ppals_tensor_center(self._h, mode, None, HOST, None))
+            return None
+        if offsets == "numpy":
+            out = np.empty(L * T, dtype=np.float64)
+            _check(lib().ppals_tensor_center(self._h, mode, _dp(out), HOST, None))
+            return out.reshape(shape, order="F")
+        if offsets == "torch":
+            torch = _torch()
+            buf = torch.empty(L * T, dtype=torch.float64, device=f"cuda:{self.ctx.device}")
+            _check(lib().ppals_tensor_center(self._h, mode, C.c_void_p(buf.data_ptr()), DEVICE,
+                                             C.c_void_p(int(self._stream(stream) or 0))))
+            n = len(shape)  # element l + L t of buf is element (i_0, ..) of the result, first index fastest
+            return buf.view(*reversed(shape)).permute(*reversed(range(n)))
+        raise ValueError('offsets must be None, "numpy" or "torch"')
+
+    def shift(self, mode, offsets, alpha=1.0, stream=None):
+        """V <- V + alpha * offsets, the offsets (numpy, or a float64 torch tensor on the context's device) of
+        the tensor's shape with shape[mode] = 1, as center returns them: alpha = 1 undoes a centring, alpha = -1
+        applies a calibration set's means to new data. A torch tensor is read in place when it already lies first
+        index fastest; the call is then ordered on `stream` and the host does not wait."""
+        mode = int(mode)
+        L, _, T, shape = self._prep_shape(mode)
+        if type(offsets).__module__.split(".")[0] == "torch":
+            torch = _torch()
+            if offsets.dtype != torch.float64:
+                raise PpalsError(f"the offsets must be float64, not {offsets.dtype}")
+            if offsets.device.type != "cuda" or offsets.device.index != self.ctx.device:
+                raise PpalsError(f"the offsets are on {offsets.device}, the context on cuda:{self.ctx.device}")
+            if list(offsets.shape) != shape:
+                raise PpalsError(f"the offsets have shape {list(offsets.shape)}, expected {shape}")
+            flat_ = offsets.permute(*reversed(range(len(shape)))).contiguous().view(-1)
+            _check(lib().ppals_tensor_shift(self._h, mode, C.c_void_p(flat_.data_ptr()), DEVICE,
+                                            C.c_double(alpha), C.c_void_p(int(self._stream(stream) or 0))))
+            return self
+        o = np.asarray(offsets, dtype=np.float64)
+        if list(o.shape) != shape and 0 <= mode < len(self.lens):
+            raise PpalsError(f"the offsets have shape {list(o.shape)}, expected {shape}")
+        o = np.ascontiguousarray(o.ravel(order="F"))
+        _check(lib().ppals_tensor_shift(self._h, mode, _dp(o), HOST, C.c_double(alpha), None))
+        return self
+
+    def slice_sumsq(self, mode):
+        """ss[x] = the sum of V^2 over slice x of `mode` (fp64; the tensor is only read)"""
+        mode = int(mode)
+        out = np.empty(self._prep_shape(mode)[1], dtype=np.float64)
+        _check(lib().ppals_tensor_slice_sumsq(self._h, mode, _dp(out)))
+        return out
+
+    def scale(self, mode):
+        """every slice of `mode` divided by its root mean square; returns the rms values (a slice whose rms is
+        not a positive finite number stays as it is)"""
+        mode = int(mode)
+        out = np.empty(self._prep_shape(mode)[1], dtype=np.float64)
+        _check(lib().ppals_tensor_scale(self._h, mode, _dp(out)))
+        return out
+
+    def rescale(self, mode, factors):
+        """slice x of `mode` multiplied by factors[x]"""
+        mode = int(mode)
+        f = np.ascontiguousarray(np.asarray(factors, dtype=np.float64).ravel())
+        J = self._prep_shape(mode)[1]
+        if f.size != J and 0 <= mode < len(self.lens):
+            raise PpalsError(f"{f.size} factors for {J} slices")
+        _check(lib().ppals_tensor_rescale(self._h, mode, _dp(f)))
+        return self
+
     def close(self):
         if self._h:
             lib().ppals_tensor_destroy(self._h)
@@ -391,6 +479,73 @@ def _opts(tol=0.0, timelimit=5e3, maxiter=0, lam=0.0, resprint=10, bench=0, tol_
           ratio_step=1.0, csv=None, csv_append=0, verbose=0, update_percentage=1.0):
     return _Opts(tol, timelimit, maxiter, lam, resprint, bench, tol_init, ratio_step,
                  csv.encode() if csv else None, csv_append, verbose, update_percentage)
+
+
+
+def _usable_rms(rms):
+    """the rms values Tensor.scale divided by: 1 where a slice was left alone (rms not positive finite)"""
+    rms = np.asarray(rms, dtype=np.float64)
+    return np.where(np.isfinite(rms) & (rms > 0), rms, 1.0)
+
+
+class Preprocessing:
+    """What ppals.preprocess did to a tensor, in order: ("center", mode, offsets) and ("scale", mode, rms)
+    steps, the arrays as Tensor.center(mode, "numpy") and Tensor.scale(mode) returned them."""
+
+    def __init__(self, lens):
+        self.lens = [int(x) for x in lens]
+        self.steps = []
+
+    def apply(self, other):
+        """the same offsets and factors on new data (a tensor of the same extents): the calibration set's
+        preprocessing applied to a test set"""
+        if list(other.lens) != self.lens:
+            raise PpalsError(f"the tensor has extents {other.lens}, the preprocessing {self.lens}")
+        for kind, mode, a in self.steps:
+            if kind == "center":
+                other.shift(mode, a, -1.0)
+            else:
+                other.rescale(mode, 1.0 / _usable_rms(a))
+        return other
+
+    def undo(self, tensor):
+        """back to the raw data (up to the roundings of the storage type): the steps inverted, last first"""
+        if list(tensor.lens) != self.lens:
+            raise PpalsError(f"the tensor has extents {tensor.lens}, the preprocessing {self.lens}")
+        for kind, mode, a in reversed(self.steps):
+            if kind == "center":
+                tensor.shift(mode, a, 1.0)
+            else:
+                tensor.rescale(mode, _usable_rms(a))
+        return tensor
+
+    def unscale_factors(self, Ws):
+        """factors of a model of the scaled tensor -> factors of the model of the unscaled (still centred) one:
+        the rows of W_mode multiplied by the rms of every scaling of that mode"""
+        out = [np.array(W, dtype=np.float64, order="F") for W in Ws]
+        for kind, mode, a in self.steps:
+            if kind == "scale":
+                out[mode] *= _usable_rms(a)[:, None]
+        return out
+
+
+def preprocess(tensor, center=(), scale=(), scale_iters=1):
+    """Centre `tensor` across every mode of `center`, then scale it within every mode of `scale` (the whole list
+    scale_iters times over: scaling within several modes at once is iterative), in place; returns the
+    Preprocessing record. A mode in both lists is refused: scaling within a mode destroys centring across it
+    (Bro & Smilde 2003)."""
+    center, scale = [int(m) for m in center], [int(m) for m in scale]
+    both = sorted(set(center) & set(scale))
+    if both:
+        raise ValueError(f"modes {both} are both centred across and scaled within: the scaling would destroy "
+                         "the centring")
+    rec = Preprocessing(tensor.lens)
+    for m in center:
+        rec.steps.append(("center", m, tensor.center(m, "numpy")))
+    for _ in range(int(scale_iters)):
+        for m in scale:
+            rec.steps.append(("scale", m, tensor.scale(m)))
+    return rec
 
 
 class _ModelExport:
