@@ -285,6 +285,37 @@ int ppals_cp_get_nonneg(const ppals_cp *s);
 #define PPALS_ORTHO_MIN_RATIO 9.094947017729282379150390625e-13 /* 2^-40 */
 int ppals_cp_set_mode_constraints(ppals_cp *s, const int *kinds /* N */);
 int ppals_cp_get_mode_constraints(const ppals_cp *s, int *kinds /* N */);
+/* Shapes for non-negative modes: one shape per mode (shapes[N]), NONE everywhere at first. A shape refines a
+ * mode of kind PPALS_MODE_NONNEG and no other; the kinds, and ppals_cp_get_mode_constraints, know nothing of it.
+ *   PPALS_SHAPE_NONE        the HALS pass as it is. A session whose shapes are all NONE is bit for bit, and
+ *                           launch for launch, a session on which the call was never made.
+ *   PPALS_SHAPE_UNIMODAL    every column rises to one peak and falls: for some row p it is non-decreasing on rows
+ *                           0..p and non-increasing on rows p+1..s-1 (plateaus allowed; monotone columns included)
+ *   PPALS_SHAPE_INCREASING  every column is non-decreasing over the rows
+ *   PPALS_SHAPE_DECREASING  every column is non-increasing over the rows
+ * The update of a shaped mode (Bro & Sidiropoulos, J. Chemometrics 1998), in fp64: grad = -M + W_old S as for
+ * every kind; then for r = 0 .. R-1 in this order, with d = S[r,r],
+ *   v[x] = w[x,r] + (M[x,r] - sum_q w[x,q] S[q,r]) / d   for all rows x, columns q < r already replaced,
+ *   w[:,r] <- the u of least ||u - v||^2 among the sequences of the shape with u >= PPALS_NN_FLOOR
+ * (pool-adjacent-violators, clipped at the floor; for UNIMODAL the peak row of least error, the smallest on a
+ * tie). A column whose d is not a positive finite number, or whose v has a non-finite entry, stays as it is.
+ * Each column step minimises over a set that holds the current column once the factor has the shape, so from
+ * the first sweep on the residual does not rise. The factor need not have the shape when the call is made: the
+ * first update projects it. Normalize stays on: a positive column scale keeps every shape. Everything a NONNEG
+ * mode allows works (both schedules, ppals_cp_sweeps_dt, ppals_cp_dt, ppals_cpd_als, ppals_cp_em, multi-start
+ * and rank-sweep sessions; ppals_cp_multi_take copies factors and ignores shapes), and everything it refuses
+ * stays refused. ppals_cp_set_mode_constraints and ppals_cp_set_nonneg reset to NONE the shape of every mode
+ * that ends up not NONNEG.
+ * Every refusal happens before anything is launched and leaves shapes and session as they were, the message
+ * starting with the function's name. PPALS_ERR_ARG: a NULL session or shapes, a shape outside 0..3, a shape
+ * other than NONE on a mode whose kind is not NONNEG. PPALS_ERR_UNSUPPORTED: a shape on the hold-out mode, and
+ * ppals_cp_multi_set_holdout on a shaped mode (zeroed rows break any shape). */
+#define PPALS_SHAPE_NONE 0
+#define PPALS_SHAPE_UNIMODAL 1
+#define PPALS_SHAPE_INCREASING 2
+#define PPALS_SHAPE_DECREASING 3
+int ppals_cp_set_mode_shapes(ppals_cp *s, const int *shapes /* N */);
+int ppals_cp_get_mode_shapes(const ppals_cp *s, int *shapes /* N */);
 /* Where the multi-sweep schedule's first-level intermediates lie (no counterpart in the reference:
  * CTF places its own buffers). The choice is made ONLINE: the first ~20 visits of a root run the
  * sweep's own scan at a different offset / store kind of the result, timed on the stream; then the
@@ -432,6 +463,11 @@ int ppals_cp_multi_get_nonneg(const ppals_cp_multi *s);
  * FIXED or ORTHO mode, and making the hold-out mode FIXED or ORTHO. */
 int ppals_cp_multi_set_mode_constraints(ppals_cp_multi *s, const int *kinds /* N: one kind per mode, for all starts */);
 int ppals_cp_multi_get_mode_constraints(const ppals_cp_multi *s, int *kinds /* N */);
+/* The shapes of ppals_cp_set_mode_shapes for a multi-start or rank-sweep session: one shape per mode, shared by
+ * all starts, every start's columns projected on their own (nothing couples two starts; a start matches an
+ * ordinary session of the same start bit for bit). The same rules and refusals. */
+int ppals_cp_multi_set_mode_shapes(ppals_cp_multi *s, const int *shapes /* N, for all starts */);
+int ppals_cp_multi_get_mode_shapes(const ppals_cp_multi *s, int *shapes /* N */);
 
 /* ---- core consistency diagnostic (CORCONDIA: R. Bro, H. A. L. Kiers, "A new efficient method for
  * determining the number of components in PARAFAC models", J. Chemometrics 17 (2003) 274-286; no

@@ -893,6 +893,7 @@ void CpEngine::set_nonneg(bool on) {
       throw Unsupported("ppals: PPALS_TEST_BLOCKED_UPDATE has no non-negative update");
   }
   for (int i = 0; i < N_; i++) kind_[i] = on ? kModeNonneg : kModeFree;
+  drop_stale_shapes();
 }
 
 int CpEngine::check_mode_kinds(const int *kinds, std::string *why) const {
@@ -943,6 +944,33 @@ void CpEngine::set_mode_kinds(const int *kinds) {
     }
     kind_[i] = kinds[i];
   }
+  drop_stale_shapes();
+}
+
+int CpEngine::check_mode_shapes(const int *shapes, std::string *why) const {
+  for (int i = 0; i < N_; i++) {
+    if (shapes[i] < kShapeNone || shapes[i] > kShapeDecreasing) {
+      *why = "a shape must be PPALS_SHAPE_NONE, _UNIMODAL, _INCREASING or _DECREASING";
+      return 1;
+    }
+    if (shapes[i] != kShapeNone && kind_[i] != kModeNonneg) {
+      *why = "a shape needs a mode of kind PPALS_MODE_NONNEG";
+      return 1;
+    }
+  }
+  if (hold_mode_ >= 0 && shapes[hold_mode_] != kShapeNone) {
+    *why = "the hold-out mode cannot have a shape";
+    return 2;
+  }
+  return 0;
+}
+
+void CpEngine::set_mode_shapes(const int *shapes) {
+  std::string why;
+  const int rc = check_mode_shapes(shapes, &why);
+  if (rc == 2) throw Unsupported("ppals: " + why);
+  if (rc) throw std::invalid_argument("ppals: " + why);
+  for (int i = 0; i < N_; i++) shape_[i] = shapes[i];
 }
 
 bool CpEngine::factors_nonneg(unsigned modes) {
@@ -1195,6 +1223,13 @@ void CpEngine::mode_update(int i, const double *M, int64_t ldm, double lambda, b
     if (pp || dist_) throw std::logic_error("ppals: an orthonormal mode updates exactly, on one rank");
     ops_.cp_mode_update_ortho_ragged(G_, N_, i, start_table(), lambda, M, ldm, W_[i], s, gradW_[i], s, s,
                                      gradsq_ + (size_t)i * K_, S_);
+    return;
+  }
+  if (hals && shape_[i] != kShapeNone) {  // column by column onto the shape's set, through the table as ORTHO
+    // goes; the hold-out mode never has a shape (set_mode_shapes, set_holdout)
+    if (pp || dist_) throw std::logic_error("ppals: a shaped mode updates exactly, on one rank");
+    ops_.cp_mode_update_shape_ragged(G_, N_, i, start_table(), lambda, M, ldm, W_[i], s, gradW_[i], s, s,
+                                     gradsq_ + (size_t)i * K_, S_, shape_[i]);
     return;
   }
   if (multi_) {  // block-diagonal over starts: one batched update, every start its own system

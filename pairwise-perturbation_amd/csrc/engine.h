@@ -157,6 +157,16 @@ class CpEngine {
     for (int i = 0; i < N_; i++) kind_[i] = kinds[i];
   }
   int mode_kind(int i) const { return kind_[i]; }
+  // Shapes (include/ppals.h, PPALS_SHAPE_*): a NONNEG mode whose shape is not kShapeNone is updated by
+  // Ops::cp_mode_update_shape_ragged through start_table() — one path for ordinary, multi-start and rank-sweep
+  // sessions — instead of the HALS pass; a mode of shape kShapeNone takes exactly the launches it took before.
+  // Refused before anything changes: std::invalid_argument for a shape outside 0..3 and for a shape on a mode
+  // that is not NONNEG, Unsupported for a shape on the hold-out mode (zeroed rows break any shape). Factors,
+  // Grams and caches are untouched. set_mode_kinds and set_nonneg drop the shape of a mode that ends up not
+  // NONNEG (a set_nonneg the C ABI takes back had turned every mode NONNEG and so dropped none).
+  void set_mode_shapes(const int *shapes);
+  int check_mode_shapes(const int *shapes, std::string *why) const;  // 0 fine, 1 a bad argument, 2 unsupported
+  int mode_shape(int i) const { return shape_[i]; }
   bool all_free() const { return !any_nonfree(); }
   bool any_nonfree() const {
     for (int i = 0; i < N_; i++)
@@ -495,6 +505,11 @@ class CpEngine {
   bool ragged_ = false;
   bool multi_ = false;
   int kind_[MAX_ORDER] = {0};  // set_mode_kinds / set_nonneg: kModeFree everywhere at first
+  int shape_[MAX_ORDER] = {0};  // set_mode_shapes: kShapeNone everywhere at first; != 0 only where kind_ is NONNEG
+  void drop_stale_shapes() {    // (after every change of kind_)
+    for (int i = 0; i < N_; i++)
+      if (kind_[i] != kModeNonneg) shape_[i] = kShapeNone;
+  }
   bool any_fixed() const {
     for (int i = 0; i < N_; i++)
       if (kind_[i] == kModeFixed) return true;

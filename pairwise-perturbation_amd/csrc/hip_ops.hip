@@ -21,6 +21,7 @@
 #include "kernels_small.hip.h"
 #include "kernels_nn.hip.h"
 #include "kernels_polar.hip.h"
+#include "kernels_shape.hip.h"
 #include "kernels_holdout.hip.h"
 #include "kernels_corcondia.hip.h"
 #include "kernels_fms.hip.h"
@@ -192,6 +193,8 @@ class HipOps : public Ops {
                                   (int)fms_lds_bytes(FMS_MAXC, FMS_MAXC, false)));
     HIP_CHECK(hipFuncSetAttribute((const void *)k_polar_factor, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   96 * 1024));  // (67.5 KB at R = 64)
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_shape_columns, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)kShapeLdsBytes));
   }
   ~HipOps() override {
     hipSetDevice(dev_);
@@ -2273,6 +2276,52 @@ class HipOps : public Ops {
     prof_begin(1, 0.0);
     hipLaunchKernelGGL(k_cp_update_ortho_ragged, dim3((unsigned)nb, (unsigned)t.nstarts), dim3(64), lds2, st_, Gall,
                        N, mode, t, lambda, M, ldm, W, ldw, grad, ldg, rows, part, S, Tm, status);
+    prof_end();
+    prof_begin(1, 0.0);
+    hipLaunchKernelGGL(k_cp_finish_nn_ragged, dim3((unsigned)t.nstarts), dim3(1024), 0, st_, part, (int)nb,
+                       gradsq, W, ldw, rows, t, N, mode, Gall);
+    prof_end();
+    HIP_CHECK(hipGetLastError());
+  }
+  // The shaped non-negative mode update (kernels_shape.hip.h) in THREE launches whatever the starts, ranks and
+  // rows: the gradient on (row tiles x starts), a workgroup per start for the column loop, then
+  // k_cp_finish_nn_ragged for the sums and the Grams. Each launch is bracketed on its own, so the launch profile
+  // counts them. The column loop keeps its work arrays in LDS while S and shape_work_bytes(rows) fit in
+  // kShapeLdsBytes (route tag "lds"), else in the scratch behind the tile sums ("global").
+  void cp_mode_update_shape_ragged(double *Gall, int N, int mode, const StartTable &t, double lambda,
+                                   const double *M, int64_t ldm, double *W, int64_t ldw, double *grad,
+                                   int64_t ldg, int64_t rows, double *gradsq, double *S, int shape) override {
+    RoctxRange roctx_("K4-K6 mode update (shaped non-negative)");
+    check_table(t);
+    const int R = t.max_rank();
+    if (R > 64) throw Unsupported("ppals: the shaped mode update supports R <= 64");
+    if (shape < kShapeUnimodal || shape > kShapeDecreasing)
+      throw std::invalid_argument("ppals: a shaped mode update needs PPALS_SHAPE_UNIMODAL, _INCREASING or _DECREASING");
+    if (sys_armed_ || sys_ready_ || norm_armed_)
+      throw std::logic_error("ppals: armed S / Normalize in front of a shaped mode update");
+    if (rows <= 0) {
+      Ops::cp_mode_update_shape_ragged(Gall, N, mode, t, lambda, M, ldm, W, ldw, grad, ldg, rows, gradsq, S, shape);
+      return;
+    }
+    const int64_t nb = (rows + 63) / 64;
+    if (rows > (int64_t)1 << 30 || nb * t.nstarts > (int64_t)1 << 30)
+      throw std::runtime_error("ppals: mode too long for the shaped update");
+    const size_t lds1 = sizeof(double) * ((size_t)R * R + 64 * (size_t)R);
+    const size_t sbytes = sizeof(double) * (size_t)R * R, wbytes = shape_work_bytes(rows);
+    const bool in_lds = sbytes + wbytes <= kShapeLdsBytes;
+    const size_t npart = (size_t)nb * t.nstarts, wstride = wbytes / sizeof(double);
+    double *part = (double *)ensure(ws_big2_, ws_big2_sz_,
+                                    sizeof(double) * npart + (in_lds ? 0 : wbytes * (size_t)t.nstarts));
+    double *gwork = in_lds ? nullptr : part + npart;
+    route("update_shape kind=%d R=%d starts=%d rows=%lld %s", shape, R, t.nstarts, (long long)rows,
+          in_lds ? "lds" : "global");
+    prof_begin(1, 0.0);
+    hipLaunchKernelGGL(k_shape_grad, dim3((unsigned)nb, (unsigned)t.nstarts), dim3(64), lds1, st_, Gall, N, mode, t,
+                       lambda, M, ldm, W, ldw, grad, ldg, rows, part, S);
+    prof_end();
+    prof_begin(1, 0.0);
+    hipLaunchKernelGGL(k_shape_columns, dim3((unsigned)t.nstarts), dim3(1024), sbytes + (in_lds ? wbytes : 0), st_,
+                       Gall, N, mode, t, lambda, M, ldm, W, ldw, rows, shape, kNnFloor, R, gwork, (int64_t)wstride);
     prof_end();
     prof_begin(1, 0.0);
     hipLaunchKernelGGL(k_cp_finish_nn_ragged, dim3((unsigned)t.nstarts), dim3(1024), 0, st_, part, (int)nb,

@@ -64,6 +64,13 @@ constexpr double kNnFloor = 1e-16;
 constexpr double kOrthoMinRatio = 0x1p-40;
 // the kind of a mode's update (PPALS_MODE_* of the C ABI)
 enum ModeKind { kModeFree = 0, kModeNonneg = 1, kModeFixed = 2, kModeOrtho = 3 };
+// the shape of a NONNEG mode's columns (PPALS_SHAPE_* of the C ABI)
+enum ModeShape { kShapeNone = 0, kShapeUnimodal = 1, kShapeIncreasing = 2, kShapeDecreasing = 3 };
+// the shaped update's column loop (kernels_shape.hip.h) keeps S (R^2 doubles, R the largest rank of the call) and
+// its work arrays of shape_work_bytes(rows) in LDS while both fit in kShapeLdsBytes — 152 of the 160 KiB a
+// gfx950 workgroup may declare, the rest for its static arrays — and the work arrays in global memory above
+constexpr size_t kShapeLdsBytes = 152 * 1024;
+inline size_t shape_work_bytes(int64_t rows) { return 64 * (size_t)rows + 8; }
 
 // a factor-matrix operand of a Khatri-Rao product: `rows` rows starting at `ptr`, leading dim ld
 // The starts of a multi-start session whose ranks differ (a rank sweep), handed to the ragged ops — and to
@@ -687,6 +694,156 @@ class Ops {
       h2d(gradsq + b, &gs, sizeof(double));
       if (S) h2d(S + t.sq[b], s.data(), sizeof(double) * RR);
       gram(Wb, rows, ldw, R, Gb + (size_t)mode * RR);
+    }
+  }
+  // One whole single-rank SHAPED non-negative mode update per start (PPALS_SHAPE_* on a PPALS_MODE_NONNEG mode;
+  // the layout of the ragged ops above — an ordinary session is a table of one start): with
+  // S = Hadamard_{j != mode} G_j + lambda I,
+  //   grad = -M + W_old S (as for every kind), gradsq[b] = sum grad_b^2,
+  //   for r = 0 .. R_b - 1 in this order (Gauss-Seidel over columns): d = S[r,r]; if d is not a positive finite
+  //   number the column stays; v[x] = w[x,r] + (M[x,r] - sum_q w[x,q] S[q,r]) / d with the current W (columns
+  //   q < r replaced already); if some v[x] is not finite the column stays; else w[:,r] <- the least-squares
+  //   projection of v onto the shape's set: u >= kNnFloor and u non-decreasing (kShapeIncreasing), non-increasing
+  //   (kShapeDecreasing), or non-decreasing on rows 0..p and non-increasing on rows p+1..rows-1 for some p
+  //   (kShapeUnimodal; the p of least error, the smallest on a tie) — shape_project below,
+  //   the Gram of the new W_b into Gall; S (may be nullptr) receives the systems.
+  // Ranks <= 64, any rows >= 1. Nothing couples two starts; the same state gives the same bits — of ONE back
+  // end. A tie between two splits is decided to rounding: the split errors are sums that cancel, and back ends
+  // may form them differently (this default divides, the HIP kernel multiplies by a refined reciprocal), so on
+  // errors that agree to about 1e-15 |v|^2 two back ends may choose different p. Any of them is a minimiser to
+  // that precision; nothing may rely on the back ends agreeing there.
+  // This default is built from d2h / h2d and a host loop (what the host stand-in runs, as with
+  // cp_mode_update_ortho_ragged); the product back end overrides it with three launches.
+  virtual void cp_mode_update_shape_ragged(double *Gall, int N, int mode, const StartTable &t, double lambda,
+                                           const double *M, int64_t ldm, double *W, int64_t ldw, double *grad,
+                                           int64_t ldg, int64_t rows, double *gradsq, double *S, int shape) {
+    if (t.max_rank() > 64) throw Unsupported("ppals: the shaped mode update supports R <= 64");
+    if (shape < kShapeUnimodal || shape > kShapeDecreasing)
+      throw std::invalid_argument("ppals: a shaped mode update needs PPALS_SHAPE_UNIMODAL, _INCREASING or _DECREASING");
+    for (int b = 0; b < t.nstarts; b++) {
+      const int R = t.rank(b);
+      const size_t RR = (size_t)R * R;
+      double *Gb = Gall + (size_t)N * t.sq[b];
+      const double *Mb = M + (size_t)t.col[b] * ldm;
+      double *Wb = W + (size_t)t.col[b] * ldw, *gb = grad + (size_t)t.col[b] * ldg;
+      double gs = 0;
+      if (rows <= 0) {
+        h2d(gradsq + b, &gs, sizeof(double));
+        gram(Wb, rows, ldw, R, Gb + (size_t)mode * RR);
+        continue;
+      }
+      std::vector<double> g((size_t)N * RR), s(RR, 1.0), m((size_t)ldm * (R - 1) + rows),
+          w((size_t)ldw * (R - 1) + rows), gr((size_t)ldg * (R - 1) + rows);
+      d2h(g.data(), Gb, sizeof(double) * g.size());
+      d2h(m.data(), Mb, sizeof(double) * m.size());
+      d2h(w.data(), Wb, sizeof(double) * w.size());
+      d2h(gr.data(), gb, sizeof(double) * gr.size());
+      for (size_t e = 0; e < RR; e++) {  // the index order of gram_system (als_CP.cxx:219-232)
+        bool first = true;
+        for (int ii = 0; ii < N - 1; ii++) {
+          const double gv = g[(size_t)(ii == mode ? N - 1 : ii) * RR + e];
+          s[e] = first ? gv : s[e] * gv;
+          first = false;
+        }
+        if (e % R == e / R) s[e] += lambda;
+      }
+      for (int r = 0; r < R; r++)
+        for (int64_t x = 0; x < rows; x++) {
+          double acc = 0;
+          for (int q = 0; q < R; q++) acc += w[x + ldw * q] * s[q + (size_t)R * r];
+          const double gv = -m[x + ldm * r] + acc;
+          gr[x + ldg * r] = gv;
+          gs += gv * gv;
+        }
+      std::vector<double> v((size_t)rows), u((size_t)rows);
+      for (int r = 0; r < R; r++) {
+        const double d = s[r + (size_t)R * r];
+        if (!(d > 0) || d > 1.79769313486231570e308) continue;
+        bool finite = true;
+        for (int64_t x = 0; x < rows; x++) {
+          double acc = 0;
+          for (int q = 0; q < R; q++) acc += w[x + ldw * q] * s[q + (size_t)R * r];
+          v[x] = w[x + ldw * r] + (m[x + ldm * r] - acc) / d;
+          finite = finite && std::fabs(v[x]) <= 1.79769313486231570e308;
+        }
+        if (!finite) continue;
+        shape_project(v.data(), rows, shape, kNnFloor, u.data());
+        for (int64_t x = 0; x < rows; x++) w[x + ldw * r] = u[x];
+      }
+      h2d(Wb, w.data(), sizeof(double) * w.size());
+      h2d(gb, gr.data(), sizeof(double) * gr.size());
+      h2d(gradsq + b, &gs, sizeof(double));
+      if (S) h2d(S + t.sq[b], s.data(), sizeof(double) * RR);
+      gram(Wb, rows, ldw, R, Gb + (size_t)mode * RR);
+    }
+  }
+  // u = argmin ||u - v||^2 over the shape's set (cp_mode_update_shape_ragged), on the host: pool-adjacent-
+  // violators left to right and right to left, blocks as (sum, count), the fit clipped at `floor` (the bounded
+  // isotonic fit is the unbounded one clipped). For kShapeUnimodal the two passes also leave, for every prefix
+  // and suffix, the error of its clipped fit — a block's is sumsq - 2 c sum + c^2 count with c = max(mean,
+  // floor) — and the split p of least total wins, the smallest on a tie.
+  static void shape_project(const double *v, int64_t n, int shape, double floor, double *u) {
+    struct Blk {
+      double sum, sumsq, err;  // err: the clipped error of all blocks up to and including this one
+      int64_t cnt;
+    };
+    std::vector<Blk> st;
+    // the non-decreasing fit of the m entries a[0], a[step], a[2 step], ... as blocks on `st`;
+    // err[k] = the clipped error of the fit of the first k + 1 of them
+    auto pass = [&st, floor](const double *a, int64_t step, int64_t m, double *err) {
+      st.clear();
+      for (int64_t k = 0; k < m; k++) {
+        const double x = a[k * step];
+        Blk nb{x, x * x, 0.0, 1};
+        while (!st.empty() && st.back().sum * (double)nb.cnt >= nb.sum * (double)st.back().cnt) {
+          nb.sum += st.back().sum;
+          nb.sumsq += st.back().sumsq;
+          nb.cnt += st.back().cnt;
+          st.pop_back();
+        }
+        const double mean = nb.sum / (double)nb.cnt, c = mean > floor ? mean : floor;
+        nb.err = (st.empty() ? 0.0 : st.back().err) + (nb.sumsq - 2.0 * c * nb.sum + c * c * (double)nb.cnt);
+        st.push_back(nb);
+        if (err) err[k] = nb.err;
+      }
+    };
+    // the blocks' clipped means into o[0], o[step], ...
+    auto emit = [&st, floor](double *o, int64_t step) {
+      int64_t k = 0;
+      for (const Blk &b : st) {
+        const double mean = b.sum / (double)b.cnt, c = mean > floor ? mean : floor;
+        for (int64_t j = 0; j < b.cnt; j++, k++) o[k * step] = c;
+      }
+    };
+    // (a non-increasing fit is the non-decreasing fit of the sequence read backwards)
+    if (shape == kShapeIncreasing) {
+      pass(v, 1, n, nullptr);
+      emit(u, 1);
+      return;
+    }
+    if (shape == kShapeDecreasing) {
+      pass(v + n - 1, -1, n, nullptr);
+      emit(u + n - 1, -1);
+      return;
+    }
+    std::vector<double> ep((size_t)n), es((size_t)n);
+    pass(v, 1, n, ep.data());
+    pass(v + n - 1, -1, n, es.data());
+    int64_t best = 0;
+    double ebest = 0;
+    for (int64_t p = 0; p < n; p++) {  // rows 0..p rise, rows p+1..n-1 fall
+      const double e = ep[p] + (p + 1 < n ? es[n - 2 - p] : 0.0);
+      if (p == 0 || e < ebest) {
+        ebest = e;
+        best = p;
+      }
+    }
+    // the winner's two fits, each a pass over its own part (later entries pool a prefix's blocks away)
+    pass(v, 1, best + 1, nullptr);
+    emit(u, 1);
+    if (best + 1 < n) {
+      pass(v + n - 1, -1, n - 1 - best, nullptr);
+      emit(u + n - 1, -1);
     }
   }
   // G_b = W_b^T W_b of the same column blocks into the session's Gram store: Gram (start b, mode) at

@@ -607,6 +607,33 @@ int ppals_cp_set_mode_constraints(ppals_cp *s, const int *kinds) {
 int ppals_cp_get_mode_constraints(const ppals_cp *s, int *kinds) {
   return get_mode_constraints(s ? s->eng : nullptr, kinds, "ppals_cp_get_mode_constraints");
 }
+static_assert(PPALS_SHAPE_NONE == ppals::kShapeNone && PPALS_SHAPE_UNIMODAL == ppals::kShapeUnimodal &&
+                  PPALS_SHAPE_INCREASING == ppals::kShapeIncreasing && PPALS_SHAPE_DECREASING == ppals::kShapeDecreasing,
+              "the ABI's shapes are the engine's");
+// (both kinds of session: everything is refused before the engine changes anything)
+static int set_mode_shapes(CpEngine *e, const int *shapes, const char *fn) {
+  if (!e) return fail_fn(PPALS_ERR_ARG, fn, "NULL session");
+  if (!shapes) return fail_fn(PPALS_ERR_ARG, fn, "shapes is NULL");
+  API_BEGIN
+  std::string why;
+  if (const int rc = e->check_mode_shapes(shapes, &why))
+    return fail_fn(rc == 2 ? PPALS_ERR_UNSUPPORTED : PPALS_ERR_ARG, fn, why.c_str());
+  e->set_mode_shapes(shapes);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+static int get_mode_shapes(const CpEngine *e, int *shapes, const char *fn) {
+  if (!e) return fail_fn(PPALS_ERR_ARG, fn, "NULL session");
+  if (!shapes) return fail_fn(PPALS_ERR_ARG, fn, "shapes is NULL");
+  for (int i = 0; i < e->order(); i++) shapes[i] = e->mode_shape(i);
+  return PPALS_OK;
+}
+int ppals_cp_set_mode_shapes(ppals_cp *s, const int *shapes) {
+  return set_mode_shapes(s ? s->eng : nullptr, shapes, "ppals_cp_set_mode_shapes");
+}
+int ppals_cp_get_mode_shapes(const ppals_cp *s, int *shapes) {
+  return get_mode_shapes(s ? s->eng : nullptr, shapes, "ppals_cp_get_mode_shapes");
+}
 int ppals_cp_placement_report(const ppals_cp *s, char *buf, int cap) {
   if (!s || !s->eng || !buf || cap <= 0) return fail(PPALS_ERR_ARG, "NULL argument");
   API_BEGIN
@@ -971,6 +998,12 @@ int ppals_cp_multi_set_mode_constraints(ppals_cp_multi *s, const int *kinds) {
 int ppals_cp_multi_get_mode_constraints(const ppals_cp_multi *s, int *kinds) {
   return get_mode_constraints(s ? s->eng : nullptr, kinds, "ppals_cp_multi_get_mode_constraints");
 }
+int ppals_cp_multi_set_mode_shapes(ppals_cp_multi *s, const int *shapes) {
+  return set_mode_shapes(s ? s->eng : nullptr, shapes, "ppals_cp_multi_set_mode_shapes");
+}
+int ppals_cp_multi_get_mode_shapes(const ppals_cp_multi *s, int *shapes) {
+  return get_mode_shapes(s ? s->eng : nullptr, shapes, "ppals_cp_multi_get_mode_shapes");
+}
 int ppals_cp_multi_get_nonneg(const ppals_cp_multi *s) {
   return s && s->eng ? (s->eng->nonneg() ? 1 : 0) : PPALS_ERR_ARG;
 }
@@ -1025,6 +1058,8 @@ int ppals_cp_multi_set_holdout(ppals_cp_multi *s, int mode, const uint8_t *keep)
     if (mode < 0 || mode >= s->eng->order()) return fail_fn(PPALS_ERR_ARG, fn, "mode must be in [0, N)");
     if (s->eng->mode_kind(mode) == ppals::kModeFixed || s->eng->mode_kind(mode) == ppals::kModeOrtho)
       return fail_fn(PPALS_ERR_UNSUPPORTED, fn, "the hold-out mode cannot be fixed or orthonormal");
+    if (s->eng->mode_shape(mode) != ppals::kShapeNone)
+      return fail_fn(PPALS_ERR_UNSUPPORTED, fn, "the hold-out mode cannot have a shape");
     const int64_t n = s->eng->mode_extent(mode);
     for (int b = 0; b < s->eng->nstarts(); b++) {
       bool any = false;

@@ -74,12 +74,16 @@ EXPORTS = [
     "ppals_cp_multi_take_predicted",
     "ppals_cp_set_mode_constraints", "ppals_cp_get_mode_constraints",
     "ppals_cp_multi_set_mode_constraints", "ppals_cp_multi_get_mode_constraints",
+    "ppals_cp_set_mode_shapes", "ppals_cp_get_mode_shapes",
+    "ppals_cp_multi_set_mode_shapes", "ppals_cp_multi_get_mode_shapes",
     "ppals_tensor_center", "ppals_tensor_shift", "ppals_tensor_slice_sumsq", "ppals_tensor_scale",
     "ppals_tensor_rescale",
 ]
 HOST, DEVICE = 0, 1  # PPALS_HOST / PPALS_DEVICE: where the offsets of Tensor.center / Tensor.shift lie
 MODE_FREE, MODE_NONNEG, MODE_FIXED, MODE_ORTHO = 0, 1, 2, 3  # PPALS_MODE_*
 MODE_KINDS = ("free", "nonneg", "fixed", "ortho")
+SHAPE_NONE, SHAPE_UNIMODAL, SHAPE_INCREASING, SHAPE_DECREASING = 0, 1, 2, 3  # PPALS_SHAPE_*
+SHAPE_KINDS = ("none", "unimodal", "increasing", "decreasing")
 MODEL, RESIDUAL = 0, 1  # PPALS_MODEL / PPALS_RESIDUAL
 FMS_WEIGHTS = 1  # PPALS_FMS_WEIGHTS
 
@@ -90,6 +94,14 @@ def _kinds(kinds, n):
     if len(kinds) != n:
         raise ValueError(f"one kind per mode: {n} expected, {len(kinds)} given")
     return (C.c_int * n)(*[MODE_KINDS.index(k) if isinstance(k, str) else int(k) for k in kinds])
+
+
+def _shapes(shapes, n):
+    """a shape per mode, as ints or as the strings of SHAPE_KINDS, into a C array of n ints"""
+    shapes = list(shapes)
+    if len(shapes) != n:
+        raise ValueError(f"one shape per mode: {n} expected, {len(shapes)} given")
+    return (C.c_int * n)(*[SHAPE_KINDS.index(k) if isinstance(k, str) else int(k) for k in shapes])
 
 
 def lib(path=None):
@@ -694,6 +706,20 @@ class CP(_ModelExport, _Impute):
         _check(lib().ppals_cp_get_mode_constraints(self._h, out))
         return [MODE_KINDS[k] for k in out]
 
+    def set_mode_shapes(self, shapes):
+        """one shape per mode, ints (SHAPE_*) or "none" | "unimodal" | "increasing" | "decreasing", on modes of
+        kind "nonneg" only: every column of a shaped mode's factor is, update by update, the least-squares
+        projection of its HALS target onto the non-negative sequences with one peak, or that never fall, or
+        that never rise. All "none" is the session as it was. Changing a mode's kind away from "nonneg"
+        clears its shape."""
+        _check(lib().ppals_cp_set_mode_shapes(self._h, _shapes(shapes, len(self.lens))))
+
+    @property
+    def mode_shapes(self):
+        out = (C.c_int * len(self.lens))()
+        _check(lib().ppals_cp_get_mode_shapes(self._h, out))
+        return [SHAPE_KINDS[k] for k in out]
+
     def placement_report(self):
         """where the online placement choice put each root's first-level intermediate (dict)"""
         import json
@@ -939,6 +965,17 @@ class CPMulti:
         out = (C.c_int * len(self.lens))()
         _check(lib().ppals_cp_multi_get_mode_constraints(self._h, out))
         return [MODE_KINDS[k] for k in out]
+
+    def set_mode_shapes(self, shapes):
+        """CP.set_mode_shapes for every start: one shape per mode, shared by all starts (not on the hold-out
+        mode)"""
+        _check(lib().ppals_cp_multi_set_mode_shapes(self._h, _shapes(shapes, len(self.lens))))
+
+    @property
+    def mode_shapes(self):
+        out = (C.c_int * len(self.lens))()
+        _check(lib().ppals_cp_multi_get_mode_shapes(self._h, out))
+        return [SHAPE_KINDS[k] for k in out]
 
     def sweeps(self, n, lam=0.0):
         _check(lib().ppals_cp_multi_sweeps(self._h, int(n), C.c_double(lam)))
