@@ -718,6 +718,61 @@ int ppals_cp_em(ppals_cp *s, const void *mask, const int64_t *box_lo, const int6
                 const int64_t *strides, void *stream, const ppals_cp_opts *o, int inner_sweeps,
                 int *iters, double *observed_res);
 
+/* ---- CP with element weights (the N-way toolbox's parafac(..., Weights); MILES; maximum-likelihood
+ * PARAFAC): min sum_e h_e (x_e - m_e)^2 by Kiers' majorization (Kiers 1997) ----
+ * With weights scaled to 0 <= h <= 1 and the current model m0, the working tensor z = m0 + h (x - m0)
+ * satisfies  sum h (x - m)^2 <= sum (z - m)^2 + sum h (1 - h) (x - m0)^2  for every m, with equality at
+ * m = m0: any ordinary sweep on Z (constrained and shaped ones, both schedules, lambda > 0) cannot raise the
+ * weighted loss. For h in {0, 1} this is the EM imputation above.
+ *
+ * `data` and `weights` are two views of the SAME box of the GLOBAL tensor, each given exactly as the source of
+ * ppals_tensor_import_device: both of element type `dtype` (PPALS_F32 or PPALS_F64), each with its own
+ * strides >= 0 in elements (0 broadcasts: a per-variable weight vector is a view with one non-zero stride),
+ * NULL strides = dense over the box, first index fastest.
+ *
+ * ppals_cp_wls_device: one majorization step. For every element of the box in this rank's leading-mode rows,
+ * m the fp64 model [[W_0..W_{N-1}]] of the current factors (products and sums on the fp64 matrix cores),
+ * x and h the view values widened to fp64, the value stored is
+ *     h >= 1:            z = x                  loss contribution (x - m)^2
+ *     h <= 0 or NaN:     z = m                  0; x is not used and may be NaN or Inf
+ *     0 < h < 1:         z = fma(h, x - m, m)   h (x - m)^2
+ * rounded once to the storage type, as ppals_tensor_import_device rounds an fp64 source. Elements outside
+ * the box and other ranks' rows are untouched. The model sum is formed with the rank steps in the order the
+ * imputation uses (4-wide fp64 MFMA steps, k ascending): with weights in {0, 1} and `data` holding the
+ * tensor's own stored values, the resident tensor after the call equals, BIT FOR BIT, the tensor after
+ * ppals_cp_impute_device with the corresponding mask from the same state (the mask laid out as `data`:
+ * the unit-stride mode of the first side view leads the second mode group in both calls).
+ *   weighted_sq == NULL: the host does not block; ordered on `stream` as the imputation is (the views may be
+ *     changed by work queued on `stream` after the call).
+ *   weighted_sq != NULL: *weighted_sq = the sum of the loss contributions over the box, formed in fp64 from
+ *     x and m (it never sees the storage type) in a fixed order (the same state gives the same bits), summed
+ *     over the ranks by one scalar all-reduce; the call returns when it is on the host.
+ * The call bumps the tensor's generation like an imputation; factors, Grams and gradients do not change.
+ * Refused before anything is launched or allocated:
+ *   PPALS_ERR_ARG: a NULL pointer for either view; a dtype other than F32 / F64; any check
+ *     ppals_tensor_check_device_view makes of an import source, made of both views (the message starts with
+ *     the function's name and says which view failed);
+ *   PPALS_ERR_UNSUPPORTED: BF16 storage (a bf16 rounding of z is coarser than the h (x - m) correction it
+ *     carries, so the majorization no longer holds); R > 128 (the factor tile is kept in LDS); a back end
+ *     without device views ("no device views", after the arithmetic checks, as for the imputation).
+ * A multi-start session's inner engine is refused the way the imputation refuses it. */
+int ppals_cp_wls_device(ppals_cp *s, const void *data, const void *weights, int dtype,
+                        const int64_t *box_lo, const int64_t *box_len,
+                        const int64_t *data_strides, const int64_t *weight_strides,
+                        void *stream, double *weighted_sq /* may be NULL */);
+/* Weighted CP: iteration k is a step followed by ppals_cp_sweeps_dt(inner_sweeps, o->lambda). The looks
+ * (iterations 0, resprint, 2 resprint, ...), the last step on the way out, *iters and
+ * *weighted_res = sqrt(loss) are those of ppals_cp_em. Stop rules at a look: weighted residual <= o->tol:
+ * returns 1; from the second look on, prev - cur <= rel_change * prev: returns 2 (noisy data never reaches
+ * an absolute tolerance; rel_change = 0 turns this rule off); o->maxiter or o->timelimit (agreed across
+ * ranks): returns 0. <0 on error: the refusals of ppals_cp_wls_device, and inner_sweeps < 1 or
+ * rel_change < 0 (PPALS_ERR_ARG). Both views must stay unchanged for the duration. */
+int ppals_cp_wls(ppals_cp *s, const void *data, const void *weights, int dtype,
+                 const int64_t *box_lo, const int64_t *box_len,
+                 const int64_t *data_strides, const int64_t *weight_strides, void *stream,
+                 const ppals_cp_opts *o, int inner_sweeps, double rel_change,
+                 int *iters, double *weighted_res);
+
 /* ---- Tucker with missing entries (TensorLy's tucker(mask=...)): imputation and an EM driver ----
  * The contracts of ppals_cp_impute_device / ppals_cp_em with a Tucker session in the CP session's place:
  * the same PPALS_U8 mask view (a box of the GLOBAL tensor, strides >= 0, 0 broadcasts, NULL = dense, a byte

@@ -303,6 +303,37 @@ inline ModelPlan dv_model_swapped(ModelPlan mp) {
   std::swap(mp.roff, mp.voff);
   return mp;
 }
+// The weighted step (ppals_cp_wls_device, Ops::model_wls) reads TWO side views of one box beside the shard
+// it rewrites: the data (the plan's vs / voff, as an export view's) and the weights, which a ModelSide
+// carries: per mode of each group its stride, and the offset of the first element, cut to the rank's rows
+// exactly as dv_model_box cuts the first view. `w` must be a checked view of the same box as the one `b`
+// was cut from (same lo and len): only its strides differ.
+struct ModelSide {
+  ModelGroup ga, gb;  // len / mode as the plan's groups; vs = the second view's strides (rs unused, 0)
+  int64_t off = 0;
+};
+inline ModelSide dv_model_side(const ViewArgs &w, const ModelBox &b, const ModelPlan &mp) {
+  ModelSide s;
+  s.off = (b.lo[0] - w.lo[0]) * w.stride[0];
+  auto fill = [&](const ModelGroup &g, ModelGroup &o) {
+    o.n = g.n;
+    o.count = g.count;
+    for (int i = 0; i < g.n; i++) {
+      o.mode[i] = g.mode[i];
+      o.len[i] = g.len[i];
+      o.vs[i] = w.stride[g.mode[i]];
+      o.rs[i] = 0;
+    }
+  };
+  fill(mp.ga, s.ga);
+  fill(mp.gb, s.gb);
+  return s;
+}
+// How a side view is read by the weighted step: with the lane index along a (in the store pass) when it is
+// unit-stride in A's fastest mode, or has no unit-stride run along b to prefer; otherwise with the lane
+// index along b, through LDS. sa / sb: the view's strides in the first mode of group A / B (0 if the
+// group is empty). A stride of 0 is a broadcast: every lane reads one address, either way.
+inline bool dv_side_along_a(int64_t sa, int64_t sb) { return sa == 1 || sb != 1; }
 // The second pass of the two-pass residual, view -= model: "V" is the view itself (its offsets in place
 // of the shard's), after the tensor export has filled it.
 inline ModelPlan dv_model_rmw(ModelPlan mp) {

@@ -2516,26 +2516,34 @@ void CpEngine::export_model(const ViewArgs &a, void *dst, bool residual, void *s
 // Group A = the shard's fastest modes (its own order) until A reaches the square root of the box: the
 // lane index of the store pass runs along it, and so do the V reads of the observed residual. Group B =
 // the rest, a mode in which the mask is unit-stride first: when the mask is not contiguous along A its
-// bytes, 1 B per element, are the side read along b through LDS.
+// bytes, 1 B per element, are the side read along b through LDS. (The weighted step groups the same way:
+// its first side view, the data, in the mask's place, and `second`, the strides of its weights view, asked
+// only when the first has no unit-stride mode outside A.)
+void CpEngine::shard_groups(const ModelBox &bx, const int64_t *second, ModelPlan &mp) const {
+  int64_t total = 1;
+  for (int m = 0; m < N_; m++) total *= bx.len[m];
+  bool inA[MAX_ORDER] = {};
+  for (int m = 0; m < N_ && (mp.ga.count < 64 || mp.ga.count * mp.ga.count < total); m++)
+    if (bx.len[m] > 1) {
+      mp.ga.add(bx, m);
+      inA[m] = true;
+    }
+  int first = -1;
+  for (int m = 0; m < N_ && first < 0; m++)
+    if (!inA[m] && bx.len[m] > 1 && bx.vs[m] == 1) first = m;
+  for (int m = 0; second && m < N_ && first < 0; m++)
+    if (!inA[m] && bx.len[m] > 1 && second[m] == 1) first = m;
+  if (first >= 0) mp.gb.add(bx, first);
+  for (int m = 0; m < N_; m++)
+    if (!inA[m] && m != first) mp.gb.add(bx, m);
+}
+
 void CpEngine::impute(const ViewArgs &a, const void *mask, void *stream, double *observed_sq) {
   if (multi_) throw std::logic_error("ppals: a multi-start session does not impute (take the winner first)");
   ModelBox bx;
   if (dv_model_box(a, V_.glens, V_.row0, V_.llens[0], &bx)) {
     ModelPlan mp;
-    int64_t total = 1;
-    for (int m = 0; m < N_; m++) total *= bx.len[m];
-    bool inA[MAX_ORDER] = {};
-    for (int m = 0; m < N_ && (mp.ga.count < 64 || mp.ga.count * mp.ga.count < total); m++)
-      if (bx.len[m] > 1) {
-        mp.ga.add(bx, m);
-        inA[m] = true;
-      }
-    int first = -1;
-    for (int m = 0; m < N_ && first < 0; m++)
-      if (!inA[m] && bx.len[m] > 1 && bx.vs[m] == 1) first = m;
-    if (first >= 0) mp.gb.add(bx, first);
-    for (int m = 0; m < N_; m++)
-      if (!inA[m] && m != first) mp.gb.add(bx, m);
+    shard_groups(bx, nullptr, mp);
     model_operands(bx, mp);
     ops_.model_impute(mp, xq_, xp_, R_, false, mask, V_.data, V_.dtype, observed_sq ? scal_ : nullptr, stream);
     // the contents changed with that launch: every session on the tensor, this one too, rebuilds what
@@ -2549,28 +2557,79 @@ void CpEngine::impute(const ViewArgs &a, const void *mask, void *stream, double 
   ops_.d2h(observed_sq, scal_, sizeof(double));
 }
 
-int CpEngine::run_em(const ViewArgs &a, const void *mask, void *stream, const CpOpts &o, int inner_sweeps,
-                     int *iters, double *observed_res) {
+// The loop of ppals_cp_em and ppals_cp_wls: iteration k is step(&sq or nullptr) followed by inner_sweeps
+// sweeps; sq is looked at every o.resprint iterations, and one last step with it runs on the way out
+// unless the stopping look just did. Returns 1: a look found sqrt(sq) <= o.tol; 2: from the second look
+// on, the residual fell by no more than rel_change of the look before (0: no such rule); 0 otherwise.
+template <typename Step>
+int CpEngine::em_loop(Step &&step, const CpOpts &o, int inner_sweeps, double rel_change, int *iters, double *res) {
   const double t0 = now();
-  double sq = 0;
-  int k = 0;
-  bool on_tol = false, fresh = false;  // fresh: the tensor and sq belong to the current factors
+  double sq = 0, prev = -1;
+  int k = 0, why = 0;
+  bool fresh = false;  // fresh: the tensor and sq belong to the current factors
   while (k < o.maxiter) {
     const bool look = k % o.resprint == 0;
-    impute(a, mask, stream, look ? &sq : nullptr);
+    step(look ? &sq : nullptr);
     fresh = look;
     if (look) {
-      on_tol = std::sqrt(sq) <= o.tol;
-      if (on_tol || agree(now() - t0 > o.timelimit)) break;
+      const double cur = std::sqrt(sq);
+      if (cur <= o.tol)
+        why = 1;
+      else if (rel_change > 0 && prev >= 0 && prev - cur <= rel_change * prev)
+        why = 2;
+      prev = cur;
+      if (why || agree(now() - t0 > o.timelimit)) break;
     }
     for (int i = 0; i < inner_sweeps; i++) sweep_dt(o.lambda);
     fresh = false;
     k++;
   }
-  if (!fresh) impute(a, mask, stream, &sq);
+  if (!fresh) step(&sq);
   if (iters) *iters = k;
-  if (observed_res) *observed_res = std::sqrt(sq);
-  return on_tol ? 1 : 0;
+  if (res) *res = std::sqrt(sq);
+  return why;
+}
+
+int CpEngine::run_em(const ViewArgs &a, const void *mask, void *stream, const CpOpts &o, int inner_sweeps,
+                     int *iters, double *observed_res) {
+  return em_loop([&](double *sq) { impute(a, mask, stream, sq); }, o, inner_sweeps, 0.0, iters, observed_res);
+}
+
+// The weighted step: the imputation's plan with the data view in the mask's place, and the
+// weights view beside it (ModelSide). Every element of the box is stored.
+const char *CpEngine::wls_refusal() const {
+  if (V_.dtype == BF16)
+    return "BF16 storage is not supported: a bf16 rounding of the working tensor is coarser than the "
+           "h (x - m) correction it carries, so the majorization no longer holds";
+  if (R_ > 128) return "R > 128 is not supported: the factor tile is kept in LDS";
+  return nullptr;
+}
+
+void CpEngine::wls_step(const ViewArgs &a, const void *data, const ViewArgs &w, const void *weights, void *stream,
+                        double *weighted_sq) {
+  if (multi_) throw std::logic_error("ppals: a multi-start session takes no weighted step (take the winner first)");
+  if (const char *why = wls_refusal()) throw Unsupported(std::string("ppals: ") + why);
+  ModelBox bx;
+  if (dv_model_box(a, V_.glens, V_.row0, V_.llens[0], &bx)) {
+    ModelPlan mp;
+    shard_groups(bx, w.stride, mp);
+    model_operands(bx, mp);
+    const ModelSide ws = dv_model_side(w, bx, mp);
+    ops_.model_wls(mp, ws, xq_, xp_, R_, data, weights, a.dtype, V_.data, V_.dtype, weighted_sq ? scal_ : nullptr,
+                   stream);
+    if (V_.generation) ++*V_.generation;  // (as after an imputation)
+  } else if (weighted_sq) {
+    ops_.zero(scal_, sizeof(double));  // none of the box in this rank's rows
+  }
+  if (!weighted_sq) return;
+  if (dist_) comm_.allreduce_sum(scal_, 1);
+  ops_.d2h(weighted_sq, scal_, sizeof(double));
+}
+
+int CpEngine::run_wls(const ViewArgs &a, const void *data, const ViewArgs &w, const void *weights, void *stream,
+                      const CpOpts &o, int inner_sweeps, double rel_change, int *iters, double *weighted_res) {
+  return em_loop([&](double *sq) { wls_step(a, data, w, weights, stream, sq); }, o, inner_sweeps, rel_change, iters,
+                 weighted_res);
 }
 
 // ---------------------------------------------------------------------------- core consistency

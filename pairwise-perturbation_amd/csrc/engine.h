@@ -228,6 +228,19 @@ class CpEngine {
   // Returns 1 if a look found the residual <= o.tol.
   int run_em(const ViewArgs &a, const void *mask, void *stream, const CpOpts &o, int inner_sweeps,
              int *iters, double *observed_res);
+  // The majorization step of weighted CP (ppals_cp_wls_device): every element of this rank's rows of the
+  // box becomes x, the model, or fma(h, x - model, model) by its weight h, rounded once to the storage type;
+  // `a` / `w`: checked import views of one box (F32 or F64, the same type) at `data` / `weights`. Bumps the
+  // tensor's generation; factors, Grams and gradients do not change. weighted_sq == nullptr: asynchronous;
+  // otherwise *weighted_sq = the weighted loss over the box, all ranks, and the call waits for it.
+  void wls_step(const ViewArgs &a, const void *data, const ViewArgs &w, const void *weights, void *stream,
+                double *weighted_sq);
+  // why this session's tensor or rank admits no weighted step (BF16 storage, R > 128), or nullptr
+  const char *wls_refusal() const;
+  // ppals_cp_wls: repeat { wls_step; inner_sweeps exact sweeps }, the looks and the last step as run_em.
+  // Returns 1 on tol, 2 when the weighted residual fell by no more than rel_change of the look before.
+  int run_wls(const ViewArgs &a, const void *data, const ViewArgs &w, const void *weights, void *stream,
+              const CpOpts &o, int inner_sweeps, double rel_change, int *iters, double *weighted_res);
   const TensorDesc &tensor() const { return V_; }
   // The core consistency diagnostic (Bro & Kiers 2003; include/ppals.h): per start b, with
   // P_i = W_i (W_i^T W_i)^-1 of its current factors, the core G_b = V x_0 P_0^T ... x_{N-1} P_{N-1}^T
@@ -602,6 +615,10 @@ class CpEngine {
   const PackedSrc *packed_for(const ScanPlan &pl, PackedSrc &out);
   void check_tensor_generation();
   void model_operands(const ModelBox &bx, ModelPlan &mp);  // xq_ / xp_ and the offsets of a grouped plan
+  // groups that follow the shard (the imputation, the weighted step); `second`: a second side view's strides
+  void shard_groups(const ModelBox &bx, const int64_t *second, ModelPlan &mp) const;
+  template <typename Step>  // the loop run_em and run_wls share (engine.cpp)
+  int em_loop(Step &&step, const CpOpts &o, int inner_sweeps, double rel_change, int *iters, double *res);
   // s x R partials up to this size use one all-reduce + redundant update instead of
   // reduce-scatter + row-block update + all-gather (PPALS_COMM_SMALL_BYTES overrides)
   int64_t small_msg_bytes_ = 1 << 20;

@@ -29,6 +29,7 @@
 #include "kernels_eig.hip.h"
 #include "kernels_io.hip.h"
 #include "kernels_model.hip.h"
+#include "kernels_wls.hip.h"
 #include "kernels_bf16.hip.h"
 #include "kernels_prep.hip.h"
 
@@ -181,6 +182,15 @@ class HipOps : public Ops {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, mw_max));
     HIP_CHECK(hipFuncSetAttribute((const void *)k_model_impute_wide<double, true>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, mw_max));
+    const int wl_max = (int)wl_lds_bytes(WL_KMAX, sizeof(double));
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_model_wls<float, float>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, wl_max));
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_model_wls<float, double>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, wl_max));
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_model_wls<double, float>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, wl_max));
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_model_wls<double, double>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, wl_max));
     // (the on-chip centring tile: 56 KiB of image + 8 KiB of partial sums at VEC = 4 is the whole 64 KiB)
     HIP_CHECK(hipFuncSetAttribute((const void *)k_prep_rows<float, 4, 16, PREP_CENTER, true>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
@@ -1111,6 +1121,100 @@ class HipOps : public Ops {
       impute_launch(grid, (double *)V, m, Q, P, K, mp, tab, flags, part, wide);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventRecord(io_ev_out_, st_));  // and the caller may change the mask after the reads
+    HIP_CHECK(hipStreamWaitEvent(cs, io_ev_out_, 0));
+    if (sumsq) {
+      hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(1024), 0, st_, part, (int)npart, sumsq);
+      HIP_CHECK(hipGetLastError());
+    }
+  }
+
+  // ------------------------------------------------------------------ the weighted step
+  // flags of one side view of k_model_wls (`along_a`, `unit`, `vec` = the side's three bits): how it is
+  // read (dv_side_along_a), whether offA(a) = a, and whether a lane's vw elements are one aligned vector
+  static int wls_side_flags(const ModelGroup &ga, const ModelGroup &gb, const int64_t *sa, const int64_t *sb,
+                            int64_t off, const void *p, int vw, bool vec_st, int along_a, int unit, int vec) {
+    int first_a = 0, first_b = 0;  // (groups may hold modes of extent 1: their strides never count)
+    while (first_a < ga.n && ga.len[first_a] <= 1) first_a++;
+    while (first_b < gb.n && gb.len[first_b] <= 1) first_b++;
+    const int64_t s_a = first_a < ga.n ? sa[first_a] : 0, s_b = first_b < gb.n ? sb[first_b] : 0;
+    if (!dv_side_along_a(s_a, s_b)) return 0;
+    int f = along_a;
+    if (!ModelGroup::unit(ga.n, ga.len, sa)) return f;
+    f |= unit;
+    bool v = vec_st && off % vw == 0 && ((uintptr_t)p) % 16 == 0;
+    for (int i = 0; i < gb.n; i++)
+      if (gb.len[i] > 1 && sb[i] % vw != 0) v = false;
+    return f | (v ? vec : 0);
+  }
+  template <typename D, typename TS>
+  void wls_launch(dim3 grid, size_t lds, D *V, const void *X, const void *H, const double *Q, const double *P,
+                  int K, const ModelPlan &mp, int64_t woff, const int64_t *tab, int flags, double *part) {
+    const int64_t A = mp.ga.count, B = mp.gb.count;
+    const int64_t *tav = tab, *tax = tab + A, *taw = tab + 2 * A, *tbv = tab + 3 * A, *tbx = tbv + B,
+                  *tbw = tbx + B;
+    hipLaunchKernelGGL((k_model_wls<D, TS>), grid, dim3(256), lds, st_, V, (const TS *)X, (const TS *)H, Q, P, K,
+                       mp, woff, tav, tax, taw, tbv, tbx, tbw, flags, part);
+  }
+  void model_wls(const ModelPlan &plan, const ModelSide &ws, const double *Q, const double *P, int K,
+                 const void *data, const void *weights, int vdt, void *V, int dt, double *sumsq,
+                 void *caller_stream) override {
+    HIP_CHECK(hipSetDevice(dev_));
+    const int64_t A = plan.ga.count, B = plan.gb.count;
+    if (A <= 0 || B <= 0) {
+      if (sumsq) zero(sumsq, sizeof(double));
+      return;
+    }
+    if (K < 1 || K > WL_KMAX) throw std::runtime_error("ppals: model_wls needs 1 <= K <= 128");
+    if ((dt != F32 && dt != F64) || (vdt != DV_F32 && vdt != DV_F64))
+      throw std::runtime_error("ppals: model_wls stores F32 or F64 and reads F32 or F64 views");
+    const ModelPlan mp = dv_model_swapped(plan);  // the kernel's "view" is the shard, its "shard" the data
+    const int vw = dt == F32 ? 4 : 2;
+    const bool a_unit = mp.ga.view_unit();
+    bool vec_st = a_unit && A % vw == 0 && mp.voff % vw == 0 && ((uintptr_t)V) % 16 == 0;
+    for (int i = 0; i < mp.gb.n; i++)
+      if (mp.gb.len[i] > 1 && mp.gb.vs[i] % vw != 0) vec_st = false;
+    int flags = (a_unit ? WL_A_UNIT : 0) | (vec_st ? WL_VEC_ST : 0);
+    flags |= wls_side_flags(mp.ga, mp.gb, mp.ga.rs, mp.gb.rs, mp.roff, data, vw, vec_st, WL_X_ALONG_A, WL_X_UNIT,
+                            WL_X_VEC);
+    flags |= wls_side_flags(mp.ga, mp.gb, ws.ga.vs, ws.gb.vs, ws.off, weights, vw, vec_st, WL_H_ALONG_A, WL_H_UNIT,
+                            WL_H_VEC);
+    const bool one_b = !(flags & WL_X_ALONG_A) != !(flags & WL_H_ALONG_A);
+    const size_t lds = wl_lds_bytes(K, one_b ? (vdt == DV_F32 ? 4 : 8) : 0);
+    // the three offset tables of both groups, built on the engine stream (nothing of the caller's is read), and
+    // two rounds of the workgroups the LDS lets a CU hold, each walking its share of the b tiles
+    const int64_t ntA = (A + MV_TILE - 1) / MV_TILE, ntB = (B + MV_TILE - 1) / MV_TILE;
+    if (ntA > 0x7fffffff) throw std::runtime_error("ppals: model view too wide");
+    int64_t *tab = (int64_t *)ensure(ws_mv_, ws_mv_sz_, sizeof(int64_t) * 3 * (size_t)(A + B));
+    hipLaunchKernelGGL(k_model_offsets, dim3(grid_for(A, 256)), dim3(256), 0, st_, mp.ga, tab, tab + A);
+    hipLaunchKernelGGL(k_model_offsets_side, dim3(grid_for(A, 256)), dim3(256), 0, st_, ws.ga, tab + 2 * A);
+    hipLaunchKernelGGL(k_model_offsets, dim3(grid_for(B, 256)), dim3(256), 0, st_, mp.gb, tab + 3 * A,
+                       tab + 3 * A + B);
+    hipLaunchKernelGGL(k_model_offsets_side, dim3(grid_for(B, 256)), dim3(256), 0, st_, ws.gb, tab + 3 * A + 2 * B);
+    HIP_CHECK(hipGetLastError());
+    const int64_t want = std::max<int64_t>(1, ((int64_t)ncu_ * 2 * wl_wgs_per_cu(lds) + ntA - 1) / ntA);
+    const dim3 grid((unsigned)ntA, (unsigned)std::min<int64_t>(std::min<int64_t>(want, ntB), 65535));
+    const int64_t npart = (int64_t)grid.x * grid.y;
+    if (npart > 0x7fffffff) throw std::runtime_error("ppals: model view too wide");
+    double *part = (double *)ensure(ws_part_, ws_part_sz_, sizeof(double) * npart);
+    route("model.wls.%s.%s K=%d flags=%d lds=%zu", dt == F32 ? "f32" : "f64", vdt == DV_F32 ? "f32" : "f64", K, flags,
+          lds);
+    if (!io_ev_in_) {
+      HIP_CHECK(hipEventCreateWithFlags(&io_ev_in_, hipEventDisableTiming));
+      HIP_CHECK(hipEventCreateWithFlags(&io_ev_out_, hipEventDisableTiming));
+    }
+    hipStream_t cs = (hipStream_t)caller_stream;
+    HIP_CHECK(hipEventRecord(io_ev_in_, cs));  // the views are ready once the caller's work so far is done
+    HIP_CHECK(hipStreamWaitEvent(st_, io_ev_in_, 0));
+    if (dt == F32 && vdt == DV_F32)
+      wls_launch<float, float>(grid, lds, (float *)V, data, weights, Q, P, K, mp, ws.off, tab, flags, part);
+    else if (dt == F32)
+      wls_launch<float, double>(grid, lds, (float *)V, data, weights, Q, P, K, mp, ws.off, tab, flags, part);
+    else if (vdt == DV_F32)
+      wls_launch<double, float>(grid, lds, (double *)V, data, weights, Q, P, K, mp, ws.off, tab, flags, part);
+    else
+      wls_launch<double, double>(grid, lds, (double *)V, data, weights, Q, P, K, mp, ws.off, tab, flags, part);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(io_ev_out_, st_));  // and the caller may change the views after the reads
     HIP_CHECK(hipStreamWaitEvent(cs, io_ev_out_, 0));
     if (sumsq) {
       hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(1024), 0, st_, part, (int)npart, sumsq);

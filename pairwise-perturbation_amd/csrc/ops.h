@@ -248,6 +248,20 @@ class Ops {
     throw Unsupported("ppals: this back end has no device views");
   }
 
+  // The weighted step (ppals_cp_wls_device): every element of the plan's box of the shard V becomes
+  //   z = x where h >= 1,  the model sum where h <= 0 or NaN,  fma(h, x - sum, sum) otherwise,
+  // rounded once to the storage type dt (F32 / F64), x and h the elements of the data view (the plan's vs /
+  // voff, as model_impute's mask) and of the weights view (`ws`, dv_model_side), both of type vdt (DV_F32 /
+  // DV_F64). Group A follows the SHARD's fast side; the sum over k runs in model_impute's order, so weights
+  // in {0, 1} store the imputation's bits. sumsq (device scalar, may be nullptr): the loss, sum of
+  // min(h, 1) (x - sum)^2 over the elements with h > 0, in fp64, in a fixed order. 1 <= K <= 128. Ordered on
+  // `caller_stream` as copy_view; the host does not block.
+  virtual void model_wls(const ModelPlan & /*mp*/, const ModelSide & /*ws*/, const double * /*Q*/,
+                         const double * /*P*/, int /*K*/, const void * /*data*/, const void * /*weights*/,
+                         int /*vdt*/, void * /*V*/, int /*dt*/, double * /*sumsq*/, void * /*caller_stream*/) {
+    throw Unsupported("ppals: this back end has no device views");
+  }
+
   // Order work on the engine stream against a caller's stream, as copy_view does it: join_stream makes the
   // work queued on the engine stream from now on wait for what `caller_stream` holds so far, release_stream
   // makes what the caller queues there later wait for the engine stream's work so far. The host does not block.

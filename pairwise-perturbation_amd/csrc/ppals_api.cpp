@@ -421,14 +421,9 @@ int ppals_tensor_rescale(ppals_tensor *t, int mode, const double *factors) {
 // ------------------------------------------------------------------ device views
 // every check of ppals_tensor_check_device_view; on success *a holds the resolved view
 // (`what` names the entry point in the messages; the model exports check their views here too)
-static int check_desc_view(ppals_ctx *ctx, const TensorDesc &d, const char *what, int dir,
-                           const void *ptr, int dtype, const int64_t *box_lo, const int64_t *box_len,
-                           const int64_t *strides, ViewArgs *a, bool mask = false) {
+// (the half that asks the runtime about the pointer, after dv_check_args has resolved *a)
+static int check_view_ptr(ppals_ctx *ctx, const char *what, const void *ptr, const ViewArgs *a) {
   std::string err;
-  if (!dv_check_args(dir, d.order, d.glens, dtype, box_lo, box_len, strides, a, &err, mask)) {
-    g_err = what + err;
-    return PPALS_ERR_ARG;
-  }
   Ops::PtrInfo info;
   if (!ctx->ops->device_ptr_info(ptr, &info, &err) || !info.is_device) {
     g_err = std::string(what) + "the pointer is not device memory of the context's device (" +
@@ -444,6 +439,16 @@ static int check_desc_view(ppals_ctx *ctx, const TensorDesc &d, const char *what
     return PPALS_ERR_ARG;
   }
   return PPALS_OK;
+}
+static int check_desc_view(ppals_ctx *ctx, const TensorDesc &d, const char *what, int dir,
+                           const void *ptr, int dtype, const int64_t *box_lo, const int64_t *box_len,
+                           const int64_t *strides, ViewArgs *a, bool mask = false) {
+  std::string err;
+  if (!dv_check_args(dir, d.order, d.glens, dtype, box_lo, box_len, strides, a, &err, mask)) {
+    g_err = what + err;
+    return PPALS_ERR_ARG;
+  }
+  return check_view_ptr(ctx, what, ptr, a);
 }
 static int check_view(ppals_tensor *t, int dir, const void *ptr, int dtype, const int64_t *box_lo,
                       const int64_t *box_len, const int64_t *strides, ViewArgs *a) {
@@ -861,6 +866,56 @@ int ppals_cp_em(ppals_cp *s, const void *mask, const int64_t *box_lo, const int6
   const int rc = check_mask_view(s->ctx, s->eng->tensor(), "ppals_cp_em: ", mask, box_lo, box_len, strides, &a);
   if (rc != PPALS_OK) return rc;
   return s->eng->run_em(a, mask, stream, to_opts(o), inner_sweeps, iters, observed_res);
+  API_END(PPALS_ERR_HIP)
+}
+
+// the two views of a weighted step: every check ppals_tensor_check_device_view makes of an import source,
+// the arithmetic of both views (and what the session itself refuses) ahead of the pointer queries
+static int check_wls_views(ppals_cp *s, const char *fn, const void *data, const void *weights, int dtype,
+                           const int64_t *box_lo, const int64_t *box_len, const int64_t *data_strides,
+                           const int64_t *weight_strides, ViewArgs *a, ViewArgs *w) {
+  if (!data) return fail_fn(PPALS_ERR_ARG, fn, "the data pointer is NULL");
+  if (!weights) return fail_fn(PPALS_ERR_ARG, fn, "the weights pointer is NULL");
+  if (dtype != PPALS_F32 && dtype != PPALS_F64)
+    return fail_fn(PPALS_ERR_ARG, fn, "bad dtype of the data and weights views (PPALS_F32 or PPALS_F64)");
+  const TensorDesc &d = s->eng->tensor();
+  std::string err;
+  if (!dv_check_args(DV_IMPORT, d.order, d.glens, dtype, box_lo, box_len, data_strides, a, &err))
+    return fail_fn(PPALS_ERR_ARG, fn, ("the data view: " + err).c_str());
+  if (!dv_check_args(DV_IMPORT, d.order, d.glens, dtype, box_lo, box_len, weight_strides, w, &err))
+    return fail_fn(PPALS_ERR_ARG, fn, ("the weights view: " + err).c_str());
+  if (const char *why = s->eng->wls_refusal()) return fail_fn(PPALS_ERR_UNSUPPORTED, fn, why);
+  const std::string pre = std::string(fn) + ": ";
+  if (const int rc = check_view_ptr(s->ctx, (pre + "the data view: ").c_str(), data, a)) return rc;
+  return check_view_ptr(s->ctx, (pre + "the weights view: ").c_str(), weights, w);
+}
+int ppals_cp_wls_device(ppals_cp *s, const void *data, const void *weights, int dtype, const int64_t *box_lo,
+                        const int64_t *box_len, const int64_t *data_strides, const int64_t *weight_strides,
+                        void *stream, double *weighted_sq) {
+  if (!s || !s->eng || !s->ctx) return fail(PPALS_ERR_ARG, "NULL session");
+  API_BEGIN
+  ViewArgs a, w;
+  const int rc = check_wls_views(s, "ppals_cp_wls_device", data, weights, dtype, box_lo, box_len, data_strides,
+                                 weight_strides, &a, &w);
+  if (rc != PPALS_OK) return rc;
+  s->eng->wls_step(a, data, w, weights, stream, weighted_sq);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_cp_wls(ppals_cp *s, const void *data, const void *weights, int dtype, const int64_t *box_lo,
+                 const int64_t *box_len, const int64_t *data_strides, const int64_t *weight_strides, void *stream,
+                 const ppals_cp_opts *o, int inner_sweeps, double rel_change, int *iters, double *weighted_res) {
+  API_BEGIN
+  if (!o) return fail(PPALS_ERR_ARG, "ppals_cp_wls: NULL options");
+  if (inner_sweeps < 1) return fail(PPALS_ERR_ARG, "ppals_cp_wls: inner_sweeps must be at least 1");
+  if (!(rel_change >= 0)) return fail(PPALS_ERR_ARG, "ppals_cp_wls: rel_change must not be negative");
+  if (o->maxiter < 0) return fail(PPALS_ERR_ARG, "ppals_cp_wls: maxiter must not be negative");
+  if (!s || !s->eng || !s->ctx) return fail(PPALS_ERR_ARG, "NULL session");
+  ViewArgs a, w;
+  const int rc = check_wls_views(s, "ppals_cp_wls", data, weights, dtype, box_lo, box_len, data_strides,
+                                 weight_strides, &a, &w);
+  if (rc != PPALS_OK) return rc;
+  return s->eng->run_wls(a, data, w, weights, stream, to_opts(o), inner_sweeps, rel_change, iters, weighted_res);
   API_END(PPALS_ERR_HIP)
 }
 

@@ -61,7 +61,7 @@ EXPORTS = [
     "ppals_cp_multi_create", "ppals_cp_multi_destroy", "ppals_cp_multi_set_factors",
     "ppals_cp_multi_get_factors", "ppals_cp_multi_set_schedule", "ppals_cp_multi_sweeps",
     "ppals_cp_multi_residuals", "ppals_cp_multi_gradnorms", "ppals_cp_multi_run",
-    "ppals_cp_multi_take", "ppals_cp_impute_device", "ppals_cp_em",
+    "ppals_cp_multi_take", "ppals_cp_impute_device", "ppals_cp_em", "ppals_cp_wls_device", "ppals_cp_wls",
     "ppals_cp_set_nonneg", "ppals_cp_get_nonneg",
     "ppals_cp_multi_set_nonneg", "ppals_cp_multi_get_nonneg",
     "ppals_cp_multi_create_ranks", "ppals_cp_multi_ranks",
@@ -646,7 +646,79 @@ class _Impute:
         return rc, it.value, res.value
 
 
-class CP(_ModelExport, _Impute):
+def weights_from_std(std):
+    """element weights for CP.wls_torch / run_wls from a noise standard deviation per element (a numpy array or
+    a torch tensor, any shape that broadcasts against the data): std.min()**2 / std**2, which lies in (0, 1]
+    as Kiers' majorization wants, with 0 where std is inf or NaN (such an element is missing)."""
+    if isinstance(std, np.ndarray) or not hasattr(std, "device"):
+        std = np.asarray(std, dtype=np.float64)
+        ok = np.isfinite(std)
+        lo = std[ok].min() if ok.any() else 1.0
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(ok, (lo / std) ** 2, 0.0)
+    torch = _torch()
+    ok = torch.isfinite(std)
+    lo = std[ok].min() if bool(ok.any()) else torch.ones((), dtype=std.dtype, device=std.device)
+    return torch.where(ok, (lo / std) ** 2, torch.zeros((), dtype=std.dtype, device=std.device))
+
+
+class _Wls:
+    """element weights (ppals_cp_wls_device / ppals_cp_wls): Kiers' majorization step and its driver"""
+
+    def _wls_views(self, shape, data_strides, weight_strides, lo):
+        blo, blen = Tensor._box(self, shape, lo)
+        n = len(self.lens)
+        return (blo, blen, (C.c_int64 * n)(*[int(x) for x in data_strides]),
+                (C.c_int64 * n)(*[int(x) for x in weight_strides]))
+
+    def wls_device(self, data_ptr, weights_ptr, dtype, shape, data_strides, weight_strides, lo=None, stream=0,
+                   want_loss=False):
+        """raw ppals_cp_wls_device: every element of the box at lo becomes x (weight h >= 1), the current model
+        m (h <= 0 or NaN) or fma(h, x - m, m), x and h read from the two views (F32 or F64, strides in
+        elements, 0 broadcasts). Returns the weighted loss sum h (x - m)^2 if want_loss (the call then waits
+        for it), else None (the host does not wait)."""
+        blo, blen, ds, ws = self._wls_views(shape, data_strides, weight_strides, lo)
+        sq = C.c_double(0)
+        _check(lib().ppals_cp_wls_device(self._h, C.c_void_p(int(data_ptr)), C.c_void_p(int(weights_ptr)), int(dtype),
+                                         blo, blen, ds, ws, C.c_void_p(int(stream or 0)),
+                                         C.byref(sq) if want_loss else None))
+        return float(sq.value) if want_loss else None
+
+    def _torch_wls(self, data, weights):
+        torch = _torch()
+        if data.dtype != weights.dtype:
+            raise TypeError(f"data is {data.dtype} and weights {weights.dtype}: the two views share one dtype")
+        if data.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"the torch dtype {data.dtype} of data and weights is not torch.float32 or torch.float64")
+        if tuple(weights.shape) != tuple(data.shape):
+            weights = weights.expand(data.shape)   # stride 0 where it broadcasts: no copy
+        dptr, code, shape, dstr = self.V._torch_view(data, (torch.float32, torch.float64))
+        wptr, _, _, wstr = self.V._torch_view(weights, (torch.float32, torch.float64))
+        return dptr, wptr, code, shape, dstr, wstr
+
+    def wls_torch(self, data, weights, lo=None, stream=None, want_loss=False):
+        """wls_device with torch tensors on the context's device (f32 or f64, the same dtype, any strides);
+        `weights` is expanded to data.shape when it broadcasts (a per-variable vector costs its own length).
+        The box at lo has data's shape. Ordered on `stream` (default: torch's current stream)."""
+        dptr, wptr, code, shape, dstr, wstr = self._torch_wls(data, weights)
+        return self.wls_device(dptr, wptr, code, shape, dstr, wstr, lo, Tensor._stream(stream), want_loss)
+
+    def run_wls(self, data, weights, inner_sweeps=1, rel_change=0.0, lo=None, stream=None, **opts):
+        """ppals_cp_wls: repeat { majorization step; inner_sweeps exact sweeps } until maxiter iterations,
+        timelimit, a weighted residual <= tol (rc 1) or, from the second look on, a fall of no more than
+        rel_change of the residual at the look before (rc 2); looks every resprint iterations. Uses tol,
+        timelimit, maxiter, resprint and lam. Returns (rc, iterations, weighted residual sqrt(sum h (x - m)^2))."""
+        dptr, wptr, code, shape, dstr, wstr = self._torch_wls(data, weights)
+        blo, blen, ds, ws = self._wls_views(shape, dstr, wstr, lo)
+        o = _opts(**opts)
+        it, res = C.c_int(0), C.c_double(0)
+        rc = _check(lib().ppals_cp_wls(self._h, C.c_void_p(int(dptr)), C.c_void_p(int(wptr)), int(code), blo, blen,
+                                       ds, ws, C.c_void_p(int(Tensor._stream(stream) or 0)), C.byref(o),
+                                       int(inner_sweeps), C.c_double(float(rel_change)), C.byref(it), C.byref(res)))
+        return rc, it.value, res.value
+
+
+class CP(_ModelExport, _Impute, _Wls):
     """a CP-ALS session: factors, Grams and dimension-tree caches resident in HBM"""
     _export_fn = "ppals_cp_export_model_device"
     _impute_fn, _em_fn = "ppals_cp_impute_device", "ppals_cp_em"
