@@ -773,6 +773,62 @@ int ppals_cp_wls(ppals_cp *s, const void *data, const void *weights, int dtype,
                  const ppals_cp_opts *o, int inner_sweeps, double rel_change,
                  int *iters, double *weighted_res);
 
+/* ---- Robust CP: Huber's loss by majorization (Huber 1964; Kiers 1997) ----
+ * For data with gross outliers (scatter lines, dead pixels, spikes) of which neither a noise estimate nor a
+ * mask is known: min L_c(m) = sum_e h_e rho_c(x_e - m_e), rho_c(r) = r^2 for |r| <= c and c (2 |r| - c)
+ * otherwise (Huber's function scaled so that its quadratic part is the plain sum of squares; c = +inf is the
+ * weighted loss above). With the current model m0, r0 = x - m0 and omega = min(1, c / |r0|),
+ * rho_c(r) <= omega r^2 + (rho_c(r0) - omega r0^2) for every r, with equality at r0; Kiers' step with the
+ * weight h omega <= 1 gives the working tensor z = m0 + h clip(x - m0, -c, c) and
+ * L_c(m) <= sum (z - m)^2 + const(m0), equality at m0: any ordinary sweep on Z cannot raise L_c.
+ *
+ * ppals_cp_huber_device: one such step. Views, checks, box semantics, stream ordering, the generation bump
+ * and the refusals are those of ppals_cp_wls_device; `weights` may be NULL (h = 1 everywhere; weight_strides is
+ * then ignored), which is how robust fits are usually run and reads one view less. Per element, m the fp64
+ * model formed as the weighted step forms it, x and h widened to fp64:
+ *     !(h > 0) (h <= 0 or NaN):              z = m                  loss 0; x is not looked at
+ *     d = x - m, a = |d|, !(a > c), h >= 1:  z = x                  d^2
+ *     same, 0 < h < 1:                       z = fma(h, d, m)       h d^2
+ *     a > c, dc = copysign(c, d), h >= 1:    z = m + dc             c (2 a - c)        counts as clipped
+ *     same, 0 < h < 1:                       z = fma(h, dc, m)      h c (2 a - c)      counts as clipped
+ * rounded once to the storage type. A NaN x lands in the !(a > c) rows and propagates as in the weighted step;
+ * an infinite x under h > 0 and finite c is stored as m +- c and makes the loss infinite.
+ *   huber_loss == NULL and clipped == NULL: the host does not block. Otherwise *huber_loss = L_c and
+ *   *clipped = the number of clipped elements over the box, each formed in a fixed order (the same state gives
+ *   the same bits) and summed over the ranks; the call returns when they are on the host.
+ * With weights and c = +inf the resident tensor and the returned loss equal, BIT FOR BIT, those of
+ * ppals_cp_wls_device from the same state; with weights == NULL and c = +inf the tensor equals an import of
+ * `data`. PPALS_ERR_ARG in addition for !(c > 0) (zero, negative, NaN). */
+int ppals_cp_huber_device(ppals_cp *s, const void *data, const void *weights /* NULL: h = 1 everywhere */,
+                          int dtype, const int64_t *box_lo, const int64_t *box_len,
+                          const int64_t *data_strides, const int64_t *weight_strides /* ignored if weights NULL */,
+                          double c, void *stream, double *huber_loss /* may be NULL */,
+                          int64_t *clipped /* may be NULL */);
+/* Robust CP at a FIXED c: ppals_cp_wls with the Huber step in the weighted step's place; looks, stop rules,
+ * return codes, the last step on the way out and *iters are those of ppals_cp_wls, *robust_res = sqrt(L_c).
+ * The argument errors are those of ppals_cp_wls, and !(c > 0). (c is not re-estimated inside: that would break
+ * the monotone descent. Stage it outside: some plain sweeps, c from the residual quantile below, a run; c
+ * again from the robust fit's residuals, a second run.) */
+int ppals_cp_robust(ppals_cp *s, const void *data, const void *weights, int dtype, const int64_t *box_lo,
+                    const int64_t *box_len, const int64_t *data_strides, const int64_t *weight_strides,
+                    void *stream, double c, const ppals_cp_opts *o, int inner_sweeps, double rel_change,
+                    int *iters, double *robust_res /* sqrt(L_c) */);
+/* A quantile of the absolute residuals |x - m| of the current factors over the box, without materialising the
+ * residual: what the threshold c is chosen from (1.345 x 1.4826 x the median is the usual choice). Reads the
+ * session's factors and the views only: no resident tensor is read and nothing is written, so every storage
+ * type is accepted (BF16 too) and session and tensor are left bit for bit.
+ * Over the elements of the box with h > 0 (all of them if weights == NULL), a_e = (float)|x_e - m_e|: the fp64
+ * difference rounded to nearest fp32, every NaN one canonical NaN that sorts after +inf. *count = n, the number
+ * of such elements; k = min(n - 1, max(0, ceil(p n) - 1)) in fp64; *value = the k-th smallest a_e (0-based)
+ * widened to double; n = 0: *value = NaN, PPALS_OK. Exact (a radix select on integer counts): the result
+ * does not depend on the launch geometry. The call waits for the result.
+ * PPALS_ERR_ARG: p outside [0, 1] or NaN, NULL value, and the view checks of ppals_cp_huber_device;
+ * PPALS_ERR_UNSUPPORTED: R > 128, a context of more than one rank, a back end without device views. */
+int ppals_cp_abs_residual_quantile(ppals_cp *s, const void *data, const void *weights /* may be NULL */, int dtype,
+                                   const int64_t *box_lo, const int64_t *box_len, const int64_t *data_strides,
+                                   const int64_t *weight_strides, void *stream, double p,
+                                   double *value, int64_t *count);
+
 /* ---- Tucker with missing entries (TensorLy's tucker(mask=...)): imputation and an EM driver ----
  * The contracts of ppals_cp_impute_device / ppals_cp_em with a Tucker session in the CP session's place:
  * the same PPALS_U8 mask view (a box of the GLOBAL tensor, strides >= 0, 0 broadcasts, NULL = dense, a byte

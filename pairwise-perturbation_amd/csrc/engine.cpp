@@ -29,6 +29,7 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <limits>
 #include <stdexcept>
 
 namespace ppals {
@@ -2605,31 +2606,109 @@ const char *CpEngine::wls_refusal() const {
   return nullptr;
 }
 
-void CpEngine::wls_step(const ViewArgs &a, const void *data, const ViewArgs &w, const void *weights, void *stream,
-                        double *weighted_sq) {
-  if (multi_) throw std::logic_error("ppals: a multi-start session takes no weighted step (take the winner first)");
+// The body of wls_step and huber_step: `c` < 0 asks for the weighted rule (then `w` is given), otherwise the
+// Huber rule at that threshold, `w` == nullptr for the family without weights. out[0] = the loss, out[1] =
+// the clipped count (Huber only), both over all ranks; out == nullptr: asynchronous.
+void CpEngine::side_step(const char *what, const ViewArgs &a, const void *data, const ViewArgs *w,
+                         const void *weights, void *stream, double c, double *out) {
+  if (multi_)
+    throw std::logic_error(std::string("ppals: a multi-start session takes no ") + what +
+                           " step (take the winner first)");
   if (const char *why = wls_refusal()) throw Unsupported(std::string("ppals: ") + why);
+  const bool huber = c >= 0;
+  const int nout = huber ? 2 : 1;
   ModelBox bx;
   if (dv_model_box(a, V_.glens, V_.row0, V_.llens[0], &bx)) {
     ModelPlan mp;
-    shard_groups(bx, w.stride, mp);
+    shard_groups(bx, w ? w->stride : nullptr, mp);
     model_operands(bx, mp);
-    const ModelSide ws = dv_model_side(w, bx, mp);
-    ops_.model_wls(mp, ws, xq_, xp_, R_, data, weights, a.dtype, V_.data, V_.dtype, weighted_sq ? scal_ : nullptr,
-                   stream);
+    ModelSide ws;
+    if (w) ws = dv_model_side(*w, bx, mp);
+    if (huber)
+      ops_.model_huber(mp, w ? &ws : nullptr, xq_, xp_, R_, data, weights, a.dtype, V_.data, V_.dtype, c,
+                       out ? scal_ : nullptr, stream);
+    else
+      ops_.model_wls(mp, ws, xq_, xp_, R_, data, weights, a.dtype, V_.data, V_.dtype, out ? scal_ : nullptr, stream);
     if (V_.generation) ++*V_.generation;  // (as after an imputation)
-  } else if (weighted_sq) {
-    ops_.zero(scal_, sizeof(double));  // none of the box in this rank's rows
+  } else if (out) {
+    ops_.zero(scal_, sizeof(double) * nout);  // none of the box in this rank's rows
   }
-  if (!weighted_sq) return;
-  if (dist_) comm_.allreduce_sum(scal_, 1);
-  ops_.d2h(weighted_sq, scal_, sizeof(double));
+  if (!out) return;
+  if (dist_) comm_.allreduce_sum(scal_, nout);
+  ops_.d2h(out, scal_, sizeof(double) * nout);
+}
+
+void CpEngine::wls_step(const ViewArgs &a, const void *data, const ViewArgs &w, const void *weights, void *stream,
+                        double *weighted_sq) {
+  side_step("weighted", a, data, &w, weights, stream, -1.0, weighted_sq);
 }
 
 int CpEngine::run_wls(const ViewArgs &a, const void *data, const ViewArgs &w, const void *weights, void *stream,
                       const CpOpts &o, int inner_sweeps, double rel_change, int *iters, double *weighted_res) {
   return em_loop([&](double *sq) { wls_step(a, data, w, weights, stream, sq); }, o, inner_sweeps, rel_change, iters,
                  weighted_res);
+}
+
+// The Huber step: the weighted step with the residual clipped to [-c, c] first.
+void CpEngine::huber_step(const ViewArgs &a, const void *data, const ViewArgs *w, const void *weights, void *stream,
+                          double c, double *huber_loss, int64_t *clipped) {
+  double out[2] = {0, 0};
+  side_step("Huber", a, data, w, weights, stream, c, (huber_loss || clipped) ? out : nullptr);
+  if (huber_loss) *huber_loss = out[0];
+  if (clipped) *clipped = (int64_t)out[1];
+}
+
+int CpEngine::run_robust(const ViewArgs &a, const void *data, const ViewArgs *w, const void *weights, void *stream,
+                         double c, const CpOpts &o, int inner_sweeps, double rel_change, int *iters,
+                         double *robust_res) {
+  return em_loop([&](double *sq) { huber_step(a, data, w, weights, stream, c, sq, nullptr); }, o, inner_sweeps,
+                 rel_change, iters, robust_res);
+}
+
+const char *CpEngine::quantile_refusal() const {
+  if (R_ > 128) return "R > 128 is not supported: the factor tile is kept in LDS";
+  if (P_ > 1) return "the residual quantile runs on one rank";
+  return nullptr;
+}
+
+// The k-th smallest (k = min(n - 1, max(0, ceil(p n) - 1))) of (float)|x - m| over the box's elements with
+// h > 0, by a radix select on the fp32 patterns: 11, 10 and 10 bits, one histogram pass each, the bin picked
+// here between the passes. Nothing of the tensor is read: only its shape and this rank's rows.
+void CpEngine::abs_residual_quantile(const ViewArgs &a, const void *data, const ViewArgs *w, const void *weights,
+                                     void *stream, double p, double *value, int64_t *count) {
+  if (multi_) throw std::logic_error("ppals: a multi-start session has no residual quantile (take the winner first)");
+  if (const char *why = quantile_refusal()) throw Unsupported(std::string("ppals: ") + why);
+  ModelBox bx;
+  uint64_t n = 0;
+  uint32_t key = 0;
+  if (dv_model_box(a, V_.glens, V_.row0, V_.llens[0], &bx)) {
+    ModelPlan mp;
+    shard_groups(bx, w ? w->stride : nullptr, mp);
+    model_operands(bx, mp);
+    ModelSide ws;
+    if (w) ws = dv_model_side(*w, bx, mp);
+    std::vector<uint64_t> hist(Ops::ABSRES_BINS);
+    uint64_t k = 0;
+    const int shifts[3] = {20, 10, 0}, bits[3] = {11, 10, 10};
+    for (int pass = 0; pass < 3; pass++) {
+      const int pshift = pass == 0 ? 31 : shifts[pass - 1];
+      ops_.model_absres_hist(mp, w ? &ws : nullptr, xq_, xp_, R_, data, weights, a.dtype, pshift, key >> pshift,
+                             shifts[pass], (1u << bits[pass]) - 1, hist.data(), stream);
+      if (pass == 0) {
+        for (uint64_t h : hist) n += h;
+        if (n == 0) break;
+        const double want = std::ceil(p * (double)n) - 1.0;
+        k = want <= 0 ? 0 : (want >= (double)(n - 1) ? n - 1 : (uint64_t)want);
+      }
+      uint32_t b = 0;
+      while (k >= hist[b]) k -= hist[b++];  // (the pass counted exactly the keys of the chosen prefix: k < their sum)
+      key |= b << shifts[pass];
+    }
+  }
+  if (count) *count = (int64_t)n;
+  float f;
+  std::memcpy(&f, &key, sizeof f);
+  *value = n ? (double)f : std::numeric_limits<double>::quiet_NaN();
 }
 
 // ---------------------------------------------------------------------------- core consistency

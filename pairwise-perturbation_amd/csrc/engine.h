@@ -241,6 +241,20 @@ class CpEngine {
   // Returns 1 on tol, 2 when the weighted residual fell by no more than rel_change of the look before.
   int run_wls(const ViewArgs &a, const void *data, const ViewArgs &w, const void *weights, void *stream,
               const CpOpts &o, int inner_sweeps, double rel_change, int *iters, double *weighted_res);
+  // The Huber step (ppals_cp_huber_device): wls_step with the residual clipped to [-c, c], c > 0 (+inf: the
+  // weighted step's bits and loss). w == nullptr: no weights view, h = 1. huber_loss / clipped (either may be
+  // nullptr; both nullptr: asynchronous): sum h rho_c(x - m) and the number of elements with |x - m| > c, all ranks.
+  void huber_step(const ViewArgs &a, const void *data, const ViewArgs *w, const void *weights, void *stream, double c,
+                  double *huber_loss, int64_t *clipped);
+  // ppals_cp_robust: run_wls with the Huber step at a fixed c; *robust_res = sqrt(the Huber loss).
+  int run_robust(const ViewArgs &a, const void *data, const ViewArgs *w, const void *weights, void *stream, double c,
+                 const CpOpts &o, int inner_sweeps, double rel_change, int *iters, double *robust_res);
+  // ppals_cp_abs_residual_quantile: *count = the elements of the box with h > 0 (w == nullptr: all), *value =
+  // the k-th smallest (float)|x - m| among them, k = min(n - 1, max(0, ceil(p n) - 1)), NaN last; NaN if there
+  // are none. Reads the factors and the views only (any storage type); waits for the result.
+  const char *quantile_refusal() const;  // R > 128, more than one rank; or nullptr
+  void abs_residual_quantile(const ViewArgs &a, const void *data, const ViewArgs *w, const void *weights,
+                             void *stream, double p, double *value, int64_t *count);
   const TensorDesc &tensor() const { return V_; }
   // The core consistency diagnostic (Bro & Kiers 2003; include/ppals.h): per start b, with
   // P_i = W_i (W_i^T W_i)^-1 of its current factors, the core G_b = V x_0 P_0^T ... x_{N-1} P_{N-1}^T
@@ -617,7 +631,10 @@ class CpEngine {
   void model_operands(const ModelBox &bx, ModelPlan &mp);  // xq_ / xp_ and the offsets of a grouped plan
   // groups that follow the shard (the imputation, the weighted step); `second`: a second side view's strides
   void shard_groups(const ModelBox &bx, const int64_t *second, ModelPlan &mp) const;
-  template <typename Step>  // the loop run_em and run_wls share (engine.cpp)
+  // the body wls_step and huber_step share (engine.cpp)
+  void side_step(const char *what, const ViewArgs &a, const void *data, const ViewArgs *w, const void *weights,
+                 void *stream, double c, double *out);
+  template <typename Step>  // the loop run_em, run_wls and run_robust share (engine.cpp)
   int em_loop(Step &&step, const CpOpts &o, int inner_sweeps, double rel_change, int *iters, double *res);
   // s x R partials up to this size use one all-reduce + redundant update instead of
   // reduce-scatter + row-block update + all-gather (PPALS_COMM_SMALL_BYTES overrides)

@@ -30,6 +30,7 @@
 #include "kernels_io.hip.h"
 #include "kernels_model.hip.h"
 #include "kernels_wls.hip.h"
+#include "kernels_huber.hip.h"
 #include "kernels_bf16.hip.h"
 #include "kernels_prep.hip.h"
 
@@ -191,6 +192,16 @@ class HipOps : public Ops {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, wl_max));
     HIP_CHECK(hipFuncSetAttribute((const void *)k_model_wls<double, double>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, wl_max));
+    const void *huber_kernels[] = {
+        (const void *)k_model_huber<float, float>,      (const void *)k_model_huber<float, double>,
+        (const void *)k_model_huber<double, float>,     (const void *)k_model_huber<double, double>,
+        (const void *)k_model_huber_now<float, float>,  (const void *)k_model_huber_now<float, double>,
+        (const void *)k_model_huber_now<double, float>, (const void *)k_model_huber_now<double, double>,
+        (const void *)k_model_absres_hist<float, true>, (const void *)k_model_absres_hist<float, false>,
+        (const void *)k_model_absres_hist<double, true>, (const void *)k_model_absres_hist<double, false>};
+    for (const void *k : huber_kernels)
+      HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    wl_max + (int)(sizeof(uint32_t) * WL_HIST_BINS)));
     // (the on-chip centring tile: 56 KiB of image + 8 KiB of partial sums at VEC = 4 is the whole 64 KiB)
     HIP_CHECK(hipFuncSetAttribute((const void *)k_prep_rows<float, 4, 16, PREP_CENTER, true>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
@@ -222,6 +233,7 @@ class HipOps : public Ops {
     if (ws_pack_) hipFree(ws_pack_);
     if (pack_spread_) hipFree(pack_spread_);
     if (ws_mv_) hipFree(ws_mv_);
+    if (ws_hist_) hipFree(ws_hist_);
     if (ws_slab_) hipFree(ws_slab_);
     if (ws_krp_) hipFree(ws_krp_);
     if (ws_part_) hipFree(ws_part_);
@@ -1146,58 +1158,104 @@ class HipOps : public Ops {
       if (gb.len[i] > 1 && sb[i] % vw != 0) v = false;
     return f | (v ? vec : 0);
   }
+  // One launch of the tile loop of kernels_wls.hip.h: the weighted step (WL_WLS), the Huber step (WL_HUBER, `c`;
+  // ws == nullptr: the family without a weights view) or a pass of the residual quantile's radix select
+  // (WL_HIST: V is not touched, `ghist`). out (device, may be nullptr): the loss, and for WL_HUBER the clipped
+  // count behind it.
+  struct WlJob {
+    int kind;
+    const ModelSide *ws;
+    const void *data, *weights;
+    int vdt;
+    void *V;
+    int dt;
+    double c;
+    double *out;
+    int pshift, shift;
+    uint32_t prefix, mask;
+    unsigned long long *ghist;
+  };
   template <typename D, typename TS>
-  void wls_launch(dim3 grid, size_t lds, D *V, const void *X, const void *H, const double *Q, const double *P,
-                  int K, const ModelPlan &mp, int64_t woff, const int64_t *tab, int flags, double *part) {
+  void wl_launch(const WlJob &j, dim3 grid, size_t lds, const double *Q, const double *P, int K, const ModelPlan &mp,
+                 const int64_t *tab, int flags, double *part) {
     const int64_t A = mp.ga.count, B = mp.gb.count;
-    const int64_t *tav = tab, *tax = tab + A, *taw = tab + 2 * A, *tbv = tab + 3 * A, *tbx = tbv + B,
-                  *tbw = tbx + B;
-    hipLaunchKernelGGL((k_model_wls<D, TS>), grid, dim3(256), lds, st_, V, (const TS *)X, (const TS *)H, Q, P, K,
-                       mp, woff, tav, tax, taw, tbv, tbx, tbw, flags, part);
+    const int nt = j.ws ? 3 : 2;  // tables per group: the shard's, the data's, the weights'
+    const int64_t *tav = tab, *tax = tab + A, *taw = tab + 2 * A, *tbv = tab + nt * A, *tbx = tbv + B, *tbw = tbx + B;
+    D *V = (D *)j.V;
+    const TS *X = (const TS *)j.data, *H = (const TS *)j.weights;
+    const int64_t woff = j.ws ? j.ws->off : 0;
+    if (j.kind == WL_WLS)
+      hipLaunchKernelGGL((k_model_wls<D, TS>), grid, dim3(256), lds, st_, V, X, H, Q, P, K, mp, woff, tav, tax, taw, tbv,
+                         tbx, tbw, flags, part);
+    else if (j.kind == WL_HUBER && j.ws)
+      hipLaunchKernelGGL((k_model_huber<D, TS>), grid, dim3(256), lds, st_, V, X, H, Q, P, K, mp, woff, tav, tax, taw,
+                         tbv, tbx, tbw, flags, j.c, part);
+    else if (j.kind == WL_HUBER)
+      hipLaunchKernelGGL((k_model_huber_now<D, TS>), grid, dim3(256), lds, st_, V, X, Q, P, K, mp, tav, tax, tbv, tbx,
+                         flags, j.c, part);
+    else if constexpr (std::is_same<D, TS>::value) {
+      if (j.ws)
+        hipLaunchKernelGGL((k_model_absres_hist<TS, true>), grid, dim3(256), lds, st_, X, H, Q, P, K, mp, woff, tax, taw,
+                           tbx, tbw, flags, j.pshift, j.prefix, j.shift, j.mask, j.ghist);
+      else
+        hipLaunchKernelGGL((k_model_absres_hist<TS, false>), grid, dim3(256), lds, st_, X, H, Q, P, K, mp, woff, tax, taw,
+                           tbx, tbw, flags, j.pshift, j.prefix, j.shift, j.mask, j.ghist);
+    }
   }
-  void model_wls(const ModelPlan &plan, const ModelSide &ws, const double *Q, const double *P, int K,
-                 const void *data, const void *weights, int vdt, void *V, int dt, double *sumsq,
-                 void *caller_stream) override {
+  void wl_run(const WlJob &j, const char *name, const ModelPlan &plan, const double *Q, const double *P, int K,
+              void *caller_stream) {
     HIP_CHECK(hipSetDevice(dev_));
     const int64_t A = plan.ga.count, B = plan.gb.count;
+    const int nout = j.kind == WL_HUBER ? 2 : 1;
     if (A <= 0 || B <= 0) {
-      if (sumsq) zero(sumsq, sizeof(double));
+      if (j.out) zero(j.out, sizeof(double) * nout);
       return;
     }
-    if (K < 1 || K > WL_KMAX) throw std::runtime_error("ppals: model_wls needs 1 <= K <= 128");
-    if ((dt != F32 && dt != F64) || (vdt != DV_F32 && vdt != DV_F64))
-      throw std::runtime_error("ppals: model_wls stores F32 or F64 and reads F32 or F64 views");
+    const bool hist = j.kind == WL_HIST;
+    if (K < 1 || K > WL_KMAX) throw std::runtime_error(std::string("ppals: ") + name + " needs 1 <= K <= 128");
+    if ((!hist && j.dt != F32 && j.dt != F64) || (j.vdt != DV_F32 && j.vdt != DV_F64))
+      throw std::runtime_error(std::string("ppals: ") + name + " stores F32 or F64 and reads F32 or F64 views");
     const ModelPlan mp = dv_model_swapped(plan);  // the kernel's "view" is the shard, its "shard" the data
-    const int vw = dt == F32 ? 4 : 2;
-    const bool a_unit = mp.ga.view_unit();
-    bool vec_st = a_unit && A % vw == 0 && mp.voff % vw == 0 && ((uintptr_t)V) % 16 == 0;
-    for (int i = 0; i < mp.gb.n; i++)
+    // (a histogram pass stores nothing: its lanes take 16-byte runs of the views whenever A allows whole runs)
+    const int sdt = hist ? (j.vdt == DV_F32 ? F32 : F64) : j.dt;
+    const int vw = sdt == F32 ? 4 : 2;
+    const bool a_unit = hist || mp.ga.view_unit();
+    bool vec_st = a_unit && A % vw == 0 && (hist || (mp.voff % vw == 0 && ((uintptr_t)j.V) % 16 == 0));
+    for (int i = 0; i < mp.gb.n && !hist; i++)
       if (mp.gb.len[i] > 1 && mp.gb.vs[i] % vw != 0) vec_st = false;
     int flags = (a_unit ? WL_A_UNIT : 0) | (vec_st ? WL_VEC_ST : 0);
-    flags |= wls_side_flags(mp.ga, mp.gb, mp.ga.rs, mp.gb.rs, mp.roff, data, vw, vec_st, WL_X_ALONG_A, WL_X_UNIT,
+    flags |= wls_side_flags(mp.ga, mp.gb, mp.ga.rs, mp.gb.rs, mp.roff, j.data, vw, vec_st, WL_X_ALONG_A, WL_X_UNIT,
                             WL_X_VEC);
-    flags |= wls_side_flags(mp.ga, mp.gb, ws.ga.vs, ws.gb.vs, ws.off, weights, vw, vec_st, WL_H_ALONG_A, WL_H_UNIT,
-                            WL_H_VEC);
-    const bool one_b = !(flags & WL_X_ALONG_A) != !(flags & WL_H_ALONG_A);
-    const size_t lds = wl_lds_bytes(K, one_b ? (vdt == DV_F32 ? 4 : 8) : 0);
-    // the three offset tables of both groups, built on the engine stream (nothing of the caller's is read), and
+    if (j.ws)
+      flags |= wls_side_flags(mp.ga, mp.gb, j.ws->ga.vs, j.ws->gb.vs, j.ws->off, j.weights, vw, vec_st, WL_H_ALONG_A,
+                              WL_H_UNIT, WL_H_VEC);
+    const bool one_b = j.ws && !(flags & WL_X_ALONG_A) != !(flags & WL_H_ALONG_A);
+    const size_t lds = wl_lds_bytes(K, one_b ? (j.vdt == DV_F32 ? 4 : 8) : 0) +
+                       (hist ? sizeof(uint32_t) * WL_HIST_BINS : 0);
+    // the offset tables of both groups, built on the engine stream (nothing of the caller's is read), and
     // two rounds of the workgroups the LDS lets a CU hold, each walking its share of the b tiles
     const int64_t ntA = (A + MV_TILE - 1) / MV_TILE, ntB = (B + MV_TILE - 1) / MV_TILE;
     if (ntA > 0x7fffffff) throw std::runtime_error("ppals: model view too wide");
-    int64_t *tab = (int64_t *)ensure(ws_mv_, ws_mv_sz_, sizeof(int64_t) * 3 * (size_t)(A + B));
+    const int nt = j.ws ? 3 : 2;
+    int64_t *tab = (int64_t *)ensure(ws_mv_, ws_mv_sz_, sizeof(int64_t) * nt * (size_t)(A + B));
     hipLaunchKernelGGL(k_model_offsets, dim3(grid_for(A, 256)), dim3(256), 0, st_, mp.ga, tab, tab + A);
-    hipLaunchKernelGGL(k_model_offsets_side, dim3(grid_for(A, 256)), dim3(256), 0, st_, ws.ga, tab + 2 * A);
-    hipLaunchKernelGGL(k_model_offsets, dim3(grid_for(B, 256)), dim3(256), 0, st_, mp.gb, tab + 3 * A,
-                       tab + 3 * A + B);
-    hipLaunchKernelGGL(k_model_offsets_side, dim3(grid_for(B, 256)), dim3(256), 0, st_, ws.gb, tab + 3 * A + 2 * B);
+    if (j.ws) hipLaunchKernelGGL(k_model_offsets_side, dim3(grid_for(A, 256)), dim3(256), 0, st_, j.ws->ga, tab + 2 * A);
+    hipLaunchKernelGGL(k_model_offsets, dim3(grid_for(B, 256)), dim3(256), 0, st_, mp.gb, tab + nt * A,
+                       tab + nt * A + B);
+    if (j.ws)
+      hipLaunchKernelGGL(k_model_offsets_side, dim3(grid_for(B, 256)), dim3(256), 0, st_, j.ws->gb, tab + 3 * A + 2 * B);
     HIP_CHECK(hipGetLastError());
     const int64_t want = std::max<int64_t>(1, ((int64_t)ncu_ * 2 * wl_wgs_per_cu(lds) + ntA - 1) / ntA);
     const dim3 grid((unsigned)ntA, (unsigned)std::min<int64_t>(std::min<int64_t>(want, ntB), 65535));
     const int64_t npart = (int64_t)grid.x * grid.y;
-    if (npart > 0x7fffffff) throw std::runtime_error("ppals: model view too wide");
-    double *part = (double *)ensure(ws_part_, ws_part_sz_, sizeof(double) * npart);
-    route("model.wls.%s.%s K=%d flags=%d lds=%zu", dt == F32 ? "f32" : "f64", vdt == DV_F32 ? "f32" : "f64", K, flags,
-          lds);
+    if (npart * nout > 0x7fffffff) throw std::runtime_error("ppals: model view too wide");
+    double *part = hist ? nullptr : (double *)ensure(ws_part_, ws_part_sz_, sizeof(double) * npart * nout);
+    const char *vn = j.vdt == DV_F32 ? "f32" : "f64";
+    if (hist)
+      route("model.absres_hist.%s%s K=%d flags=%d lds=%zu shift=%d", vn, j.ws ? "" : ".now", K, flags, lds, j.shift);
+    else
+      route("model.%s.%s.%s%s K=%d flags=%d lds=%zu", j.kind == WL_WLS ? "wls" : "huber", j.dt == F32 ? "f32" : "f64", vn,
+            j.ws ? "" : ".now", K, flags, lds);
     if (!io_ev_in_) {
       HIP_CHECK(hipEventCreateWithFlags(&io_ev_in_, hipEventDisableTiming));
       HIP_CHECK(hipEventCreateWithFlags(&io_ev_out_, hipEventDisableTiming));
@@ -1205,21 +1263,46 @@ class HipOps : public Ops {
     hipStream_t cs = (hipStream_t)caller_stream;
     HIP_CHECK(hipEventRecord(io_ev_in_, cs));  // the views are ready once the caller's work so far is done
     HIP_CHECK(hipStreamWaitEvent(st_, io_ev_in_, 0));
-    if (dt == F32 && vdt == DV_F32)
-      wls_launch<float, float>(grid, lds, (float *)V, data, weights, Q, P, K, mp, ws.off, tab, flags, part);
-    else if (dt == F32)
-      wls_launch<float, double>(grid, lds, (float *)V, data, weights, Q, P, K, mp, ws.off, tab, flags, part);
-    else if (vdt == DV_F32)
-      wls_launch<double, float>(grid, lds, (double *)V, data, weights, Q, P, K, mp, ws.off, tab, flags, part);
+    if (sdt == F32 && j.vdt == DV_F32)
+      wl_launch<float, float>(j, grid, lds, Q, P, K, mp, tab, flags, part);
+    else if (sdt == F32)
+      wl_launch<float, double>(j, grid, lds, Q, P, K, mp, tab, flags, part);
+    else if (j.vdt == DV_F32)
+      wl_launch<double, float>(j, grid, lds, Q, P, K, mp, tab, flags, part);
     else
-      wls_launch<double, double>(grid, lds, (double *)V, data, weights, Q, P, K, mp, ws.off, tab, flags, part);
+      wl_launch<double, double>(j, grid, lds, Q, P, K, mp, tab, flags, part);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventRecord(io_ev_out_, st_));  // and the caller may change the views after the reads
     HIP_CHECK(hipStreamWaitEvent(cs, io_ev_out_, 0));
-    if (sumsq) {
-      hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(1024), 0, st_, part, (int)npart, sumsq);
+    for (int i = 0; j.out && i < nout; i++) {
+      hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(1024), 0, st_, part + i * npart, (int)npart, j.out + i);
       HIP_CHECK(hipGetLastError());
     }
+  }
+  void model_wls(const ModelPlan &plan, const ModelSide &ws, const double *Q, const double *P, int K,
+                 const void *data, const void *weights, int vdt, void *V, int dt, double *sumsq,
+                 void *caller_stream) override {
+    wl_run(WlJob{WL_WLS, &ws, data, weights, vdt, V, dt, 0.0, sumsq, 0, 0, 0, 0, nullptr}, "model_wls", plan, Q, P, K,
+           caller_stream);
+  }
+  void model_huber(const ModelPlan &plan, const ModelSide *ws, const double *Q, const double *P, int K,
+                   const void *data, const void *weights, int vdt, void *V, int dt, double c, double *loss_clipped,
+                   void *caller_stream) override {
+    wl_run(WlJob{WL_HUBER, ws, data, ws ? weights : nullptr, vdt, V, dt, c, loss_clipped, 0, 0, 0, 0, nullptr},
+           "model_huber", plan, Q, P, K, caller_stream);
+  }
+  void model_absres_hist(const ModelPlan &plan, const ModelSide *ws, const double *Q, const double *P, int K,
+                         const void *data, const void *weights, int vdt, int pshift, uint32_t prefix, int shift,
+                         uint32_t mask, uint64_t *hist /* host, WL_HIST_BINS */, void *caller_stream) override {
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "");
+    HIP_CHECK(hipSetDevice(dev_));
+    unsigned long long *gh =
+        (unsigned long long *)ensure(ws_hist_, ws_hist_sz_, sizeof(unsigned long long) * WL_HIST_BINS);
+    zero(gh, sizeof(unsigned long long) * WL_HIST_BINS);
+    wl_run(WlJob{WL_HIST, ws, data, ws ? weights : nullptr, vdt, nullptr, 0, 0.0, nullptr, pshift, shift, prefix, mask,
+                 gh},
+           "model_absres_hist", plan, Q, P, K, caller_stream);
+    d2h(hist, gh, sizeof(unsigned long long) * WL_HIST_BINS);
   }
 
   void *try_alloc(size_t bytes) override {
@@ -4477,6 +4560,8 @@ class HipOps : public Ops {
   void *ws_mttv_ = nullptr;  // partial sums of a j-split k_mttv_l
   void *ws_mv_ = nullptr;    // offset tables of model_to_view
   size_t ws_mv_sz_ = 0;
+  void *ws_hist_ = nullptr;  // the global histogram of model_absres_hist
+  size_t ws_hist_sz_ = 0;
   size_t ws_mttv_sz_ = 0;
   void *ws_pack_ = nullptr, *ws_slab_ = nullptr, *ws_krp_ = nullptr, *ws_part_ = nullptr,
        *ws_small_ = nullptr, *ws_big_ = nullptr, *ws_big2_ = nullptr;

@@ -47,6 +47,7 @@
 namespace ppals {
 
 constexpr int WL_KMAX = 128;
+constexpr int WL_HIST_BINS = 2048;  // (kernels_huber.hip.h: the quantile's histogram follows the images in LDS)
 constexpr size_t WL_LDS_FIXED = sizeof(double) * MV_TILE * (MV_TILE + 1) + sizeof(int64_t) * 6 * MV_TILE;
 inline size_t wl_lds_bytes(int K, size_t side_elem /* 0: no typed image */) {
   return sizeof(double) * MW_LDQ * (size_t)(4 * ((K + 3) / 4)) + WL_LDS_FIXED +
@@ -88,6 +89,26 @@ __device__ __forceinline__ double wl_rule(double x, double h, double m, double &
   return __fma_rn(h, d, m);
 }
 
+// What a kernel built on the tile loop (kernels_wls_tile.hip.h, the body of k_model_wls below) does with an
+// element (x, h, m): the compile-time policy KIND, and HAS_H = false for a family without a weights view
+// (h = 1 everywhere: no H pointer, no third offset table). WL_WLS is the rule above; the other two live in kernels_huber.hip.h. WlCtx is the state a rule
+// keeps per thread: a rule touches only its own members, the rest never exist in the compiled kernel.
+enum { WL_WLS = 0, WL_HUBER = 1, WL_HIST = 2 };
+struct WlCtx {
+  double acc = 0.0;    // this thread's share of the loss
+  double c = 0.0;      // WL_HUBER: the clipping threshold
+  double nclip = 0.0;  // WL_HUBER: this thread's count of clipped elements (exact: an integer in a double)
+  uint32_t *hist = nullptr;  // WL_HIST: the workgroup's histogram in LDS, and the pass (kernels_huber.hip.h)
+  uint32_t prefix = 0, mask = 0;
+  int pshift = 31, shift = 0;
+};
+template <int KIND>
+__device__ __forceinline__ double wl_apply(double x, double h, double m, WlCtx &cx);
+template <>
+__device__ __forceinline__ double wl_apply<WL_WLS>(double x, double h, double m, WlCtx &cx) {
+  return wl_rule(x, h, m, cx.acc);
+}
+
 template <typename TS, int VW>
 struct alignas((VW * sizeof(TS) > 16) ? 16 : VW * sizeof(TS)) wl_vec {
   TS v[VW];
@@ -120,12 +141,12 @@ __device__ __forceinline__ void wl_load(const WlSide<TS> &s, int64_t a0, int al,
 }
 
 // The store pass. VW = 1: lane index along a, rows wave, wave + 4, ...; VW > 1: 64 / VW lanes a row, 16-byte
-// stores. done: the image already holds z (both sides were read along b).
-template <typename D, typename TS, int VW>
+// stores. done: the image already holds z (both sides were read along b). WL_HIST stores nothing.
+template <typename D, typename TS, int VW, int KIND, bool HAS_H>
 __device__ __forceinline__ void wl_store(D *dst, const ModelPlan &mp, const double (*img)[MV_TILE + 1],
                                          const TS (*simg)[MV_TILE + 1], const int64_t *sav, const int64_t *sbv,
                                          const WlSide<TS> &X, const WlSide<TS> &H, int64_t a0, int na, int nb,
-                                         bool a_unit, bool done, double &acc) {
+                                         bool a_unit, bool done, WlCtx &cx) {
   constexpr int TPR = MV_TILE / VW, RPP = 256 / TPR, NR = MV_TILE / RPP, CH = NR < 8 ? NR : 8;
   const int al = ((int)threadIdx.x % TPR) * VW, br = (int)threadIdx.x / TPR;
 #pragma unroll
@@ -137,7 +158,7 @@ __device__ __forceinline__ void wl_store(D *dst, const ModelPlan &mp, const doub
         const int bl = br + RPP * (c + i);
         const bool ok = al < na && bl < nb;
         if (!X.in_lds) wl_load<TS, VW>(X, a0, al, bl, ok, xv[i]);
-        if (!H.in_lds) wl_load<TS, VW>(H, a0, al, bl, ok, hv[i]);
+        if (HAS_H && !H.in_lds) wl_load<TS, VW>(H, a0, al, bl, ok, hv[i]);
       }
     }
 #pragma unroll
@@ -150,11 +171,12 @@ __device__ __forceinline__ void wl_store(D *dst, const ModelPlan &mp, const doub
           double z = img[bl][al + e];
           if (!done) {
             const double x = X.in_lds ? (double)simg[bl][al + e] : (double)xv[i][e];
-            const double h = H.in_lds ? (double)simg[bl][al + e] : (double)hv[i][e];
-            z = wl_rule(x, h, z, acc);
+            const double h = !HAS_H ? 1.0 : H.in_lds ? (double)simg[bl][al + e] : (double)hv[i][e];
+            z = wl_apply<KIND>(x, h, z, cx);
           }
           o.v[e] = (D)z;
         }
+        if (KIND == WL_HIST) continue;
         if (VW > 1)
           *reinterpret_cast<mv_vec<D> *>(dst + (mp.voff + sbv[bl] + a0 + al)) = o;
         else
@@ -170,134 +192,10 @@ __global__ __launch_bounds__(256, 2) void k_model_wls(
     ModelPlan mp, int64_t woff, const int64_t *__restrict__ tav, const int64_t *__restrict__ tax,
     const int64_t *__restrict__ taw, const int64_t *__restrict__ tbv, const int64_t *__restrict__ tbx,
     const int64_t *__restrict__ tbw, int flags, double *__restrict__ part) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char wl_lds[];
-  const int RB = (K + 3) / 4;
-  double *qs = reinterpret_cast<double *>(wl_lds);  // [4 RB][MW_LDQ]
-  double(*img)[MV_TILE + 1] = reinterpret_cast<double(*)[MV_TILE + 1]>(qs + (size_t)4 * RB * MW_LDQ);
-  int64_t *sav = reinterpret_cast<int64_t *>(img + MV_TILE), *sax = sav + MV_TILE, *saw = sax + MV_TILE,
-          *sbv = saw + MV_TILE, *sbx = sbv + MV_TILE, *sbw = sbx + MV_TILE;
-  TS(*simg)[MV_TILE + 1] = reinterpret_cast<TS(*)[MV_TILE + 1]>(sbw + MV_TILE);  // (one side along b only)
-  double acc = 0.0;  // this thread's share of the loss
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int g = lane >> 4, j16 = lane & 15;
-  const int64_t A = mp.ga.count, B = mp.gb.count, a0 = (int64_t)blockIdx.x * MV_TILE;
-  const int na = (int)min((int64_t)MV_TILE, A - a0);
-  const bool a_unit = flags & WL_A_UNIT, vec_st = flags & WL_VEC_ST;
-  const bool x_b = !(flags & WL_X_ALONG_A), h_b = !(flags & WL_H_ALONG_A), both_b = x_b && h_b;
-  const int64_t nbt = (B + MV_TILE - 1) / MV_TILE;
-  const WlSide<TS> X{Xp, sax, sbx, mp.roff, x_b, (flags & WL_X_UNIT) != 0, (flags & WL_X_VEC) != 0};
-  const WlSide<TS> H{Hp, saw, sbw, woff, h_b, (flags & WL_H_UNIT) != 0, (flags & WL_H_VEC) != 0};
-
-  for (int e = threadIdx.x; e < 4 * RB * MV_TILE; e += 256) {  // the Q image: 4 rows of k per pass
-    const int k = e / MV_TILE, al = e % MV_TILE;
-    qs[k * MW_LDQ + al] = (al < na && k < K) ? Q[a0 + al + mp.ldq * (int64_t)k] : 0.0;
-  }
-  if (threadIdx.x < MV_TILE) {
-    const int i = threadIdx.x;
-    sav[i] = i < na ? tav[a0 + i] : 0;
-    sax[i] = i < na ? tax[a0 + i] : 0;
-    saw[i] = i < na ? taw[a0 + i] : 0;
-  }
-  // this lane's row b = 16 wave + j16 of tile tb_ in P (nullptr outside), and a chunk of it:
-  // p[rb] = P[b, 4 (c0 + rb) + g] (0 outside)
-  auto p_row = [&](int64_t tb_) -> const double * {
-    const int64_t b_ = tb_ * MV_TILE + 16 * wave + j16;
-    if (tb_ >= nbt || b_ >= B) return nullptr;
-    const int64_t q_ = b_ / mp.pL;
-    return P + ((b_ - q_ * mp.pL) + mp.pLK * q_);
-  };
-  auto p_chunk = [&](const double *row, int c0, double(&p)[MW_CH]) {
-#pragma unroll
-    for (int rb = 0; rb < MW_CH; rb++) {
-      const int k_ = 4 * (c0 + rb) + g;
-      p[rb] = (row && k_ < K) ? row[mp.pL * (int64_t)k_] : 0.0;
-    }
-  };
-  int64_t nbv = 0, nbx = 0, nbw = 0;
-  const int ib = (int)threadIdx.x - MV_TILE;  // threads 64..127: the b offsets, a tile ahead
-  auto load_b = [&](int64_t tb_) {
-    const int64_t bb = tb_ * MV_TILE + ib;
-    const bool ok = ib >= 0 && ib < MV_TILE && tb_ < nbt && bb < B;
-    nbv = ok ? tbv[bb] : 0;
-    nbx = ok ? tbx[bb] : 0;
-    nbw = ok ? tbw[bb] : 0;
-  };
-  const double *prow = p_row(blockIdx.y);
-  double pn[MW_CH];
-  p_chunk(prow, 0, pn);
-  load_b(blockIdx.y);
-  __syncthreads();  // the Q image is complete
-
-  for (int64_t tb = blockIdx.y; tb < nbt; tb += gridDim.y) {
-    const int nb = (int)min((int64_t)MV_TILE, B - tb * MV_TILE);
-    if (ib >= 0 && ib < MV_TILE) {
-      sbv[ib] = nbv;
-      sbx[ib] = nbx;
-      sbw[ib] = nbw;
-    }
-    load_b(tb + gridDim.y);
-    const double *pnext = p_row(tb + gridDim.y);
-    mv_f64x4 d[4];
-#pragma unroll
-    for (int t = 0; t < 4; t++) d[t] = mv_f64x4{0.0, 0.0, 0.0, 0.0};
-    for (int c0 = 0; c0 < RB; c0 += MW_CH) {
-      double pa[MW_CH];
-#pragma unroll
-      for (int rb = 0; rb < MW_CH; rb++) pa[rb] = pn[rb];
-      if (c0 + MW_CH < RB)
-        p_chunk(prow, c0 + MW_CH, pn);
-      else
-        p_chunk(pnext, 0, pn);
-#pragma unroll
-      for (int rb = 0; rb < MW_CH; rb++) {
-        if (c0 + rb < RB) {
-          const double *qk = qs + (4 * (c0 + rb) + g) * MW_LDQ + j16;
-#pragma unroll
-          for (int t = 0; t < 4; t++)
-            d[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[rb], qk[16 * t], d[t], 0, 0, 0);
-        }
-      }
-    }
-    prow = pnext;
-#pragma unroll
-    for (int t = 0; t < 4; t++)
-#pragma unroll
-      for (int r = 0; r < 4; r++) img[16 * wave + g + 4 * r][16 * t + j16] = d[t][r];
-    __syncthreads();
-    if (x_b || h_b) {  // the side views whose unit-stride run lies along b: lane index along b
-      constexpr int NH = MV_TILE / 8;
-      const int bl = lane;
-      const int64_t x0 = X.off + sax[0] + sbx[0], h0 = H.off + saw[0] + sbw[0];
-#pragma unroll
-      for (int hf = 0; hf < 2; hf++) {
-        TS xv[NH], hv[NH];
-#pragma unroll
-        for (int i = 0; i < NH; i++) {
-          const int al = wave + 4 * (NH * hf + i);
-          const bool ok = al < na && bl < nb;
-          if (x_b) xv[i] = Xp[ok ? X.off + sax[al] + sbx[bl] : x0];
-          if (h_b) hv[i] = Hp[ok ? H.off + saw[al] + sbw[bl] : h0];
-        }
-#pragma unroll
-        for (int i = 0; i < NH; i++) {
-          const int al = wave + 4 * (NH * hf + i);
-          if (both_b) {
-            if (al < na && bl < nb) img[bl][al] = wl_rule((double)xv[i], (double)hv[i], img[bl][al], acc);
-          } else {
-            simg[bl][al] = x_b ? xv[i] : hv[i];
-          }
-        }
-      }
-      __syncthreads();
-    }
-    if (vec_st)
-      wl_store<D, TS, 16 / sizeof(D)>(dst, mp, img, simg, sav, sbv, X, H, a0, na, nb, a_unit, both_b, acc);
-    else
-      wl_store<D, TS, 1>(dst, mp, img, simg, sav, sbv, X, H, a0, na, nb, a_unit, both_b, acc);
-    __syncthreads();  // the images and the b offsets are rewritten by the next tile
-  }
-  acc = block_sum(acc, &img[0][0]);
-  if (threadIdx.x == 0) part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = acc;
+  constexpr int KIND = WL_WLS;
+  constexpr bool HAS_H = true;
+  WlCtx cx;
+#include "kernels_wls_tile.hip.h"
 }
 
 }  // namespace ppals

@@ -262,6 +262,29 @@ class Ops {
     throw Unsupported("ppals: this back end has no device views");
   }
 
+  // The Huber step (ppals_cp_huber_device): model_wls with a clipping threshold c > 0 (+inf: model_wls's
+  // bits and loss). Where h > 0 and |x - sum| > c the value stored is sum +- c (h >= 1) or
+  // fma(h, +-c, sum), the loss contribution min(h, 1) c (2 |x - sum| - c), and the element counts as clipped.
+  // ws == nullptr: no weights view, h = 1 everywhere (`weights` is not read). loss_clipped (device, two
+  // doubles, may be nullptr): the loss and the clipped count, both in a fixed order.
+  virtual void model_huber(const ModelPlan & /*mp*/, const ModelSide * /*ws*/, const double * /*Q*/,
+                           const double * /*P*/, int /*K*/, const void * /*data*/, const void * /*weights*/,
+                           int /*vdt*/, void * /*V*/, int /*dt*/, double /*c*/, double * /*loss_clipped*/,
+                           void * /*caller_stream*/) {
+    throw Unsupported("ppals: this back end has no device views");
+  }
+  // One pass of the radix select of ppals_cp_abs_residual_quantile: over the elements of the plan's box with
+  // h > 0 (all with ws == nullptr), key = the fp32 pattern of (float)|x - sum| (every NaN: 0x7fc00000);
+  // hist[(key >> shift) & mask] counts the keys with key >> pshift == prefix. `hist`: ABSRES_BINS counts on
+  // the HOST; the call waits for them. Integer counts: the same for every grid. Reads no tensor.
+  static constexpr int ABSRES_BINS = 2048;
+  virtual void model_absres_hist(const ModelPlan & /*mp*/, const ModelSide * /*ws*/, const double * /*Q*/,
+                                 const double * /*P*/, int /*K*/, const void * /*data*/, const void * /*weights*/,
+                                 int /*vdt*/, int /*pshift*/, uint32_t /*prefix*/, int /*shift*/, uint32_t /*mask*/,
+                                 uint64_t * /*hist*/, void * /*caller_stream*/) {
+    throw Unsupported("ppals: this back end has no device views");
+  }
+
   // Order work on the engine stream against a caller's stream, as copy_view does it: join_stream makes the
   // work queued on the engine stream from now on wait for what `caller_stream` holds so far, release_stream
   // makes what the caller queues there later wait for the engine stream's work so far. The host does not block.

@@ -871,23 +871,26 @@ int ppals_cp_em(ppals_cp *s, const void *mask, const int64_t *box_lo, const int6
 
 // the two views of a weighted step: every check ppals_tensor_check_device_view makes of an import source,
 // the arithmetic of both views (and what the session itself refuses) ahead of the pointer queries
+// (weights_optional: the Huber step and the residual quantile take weights == NULL for h = 1 everywhere, and
+// `w` is then left alone; `refusal`: what the session refuses for this entry point, or nullptr)
 static int check_wls_views(ppals_cp *s, const char *fn, const void *data, const void *weights, int dtype,
                            const int64_t *box_lo, const int64_t *box_len, const int64_t *data_strides,
-                           const int64_t *weight_strides, ViewArgs *a, ViewArgs *w) {
+                           const int64_t *weight_strides, ViewArgs *a, ViewArgs *w, bool weights_optional = false,
+                           const char *refusal = nullptr, bool own_refusal = false) {
   if (!data) return fail_fn(PPALS_ERR_ARG, fn, "the data pointer is NULL");
-  if (!weights) return fail_fn(PPALS_ERR_ARG, fn, "the weights pointer is NULL");
+  if (!weights && !weights_optional) return fail_fn(PPALS_ERR_ARG, fn, "the weights pointer is NULL");
   if (dtype != PPALS_F32 && dtype != PPALS_F64)
     return fail_fn(PPALS_ERR_ARG, fn, "bad dtype of the data and weights views (PPALS_F32 or PPALS_F64)");
   const TensorDesc &d = s->eng->tensor();
   std::string err;
   if (!dv_check_args(DV_IMPORT, d.order, d.glens, dtype, box_lo, box_len, data_strides, a, &err))
     return fail_fn(PPALS_ERR_ARG, fn, ("the data view: " + err).c_str());
-  if (!dv_check_args(DV_IMPORT, d.order, d.glens, dtype, box_lo, box_len, weight_strides, w, &err))
+  if (weights && !dv_check_args(DV_IMPORT, d.order, d.glens, dtype, box_lo, box_len, weight_strides, w, &err))
     return fail_fn(PPALS_ERR_ARG, fn, ("the weights view: " + err).c_str());
-  if (const char *why = s->eng->wls_refusal()) return fail_fn(PPALS_ERR_UNSUPPORTED, fn, why);
+  if (const char *why = own_refusal ? refusal : s->eng->wls_refusal()) return fail_fn(PPALS_ERR_UNSUPPORTED, fn, why);
   const std::string pre = std::string(fn) + ": ";
   if (const int rc = check_view_ptr(s->ctx, (pre + "the data view: ").c_str(), data, a)) return rc;
-  return check_view_ptr(s->ctx, (pre + "the weights view: ").c_str(), weights, w);
+  return weights ? check_view_ptr(s->ctx, (pre + "the weights view: ").c_str(), weights, w) : PPALS_OK;
 }
 int ppals_cp_wls_device(ppals_cp *s, const void *data, const void *weights, int dtype, const int64_t *box_lo,
                         const int64_t *box_len, const int64_t *data_strides, const int64_t *weight_strides,
@@ -916,6 +919,57 @@ int ppals_cp_wls(ppals_cp *s, const void *data, const void *weights, int dtype, 
                                  weight_strides, &a, &w);
   if (rc != PPALS_OK) return rc;
   return s->eng->run_wls(a, data, w, weights, stream, to_opts(o), inner_sweeps, rel_change, iters, weighted_res);
+  API_END(PPALS_ERR_HIP)
+}
+
+// ------------------------------------------------------------------ robust CP (Huber)
+int ppals_cp_huber_device(ppals_cp *s, const void *data, const void *weights, int dtype, const int64_t *box_lo,
+                          const int64_t *box_len, const int64_t *data_strides, const int64_t *weight_strides,
+                          double c, void *stream, double *huber_loss, int64_t *clipped) {
+  if (!s || !s->eng || !s->ctx) return fail(PPALS_ERR_ARG, "NULL session");
+  API_BEGIN
+  if (!(c > 0)) return fail(PPALS_ERR_ARG, "ppals_cp_huber_device: c must be positive (+inf: no clipping)");
+  ViewArgs a, w;
+  const int rc = check_wls_views(s, "ppals_cp_huber_device", data, weights, dtype, box_lo, box_len, data_strides,
+                                 weight_strides, &a, &w, true);
+  if (rc != PPALS_OK) return rc;
+  s->eng->huber_step(a, data, weights ? &w : nullptr, weights, stream, c, huber_loss, clipped);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_cp_robust(ppals_cp *s, const void *data, const void *weights, int dtype, const int64_t *box_lo,
+                    const int64_t *box_len, const int64_t *data_strides, const int64_t *weight_strides, void *stream,
+                    double c, const ppals_cp_opts *o, int inner_sweeps, double rel_change, int *iters,
+                    double *robust_res) {
+  API_BEGIN
+  if (!o) return fail(PPALS_ERR_ARG, "ppals_cp_robust: NULL options");
+  if (inner_sweeps < 1) return fail(PPALS_ERR_ARG, "ppals_cp_robust: inner_sweeps must be at least 1");
+  if (!(rel_change >= 0)) return fail(PPALS_ERR_ARG, "ppals_cp_robust: rel_change must not be negative");
+  if (o->maxiter < 0) return fail(PPALS_ERR_ARG, "ppals_cp_robust: maxiter must not be negative");
+  if (!(c > 0)) return fail(PPALS_ERR_ARG, "ppals_cp_robust: c must be positive (+inf: no clipping)");
+  if (!s || !s->eng || !s->ctx) return fail(PPALS_ERR_ARG, "NULL session");
+  ViewArgs a, w;
+  const int rc = check_wls_views(s, "ppals_cp_robust", data, weights, dtype, box_lo, box_len, data_strides,
+                                 weight_strides, &a, &w, true);
+  if (rc != PPALS_OK) return rc;
+  return s->eng->run_robust(a, data, weights ? &w : nullptr, weights, stream, c, to_opts(o), inner_sweeps, rel_change,
+                            iters, robust_res);
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_cp_abs_residual_quantile(ppals_cp *s, const void *data, const void *weights, int dtype,
+                                   const int64_t *box_lo, const int64_t *box_len, const int64_t *data_strides,
+                                   const int64_t *weight_strides, void *stream, double p, double *value,
+                                   int64_t *count) {
+  if (!s || !s->eng || !s->ctx) return fail(PPALS_ERR_ARG, "NULL session");
+  API_BEGIN
+  if (!(p >= 0 && p <= 1)) return fail(PPALS_ERR_ARG, "ppals_cp_abs_residual_quantile: p must lie in [0, 1]");
+  if (!value) return fail(PPALS_ERR_ARG, "ppals_cp_abs_residual_quantile: NULL value");
+  ViewArgs a, w;
+  const int rc = check_wls_views(s, "ppals_cp_abs_residual_quantile", data, weights, dtype, box_lo, box_len,
+                                 data_strides, weight_strides, &a, &w, true, s->eng->quantile_refusal(), true);
+  if (rc != PPALS_OK) return rc;
+  s->eng->abs_residual_quantile(a, data, weights ? &w : nullptr, weights, stream, p, value, count);
+  return PPALS_OK;
   API_END(PPALS_ERR_HIP)
 }
 

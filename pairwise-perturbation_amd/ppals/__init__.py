@@ -62,6 +62,7 @@ EXPORTS = [
     "ppals_cp_multi_get_factors", "ppals_cp_multi_set_schedule", "ppals_cp_multi_sweeps",
     "ppals_cp_multi_residuals", "ppals_cp_multi_gradnorms", "ppals_cp_multi_run",
     "ppals_cp_multi_take", "ppals_cp_impute_device", "ppals_cp_em", "ppals_cp_wls_device", "ppals_cp_wls",
+    "ppals_cp_huber_device", "ppals_cp_robust", "ppals_cp_abs_residual_quantile",
     "ppals_cp_set_nonneg", "ppals_cp_get_nonneg",
     "ppals_cp_multi_set_nonneg", "ppals_cp_multi_get_nonneg",
     "ppals_cp_multi_create_ranks", "ppals_cp_multi_ranks",
@@ -718,7 +719,87 @@ class _Wls:
         return rc, it.value, res.value
 
 
-class CP(_ModelExport, _Impute, _Wls):
+class _Robust:
+    """robust CP (ppals_cp_huber_device / ppals_cp_robust / ppals_cp_abs_residual_quantile): Huber's loss by
+    majorization, and the residual quantile its threshold is chosen from"""
+
+    def _robust_views(self, data, weights):
+        """(data ptr, weights ptr or None, dtype code, shape, data strides, weights strides) of torch tensors"""
+        torch = _torch()
+        if weights is not None:
+            return self._torch_wls(data, weights)
+        if data.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"the torch dtype {data.dtype} of data is not torch.float32 or torch.float64")
+        dptr, code, shape, dstr = self.V._torch_view(data, (torch.float32, torch.float64))
+        return dptr, None, code, shape, dstr, dstr
+
+    def huber_device(self, data_ptr, weights_ptr, dtype, shape, data_strides, weight_strides, c, lo=None, stream=0,
+                     want_loss=False):
+        """raw ppals_cp_huber_device: wls_device with the residual clipped to [-c, c] (c > 0; inf: wls_device's
+        bits); weights_ptr None or 0: weight 1 everywhere (weight_strides is then ignored). Returns
+        (Huber loss, number of clipped elements) if want_loss (the call then waits), else None."""
+        blo, blen, ds, ws = self._wls_views(shape, data_strides, weight_strides or data_strides, lo)
+        loss, clipped = C.c_double(0), C.c_int64(0)
+        _check(lib().ppals_cp_huber_device(self._h, C.c_void_p(int(data_ptr)),
+                                           C.c_void_p(int(weights_ptr)) if weights_ptr else None, int(dtype), blo, blen,
+                                           ds, ws, C.c_double(float(c)), C.c_void_p(int(stream or 0)),
+                                           C.byref(loss) if want_loss else None,
+                                           C.byref(clipped) if want_loss else None))
+        return (float(loss.value), int(clipped.value)) if want_loss else None
+
+    def huber_torch(self, data, c, weights=None, lo=None, stream=None, want_loss=False):
+        """huber_device with torch tensors on the context's device (f32 or f64, the same dtype, any strides;
+        `weights` is expanded when it broadcasts, None: weight 1 everywhere, which reads one view less). Every
+        element of the box at lo becomes m + h clip(x - m, -c, c), m the current model. Returns None, or
+        (loss, clipped) when want_loss is set."""
+        dptr, wptr, code, shape, dstr, wstr = self._robust_views(data, weights)
+        return self.huber_device(dptr, wptr, code, shape, dstr, wstr, c, lo, Tensor._stream(stream), want_loss)
+
+    def abs_residual_quantile_torch(self, data, p=0.5, weights=None, lo=None, stream=None):
+        """ppals_cp_abs_residual_quantile: (value, count), count the elements of the box with weight > 0 (all
+        without weights) and value the k-th smallest (float)|x - m| among them, k = min(count - 1,
+        max(0, ceil(p count) - 1)), NaN last; (nan, 0) if there are none. Exact; reads no tensor (any storage)."""
+        dptr, wptr, code, shape, dstr, wstr = self._robust_views(data, weights)
+        blo, blen, ds, ws = self._wls_views(shape, dstr, wstr, lo)
+        val, cnt = C.c_double(0), C.c_int64(0)
+        _check(lib().ppals_cp_abs_residual_quantile(self._h, C.c_void_p(int(dptr)),
+                                                    C.c_void_p(int(wptr)) if wptr else None, int(code), blo, blen,
+                                                    ds, ws, C.c_void_p(int(Tensor._stream(stream) or 0)),
+                                                    C.c_double(float(p)), C.byref(val), C.byref(cnt)))
+        return float(val.value), int(cnt.value)
+
+    def robust_scale(self, data, weights=None, lo=None, stream=None):
+        """1.4826 x the median of |x - m|: the MAD scale of the current residuals (a consistent estimate of the
+        noise's standard deviation under Gaussian noise, whatever a minority of outliers does)"""
+        return 1.4826 * self.abs_residual_quantile_torch(data, 0.5, weights, lo, stream)[0]
+
+    def run_robust(self, data, c=None, weights=None, tune=1.345, inner_sweeps=1, rel_change=0.0, lo=None,
+                   stream=None, **opts):
+        """ppals_cp_robust: repeat { Huber step at the fixed threshold c; inner_sweeps exact sweeps } with the
+        looks and stop rules of run_wls. c=None: tune x robust_scale(...), taken ONCE from the factors the
+        session holds (1.345: 95 % efficiency under Gaussian noise). Returns (rc, iterations, sqrt(Huber loss), c).
+
+        The intended staging, from a random start: the scale of a poor fit is large, so estimate it twice,
+
+            cp.sweeps_dt(20)                                   # some plain sweeps
+            rc, it, res, c1 = cp.run_robust(x, maxiter=100)    # c from the plain fit's residuals
+            rc, it, res, c2 = cp.run_robust(x, maxiter=100)    # c again, from the robust fit: the noise's scale
+
+        (c is never re-estimated inside a call: the loss of a call falls monotonically only at a fixed c.)"""
+        if c is None:
+            c = float(tune) * self.robust_scale(data, weights, lo, stream)
+        dptr, wptr, code, shape, dstr, wstr = self._robust_views(data, weights)
+        blo, blen, ds, ws = self._wls_views(shape, dstr, wstr, lo)
+        o = _opts(**opts)
+        it, res = C.c_int(0), C.c_double(0)
+        rc = _check(lib().ppals_cp_robust(self._h, C.c_void_p(int(dptr)), C.c_void_p(int(wptr)) if wptr else None,
+                                          int(code), blo, blen, ds, ws, C.c_void_p(int(Tensor._stream(stream) or 0)),
+                                          C.c_double(float(c)), C.byref(o), int(inner_sweeps),
+                                          C.c_double(float(rel_change)), C.byref(it), C.byref(res)))
+        return rc, it.value, res.value, float(c)
+
+
+class CP(_ModelExport, _Impute, _Wls, _Robust):
     """a CP-ALS session: factors, Grams and dimension-tree caches resident in HBM"""
     _export_fn = "ppals_cp_export_model_device"
     _impute_fn, _em_fn = "ppals_cp_impute_device", "ppals_cp_em"
