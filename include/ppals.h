@@ -42,6 +42,7 @@ typedef struct ppals_tensor ppals_tensor; /* the (local shard of the) dense inpu
 typedef struct ppals_cp ppals_cp;         /* a CP-ALS session: factors, Grams, tree caches in HBM */
 typedef struct ppals_cp_multi ppals_cp_multi; /* several CP-ALS starts sharing the tensor scans */
 typedef struct ppals_tucker ppals_tucker; /* a Tucker-HOOI session */
+typedef struct ppals_parafac2 ppals_parafac2; /* a PARAFAC2 fit: projections, compressed tensor, inner CP session */
 
 const char *ppals_last_error(void);
 const char *ppals_version(void);
@@ -828,6 +829,70 @@ int ppals_cp_abs_residual_quantile(ppals_cp *s, const void *data, const void *we
                                    const int64_t *box_lo, const int64_t *box_len, const int64_t *data_strides,
                                    const int64_t *weight_strides, void *stream, double p,
                                    double *value, int64_t *count);
+
+/* ---- PARAFAC2 (Harshman 1972; Kiers, ten Berge & Bro 1999): direct fitting ----
+ * A CP model whose profiles in mode 0 may differ from slice to slice as long as their cross product stays the
+ * same: chromatography with retention-time shifts, batch processes, EEG with varying latencies. The data is a
+ * device view X of extents I x J x K, mode 0 the shifting mode, mode 2 the slices, X_k = X[:, :, k]:
+ *     X_k ~ P_k B D_k A^T,   P_k (I x R) with orthonormal columns, B (R x R), A (J x R), D_k = diag(C[k, :]).
+ * With the compressed tensor Y (R x J x K), Y_k = P_k^T X_k, [[B, A, C]] is a rank-R CP model of Y and
+ *     ||X - model||^2 = (||X||^2 - ||Y||^2) + ||Y - [[B, A, C]]||^2 = lost_sq + (the inner session's residual)^2.
+ * The object owns Y (stored as `storage_dtype`, PPALS_F32 or PPALS_F64), an ordinary ppals_cp session of rank R
+ * on it (mode 0 = B, mode 1 = A, mode 2 = C), the projections P and the step's scratch (2 I R K doubles).
+ *
+ * ppals_parafac2_create: refused before anything is allocated — PPALS_ERR_ARG for R < 2, R > 64 (the Jacobi of
+ * the slice polar factors keeps its R x R system in LDS), R > min(I, J), extents < 1, a bad dtype;
+ * PPALS_ERR_UNSUPPORTED for PPALS_BF16 storage, a context of more than one rank (Y's leading mode is R and cannot
+ * be sharded usefully) and a back end without device views. Initial state: B = I_R, C = 1,
+ * A = ppals_fill_uniform_host(J R values, seed 1, offset 0) in [0, 1), every P_k the first R identity columns,
+ * Y zero.
+ * ppals_parafac2_cp: the inner session, BORROWED: use it for ppals_cp_set_factors / get_factors (the blocks
+ * B, A, C in this order), set_mode_constraints, set_mode_shapes, set_schedule, sweeps, residual, leverages,
+ * core consistency and ppals_cp_fms. NEVER pass it to ppals_cp_destroy: ppals_parafac2_destroy destroys it, the
+ * tensor and the buffers. Mode 0 (B) must stay PPALS_MODE_FREE: the step and the driver refuse with
+ * PPALS_ERR_ARG otherwise. */
+int ppals_parafac2_create(ppals_ctx *ctx, int64_t I, int64_t J, int64_t K, int R, int storage_dtype,
+                          ppals_parafac2 **out);
+void ppals_parafac2_destroy(ppals_parafac2 *p);
+ppals_cp *ppals_parafac2_cp(ppals_parafac2 *p);
+/* The compressed tensor Y (R x J x K, r fastest), BORROWED like the session: for ppals_tensor_download,
+ * ppals_tensor_export_device and ppals_tensor_norm. Never destroy it, and do not write to it: the step owns its
+ * contents. */
+ppals_tensor *ppals_parafac2_tensor(ppals_parafac2 *p);
+/* One projection step from the inner session's current B, A, C. For every slice k:
+ *   Q_k = X_k A D_k B^T                         first pass over X, elements widened to fp64
+ *   P_k = Q_k (Q_k^T Q_k)^(-1/2)                the Gram route in fp64 under the rule of the orthonormal mode
+ *       update: a converged Jacobi, every eigenvalue theta positive and finite and
+ *       theta_min > theta_max * PPALS_ORTHO_MIN_RATIO; a slice that fails it KEEPS ITS PREVIOUS P_k and counts
+ *       in *failed (an all-zero slice is such a slice: ordinary input, not an error)
+ *   Y_k = P_k^T X_k                             second pass over X, rounded once to the storage type and written
+ *       into the resident tensor; the tensor's generation is bumped, the session's factors do not change.
+ * `data`: device memory of the context's device, `dtype` PPALS_F32 or PPALS_F64, `strides` in elements for the
+ * modes (0, 1, 2), NULL = dense with the first index fastest. The pointer (not NULL, aligned to its element
+ * size, device memory) and the range (the view's span inside its allocation) are checked as
+ * ppals_tensor_check_device_view checks an import source: PPALS_ERR_ARG. strides[0] != 1 or slices that
+ * overlap (a zero stride, aliased elements): PPALS_ERR_UNSUPPORTED — permute so that the shifting mode comes
+ * first and make the tensor contiguous. Padded slices (strides[1] > I, strides[2] > strides[1] J) are fine.
+ * Every refusal comes before any launch and leaves tensor, session and projections unchanged.
+ * The reads of X wait for the work `stream` holds so far, and work queued on `stream` later waits for them.
+ *   lost_sq == NULL and failed == NULL: the host does not block. Otherwise *lost_sq = sum x^2 - sum y^2, both
+ *   sums in fp64 before the rounding of Y and in a fixed order (the same state gives the same bits), *failed =
+ *   the number of slices that kept their P_k, and the call returns when they are on the host.
+ * The number of launches does not depend on I, J, K, R. */
+int ppals_parafac2_step_device(ppals_parafac2 *p, const void *data, int dtype, const int64_t *strides /* or NULL */,
+                               void *stream, double *lost_sq /* may be NULL */, int *failed /* may be NULL */);
+/* Direct fitting: iteration k is a step followed by inner_sweeps exact sweeps of the inner session at o->lambda,
+ * with the looks, stop rules, return codes (1: tol, 2: rel_change), the last step on the way out and *iters of
+ * ppals_cp_wls. The quantity looked at is lost_sq + residual^2, the residual the inner session's taken after the
+ * step (one pass over the small Y); *res is its square root, ||X - model||. A sweep lowers the second term and
+ * leaves the first, a step minimises the total over the P_k: the loss never rises. Argument errors: those of
+ * ppals_cp_wls (NULL o, inner_sweeps < 1, rel_change < 0 or NaN, o->maxiter < 0) and of the step. */
+int ppals_parafac2_run(ppals_parafac2 *p, const void *data, int dtype, const int64_t *strides, void *stream,
+                       const ppals_cp_opts *o, int inner_sweeps, double rel_change, int *iters, double *res);
+/* The projections: P_host receives I R K doubles, P_k column-major at I R k; the device pointer (same layout)
+ * stays the object's and is valid until ppals_parafac2_destroy; it is written by work on the engine stream. */
+int ppals_parafac2_projections(ppals_parafac2 *p, double *P_host);
+int ppals_parafac2_projections_device(ppals_parafac2 *p, const double **P);
 
 /* ---- Tucker with missing entries (TensorLy's tucker(mask=...)): imputation and an EM driver ----
  * The contracts of ppals_cp_impute_device / ppals_cp_em with a Tucker session in the CP session's place:

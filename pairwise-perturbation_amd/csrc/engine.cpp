@@ -2665,6 +2665,12 @@ int CpEngine::run_robust(const ViewArgs &a, const void *data, const ViewArgs *w,
                  rel_change, iters, robust_res);
 }
 
+int CpEngine::run_steps(const std::function<void(double *)> &step, const CpOpts &o, int inner_sweeps,
+                        double rel_change, int *iters, double *res) {
+  if (multi_) throw std::logic_error("ppals: a multi-start session drives no step loop (take the winner first)");
+  return em_loop(step, o, inner_sweeps, rel_change, iters, res);
+}
+
 const char *CpEngine::quantile_refusal() const {
   if (R_ > 128) return "R > 128 is not supported: the factor tile is kept in LDS";
   if (P_ > 1) return "the residual quantile runs on one rank";

@@ -4,6 +4,7 @@
 #pragma once
 #include <cstdint>
 #include <cstdlib>
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -255,6 +256,12 @@ class CpEngine {
   const char *quantile_refusal() const;  // R > 128, more than one rank; or nullptr
   void abs_residual_quantile(const ViewArgs &a, const void *data, const ViewArgs *w, const void *weights,
                              void *stream, double p, double *value, int64_t *count);
+  // PARAFAC2 (ppals_parafac2_*): the owner's projection step reads this session's factors on the device
+  // (mode i: glens[i] x R, column-major) and drives { step; sweeps } through the loop of run_wls, `step`
+  // in the weighted step's place (it hands back the quantity looked at when its argument is not nullptr).
+  const double *factor_device(int i) const { return W_[i]; }
+  int run_steps(const std::function<void(double *)> &step, const CpOpts &o, int inner_sweeps, double rel_change,
+                int *iters, double *res);
   const TensorDesc &tensor() const { return V_; }
   // The core consistency diagnostic (Bro & Kiers 2003; include/ppals.h): per start b, with
   // P_i = W_i (W_i^T W_i)^-1 of its current factors, the core G_b = V x_0 P_0^T ... x_{N-1} P_{N-1}^T

@@ -31,6 +31,7 @@
 #include "kernels_model.hip.h"
 #include "kernels_wls.hip.h"
 #include "kernels_huber.hip.h"
+#include "kernels_parafac2.hip.h"
 #include "kernels_bf16.hip.h"
 #include "kernels_prep.hip.h"
 
@@ -216,6 +217,10 @@ class HipOps : public Ops {
                                   96 * 1024));  // (67.5 KB at R = 64)
     HIP_CHECK(hipFuncSetAttribute((const void *)k_shape_columns, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)kShapeLdsBytes));
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_p2_polar, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+    const void *p2_wide[] = {(const void *)k_p2_project<float, 4>, (const void *)k_p2_project<double, 4>};
+    for (const void *k : p2_wide)  // (R > 48: 72 KB at R = 64; every other instantiation stays below 64 KB)
+      HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p2_project_lds(64)));
   }
   ~HipOps() override {
     hipSetDevice(dev_);
@@ -1303,6 +1308,63 @@ class HipOps : public Ops {
                  gh},
            "model_absres_hist", plan, Q, P, K, caller_stream);
     d2h(hist, gh, sizeof(unsigned long long) * WL_HIST_BINS);
+  }
+
+  // ------------------------------------------------------------------ PARAFAC2 (kernels_parafac2.hip.h)
+  void parafac2_check() override {}
+  void parafac2_init(double *P, int64_t I, int R, int64_t K) override {
+    HIP_CHECK(hipSetDevice(dev_));
+    hipLaunchKernelGGL(k_p2_init, dim3(grid_for(I * R * K, 256)), dim3(256), 0, st_, P, I, R, K);
+    HIP_CHECK(hipGetLastError());
+  }
+  template <typename TX, int NT>
+  void p2_launch(const Parafac2Step &s, int ti, int tj, double *part) {
+    const TX *X = (const TX *)s.X;
+    hipLaunchKernelGGL((k_p2_project<TX, NT>), dim3((unsigned)(ti * s.K)), dim3(256), p2_project_lds(s.R), st_, X, s.s1,
+                       s.s2, s.I, s.J, s.R, s.A, s.B, s.C, s.K, ti, s.Q);
+    const size_t lds_polar = sizeof(double) * (2 * (size_t)s.R * (s.R + 1) + 64 + 18) + sizeof(int) * 64;
+    hipLaunchKernelGGL(k_p2_polar, dim3((unsigned)s.K), dim3(1024), lds_polar, st_, s.Q, s.I, s.R, s.min_ratio, s.T,
+                       s.status);
+    hipLaunchKernelGGL(k_p2_apply, dim3((unsigned)(ti * s.K)), dim3(256),
+                       sizeof(double) * ((size_t)s.R * s.R + 64 * (size_t)s.R), st_, s.Q, s.T, s.status, s.I, s.R, ti,
+                       s.P);
+    if (s.dt == F32)
+      hipLaunchKernelGGL((k_p2_compress<TX, float, NT>), dim3((unsigned)(tj * s.K)), dim3(256), p2_compress_lds(s.R),
+                         st_, X, s.s1, s.s2, s.I, s.J, s.R, s.P, tj, (float *)s.Y, part);
+    else
+      hipLaunchKernelGGL((k_p2_compress<TX, double, NT>), dim3((unsigned)(tj * s.K)), dim3(256), p2_compress_lds(s.R),
+                         st_, X, s.s1, s.s2, s.I, s.J, s.R, s.P, tj, (double *)s.Y, part);
+  }
+  // seven launches whatever the extents: project, polar, apply, compress, the two sums and the failed count
+  // (the last three only when `out` is asked for)
+  void parafac2_step(const Parafac2Step &s, void *caller_stream) override {
+    HIP_CHECK(hipSetDevice(dev_));
+    if (s.R < 2 || s.R > 64 || s.I < s.R || s.J < s.R || s.K < 1)
+      throw std::runtime_error("ppals: parafac2_step needs 2 <= R <= min(64, I, J) and K >= 1");
+    if ((s.dt != F32 && s.dt != F64) || (s.vdt != DV_F32 && s.vdt != DV_F64))
+      throw std::runtime_error("ppals: parafac2_step stores F32 or F64 and reads an F32 or F64 view");
+    const int64_t ti = (s.I + P2_TILE - 1) / P2_TILE, tj = (s.J + P2_TILE - 1) / P2_TILE;
+    if (ti * s.K > 0x7fffffff || tj * s.K > 0x3fffffff) throw std::runtime_error("ppals: parafac2_step: too many tiles");
+    const int64_t npart = tj * s.K;
+    double *part = (double *)ensure(ws_part_, ws_part_sz_, sizeof(double) * 2 * npart);
+    const int nt = (s.R + 15) / 16;
+    route("parafac2.step.%s.%s R=%d nt=%d tiles=%dx%d lds=%zu,%zu", s.dt == F32 ? "f32" : "f64",
+          s.vdt == DV_F32 ? "f32" : "f64", s.R, nt, (int)ti, (int)tj, p2_project_lds(s.R), p2_compress_lds(s.R));
+    join_stream(caller_stream);  // the view is ready once the caller's work so far is done
+    dispatch<1, 2, 3, 4>(nt, [&](auto NT) {
+      if (s.vdt == DV_F32)
+        p2_launch<float, NT()>(s, (int)ti, (int)tj, part);
+      else
+        p2_launch<double, NT()>(s, (int)ti, (int)tj, part);
+    });
+    HIP_CHECK(hipGetLastError());
+    release_stream(caller_stream);  // and the caller may change the view after the reads
+    if (s.out) {
+      hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(1024), 0, st_, part, (int)npart, s.out);
+      hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(1024), 0, st_, part + npart, (int)npart, s.out + 1);
+      hipLaunchKernelGGL(k_p2_failed, dim3(1), dim3(1024), 0, st_, s.status, s.K, s.out + 2);
+      HIP_CHECK(hipGetLastError());
+    }
   }
 
   void *try_alloc(size_t bytes) override {

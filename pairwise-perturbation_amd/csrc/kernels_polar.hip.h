@@ -19,12 +19,11 @@ namespace ppals {
 // dynamic LDS: A[R][R+1], Q[R][R+1] | cs[64] doubles | red[18] doubles | pq[64] ints, R the largest rank
 // of the launch — 67.5 KB at R = 64, so one workgroup per CU; a start of a smaller rank uses the front.
 // C is gathered in Q's place with leading dimension R before the Jacobi initialises Q.
-__global__ __launch_bounds__(1024) void k_polar_factor(const double *__restrict__ M, int64_t ldm, int64_t rows,
-                                                      StartTable t, double min_ratio, double *__restrict__ T,
-                                                      int *__restrict__ status) {
-  extern __shared__ double lds[];
-  const int b = blockIdx.x;
-  const int R = t.col[b + 1] - t.col[b];
+// (polar_factor_body: the workgroup's work on one matrix M of R columns, so that the slice polar factors of
+// PARAFAC2, kernels_parafac2.hip.h, run the same code on a batch that a StartTable cannot carry)
+__device__ inline void polar_factor_body(const double *__restrict__ M, int64_t ldm, int64_t rows, int R,
+                                         double min_ratio, double *__restrict__ Tb, int *__restrict__ status_b,
+                                         double *lds) {
   const int ldA = R + 1;
   double *A = lds;
   double *Q = A + R * ldA;
@@ -32,7 +31,7 @@ __global__ __launch_bounds__(1024) void k_polar_factor(const double *__restrict_
   double *red = cs + 64;
   int *pq = (int *)(red + 18);
   const int tid = threadIdx.x;
-  gram_pairs(M + (int64_t)t.col[b] * ldm, rows, ldm, R, Q, tid >> 6, blockDim.x >> 6);
+  gram_pairs(M, rows, ldm, R, Q, tid >> 6, blockDim.x >> 6);
   __syncthreads();
   for (int e = tid; e < R * R; e += blockDim.x) A[(e % R) * ldA + e / R] = Q[e];
   __syncthreads();
@@ -60,17 +59,24 @@ __global__ __launch_bounds__(1024) void k_polar_factor(const double *__restrict_
     tmax = th > tmax ? th : tmax;
   }
   if (good && tmin <= tmax * min_ratio) good = false;
-  if (tid == 0) status[b] = good ? 1 : 0;
+  if (tid == 0) *status_b = good ? 1 : 0;
   if (!good) return;
   if (tid < R) cs[tid] = 1.0 / sqrt(A[tid * ldA + tid]);
   __syncthreads();
-  double *Tb = T + t.sq[b];
   for (int e = tid; e < R * R; e += blockDim.x) {  // T[i, j] = sum_k U[i, k] U[j, k] / sqrt(theta_k)
     const int i = e % R, j = e / R;
     double acc = 0;
     for (int k = 0; k < R; k++) acc += Q[i * ldA + k] * cs[k] * Q[j * ldA + k];
     Tb[e] = acc;
   }
+}
+__global__ __launch_bounds__(1024) void k_polar_factor(const double *__restrict__ M, int64_t ldm, int64_t rows,
+                                                      StartTable t, double min_ratio, double *__restrict__ T,
+                                                      int *__restrict__ status) {
+  extern __shared__ double lds[];
+  const int b = blockIdx.x;
+  polar_factor_body(M + (int64_t)t.col[b] * ldm, ldm, rows, t.col[b + 1] - t.col[b], min_ratio, T + t.sq[b],
+                    status + b, lds);
 }
 
 // Launch 2, a grid of (row tiles x starts); a workgroup is ONE wave on a tile of 64 rows, a lane one row, with

@@ -285,6 +285,42 @@ class Ops {
     throw Unsupported("ppals: this back end has no device views");
   }
 
+  // PARAFAC2 (ppals_parafac2_*): the projection step on a device view X of extents I x J x K
+  // with unit stride in mode 0. parafac2_check refuses where the back end has no device views and does
+  // nothing else; parafac2_init writes the first R identity columns into every I x R slice of P.
+  // parafac2_step, in a number of launches that does not depend on the extents, for every slice k:
+  //   Q_k = X_k A diag(C[k, :]) B^T                        (I x R, fp64, column-major at Q + I R k)
+  //   C_k = Q_k^T Q_k = U diag(theta) U^T; status[k] = 1 under the rule of cp_mode_update_ortho_ragged
+  //   (converged Jacobi, every theta positive and finite, theta_min > theta_max * min_ratio), else 0
+  //   P_k = Q_k U diag(theta^-1/2) U^T where status[k] is 1; P_k as it was otherwise
+  //   Y[:, j, k] = P_k^T X_k[:, j], rounded once to the storage type dt (F32 or F64), r fastest
+  // out (device, 3 doubles, may be nullptr): sum x^2, sum y^2 (fp64, before the rounding) and the number of
+  // slices whose status is 0, each formed in a fixed order. The reads of X are ordered after what
+  // caller_stream holds, and what the caller queues there later waits for them.
+  struct Parafac2Step {
+    int64_t I = 0, J = 0, K = 0;
+    int R = 0;
+    const void *X = nullptr;
+    int vdt = 0;                // DV_F32 or DV_F64
+    int64_t s1 = 0, s2 = 0;     // the element strides of modes 1 and 2
+    const double *B = nullptr;  // R x R, J x R, K x R: column-major, leading dimensions R, J, K
+    const double *A = nullptr;
+    const double *C = nullptr;
+    double *Q = nullptr, *P = nullptr, *T = nullptr;  // I x R x K twice; R x R x K
+    int *status = nullptr;
+    double min_ratio = 0;
+    void *Y = nullptr;
+    int dt = 0;
+    double *out = nullptr;
+  };
+  virtual void parafac2_check() { throw Unsupported("ppals: this back end has no device views"); }
+  virtual void parafac2_init(double * /*P*/, int64_t /*I*/, int /*R*/, int64_t /*K*/) {
+    throw Unsupported("ppals: this back end has no device views");
+  }
+  virtual void parafac2_step(const Parafac2Step & /*s*/, void * /*caller_stream*/) {
+    throw Unsupported("ppals: this back end has no device views");
+  }
+
   // Order work on the engine stream against a caller's stream, as copy_view does it: join_stream makes the
   // work queued on the engine stream from now on wait for what `caller_stream` holds so far, release_stream
   // makes what the caller queues there later wait for the engine stream's work so far. The host does not block.

@@ -1,6 +1,7 @@
 // ppals_api.cpp — the C ABI declared in include/ppals.h: thin, exception-free glue between plain
 // pointers/sizes and the engine. The backend (device ops + communicator) comes from backend.h:
 // libppals.so links the HIP/RCCL backend; there is no other backend in the product.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -8,6 +9,7 @@
 #include <stdexcept>
 #include <set>
 #include <string>
+#include <vector>
 
 #include "../../include/ppals.h"
 #include "backend.h"
@@ -33,6 +35,7 @@ struct ppals_ctx {
   std::set<ppals_cp_multi *> multis;
   std::set<ppals_tucker *> tks;
   std::set<ppals_tensor *> tensors;
+  std::set<struct ppals_parafac2 *> p2s;
 };
 struct ppals_tensor {
   ppals_ctx *ctx;
@@ -51,6 +54,18 @@ struct ppals_cp_multi {
 struct ppals_tucker {
   ppals_ctx *ctx;
   TuckerEngine *eng;
+};
+// PARAFAC2: the owner of the compressed tensor Y (R x J x K), of the rank-R session on it and of the
+// projections. Y and cp are ordinary handles of the context (it leaves them dead like any other when it goes
+// first); the device buffers are this object's.
+struct ppals_parafac2 {
+  ppals_ctx *ctx;
+  int64_t I, J, K;
+  int R;
+  ppals_tensor *Y;
+  ppals_cp *cp;
+  double *P, *Q, *T, *out;  // I x R x K twice, R x R x K, 3 doubles
+  int *status;              // K
 };
 
 #define API_BEGIN try {
@@ -99,8 +114,22 @@ int ppals_ctx_create(ppals_ctx **out, int device) {
   return PPALS_OK;
   API_END(PPALS_ERR_NO_DEVICE)
 }
+static void p2_free_buffers(ppals_parafac2 *p) {
+  for (void *b : {(void *)p->P, (void *)p->Q, (void *)p->T, (void *)p->out, (void *)p->status}) {
+    try {
+      p->ctx->ops->free(b);
+    } catch (...) {
+    }
+  }
+  p->P = p->Q = p->T = p->out = nullptr;
+  p->status = nullptr;
+}
 void ppals_ctx_destroy(ppals_ctx *ctx) {
   if (!ctx) return;
+  for (ppals_parafac2 *p : ctx->p2s) {  // (its session and tensor are in the sets below)
+    p2_free_buffers(p);
+    p->ctx = nullptr;
+  }
   for (ppals_cp *s : ctx->cps) {
     delete s->eng;
     s->eng = nullptr;
@@ -971,6 +1000,169 @@ int ppals_cp_abs_residual_quantile(ppals_cp *s, const void *data, const void *we
   s->eng->abs_residual_quantile(a, data, weights ? &w : nullptr, weights, stream, p, value, count);
   return PPALS_OK;
   API_END(PPALS_ERR_HIP)
+}
+
+// ------------------------------------------------------------------ PARAFAC2
+int ppals_parafac2_create(ppals_ctx *ctx, int64_t I, int64_t J, int64_t K, int R, int storage_dtype,
+                          ppals_parafac2 **out) {
+  const char *fn = "ppals_parafac2_create";
+  if (!ctx || !out) return fail_fn(PPALS_ERR_ARG, fn, "NULL argument");
+  *out = nullptr;
+  if (I < 1 || J < 1 || K < 1) return fail_fn(PPALS_ERR_ARG, fn, "the extents I, J, K must be positive");
+  if (R < 2 || R > 64) return fail_fn(PPALS_ERR_ARG, fn, "the rank must lie in [2, 64]");
+  if (R > I || R > J) return fail_fn(PPALS_ERR_ARG, fn, "the rank must not exceed min(I, J)");
+  if (storage_dtype != PPALS_F32 && storage_dtype != PPALS_F64 && storage_dtype != PPALS_BF16)
+    return fail_fn(PPALS_ERR_ARG, fn, "bad storage dtype");
+  if (storage_dtype == PPALS_BF16)
+    return fail_fn(PPALS_ERR_UNSUPPORTED, fn,
+                   "BF16 storage is not supported: the loss identity needs Y = P^T X to a rounding well below the "
+                   "residual it is compared with");
+  if (ctx->c().size() > 1)
+    return fail_fn(PPALS_ERR_UNSUPPORTED, fn,
+                   "a context of more than one rank is not supported (the compressed tensor's leading mode is the "
+                   "rank R and cannot be sharded usefully)");
+  API_BEGIN
+  ctx->ops->parafac2_check();  // a back end without device views refuses here, nothing allocated
+  std::unique_ptr<ppals_parafac2> p(new ppals_parafac2());
+  p->ctx = ctx;
+  p->I = I, p->J = J, p->K = K, p->R = R;
+  const int64_t lens[3] = {R, J, K};
+  int rc = ppals_tensor_create(ctx, 3, lens, storage_dtype, &p->Y);
+  if (rc == PPALS_OK) {
+    ctx->ops->zero(p->Y->d.data, (size_t)p->Y->d.nloc * dtype_size(p->Y->d.dtype));
+    rc = ppals_cp_create(ctx, p->Y, R, &p->cp);
+  }
+  if (rc == PPALS_OK) {  // B = I_R, A = the uniform generator's block of mode 1, C = 1
+    std::vector<double> W((size_t)R * (R + J + K), 0.0);
+    for (int r = 0; r < R; r++) W[(size_t)r * (R + 1)] = 1.0;
+    ppals_fill_uniform_host(W.data() + (size_t)R * R, J * R, 1, 0, 0.0, 1.0);
+    std::fill(W.begin() + (size_t)R * (R + J), W.end(), 1.0);
+    rc = ppals_cp_set_factors(p->cp, W.data(), nullptr);
+  }
+  if (rc != PPALS_OK) {
+    ppals_cp_destroy(p->cp);
+    ppals_tensor_destroy(p->Y);
+    return rc;
+  }
+  ctx->p2s.insert(p.get());  // from here on ppals_parafac2_destroy undoes everything
+  ppals_parafac2 *q = p.release();
+  try {
+    const size_t n = sizeof(double) * (size_t)I * R * K;
+    q->P = (double *)ctx->ops->alloc(n);
+    q->Q = (double *)ctx->ops->alloc(n);
+    q->T = (double *)ctx->ops->alloc(sizeof(double) * (size_t)R * R * K);
+    q->out = (double *)ctx->ops->alloc(sizeof(double) * 3);
+    q->status = (int *)ctx->ops->alloc(sizeof(int) * (size_t)K);
+    ctx->ops->zero(q->status, sizeof(int) * (size_t)K);
+    ctx->ops->parafac2_init(q->P, I, R, K);
+  } catch (...) {
+    ppals_parafac2_destroy(q);
+    throw;
+  }
+  *out = q;
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+void ppals_parafac2_destroy(ppals_parafac2 *p) {
+  if (!p) return;
+  if (p->ctx) {
+    p2_free_buffers(p);
+    p->ctx->p2s.erase(p);
+  }
+  ppals_cp_destroy(p->cp);  // (dead handles when the context went first: then these only delete them)
+  ppals_tensor_destroy(p->Y);
+  delete p;
+}
+ppals_cp *ppals_parafac2_cp(ppals_parafac2 *p) { return p && p->ctx ? p->cp : nullptr; }
+ppals_tensor *ppals_parafac2_tensor(ppals_parafac2 *p) { return p && p->ctx ? p->Y : nullptr; }
+
+// every check of a step, nothing launched or allocated: on success *st is ready but for `out`
+static int p2_check_step(ppals_parafac2 *p, const char *fn, const void *data, int dtype, const int64_t *strides,
+                         Ops::Parafac2Step *st) {
+  if (!p || !p->ctx || !p->cp || !p->cp->eng) return fail_fn(PPALS_ERR_ARG, fn, "NULL or dead handle");
+  if (!data) return fail_fn(PPALS_ERR_ARG, fn, "the data pointer is NULL");
+  if (dtype != PPALS_F32 && dtype != PPALS_F64)
+    return fail_fn(PPALS_ERR_ARG, fn, "bad dtype of the data view (PPALS_F32 or PPALS_F64)");
+  if (p->cp->eng->mode_kind(0) != ppals::kModeFree)
+    return fail_fn(PPALS_ERR_ARG, fn, "mode 0 of the inner session (B) must stay PPALS_MODE_FREE");
+  const int64_t lens[3] = {p->I, p->J, p->K};
+  ViewArgs a;
+  std::string err;
+  if (!dv_check_args(DV_IMPORT, 3, lens, dtype, nullptr, nullptr, strides, &a, &err))
+    return fail_fn(PPALS_ERR_ARG, fn, ("the data view: " + err).c_str());
+  if (a.stride[0] != 1 || !dv_no_self_overlap(3, a.len, a.stride))
+    return fail_fn(PPALS_ERR_UNSUPPORTED, fn,
+                   "the data view needs a unit stride in mode 0 and slices that do not overlap: permute the tensor "
+                   "so that the shifting mode comes first and make it contiguous");
+  if ((uintptr_t)data % (uintptr_t)a.esize)
+    return fail_fn(PPALS_ERR_ARG, fn, "the data pointer is not aligned to its element size");
+  const int rc = check_view_ptr(p->ctx, (std::string(fn) + ": the data view: ").c_str(), data, &a);
+  if (rc != PPALS_OK) return rc;
+  const CpEngine &e = *p->cp->eng;
+  st->I = p->I, st->J = p->J, st->K = p->K, st->R = p->R;
+  st->X = data, st->vdt = dtype, st->s1 = a.stride[1], st->s2 = a.stride[2];
+  st->B = e.factor_device(0), st->A = e.factor_device(1), st->C = e.factor_device(2);
+  st->Q = p->Q, st->P = p->P, st->T = p->T, st->status = p->status;
+  st->min_ratio = PPALS_ORTHO_MIN_RATIO;
+  st->Y = p->Y->d.data, st->dt = p->Y->d.dtype;
+  return PPALS_OK;
+}
+static void p2_step(ppals_parafac2 *p, Ops::Parafac2Step st, void *stream, double *lost_sq, int *failed) {
+  const bool want = lost_sq || failed;
+  st.out = want ? p->out : nullptr;
+  p->Y->generation++;  // the contents change with these launches: the session rebuilds what it derived
+  p->ctx->ops->parafac2_step(st, stream);
+  if (!want) return;
+  double o[3];
+  p->ctx->ops->d2h(o, p->out, sizeof(o));
+  if (lost_sq) *lost_sq = o[0] - o[1];
+  if (failed) *failed = (int)o[2];
+}
+int ppals_parafac2_step_device(ppals_parafac2 *p, const void *data, int dtype, const int64_t *strides, void *stream,
+                               double *lost_sq, int *failed) {
+  API_BEGIN
+  Ops::Parafac2Step st;
+  const int rc = p2_check_step(p, "ppals_parafac2_step_device", data, dtype, strides, &st);
+  if (rc != PPALS_OK) return rc;
+  p2_step(p, st, stream, lost_sq, failed);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_parafac2_run(ppals_parafac2 *p, const void *data, int dtype, const int64_t *strides, void *stream,
+                       const ppals_cp_opts *o, int inner_sweeps, double rel_change, int *iters, double *res) {
+  API_BEGIN
+  if (!o) return fail(PPALS_ERR_ARG, "ppals_parafac2_run: NULL options");
+  if (inner_sweeps < 1) return fail(PPALS_ERR_ARG, "ppals_parafac2_run: inner_sweeps must be at least 1");
+  if (!(rel_change >= 0)) return fail(PPALS_ERR_ARG, "ppals_parafac2_run: rel_change must not be negative");
+  if (o->maxiter < 0) return fail(PPALS_ERR_ARG, "ppals_parafac2_run: maxiter must not be negative");
+  Ops::Parafac2Step st;
+  const int rc = p2_check_step(p, "ppals_parafac2_run", data, dtype, strides, &st);
+  if (rc != PPALS_OK) return rc;
+  CpEngine *e = p->cp->eng;
+  // the quantity looked at: lost_sq + the inner residual^2 after the step (one pass over the small Y)
+  return e->run_steps(
+      [&](double *sq) {
+        double lost = 0;
+        p2_step(p, st, stream, sq ? &lost : nullptr, nullptr);
+        if (sq) {
+          const double r = e->residual();
+          *sq = std::max(lost, 0.0) + r * r;
+        }
+      },
+      to_opts(o), inner_sweeps, rel_change, iters, res);
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_parafac2_projections(ppals_parafac2 *p, double *P_host) {
+  if (!p || !p->ctx || !P_host) return fail(PPALS_ERR_ARG, "ppals_parafac2_projections: NULL argument or dead handle");
+  API_BEGIN
+  p->ctx->ops->d2h(P_host, p->P, sizeof(double) * (size_t)p->I * p->R * p->K);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_parafac2_projections_device(ppals_parafac2 *p, const double **P) {
+  if (!p || !p->ctx || !P) return fail(PPALS_ERR_ARG, "ppals_parafac2_projections_device: NULL argument or dead handle");
+  *P = p->P;
+  return PPALS_OK;
 }
 
 // ------------------------------------------------------------------ multi-start CP

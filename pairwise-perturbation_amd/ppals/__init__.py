@@ -79,6 +79,9 @@ EXPORTS = [
     "ppals_cp_multi_set_mode_shapes", "ppals_cp_multi_get_mode_shapes",
     "ppals_tensor_center", "ppals_tensor_shift", "ppals_tensor_slice_sumsq", "ppals_tensor_scale",
     "ppals_tensor_rescale",
+    "ppals_parafac2_create", "ppals_parafac2_destroy", "ppals_parafac2_cp", "ppals_parafac2_tensor",
+    "ppals_parafac2_step_device",
+    "ppals_parafac2_run", "ppals_parafac2_projections", "ppals_parafac2_projections_device",
 ]
 HOST, DEVICE = 0, 1  # PPALS_HOST / PPALS_DEVICE: where the offsets of Tensor.center / Tensor.shift lie
 MODE_FREE, MODE_NONNEG, MODE_FIXED, MODE_ORTHO = 0, 1, 2, 3  # PPALS_MODE_*
@@ -1027,6 +1030,160 @@ class CP(_ModelExport, _Impute, _Wls, _Robust):
             self.close()
         except Exception:
             pass
+
+
+class _BorrowedCP(CP):
+    """the inner session of a Parafac2: a CP on the compressed tensor; closing it does nothing
+    (ppals_parafac2_destroy destroys the session)"""
+
+    def __init__(self, owner, handle, lens, R):
+        self.ctx, self.V, self.R = owner.ctx, None, R
+        self.lens = list(lens)
+        self._owner = owner  # keeps the owner alive while the session is in use
+        self._h = handle
+
+    def close(self):
+        self._h = C.c_void_p()
+
+
+class _BorrowedTensor(Tensor):
+    """the compressed tensor of a Parafac2 (R x J x K): download, export and norm; closing it does nothing"""
+
+    def __init__(self, owner, handle, lens, dtype):
+        self.ctx, self.lens, self.dtype, self._owner, self._h = owner.ctx, list(lens), dtype, owner, handle
+
+    def close(self):
+        self._h = C.c_void_p()
+
+
+class Parafac2:
+    """PARAFAC2 by direct fitting (ppals_parafac2_*): X_k ~ P_k B diag(C[k, :]) A^T for the slices X_k = X[:, :, k]
+    of an I x J x K torch tensor on the context's device, P_k^T P_k = I. `.cp` is the rank-R CP session on the
+    compressed tensor (R x J x K; factors [B, A, C]): constraints, shapes, schedule and diagnostics are set there;
+    mode 0 (B) must stay free."""
+
+    def __init__(self, ctx, I, J, K, R, dtype=F64):
+        self.ctx, self.I, self.J, self.K, self.R, self.dtype = ctx, int(I), int(J), int(K), int(R), dtype
+        self._h = C.c_void_p()
+        _check(lib().ppals_parafac2_create(ctx._h, C.c_int64(self.I), C.c_int64(self.J), C.c_int64(self.K), self.R,
+                                           int(dtype), C.byref(self._h)))
+        lib().ppals_parafac2_cp.restype = C.c_void_p
+        self.cp = _BorrowedCP(self, C.c_void_p(lib().ppals_parafac2_cp(self._h)), [self.R, self.J, self.K], self.R)
+        lib().ppals_parafac2_tensor.restype = C.c_void_p
+        self.Y = _BorrowedTensor(self, C.c_void_p(lib().ppals_parafac2_tensor(self._h)), [self.R, self.J, self.K], dtype)
+        self.cp.V = self.Y
+        ctx._children.add(self)
+
+    def _view(self, X):
+        torch = _torch()
+        if X.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"the torch dtype {X.dtype} of X is not torch.float32 or torch.float64")
+        if X.device.type != "cuda" or X.device.index != self.ctx.device:
+            raise PpalsError(f"the torch tensor is on {X.device}, the context on cuda:{self.ctx.device}")
+        if tuple(X.shape) != (self.I, self.J, self.K):
+            raise PpalsError(f"X has shape {tuple(X.shape)}, the model {(self.I, self.J, self.K)}")
+        return X.data_ptr(), (F64 if X.dtype == torch.float64 else F32), (C.c_int64 * 3)(*X.stride())
+
+    def step_device(self, ptr, dtype, strides=None, stream=0, want=True):
+        """raw ppals_parafac2_step_device; strides in elements (None: dense, first index fastest). Returns
+        (lost_sq, failed) if want (the call then waits), else None."""
+        st = (C.c_int64 * 3)(*[int(x) for x in strides]) if strides is not None else None
+        lost, failed = C.c_double(0), C.c_int(0)
+        _check(lib().ppals_parafac2_step_device(self._h, C.c_void_p(int(ptr)), int(dtype), st,
+                                                C.c_void_p(int(stream or 0)), C.byref(lost) if want else None,
+                                                C.byref(failed) if want else None))
+        return (float(lost.value), int(failed.value)) if want else None
+
+    def step_torch(self, X, stream=None, want=True):
+        """one projection step from the session's current factors: new P_k where Q_k has a polar factor, Y = P^T X
+        into the compressed tensor. X: float32 or float64 with X.stride(0) == 1 (e.g. made by
+        x.permute(2, 1, 0).contiguous().permute(2, 1, 0)). Returns (lost_sq, failed), or None if not want."""
+        ptr, code, st = self._view(X)
+        return self.step_device(ptr, code, st, Tensor._stream(stream), want)
+
+    def run(self, X, inner_sweeps=1, rel_change=0.0, stream=None, **opts):
+        """ppals_parafac2_run: repeat { step; inner_sweeps exact sweeps } with the looks and stop rules of
+        CP.run_wls. Returns (rc, iterations, ||X - model||)."""
+        ptr, code, st = self._view(X)
+        o = _opts(**opts)
+        it, res = C.c_int(0), C.c_double(0)
+        rc = _check(lib().ppals_parafac2_run(self._h, C.c_void_p(int(ptr)), int(code), st,
+                                             C.c_void_p(int(Tensor._stream(stream) or 0)), C.byref(o),
+                                             int(inner_sweeps), C.c_double(float(rel_change)), C.byref(it),
+                                             C.byref(res)))
+        return rc, it.value, res.value
+
+    def loss(self, X, stream=None):
+        """||X - model||^2 of the session's current factors with the P_k that are best for them: takes a step
+        (which can only lower the loss), then lost_sq + the inner residual squared"""
+        lost, _ = self.step_torch(X, stream)
+        return max(lost, 0.0) + self.cp.residual() ** 2
+
+    def projections(self):
+        """the P_k as a K x I x R numpy array"""
+        out = np.empty((self.I, self.R, self.K), order="F")
+        _check(lib().ppals_parafac2_projections(self._h, _dp(out)))
+        return np.ascontiguousarray(out.transpose(2, 0, 1))
+
+    def projections_device(self):
+        """the device pointer of P (I x R x K doubles, first index fastest), the object's"""
+        ptr = c_dp()
+        _check(lib().ppals_parafac2_projections_device(self._h, C.byref(ptr)))
+        return C.cast(ptr, C.c_void_p).value
+
+    def profiles(self):
+        """the slice profiles P_k B as a K x I x R numpy array"""
+        return self.projections() @ self.cp.get_factors()[0]
+
+    def close(self):
+        if self._h:
+            self.cp.close()
+            self.Y.close()
+            lib().ppals_parafac2_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def parafac2(X, R, n_iter=100, nonneg_modes=(), inner_sweeps=1, rel_change=0.0, dtype=F64, ctx=None, A0=None):
+    """PARAFAC2 of a torch tensor X (I x J x K on a GPU, float32 or float64; mode 0 shifts, mode 2 are the slices).
+    nonneg_modes: which of the modes 1 (A) and 2 (C) are non-negative. Looks at the loss at every iteration.
+    Returns a dict: B, A, C, projections (K x I x R), profiles (K x I x R), losses (||X - model||^2 per
+    iteration, the final one last), iterations, rc."""
+    if X.stride(0) != 1:
+        X = X.permute(2, 1, 0).contiguous().permute(2, 1, 0)
+    own = ctx is None
+    ctx = ctx or Context(X.device.index or 0)
+    I, J, K = X.shape
+    p2 = Parafac2(ctx, I, J, K, R, dtype)
+    try:
+        if A0 is not None:
+            p2.cp.set_factors([np.eye(R), np.asarray(A0, dtype=np.float64), np.ones((K, R))])
+        if nonneg_modes:
+            if 0 in nonneg_modes:
+                raise ValueError("mode 0 (B) must stay free in PARAFAC2")
+            p2.cp.set_mode_constraints(["nonneg" if m in nonneg_modes else "free" for m in range(3)])
+        losses, rc, it = [], 0, 0
+        for it in range(int(n_iter)):
+            losses.append(p2.loss(X))
+            if rel_change > 0 and it > 0 and losses[-2] - losses[-1] <= rel_change * losses[-2]:
+                rc = 2
+                break
+            p2.cp.sweeps_dt(inner_sweeps)
+        else:
+            it = int(n_iter)
+            losses.append(p2.loss(X))
+        B, A, Cm = p2.cp.get_factors()
+        return dict(B=B, A=A, C=Cm, projections=p2.projections(), profiles=p2.profiles(), losses=losses,
+                    iterations=it, rc=rc)
+    finally:
+        p2.close()
+        if own:
+            ctx.close()
 
 
 class CPMulti:
