@@ -894,6 +894,67 @@ int ppals_parafac2_run(ppals_parafac2 *p, const void *data, int dtype, const int
 int ppals_parafac2_projections(ppals_parafac2 *p, double *P_host);
 int ppals_parafac2_projections_device(ppals_parafac2 *p, const double **P);
 
+/* ---- N-PLS regression (multilinear PLS: Bro, J. Chemometrics 10 (1996) 47-61; `npls` of the N-way toolbox) ----
+ * X is a resident tensor of any order N >= 2, `mode` its sample mode with I = lens[mode] samples; Y is I x M on
+ * the host, column-major. The caller has centred both (ppals_tensor_center for X). Component f has one unit weight
+ * vector for every mode off the sample mode, W_f their outer product (laid out like a sample's slice), scores
+ * t_f = (X - sum_{g<f} t_g o W_g) . W_f, response weights q_f (unit) and u_f = Y_res q_f; the inner relation
+ * B[0..f, f] = (T^T T)^-1 T^T u_f is upper triangular (the scores of N-PLS are not orthogonal), and
+ * Y_res = Y - T B Q^T. W_f is the best rank-one approximation, by alternating power iterations from the fibres
+ * through the entry of largest magnitude, of Z = sum_m q_m Z_m, Z_m the deflated tensor contracted with column m of
+ * Y_res; q is iterated from the column of Y_res with the largest sum of squares. Signs: the entry of largest
+ * magnitude of every weight vector but the last is positive, the last makes <Z, W> positive.
+ *
+ * The tensor is NEVER WRITTEN and nothing of its size is allocated: the deflated tensor is not formed. A component
+ * reads X twice (a contraction with the M columns of Y_res, a slice inner product with W_f); the working set is
+ * M + 2 arrays of a slice's size in fp64. Elements are widened to fp64 as stored, sums are fp64 in a fixed
+ * order: the same state gives the same bits. The calls read the primary resident layout, are ordered after the
+ * work queued on the engine stream, bump no generation and disturb no session. They return with the results on
+ * the host.
+ *
+ * Refusals come before anything is launched or allocated and the message starts with the function's name:
+ * PPALS_ERR_ARG for NULL or dead handles, `mode` outside [0, N), M < 1, F < 1 or F > I, a non-finite Y, bad options
+ * (a negative or NaN tolerance, a cap below 1), ncomp outside [1, components fitted], Xnew of another order or with
+ * other extents off the sample mode; PPALS_ERR_UNSUPPORTED for a context of more than one rank.
+ *
+ * A zero or non-finite Z ends the fit with the components so far (possibly none): not an error, ppals_npls_dims
+ * tells. status[f]: bit 0 the power iterations ran into hopm_max, bit 1 the loop over q into inner_max. */
+typedef struct ppals_npls ppals_npls; /* a fitted N-PLS model: host arrays only, no reference to X or the context */
+typedef struct {
+  double hopm_tol; /* the power iterations stop when no weight entry moved by more than this (1e-12) */
+  int hopm_max;    /* ... or after this many rounds (500) */
+  double inner_tol; /* the loop over q (M > 1) stops when no entry of q moved by more than this (1e-12) */
+  int inner_max;    /* ... or after this many rounds (200) */
+} ppals_npls_opts;
+enum {
+  PPALS_NPLS_T = 0,      /* I x F   scores of X */
+  PPALS_NPLS_U = 1,      /* I x F   scores of Y */
+  PPALS_NPLS_Q = 2,      /* M x F   response weights, unit columns */
+  PPALS_NPLS_B = 3,      /* F x F   inner relation, upper triangular */
+  PPALS_NPLS_SSX = 4,    /* F       1 - ||X - sum_{g<=f} t_g o W_g||^2 / ||X||^2, from ||X||^2 - 2 sum t_g.s_g +
+                                    sum (t_g.t_h) <W_g, W_h> at no pass: a difference, it loses digits when the
+                                    residual is tiny */
+  PPALS_NPLS_SSY = 5,    /* F       1 - ||Y_res||^2 / ||Y||^2 */
+  PPALS_NPLS_STATUS = 6, /* F       the status bits, as doubles */
+  PPALS_NPLS_W = 16      /* + k: lens x F, the weights of the k-th mode off the sample mode, k in [0, N - 1) */
+};
+/* opts == NULL: the defaults above. F counts the components wanted; all arrays below have the fitted number. */
+int ppals_npls_fit(ppals_tensor *X, int mode, const double *Y, int M, int F, const ppals_npls_opts *opts,
+                   ppals_npls **out);
+void ppals_npls_destroy(ppals_npls *m);
+/* any pointer may be NULL; lens: `order` extents, those of the training tensor */
+int ppals_npls_dims(const ppals_npls *m, int *order, int *mode, int64_t *lens, int *M, int *wanted, int *fitted);
+/* `what` as above, column-major; *n receives the number of doubles, out == NULL only asks for it */
+int ppals_npls_get(const ppals_npls *m, int what, double *out, int64_t *n);
+/* Yhat (Inew x M) from the first ncomp components, for a tensor of the model's order and extents off the sample
+ * mode and any Inew: ONE pass over Xnew gives all raw scores, the rest is on the host. Tnew: Inew x ncomp. */
+int ppals_npls_predict(const ppals_npls *m, ppals_tensor *Xnew, int ncomp, double *Yhat, double *Tnew /* may be NULL */);
+/* The two tensor passes on their own, host pointers, the tensor viewed as [L, I, T] around `mode` (first index
+ * fastest): Z[l,t,c] = sum_i X[l,i,t] U[i,c] (U: I x C, Z: L T C doubles) and S[i,c] = sum_{l,t} X[l,i,t] W[l,t,c]
+ * (W: L T C, S: I x C). Column c has the bits of that column computed alone. Refusals as above (C < 1 too). */
+int ppals_tensor_contract_mode(ppals_tensor *t, int mode, const double *U, int C, double *Z);
+int ppals_tensor_slice_inner(ppals_tensor *t, int mode, const double *W, int C, double *S);
+
 /* ---- Tucker with missing entries (TensorLy's tucker(mask=...)): imputation and an EM driver ----
  * The contracts of ppals_cp_impute_device / ppals_cp_em with a Tucker session in the CP session's place:
  * the same PPALS_U8 mask view (a box of the GLOBAL tensor, strides >= 0, 0 broadcasts, NULL = dense, a byte

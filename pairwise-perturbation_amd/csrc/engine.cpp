@@ -273,6 +273,360 @@ void tensor_scale(Ops &ops, const TensorDesc &V, int mode, double *rms_host) {
   tensor_rescale(ops, V, mode, f.data());
 }
 
+// ============================================================================ N-PLS
+namespace {
+struct DevBuf {  // a device array of doubles for the length of a call
+  Ops &ops;
+  double *p;
+  DevBuf(Ops &o, int64_t n) : ops(o), p((double *)o.alloc(sizeof(double) * (size_t)std::max<int64_t>(n, 1))) {}
+  ~DevBuf() {
+    try {
+      ops.free(p);
+    } catch (...) {
+    }
+  }
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+};
+double dotn(const double *a, const double *b, int64_t n) {
+  double s = 0;
+  for (int64_t i = 0; i < n; i++) s += a[i] * b[i];
+  return s;
+}
+// A x = b, A n x n column-major (destroyed), partial pivoting; a zero pivot gives x = 0 for that unknown
+void solve_small(std::vector<double> &A, std::vector<double> &b, int n) {
+  for (int k = 0; k < n; k++) {
+    int p = k;
+    for (int i = k + 1; i < n; i++)
+      if (std::fabs(A[i + (size_t)n * k]) > std::fabs(A[p + (size_t)n * k])) p = i;
+    if (p != k) {
+      for (int j = 0; j < n; j++) std::swap(A[k + (size_t)n * j], A[p + (size_t)n * j]);
+      std::swap(b[k], b[p]);
+    }
+    const double d = A[k + (size_t)n * k];
+    if (d == 0) continue;
+    for (int i = k + 1; i < n; i++) {
+      const double m = A[i + (size_t)n * k] / d;
+      if (m == 0) continue;
+      for (int j = k; j < n; j++) A[i + (size_t)n * j] -= m * A[k + (size_t)n * j];
+      b[i] -= m * b[k];
+    }
+  }
+  for (int k = n - 1; k >= 0; k--) {
+    double s = b[k];
+    for (int j = k + 1; j < n; j++) s -= A[k + (size_t)n * j] * b[j];
+    const double d = A[k + (size_t)n * k];
+    b[k] = d == 0 ? 0.0 : s / d;
+  }
+}
+// the modes off the sample mode: their extents, and where each one's vector starts in a component's weights
+struct NplsDims {
+  int K = 0;
+  int64_t ext[MAX_ORDER], off[MAX_ORDER], sum = 0, LT = 1;
+  NplsDims(int order, const int64_t *lens, int mode) {
+    for (int i = 0; i < order; i++)
+      if (i != mode) {
+        ext[K] = lens[i];
+        off[K] = sum;
+        sum += lens[i];
+        LT *= lens[i];
+        K++;
+      }
+  }
+};
+// A = the outer product of the K vectors at wdev + off[k], leaving out mode `skip` (-1: none)
+void npls_outer(Ops &ops, const NplsDims &d, const double *wdev, int skip, double *A) {
+  int64_t ext[MAX_ORDER], n = 1;
+  const double *w[MAX_ORDER];
+  int K = 0;
+  for (int k = 0; k < d.K; k++)
+    if (k != skip) {
+      ext[K] = d.ext[k];
+      w[K] = wdev + d.off[k];
+      n *= d.ext[k];
+      K++;
+    }
+  ops.zero(A, sizeof(double) * (size_t)n);
+  ops.npls_outer_axpy(A, ext, K, w, 1.0);
+}
+// v = Z contracted with the vectors at wdev over every mode but k (ext[k] doubles on the host); scratch: LT doubles
+void npls_mode_product(Ops &ops, const NplsDims &d, const double *Z, const double *wdev, int k, double *scratch,
+                       double *dS, double *v) {
+  int64_t L = 1, T = 1;
+  for (int j = 0; j < k; j++) L *= d.ext[j];
+  for (int j = k + 1; j < d.K; j++) T *= d.ext[j];
+  npls_outer(ops, d, wdev, k, scratch);
+  ops.npls_slice_inner(Z, F64, L, d.ext[k], T, scratch, 1, dS);
+  ops.d2h(v, dS, sizeof(double) * (size_t)d.ext[k]);
+}
+bool normalise(double *v, int64_t n) {
+  const double nrm = std::sqrt(dotn(v, v, n));
+  if (!(nrm > 0) || !std::isfinite(nrm)) return false;
+  for (int64_t i = 0; i < n; i++) v[i] /= nrm;
+  return true;
+}
+// The best rank-one approximation of Z (order K, LT doubles on the device) by alternating power iterations, started
+// from the fibres through the entry of largest magnitude. w: d.sum doubles on the host, wdev: the same on the
+// device (left holding w). false: Z is zero or not finite. *capped: hopm_max rounds ran without settling.
+bool npls_rank_one(Ops &ops, const NplsDims &d, const double *Z, const NplsOpts &o, double *w, double *wdev,
+                   double *scratch, double *dS, double *dE, bool *capped) {
+  *capped = false;
+  double top[2];
+  ops.npls_argmax(Z, d.LT, dS);
+  ops.d2h(top, dS, sizeof(top));
+  if (!(top[0] > 0) || !std::isfinite(top[0])) return false;
+  if (d.K == 1) {  // ordinary PLS: w = Z / |Z|
+    ops.d2h(w, Z, sizeof(double) * (size_t)d.ext[0]);
+    if (!normalise(w, d.ext[0])) return false;
+    ops.h2d(wdev, w, sizeof(double) * (size_t)d.sum);
+    return true;
+  }
+  {  // the start: unit vectors at the position of the largest entry pick its fibres
+    std::vector<double> e((size_t)d.sum, 0.0);
+    int64_t rem = (int64_t)top[1];
+    for (int k = 0; k < d.K; k++) {
+      e[(size_t)(d.off[k] + rem % d.ext[k])] = 1.0;
+      rem /= d.ext[k];
+    }
+    ops.h2d(dE, e.data(), sizeof(double) * e.size());
+    for (int k = 0; k < d.K; k++) {
+      npls_mode_product(ops, d, Z, dE, k, scratch, dS, w + d.off[k]);
+      if (!normalise(w + d.off[k], d.ext[k])) return false;
+    }
+    ops.h2d(wdev, w, sizeof(double) * (size_t)d.sum);
+  }
+  std::vector<double> v;
+  bool settled = false;
+  for (int round = 0; round < o.hopm_max && !settled; round++) {
+    double moved = 0;
+    for (int k = 0; k < d.K; k++) {
+      v.resize((size_t)d.ext[k]);
+      npls_mode_product(ops, d, Z, wdev, k, scratch, dS, v.data());
+      if (!normalise(v.data(), d.ext[k])) return false;
+      for (int64_t i = 0; i < d.ext[k]; i++) {
+        moved = std::max(moved, std::fabs(v[(size_t)i] - w[d.off[k] + i]));
+        w[d.off[k] + i] = v[(size_t)i];
+      }
+      ops.h2d(wdev + d.off[k], v.data(), sizeof(double) * v.size());
+    }
+    settled = moved <= o.hopm_tol;
+  }
+  *capped = !settled;
+  // signs: the entry of largest magnitude of every vector but the last positive; the last one, updated last, has
+  // <Z, W> > 0 with the others as they were and takes their flips
+  double sg = 1.0;
+  for (int k = 0; k + 1 < d.K; k++) {
+    int64_t p = 0;
+    for (int64_t i = 1; i < d.ext[k]; i++)
+      if (std::fabs(w[d.off[k] + i]) > std::fabs(w[d.off[k] + p])) p = i;
+    if (w[d.off[k] + p] < 0) {
+      for (int64_t i = 0; i < d.ext[k]; i++) w[d.off[k] + i] = -w[d.off[k] + i];
+      sg = -sg;
+    }
+  }
+  if (sg < 0)
+    for (int64_t i = 0; i < d.ext[d.K - 1]; i++) w[d.off[d.K - 1] + i] = -w[d.off[d.K - 1] + i];
+  ops.h2d(wdev, w, sizeof(double) * (size_t)d.sum);
+  return true;
+}
+// <W_g, W_h> = prod_k w_g^(k) . w_h^(k); wall: component g at g * d.sum
+double npls_ww(const NplsDims &d, const double *wall, int g, int h) {
+  double p = 1.0;
+  for (int k = 0; k < d.K; k++) p *= dotn(wall + g * d.sum + d.off[k], wall + h * d.sum + d.off[k], d.ext[k]);
+  return p;
+}
+}  // namespace
+
+void tensor_contract_mode(Ops &ops, const TensorDesc &V, int mode, const double *U_host, int C, double *Z_host) {
+  const PrepShape s = prep_shape(V, mode);
+  DevBuf U(ops, s.J * C), Z(ops, s.L * s.T * C);
+  ops.h2d(U.p, U_host, sizeof(double) * (size_t)(s.J * C));
+  ops.npls_contract(V.data, V.dtype, s.L, s.J, s.T, U.p, C, Z.p);
+  ops.d2h(Z_host, Z.p, sizeof(double) * (size_t)(s.L * s.T * C));
+}
+void tensor_slice_inner(Ops &ops, const TensorDesc &V, int mode, const double *W_host, int C, double *S_host) {
+  const PrepShape s = prep_shape(V, mode);
+  DevBuf W(ops, s.L * s.T * C), S(ops, s.J * C);
+  ops.h2d(W.p, W_host, sizeof(double) * (size_t)(s.L * s.T * C));
+  ops.npls_slice_inner(V.data, V.dtype, s.L, s.J, s.T, W.p, C, S.p);
+  ops.d2h(S_host, S.p, sizeof(double) * (size_t)(s.J * C));
+}
+
+void npls_fit(Ops &ops, const TensorDesc &X, int mode, const double *Y, int M, int F, const NplsOpts &o,
+              NplsModel *out) {
+  const PrepShape s = prep_shape(X, mode);
+  const int64_t I = s.J;
+  const NplsDims d(X.order, X.llens, mode);
+  const int64_t LT = d.LT;
+  NplsModel m;
+  m.order = X.order;
+  m.mode = mode;
+  m.M = M;
+  m.F = F;
+  for (int i = 0; i < X.order; i++) m.lens[i] = X.llens[i];
+  std::vector<double> T((size_t)I * F, 0.0), S((size_t)I * F, 0.0), Uy((size_t)I * F, 0.0), Q((size_t)M * F, 0.0);
+  std::vector<double> B((size_t)F * F, 0.0), wall((size_t)d.sum * F, 0.0), Yres(Y, Y + (size_t)I * M), q((size_t)M), qn((size_t)M);
+  const double normY2 = dotn(Y, Y, I * M);
+  double normX2 = 0;
+  {
+    std::vector<double> ss((size_t)I);
+    tensor_slice_sumsq(ops, X, mode, ss.data());
+    for (int64_t i = 0; i < I; i++) normX2 += ss[(size_t)i];
+  }
+  DevBuf dY(ops, I * M), dZm(ops, LT * M), dZ(ops, LT), dW(ops, LT), dwall(ops, d.sum * F), dE(ops, d.sum);
+  DevBuf dS(ops, std::max<int64_t>(std::max<int64_t>(I, M), std::max<int64_t>(d.sum, 2))), dq(ops, M);
+  int f = 0;
+  for (; f < F; f++) {
+    // 1. Z_m of the deflated tensor, without deflating
+    ops.h2d(dY.p, Yres.data(), sizeof(double) * Yres.size());
+    ops.npls_contract(X.data, X.dtype, s.L, I, s.T, dY.p, M, dZm.p);
+    for (int g = 0; g < f; g++)
+      for (int c = 0; c < M; c++) {
+        const double coef = dotn(&T[(size_t)I * g], &Yres[(size_t)I * c], I);
+        const double *w[MAX_ORDER];
+        for (int k = 0; k < d.K; k++) w[k] = dwall.p + g * d.sum + d.off[k];
+        if (coef != 0) ops.npls_outer_axpy(dZm.p + LT * c, d.ext, d.K, w, -coef);
+      }
+    // 2. q = e_m*, the column of Y_res with the largest sum of squares
+    int best = 0;
+    double bestss = -1;
+    for (int c = 0; c < M; c++) {
+      const double ss = dotn(&Yres[(size_t)I * c], &Yres[(size_t)I * c], I);
+      if (ss > bestss) {
+        bestss = ss;
+        best = c;
+      }
+    }
+    std::fill(q.begin(), q.end(), 0.0);
+    q[(size_t)best] = 1.0;
+    double *w = &wall[(size_t)d.sum * f], *wdev = dwall.p + d.sum * f;
+    int status = 0;
+    bool ok = true;
+    for (int round = 0;; round++) {
+      // 3. Z = sum_m q_m Z_m and its best rank-one approximation
+      const double *Zp = dZm.p;
+      if (M > 1) {
+        ops.h2d(dq.p, q.data(), sizeof(double) * (size_t)M);
+        ops.npls_contract(dZm.p, F64, LT, M, 1, dq.p, 1, dZ.p);
+        Zp = dZ.p;
+      }
+      bool capped = false;
+      ok = npls_rank_one(ops, d, Zp, o, w, wdev, dW.p, dS.p, dE.p, &capped);
+      if (!ok) break;
+      status = (status & ~1) | (capped ? 1 : 0);
+      npls_outer(ops, d, wdev, -1, dW.p);
+      // 4. q'_m = <Z_m, W>, normalised
+      ops.npls_slice_inner(dZm.p, F64, LT, M, 1, dW.p, 1, dS.p);
+      ops.d2h(qn.data(), dS.p, sizeof(double) * (size_t)M);
+      if (!normalise(qn.data(), M)) {
+        ok = false;
+        break;
+      }
+      double moved = 0;
+      for (int c = 0; c < M; c++) moved = std::max(moved, std::fabs(qn[(size_t)c] - q[(size_t)c]));
+      q = qn;
+      if (M == 1 || moved <= o.inner_tol) break;
+      if (round + 1 >= o.inner_max) {
+        status |= 2;
+        break;
+      }
+    }
+    if (!ok) break;
+    // 5. the raw scores, one pass; t_f of the deflated tensor from them
+    ops.npls_slice_inner(X.data, X.dtype, s.L, I, s.T, dW.p, 1, dS.p);
+    ops.d2h(&S[(size_t)I * f], dS.p, sizeof(double) * (size_t)I);
+    std::copy(&S[(size_t)I * f], &S[(size_t)I * f] + I, &T[(size_t)I * f]);
+    for (int g = 0; g < f; g++) {
+      const double ww = npls_ww(d, wall.data(), g, f);
+      for (int64_t i = 0; i < I; i++) T[(size_t)(i + I * f)] -= T[(size_t)(i + I * g)] * ww;
+    }
+    // 6. inner relation and the residual of Y
+    for (int c = 0; c < M; c++) Q[(size_t)(c + M * f)] = q[(size_t)c];
+    for (int64_t i = 0; i < I; i++) {
+      double u = 0;
+      for (int c = 0; c < M; c++) u += Yres[(size_t)(i + I * c)] * q[(size_t)c];
+      Uy[(size_t)(i + I * f)] = u;
+    }
+    const int n = f + 1;
+    std::vector<double> G((size_t)n * n), b((size_t)n);
+    for (int g = 0; g < n; g++) {
+      for (int h = 0; h < n; h++) G[g + (size_t)n * h] = dotn(&T[(size_t)I * g], &T[(size_t)I * h], I);
+      b[(size_t)g] = dotn(&T[(size_t)I * g], &Uy[(size_t)I * f], I);
+    }
+    std::vector<double> TtT = G;
+    solve_small(G, b, n);
+    for (int g = 0; g < n; g++) B[g + (size_t)F * f] = b[(size_t)g];
+    Yres.assign(Y, Y + (size_t)I * M);
+    for (int h = 0; h < n; h++)
+      for (int g = 0; g <= h; g++) {
+        const double bgh = B[g + (size_t)F * h];
+        if (bgh == 0) continue;
+        for (int c = 0; c < M; c++) {
+          const double bq = bgh * Q[(size_t)(c + M * h)];
+          for (int64_t i = 0; i < I; i++) Yres[(size_t)(i + I * c)] -= T[(size_t)(i + I * g)] * bq;
+        }
+      }
+    // 7. explained variation
+    m.ssy.push_back(1.0 - dotn(Yres.data(), Yres.data(), I * M) / normY2);
+    double res = normX2;
+    for (int g = 0; g < n; g++) {
+      res -= 2.0 * dotn(&T[(size_t)I * g], &S[(size_t)I * g], I);
+      for (int h = 0; h < n; h++) res += TtT[g + (size_t)n * h] * npls_ww(d, wall.data(), g, h);
+    }
+    m.ssx.push_back(1.0 - res / normX2);
+    m.status.push_back(status);
+  }
+  m.nf = f;
+  m.T.assign(T.begin(), T.begin() + (size_t)I * f);
+  m.U.assign(Uy.begin(), Uy.begin() + (size_t)I * f);
+  m.Q.assign(Q.begin(), Q.begin() + (size_t)M * f);
+  m.B.assign((size_t)f * f, 0.0);
+  for (int g = 0; g < f; g++)
+    for (int h = 0; h < f; h++) m.B[g + (size_t)f * h] = B[g + (size_t)F * h];
+  m.W.resize((size_t)d.K);
+  for (int k = 0; k < d.K; k++) {
+    m.W[(size_t)k].resize((size_t)d.ext[k] * f);
+    for (int g = 0; g < f; g++)
+      std::copy(&wall[(size_t)(d.sum * g + d.off[k])], &wall[(size_t)(d.sum * g + d.off[k])] + d.ext[k],
+                &m.W[(size_t)k][(size_t)d.ext[k] * g]);
+  }
+  *out = std::move(m);
+}
+
+void npls_predict(Ops &ops, const NplsModel &m, const TensorDesc &Xnew, int ncomp, double *Yhat, double *Tnew) {
+  const PrepShape s = prep_shape(Xnew, m.mode);
+  const int64_t I = s.J;
+  const NplsDims d(m.order, m.lens, m.mode);
+  const int k = ncomp;
+  std::vector<double> wall((size_t)d.sum * k);
+  for (int g = 0; g < k; g++)
+    for (int j = 0; j < d.K; j++)
+      std::copy(&m.W[(size_t)j][(size_t)d.ext[j] * g], &m.W[(size_t)j][(size_t)d.ext[j] * g] + d.ext[j],
+                &wall[(size_t)(d.sum * g + d.off[j])]);
+  DevBuf dwall(ops, d.sum * k), dW(ops, d.LT * k), dS(ops, I * k);
+  ops.h2d(dwall.p, wall.data(), sizeof(double) * wall.size());
+  for (int g = 0; g < k; g++) npls_outer(ops, d, dwall.p + d.sum * g, -1, dW.p + d.LT * g);
+  ops.npls_slice_inner(Xnew.data, Xnew.dtype, s.L, I, s.T, dW.p, k, dS.p);
+  std::vector<double> T((size_t)I * k);
+  ops.d2h(T.data(), dS.p, sizeof(double) * T.size());
+  for (int f = 0; f < k; f++)
+    for (int g = 0; g < f; g++) {
+      const double ww = npls_ww(d, wall.data(), g, f);
+      for (int64_t i = 0; i < I; i++) T[(size_t)(i + I * f)] -= T[(size_t)(i + I * g)] * ww;
+    }
+  if (Tnew) std::copy(T.begin(), T.end(), Tnew);
+  std::fill(Yhat, Yhat + (size_t)I * m.M, 0.0);
+  for (int h = 0; h < k; h++)
+    for (int g = 0; g <= h; g++) {
+      const double bgh = m.B[g + (size_t)m.nf * h];
+      if (bgh == 0) continue;
+      for (int c = 0; c < m.M; c++) {
+        const double bq = bgh * m.Q[(size_t)(c + m.M * h)];
+        for (int64_t i = 0; i < I; i++) Yhat[(size_t)(i + I * c)] += T[(size_t)(i + I * g)] * bq;
+      }
+    }
+}
+
 // ============================================================================ CpEngine
 // total columns of a session: nstarts * R, or the sum of the starts' own ranks
 static int total_columns(int R, int nstarts, const int *ranks) {

@@ -97,6 +97,39 @@ void tensor_rescale(Ops &ops, const TensorDesc &V, int mode, const double *facto
 // slice then stays bit for bit); rms_host (lens[mode] doubles, may be nullptr) receives rms as computed
 void tensor_scale(Ops &ops, const TensorDesc &V, int mode, double *rms_host);
 
+// N-PLS regression (ppals_npls_fit / _predict; Bro, J. Chemometrics 10 (1996) 47-61; one rank). The tensor is only
+// read, through Ops::npls_contract / npls_slice_inner on its primary layout: the deflated tensor is never formed.
+// Z[l,t,c] = sum_i X[l,i,t] U[i,c] and S[i,c] = sum_{l,t} X[l,i,t] W[l,t,c] with host arrays (column-major)
+void tensor_contract_mode(Ops &ops, const TensorDesc &V, int mode, const double *U_host, int C, double *Z_host);
+void tensor_slice_inner(Ops &ops, const TensorDesc &V, int mode, const double *W_host, int C, double *S_host);
+struct NplsOpts {
+  double hopm_tol = 1e-12;
+  int hopm_max = 500;
+  double inner_tol = 1e-12;
+  int inner_max = 200;
+};
+// everything on the host, column-major; nf <= F components were fitted (a zero or non-finite Z ends the fit)
+struct NplsModel {
+  int order = 0, mode = 0, M = 0, F = 0, nf = 0;
+  int64_t lens[MAX_ORDER];             // the training extents
+  std::vector<double> T, U;            // I x nf: scores of X and of Y
+  std::vector<std::vector<double>> W;  // the order - 1 modes off the sample mode, in order: lens x nf, unit columns
+  std::vector<double> Q, B;            // M x nf; nf x nf, upper triangular
+  std::vector<double> ssx, ssy;        // nf: explained variation, cumulative (ssx is a difference: it loses
+                                       // digits when the residual is tiny)
+  std::vector<int> status;             // nf: bit 0 HOPM ran into hopm_max, bit 1 the loop over q into inner_max
+  int64_t slice_size() const {
+    int64_t n = 1;
+    for (int i = 0; i < order; i++)
+      if (i != mode) n *= lens[i];
+    return n;
+  }
+};
+void npls_fit(Ops &ops, const TensorDesc &X, int mode, const double *Y, int M, int F, const NplsOpts &o,
+              NplsModel *out);
+// Yhat: Inew x M from the first ncomp components; Tnew: Inew x ncomp (may be nullptr)
+void npls_predict(Ops &ops, const NplsModel &m, const TensorDesc &Xnew, int ncomp, double *Yhat, double *Tnew);
+
 struct CpOpts {
   double tol = 0, timelimit = 5e3;
   int maxiter = 0;

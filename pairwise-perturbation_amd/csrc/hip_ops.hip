@@ -34,6 +34,7 @@
 #include "kernels_parafac2.hip.h"
 #include "kernels_bf16.hip.h"
 #include "kernels_prep.hip.h"
+#include "kernels_npls.hip.h"
 
 namespace ppals {
 #define HIP_CHECK(expr)                                                                       \
@@ -1001,6 +1002,178 @@ class HipOps : public Ops {
       sumsq_typed((const bf16s *)V, L, J, T, ss);
     else
       sumsq_typed((const double *)V, L, J, T, ss);
+  }
+
+  // ------------------------------------------------------------------ N-PLS (kernels_npls.hip.h)
+  // The route rule, a plain formula on (dt, L, I) and the base alignment; nothing in it looks at
+  // the number of columns, so that a column has the same bits in whatever chunk it travels:
+  //   contract:    L < 64 and one t (L * I * size) within the 32 KiB run buffer: runs; beyond it long for L == 1;
+  //                everything else rows, vec = L % VEC == 0 and X aligned to VEC elements (VEC = 4, 2, 4 for f32,
+  //                f64, bf16).
+  //   slice_inner: L < 64: flat; else rows, vec = L % V16 == 0 and X aligned to 16 bytes (V16 = 4, 2, 8).
+  template <typename TV, int CW>
+  void npls_contract_chunk(const TV *X, int64_t L, int64_t I, int64_t T, const double *U, int nc, double *Z) {
+    const int64_t run_bytes = L * I * (int64_t)sizeof(TV);
+    if (L < NPLS_FLAT_L && run_bytes <= NPLS_RUN_BYTES) {
+      int64_t NT = std::max<int64_t>(1, NPLS_RUN_BYTES / run_bytes);
+      NT = std::min(NT, std::max<int64_t>(1, (T + 4 * ncu_ - 1) / (4 * (int64_t)ncu_)));
+      const int64_t F = NT * L;
+      const int G = F >= PREP_THREADS ? 1 : std::min(pow2_floor(PREP_THREADS / F), pow2_ceil(I, PREP_THREADS));
+      const int64_t nruns = (T + NT - 1) / NT;
+      const int ulds = I * NPLS_CW * (int64_t)sizeof(double) <= NPLS_ULDS_BYTES ? 1 : 0;  // (of a full chunk: not of C)
+      const size_t lds = 8 * (size_t)PREP_THREADS * CW + (ulds ? 8 * (size_t)((CW * I + 1) / 2 * 2) : 0) +
+                         (size_t)(PrepVec16<TV>::N + NT * L * I) * sizeof(TV);
+      route("npls.contract.%s.runs NT=%lld G=%d ulds=%d", sname<TV>(), (long long)NT, G, ulds);
+      hipLaunchKernelGGL((k_npls_contract_runs<TV, CW>), dim3((unsigned)std::min<int64_t>(nruns, 16384)), dim3(PREP_THREADS),
+                         (lds + 15) / 16 * 16, st_, X, (int)L, (int)I, T, (int)NT, G, U, nc, ulds, Z);
+    } else if (L == 1) {
+      route("npls.contract.%s.long", sname<TV>());
+      hipLaunchKernelGGL((k_npls_contract_long<TV, CW>), dim3((unsigned)std::min<int64_t>(T, 16384)), dim3(PREP_THREADS),
+                         8 * PREP_THREADS, st_, X, I, T, U, nc, Z);
+    } else {
+      constexpr int VEC = PrepRowsVec<TV>::N;
+      const bool vec = L % VEC == 0 && (uintptr_t)X % (VEC * sizeof(TV)) == 0;
+      const int64_t n = (vec ? L / VEC : L) * T, LT = L * T, blocks = (n + PREP_THREADS - 1) / PREP_THREADS;
+      // too few threads for the device and a long i: ns splits of i (at least 32 i each, the partial sums of a full
+      // chunk within 64 MB), folded in split order
+      int64_t ns = 1;
+      if (blocks < 4 * (int64_t)ncu_ && I >= 64) {
+        ns = std::min<int64_t>((4 * (int64_t)ncu_ + blocks - 1) / blocks, I / 32);
+        ns = std::min(ns, std::max<int64_t>(1, ((int64_t)64 << 20) / (8 * LT * NPLS_CW)));
+        ns = std::min<int64_t>(ns, 65535);
+      }
+      const dim3 grid((unsigned)std::min<int64_t>(blocks, 262144), (unsigned)ns);
+      double *out = ns > 1 ? (double *)ensure(ws_part_, ws_part_sz_, sizeof(double) * (size_t)ns * CW * LT) : Z;
+      const int64_t sstride = ns > 1 ? CW * LT : 0;
+      route("npls.contract.%s.rows vec=%d ns=%lld", sname<TV>(), vec ? 1 : 0, (long long)ns);
+      if (vec)
+        hipLaunchKernelGGL((k_npls_contract_rows<TV, VEC, CW>), grid, dim3(PREP_THREADS), 0, st_, X, L, I, T, U, nc, out, LT,
+                           sstride);
+      else
+        hipLaunchKernelGGL((k_npls_contract_rows<TV, 1, CW>), grid, dim3(PREP_THREADS), 0, st_, X, L, I, T, U, nc, out, LT,
+                           sstride);
+      if (ns > 1)
+        hipLaunchKernelGGL(k_npls_fold, dim3(grid_for(LT, 256)), dim3(256), 0, st_, out, (int)ns, CW, (int64_t)1, LT, nc, Z);
+    }
+  }
+  // nb blocks a row of partial sums: enough for ~8 workgroups a CU, no more than there are rows of t, the partial
+  // sums of a full chunk capped at 64 MB
+  int64_t npls_nb(int64_t gx, int64_t rows, int64_t T, int Y) {
+    int64_t nb = std::max<int64_t>(1, (8 * (int64_t)ncu_ + gx - 1) / gx);
+    nb = std::min(nb, (T + Y - 1) / Y);
+    nb = std::min(nb, std::max<int64_t>(1, ((int64_t)64 << 20) / (8 * rows * NPLS_CW)));
+    return std::min<int64_t>(nb, 65535);
+  }
+  template <typename TV, int CW>
+  void npls_si_chunk(const TV *X, int64_t L, int64_t I, int64_t T, const double *W, int nc, double *S) {
+    if (L < NPLS_FLAT_L) {
+      const int64_t J = L * I;
+      const int XL = pow2_ceil(J, PREP_THREADS), Y = PREP_THREADS / XL;
+      const int64_t gx = (J + XL - 1) / XL, nb = npls_nb(gx, J, T, Y);
+      if (gx > 0x7fffffff) throw Unsupported("ppals: slice_inner supports at most 2^31 - 1 rows of partial sums");
+      double *part = (double *)ensure(ws_part_, ws_part_sz_, sizeof(double) * (size_t)nb * CW * J);
+      route("npls.slice_inner.%s.flat X=%d nb=%lld", sname<TV>(), XL, (long long)nb);
+      hipLaunchKernelGGL((k_npls_si_flat<TV, CW>), dim3((unsigned)gx, (unsigned)nb), dim3(PREP_THREADS),
+                         8 * PREP_THREADS * CW, st_, X, L, J, T, XL, W, nc, part);
+      hipLaunchKernelGGL(k_npls_fold, dim3(grid_for(I, 256)), dim3(256), 0, st_, part, (int)nb, CW, L, I, nc, S);
+      return;
+    }
+    constexpr int VEC = PrepVec16<TV>::N;
+    const bool vec = L % VEC == 0 && (uintptr_t)X % 16 == 0;
+    const int64_t Lv = vec ? L / VEC : L;
+    const int XL = pow2_ceil(Lv, PREP_THREADS), Y = PREP_THREADS / XL;
+    const int64_t gx = (I + NPLS_IB - 1) / NPLS_IB, nbt = npls_nb(gx, I, T, Y);
+    // where the rows of t leave the device short of work (T = 1: the sample mode last), the blocks split l as well
+    int64_t nbl = 1;
+    if (gx * nbt < 8 * (int64_t)ncu_) {
+      nbl = std::min<int64_t>((8 * (int64_t)ncu_ + gx * nbt - 1) / (gx * nbt), (Lv + XL - 1) / XL);
+      nbl = std::min(nbl, std::max<int64_t>(1, ((int64_t)64 << 20) / (8 * I * NPLS_CW * nbt)));
+      nbl = std::max<int64_t>(1, std::min<int64_t>(nbl, 65535 / nbt));
+    }
+    const int64_t nb = nbt * nbl;
+    if (gx > 0x7fffffff) throw Unsupported("ppals: slice_inner supports at most 2^33 - 4 slices");
+    double *part = (double *)ensure(ws_part_, ws_part_sz_, sizeof(double) * (size_t)nb * CW * I);
+    route("npls.slice_inner.%s.rows vec=%d X=%d nbt=%lld nbl=%lld", sname<TV>(), vec ? 1 : 0, XL, (long long)nbt, (long long)nbl);
+    const dim3 grid((unsigned)gx, (unsigned)nb);
+    if (vec)
+      hipLaunchKernelGGL((k_npls_si_rows<TV, VEC, CW>), grid, dim3(PREP_THREADS), 8 * PREP_THREADS, st_, X, L, I, T, XL,
+                         (int)nbl, W, nc, part);
+    else
+      hipLaunchKernelGGL((k_npls_si_rows<TV, 1, CW>), grid, dim3(PREP_THREADS), 8 * PREP_THREADS, st_, X, L, I, T, XL,
+                         (int)nbl, W, nc, part);
+    hipLaunchKernelGGL(k_npls_fold, dim3(grid_for(I, 256)), dim3(256), 0, st_, part, (int)nb, CW, (int64_t)1, I, nc, S);
+  }
+  // a single column goes alone, more in chunks of NPLS_CW
+  template <typename TV>
+  void npls_contract_typed(const TV *X, int64_t L, int64_t I, int64_t T, const double *U, int C, double *Z) {
+    if (C == 1) npls_contract_chunk<TV, 1>(X, L, I, T, U, 1, Z);
+    else
+      for (int c0 = 0; c0 < C; c0 += NPLS_CW)
+        npls_contract_chunk<TV, NPLS_CW>(X, L, I, T, U + I * c0, std::min(NPLS_CW, C - c0), Z + L * T * c0);
+    HIP_CHECK(hipGetLastError());
+  }
+  template <typename TV>
+  void npls_si_typed(const TV *X, int64_t L, int64_t I, int64_t T, const double *W, int C, double *S) {
+    if (C == 1) npls_si_chunk<TV, 1>(X, L, I, T, W, 1, S);
+    else
+      for (int c0 = 0; c0 < C; c0 += NPLS_CW)
+        npls_si_chunk<TV, NPLS_CW>(X, L, I, T, W + L * T * c0, std::min(NPLS_CW, C - c0), S + I * c0);
+    HIP_CHECK(hipGetLastError());
+  }
+  void npls_contract(const void *X, int dt, int64_t L, int64_t I, int64_t T, const double *U, int C, double *Z) override {
+    if (L * T <= 0 || C <= 0) return;
+    if (I <= 0) {
+      zero(Z, sizeof(double) * L * T * C);
+      return;
+    }
+    // (profile slot 0, with the tensor scans: the bytes a chunk reads, once per chunk)
+    prof_begin(0, (double)L * I * T * dtype_size(dt) * (C == 1 ? 1 : (C + NPLS_CW - 1) / NPLS_CW));
+    if (dt == F32)
+      npls_contract_typed((const float *)X, L, I, T, U, C, Z);
+    else if (dt == BF16)
+      npls_contract_typed((const bf16s *)X, L, I, T, U, C, Z);
+    else
+      npls_contract_typed((const double *)X, L, I, T, U, C, Z);
+    prof_end();
+  }
+  void npls_slice_inner(const void *X, int dt, int64_t L, int64_t I, int64_t T, const double *W, int C, double *S) override {
+    if (I <= 0 || C <= 0) return;
+    if (L * T <= 0) {
+      zero(S, sizeof(double) * I * C);
+      return;
+    }
+    prof_begin(0, (double)L * I * T * dtype_size(dt) * (C == 1 ? 1 : (C + NPLS_CW - 1) / NPLS_CW));
+    if (dt == F32)
+      npls_si_typed((const float *)X, L, I, T, W, C, S);
+    else if (dt == BF16)
+      npls_si_typed((const bf16s *)X, L, I, T, W, C, S);
+    else
+      npls_si_typed((const double *)X, L, I, T, W, C, S);
+    prof_end();
+  }
+  void npls_outer_axpy(double *A, const int64_t *ext, int K, const double *const *w, double alpha) override {
+    if (K < 1 || K > NPLS_MAX_DIMS) throw Unsupported("ppals: outer_axpy takes 1 to 8 vectors");
+    NplsOuter o;
+    o.K = K;
+    int64_t n = 1;
+    for (int k = 0; k < K; k++) {
+      o.ext[k] = ext[k];
+      o.w[k] = w[k];
+      n *= ext[k];
+    }
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_npls_outer_axpy, dim3(grid_for(n, 256, 16384)), dim3(256), 0, st_, A, n, o, alpha);
+    HIP_CHECK(hipGetLastError());
+  }
+  void npls_argmax(const double *Z, int64_t n, double *out) override {
+    if (n <= 0) return;
+    const int np = grid_for(n, PREP_THREADS, 1024);
+    char *ws = (char *)ensure(ws_part_, ws_part_sz_, 16 * (size_t)np);
+    double *pv = (double *)ws;
+    int64_t *pi = (int64_t *)(ws + 8 * (size_t)np);
+    hipLaunchKernelGGL(k_npls_argmax_part, dim3(np), dim3(PREP_THREADS), 0, st_, Z, n, pv, pi);
+    hipLaunchKernelGGL(k_npls_argmax_fold, dim3(1), dim3(PREP_THREADS), 0, st_, pv, pi, np, n, out);
+    HIP_CHECK(hipGetLastError());
   }
 
   // ------------------------------------------------------------------ model through a view

@@ -412,6 +412,83 @@ class Ops {
     h2d(V, h.data(), h.size());
   }
 
+  // ---- N-PLS (ppals_npls_fit / _predict, ppals_tensor_contract_mode / _slice_inner) ----
+  // X (storage type dt, or an fp64 work array with dt = F64) viewed as [L, I, T], first index fastest, and only
+  // read. Elements are widened to fp64 as stored, sums are formed in fp64 in a fixed order (no atomics), and column
+  // c of a C-column call has the bits of that column computed alone. All pointers are device memory. The defaults
+  // are the fp64 host twins built from d2h / h2d; the product back end overrides them with its kernels.
+  //   npls_contract:     Z[l + L*t + L*T*c] = sum_i X[l,i,t] U[i + I*c]
+  //   npls_slice_inner:  S[i + I*c] = sum_{l,t} X[l,i,t] W[l + L*t + L*T*c]
+  //   npls_outer_axpy:   A[e] += alpha prod_k w[k][e_k], A of order K (1..8) with extents ext, first index fastest
+  //   npls_argmax:       out[0] = max |Z[e]| (a non-finite entry counts as +inf), out[1] = its first index
+  virtual void npls_contract(const void *X, int dt, int64_t L, int64_t I, int64_t T, const double *U, int C, double *Z) {
+    if (L * T <= 0 || C <= 0) return;
+    const size_t n = (size_t)L * I * T, LT = (size_t)L * T;
+    std::vector<char> h(n * dtype_size(dt));
+    std::vector<double> u((size_t)I * C), z(LT * C, 0.0);
+    d2h(h.data(), X, h.size());
+    d2h(u.data(), U, sizeof(double) * u.size());
+    for (int c = 0; c < C; c++)
+      for (int64_t t = 0; t < T; t++)
+        for (int64_t i = 0; i < I; i++)
+          for (int64_t l = 0; l < L; l++)
+            z[(size_t)(l + L * t) + LT * c] += prep_load(h.data(), dt, (size_t)(l + L * (i + I * t))) * u[(size_t)i + (size_t)I * c];
+    h2d(Z, z.data(), sizeof(double) * z.size());
+  }
+  virtual void npls_slice_inner(const void *X, int dt, int64_t L, int64_t I, int64_t T, const double *W, int C, double *S) {
+    if (I <= 0 || C <= 0) return;
+    const size_t n = (size_t)L * I * T, LT = (size_t)L * T;
+    std::vector<char> h(n * dtype_size(dt));
+    std::vector<double> w(LT * C), s((size_t)I * C, 0.0);
+    d2h(h.data(), X, h.size());
+    d2h(w.data(), W, sizeof(double) * w.size());
+    for (int c = 0; c < C; c++)
+      for (int64_t t = 0; t < T; t++)
+        for (int64_t i = 0; i < I; i++)
+          for (int64_t l = 0; l < L; l++)
+            s[(size_t)i + (size_t)I * c] += prep_load(h.data(), dt, (size_t)(l + L * (i + I * t))) * w[(size_t)(l + L * t) + LT * c];
+    h2d(S, s.data(), sizeof(double) * s.size());
+  }
+  virtual void npls_outer_axpy(double *A, const int64_t *ext, int K, const double *const *w, double alpha) {
+    if (K < 1 || K > MAX_ORDER) throw Unsupported("ppals: outer_axpy takes 1 to 8 vectors");
+    size_t n = 1;
+    std::vector<std::vector<double>> hw((size_t)K);
+    for (int k = 0; k < K; k++) {
+      n *= (size_t)ext[k];
+      hw[(size_t)k].resize((size_t)ext[k]);
+      d2h(hw[(size_t)k].data(), w[k], sizeof(double) * (size_t)ext[k]);
+    }
+    if (n == 0) return;
+    std::vector<double> a(n);
+    d2h(a.data(), A, sizeof(double) * n);
+    for (size_t e = 0; e < n; e++) {
+      size_t rem = e;
+      double p = 1.0;
+      for (int k = 0; k < K; k++) {
+        const size_t ik = rem % (size_t)ext[k];
+        rem /= (size_t)ext[k];
+        p = k == 0 ? hw[0][ik] : p * hw[(size_t)k][ik];
+      }
+      a[e] += alpha * p;
+    }
+    h2d(A, a.data(), sizeof(double) * n);
+  }
+  virtual void npls_argmax(const double *Z, int64_t n, double *out) {
+    if (n <= 0) return;
+    std::vector<double> z((size_t)n);
+    d2h(z.data(), Z, sizeof(double) * z.size());
+    double o[2] = {-1.0, 0.0};
+    for (int64_t e = 0; e < n; e++) {
+      double a = std::fabs(z[(size_t)e]);
+      if (!(a <= std::numeric_limits<double>::max())) a = std::numeric_limits<double>::infinity();
+      if (a > o[0]) {
+        o[0] = a;
+        o[1] = (double)e;
+      }
+    }
+    h2d(out, o, sizeof(o));
+  }
+
   // ---- Khatri-Rao product, plain: out[j + J*c] = prod_f W_f[j_f + ld_f*(col0+c)], fp64 ----
   virtual void krp(double *out, const FactorRef *f, int nf, int col0, int ncols) = 0;
 

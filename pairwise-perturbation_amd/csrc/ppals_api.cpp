@@ -447,6 +447,131 @@ int ppals_tensor_rescale(ppals_tensor *t, int mode, const double *factors) {
   API_END(PPALS_ERR_HIP)
 }
 
+// ------------------------------------------------------------------ N-PLS regression
+// (the tensor is only read: nothing is bumped; the checks of the handle, the mode and the ranks are prep_check's)
+struct ppals_npls {
+  NplsModel m;
+};
+static int npls_check_finite(const double *a, int64_t n, const char *fn, const char *name) {
+  for (int64_t i = 0; i < n; i++)
+    if (!std::isfinite(a[i]))
+      return fail_fn(PPALS_ERR_ARG, fn, (std::string(name) + "[" + std::to_string(i) + "] is not finite").c_str());
+  return PPALS_OK;
+}
+int ppals_tensor_contract_mode(ppals_tensor *t, int mode, const double *U, int C, double *Z) {
+  static const char *fn = "ppals_tensor_contract_mode";
+  API_BEGIN
+  const int rc = prep_check(t, mode, fn);
+  if (rc != PPALS_OK) return rc;
+  if (!U || !Z) return fail_fn(PPALS_ERR_ARG, fn, "U or Z is NULL");
+  if (C < 1) return fail_fn(PPALS_ERR_ARG, fn, "C must be at least 1");
+  tensor_contract_mode(*t->ctx->ops, t->d, mode, U, C, Z);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_tensor_slice_inner(ppals_tensor *t, int mode, const double *W, int C, double *S) {
+  static const char *fn = "ppals_tensor_slice_inner";
+  API_BEGIN
+  const int rc = prep_check(t, mode, fn);
+  if (rc != PPALS_OK) return rc;
+  if (!W || !S) return fail_fn(PPALS_ERR_ARG, fn, "W or S is NULL");
+  if (C < 1) return fail_fn(PPALS_ERR_ARG, fn, "C must be at least 1");
+  tensor_slice_inner(*t->ctx->ops, t->d, mode, W, C, S);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_npls_fit(ppals_tensor *X, int mode, const double *Y, int M, int F, const ppals_npls_opts *opts,
+                   ppals_npls **out) {
+  static const char *fn = "ppals_npls_fit";
+  if (out) *out = nullptr;
+  API_BEGIN
+  int rc = prep_check(X, mode, fn);
+  if (rc != PPALS_OK) return rc;
+  if (!Y || !out) return fail_fn(PPALS_ERR_ARG, fn, "Y or out is NULL");
+  if (X->d.order < 2) return fail_fn(PPALS_ERR_ARG, fn, "the tensor must have at least two modes");
+  if (M < 1) return fail_fn(PPALS_ERR_ARG, fn, "M must be at least 1");
+  const int64_t I = X->d.llens[mode];
+  if (F < 1 || F > I)
+    return fail_fn(PPALS_ERR_ARG, fn, ("F = " + std::to_string(F) + " is outside [1, " + std::to_string(I) +
+                                       "], the number of samples").c_str());
+  NplsOpts o;
+  if (opts) {
+    o.hopm_tol = opts->hopm_tol;
+    o.hopm_max = opts->hopm_max;
+    o.inner_tol = opts->inner_tol;
+    o.inner_max = opts->inner_max;
+    if (!(o.hopm_tol >= 0) || !(o.inner_tol >= 0)) return fail_fn(PPALS_ERR_ARG, fn, "a tolerance is negative or NaN");
+    if (o.hopm_max < 1 || o.inner_max < 1) return fail_fn(PPALS_ERR_ARG, fn, "hopm_max and inner_max must be at least 1");
+  }
+  rc = npls_check_finite(Y, I * M, fn, "Y");
+  if (rc != PPALS_OK) return rc;
+  std::unique_ptr<ppals_npls> m(new ppals_npls);
+  npls_fit(*X->ctx->ops, X->d, mode, Y, M, F, o, &m->m);
+  *out = m.release();
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+void ppals_npls_destroy(ppals_npls *m) { delete m; }
+int ppals_npls_dims(const ppals_npls *m, int *order, int *mode, int64_t *lens, int *M, int *wanted, int *fitted) {
+  if (!m) return fail_fn(PPALS_ERR_ARG, "ppals_npls_dims", "NULL model");
+  if (order) *order = m->m.order;
+  if (mode) *mode = m->m.mode;
+  if (lens)
+    for (int i = 0; i < m->m.order; i++) lens[i] = m->m.lens[i];
+  if (M) *M = m->m.M;
+  if (wanted) *wanted = m->m.F;
+  if (fitted) *fitted = m->m.nf;
+  return PPALS_OK;
+}
+int ppals_npls_get(const ppals_npls *m, int what, double *out, int64_t *n) {
+  static const char *fn = "ppals_npls_get";
+  if (!m) return fail_fn(PPALS_ERR_ARG, fn, "NULL model");
+  API_BEGIN
+  const NplsModel &d = m->m;
+  std::vector<double> st;
+  const std::vector<double> *src = nullptr;
+  switch (what) {
+    case PPALS_NPLS_T: src = &d.T; break;
+    case PPALS_NPLS_U: src = &d.U; break;
+    case PPALS_NPLS_Q: src = &d.Q; break;
+    case PPALS_NPLS_B: src = &d.B; break;
+    case PPALS_NPLS_SSX: src = &d.ssx; break;
+    case PPALS_NPLS_SSY: src = &d.ssy; break;
+    case PPALS_NPLS_STATUS:
+      st.assign(d.status.begin(), d.status.end());
+      src = &st;
+      break;
+    default:
+      if (what >= PPALS_NPLS_W && what < PPALS_NPLS_W + d.order - 1) src = &d.W[(size_t)(what - PPALS_NPLS_W)];
+  }
+  if (!src) return fail_fn(PPALS_ERR_ARG, fn, ("there is no array " + std::to_string(what)).c_str());
+  if (n) *n = (int64_t)src->size();
+  if (out && !src->empty()) std::memcpy(out, src->data(), sizeof(double) * src->size());
+  return PPALS_OK;
+  API_END(PPALS_ERR_ARG)
+}
+int ppals_npls_predict(const ppals_npls *m, ppals_tensor *Xnew, int ncomp, double *Yhat, double *Tnew) {
+  static const char *fn = "ppals_npls_predict";
+  API_BEGIN
+  if (!m) return fail_fn(PPALS_ERR_ARG, fn, "NULL model");
+  const int rc = prep_check(Xnew, m->m.mode, fn);  // (the mode is the model's: in range whenever the orders agree)
+  if (rc != PPALS_OK && (!Xnew || !Xnew->ctx || Xnew->d.order == m->m.order)) return rc;
+  if (Xnew->d.order != m->m.order)
+    return fail_fn(PPALS_ERR_ARG, fn, ("the tensor has " + std::to_string(Xnew->d.order) + " modes, the model " +
+                                       std::to_string(m->m.order)).c_str());
+  for (int i = 0; i < m->m.order; i++)
+    if (i != m->m.mode && Xnew->d.llens[i] != m->m.lens[i])
+      return fail_fn(PPALS_ERR_ARG, fn, ("mode " + std::to_string(i) + " has extent " + std::to_string(Xnew->d.llens[i]) +
+                                         ", the model's has " + std::to_string(m->m.lens[i])).c_str());
+  if (ncomp < 1 || ncomp > m->m.nf)
+    return fail_fn(PPALS_ERR_ARG, fn, ("ncomp = " + std::to_string(ncomp) + " is outside [1, " +
+                                       std::to_string(m->m.nf) + "], the components fitted").c_str());
+  if (!Yhat) return fail_fn(PPALS_ERR_ARG, fn, "Yhat is NULL");
+  npls_predict(*Xnew->ctx->ops, m->m, Xnew->d, ncomp, Yhat, Tnew);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+
 // ------------------------------------------------------------------ device views
 // every check of ppals_tensor_check_device_view; on success *a holds the resolved view
 // (`what` names the entry point in the messages; the model exports check their views here too)

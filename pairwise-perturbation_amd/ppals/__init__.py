@@ -82,6 +82,8 @@ EXPORTS = [
     "ppals_parafac2_create", "ppals_parafac2_destroy", "ppals_parafac2_cp", "ppals_parafac2_tensor",
     "ppals_parafac2_step_device",
     "ppals_parafac2_run", "ppals_parafac2_projections", "ppals_parafac2_projections_device",
+    "ppals_npls_fit", "ppals_npls_destroy", "ppals_npls_dims", "ppals_npls_get", "ppals_npls_predict",
+    "ppals_tensor_contract_mode", "ppals_tensor_slice_inner",
 ]
 HOST, DEVICE = 0, 1  # PPALS_HOST / PPALS_DEVICE: where the offsets of Tensor.center / Tensor.shift lie
 MODE_FREE, MODE_NONNEG, MODE_FIXED, MODE_ORTHO = 0, 1, 2, 3  # PPALS_MODE_*
@@ -478,6 +480,29 @@ class Tensor:
             raise PpalsError(f"{f.size} factors for {J} slices")
         _check(lib().ppals_tensor_rescale(self._h, mode, _dp(f)))
         return self
+
+    # ---- the two tensor passes of N-PLS (include/ppals.h, "N-PLS regression"): the tensor is only read ----
+    def contract_mode(self, mode, U):
+        """Z[..., c] = sum_i X[.., i, ..] U[i, c]: the tensor contracted over `mode` with the columns of U
+        (lens[mode] x C, or a vector). Returns an fp64 array of the tensor's shape without `mode`, C last."""
+        mode = int(mode)
+        L, I, T, _ = self._prep_shape(mode)
+        U2 = np.asfortranarray(np.asarray(U, dtype=np.float64).reshape(I, -1, order="F"))
+        Cn = U2.shape[1]
+        Z = np.empty(L * T * Cn, dtype=np.float64)
+        _check(lib().ppals_tensor_contract_mode(self._h, mode, _dp(U2), Cn, _dp(Z)))
+        return Z.reshape(self.lens[:mode] + self.lens[mode + 1:] + [Cn], order="F")
+
+    def slice_inner(self, mode, W):
+        """S[i, c] = <slice i of `mode`, W[..., c]>: W has the tensor's shape without `mode`, optionally with
+        C columns last. Returns lens[mode] x C (fp64)."""
+        mode = int(mode)
+        L, I, T, _ = self._prep_shape(mode)
+        W2 = np.asfortranarray(np.asarray(W, dtype=np.float64).reshape(L * T, -1, order="F"))
+        Cn = W2.shape[1]
+        S = np.empty((I, Cn), dtype=np.float64, order="F")
+        _check(lib().ppals_tensor_slice_inner(self._h, mode, _dp(W2), Cn, _dp(S)))
+        return S
 
     def close(self):
         if self._h:
@@ -1184,6 +1209,90 @@ def parafac2(X, R, n_iter=100, nonneg_modes=(), inner_sweeps=1, rel_change=0.0, 
         p2.close()
         if own:
             ctx.close()
+
+
+class _NplsOpts(C.Structure):
+    _fields_ = [("hopm_tol", C.c_double), ("hopm_max", C.c_int), ("inner_tol", C.c_double), ("inner_max", C.c_int)]
+
+
+NPLS_T, NPLS_U, NPLS_Q, NPLS_B, NPLS_SSX, NPLS_SSY, NPLS_STATUS, NPLS_W = 0, 1, 2, 3, 4, 5, 6, 16  # PPALS_NPLS_*
+
+
+def _host_matrix(Y):
+    """numpy, or a torch tensor on any device, as an fp64 Fortran-ordered I x M array on the host"""
+    if type(Y).__module__.split(".")[0] == "torch":
+        Y = Y.detach().cpu().numpy()
+    Y = np.asarray(Y, dtype=np.float64)
+    return np.asfortranarray(Y.reshape(Y.shape[0], -1) if Y.ndim != 2 else Y)
+
+
+class NPLS:
+    """N-PLS regression (multilinear PLS, Bro 1996) of Y (I x M) on the resident tensor, `mode` its sample mode;
+    both centred by the caller (Tensor.center). The tensor is only read: no copy, no deflation, live sessions are
+    undisturbed. After fit: scores (I x F), y_scores (I x F), weights (a lens x F matrix for every mode off the
+    sample mode), y_loadings (M x F), inner (F x F, upper triangular), ssx, ssy (cumulative explained variation) and
+    status (bit 0: the power iterations hit their cap, bit 1: the loop over q did). F may be smaller than ncomp:
+    the fit ends where nothing is left to explain."""
+
+    def __init__(self, hopm_tol=1e-12, hopm_max=500, inner_tol=1e-12, inner_max=200):
+        self._opts = _NplsOpts(hopm_tol, hopm_max, inner_tol, inner_max)
+        self._h = C.c_void_p()
+
+    def _get(self, what, shape):
+        n = C.c_int64(0)
+        _check(lib().ppals_npls_get(self._h, what, None, C.byref(n)))
+        out = np.empty(n.value, dtype=np.float64)
+        _check(lib().ppals_npls_get(self._h, what, _dp(out), C.byref(n)))
+        return out.reshape(shape, order="F")
+
+    def fit(self, tensor, Y, ncomp, mode=0):
+        self.close()
+        Yh = _host_matrix(Y)
+        mode = int(mode)
+        I = tensor.lens[mode] if 0 <= mode < len(tensor.lens) else Yh.shape[0]
+        if Yh.shape[0] != I:
+            raise PpalsError(f"Y has {Yh.shape[0]} rows, the sample mode {I}")
+        M = Yh.shape[1]
+        _check(lib().ppals_npls_fit(tensor._h, mode, _dp(Yh), M, int(ncomp), C.byref(self._opts), C.byref(self._h)))
+        fitted = C.c_int(0)
+        _check(lib().ppals_npls_dims(self._h, None, None, None, None, None, C.byref(fitted)))
+        F = fitted.value
+        self.mode, self.lens, self.ncomp, self.M = mode, list(tensor.lens), F, M
+        self.scores = self._get(NPLS_T, (I, F))
+        self.y_scores = self._get(NPLS_U, (I, F))
+        self.y_loadings = self._get(NPLS_Q, (M, F))
+        self.inner = self._get(NPLS_B, (F, F))
+        self.ssx, self.ssy = self._get(NPLS_SSX, (F,)), self._get(NPLS_SSY, (F,))
+        self.status = self._get(NPLS_STATUS, (F,)).astype(np.int64)
+        off = [n for i, n in enumerate(tensor.lens) if i != mode]
+        self.weights = [self._get(NPLS_W + k, (n, F)) for k, n in enumerate(off)]
+        return self
+
+    def predict(self, tensor, ncomp=None, return_scores=False):
+        """Yhat (I_new x M, numpy) for a tensor with the training extents off the sample mode, from the first ncomp
+        components (default: all): one pass over the tensor. return_scores: (Yhat, T_new)."""
+        k = self.ncomp if ncomp is None else int(ncomp)
+        I = tensor.lens[self.mode] if self.mode < len(tensor.lens) else 1
+        Yhat = np.empty((I, self.M), dtype=np.float64, order="F")
+        Tn = np.empty((I, max(k, 0)), dtype=np.float64, order="F")
+        _check(lib().ppals_npls_predict(self._h, tensor._h, k, _dp(Yhat), _dp(Tn)))
+        return (Yhat, Tn) if return_scores else Yhat
+
+    def close(self):
+        if self._h:
+            lib().ppals_npls_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def npls(tensor, Y, ncomp, mode=0, **opts):
+    """NPLS(**opts).fit(tensor, Y, ncomp, mode)"""
+    return NPLS(**opts).fit(tensor, Y, ncomp, mode)
 
 
 class CPMulti:
