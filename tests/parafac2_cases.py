@@ -90,9 +90,10 @@ def check_step(p, v, Xh, B, A, Cm, dt, what, P_prev=None, want_failed=0):
 
 def values(which):
     """step values and the identity for one shape: f32 and f64 views, F32 and F64 storage, padded slices for the
-    f64 storage"""
+    f64 storage. The shapes 5..7 have three and four rank tiles, and their inner CP session (residual, get_factors,
+    the loss identity) runs at ranks up to 64 on an R x J x K tensor."""
     i = int(which)
-    shape = ref.SHAPES[i]
+    shape = inputs.ALL_SHAPES[i]      # 0..4: ref.SHAPES; 5..7: ref.SHAPES_WIDE (three and four rank tiles of 16)
     X, B, A, Cm = inputs.values_inputs(i)
     ctx = pp.Context(0)
     for tdt, dt in COMBOS:
@@ -106,7 +107,7 @@ def values(which):
 def truth():
     """noise-free planted data and the planted factors: the step returns the planted P_k and loses nothing"""
     ctx = pp.Context(0)
-    for i, shape in enumerate(ref.SHAPES):
+    for i, shape in enumerate(inputs.ALL_SHAPES):
         X, B, A, Cm, P0 = inputs.truth_inputs(i)
         for dt in (pp.F32, pp.F64):
             v, Xh = view(X, torch.float64, padded=i % 2 == 0)

@@ -9,6 +9,14 @@ U = 2.0 ** -52
 SHAPES = ((23, 17, 5, 3), (70, 9, 6, 2), (16, 130, 4, 5), (9, 7, 33, 4), (40, 33, 5, 17))
 DRIVER = (30, 20, 12, 3)
 KAPPA_CAP = 1e5
+# the larger ranks (planted_wide / step_case_wide): the binding-level shapes, and the op-level table of
+# tests/parafac2_op_cases.py — the rank sweep at (130, 70, 2) and the edges
+SHAPES_WIDE = ((65, 96, 2, 33), (130, 70, 3, 49), (64, 64, 2, 64))
+OP_SWEEP_RANKS = (2, 15, 16, 17, 32, 33, 48, 49, 63, 64)
+OP_SWEEP = tuple((130, 70, 2, R) for R in OP_SWEEP_RANKS)
+OP_EDGES = ((64, 64, 1, 64), (65, 64, 2, 64), (64, 65, 2, 64), (128, 96, 2, 64), (33, 33, 3, 33), (64, 130, 2, 33),
+            (49, 64, 3, 49), (70, 49, 2, 49))
+KAPPA_WIDE_CAP = 1e3          # a condition on the inputs of these cases: p_bound is at most 1.4e-8 under it
 
 
 def identity_projections(I, K, R):
@@ -126,6 +134,34 @@ def step_case(shape, seed):
     rng = np.random.default_rng(seed + 1000)
     B = B + 0.05 * rng.standard_normal(B.shape)
     A = A + 0.05 * rng.uniform(0.0, 1.0, A.shape)
+    C = C + 0.05 * rng.uniform(0.0, 1.0, C.shape)
+    return X, B, A, C
+
+
+def planted_wide(I, J, K, R, seed, noise=0.0):
+    """a planted model whose Q_k stay well conditioned up to R = 64 (J >= R): random orthonormal P_k, A with
+    orthogonal columns of lengths in U(0.5, 1.5), C in U(0.5, 1.5), B = I + 0.3 / sqrt(R) U(-1, 1); noise is
+    relative to ||X||. Returns (X, P, B, A, C), X first index fastest."""
+    rng = np.random.default_rng(seed)
+    P = np.stack([np.linalg.qr(rng.standard_normal((I, R)))[0] for _ in range(K)])
+    A = np.linalg.qr(rng.standard_normal((J, R)))[0] * rng.uniform(0.5, 1.5, R)
+    C = rng.uniform(0.5, 1.5, (K, R))
+    B = np.eye(R) + 0.3 / np.sqrt(R) * rng.uniform(-1.0, 1.0, (R, R))
+    X = model(P, B, A, C)
+    if noise:
+        E = rng.standard_normal(X.shape)
+        X = X + noise * np.linalg.norm(X) / np.linalg.norm(E) * E
+    return np.asfortranarray(X), P, B, A, C
+
+
+def step_case_wide(shape, seed):
+    """step_case for the larger ranks: noisy planted_wide data, the factors moved off the planted ones by
+    0.05 / sqrt(R) (B), 0.05 / sqrt(J) (A) and 0.05 U(0, 1) (C)"""
+    I, J, K, R = shape
+    X, _, B, A, C = planted_wide(I, J, K, R, seed, noise=0.05)
+    rng = np.random.default_rng(seed + 1000)
+    B = B + 0.05 / np.sqrt(R) * rng.standard_normal(B.shape)
+    A = A + 0.05 / np.sqrt(J) * rng.standard_normal(A.shape)
     C = C + 0.05 * rng.uniform(0.0, 1.0, C.shape)
     return X, B, A, C
 

@@ -27,7 +27,9 @@ def run_case(*name, timeout=300, **env):
     assert f"parafac2 case {' '.join(name)}: ok" in p.stdout
 
 
-@pytest.mark.parametrize("shape", range(5))   # (23, 17, 5, 3), (70, 9, 6, 2), (16, 130, 4, 5), (9, 7, 33, 4), (40, 33, 5, 17)
+# (23, 17, 5, 3), (70, 9, 6, 2), (16, 130, 4, 5), (9, 7, 33, 4), (40, 33, 5, 17); then the wide generator's
+# (65, 96, 2, 33), (130, 70, 3, 49), (64, 64, 2, 64): three and four rank tiles, and an inner CP session of rank 64
+@pytest.mark.parametrize("shape", range(8))
 def test_step_values_and_the_loss_identity(shape):
     run_case("values", str(shape))
 

@@ -70,6 +70,40 @@ def test_condition_numbers_of_every_gpu_case_stay_below_the_cap():
     assert ref.kappas(X, B, A, C).max() <= 500.0
 
 
+def test_condition_numbers_of_the_wide_inputs_stay_below_their_cap():
+    """every op-level input (tests/parafac2_op_cases.py) and the binding-level cases 5..7, as fp64 values and
+    rounded to fp32 (what an f32 view holds): KAPPA_WIDE_CAP is a condition on these inputs. A failed-slice case
+    has exactly one slice outside it, slice 1, far on the other side of the status rule's threshold."""
+    import parafac2_cases_inputs as inputs
+    worst = 0.0
+    for name, (X, B, A, C) in inputs.all_wide_inputs():
+        for Xv in (X, X.astype(np.float32).astype(np.float64)):
+            sv = [np.linalg.svd(((Xv[:, :, k] @ A) * C[k]) @ B.T, compute_uv=False) for k in range(Xv.shape[2])]
+            with np.errstate(divide="ignore"):
+                kap = np.array([s[0] / s[-1] if s[0] > 0 else np.inf for s in sv])
+            if "failed" in name:
+                assert not kap[1] ** -2.0 > 2.0 ** -45, (name, kap)
+                kap = np.delete(kap, 1)
+            assert np.all(np.isfinite(kap)) and kap.max() <= ref.KAPPA_WIDE_CAP, (name, kap)
+            worst = max(worst, kap.max())
+    print("the largest condition number of a wide input:", worst)
+    for shape in inputs.FAILED_SHAPES:
+        X1 = inputs.failed_slice_inputs(shape, "rank")[0][:, :, 1]
+        assert np.array_equal(X1, X1.astype(np.float32)) and np.linalg.matrix_rank(X1) == shape[3] - 1
+
+
+def test_the_wide_generator_keeps_the_loss_identity_and_the_truth():
+    for shape in ref.SHAPES_WIDE:
+        I, J, K, R = shape
+        X, B, A, C = ref.step_case_wide(shape, 7)
+        P, Y, lost, failed = ref.step(X, B, A, C)
+        xx = np.sum(X * X)
+        assert failed == 0 and abs(lost + np.sum((Y - ref.cp_model(B, A, C)) ** 2) - ref.loss(X, P, B, A, C)) <= 1e-12 * xx
+        X, P0, B, A, C = ref.planted_wide(I, J, K, R, 3)
+        P, _, lost, failed = ref.step(X, B, A, C)
+        assert failed == 0 and np.abs(P - P0).max() < 1e-9 and abs(lost) <= 1e-12 * np.sum(X * X)
+
+
 def test_the_driver_case_has_something_to_do():
     """the reference's loss at the first look (a step from the start, no sweep yet) is several times its loss
     after twenty iterations, so a driver that does nothing cannot pass the GPU case that compares with it"""
