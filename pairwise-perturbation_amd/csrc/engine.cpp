@@ -694,7 +694,7 @@ CpEngine::CpEngine(Ops &ops, Comm &comm, const TensorDesc &V, int R, int nstarts
   if (const char *e = std::getenv("PPALS_TEST_BLOCKED_UPDATE")) test_blocks_ = std::atoi(e);
   if (N_ < 3) schedule_ = 0;
   if (const char *e = std::getenv("PPALS_PLACE_TUNE")) ms_tune_enabled_ = std::atoi(e) != 0;
-  if (const char *e = std::getenv("PPALS_PACK_LAYOUT")) pack_mode_ = std::atoi(e) == 0 ? 0 : (std::atoi(e) == 1 ? 1 : -1);
+  if (const char *e = std::getenv("PPALS_PACK_LAYOUT")) pack_mode_ = std::atoi(e) >= 0 && std::atoi(e) <= 2 ? std::atoi(e) : -1;
   if (N_ >= 3) {  // multi-sweep structures exist for every session so the schedule can be switched
     ms_set_roots(ms_choose_roots());
     ms_scales_ = (double *)ops_.alloc(sizeof(double) * 32);
@@ -984,7 +984,8 @@ bool CpEngine::plan_scan(int first, int k, bool natural_only, ScanPlan &plan) {
   return true;
 }
 
-// Packed twins (ops.h PackedSrc, kernels_pack.hip.h): a lossless 3.5-byte-per-element copy of an
+// Packed twins (ops.h PackedSrc, kernels_pack.hip.h): a lossless copy of 3.25 or 3.5 bytes per element
+// (26 bits while at most 1/16 of the blocks need an escape plane, else 28) of an
 // unpadded fp32 layout in the block order of ONE scan shape, which the one-n-tile scan then reads
 // instead of the layout — the scan is HBM-bound, the tensor does not change between sweeps, and the
 // copy is made once like the second resident layout. Optional like the padded third copy: taken
@@ -993,8 +994,8 @@ bool CpEngine::plan_scan(int first, int k, bool natural_only, ScanPlan &plan) {
 // (order 4, s = 200: four of 5.6 GB beside two layouts of 6.4 GB). All or nothing per twin: one
 // block whose top bytes span 16 values or more (mixed signs, zeros beside large values) and the
 // scan reads the plain layout, as does every launch the packed kernel does not serve (ops.h).
-// PPALS_PACK_LAYOUT=0 never packs, =1 packs whatever the size (tests), default: tensors of at
-// least 100 MB. Sharded, multi-start and rank-sweep sessions do not pack; a session whose tensor
+// PPALS_PACK_LAYOUT=0 never packs, =1 / =2 pack in the 28-bit / 26-bit format whatever the size
+// (tests), default: tensors of at least 100 MB, the format by the rule above. Sharded, multi-start and rank-sweep sessions do not pack; a session whose tensor
 // keeps being rewritten (masked EM) stops packing at the third rewrite.
 namespace {
 // names the packed twin for the scans inside a scope and takes it back on every way out
@@ -1009,20 +1010,58 @@ void CpEngine::packs_release() {
   for (auto &t : packs_) {
     ops_.free(t.data);
     ops_.free(t.bases);
+    ops_.free(t.esc);
   }
   packs_.clear();
 }
 
+// Survey the twin's source, choose its format (pack_choose_format), make room and pack. Called for a
+// new twin and again when the tensor was rewritten: the buffers are kept where the format is the
+// same and the escape planes still fit. On any refusal the twin holds no memory and says why.
 bool CpEngine::pack_fill(PackedTwin &t) {
-  const int spread = ops_.pack_layout(t.src, V_.dtype, t.L, t.J, t.T, t.data, t.bases);
-  if (spread >= 0 && spread < PACK_WINDOW) return true;
-  ops_.free(t.data);
-  ops_.free(t.bases);
-  t.data = t.bases = nullptr;
-  t.bytes = 0;
-  t.reason = spread < 0 ? "scan shape has no packed route"
-                        : "top bytes of a block span " + std::to_string(spread + 1) + " values (window 16)";
-  return false;
+  auto drop = [&](const std::string &why) {
+    ops_.free(t.data);
+    ops_.free(t.bases);
+    ops_.free(t.esc);
+    t.data = t.bases = t.esc = nullptr;
+    t.bytes = t.esc_room = 0;
+    t.format = 0;
+    t.escapes = 0;
+    t.reason = why;
+    return false;
+  };
+  const bool forced = pack_mode_ == 1 || pack_mode_ == 2;
+  const size_t bb = pack_base_bytes(t.L, t.J, t.T);
+  if (!t.bases && !(t.bases = ops_.try_alloc(bb))) return drop("allocation failed");
+  const PackSurvey sv = ops_.pack_survey(t.src, V_.dtype, t.L, t.J, t.T, t.bases);
+  if (sv.spread < 0) return drop("scan shape has no packed route");
+  if (sv.spread >= PACK_WINDOW)
+    return drop("top bytes of a block span " + std::to_string(sv.spread + 1) + " values (window 16)");
+  const int fmt = pack_choose_format(pack_mode_, sv.spread, sv.escapes, pack_blocks_of(t.L, t.J, t.T));
+  if (!fmt) return drop("more escape blocks than the side word can number");
+  const size_t db = pack_data_bytes(fmt, t.L, t.J, t.T);
+  const size_t eb = fmt == PACK_FMT26 ? (size_t)sv.escapes * PACK26_ESC_BYTES : 0;
+  if (t.data && (fmt != t.format || eb > t.esc_room)) {
+    ops_.free(t.data);
+    ops_.free(t.esc);
+    t.data = t.esc = nullptr;
+    t.esc_room = 0;
+  }
+  if (!t.data) {
+    if (!forced && db + bb + eb >= (size_t)t.L * (size_t)t.J * (size_t)t.T * 4)
+      return drop("row tiles would pad away what packing saves");  // (a batch ends with a whole tile of 256 rows)
+    if (!optional_fits(db + eb)) return drop("no room beside what the session still allocates");
+    t.data = ops_.try_alloc(db);
+    t.esc = t.data && eb ? ops_.try_alloc(eb) : nullptr;
+    if (!t.data || (eb && !t.esc)) return drop("allocation failed");
+    t.esc_room = eb;
+  }
+  t.format = fmt;
+  t.escapes = sv.escapes;  // (as surveyed, whichever format was chosen)
+  t.bytes = db + bb + eb;
+  t.reason.clear();
+  ops_.pack_write(t.src, t.L, t.J, t.T, fmt, t.bases, t.data, t.esc);
+  return true;
 }
 
 const PackedSrc *CpEngine::packed_for(const ScanPlan &pl, PackedSrc &out) {
@@ -1032,7 +1071,7 @@ const PackedSrc *CpEngine::packed_for(const ScanPlan &pl, PackedSrc &out) {
     else if (R_ > 16) pack_off_reason_ = "not eligible: more than 16 result columns";
     else if (dist_) pack_off_reason_ = "not eligible: sharded session";
     else if (multi_) pack_off_reason_ = "not eligible: multi-start session";
-    else if (pack_mode_ != 1 && (double)V_.nloc * 4.0 < 1e8) pack_off_reason_ = "tensor below 100 MB";
+    else if (pack_mode_ < 0 && (double)V_.nloc * 4.0 < 1e8) pack_off_reason_ = "tensor below 100 MB";
   }
   if (!pack_off_reason_.empty()) return nullptr;
   const int li = (int)(pl.lay - lay_.data());
@@ -1046,33 +1085,21 @@ const PackedSrc *CpEngine::packed_for(const ScanPlan &pl, PackedSrc &out) {
     n.L = pl.L;
     n.J = pl.J;
     n.T = pl.T;
-    const size_t db = pack_data_bytes(n.L, n.J, n.T), bb = pack_base_bytes(n.L, n.J, n.T);
-    if (pl.lay->q > 0) {
+    if (pl.lay->q > 0)
       n.reason = "padded layout";
-    } else if (n.L < 4 || n.L % 4) {
+    else if (n.L < 4 || n.L % 4)
       n.reason = "scan shape has no packed route";  // (no whole lanes of 4 rows)
-    } else if (pack_mode_ != 1 && db + bb >= (size_t)n.L * (size_t)n.J * (size_t)n.T * 4) {
-      n.reason = "row tiles would pad away what packing saves";  // (a batch ends with a whole tile of 256 rows)
-    } else if (!optional_fits(db + bb)) {
-      n.reason = "no room beside what the session still allocates";
-    } else {
-      n.data = ops_.try_alloc(db);
-      n.bases = n.data ? ops_.try_alloc(bb) : nullptr;
-      if (!n.bases) {
-        ops_.free(n.data);
-        n.data = nullptr;
-        n.reason = "allocation failed";
-      } else {
-        n.bytes = db + bb;
-        pack_fill(n);
-      }
-    }
+    else
+      pack_fill(n);
     packs_.push_back(n);
     t = &packs_.back();
   }
   if (!t->data) return nullptr;
   out.data = t->data;
   out.bases = t->bases;
+  out.esc = t->esc;
+  out.format = t->format;
+  out.escapes = t->escapes;
   out.L = t->L;
   out.J = t->J;
   out.T = t->T;
@@ -3586,7 +3613,7 @@ void CpEngine::pp_build_all() {
   }
 }
 std::string CpEngine::placement_report() const {
-  char buf[400];
+  char buf[512];
   std::string out = "{\"mode\": ";
   out += ms_tune_enabled_ && ms_X_slack() > 0 ? "\"online\"" : "\"off\"";
   out += ", \"setup_s\": 0.0, \"candidate_blocks_held\": ";
@@ -3613,17 +3640,18 @@ std::string CpEngine::placement_report() const {
   out += "]";
   // packed twins of the layouts, one row per scan shape that asked for one
   out += ", \"packed\": {\"mode\": ";
-  out += pack_mode_ == 0 ? "\"off\"" : (pack_mode_ == 1 ? "\"on\"" : "\"auto\"");
+  out += pack_mode_ == 0 ? "\"off\"" : (pack_mode_ > 0 ? "\"on\"" : "\"auto\"");
   out += ", \"refused\": \"" + pack_off_reason_ + "\", \"packed_scans\": " + std::to_string(ops_.scan_packed_launches()) +
          ", \"layouts\": [";
   for (size_t k = 0; k < packs_.size(); k++) {
     const PackedTwin &t = packs_[k];
     snprintf(buf, sizeof buf,
              "%s{\"layout\": \"%s\", \"rows\": %lld, \"reduced\": %lld, \"batches\": %lld, \"packed\": %s, "
-             "\"bytes_per_element\": %.4f, \"reason\": \"%s\"}",
+             "\"bytes_per_element\": %.4f, \"format\": %d, \"escape_blocks\": %lld, \"reason\": \"%s\"}",
              k ? ", " : "", t.layout == 0 ? "tensor" : (t.layout == 1 ? "second (transposed) copy" : "padded copy"),
              (long long)t.L, (long long)t.J, (long long)t.T, t.data ? "true" : "false",
-             t.data ? (double)t.bytes / ((double)t.L * (double)t.J * (double)t.T) : 4.0, t.reason.c_str());
+             t.data ? (double)t.bytes / ((double)t.L * (double)t.J * (double)t.T) : 4.0, t.format,
+             (long long)t.escapes, t.reason.c_str());
     out += buf;
   }
   out += "]}}";

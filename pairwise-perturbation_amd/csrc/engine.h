@@ -642,12 +642,16 @@ class CpEngine {
     int layout = 0;             // index into lay_
     const void *src = nullptr;  // that layout's elements
     int64_t L = 0, J = 0, T = 0;
-    void *data = nullptr, *bases = nullptr;
-    size_t bytes = 0;
+    void *data = nullptr, *bases = nullptr, *esc = nullptr;
+    int format = 0;             // PACK_FMT28 / PACK_FMT26 (0: no copy)
+    int64_t escapes = 0;        // blocks that need an escape plane in format 26, as surveyed
+    size_t esc_room = 0;        // bytes behind esc
+    size_t bytes = 0;           // blocks + side words + escape planes
     std::string reason;         // why there is no copy ("" while there is one)
   };
   std::vector<PackedTwin> packs_;
-  int pack_mode_ = -1;            // PPALS_PACK_LAYOUT: 0 never, 1 whatever the size, -1 auto
+  // PPALS_PACK_LAYOUT: 0 never, 1 / 2 the 28-bit / 26-bit format whatever the size, -1 auto
+  int pack_mode_ = -1;
   int pack_regen_ = 0;            // times the tensor changed under this session
   std::string pack_off_reason_;   // why this session does not pack at all ("" while it may)
   bool optional_fits(size_t bytes);  // an optional copy of `bytes` fits behind what is still to come

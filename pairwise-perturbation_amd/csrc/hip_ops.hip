@@ -237,7 +237,7 @@ class HipOps : public Ops {
     }
     if (ws_mttv_) hipFree(ws_mttv_);
     if (ws_pack_) hipFree(ws_pack_);
-    if (pack_spread_) hipFree(pack_spread_);
+    if (pack_stats_) hipFree(pack_stats_);
     if (ws_mv_) hipFree(ws_mv_);
     if (ws_hist_) hipFree(ws_hist_);
     if (ws_slab_) hipFree(ws_slab_);
@@ -1555,30 +1555,46 @@ class HipOps : public Ops {
   }
   PackedSrc scan_pk_;
   int64_t scan_pk_launches_ = 0;
+  // PPALS_PK2_DECODE=branch (measurements only): the 26-bit scan adds its escape bits under a branch
+  bool scan_pk2_branch_ = [] {
+    const char *e = getenv("PPALS_PK2_DECODE");
+    return e && std::string(e) == "branch";
+  }();
   int64_t scan_packed_launches() override { return scan_pk_launches_; }
-  int *pack_spread_ = nullptr;  // device word of pack_layout's pre-pass
-  int pack_layout(const void *src, int dt, int64_t L, int64_t J, int64_t T, void *data, void *bases) override {
+  int *pack_stats_ = nullptr;  // device words of the pre-pass: largest spread, escape blocks
+  PackSurvey pack_survey(const void *src, int dt, int64_t L, int64_t J, int64_t T, void *bases) override {
     // what the packed scan route itself needs (scan_t): fp32, whole lanes of 4 rows, 16-byte aligned
     // rows, 32-bit tile ids and block counts
     const int64_t n_mtiles = (L + 255) / 256, nkb = (J + 15) / 16;
+    PackSurvey sv;
     if (dt != F32 || L < 4 || L % 4 || J < 1 || T < 1 || (((uintptr_t)src) & 15) || n_mtiles * T > 0x7fffffff ||
         n_mtiles * T * nkb > 0x7fffffff)
-      return -1;
-    if (!pack_spread_) pack_spread_ = (int *)alloc(sizeof(int));
+      return sv;
+    if (!pack_stats_) pack_stats_ = (int *)alloc(2 * sizeof(int));
     const unsigned nblocks = (unsigned)(n_mtiles * T * nkb);
-    HIP_CHECK(hipMemsetAsync(pack_spread_, 0, sizeof(int), st_));
+    HIP_CHECK(hipMemsetAsync(pack_stats_, 0, 2 * sizeof(int), st_));
     hipLaunchKernelGGL(k_pk_prepass, dim3(nblocks), dim3(256), 0, st_, (const float *)src, L, J, (int)n_mtiles,
-                       (int)nkb, (pk_u32 *)bases, pack_spread_);
+                       (int)nkb, (pk_u32 *)bases, pack_stats_);
     HIP_CHECK(hipGetLastError());
-    int spread = 0;
-    HIP_CHECK(hipMemcpyAsync(&spread, pack_spread_, sizeof(int), hipMemcpyDeviceToHost, st_));
+    int stats[2] = {0, 0};
+    HIP_CHECK(hipMemcpyAsync(stats, pack_stats_, sizeof stats, hipMemcpyDeviceToHost, st_));
     HIP_CHECK(hipStreamSynchronize(st_));
-    if (spread >= PACK_WINDOW) return spread;
-    hipLaunchKernelGGL(k_pk_pack, dim3(nblocks), dim3(256), 0, st_, (const float *)src, L, J, (int)n_mtiles, (int)nkb,
-                       pack_tile_bytes(J), (const pk_u32 *)bases, (char *)data);
+    sv.spread = stats[0];
+    sv.escapes = stats[1];
+    return sv;
+  }
+  void pack_write(const void *src, int64_t L, int64_t J, int64_t T, int format, void *bases, void *data,
+                  void *esc) override {
+    const int64_t n_mtiles = (L + 255) / 256, nkb = (J + 15) / 16;
+    const unsigned nblocks = (unsigned)(n_mtiles * T * nkb);
+    hipLaunchKernelGGL(k_pk_side_words, dim3(1), dim3(1024), 0, st_, (pk_u32 *)bases, (int64_t)nblocks, format);
+    HIP_CHECK(hipGetLastError());
+    dispatch<PACK_FMT26, PACK_FMT28>(format, [&](auto fmt) {
+      hipLaunchKernelGGL((k_pk_pack<fmt>), dim3(nblocks), dim3(256), 0, st_, (const float *)src, L, J, (int)n_mtiles,
+                         (int)nkb, pack_tile_bytes(fmt, J), (const pk_u32 *)bases, (char *)data, (char *)esc);
+    });
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(st_));
-    return spread;
   }
   void scan_profile_slot(int slot) override { scan_slot_ = slot == 1 ? 1 : 0; }
   int scan_nt_mode_ = -1;
@@ -1790,13 +1806,17 @@ class HipOps : public Ops {
                                 d.row_ld == 0 && scan_tail_split<TV>(NT, n_mtiles) >= 0;
         if (takes_tail) nts = false;
         // the packed twin of this very scan (Ops::scan_packed_source): the one-n-tile fp32 buffer route,
-        // unpadded and without k-split; the same result bits from 3.5 instead of 4 bytes per element
+        // unpadded and without k-split; the same result bits from 3.5 or 3.25 instead of 4 bytes per element
         bool takes_pk = false;
         if constexpr (sizeof(TV) == 4)
           takes_pk = takes_buf && NT == 1 && nsplit == 1 && d.row_ld == 0 && scan_pk_.data && scan_pk_.L == L &&
                      scan_pk_.J == J && scan_pk_.T == T;
-        // (the profile counts the bytes the launch addresses: the packed source + the result)
-        prof_begin(scan_slot_, takes_pk ? (double)pack_data_bytes(L, J, T) + (double)pack_base_bytes(L, J, T) +
+        const bool pk26 = takes_pk && scan_pk_.format == PACK_FMT26;
+        // (the profile counts the bytes the launch addresses: the packed source — blocks, side words and
+        // the escape planes of a 26-bit twin — + the result)
+        prof_begin(scan_slot_, takes_pk ? (double)pack_data_bytes(scan_pk_.format, L, J, T) +
+                                              (double)pack_base_bytes(L, J, T) +
+                                              (pk26 ? (double)scan_pk_.escapes * PACK26_ESC_BYTES : 0.0) +
                                               (double)L * (double)T * ncols * (out32 ? 4.0 : 8.0)
                                         : bytes);
         // (measured: with NT >= 2 the fp32 build of the buffer variant drops to 2 waves/SIMD and
@@ -1810,7 +1830,8 @@ class HipOps : public Ops {
         if (takes_tail)
           route("scan.%s.suffix.tail nt=%d from=%d", tname<TV>(), NT, scan_tail_split<TV>(NT, n_mtiles));
         else if (takes_pk)
-          route("scan.%s.suffix.pk nt=1 nsplit=1 nts=%d pad=0 out32=%d", tname<TV>(), nts ? 1 : 0, out32);
+          route("scan.%s.suffix.%s nt=1 nsplit=1 nts=%d pad=0 out32=%d", tname<TV>(), pk26 ? "pk2" : "pk", nts ? 1 : 0,
+                out32);
         else if (takes_buf || (al && M >= VEC))
           route("scan.%s.suffix.%s nt=%d nsplit=%d nts=%d pad=%d out32=%d", tname<TV>(), takes_buf ? "buf" : "fast",
                 NT, nsplit, nts ? 1 : 0, pad.ld ? 1 : 0, out32);
@@ -1832,11 +1853,21 @@ class HipOps : public Ops {
           });
         } else if (takes_pk) {
           scan_pk_launches_++;
-          dispatch<5, 1>(nts ? 5 : 1, [&](auto opt) {
-            hipLaunchKernelGGL((k_scan_suffix_pk<opt>), grid_p, dim3(256), 0, st_, (const char *)scan_pk_.data,
-                               (const unsigned int *)scan_pk_.bases, pack_tile_bytes(J), M, (const float *)P, n_mtiles,
-                               nblk, d.p, d.nstride, d.batch_stride, ncols, d.out32, nblocks);
-          });
+          if (pk26)
+            // (bit 3, the branched escape decode, is the other side of the A/B in profiles/pack26_bench.md)
+            dispatch<5, 1, 13, 9>((nts ? 5 : 1) | (scan_pk2_branch_ ? 8 : 0), [&](auto opt) {
+              hipLaunchKernelGGL((k_scan_suffix_pk2<opt>), grid_p, dim3(256), 0, st_, (const char *)scan_pk_.data,
+                                 (const unsigned int *)scan_pk_.bases, (const char *)scan_pk_.esc,
+                                 pack_tile_bytes(PACK_FMT26, J), M, (const float *)P, n_mtiles, nblk, d.p, d.nstride,
+                                 d.batch_stride, ncols, d.out32, nblocks);
+            });
+          else
+            dispatch<5, 1>(nts ? 5 : 1, [&](auto opt) {
+              hipLaunchKernelGGL((k_scan_suffix_pk<opt>), grid_p, dim3(256), 0, st_, (const char *)scan_pk_.data,
+                                 (const unsigned int *)scan_pk_.bases, pack_tile_bytes(PACK_FMT28, J), M,
+                                 (const float *)P, n_mtiles, nblk, d.p, d.nstride, d.batch_stride, ncols, d.out32,
+                                 nblocks);
+            });
         } else {
           dispatch<1, 2, 3, 4>(NT, [&](auto nt) {
             if (takes_buf)

@@ -1,5 +1,5 @@
-// kernels_pack.hip.h — the lossless 28-bit resident copy of an fp32 tensor that k_scan_suffix_pk
-// (kernels_scan.hip.h) reads: 3.5 bytes per element instead of 4.
+// kernels_pack.hip.h — the lossless resident copies of an fp32 tensor that k_scan_suffix_pk (28 bits
+// per element, 3.5 bytes) and k_scan_suffix_pk2 (26 bits, 3.25 bytes) read (kernels_scan.hip.h).
 //
 // The copy is made for ONE scan shape [L rows, J reduced, T batches] and is stored block-major in that
 // scan's own unit. A BLOCK is what one workgroup of the one-n-tile fp32 buffer-load scan consumes per
@@ -7,13 +7,13 @@
 // kernel's lane mapping — lane (g, j16) of wave w holds rows 256*tile + 64*w + 4*j16 .. +3 of the
 // reduction indices 16*kb + 4*u + g, u = 0..3 (k-quad u).
 //
-// An element is stored as the low 24 bits of its fp32 word and a 4-bit code c; the word is
+// An element is stored as the low 24 bits of its fp32 word and a code c; the word is
 //   ((base + c) << 24) | low24            base: one byte per block, the smallest top byte in it
 // so a block qualifies when the top bytes (sign + upper seven exponent bits) of its elements span at
-// most 16 consecutive values; a layout is packed only if EVERY block qualifies (pk_prepass reports
-// the largest spread).
+// most 16 consecutive values; a layout is packed only if EVERY block qualifies (the pre-pass reports
+// the largest spread). The per-lane arithmetic of both formats is pack_codec.h.
 //
-// Bytes of a block (PACK_BLOCK_BYTES = 14336 when whole):
+// FORMAT 28. Bytes of a block (PACK_BLOCK_BYTES = 14336 when whole):
 //   [0, 2048)                  code plane: 8 bytes per thread (wave*512 + lane*8): dword 0 serves
 //                              quads 0 (even nibbles) and 1 (odd nibbles), dword 1 quads 2 and 3;
 //                              nibble pair jj of a dword belongs to the lane's row jj
@@ -26,7 +26,19 @@
 // tiles consecutive in the kernel's tile order (row tile fastest, then batch); rows beyond L in the
 // last row tile of a batch and indices beyond J inside a stored quad hold low part 0, code 0 (the
 // scan never stores those rows, and the packed Khatri-Rao operand is zero at those indices).
-// One word per block, base replicated into its four bytes, sits in a side array.
+// One side word per block, base replicated into its four bytes, sits in a side array.
+//
+// FORMAT 26. The same blocks, quads, tile order and tails; the code plane is half as large
+// (PACK26_BLOCK_BYTES = 13312 when whole):
+//   [0, 1024)                  code plane: one dword per thread (wave*256 + lane*4); byte jj holds the
+//                              LOW two code bits of the lane's row jj, quad u at bits 2u..2u+1
+//   [1024 + 3072*u, + 3072)    k-quad u, as above
+// A block whose top bytes spread over 4..15 (an ESCAPE block) keeps its quads and low code bits where
+// they always lie — block addresses stay arithmetic — and the UPPER two code bits of every element,
+// in the same dword arrangement, in an escape plane of 1024 bytes in a side buffer, at the block's
+// escape ordinal. Ordinals count the escape blocks in block order (k_pk_side_words: a prefix sum, no
+// atomic counter, so the same tensor always gives the same bytes). The side word is
+// base | (ordinal + 1) << 8; upper 24 bits zero: no escape plane, the scan reads zeros for it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -63,12 +75,14 @@ __device__ inline PkLane pk_gather(const float *__restrict__ V, int64_t L, int64
   return r;
 }
 
-// pre-pass, one workgroup per block: bases[gid] = the block's smallest top byte (x 0x01010101), and
-// *spread = the largest (max - min) of any block — an integer maximum, so the order of the atomic
-// updates does not matter; nothing a scan reads is accumulated atomically
+// pre-pass, one workgroup per block: bases[gid] = the block's smallest top byte, with bit 8 set if
+// the block would need an escape plane in format 26 (provisional: k_pk_side_words finishes the
+// word); stats[0] = the largest (max - min) of any block, stats[1] = the number of escape blocks —
+// an integer maximum and an integer count, so the order of the atomic updates does not matter;
+// nothing a scan reads is accumulated atomically
 __global__ __launch_bounds__(256) void k_pk_prepass(const float *__restrict__ V, int64_t L, int64_t J,
                                                     int n_mtiles, int nkb, pk_u32 *__restrict__ bases,
-                                                    int *__restrict__ spread) {
+                                                    int *__restrict__ stats) {
   __shared__ int smn[256], smx[256];
   const int64_t gid = blockIdx.x;
   const PkLane r = pk_gather(V, L, J, n_mtiles, nkb, gid, threadIdx.x);
@@ -96,22 +110,54 @@ __global__ __launch_bounds__(256) void k_pk_prepass(const float *__restrict__ V,
     mn = smn[0];
     mx = smx[0];
     if (mx < mn) mn = mx = 0;
-    bases[gid] = (pk_u32)mn * 0x01010101u;
-    atomicMax(spread, mx - mn);
+    const bool escape = mx - mn >= PACK26_WINDOW;
+    bases[gid] = (pk_u32)mn | (escape ? 0x100u : 0u);
+    atomicMax(stats, mx - mn);
+    if (escape) atomicAdd(stats + 1, 1);
   }
 }
 
-// the copy itself (after a pre-pass whose spread is below PACK_WINDOW), one workgroup per block
+// the side words of format `fmt` from the pre-pass's provisional ones, in place. ONE workgroup:
+// thread t owns the blocks [t*per, (t+1)*per), counts its escape flags, the counts are summed in
+// thread order (an exclusive prefix sum through shared memory), and the thread numbers its escape
+// blocks from there — ordinals in block order, the same on every run.
+__global__ __launch_bounds__(1024) void k_pk_side_words(pk_u32 *__restrict__ bases, int64_t nblocks, int fmt) {
+  __shared__ unsigned int cnt[1024];
+  const int64_t per = (nblocks + 1023) / 1024;
+  const int64_t b0 = min(nblocks, (int64_t)threadIdx.x * per), b1 = min(nblocks, b0 + per);
+  unsigned int mine = 0;
+  if (fmt == PACK_FMT26)
+    for (int64_t b = b0; b < b1; b++) mine += (bases[b] >> 8) & 1u;
+  cnt[threadIdx.x] = mine;
+  __syncthreads();
+  for (int s = 1; s < 1024; s <<= 1) {  // inclusive scan, two barriers per step
+    const unsigned int add = (int)threadIdx.x >= s ? cnt[threadIdx.x - s] : 0u;
+    __syncthreads();
+    cnt[threadIdx.x] += add;
+    __syncthreads();
+  }
+  unsigned int ordinal = cnt[threadIdx.x] - mine;
+  for (int64_t b = b0; b < b1; b++) {
+    const pk_u32 w = bases[b];
+    const bool escape = (w >> 8) & 1u;
+    bases[b] = pk_side_word(fmt, w & 0xffu, escape, ordinal);
+    ordinal += escape ? 1u : 0u;
+  }
+}
+
+// the copy itself (after a pre-pass whose spread is below PACK_WINDOW, and k_pk_side_words<FMT>), one
+// workgroup per block
+template <int FMT>
 __global__ __launch_bounds__(256) void k_pk_pack(const float *__restrict__ V, int64_t L, int64_t J, int n_mtiles,
                                                  int nkb, int64_t tile_bytes, const pk_u32 *__restrict__ bases,
-                                                 char *__restrict__ out) {
+                                                 char *__restrict__ out, char *__restrict__ esc) {
   const int64_t gid = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const PkLane r = pk_gather(V, L, J, n_mtiles, nkb, gid, tid);
-  const pk_u32 base = bases[gid] & 0xffu;
+  const pk_u32 side = bases[gid], base = side & 0xffu;
   const int64_t tile = gid / nkb;
   const int kb = (int)(gid % nkb);
-  char *blk = out + tile * tile_bytes + (int64_t)kb * PACK_BLOCK_BYTES;
+  char *blk = out + tile * tile_bytes + (int64_t)kb * pack_block_bytes(FMT);
   pk_u32 cw[2] = {0u, 0u};
 #pragma unroll
   for (int u = 0; u < 4; u++) {
@@ -119,15 +165,27 @@ __global__ __launch_bounds__(256) void k_pk_pack(const float *__restrict__ V, in
 #pragma unroll
     for (int jj = 0; jj < 4; jj++) {
       e[jj] = r.ok[u][jj] ? r.e[u][jj] : base << 24;  // absent: low part 0, code 0
-      cw[u >> 1] |= ((e[jj] >> 24) - base) << (8 * jj + 4 * (u & 1));
+      if constexpr (FMT == PACK_FMT26)
+        pk26_put(cw[0], cw[1], u, jj, (e[jj] >> 24) - base);
+      else
+        pk28_put(cw, u, jj, (e[jj] >> 24) - base);
     }
     if ((int64_t)kb * 16 + 4 * u < J) {
-      pk_u32 *q = reinterpret_cast<pk_u32 *>(blk + PACK_CODE_BYTES + u * PACK_QUAD_BYTES + wave * 768 + lane * 12);
+      pk_u32 *q = reinterpret_cast<pk_u32 *>(blk + pack_code_bytes(FMT) + u * PACK_QUAD_BYTES + pk_quad_offset(wave, lane));
+      pk_u32 qw[3];
+      pk_quad_encode(e, qw);
 #pragma unroll
-      for (int i = 0; i < 3; i++) q[i] = (e[i] & 0xffffffu) | (((e[3] >> (8 * i)) & 0xffu) << 24);
+      for (int i = 0; i < 3; i++) q[i] = qw[i];
     }
   }
-  *reinterpret_cast<pk_u32x2 *>(blk + wave * 512 + lane * 8) = pk_u32x2{cw[0], cw[1]};
+  if constexpr (FMT == PACK_FMT26) {
+    *reinterpret_cast<pk_u32 *>(blk + pk_code_offset(FMT, wave, lane)) = cw[0];
+    if (side >> 8)  // (block-uniform) the escape plane of this block, at its ordinal
+      *reinterpret_cast<pk_u32 *>(esc + (int64_t)((side >> 8) - 1u) * PACK26_ESC_BYTES +
+                                  pk_code_offset(FMT, wave, lane)) = cw[1];
+  } else {
+    *reinterpret_cast<pk_u32x2 *>(blk + pk_code_offset(FMT, wave, lane)) = pk_u32x2{cw[0], cw[1]};
+  }
 }
 
 }  // namespace ppals

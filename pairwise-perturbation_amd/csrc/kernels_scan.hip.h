@@ -768,23 +768,36 @@ __global__ __launch_bounds__(256) void k_scan_suffix_buf(
 // block i the words of block i+1 are rebuilt — per quad 3 VALU operations for the four top bytes
 // (base + code, one per byte) and 6 byte permutes — where the plain kernel copies its registers.
 // Held at the plain kernel's 3 waves per SIMD (the registers would allow 4, measured 1-2 % slower).
-// OPT bit 0: non-temporal tensor loads, bit 2: non-temporal result stores.
+//
+// The 26-BIT twin (k_scan_suffix_pk2, FMT = PACK_FMT26) is the same walk over blocks of 13312 bytes:
+// per block a lane issues one b32 code load, the four b96 quad loads and one UNCONDITIONAL b32 load
+// of the block's escape plane — through a descriptor of its own, built from the block's side word:
+// base esc + ordinal * 1024 with 1024 records for an escape block, 0 records otherwise, so that a
+// block without an escape plane reads zeros and moves no bytes. No load sits under a branch (the
+// counted vmcnt waits stay what they are). The side word is therefore needed when the loads of a
+// block are ISSUED: it is fetched through the scalar cache one block further ahead (sw_next: asked
+// for under the MFMAs of block i - 1, used for the loads of block i + 1 issued in iteration i).
+// The top bytes of a quad are (codes >> 2u & 0x03030303) + base, plus the escape bits in place.
+// OPT bit 0: non-temporal tensor loads, bit 2: non-temporal result stores, bit 3 (FMT 26 only): add
+// the escape bits under a wave-uniform branch instead of always.
 typedef unsigned int scan_u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int scan_u32x3 __attribute__((ext_vector_type(3)));
-template <int OPT>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_scan_suffix_pk(
-    const char *__restrict__ Vp, const unsigned int *__restrict__ bases, int64_t tile_bytes, int64_t M,
-    const float *__restrict__ P, int n_mtiles, int nkb, double *__restrict__ out, int64_t out_nstride,
-    int64_t out_batch_stride, int ncols, int out32, int64_t ntiles) {
+template <int FMT, int OPT>
+__device__ __forceinline__ void scan_suffix_packed(
+    const char *__restrict__ Vp, const unsigned int *__restrict__ bases, const char *__restrict__ esc,
+    int64_t tile_bytes, int64_t M, const float *__restrict__ P, int n_mtiles, int nkb, double *__restrict__ out,
+    int64_t out_nstride, int64_t out_batch_stride, int ncols, int out32, int64_t ntiles) {
   typedef ScanTraits<float> TR;
   typedef unsigned int u32;
   constexpr int VEC = 4, FLUSH = SCAN_FLUSH;
   constexpr int AUXV = (OPT & 1) ? 2 : 0;
+  constexpr bool F26 = FMT == PACK_FMT26;
+  constexpr int BLOCK_BYTES = pack_block_bytes(FMT);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = lane >> 4, j16 = lane & 15;
   const int voffP = (int)((g * 16 + j16) * VEC * (int)sizeof(float));
-  const int voffC = wave * 512 + lane * 8;
-  const int voffQ = PACK_CODE_BYTES + wave * 768 + lane * 12;
+  const int voffC = pk_code_offset(FMT, wave, lane);
+  const int voffQ = pack_code_bytes(FMT) + pk_quad_offset(wave, lane);
   const __amdgpu_buffer_rsrc_t rsrcP = __builtin_amdgcn_make_buffer_rsrc(
       (void *)P, 0, (int)((int64_t)nkb * (4 * 16 * VEC) * (int64_t)sizeof(float)), 0x00020000);
 
@@ -801,47 +814,82 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     t.m = m0 + (int64_t)VEC * j16;
     t.obase = batch * out_batch_stride;
   };
+  // c: the lane's code words (format 26: c[0] the codes, c[1] its dword of the escape plane);
+  // b: the block's base in all four bytes; x (format 26): the block has an escape plane
   struct Raw {
     u32 w[12], c[2], b;
+    bool x;
     f32x4 p;
   };
+  // side word of block (tile_, kb_), through the scalar cache
+#define PPALS_PK_SIDE(tile_, kb_) \
+  bases[(int64_t)__builtin_amdgcn_readfirstlane((int)(tile_)) * nkb + __builtin_amdgcn_readfirstlane((int)(kb_))]
   // the descriptor ends with the tile: the absent quads of a short last block read as zero (their
-  // words then decode to a finite value, and the packed Khatri-Rao operand is zero there)
-#define PPALS_PK_LOAD(tile_, kb_, r_)                                                                 \
+  // words then decode to a finite value, and the packed Khatri-Rao operand is zero there).
+  // side_: format 26 only, the block's side word (already there: see sw_next below)
+#define PPALS_PK_LOAD(tile_, kb_, r_, side_)                                                          \
   {                                                                                                   \
     const int t_ = __builtin_amdgcn_readfirstlane((int)(tile_));                                      \
     const int k_ = __builtin_amdgcn_readfirstlane((int)(kb_));                                        \
-    const int64_t koff_ = (int64_t)k_ * PACK_BLOCK_BYTES;                                             \
+    const int64_t koff_ = (int64_t)k_ * BLOCK_BYTES;                                                  \
     const __amdgpu_buffer_rsrc_t rs_ = __builtin_amdgcn_make_buffer_rsrc(                             \
         (void *)(Vp + (int64_t)t_ * tile_bytes + koff_), 0,                                           \
-        (int)min(tile_bytes - koff_, (int64_t)PACK_BLOCK_BYTES), 0x00020000);                         \
+        (int)min(tile_bytes - koff_, (int64_t)BLOCK_BYTES), 0x00020000);                              \
     _Pragma("unroll") for (int u = 0; u < 4; u++) {                                                   \
       const scan_u32x3 q_ = __builtin_amdgcn_raw_buffer_load_b96(rs_, voffQ, u * PACK_QUAD_BYTES, AUXV); \
       r_.w[3 * u] = q_[0];                                                                            \
       r_.w[3 * u + 1] = q_[1];                                                                        \
       r_.w[3 * u + 2] = q_[2];                                                                        \
     }                                                                                                 \
-    const scan_u32x2 c_ = __builtin_amdgcn_raw_buffer_load_b64(rs_, voffC, 0, AUXV);                  \
-    r_.c[0] = c_[0];                                                                                  \
-    r_.c[1] = c_[1];                                                                                  \
-    r_.b = bases[(int64_t)t_ * nkb + k_];                                                             \
+    if constexpr (F26) {                                                                              \
+      const u32 s_ = (u32)__builtin_amdgcn_readfirstlane((int)(side_));                               \
+      const u32 op_ = s_ >> 8; /* escape ordinal + 1, 0: none -> a descriptor of no records */       \
+      const __amdgpu_buffer_rsrc_t re_ = __builtin_amdgcn_make_buffer_rsrc(                           \
+          (void *)(esc + (int64_t)(op_ ? op_ - 1u : 0u) * PACK26_ESC_BYTES), 0,                       \
+          op_ ? PACK26_ESC_BYTES : 0, 0x00020000);                                                    \
+      r_.c[0] = __builtin_amdgcn_raw_buffer_load_b32(rs_, voffC, 0, AUXV);                            \
+      r_.c[1] = __builtin_amdgcn_raw_buffer_load_b32(re_, voffC, 0, AUXV);                            \
+      r_.b = (s_ & 0xffu) * 0x01010101u;                                                              \
+      r_.x = op_ != 0u;                                                                               \
+    } else {                                                                                          \
+      const scan_u32x2 c_ = __builtin_amdgcn_raw_buffer_load_b64(rs_, voffC, 0, AUXV);                \
+      r_.c[0] = c_[0];                                                                                \
+      r_.c[1] = c_[1];                                                                                \
+      r_.b = bases[(int64_t)t_ * nkb + k_];                                                           \
+      r_.x = false;                                                                                   \
+    }                                                                                                 \
     r_.p = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(                           \
                                          rsrcP, voffP, k_ * (4 * 16 * VEC) * (int)sizeof(float), 0)); \
   }
-  // the 16 fp32 words of a block. v_perm_b32(hi, lo, sel): selector bytes 0..3 take lo's bytes,
-  // 4..7 hi's, 0x0c gives zero. (base + code <= 255 in every byte: no carries)
+  // the 16 fp32 words of a block (pack_codec.h: per quad 3 VALU operations for the top bytes, 3 more
+  // for the escape bits of format 26, and the six byte permutes)
   auto unpack = [](const Raw &r, f32x4(&v)[4]) {
+    u32 tops[4];
 #pragma unroll
     for (int u = 0; u < 4; u++) {
-      const u32 cw = r.c[u >> 1];
-      const u32 T = (((u & 1) ? cw >> 4 : cw) & 0x0f0f0f0fu) + r.b;
-      const u32 w0 = r.w[3 * u], w1 = r.w[3 * u + 1], w2 = r.w[3 * u + 2];
-      v[u][0] = __uint_as_float(__builtin_amdgcn_perm(T, w0, 0x04020100u));
-      v[u][1] = __uint_as_float(__builtin_amdgcn_perm(T, w1, 0x05020100u));
-      v[u][2] = __uint_as_float(__builtin_amdgcn_perm(T, w2, 0x06020100u));
-      v[u][3] = __uint_as_float(__builtin_amdgcn_perm(w1, w0, 0x0c0c0703u) |  // w0.b3, w1.b3, 0, 0
-                                __builtin_amdgcn_perm(T, w2, 0x07030c0cu));   // 0, 0, w2.b3, T.b3
+      if constexpr (!F26)
+        tops[u] = pk28_tops(r.c[0], r.c[1], u, r.b);
+      else if constexpr (OPT & 8)
+        tops[u] = pk26_tops(r.c[0], u, r.b);
+      else
+        tops[u] = pk26_tops(r.c[0], u, r.b) + pk26_escape(r.c[1], u);
     }
+    if constexpr (F26 && (OPT & 8)) {
+      if (r.x) {  // wave-uniform, no load inside
+#pragma unroll
+        for (int u = 0; u < 4; u++) tops[u] += pk26_escape(r.c[1], u);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      u32 e[4];
+      pk_quad_decode(tops[u], r.w[3 * u], r.w[3 * u + 1], r.w[3 * u + 2], e);
+#pragma unroll
+      for (int jj = 0; jj < 4; jj++) v[u][jj] = __uint_as_float(e[jj]);
+    }
+  };
+  auto live_at = [&](int64_t t) {  // decode(t).live alone
+    return ((int64_t)((unsigned)t % (unsigned)n_mtiles) * 4 + wave) * (16 * VEC) < M;
   };
 
   Tile cur, nxt;
@@ -854,9 +902,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   f32x4 cv[4], cb;
   {
     Raw r0;
-    PPALS_PK_LOAD(id, 0, r0);
+    u32 sw0 = 0;
+    if constexpr (F26) sw0 = PPALS_PK_SIDE(id, 0);
+    PPALS_PK_LOAD(id, 0, r0, sw0);
     unpack(r0, cv);
     cb = r0.p;
+  }
+  // format 26: the side word of the block whose loads the coming iteration issues — at first the
+  // second block of this wave's walk (the first again if there is no other)
+  u32 sw_next = 0;
+  if constexpr (F26) {
+    if (nkb > 1) {
+      sw_next = PPALS_PK_SIDE(id, 1);
+    } else {
+      int64_t t = id + gridDim.x;
+      for (; t < ntiles; t += gridDim.x)
+        if (live_at(t)) break;
+      sw_next = PPALS_PK_SIDE(t < ntiles ? t : id, 0);
+    }
   }
 
   for (;;) {
@@ -868,6 +931,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         has_next = true;
         break;
       }
+    }
+    // format 26: the live tile after the next one, which the side-word fetch reaches when a tile is
+    // a single block
+    int64_t nnid = ntiles;
+    if constexpr (F26) {
+      if (nkb == 1 && has_next)
+        for (nnid = nid + gridDim.x; nnid < ntiles; nnid += gridDim.x)
+          if (live_at(nnid)) break;
     }
     f32x4 acc[VEC];
     double acc64[VEC][4];
@@ -887,7 +958,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         const bool same = kb + 1 < nkb;
         const int64_t pt = (same || !has_next) ? id : nid;
         const int pk = same ? kb + 1 : (has_next ? 0 : kb);
-        PPALS_PK_LOAD(pt, pk, nr);
+        u32 sw = 0;
+        if constexpr (F26) {
+          // this block's side word came with the previous iteration; ask now for that of the block
+          // AFTER (pt, pk) in this wave's walk — the next of its tile, else the first of the tile
+          // behind it, else itself
+          sw = sw_next;
+          const int64_t after = pt == id ? (has_next ? nid : ntiles) : nnid;
+          const bool stay = pk + 1 < nkb, hop = !stay && after < ntiles;
+          sw_next = PPALS_PK_SIDE(hop ? after : pt, stay ? pk + 1 : (hop ? 0 : pk));
+        }
+        PPALS_PK_LOAD(pt, pk, nr, sw);
         // (the scheduler must not pull the unpacking, and with it the wait for the loads just
         // issued, up between the MFMAs: block i+1 stays in flight under all MFMAs of block i)
         __builtin_amdgcn_sched_barrier(0);
@@ -947,6 +1028,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     id = nid;
   }
 #undef PPALS_PK_LOAD
+#undef PPALS_PK_SIDE
+}
+
+template <int OPT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_scan_suffix_pk(
+    const char *__restrict__ Vp, const unsigned int *__restrict__ bases, int64_t tile_bytes, int64_t M,
+    const float *__restrict__ P, int n_mtiles, int nkb, double *__restrict__ out, int64_t out_nstride,
+    int64_t out_batch_stride, int ncols, int out32, int64_t ntiles) {
+  scan_suffix_packed<PACK_FMT28, OPT>(Vp, bases, nullptr, tile_bytes, M, P, n_mtiles, nkb, out, out_nstride,
+                                      out_batch_stride, ncols, out32, ntiles);
+}
+
+template <int OPT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_scan_suffix_pk2(
+    const char *__restrict__ Vp, const unsigned int *__restrict__ bases, const char *__restrict__ esc,
+    int64_t tile_bytes, int64_t M, const float *__restrict__ P, int n_mtiles, int nkb, double *__restrict__ out,
+    int64_t out_nstride, int64_t out_batch_stride, int ncols, int out32, int64_t ntiles) {
+  scan_suffix_packed<PACK_FMT26, OPT>(Vp, bases, esc, tile_bytes, M, P, n_mtiles, nkb, out, out_nstride,
+                                      out_batch_stride, ncols, out32, ntiles);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -16,6 +16,7 @@
 
 #include "bf16.h"
 #include "device_view.h"
+#include "pack_codec.h"
 #include "preload_policy.h"
 
 namespace ppals {
@@ -33,27 +34,30 @@ struct RowPad {
   int64_t ld = 0, valid = 0;  // ld == 0: not padded
 };
 
-// The packed (28 bits per element) twin of a resident fp32 layout for ONE scan shape [L, J, T]
-// (format: kernels_pack.hip.h). A block is 256 rows x 16 reduction indices: a code plane and four
-// k-quads; a short last k-block stores only the quads that reach below J.
-constexpr int PACK_BLOCK_BYTES = 14336, PACK_CODE_BYTES = 2048, PACK_QUAD_BYTES = 3072;
-constexpr int PACK_WINDOW = 16;  // top bytes of a block must span fewer values than this
+// The packed twin (28 or 26 bits per element) of a resident fp32 layout for ONE scan shape [L, J, T]
+// (formats: kernels_pack.hip.h, pack_codec.h). A block is 256 rows x 16 reduction indices: a code
+// plane and four k-quads; a short last k-block stores only the quads that reach below J. A 26-bit
+// twin keeps the upper code bits of its few wide blocks in escape planes beside the blocks.
 struct PackedSrc {
-  const void *data = nullptr;   // the blocks: pack_tile_bytes(J) per (row tile, batch)
-  const void *bases = nullptr;  // one 32-bit word per block
+  const void *data = nullptr;   // the blocks: pack_tile_bytes(format, J) per (row tile, batch)
+  const void *bases = nullptr;  // the side words: one 32-bit word per block
+  const void *esc = nullptr;    // format 26: PACK26_ESC_BYTES per escape block, by ordinal
+  int format = 0;               // PACK_FMT28 / PACK_FMT26
+  int64_t escapes = 0;          // escape blocks
   int64_t L = 0, J = 0, T = 0;
 };
-inline int64_t pack_tile_bytes(int64_t J) {
-  const int64_t kfull = J / 16, rem = J - kfull * 16;
-  return kfull * PACK_BLOCK_BYTES + (rem ? PACK_CODE_BYTES + (rem + 3) / 4 * PACK_QUAD_BYTES : 0);
-}
 inline int64_t pack_tiles(int64_t L, int64_t T) { return (L + 255) / 256 * T; }
-inline size_t pack_data_bytes(int64_t L, int64_t J, int64_t T) {
-  return (size_t)pack_tiles(L, T) * (size_t)pack_tile_bytes(J);
+inline int64_t pack_blocks_of(int64_t L, int64_t J, int64_t T) { return pack_tiles(L, T) * ((J + 15) / 16); }
+inline size_t pack_data_bytes(int fmt, int64_t L, int64_t J, int64_t T) {
+  return (size_t)pack_tiles(L, T) * (size_t)pack_tile_bytes(fmt, J);
 }
-inline size_t pack_base_bytes(int64_t L, int64_t J, int64_t T) {
-  return (size_t)pack_tiles(L, T) * (size_t)((J + 15) / 16) * 4;
-}
+inline size_t pack_base_bytes(int64_t L, int64_t J, int64_t T) { return (size_t)pack_blocks_of(L, J, T) * 4; }
+// what pack_survey found: the largest spread of top bytes in a block (-1: this back end, or this
+// shape, has no packed scans) and the blocks whose spread needs an escape plane in format 26
+struct PackSurvey {
+  int spread = -1;
+  int64_t escapes = 0;
+};
 
 constexpr int MAX_ORDER = 8;
 // the floor of a non-negative factor entry (PPALS_NN_FLOOR of the C ABI): not zero, so that no column
@@ -187,15 +191,19 @@ class Ops {
   virtual void scan_store_mode(int mode) { (void)mode; }
   // free device memory in bytes, (size_t)-1: unknown / unlimited
   virtual size_t mem_available() { return (size_t)-1; }
-  // Packed twins of fp32 layouts (PackedSrc). pack_layout fills `data` (pack_data_bytes) and `bases`
-  // (pack_base_bytes) from src viewed as [L, J, T] and returns the largest spread of top bytes in
-  // a block; at PACK_WINDOW or above nothing usable was written (the layout does not qualify).
-  // -1: this back end, or this shape, has no packed scans — such a back end never sees a PackedSrc.
-  // Synchronises.
-  virtual int pack_layout(const void * /*src*/, int /*dt*/, int64_t /*L*/, int64_t /*J*/, int64_t /*T*/,
-                          void * /*data*/, void * /*bases*/) {
-    return -1;
+  // Packed twins of fp32 layouts (PackedSrc), in two steps so that the caller can choose the format
+  // (pack_choose_format) and size the buffers in between. pack_survey looks at src viewed as
+  // [L, J, T] and leaves a provisional word per block in `bases` (pack_base_bytes); a back end
+  // without packed scans answers spread -1 and never sees a PackedSrc. pack_write (after a survey of
+  // the same contents whose spread is below PACK_WINDOW) finishes the side words for `format` and fills
+  // `data` (pack_data_bytes) and, in format 26, `esc` (PACK26_ESC_BYTES per surveyed escape block).
+  // Both synchronise.
+  virtual PackSurvey pack_survey(const void * /*src*/, int /*dt*/, int64_t /*L*/, int64_t /*J*/, int64_t /*T*/,
+                                 void * /*bases*/) {
+    return PackSurvey();
   }
+  virtual void pack_write(const void * /*src*/, int64_t /*L*/, int64_t /*J*/, int64_t /*T*/, int /*format*/,
+                          void * /*bases*/, void * /*data*/, void * /*esc*/) {}
   // the packed twin of the tensor the NEXT scan_contract calls read (nullptr: none). A scan whose
   // shape matches and whose launch is eligible (fp32, at most 16 result columns, the buffer-load
   // route, unpadded, no k-split) reads the twin instead of V; every other scan reads V. The
