@@ -114,24 +114,21 @@ static void split_sizes(const TensorDesc &V, int64_t *M, int64_t *K) {
 // `-tensor r` (test_ALS.cxx:275-286): V = [[W_true]], built on the device
 void tensor_fill_cp(Ops &ops, const TensorDesc &V, int R, const double *Wtrue_flat) {
   const int N = V.order;
-  std::vector<double *> W(N);
+  DeviceBufferTable W;
+  W.resize(N);
   const double *src = Wtrue_flat;
   for (int i = 0; i < N; i++) {
     size_t n = (size_t)V.glens[i] * R;
-    W[i] = (double *)ops.alloc(n * sizeof(double));
+    W.alloc(ops, i, n * sizeof(double));
     ops.h2d(W[i], src, n * sizeof(double));
     src += n;
   }
   int64_t M, K;
   split_sizes(V, &M, &K);
-  double *Q = (double *)ops.alloc(sizeof(double) * M * R);
-  double *Pm = (double *)ops.alloc(sizeof(double) * K * R);
-  split_krp(ops, V, R, W.data(), Q, Pm, &M, &K);
-  ops.fill_rank(V.data, V.dtype, M, K, Q, Pm, R);
+  DeviceBuffer Q(ops, sizeof(double) * M * R), Pm(ops, sizeof(double) * K * R);
+  split_krp(ops, V, R, W.data(), Q.as<double>(), Pm.as<double>(), &M, &K);
+  ops.fill_rank(V.data, V.dtype, M, K, Q.as<double>(), Pm.as<double>(), R);
   ops.sync();
-  ops.free(Q);
-  ops.free(Pm);
-  for (auto p : W) ops.free(p);
 }
 void tensor_fill_uniform(Ops &ops, const TensorDesc &V, uint64_t seed, double lo, double hi) {
   ops.fill_uniform(V.data, V.dtype, V.llens[0], V.glens[0], V.row0, rest_of(V), seed, lo, hi);
@@ -206,13 +203,13 @@ void tensor_fill_collinear(Ops &ops, Comm &comm, const TensorDesc &V, int R, dou
   tensor_fill_cp(ops, V, R, W.data());
   // V += ratio_noise * ||V|| / ||noise|| * noise, noise ~ U(-1,1)   (test_ALS.cxx:259-264)
   const double vnorm = tensor_norm(ops, comm, V);
-  double *d = (double *)ops.alloc(sizeof(double));
+  DeviceBuffer dbuf(ops, sizeof(double));
+  double *d = dbuf.as<double>();
   const uint64_t nseed = seed + 0x5eedull;
   ops.uniform_sumsq(V.llens[0], V.glens[0], V.row0, rest_of(V), nseed, -1.0, 1.0, d);
   if (comm.size() > 1) comm.allreduce_sum(d, 1);
   double nsq = 0;
   ops.d2h(&nsq, d, sizeof(double));
-  ops.free(d);
   const double alpha = ratio_noise * vnorm / std::sqrt(nsq);
   ops.add_uniform_noise(V.data, V.dtype, V.llens[0], V.glens[0], V.row0, rest_of(V), nseed, -1.0,
                         1.0, alpha);
@@ -222,12 +219,12 @@ void tensor_fill_collinear(Ops &ops, Comm &comm, const TensorDesc &V, int R, dou
 double tensor_norm(Ops &ops, Comm &comm, const TensorDesc &V) {
   int64_t M, K;
   split_sizes(V, &M, &K);
-  double *d = (double *)ops.alloc(sizeof(double));
+  DeviceBuffer dbuf(ops, sizeof(double));
+  double *d = dbuf.as<double>();
   ops.residual_sq(V.data, V.dtype, M, K, nullptr, nullptr, 0, d);
   if (comm.size() > 1) comm.allreduce_sum(d, 1);
   double h = 0;
   ops.d2h(&h, d, sizeof(double));
-  ops.free(d);
   return std::sqrt(h);
 }
 
@@ -248,17 +245,17 @@ void tensor_shift(Ops &ops, const TensorDesc &V, int mode, const double *offsets
 }
 void tensor_slice_sumsq(Ops &ops, const TensorDesc &V, int mode, double *ss_host) {
   const PrepShape s = prep_shape(V, mode);
-  double *d = (double *)ops.alloc(sizeof(double) * s.J);
+  DeviceBuffer dbuf(ops, sizeof(double) * s.J);
+  double *d = dbuf.as<double>();
   ops.slice_sumsq(V.data, V.dtype, s.L, s.J, s.T, d);
   ops.d2h(ss_host, d, sizeof(double) * s.J);
-  ops.free(d);
 }
 void tensor_rescale(Ops &ops, const TensorDesc &V, int mode, const double *factors_host) {
   const PrepShape s = prep_shape(V, mode);
-  double *d = (double *)ops.alloc(sizeof(double) * s.J);
+  DeviceBuffer dbuf(ops, sizeof(double) * s.J);
+  double *d = dbuf.as<double>();
   ops.h2d(d, factors_host, sizeof(double) * s.J);
-  ops.scale_slices(V.data, V.dtype, s.L, s.J, s.T, d);
-  ops.free(d);  // (waits for the launch)
+  ops.scale_slices(V.data, V.dtype, s.L, s.J, s.T, d);  // (the buffer's release waits for the launch)
 }
 void tensor_scale(Ops &ops, const TensorDesc &V, int mode, double *rms_host) {
   const PrepShape s = prep_shape(V, mode);
@@ -275,19 +272,10 @@ void tensor_scale(Ops &ops, const TensorDesc &V, int mode, double *rms_host) {
 
 // ============================================================================ N-PLS
 namespace {
-struct DevBuf {  // a device array of doubles for the length of a call
-  Ops &ops;
-  double *p;
-  DevBuf(Ops &o, int64_t n) : ops(o), p((double *)o.alloc(sizeof(double) * (size_t)std::max<int64_t>(n, 1))) {}
-  ~DevBuf() {
-    try {
-      ops.free(p);
-    } catch (...) {
-    }
-  }
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-};
+// a device array of n doubles for the length of a call
+DeviceBuffer doubles(Ops &ops, int64_t n) {
+  return DeviceBuffer(ops, sizeof(double) * (size_t)std::max<int64_t>(n, 1));
+}
 double dotn(const double *a, const double *b, int64_t n) {
   double s = 0;
   for (int64_t i = 0; i < n; i++) s += a[i] * b[i];
@@ -439,17 +427,17 @@ double npls_ww(const NplsDims &d, const double *wall, int g, int h) {
 
 void tensor_contract_mode(Ops &ops, const TensorDesc &V, int mode, const double *U_host, int C, double *Z_host) {
   const PrepShape s = prep_shape(V, mode);
-  DevBuf U(ops, s.J * C), Z(ops, s.L * s.T * C);
-  ops.h2d(U.p, U_host, sizeof(double) * (size_t)(s.J * C));
-  ops.npls_contract(V.data, V.dtype, s.L, s.J, s.T, U.p, C, Z.p);
-  ops.d2h(Z_host, Z.p, sizeof(double) * (size_t)(s.L * s.T * C));
+  DeviceBuffer U = doubles(ops, s.J * C), Z = doubles(ops, s.L * s.T * C);
+  ops.h2d(U.as<double>(), U_host, sizeof(double) * (size_t)(s.J * C));
+  ops.npls_contract(V.data, V.dtype, s.L, s.J, s.T, U.as<double>(), C, Z.as<double>());
+  ops.d2h(Z_host, Z.as<double>(), sizeof(double) * (size_t)(s.L * s.T * C));
 }
 void tensor_slice_inner(Ops &ops, const TensorDesc &V, int mode, const double *W_host, int C, double *S_host) {
   const PrepShape s = prep_shape(V, mode);
-  DevBuf W(ops, s.L * s.T * C), S(ops, s.J * C);
-  ops.h2d(W.p, W_host, sizeof(double) * (size_t)(s.L * s.T * C));
-  ops.npls_slice_inner(V.data, V.dtype, s.L, s.J, s.T, W.p, C, S.p);
-  ops.d2h(S_host, S.p, sizeof(double) * (size_t)(s.J * C));
+  DeviceBuffer W = doubles(ops, s.L * s.T * C), S = doubles(ops, s.J * C);
+  ops.h2d(W.as<double>(), W_host, sizeof(double) * (size_t)(s.L * s.T * C));
+  ops.npls_slice_inner(V.data, V.dtype, s.L, s.J, s.T, W.as<double>(), C, S.as<double>());
+  ops.d2h(S_host, S.as<double>(), sizeof(double) * (size_t)(s.J * C));
 }
 
 void npls_fit(Ops &ops, const TensorDesc &X, int mode, const double *Y, int M, int F, const NplsOpts &o,
@@ -473,19 +461,20 @@ void npls_fit(Ops &ops, const TensorDesc &X, int mode, const double *Y, int M, i
     tensor_slice_sumsq(ops, X, mode, ss.data());
     for (int64_t i = 0; i < I; i++) normX2 += ss[(size_t)i];
   }
-  DevBuf dY(ops, I * M), dZm(ops, LT * M), dZ(ops, LT), dW(ops, LT), dwall(ops, d.sum * F), dE(ops, d.sum);
-  DevBuf dS(ops, std::max<int64_t>(std::max<int64_t>(I, M), std::max<int64_t>(d.sum, 2))), dq(ops, M);
+  DeviceBuffer dY = doubles(ops, I * M), dZm = doubles(ops, LT * M), dZ = doubles(ops, LT), dW = doubles(ops, LT);
+  DeviceBuffer dwall = doubles(ops, d.sum * F), dE = doubles(ops, d.sum), dq = doubles(ops, M);
+  DeviceBuffer dS = doubles(ops, std::max<int64_t>(std::max<int64_t>(I, M), std::max<int64_t>(d.sum, 2)));
   int f = 0;
   for (; f < F; f++) {
     // 1. Z_m of the deflated tensor, without deflating
-    ops.h2d(dY.p, Yres.data(), sizeof(double) * Yres.size());
-    ops.npls_contract(X.data, X.dtype, s.L, I, s.T, dY.p, M, dZm.p);
+    ops.h2d(dY.as<double>(), Yres.data(), sizeof(double) * Yres.size());
+    ops.npls_contract(X.data, X.dtype, s.L, I, s.T, dY.as<double>(), M, dZm.as<double>());
     for (int g = 0; g < f; g++)
       for (int c = 0; c < M; c++) {
         const double coef = dotn(&T[(size_t)I * g], &Yres[(size_t)I * c], I);
         const double *w[MAX_ORDER];
-        for (int k = 0; k < d.K; k++) w[k] = dwall.p + g * d.sum + d.off[k];
-        if (coef != 0) ops.npls_outer_axpy(dZm.p + LT * c, d.ext, d.K, w, -coef);
+        for (int k = 0; k < d.K; k++) w[k] = dwall.as<double>() + g * d.sum + d.off[k];
+        if (coef != 0) ops.npls_outer_axpy(dZm.as<double>() + LT * c, d.ext, d.K, w, -coef);
       }
     // 2. q = e_m*, the column of Y_res with the largest sum of squares
     int best = 0;
@@ -499,25 +488,25 @@ void npls_fit(Ops &ops, const TensorDesc &X, int mode, const double *Y, int M, i
     }
     std::fill(q.begin(), q.end(), 0.0);
     q[(size_t)best] = 1.0;
-    double *w = &wall[(size_t)d.sum * f], *wdev = dwall.p + d.sum * f;
+    double *w = &wall[(size_t)d.sum * f], *wdev = dwall.as<double>() + d.sum * f;
     int status = 0;
     bool ok = true;
     for (int round = 0;; round++) {
       // 3. Z = sum_m q_m Z_m and its best rank-one approximation
-      const double *Zp = dZm.p;
+      const double *Zp = dZm.as<double>();
       if (M > 1) {
-        ops.h2d(dq.p, q.data(), sizeof(double) * (size_t)M);
-        ops.npls_contract(dZm.p, F64, LT, M, 1, dq.p, 1, dZ.p);
-        Zp = dZ.p;
+        ops.h2d(dq.as<double>(), q.data(), sizeof(double) * (size_t)M);
+        ops.npls_contract(dZm.as<double>(), F64, LT, M, 1, dq.as<double>(), 1, dZ.as<double>());
+        Zp = dZ.as<double>();
       }
       bool capped = false;
-      ok = npls_rank_one(ops, d, Zp, o, w, wdev, dW.p, dS.p, dE.p, &capped);
+      ok = npls_rank_one(ops, d, Zp, o, w, wdev, dW.as<double>(), dS.as<double>(), dE.as<double>(), &capped);
       if (!ok) break;
       status = (status & ~1) | (capped ? 1 : 0);
-      npls_outer(ops, d, wdev, -1, dW.p);
+      npls_outer(ops, d, wdev, -1, dW.as<double>());
       // 4. q'_m = <Z_m, W>, normalised
-      ops.npls_slice_inner(dZm.p, F64, LT, M, 1, dW.p, 1, dS.p);
-      ops.d2h(qn.data(), dS.p, sizeof(double) * (size_t)M);
+      ops.npls_slice_inner(dZm.as<double>(), F64, LT, M, 1, dW.as<double>(), 1, dS.as<double>());
+      ops.d2h(qn.data(), dS.as<double>(), sizeof(double) * (size_t)M);
       if (!normalise(qn.data(), M)) {
         ok = false;
         break;
@@ -533,8 +522,8 @@ void npls_fit(Ops &ops, const TensorDesc &X, int mode, const double *Y, int M, i
     }
     if (!ok) break;
     // 5. the raw scores, one pass; t_f of the deflated tensor from them
-    ops.npls_slice_inner(X.data, X.dtype, s.L, I, s.T, dW.p, 1, dS.p);
-    ops.d2h(&S[(size_t)I * f], dS.p, sizeof(double) * (size_t)I);
+    ops.npls_slice_inner(X.data, X.dtype, s.L, I, s.T, dW.as<double>(), 1, dS.as<double>());
+    ops.d2h(&S[(size_t)I * f], dS.as<double>(), sizeof(double) * (size_t)I);
     std::copy(&S[(size_t)I * f], &S[(size_t)I * f] + I, &T[(size_t)I * f]);
     for (int g = 0; g < f; g++) {
       const double ww = npls_ww(d, wall.data(), g, f);
@@ -603,12 +592,12 @@ void npls_predict(Ops &ops, const NplsModel &m, const TensorDesc &Xnew, int ncom
     for (int j = 0; j < d.K; j++)
       std::copy(&m.W[(size_t)j][(size_t)d.ext[j] * g], &m.W[(size_t)j][(size_t)d.ext[j] * g] + d.ext[j],
                 &wall[(size_t)(d.sum * g + d.off[j])]);
-  DevBuf dwall(ops, d.sum * k), dW(ops, d.LT * k), dS(ops, I * k);
-  ops.h2d(dwall.p, wall.data(), sizeof(double) * wall.size());
-  for (int g = 0; g < k; g++) npls_outer(ops, d, dwall.p + d.sum * g, -1, dW.p + d.LT * g);
-  ops.npls_slice_inner(Xnew.data, Xnew.dtype, s.L, I, s.T, dW.p, k, dS.p);
+  DeviceBuffer dwall = doubles(ops, d.sum * k), dW = doubles(ops, d.LT * k), dS = doubles(ops, I * k);
+  ops.h2d(dwall.as<double>(), wall.data(), sizeof(double) * wall.size());
+  for (int g = 0; g < k; g++) npls_outer(ops, d, dwall.as<double>() + d.sum * g, -1, dW.as<double>() + d.LT * g);
+  ops.npls_slice_inner(Xnew.data, Xnew.dtype, s.L, I, s.T, dW.as<double>(), k, dS.as<double>());
   std::vector<double> T((size_t)I * k);
-  ops.d2h(T.data(), dS.p, sizeof(double) * T.size());
+  ops.d2h(T.data(), dS.as<double>(), sizeof(double) * T.size());
   for (int f = 0; f < k; f++)
     for (int g = 0; g < f; g++) {
       const double ww = npls_ww(d, wall.data(), g, f);
@@ -660,15 +649,15 @@ CpEngine::CpEngine(Ops &ops, Comm &comm, const TensorDesc &V, int R, int nstarts
   slice_work_cap_ = slice_work_cap_env();
   W_.resize(N_);
   gradW_.resize(N_);
-  Wprev_.assign(N_, nullptr);
-  Winit_.assign(N_, nullptr);
-  dW_.assign(N_, nullptr);
-  dM_.assign(N_, nullptr);
-  Mm_.assign(N_, nullptr);
+  Wprev_.resize(N_);
+  Winit_.resize(N_);
+  dW_.resize(N_);
+  dM_.resize(N_);
+  Mm_.resize(N_);
   for (int i = 0; i < N_; i++) {
     size_t n = (size_t)V_.glens[i] * R_ * sizeof(double);
-    W_[i] = (double *)ops_.alloc(n);
-    gradW_[i] = (double *)ops_.alloc(n);
+    W_.alloc(ops_, i, n);
+    gradW_.alloc(ops_, i, n);
     ops_.zero(W_[i], n);
     ops_.zero(gradW_[i], n);
     maxs_ = std::max(maxs_, V_.glens[i]);
@@ -676,19 +665,19 @@ CpEngine::CpEngine(Ops &ops, Comm &comm, const TensorDesc &V, int R, int nstarts
   }
   // (a multi-start session keeps the diagonal blocks only: sum_b R_b^2 entries per mode and system)
   const size_t sys_n = multi_ ? (size_t)tab_.sq[K_] : (size_t)R_ * R_;
-  G_ = (double *)ops_.alloc(sizeof(double) * N_ * sys_n);
-  S_ = (double *)ops_.alloc(sizeof(double) * sys_n);
-  Sinv_ = (double *)ops_.alloc(sizeof(double) * sys_n);
-  gradsq_ = (double *)ops_.alloc(sizeof(double) * MAX_ORDER * K_);
-  scal_ = (double *)ops_.alloc(sizeof(double) * 4 * MAX_ORDER);
-  ops_.zero(gradsq_, sizeof(double) * MAX_ORDER * K_);
+  G_ = DeviceBuffer(ops_, sizeof(double) * N_ * sys_n);
+  S_ = DeviceBuffer(ops_, sizeof(double) * sys_n);
+  Sinv_ = DeviceBuffer(ops_, sizeof(double) * sys_n);
+  gradsq_ = DeviceBuffer(ops_, sizeof(double) * MAX_ORDER * K_);
+  scal_ = DeviceBuffer(ops_, sizeof(double) * 4 * MAX_ORDER);
+  ops_.zero(gradsq_.as<double>(), sizeof(double) * MAX_ORDER * K_);
   if (dist_) {
     size_t n = sizeof(double) * (size_t)maxblk_ * P_ * R_;
-    sendbuf_ = (double *)ops_.alloc(n);
-    recvbuf_ = (double *)ops_.alloc(sizeof(double) * (size_t)maxblk_ * R_);
-    gatherbuf_ = (double *)ops_.alloc(n);
-    ops_.zero(sendbuf_, n);
-    ops_.zero(gatherbuf_, n);
+    sendbuf_ = DeviceBuffer(ops_, n);
+    recvbuf_ = DeviceBuffer(ops_, sizeof(double) * (size_t)maxblk_ * R_);
+    gatherbuf_ = DeviceBuffer(ops_, n);
+    ops_.zero(sendbuf_.as<double>(), n);
+    ops_.zero(gatherbuf_.as<double>(), n);
   }
   if (const char *e = std::getenv("PPALS_COMM_SMALL_BYTES")) small_msg_bytes_ = std::atoll(e);
   if (const char *e = std::getenv("PPALS_TEST_BLOCKED_UPDATE")) test_blocks_ = std::atoi(e);
@@ -697,7 +686,7 @@ CpEngine::CpEngine(Ops &ops, Comm &comm, const TensorDesc &V, int R, int nstarts
   if (const char *e = std::getenv("PPALS_PACK_LAYOUT")) pack_mode_ = std::atoi(e) >= 0 && std::atoi(e) <= 2 ? std::atoi(e) : -1;
   if (N_ >= 3) {  // multi-sweep structures exist for every session so the schedule can be switched
     ms_set_roots(ms_choose_roots());
-    ms_scales_ = (double *)ops_.alloc(sizeof(double) * 32);
+    ms_scales_ = DeviceBuffer(ops_, sizeof(double) * 32);
   }
   // The second resident layout is part of the session's set-up, like the tensor itself: built
   // here rather than at the first sweep, whose [dtime] would otherwise carry a one-off multi-GB
@@ -707,7 +696,7 @@ CpEngine::CpEngine(Ops &ops, Comm &comm, const TensorDesc &V, int R, int nstarts
     Layout nat;
     nat.ptr = V_.data;
     for (int m = 0; m < N_; m++) nat.order.push_back(m);
-    lay_.push_back(nat);
+    lay_.push_back(std::move(nat));
   }
   // The block of the first-level intermediate is sized ONCE, for the largest root set plus the
   // slack the online placement choice moves inside (ms_start_step): growing it later would move
@@ -724,7 +713,7 @@ CpEngine::CpEngine(Ops &ops, Comm &comm, const TensorDesc &V, int R, int nstarts
     const size_t avail = ops_.mem_available();
     const double tensor_bytes = (double)V_.nloc * dtype_size(V_.dtype);
     if (avail == (size_t)-1 || (double)avail > 2.0 * tensor_bytes + 6.0 * (double)(xmax + ms_X_slack()) + 8e9)
-      ms_X_alt_ = ops_.try_alloc(xmax + ms_X_slack());
+      ms_X_alt_ = DeviceBuffer::try_alloc(ops_, xmax + ms_X_slack());
   }
   ensure_transposed();
   // the packed twins of the multi-sweep roots: set-up as well (several GB each at the headline)
@@ -734,10 +723,7 @@ CpEngine::CpEngine(Ops &ops, Comm &comm, const TensorDesc &V, int R, int nstarts
       PackedSrc pk;
       if (!ms_set_excluded(r, ms_k_, ms_excl_) && plan_scan(r, ms_k_, false, pl) && pl.Lc > 1) packed_for(pl, pk);
     }
-  if (place) {
-    ms_X_base_ = big_alloc(xmax + ms_X_slack());
-    ms_X_cap_ = xmax + ms_X_slack();
-  }
+  if (place) ms_X_base_ = big_alloc(xmax + ms_X_slack());
   for (int i = 0; i < MAX_ORDER; i++) grad_replicated_[i] = !dist_;
   build_tree(0, N_ - 1, -1);
   leaf_.assign(N_, -1);
@@ -758,59 +744,9 @@ CpEngine::~CpEngine() {
     ops_.sync();
   } catch (...) {
   }
-  for (auto p : W_) ops_.free(p);
-  for (auto p : gradW_) ops_.free(p);
-  for (auto p : Wprev_) ops_.free(p);
-  for (auto p : Winit_) ops_.free(p);
-  for (auto p : dW_) ops_.free(p);
-  for (auto p : dM_) ops_.free(p);
-  for (auto p : Mm_) ops_.free(p);
-  for (auto &n : nodes_) ops_.free(n.buf);
-  lr_release();
-  pp_clear();
-  for (auto &kv : pp_pool_) ops_.free(kv.second.buf);
-  ops_.free(pp_norms_);
-  ops_.free(G_);
-  ops_.free(S_);
-  ops_.free(Sinv_);
-  ops_.free(gradsq_);
-  ops_.free(scal_);
-  ops_.free(sendbuf_);
-  ops_.free(recvbuf_);
-  ops_.free(gatherbuf_);
-  ops_.free(test_blkbuf_);
-  ops_.free(Mbuf_);
-  ops_.free(Qbuf_);
-  ops_.free(xq_);
-  ops_.free(xp_);
-  for (auto q : cc_P_) ops_.free(q);
-  ops_.free(cc_flag_);
-  ops_.free(cc_out_);
-  ops_.free(cc_Y_.ptr);
-  ops_.free(cc_chain_[0].ptr);
-  ops_.free(cc_chain_[1].ptr);
-  ops_.free(cc_core_.ptr);
-  ops_.free(sl_row_.ptr);
-  ops_.free(sl_col_.ptr);
-  ops_.free(sl_out_.ptr);
-  ops_.free(sl_work_.ptr);
-  ops_.free(fms_out_.ptr);
-  ops_.free(fms_work_.ptr);
-  ops_.free(hold_keep_dev_);
-  ops_.free(hold_scores_);
-  ops_.free(Pbuf_);
-  packs_release();
-  for (auto &l : lay_)
-    if (l.owned) ops_.free(l.ptr);
+  // (the placement stopwatches still in flight are read before their blocks go away with the members)
   for (auto &ex : ms_place_)
     if (ex.timer >= 0) ops_.timer_read(ex.timer);
-  ops_.free(ms_X_base_);
-  ops_.free(ms_X_alt_);
-  ops_.free(ms_scales_);
-  for (auto &n : ms_nodes_) {
-    ops_.free(n.t.buf);
-    for (auto &t : n.tmp) ops_.free(t.buf);
-  }
 }
 
 // Second resident layout of the tensor for the RIGHT first-level node: V viewed as the matrix
@@ -903,23 +839,21 @@ void CpEngine::ensure_transposed() {
   // the optional copies back.)
   auto fits = [&](size_t bytes) { return optional_fits(bytes); };
   if (!fits(bytes_of(t))) return;
-  t.ptr = ops_.try_alloc(bytes_of(t));
-  if (!t.ptr) return;
-  t.owned = true;
-  t.bytes = bytes_of(t);
+  t.own = DeviceBuffer::try_alloc(ops_, bytes_of(t));
+  if (!t.own) return;
+  t.ptr = t.own.get();
   fill_layout(t);
-  lay_.push_back(t);
+  lay_.push_back(std::move(t));
   vt_state_ = 1;
   Layout a;
   for (int m = 0; m < N_; m++) a.order.push_back(m);
   choose_pad(a, N_ - 2);
   if (a.q > 0 && fits(bytes_of(a))) {
-    a.ptr = ops_.try_alloc(bytes_of(a));
-    if (a.ptr) {
-      a.owned = true;
-      a.bytes = bytes_of(a);
+    a.own = DeviceBuffer::try_alloc(ops_, bytes_of(a));
+    if (a.own) {
+      a.ptr = a.own.get();
       fill_layout(a);
-      lay_.push_back(a);
+      lay_.push_back(std::move(a));
     }
   }
 }
@@ -1006,24 +940,16 @@ struct PackedScope {
 };
 }  // namespace
 
-void CpEngine::packs_release() {
-  for (auto &t : packs_) {
-    ops_.free(t.data);
-    ops_.free(t.bases);
-    ops_.free(t.esc);
-  }
-  packs_.clear();
-}
+void CpEngine::packs_release() { packs_.clear(); }
 
 // Survey the twin's source, choose its format (pack_choose_format), make room and pack. Called for a
 // new twin and again when the tensor was rewritten: the buffers are kept where the format is the
 // same and the escape planes still fit. On any refusal the twin holds no memory and says why.
 bool CpEngine::pack_fill(PackedTwin &t) {
   auto drop = [&](const std::string &why) {
-    ops_.free(t.data);
-    ops_.free(t.bases);
-    ops_.free(t.esc);
-    t.data = t.bases = t.esc = nullptr;
+    t.data.reset();
+    t.bases.reset();
+    t.esc.reset();
     t.bytes = t.esc_room = 0;
     t.format = 0;
     t.escapes = 0;
@@ -1032,8 +958,8 @@ bool CpEngine::pack_fill(PackedTwin &t) {
   };
   const bool forced = pack_mode_ == 1 || pack_mode_ == 2;
   const size_t bb = pack_base_bytes(t.L, t.J, t.T);
-  if (!t.bases && !(t.bases = ops_.try_alloc(bb))) return drop("allocation failed");
-  const PackSurvey sv = ops_.pack_survey(t.src, V_.dtype, t.L, t.J, t.T, t.bases);
+  if (!t.bases && !(t.bases = DeviceBuffer::try_alloc(ops_, bb))) return drop("allocation failed");
+  const PackSurvey sv = ops_.pack_survey(t.src, V_.dtype, t.L, t.J, t.T, t.bases.get());
   if (sv.spread < 0) return drop("scan shape has no packed route");
   if (sv.spread >= PACK_WINDOW)
     return drop("top bytes of a block span " + std::to_string(sv.spread + 1) + " values (window 16)");
@@ -1042,17 +968,16 @@ bool CpEngine::pack_fill(PackedTwin &t) {
   const size_t db = pack_data_bytes(fmt, t.L, t.J, t.T);
   const size_t eb = fmt == PACK_FMT26 ? (size_t)sv.escapes * PACK26_ESC_BYTES : 0;
   if (t.data && (fmt != t.format || eb > t.esc_room)) {
-    ops_.free(t.data);
-    ops_.free(t.esc);
-    t.data = t.esc = nullptr;
+    t.data.reset();
+    t.esc.reset();
     t.esc_room = 0;
   }
   if (!t.data) {
     if (!forced && db + bb + eb >= (size_t)t.L * (size_t)t.J * (size_t)t.T * 4)
       return drop("row tiles would pad away what packing saves");  // (a batch ends with a whole tile of 256 rows)
     if (!optional_fits(db + eb)) return drop("no room beside what the session still allocates");
-    t.data = ops_.try_alloc(db);
-    t.esc = t.data && eb ? ops_.try_alloc(eb) : nullptr;
+    t.data = DeviceBuffer::try_alloc(ops_, db);
+    if (t.data && eb) t.esc = DeviceBuffer::try_alloc(ops_, eb);
     if (!t.data || (eb && !t.esc)) return drop("allocation failed");
     t.esc_room = eb;
   }
@@ -1060,7 +985,7 @@ bool CpEngine::pack_fill(PackedTwin &t) {
   t.escapes = sv.escapes;  // (as surveyed, whichever format was chosen)
   t.bytes = db + bb + eb;
   t.reason.clear();
-  ops_.pack_write(t.src, t.L, t.J, t.T, fmt, t.bases, t.data, t.esc);
+  ops_.pack_write(t.src, t.L, t.J, t.T, fmt, t.bases.get(), t.data.get(), t.esc.get());
   return true;
 }
 
@@ -1091,13 +1016,13 @@ const PackedSrc *CpEngine::packed_for(const ScanPlan &pl, PackedSrc &out) {
       n.reason = "scan shape has no packed route";  // (no whole lanes of 4 rows)
     else
       pack_fill(n);
-    packs_.push_back(n);
+    packs_.push_back(std::move(n));
     t = &packs_.back();
   }
   if (!t->data) return nullptr;
-  out.data = t->data;
-  out.bases = t->bases;
-  out.esc = t->esc;
+  out.data = t->data.get();
+  out.bases = t->bases.get();
+  out.esc = t->esc.get();
   out.format = t->format;
   out.escapes = t->escapes;
   out.L = t->L;
@@ -1114,7 +1039,7 @@ void CpEngine::check_tensor_generation() {
   if (!V_.generation || *V_.generation == tensor_gen_) return;
   tensor_gen_ = *V_.generation;
   for (const auto &l : lay_)
-    if (l.owned) fill_layout(l);
+    if (l.own) fill_layout(l);
   // packed twins: pre-pass and pack again; a twin that no longer qualifies is dropped, one that was
   // refused for its values gets another look at its next scan. The third rewrite ends packing.
   if (++pack_regen_ >= 3) {
@@ -1126,7 +1051,7 @@ void CpEngine::check_tensor_generation() {
     for (size_t k = 0; k < packs_.size();) {
       if (packs_[k].data && pack_fill(packs_[k])) {
         k++;
-      } else if (packs_[k].data == nullptr && packs_[k].reason.compare(0, 9, "top bytes") != 0) {
+      } else if (!packs_[k].data && packs_[k].reason.compare(0, 9, "top bytes") != 0) {
         k++;  // (refused for its shape or for memory: that has not changed)
       } else {
         packs_.erase(packs_.begin() + k);
@@ -1166,7 +1091,7 @@ void CpEngine::build_tree(int lo, int hi, int parent) {
     n.slo = ranges[1 - c][0];
     n.shi = ranges[1 - c][1];
     n.elems = 0;
-    nodes_.push_back(n);
+    nodes_.push_back(std::move(n));
     idx[c] = (int)nodes_.size() - 1;
   }
   build_tree(lo, mid, idx[0]);
@@ -1186,7 +1111,7 @@ void CpEngine::compute_node(int idx) {
   Node &n = nodes_[idx];
   if (n.valid) return;
   n.elems = prod_ext(n.lo, n.hi);
-  if (!n.buf) n.buf = (double *)ops_.alloc(sizeof(double) * (size_t)n.elems * R_);
+  if (!n.buf) n.buf = DeviceBuffer(ops_, sizeof(double) * (size_t)n.elems * R_);
   FactorRef f[MAX_ORDER];
   int nf = 0;
   for (int m = n.slo; m <= n.shi; m++) f[nf++] = fref(m, W_.data());
@@ -1199,39 +1124,39 @@ void CpEngine::compute_node(int idx) {
     if (!plan_scan(n.slo, n.shi - n.slo + 1, false, pl))
       throw std::runtime_error("ppals: internal error (tree node not adjacent)");
     if (pl.Lc == 1 && !sib_is_suffix) {
-      ops_.scan_contract(V_.data, V_.dtype, 1, J, n.elems, f, nf, R_, n.buf, F64, 1, n.elems);
+      ops_.scan_contract(V_.data, V_.dtype, 1, J, n.elems, f, nf, R_, n.buf.as<double>(), F64, 1, n.elems);
     } else {
       if (pl.T != 1 || pl.Lc != n.elems || pl.J != J)
         throw std::runtime_error("ppals: internal error (tree node scan shape)");
       PackedSrc pk_store;
       PackedScope scope(ops_, packed_for(pl, pk_store));
-      ops_.scan_contract(pl.lay->ptr, V_.dtype, pl.L, J, 1, f, nf, R_, n.buf, F64, n.elems, n.elems,
+      ops_.scan_contract(pl.lay->ptr, V_.dtype, pl.L, J, 1, f, nf, R_, n.buf.as<double>(), F64, n.elems, n.elems,
                          pl.pad);
     }
   } else {
     compute_node(n.parent);
     const Node &p = nodes_[n.parent];
     if (sib_is_suffix)
-      ops_.mttv(p.buf, F64, n.elems, J, 1, f, nf, R_, n.buf, n.elems, 0, nullptr);
+      ops_.mttv(p.buf.as<double>(), F64, n.elems, J, 1, f, nf, R_, n.buf.as<double>(), n.elems, 0, nullptr);
     else
-      ops_.mttv(p.buf, F64, 1, J, n.elems, f, nf, R_, n.buf, n.elems, 0, nullptr);
+      ops_.mttv(p.buf.as<double>(), F64, 1, J, n.elems, f, nf, R_, n.buf.as<double>(), n.elems, 0, nullptr);
   }
   n.valid = true;
 }
 
 void CpEngine::refresh_grams() {
-  if (multi_ && ragged_) {  // Gram (start b, mode i) at G_ + N sq_b + i R_b^2
-    for (int i = 0; i < N_; i++) ops_.gram_ragged(W_[i], V_.glens[i], V_.glens[i], tab_, N_, i, G_);
+  if (multi_ && ragged_) {  // Gram (start b, mode i) at G_.as<double>() + N sq_b + i R_b^2
+    for (int i = 0; i < N_; i++) ops_.gram_ragged(W_[i], V_.glens[i], V_.glens[i], tab_, N_, i, G_.as<double>());
     return;
   }
-  if (multi_) {  // the diagonal blocks only: Gram (start b, mode i) at G_ + (b N + i) Rs^2
+  if (multi_) {  // the diagonal blocks only: Gram (start b, mode i) at G_.as<double>() + (b N + i) Rs^2
     for (int i = 0; i < N_; i++)
-      ops_.gram_batched(W_[i], V_.glens[i], V_.glens[i], Rs_, K_, G_ + (size_t)i * Rs_ * Rs_,
+      ops_.gram_batched(W_[i], V_.glens[i], V_.glens[i], Rs_, K_, G_.as<double>() + (size_t)i * Rs_ * Rs_,
                         (int64_t)N_ * Rs_ * Rs_);
     return;
   }
   for (int i = 0; i < N_; i++)
-    ops_.gram(W_[i], V_.glens[i], V_.glens[i], R_, G_ + (size_t)i * R_ * R_);
+    ops_.gram(W_[i], V_.glens[i], V_.glens[i], R_, G_.as<double>() + (size_t)i * R_ * R_);
 }
 
 void CpEngine::set_factors(const double *Wflat, const double *gradWflat) {
@@ -1253,7 +1178,7 @@ void CpEngine::set_factors(const double *Wflat, const double *gradWflat) {
   }
   // per-mode ||grad_W[i]||^2 of the caller's gradients: a partial sweep (class API steps) mixes
   // them with the modes updated so far, exactly like CPD::update_gradnorm (src/CP.cxx:89-96)
-  ops_.h2d(gradsq_, gsi, sizeof(double) * MAX_ORDER);
+  ops_.h2d(gradsq_.as<double>(), gsi, sizeof(double) * MAX_ORDER);
   for (int i = 0; i < MAX_ORDER; i++) grad_replicated_[i] = true;
   // iter-0 [gradnorm] is the norm of the caller's initial grad_W (test_ALS.cxx:338,
   // als_CP.cxx:174-181)
@@ -1321,7 +1246,7 @@ void CpEngine::set_mode_kinds(const int *kinds) {
   for (int i = 0; i < N_; i++) {
     if (kinds[i] == kModeFixed && kind_[i] != kModeFixed) {  // its gradient is zero from here on
       ops_.zero(gradW_[i], sizeof(double) * (size_t)V_.glens[i] * R_);
-      ops_.zero(gradsq_ + (size_t)i * K_, sizeof(double) * K_);
+      ops_.zero(gradsq_.as<double>() + (size_t)i * K_, sizeof(double) * K_);
       grad_replicated_[i] = true;
     }
     kind_[i] = kinds[i];
@@ -1387,7 +1312,7 @@ void CpEngine::set_factors_start(int start, const double *Wflat, const double *g
         }
         g += n;
       }
-      ops_.h2d(gradsq_ + (size_t)i * K_ + b, &gsq, sizeof(double));
+      ops_.h2d(gradsq_.as<double>() + (size_t)i * K_ + b, &gsq, sizeof(double));
     }
   if (hold_mode_ >= 0) {  // the caller's held-out rows of these starts move into the scores
     unsigned sel = 0;
@@ -1396,7 +1321,7 @@ void CpEngine::set_factors_start(int start, const double *Wflat, const double *g
     if (!g) {  // (no gradients: the sums stay 0, whatever the gradient buffer still holds)
       const double zero = 0;
       for (int b = b0; b < b1; b++)
-        if ((hold_mask_ >> b) & 1u) ops_.h2d(gradsq_ + (size_t)hold_mode_ * K_ + b, &zero, sizeof(double));
+        if ((hold_mask_ >> b) & 1u) ops_.h2d(gradsq_.as<double>() + (size_t)hold_mode_ * K_ + b, &zero, sizeof(double));
     }
   }
   refresh_grams();
@@ -1409,8 +1334,9 @@ void CpEngine::hold_apply(unsigned starts) {
   const unsigned sel = hold_mask_ & starts;
   if (hold_mode_ < 0 || !sel) return;
   const int64_t s = V_.glens[hold_mode_];
-  ops_.cp_hold_rows(W_[hold_mode_], s, gradW_[hold_mode_], s, hold_scores_, s, s, tab_, hold_keep_dev_, sel, G_, N_,
-                    hold_mode_, gradsq_ + (size_t)hold_mode_ * K_);
+  ops_.cp_hold_rows(W_[hold_mode_], s, gradW_[hold_mode_], s, hold_scores_.as<double>(), s, s, tab_,
+                    hold_keep_dev_.as<uint8_t>(), sel, G_.as<double>(), N_,
+                    hold_mode_, gradsq_.as<double>() + (size_t)hold_mode_ * K_);
 }
 
 void CpEngine::set_holdout(int mode, const uint8_t *keep) {
@@ -1432,17 +1358,15 @@ void CpEngine::set_holdout(int mode, const uint8_t *keep) {
   }
   if (!hold_keep_dev_ || hold_rows_ != s) {
     ops_.sync();
-    ops_.free(hold_keep_dev_);
-    ops_.free(hold_scores_);
-    hold_keep_dev_ = nullptr;
-    hold_scores_ = nullptr;
-    hold_keep_dev_ = (uint8_t *)ops_.alloc((size_t)K_ * s);
-    hold_scores_ = (double *)ops_.alloc(sizeof(double) * (size_t)s * R_);
+    hold_keep_dev_.reset();
+    hold_scores_.reset();
+    hold_keep_dev_ = DeviceBuffer(ops_, (size_t)K_ * s);
+    hold_scores_ = DeviceBuffer(ops_, sizeof(double) * (size_t)s * R_);
     hold_rows_ = s;
   }
   hold_keep_.assign(keep, keep + (size_t)K_ * s);
-  ops_.h2d(hold_keep_dev_, hold_keep_.data(), hold_keep_.size());
-  ops_.zero(hold_scores_, sizeof(double) * (size_t)s * R_);
+  ops_.h2d(hold_keep_dev_.as<uint8_t>(), hold_keep_.data(), hold_keep_.size());
+  ops_.zero(hold_scores_.as<double>(), sizeof(double) * (size_t)s * R_);
   hold_mode_ = mode;
   hold_mask_ = mask;
   hold_apply(~0u);
@@ -1454,7 +1378,7 @@ void CpEngine::heldout_scores(int start, double *out) {
   if (!multi_ || hold_mode_ < 0) throw std::logic_error("ppals: the session has no hold-out");
   if (start < 0 || start >= K_) throw std::runtime_error("ppals: start out of range");
   const int64_t s = V_.glens[hold_mode_];
-  ops_.d2h(out, hold_scores_ + (size_t)s * tab_.col[start], sizeof(double) * (size_t)s * tab_.rank(start));
+  ops_.d2h(out, hold_scores_.as<double>() + (size_t)s * tab_.col[start], sizeof(double) * (size_t)s * tab_.rank(start));
 }
 
 void CpEngine::get_factors_start(int start, double *Wflat, double *gradWflat) {
@@ -1479,7 +1403,7 @@ void CpEngine::get_factors_start(int start, double *Wflat, double *gradWflat) {
 void CpEngine::gradnorms(double *out) {
   if (!multi_) throw std::logic_error("ppals: not a multi-start session");
   std::vector<double> h((size_t)N_ * K_);
-  ops_.d2h(h.data(), gradsq_, sizeof(double) * h.size());
+  ops_.d2h(h.data(), gradsq_.as<double>(), sizeof(double) * h.size());
   for (int b = 0; b < K_; b++) {
     double sum = 0;
     for (int i = 0; i < N_; i++) sum += h[(size_t)i * K_ + b];
@@ -1492,16 +1416,16 @@ void CpEngine::residuals(double *out) {
   if (!multi_) throw std::logic_error("ppals: not a multi-start session");
   int64_t M, K;
   split_sizes(V_, &M, &K);
-  if (!Qbuf_) Qbuf_ = (double *)ops_.alloc(sizeof(double) * M * Rs_);  // (Rs_: the largest start)
-  if (!Pbuf_) Pbuf_ = (double *)ops_.alloc(sizeof(double) * K * Rs_);
+  if (!Qbuf_) Qbuf_ = DeviceBuffer(ops_, sizeof(double) * M * Rs_);  // (Rs_: the largest start)
+  if (!Pbuf_) Pbuf_ = DeviceBuffer(ops_, sizeof(double) * K * Rs_);
   std::vector<double *> Wb(N_);
   for (int b = 0; b < K_; b++) {
     const int rb = tab_.rank(b);
     for (int i = 0; i < N_; i++) Wb[i] = W_[i] + (size_t)tab_.col[b] * V_.glens[i];
-    split_krp(ops_, V_, rb, Wb.data(), Qbuf_, Pbuf_, &M, &K);
-    ops_.residual_sq(V_.data, V_.dtype, M, K, Qbuf_, Pbuf_, rb, scal_);
+    split_krp(ops_, V_, rb, Wb.data(), Qbuf_.as<double>(), Pbuf_.as<double>(), &M, &K);
+    ops_.residual_sq(V_.data, V_.dtype, M, K, Qbuf_.as<double>(), Pbuf_.as<double>(), rb, scal_.as<double>());
     double h = 0;
-    ops_.d2h(&h, scal_, sizeof(double));
+    ops_.d2h(&h, scal_.as<double>(), sizeof(double));
     out[b] = std::sqrt(h);
   }
 }
@@ -1550,15 +1474,16 @@ void CpEngine::take_from(CpEngine &src, int start, bool predicted) {
     const size_t at = (size_t)V_.glens[i] * src.tab_.col[start];
     ops_.d2d(W_[i], src.W_[i] + at, n * sizeof(double));
     ops_.d2d(gradW_[i], src.gradW_[i] + at, n * sizeof(double));
-    ops_.d2d(gradsq_ + i, src.gradsq_ + (size_t)i * src.K_ + start, sizeof(double));
+    ops_.d2d(gradsq_.as<double>() + i, src.gradsq_.as<double>() + (size_t)i * src.K_ + start, sizeof(double));
     if (kind_[i] == kModeFixed) {  // (a FIXED mode's gradient is zero and stays zero)
       ops_.zero(gradW_[i], n * sizeof(double));
-      ops_.zero(gradsq_ + i, sizeof(double));
+      ops_.zero(gradsq_.as<double>() + i, sizeof(double));
     }
   }
   if (predicted) {  // the scores into the (zero) held-out rows: W + scores, the kept rows of the scores are 0
     const int m = src.hold_mode_;
-    ops_.add_inplace(W_[m], src.hold_scores_ + (size_t)V_.glens[m] * src.tab_.col[start], V_.glens[m] * R_);
+    ops_.add_inplace(W_[m], src.hold_scores_.as<double>() + (size_t)V_.glens[m] * src.tab_.col[start],
+                     V_.glens[m] * R_);
   }
   // (gradnorm() reads the copied per-mode sums: the same number set_factors would have formed on the
   // host from these gradients, with no read-back here)
@@ -1583,9 +1508,9 @@ void CpEngine::get_factors(double *Wflat, double *gradWflat) {
       if (dist_ && grad_from_sweep_ && !grad_replicated_[i]) {
         // every rank holds only its own row block of grad_W: gather it
         const int64_t blk = block_rows(V_.glens[i], P_);
-        ops_.pack_blocks(gradW_[i], V_.glens[i], V_.glens[i], R_, blk, P_, gatherbuf_);
-        comm_.allgather(gatherbuf_ + (size_t)rank_ * blk * R_, gatherbuf_, blk * R_);
-        ops_.unpack_blocks(gatherbuf_, V_.glens[i], V_.glens[i], R_, blk, P_, gradW_[i]);
+        ops_.pack_blocks(gradW_[i], V_.glens[i], V_.glens[i], R_, blk, P_, gatherbuf_.as<double>());
+        comm_.allgather(gatherbuf_.as<double>() + (size_t)rank_ * blk * R_, gatherbuf_.as<double>(), blk * R_);
+        ops_.unpack_blocks(gatherbuf_.as<double>(), V_.glens[i], V_.glens[i], R_, blk, P_, gradW_[i]);
       }
       ops_.d2h(g, gradW_[i], n * sizeof(double));
       g += n;
@@ -1598,47 +1523,50 @@ void CpEngine::get_factors(double *Wflat, double *gradWflat) {
 void CpEngine::mode_update(int i, const double *M, int64_t ldm, double lambda, bool pp,
                            double ratio) {
   const int64_t s = V_.glens[i];
+  double *const G = G_.as<double>(), *const S = S_.as<double>(), *const Sinv = Sinv_.as<double>();
+  double *const gradsq = gradsq_.as<double>(), *const sendbuf = sendbuf_.as<double>();
+  double *const recvbuf = recvbuf_.as<double>(), *const gatherbuf = gatherbuf_.as<double>();
   const bool hals = kind_[i] == kModeNonneg;  // this mode's update is the HALS pass
   if (kind_[i] == kModeFixed) throw std::logic_error("ppals: a FIXED mode has no update");
   if (kind_[i] == kModeOrtho) {  // the polar factor of M, start by start through the table (one start here
     // when the session is an ordinary one); the hold-out mode is never ORTHO (set_mode_kinds, set_holdout)
     if (pp || dist_) throw std::logic_error("ppals: an orthonormal mode updates exactly, on one rank");
-    ops_.cp_mode_update_ortho_ragged(G_, N_, i, start_table(), lambda, M, ldm, W_[i], s, gradW_[i], s, s,
-                                     gradsq_ + (size_t)i * K_, S_);
+    ops_.cp_mode_update_ortho_ragged(G, N_, i, start_table(), lambda, M, ldm, W_[i], s, gradW_[i], s, s,
+                                     gradsq + (size_t)i * K_, S);
     return;
   }
   if (hals && shape_[i] != kShapeNone) {  // column by column onto the shape's set, through the table as ORTHO
     // goes; the hold-out mode never has a shape (set_mode_shapes, set_holdout)
     if (pp || dist_) throw std::logic_error("ppals: a shaped mode updates exactly, on one rank");
-    ops_.cp_mode_update_shape_ragged(G_, N_, i, start_table(), lambda, M, ldm, W_[i], s, gradW_[i], s, s,
-                                     gradsq_ + (size_t)i * K_, S_, shape_[i]);
+    ops_.cp_mode_update_shape_ragged(G, N_, i, start_table(), lambda, M, ldm, W_[i], s, gradW_[i], s, s,
+                                     gradsq + (size_t)i * K_, S, shape_[i]);
     return;
   }
   if (multi_) {  // block-diagonal over starts: one batched update, every start its own system
     if (pp) throw std::logic_error("ppals: no PP update in a multi-start session");
     if (ragged_) {  // starts of different ranks: the same updates, addressed through the table
       if (hals)
-        ops_.cp_mode_update_nn_ragged(G_, N_, i, tab_, lambda, M, ldm, W_[i], s, gradW_[i], s, s,
-                                      gradsq_ + (size_t)i * K_, S_);
+        ops_.cp_mode_update_nn_ragged(G, N_, i, tab_, lambda, M, ldm, W_[i], s, gradW_[i], s, s,
+                                      gradsq + (size_t)i * K_, S);
       else
-        ops_.cp_mode_update_ragged(G_, N_, i, tab_, lambda, M, ldm, W_[i], s, gradW_[i], s, s,
-                                   gradsq_ + (size_t)i * K_, S_, Sinv_);
+        ops_.cp_mode_update_ragged(G, N_, i, tab_, lambda, M, ldm, W_[i], s, gradW_[i], s, s,
+                                   gradsq + (size_t)i * K_, S, Sinv);
     } else if (hals) {  // one HALS pass per start, all starts in one batched update
-      ops_.cp_mode_update_nn_batched(G_, N_, i, Rs_, K_, lambda, M, ldm, W_[i], s, gradW_[i], s, s,
-                                     gradsq_ + (size_t)i * K_, S_);
+      ops_.cp_mode_update_nn_batched(G, N_, i, Rs_, K_, lambda, M, ldm, W_[i], s, gradW_[i], s, s,
+                                     gradsq + (size_t)i * K_, S);
     } else {
-      ops_.cp_mode_update_batched(G_, N_, i, Rs_, K_, lambda, M, ldm, W_[i], s, gradW_[i], s, s,
-                                  gradsq_ + (size_t)i * K_, S_, Sinv_);
+      ops_.cp_mode_update_batched(G, N_, i, Rs_, K_, lambda, M, ldm, W_[i], s, gradW_[i], s, s,
+                                  gradsq + (size_t)i * K_, S, Sinv);
     }
     // the sample mode of a hold-out session: the rows just computed for held-out samples are their
     // predicted scores — moved aside, and zero again before another mode reads the factor
     if (i == hold_mode_) hold_apply(~0u);
     return;
   }
-  double *Gi = G_ + (size_t)i * R_ * R_;
+  double *Gi = G + (size_t)i * R_ * R_;
   if (hals) {  // one HALS pass in place of the solve (set_nonneg admits one-rank sessions only)
     if (pp || dist_) throw std::logic_error("ppals: a non-negative session updates exactly, on one rank");
-    ops_.cp_mode_update_nn(G_, N_, i, R_, lambda, M, ldm, W_[i], s, gradW_[i], s, s, gradsq_ + i, S_);
+    ops_.cp_mode_update_nn(G, N_, i, R_, lambda, M, ldm, W_[i], s, gradW_[i], s, s, gradsq + i, S);
     return;
   }
   if (!dist_) {
@@ -1649,17 +1577,17 @@ void CpEngine::mode_update(int i, const double *M, int64_t ldm, double lambda, b
       const int64_t blk = s / test_blocks_;
       const size_t bytes = sizeof(double) * (size_t)s * R_;
       if (!test_blkbuf_) {
-        test_blkbuf_ = (double *)ops_.alloc(2 * sizeof(double) * (size_t)maxs_ * R_);
+        test_blkbuf_ = DeviceBuffer(ops_, 2 * sizeof(double) * (size_t)maxs_ * R_);
       }
-      ops_.pack_blocks(M, s, ldm, R_, blk, test_blocks_, test_blkbuf_);
-      ops_.cp_mode_update_blocked(G_, N_, i, R_, lambda, test_blkbuf_, blk, test_blocks_,
-                                  test_blkbuf_ + bytes / sizeof(double), W_[i], s, gradW_[i], s, s,
-                                  gradsq_ + i, nullptr, s, nullptr, s, ratio, S_, Sinv_);
+      ops_.pack_blocks(M, s, ldm, R_, blk, test_blocks_, test_blkbuf_.as<double>());
+      ops_.cp_mode_update_blocked(G, N_, i, R_, lambda, test_blkbuf_.as<double>(), blk, test_blocks_,
+                                  test_blkbuf_.as<double>() + bytes / sizeof(double), W_[i], s, gradW_[i], s, s,
+                                  gradsq + i, nullptr, s, nullptr, s, ratio, S, Sinv);
       return;
     }
-    ops_.cp_mode_update(G_, N_, i, R_, lambda, M, ldm, W_[i], s, gradW_[i], s, s, gradsq_ + i,
-                        pp ? Winit_[i] : nullptr, s, pp ? dW_[i] : nullptr, s, ratio, S_, Sinv_,
-                        (pp && pp_norms_) ? pp_norms_ + 2 * i : nullptr);
+    ops_.cp_mode_update(G, N_, i, R_, lambda, M, ldm, W_[i], s, gradW_[i], s, s, gradsq + i,
+                        pp ? Winit_[i] : nullptr, s, pp ? dW_[i] : nullptr, s, ratio, S, Sinv,
+                        (pp && pp_norms_.as<double>()) ? pp_norms_.as<double>() + 2 * i : nullptr);
     return;
   } else if (i != 0 && (int64_t)sizeof(double) * s * R_ <= small_msg_bytes_) {
     // latency regime (s x R is a few KB): ONE all-reduce of the partial rows, then every rank runs
@@ -1667,8 +1595,8 @@ void CpEngine::mode_update(int i, const double *M, int64_t ldm, double lambda, b
     // collapsed into a single collective, and the same fused launch as on one GPU.
     if (ldm != s) throw std::runtime_error("ppals: partial MTTKRP must be contiguous");
     comm_.allreduce_sum(const_cast<double *>(M), s * R_);
-    ops_.cp_mode_update(G_, N_, i, R_, lambda, M, ldm, W_[i], s, gradW_[i], s, s, gradsq_ + i,
-                        pp ? Winit_[i] : nullptr, s, pp ? dW_[i] : nullptr, s, ratio, S_, Sinv_);
+    ops_.cp_mode_update(G, N_, i, R_, lambda, M, ldm, W_[i], s, gradW_[i], s, s, gradsq + i,
+                        pp ? Winit_[i] : nullptr, s, pp ? dW_[i] : nullptr, s, ratio, S, Sinv);
     grad_replicated_[i] = true;
     return;
   } else if (i == 0 && (int64_t)sizeof(double) * s * R_ <= small_msg_bytes_) {
@@ -1677,27 +1605,27 @@ void CpEngine::mode_update(int i, const double *M, int64_t ldm, double lambda, b
     // fused update on the assembled s x R matrix.
     const int64_t blk = block_rows(s, P_);
     const int64_t nr = std::max<int64_t>(0, std::min(blk, s - blk * rank_));
-    double *mine = gatherbuf_ + (size_t)rank_ * blk * R_;
+    double *mine = gatherbuf + (size_t)rank_ * blk * R_;
     if (blk * P_ == s && ldm == blk && nr == blk) {
       // equal blocks: the local leaf IS this rank's block as the all-gather wants it (no pack launch),
       // and the fused update reads the gathered blocks as they lie (no unpack launch)
-      comm_.allgather(M, gatherbuf_, blk * R_);
-      ops_.cp_mode_update_blocked(G_, N_, i, R_, lambda, gatherbuf_, blk, P_, sendbuf_, W_[i], s, gradW_[i],
-                                  s, s, gradsq_ + i, pp ? Winit_[i] : nullptr, s, pp ? dW_[i] : nullptr, s,
-                                  ratio, S_, Sinv_);
+      comm_.allgather(M, gatherbuf, blk * R_);
+      ops_.cp_mode_update_blocked(G, N_, i, R_, lambda, gatherbuf, blk, P_, sendbuf, W_[i], s, gradW_[i],
+                                  s, s, gradsq + i, pp ? Winit_[i] : nullptr, s, pp ? dW_[i] : nullptr, s,
+                                  ratio, S, Sinv);
       grad_replicated_[i] = true;
       return;
     }
     ops_.pack_blocks(M, nr, ldm, R_, blk, 1, mine);
-    comm_.allgather(mine, gatherbuf_, blk * R_);
-    ops_.unpack_blocks(gatherbuf_, s, s, R_, blk, P_, sendbuf_);
-    ops_.cp_mode_update(G_, N_, i, R_, lambda, sendbuf_, s, W_[i], s, gradW_[i], s, s, gradsq_ + i,
-                        pp ? Winit_[i] : nullptr, s, pp ? dW_[i] : nullptr, s, ratio, S_, Sinv_);
+    comm_.allgather(mine, gatherbuf, blk * R_);
+    ops_.unpack_blocks(gatherbuf, s, s, R_, blk, P_, sendbuf);
+    ops_.cp_mode_update(G, N_, i, R_, lambda, sendbuf, s, W_[i], s, gradW_[i], s, s, gradsq + i,
+                        pp ? Winit_[i] : nullptr, s, pp ? dW_[i] : nullptr, s, ratio, S, Sinv);
     grad_replicated_[i] = true;
     return;
   } else {
     grad_replicated_[i] = false;
-    ops_.gram_system(G_, N_, i, R_, lambda, S_, Sinv_);
+    ops_.gram_system(G, N_, i, R_, lambda, S, Sinv);
     const int64_t blk = block_rows(s, P_);
     const int64_t r0 = blk * rank_;
     const int64_t nr = std::max<int64_t>(0, std::min(blk, s - r0));
@@ -1707,23 +1635,23 @@ void CpEngine::mode_update(int i, const double *M, int64_t ldm, double lambda, b
       Mblk = M;
       ldb = ldm;
     } else {
-      ops_.pack_blocks(M, s, ldm, R_, blk, P_, sendbuf_);
-      comm_.reduce_scatter_sum(sendbuf_, recvbuf_, blk * R_);
-      Mblk = recvbuf_;
+      ops_.pack_blocks(M, s, ldm, R_, blk, P_, sendbuf);
+      comm_.reduce_scatter_sum(sendbuf, recvbuf, blk * R_);
+      Mblk = recvbuf;
       ldb = blk;
     }
-    double *mine = gatherbuf_ + (size_t)rank_ * blk * R_;
+    double *mine = gatherbuf + (size_t)rank_ * blk * R_;
     // SVD_solve_mod tail (common.cxx:753-756): the row block is written as W_init + ratio *
     // (M S^-1 - W_init) already, so after the gather dW = W - W_init holds for every row
-    ops_.cp_update(Mblk, ldb, W_[i] + r0, s, mine, blk, gradW_[i] + r0, s, nr, R_, S_, Sinv_,
-                   gradsq_ + i, pp ? Winit_[i] + r0 : nullptr, s, pp ? dW_[i] + r0 : nullptr, s,
+    ops_.cp_update(Mblk, ldb, W_[i] + r0, s, mine, blk, gradW_[i] + r0, s, nr, R_, S, Sinv,
+                   gradsq + i, pp ? Winit_[i] + r0 : nullptr, s, pp ? dW_[i] + r0 : nullptr, s,
                    ratio);
-    comm_.allgather(mine, gatherbuf_, blk * R_);
-    ops_.unpack_blocks(gatherbuf_, s, s, R_, blk, P_, W_[i]);
+    comm_.allgather(mine, gatherbuf, blk * R_);
+    ops_.unpack_blocks(gatherbuf, s, s, R_, blk, P_, W_[i]);
     if (pp) {
       double *A[1] = {W_[i]}, *B[1] = {Winit_[i]}, *D[1] = {dW_[i]};
       int64_t n[1] = {s * R_};
-      ops_.diff_norms(A, B, n, 1, 1, D, 0, scal_ + 2 * MAX_ORDER);
+      ops_.diff_norms(A, B, n, 1, 1, D, 0, scal_.as<double>() + 2 * MAX_ORDER);
     }
   }
   ops_.gram(W_[i], s, s, R_, Gi);
@@ -1756,8 +1684,8 @@ void CpEngine::normalize() {
   for (int i = 0; i < N_; i++) rows[i] = V_.glens[i];
   unsigned masks[32] = {0}, fresh = 0;
   const unsigned active = ms_collect_scales(masks, &fresh, -1);
-  ops_.normalize_ms(W_.data(), rows, N_, R_, G_, ms_scales_, masks, active, fresh,
-                    pp_norms_live_ ? pp_norms_ + 1 : nullptr);
+  ops_.normalize_ms(W_.data(), rows, N_, R_, G_.as<double>(), ms_scales_.as<double>(), masks, active, fresh,
+                    pp_norms_live_ ? pp_norms_.as<double>() + 1 : nullptr);
 }
 
 // ---------------------------------------------------------------------------- multi-sweep tree
@@ -1771,7 +1699,7 @@ void CpEngine::ms_build_tree(int lo, int hi, int parent) {
     n.parent = -1;
     n.slo = 1;
     n.shi = 0;
-    ms_nodes_.push_back(n);
+    ms_nodes_.push_back(std::move(n));
     return;
   }
   if (hi <= lo) return;
@@ -1785,19 +1713,11 @@ void CpEngine::ms_build_tree(int lo, int hi, int parent) {
     n.parent = parent;
     n.slo = ranges[1 - c][0];
     n.shi = ranges[1 - c][1];
-    ms_nodes_.push_back(n);
+    ms_nodes_.push_back(std::move(n));
     idx[c] = (int)ms_nodes_.size() - 1;
   }
   ms_build_tree(lo, mid, idx[0]);
   ms_build_tree(mid + 1, hi, idx[1]);
-}
-
-void CpEngine::ms_reserve(RTensor &t, size_t bytes) {
-  if (t.cap < bytes) {
-    ops_.free(t.buf);
-    t.buf = ops_.alloc(bytes);
-    t.cap = bytes;
-  }
 }
 
 // ---- which root sets the multi-sweep schedule uses ----
@@ -1892,10 +1812,6 @@ int CpEngine::ms_choose_roots() {
 // (re)build the step tree for k root modes: binary tree over the N - k positions of the step's
 // mode list. Cached tensors of the old tree are released.
 void CpEngine::ms_set_roots(int k) {
-  for (auto &n : ms_nodes_) {
-    ops_.free(n.t.buf);
-    for (auto &t : n.tmp) ops_.free(t.buf);
-  }
   ms_nodes_.clear();
   ms_k_ = k;
   ms_build_tree(0, N_ - k - 1, -1);
@@ -2004,14 +1920,12 @@ void CpEngine::ms_place_release_unchosen() {
   if (use[0] && use[1]) return;
   ops_.sync();
   if (!use[1]) {
-    ops_.free(ms_X_alt_);
+    ms_X_alt_.reset();
   } else {  // every root prefers the block in front of the layout: it becomes the only one
-    ops_.free(ms_X_base_);
-    ms_X_base_ = ms_X_alt_;
+    ms_X_base_ = std::move(ms_X_alt_);
     for (auto &ex : ms_place_)
       for (auto &c : ex.cands) c.blk = 0;
   }
-  ms_X_alt_ = nullptr;
   // (called at the head of a step, before its scan: no first-level intermediate is alive)
 }
 
@@ -2027,15 +1941,15 @@ size_t CpEngine::ms_X_bytes(int first, int k) const {
 // buffer does not fit any more they are given back, one at a time, and the allocation is retried —
 // the scans then read the layouts that are left (plan_scan), slower but correct. Callers must not
 // hold a ScanPlan across this call.
-void *CpEngine::big_alloc(size_t bytes) {
+DeviceBuffer CpEngine::big_alloc(size_t bytes) {
   for (;;) {
-    void *p = ops_.try_alloc(bytes);
-    if (p) return p;
+    DeviceBuffer b = DeviceBuffer::try_alloc(ops_, bytes);
+    if (b) return b;
     // first what is merely optional for SPEED OF CHOICE: the second candidate block of the placement
     // exploration (unless the intermediate alive right now lies in it) — a resident layout is worth
     // more to every later sweep than a few more candidates to ~24 visits
-    if (ms_X_alt_ && !(ms_X_.valid && (char *)ms_X_.buf >= (char *)ms_X_alt_ &&
-                       (char *)ms_X_.buf < (char *)ms_X_alt_ + ms_X_cap_)) {
+    if (ms_X_alt_ && !(ms_X_.valid && (char *)ms_X_.buf >= ms_X_alt_.as<char>() &&
+                       (char *)ms_X_.buf < ms_X_alt_.as<char>() + ms_X_alt_.size())) {
       ops_.sync();
       for (auto &ex : ms_place_) {
         if (ex.timer >= 0) {  // a sample of a candidate in the block that goes away is dropped
@@ -2044,8 +1958,7 @@ void *CpEngine::big_alloc(size_t bytes) {
         }
         for (auto &c : ex.cands) c.blk = 0;  // (its candidates now alias offsets of the first block)
       }
-      ops_.free(ms_X_alt_);
-      ms_X_alt_ = nullptr;
+      ms_X_alt_.reset();
       continue;
     }
     bool had_packs = false;
@@ -2056,15 +1969,14 @@ void *CpEngine::big_alloc(size_t bytes) {
       pack_off_reason_ = "given back for a mandatory buffer";
       continue;
     }
-    if (lay_.size() > 1 && lay_.back().owned) {
+    if (lay_.size() > 1 && lay_.back().own) {
       ops_.sync();
-      ops_.free(lay_.back().ptr);
       lay_.pop_back();
       if (lay_.size() == 1) vt_state_ = -1;
       for (auto &n : nodes_) n.valid = false;
       continue;
     }
-    return ops_.alloc(bytes);  // throws with the back end's message
+    return DeviceBuffer(ops_, bytes);  // throws with the back end's message
   }
 }
 
@@ -2082,18 +1994,15 @@ void CpEngine::ms_start_step(int first) {
   const size_t xbytes = ms_X_bytes(first, k);
   const size_t slack = ms_tune_enabled_ ? ms_X_slack() : 0;
   // (an override — the LR optimizers' per-root caches — receives the scan's result itself: no block)
-  if (!ms_X_override_ && ms_X_cap_ < xbytes + slack) {
+  if (!ms_X_override_ && ms_X_base_.size() < xbytes + slack) {
     // (the block moves: what the roots measured so far is void, they start over)
     for (auto &ex : ms_place_) {
       if (ex.timer >= 0) ops_.timer_read(ex.timer);
       ex = PlaceExplore();
     }
-    ops_.free(ms_X_base_);
-    ops_.free(ms_X_alt_);
-    ms_X_base_ = ms_X_alt_ = nullptr;
-    ms_X_cap_ = 0;
+    ms_X_base_.reset();
+    ms_X_alt_.reset();
     ms_X_base_ = big_alloc(xbytes + slack);
-    ms_X_cap_ = xbytes + slack;
   }
   ScanPlan pl;
   if (!plan_scan(first, k, false, pl)) {
@@ -2125,7 +2034,7 @@ void CpEngine::ms_start_step(int first) {
   const PackedSrc *pk = pl.Lc > 1 ? packed_for(pl, pk_store) : nullptr;
   auto launch_scan = [&](int blk, int64_t off, int nt) {
     ms_X_.buf = ms_X_override_ ? (char *)ms_X_override_
-                               : (char *)(blk == 1 && ms_X_alt_ ? ms_X_alt_ : ms_X_base_) + off;
+                               : (blk == 1 && ms_X_alt_ ? ms_X_alt_ : ms_X_base_).as<char>() + off;
     ops_.scan_store_mode(nt);
     PackedScope scope(ops_, pk);
     ops_.scan_contract(src, V_.dtype, pl.L, J, T, f.data(), (int)f.size(), R_, ms_X_.buf, ms_X_.dt,
@@ -2212,7 +2121,7 @@ void CpEngine::ms_mode_update(int i, double lambda, bool last_of_sweep) {
   // (S and S^-1 of this update depend on the other modes' Grams only: the contraction launched
   // next may prepare them on the side)
   const bool free_i = kind_[i] == kModeFree;  // the solve: the only update that takes an armed S / Normalize
-  if (!multi_ && free_i) ops_.arm_gram_system(G_, N_, i, R_, lambda, S_, Sinv_);
+  if (!multi_ && free_i) ops_.arm_gram_system(G_.as<double>(), N_, i, R_, lambda, S_.as<double>(), Sinv_.as<double>());
   ms_compute(leaf);
   ms_norm_fused_ = false;
   // the sweep's Normalize at the tail of its last update launch, with the pending scales of the cached
@@ -2222,10 +2131,11 @@ void CpEngine::ms_mode_update(int i, double lambda, bool last_of_sweep) {
     int64_t rows[MAX_ORDER];
     for (int q = 0; q < N_; q++) rows[q] = V_.glens[q];
     // (asked first with no cached tensors — a back end that cannot fold it must not see them marked)
-    if (ops_.arm_normalize(W_.data(), rows, N_, R_, G_, i, nullptr)) {
+    if (ops_.arm_normalize(W_.data(), rows, N_, R_, G_.as<double>(), i, nullptr)) {
       unsigned masks[32] = {0}, fresh = 0;
       const unsigned active = ms_collect_scales(masks, &fresh, leaf);
-      ms_norm_fused_ = ops_.arm_normalize(W_.data(), rows, N_, R_, G_, i, nullptr, ms_scales_, masks, active, fresh);
+      ms_norm_fused_ = ops_.arm_normalize(W_.data(), rows, N_, R_, G_.as<double>(), i, nullptr,
+                                          ms_scales_.as<double>(), masks, active, fresh);
     }
   }
   mode_update(i, (const double *)ms_nodes_[leaf].t.buf, ext(i), lambda, false, 1.0);
@@ -2242,7 +2152,7 @@ void CpEngine::ms_mode_update(int i, double lambda, bool last_of_sweep) {
 
 // dst = src contracted with `mode` (rank index shared), fp64 result; in_scale = pending factor of
 // src folded into dst, so dst starts with a clean scale of its own
-void CpEngine::ms_contract(const RTensor &src, int mode, RTensor &dst, const double *in_scale) {
+void CpEngine::ms_contract(const RTensor &src, int mode, RTensor &dst, DeviceBuffer &own, const double *in_scale) {
   int64_t L = 1, T = 1;
   bool before = true;
   dst.modes.clear();
@@ -2256,7 +2166,8 @@ void CpEngine::ms_contract(const RTensor &src, int mode, RTensor &dst, const dou
   }
   dst.dt = F64;
   dst.contracted = src.contracted | (1u << mode);
-  ms_reserve(dst, sizeof(double) * (size_t)L * T * R_);
+  own.reserve(ops_, sizeof(double) * (size_t)L * T * R_);
+  dst.buf = own.get();
   FactorRef f = fref(mode, W_.data());
   ops_.mttv(src.buf, src.dt, L, ext(mode), T, &f, 1, R_, (double *)dst.buf, L * T, 0, in_scale);
 }
@@ -2280,11 +2191,15 @@ void CpEngine::ms_compute(int idx) {
     return -1;
   };
   std::sort(sib.begin(), sib.end(), [&](int a, int b) { return storage_pos(a) > storage_pos(b); });
-  if (n.tmp.size() + 1 < sib.size()) n.tmp.resize(sib.size() - 1);
+  if (n.tmp.size() + 1 < sib.size()) {
+    n.tmp.resize(sib.size() - 1);
+    n.tmp_own.resize(sib.size() - 1);
+  }
   const RTensor *cur = src;
   for (size_t k = 0; k < sib.size(); k++) {
-    RTensor &dst = (k + 1 == sib.size()) ? n.t : n.tmp[k];
-    ms_contract(*cur, sib[k], dst, k == 0 ? ms_scale_of(*src) : nullptr);
+    const bool last = k + 1 == sib.size();
+    RTensor &dst = last ? n.t : n.tmp[k];
+    ms_contract(*cur, sib[k], dst, last ? n.own : n.tmp_own[k], k == 0 ? ms_scale_of(*src) : nullptr);
     cur = &dst;
   }
   if (sib.empty()) throw std::runtime_error("ppals: empty sibling set in the multi-sweep tree");
@@ -2314,9 +2229,9 @@ void CpEngine::sweep_dt(double lambda) {
     if (i == N_ - 1 && !dist_ && kind_[i] == kModeFree && !skips_normalize()) {
       int64_t rows[MAX_ORDER];
       for (int q = 0; q < N_; q++) rows[q] = V_.glens[q];
-      norm_fused = ops_.arm_normalize(W_.data(), rows, N_, R_, G_, i, nullptr);
+      norm_fused = ops_.arm_normalize(W_.data(), rows, N_, R_, G_.as<double>(), i, nullptr);
     }
-    mode_update(i, lf.buf, ext(i), lambda, false, 1.0);
+    mode_update(i, lf.buf.as<double>(), ext(i), lambda, false, 1.0);
     // every cached node that does NOT contain mode i stays valid; nodes containing mode i were
     // built from W_j, j != i only, so they stay valid too until the cache is cleared.
   }
@@ -2337,7 +2252,7 @@ void CpEngine::update_modes(int first, int count, double lambda) {
         for (auto &n : nodes_) n.valid = false;
       if (kind_[i] == kModeFixed) continue;
       compute_node(leaf_[i]);
-      mode_update(i, nodes_[leaf_[i]].buf, ext(i), lambda, false, 1.0);
+      mode_update(i, nodes_[leaf_[i]].buf.as<double>(), ext(i), lambda, false, 1.0);
     }
   }
   grad_from_sweep_ = true;
@@ -2350,23 +2265,20 @@ void CpEngine::update_modes(int first, int count, double lambda) {
 // ---------------------------------------------------------------------------- low-rank updates
 void CpEngine::lr_release() {
   for (int m = 0; m < MAX_ORDER; m++) {
-    ops_.free(lr_cache_[m]);
-    lr_cache_[m] = nullptr;
+    lr_cache_[m].reset();
     lr_have_[m] = false;
   }
-  ops_.free(lr_X_);
-  ops_.free(lr_Us_);
-  ops_.free(lr_G2_);
-  ops_.free(lr_small_);
-  ops_.free(lr_T_);
-  lr_X_ = lr_Us_ = lr_G2_ = lr_small_ = lr_T_ = nullptr;
-  lr_T_cap_ = 0;
+  lr_X_.reset();
+  lr_Us_.reset();
+  lr_G2_.reset();
+  lr_small_.reset();
+  lr_T_.reset();
 }
 
 // mttkrp_map_init of the LR optimizers (cp_dt_lr_optimizer.cxx:36-94, cp_msdt_lr_optimizer.cxx:
 // 31-75): the step's first contraction X = V x_left W_left in the root's own buffer — computed by
 // one tensor scan, or (reuse) the kept one brought up to date with the rank-r change of W_left
-// that lr_mode_update left in lr_Us_ (rows x r) and lr_small_ (VT, r x R).
+// that lr_mode_update left in lr_Us_.as<double>() (rows x r) and lr_small_.as<double>() (VT, r x R).
 void CpEngine::lr_step_begin(int left, bool reuse, int r) {
   check_tensor_generation();
   if (ms_k_ != 1) ms_set_roots(1);
@@ -2375,20 +2287,17 @@ void CpEngine::lr_step_begin(int left, bool reuse, int r) {
     ScanPlan pl;
     if (!plan_scan(left, 1, false, pl)) throw std::runtime_error("ppals: internal error (LR scan plan)");
     const int64_t n = pl.Lc * pl.T;
-    if (lr_T_cap_ < sizeof(double) * (size_t)n * r) {
-      ops_.free(lr_T_);
-      lr_T_ = (double *)ops_.alloc(sizeof(double) * (size_t)n * r);
-      lr_T_cap_ = sizeof(double) * (size_t)n * r;
-    }
+    lr_T_.reserve(ops_, sizeof(double) * (size_t)n * r);
     FactorRef f;
-    f.ptr = lr_Us_ + (left == 0 ? V_.row0 : 0);
+    f.ptr = lr_Us_.as<double>() + (left == 0 ? V_.row0 : 0);
     f.rows = ext(left);
     f.ld = V_.glens[left];
-    ops_.scan_contract(pl.lay->ptr, V_.dtype, pl.L, ext(left), pl.T, &f, 1, r, lr_T_, F64, pl.Lc, n,
+    ops_.scan_contract(pl.lay->ptr, V_.dtype, pl.L, ext(left), pl.T, &f, 1, r, lr_T_.as<double>(), F64, pl.Lc, n,
                        pl.pad);
-    ops_.lowrank_accumulate(lr_cache_[left], work_dt(V_.dtype), n, R_, lr_T_, r, lr_small_);
+    ops_.lowrank_accumulate(lr_cache_[left].get(), work_dt(V_.dtype), n, R_, lr_T_.as<double>(), r,
+                            lr_small_.as<double>());
     ms_X_ = lr_desc_[left];
-    ms_X_.buf = lr_cache_[left];
+    ms_X_.buf = lr_cache_[left].get();
     ms_X_.valid = true;
     ms_X_.pending = false;
     ms_root_ = left;
@@ -2396,7 +2305,7 @@ void CpEngine::lr_step_begin(int left, bool reuse, int r) {
     for (int q = 1; q < N_; q++) ms_order_.push_back((left + q) % N_);
     for (auto &nd : ms_nodes_) nd.t.valid = false;
   } else {
-    ms_X_override_ = lr_cache_[left];
+    ms_X_override_ = lr_cache_[left].get();
     ms_start_step(left);
     ms_X_override_ = nullptr;
     lr_desc_[left] = ms_X_;
@@ -2473,8 +2382,8 @@ static const uint64_t LR_RANDOM_SEED = 0x52414e44535644ull;  // "RANDSVD"
 
 // r > 0: get_rankR_update_cholesky (common.cxx:768-786; random == true: lr_random_) relative to `base`
 // (device, s x R; null: the current W_i): gamma = L L^T, X = (M - base gamma) L^-T, its leading r
-// singular triplets, W_i = base + (U_r s_r)(VT_r L^-1). Leaves Us = U_r s_r in lr_Us_ (s x r) and
-// VT in lr_small_ (r x R) for the next lr_step_begin. The R x R algebra runs on the host.
+// singular triplets, W_i = base + (U_r s_r)(VT_r L^-1). Leaves Us = U_r s_r in lr_Us_.as<double>() (s x r) and
+// VT in lr_small_.as<double>() (r x R) for the next lr_step_begin. The R x R algebra runs on the host.
 void CpEngine::lr_mode_update(int i, double lambda, int r, const double *base) {
   int pos = -1;
   for (size_t q = 0; q < ms_order_.size(); q++)
@@ -2491,28 +2400,30 @@ void CpEngine::lr_mode_update(int i, double lambda, int r, const double *base) {
   }
   const size_t nsr = (size_t)s * R_;
   if (!lr_X_) {
-    lr_X_ = (double *)ops_.alloc(sizeof(double) * (size_t)maxs_ * R_);
-    lr_Us_ = (double *)ops_.alloc(sizeof(double) * (size_t)maxs_ * R_);
-    lr_G2_ = (double *)ops_.alloc(sizeof(double) * (size_t)maxs_ * R_);
-    lr_small_ = (double *)ops_.alloc(sizeof(double) * 4 * (size_t)R_ * R_);
+    lr_X_ = DeviceBuffer(ops_, sizeof(double) * (size_t)maxs_ * R_);
+    lr_Us_ = DeviceBuffer(ops_, sizeof(double) * (size_t)maxs_ * R_);
+    lr_G2_ = DeviceBuffer(ops_, sizeof(double) * (size_t)maxs_ * R_);
+    lr_small_ = DeviceBuffer(ops_, sizeof(double) * 4 * (size_t)R_ * R_);
   }
-  ops_.gram_system(G_, N_, i, R_, lambda, S_, Sinv_);
+  ops_.gram_system(G_.as<double>(), N_, i, R_, lambda, S_.as<double>(), Sinv_.as<double>());
   // the gradient with the CURRENT factor (what [gradnorm] reports), W_new of the exact solve unused
-  ops_.cp_update(M, s, W_[i], s, lr_X_, s, gradW_[i], s, s, R_, S_, Sinv_, gradsq_ + i, nullptr, 0,
+  ops_.cp_update(M, s, W_[i], s, lr_X_.as<double>(), s, gradW_[i], s, s, R_, S_.as<double>(), Sinv_.as<double>(),
+                 gradsq_.as<double>() + i, nullptr, 0,
                  nullptr, 0, 1.0);
   grad_replicated_[i] = true;
   const double *negrhs = gradW_[i];  // -(M - base gamma)
   if (base && base != W_[i]) {
-    ops_.cp_update(M, s, base, s, lr_X_, s, lr_G2_, s, s, R_, S_, Sinv_, scal_ + 3 * MAX_ORDER,
+    ops_.cp_update(M, s, base, s, lr_X_.as<double>(), s, lr_G2_.as<double>(), s, s, R_, S_.as<double>(),
+                   Sinv_.as<double>(), scal_.as<double>() + 3 * MAX_ORDER,
                    nullptr, 0, nullptr, 0, 1.0);
-    negrhs = lr_G2_;
+    negrhs = lr_G2_.as<double>();
   } else {
     base = W_[i];
   }
   // host: L = chol(gamma), T1 = -L^-T  (X = negrhs * T1)
   std::vector<double> Sg((size_t)R_ * R_), L((size_t)R_ * R_, 0.0), Li((size_t)R_ * R_, 0.0),
       T1((size_t)R_ * R_, 0.0);
-  ops_.d2h(Sg.data(), S_, sizeof(double) * R_ * R_);
+  ops_.d2h(Sg.data(), S_.as<double>(), sizeof(double) * R_ * R_);
   for (int j = 0; j < R_; j++) {
     double d = Sg[j + (size_t)R_ * j];
     for (int k = 0; k < j; k++) d -= L[j + (size_t)R_ * k] * L[j + (size_t)R_ * k];
@@ -2533,10 +2444,10 @@ void CpEngine::lr_mode_update(int i, double lambda, int r, const double *base) {
     }
   for (int a = 0; a < R_; a++)
     for (int b = 0; b < R_; b++) T1[a + (size_t)R_ * b] = -Li[b + (size_t)R_ * a];  // -(L^-1)^T
-  double *dT1 = lr_small_ + (size_t)R_ * R_, *dGX = dT1 + (size_t)R_ * R_, *dV = dGX + (size_t)R_ * R_;
+  double *dT1 = lr_small_.as<double>() + (size_t)R_ * R_, *dGX = dT1 + (size_t)R_ * R_, *dV = dGX + (size_t)R_ * R_;
   ops_.h2d(dT1, T1.data(), sizeof(double) * R_ * R_);
-  ops_.rows_times_small(negrhs, s, R_, dT1, R_, nullptr, lr_X_);    // X = rhs L^-T
-  ops_.gram(lr_X_, s, s, R_, dGX);                                   // X^T X
+  ops_.rows_times_small(negrhs, s, R_, dT1, R_, nullptr, lr_X_.as<double>());    // X = rhs L^-T
+  ops_.gram(lr_X_.as<double>(), s, s, R_, dGX);                                   // X^T X
   std::vector<double> Vr((size_t)R_ * r), VT((size_t)r * R_, 0.0);
   if (!lr_random_) {
     ops_.top_eigvecs(dGX, R_, r, dV);                                // leading right singular vectors
@@ -2589,10 +2500,10 @@ void CpEngine::lr_mode_update(int i, double lambda, int r, const double *base) {
       for (int q = c; q < R_; q++) v += Vr[q + (size_t)R_ * k] * Li[q + (size_t)R_ * c];
       VT[k + (size_t)r * c] = v;
     }
-  ops_.h2d(lr_small_, VT.data(), sizeof(double) * r * R_);
-  ops_.rows_times_small(lr_X_, s, R_, dV, r, nullptr, lr_Us_);       // Us = X V_r = U_r s_r
-  ops_.rows_times_small(lr_Us_, s, r, lr_small_, R_, base, W_[i]);   // W = base + Us VT
-  ops_.gram(W_[i], s, s, R_, G_ + (size_t)i * R_ * R_);
+  ops_.h2d(lr_small_.as<double>(), VT.data(), sizeof(double) * r * R_);
+  ops_.rows_times_small(lr_X_.as<double>(), s, R_, dV, r, nullptr, lr_Us_.as<double>());       // Us = X V_r = U_r s_r
+  ops_.rows_times_small(lr_Us_.as<double>(), s, r, lr_small_.as<double>(), R_, base, W_[i]);   // W = base + Us VT
+  ops_.gram(W_[i], s, s, R_, G_.as<double>() + (size_t)i * R_ * R_);
   (void)nsr;
   ms_nodes_[leaf].t.valid = false;
 }
@@ -2619,7 +2530,8 @@ int CpEngine::run_class(int kind, const CpOpts &o, double *sweeps_out, int *iter
   // CPMSDTLROptimizer state (cp_msdt_optimizer.cxx:28, cp_msdt_lr_optimizer.cxx:9-27)
   int lr_msleft = N_;
   bool lr_cached[MAX_ORDER] = {false};
-  std::vector<double *> lr_oldW(N_, nullptr);
+  DeviceBufferTable lr_oldW;
+  lr_oldW.resize(N_);
   const int ur = o.update_rank;
   auto lr_step = [&]() -> double {
     if (kind == 3) {
@@ -2654,8 +2566,7 @@ int CpEngine::run_class(int kind, const CpOpts &o, double *sweeps_out, int *iter
         for (int m = 0; m < N_; m++)
           if (m != lr_left1 && m != lr_left2 && lr_cache_[m]) {
             ops_.sync();
-            ops_.free(lr_cache_[m]);
-            lr_cache_[m] = nullptr;
+            lr_cache_[m].reset();
             lr_have_[m] = false;
           }
       }
@@ -2666,7 +2577,7 @@ int CpEngine::run_class(int kind, const CpOpts &o, double *sweeps_out, int *iter
     const int left = lr_msleft;
     const bool reuse = lr_low && lr_cached[left];
     lr_step_begin(left, reuse, ur);
-    if (!lr_oldW[left]) lr_oldW[left] = (double *)ops_.alloc(sizeof(double) * V_.glens[left] * R_);
+    if (!lr_oldW[left]) lr_oldW.alloc(ops_, left, sizeof(double) * V_.glens[left] * R_);
     ops_.d2d(lr_oldW[left], W_[left], sizeof(double) * V_.glens[left] * R_);
     lr_cached[left] = true;
     for (int p = 0; p < N_ - 1; p++) {
@@ -2680,13 +2591,6 @@ int CpEngine::run_class(int kind, const CpOpts &o, double *sweeps_out, int *iter
     }
     return 1.0 * (N_ - 1) / N_;
   };
-  struct FreeOld {
-    Ops &ops;
-    std::vector<double *> &v;
-    ~FreeOld() {
-      for (auto p : v) ops.free(p);
-    }
-  } free_old{ops_, lr_oldW};
   std::ofstream csv;
   std::ofstream *pcsv = nullptr;
   if (rank_ == 0 && !o.csv_path.empty()) {
@@ -2767,10 +2671,10 @@ int CpEngine::run_class(int kind, const CpOpts &o, double *sweeps_out, int *iter
 
 double CpEngine::allreduce_scalar(double x) {
   if (!dist_) return x;
-  ops_.h2d(scal_, &x, sizeof(double));
-  comm_.allreduce_sum(scal_, 1);
+  ops_.h2d(scal_.as<double>(), &x, sizeof(double));
+  comm_.allreduce_sum(scal_.as<double>(), 1);
   double y = 0;
-  ops_.d2h(&y, scal_, sizeof(double));
+  ops_.d2h(&y, scal_.as<double>(), sizeof(double));
   return y;
 }
 
@@ -2785,7 +2689,7 @@ bool CpEngine::agree(bool local) {
 double CpEngine::gradnorm() {
   if (!grad_from_sweep_) return init_gradnorm_;
   double h[MAX_ORDER];
-  ops_.d2h(h, gradsq_, sizeof(double) * N_);
+  ops_.d2h(h, gradsq_.as<double>(), sizeof(double) * N_);
   double part = 0, repl = 0;  // row-block partial sums vs. sums every rank already holds in full
   for (int i = 0; i < N_; i++) (grad_replicated_[i] ? repl : part) += h[i];
   return std::sqrt(allreduce_scalar(part) + repl);
@@ -2794,13 +2698,13 @@ double CpEngine::gradnorm() {
 double CpEngine::residual() {
   int64_t M, K;
   split_sizes(V_, &M, &K);
-  if (!Qbuf_) Qbuf_ = (double *)ops_.alloc(sizeof(double) * M * R_);
-  if (!Pbuf_) Pbuf_ = (double *)ops_.alloc(sizeof(double) * K * R_);
-  split_krp(ops_, V_, R_, W_.data(), Qbuf_, Pbuf_, &M, &K);
-  ops_.residual_sq(V_.data, V_.dtype, M, K, Qbuf_, Pbuf_, R_, scal_);
-  if (dist_) comm_.allreduce_sum(scal_, 1);
+  if (!Qbuf_) Qbuf_ = DeviceBuffer(ops_, sizeof(double) * M * R_);
+  if (!Pbuf_) Pbuf_ = DeviceBuffer(ops_, sizeof(double) * K * R_);
+  split_krp(ops_, V_, R_, W_.data(), Qbuf_.as<double>(), Pbuf_.as<double>(), &M, &K);
+  ops_.residual_sq(V_.data, V_.dtype, M, K, Qbuf_.as<double>(), Pbuf_.as<double>(), R_, scal_.as<double>());
+  if (dist_) comm_.allreduce_sum(scal_.as<double>(), 1);
   double h = 0;
-  ops_.d2h(&h, scal_, sizeof(double));
+  ops_.d2h(&h, scal_.as<double>(), sizeof(double));
   return std::sqrt(h);
 }
 
@@ -2844,21 +2748,13 @@ void CpEngine::model_operands(const ModelBox &bx, ModelPlan &mp) {
     }
   };
   const int64_t A = mp.ga.count, B = mp.gb.count;
-  if (A * R_ > xq_cap_) {
-    ops_.free(xq_);
-    xq_ = (double *)ops_.alloc(sizeof(double) * A * R_);
-    xq_cap_ = A * R_;
-  }
-  if (B * R_ > xp_cap_) {
-    ops_.free(xp_);
-    xp_ = (double *)ops_.alloc(sizeof(double) * B * R_);
-    xp_cap_ = B * R_;
-  }
+  xq_.reserve(ops_, sizeof(double) * A * R_);
+  xp_.reserve(ops_, sizeof(double) * B * R_);
   FactorRef fa[MAX_ORDER], fb[MAX_ORDER];
   refs(mp.ga, fa);
   refs(mp.gb, fb);
-  ops_.krp(xq_, fa, mp.ga.n, 0, R_);
-  ops_.krp(xp_, fb, mp.gb.n, 0, R_);
+  ops_.krp(xq_.as<double>(), fa, mp.ga.n, 0, R_);
+  ops_.krp(xp_.as<double>(), fb, mp.gb.n, 0, R_);
   mp.voff = bx.voff;
   mp.roff = bx.roff;
   mp.ldq = A;
@@ -2891,7 +2787,7 @@ void CpEngine::export_model(const ViewArgs &a, void *dst, bool residual, void *s
     if (!inA[m]) mp.gb.add(bx, m);
   model_operands(bx, mp);
   ModelExportCall c{&a, &V_, dst, residual, residual_form_, false, stream};
-  model_export_run(ops_, c, mp, xq_, xp_, R_);
+  model_export_run(ops_, c, mp, xq_.as<double>(), xp_.as<double>(), R_);
 }
 
 // The imputation: the stores go to the shard, so here the grouping follows the SHARD.
@@ -2927,16 +2823,17 @@ void CpEngine::impute(const ViewArgs &a, const void *mask, void *stream, double 
     ModelPlan mp;
     shard_groups(bx, nullptr, mp);
     model_operands(bx, mp);
-    ops_.model_impute(mp, xq_, xp_, R_, false, mask, V_.data, V_.dtype, observed_sq ? scal_ : nullptr, stream);
+    ops_.model_impute(mp, xq_.as<double>(), xp_.as<double>(), R_, false, mask, V_.data, V_.dtype,
+                      observed_sq ? scal_.as<double>() : nullptr, stream);
     // the contents changed with that launch: every session on the tensor, this one too, rebuilds what
     // it derived at its next read (a rank none of whose rows lie in the box has changed nothing)
     if (V_.generation) ++*V_.generation;
   } else if (observed_sq) {
-    ops_.zero(scal_, sizeof(double));  // none of the box in this rank's rows
+    ops_.zero(scal_.as<double>(), sizeof(double));  // none of the box in this rank's rows
   }
   if (!observed_sq) return;
-  if (dist_) comm_.allreduce_sum(scal_, 1);
-  ops_.d2h(observed_sq, scal_, sizeof(double));
+  if (dist_) comm_.allreduce_sum(scal_.as<double>(), 1);
+  ops_.d2h(observed_sq, scal_.as<double>(), sizeof(double));
 }
 
 // The loop of ppals_cp_em and ppals_cp_wls: iteration k is step(&sq or nullptr) followed by inner_sweeps
@@ -3006,17 +2903,19 @@ void CpEngine::side_step(const char *what, const ViewArgs &a, const void *data, 
     ModelSide ws;
     if (w) ws = dv_model_side(*w, bx, mp);
     if (huber)
-      ops_.model_huber(mp, w ? &ws : nullptr, xq_, xp_, R_, data, weights, a.dtype, V_.data, V_.dtype, c,
-                       out ? scal_ : nullptr, stream);
+      ops_.model_huber(mp, w ? &ws : nullptr, xq_.as<double>(), xp_.as<double>(), R_, data, weights, a.dtype, V_.data,
+                       V_.dtype, c,
+                       out ? scal_.as<double>() : nullptr, stream);
     else
-      ops_.model_wls(mp, ws, xq_, xp_, R_, data, weights, a.dtype, V_.data, V_.dtype, out ? scal_ : nullptr, stream);
+      ops_.model_wls(mp, ws, xq_.as<double>(), xp_.as<double>(), R_, data, weights, a.dtype, V_.data, V_.dtype,
+                     out ? scal_.as<double>() : nullptr, stream);
     if (V_.generation) ++*V_.generation;  // (as after an imputation)
   } else if (out) {
-    ops_.zero(scal_, sizeof(double) * nout);  // none of the box in this rank's rows
+    ops_.zero(scal_.as<double>(), sizeof(double) * nout);  // none of the box in this rank's rows
   }
   if (!out) return;
-  if (dist_) comm_.allreduce_sum(scal_, nout);
-  ops_.d2h(out, scal_, sizeof(double) * nout);
+  if (dist_) comm_.allreduce_sum(scal_.as<double>(), nout);
+  ops_.d2h(out, scal_.as<double>(), sizeof(double) * nout);
 }
 
 void CpEngine::wls_step(const ViewArgs &a, const void *data, const ViewArgs &w, const void *weights, void *stream,
@@ -3079,7 +2978,8 @@ void CpEngine::abs_residual_quantile(const ViewArgs &a, const void *data, const 
     const int shifts[3] = {20, 10, 0}, bits[3] = {11, 10, 10};
     for (int pass = 0; pass < 3; pass++) {
       const int pshift = pass == 0 ? 31 : shifts[pass - 1];
-      ops_.model_absres_hist(mp, w ? &ws : nullptr, xq_, xp_, R_, data, weights, a.dtype, pshift, key >> pshift,
+      ops_.model_absres_hist(mp, w ? &ws : nullptr, xq_.as<double>(), xp_.as<double>(), R_, data, weights, a.dtype,
+                             pshift, key >> pshift,
                              shifts[pass], (1u << bits[pass]) - 1, hist.data(), stream);
       if (pass == 0) {
         for (uint64_t h : hist) n += h;
@@ -3104,17 +3004,6 @@ int64_t CpEngine::core_entries(int start) const {
   int64_t n = 1;
   for (int i = 0; i < N_ && n <= kCoreMaxEntries; i++) n *= R;
   return n;
-}
-
-void *CpEngine::cc_reserve(GrowBuf &b, size_t bytes) {
-  if (b.cap < bytes) {
-    ops_.free(b.ptr);  // (waits for what still reads it)
-    b.ptr = nullptr;
-    b.cap = 0;
-    b.ptr = ops_.alloc(bytes);
-    b.cap = bytes;
-  }
-  return b.ptr;
 }
 
 // The diagnostic of engine.h. Launches: one for the pseudo-inverse factors of all modes and starts, ONE tensor
@@ -3144,10 +3033,10 @@ void CpEngine::core_consistency(int only, double *cc_host, double *core_host) {
   int64_t rows[MAX_ORDER];
   for (int i = 0; i < N_; i++) rows[i] = V_.glens[i];
   if (cc_P_.empty()) {
-    cc_P_.assign(N_, nullptr);
-    for (int i = 0; i < N_; i++) cc_P_[i] = (double *)ops_.alloc(sizeof(double) * (size_t)rows[i] * R_);
-    cc_flag_ = (int *)ops_.alloc(sizeof(int) * K);
-    cc_out_ = (double *)ops_.alloc(sizeof(double) * K);
+    cc_P_.resize(N_);
+    for (int i = 0; i < N_; i++) cc_P_.alloc(ops_, i, sizeof(double) * (size_t)rows[i] * R_);
+    cc_flag_ = DeviceBuffer(ops_, sizeof(int) * K);
+    cc_out_ = DeviceBuffer(ops_, sizeof(double) * K);
   }
   // the contracted mode, before anything is sized (LT = the kept modes' extents)
   int m = -1;
@@ -3178,17 +3067,17 @@ void CpEngine::core_consistency(int only, double *cc_host, double *core_host) {
     }
     core_total += (size_t)core_entries(b);
   }
-  cc_reserve(cc_Y_, (size_t)LT * ncols * dtype_size(wdt));
-  if (chain_max) cc_reserve(cc_chain_[0], sizeof(double) * chain_max);
-  if (chain_max && nk > 2) cc_reserve(cc_chain_[1], sizeof(double) * chain_max);
-  cc_reserve(cc_core_, sizeof(double) * core_total);
+  cc_Y_.reserve(ops_, (size_t)LT * ncols * dtype_size(wdt));
+  if (chain_max) cc_chain_[0].reserve(ops_, sizeof(double) * chain_max);
+  if (chain_max && nk > 2) cc_chain_[1].reserve(ops_, sizeof(double) * chain_max);
+  cc_core_.reserve(ops_, sizeof(double) * core_total);
 
-  ops_.zero(cc_flag_, sizeof(int) * K);
-  ops_.cp_pinv_ragged(G_, N_, tab, W_.data(), rows, cc_P_.data(), cc_flag_);
+  ops_.zero(cc_flag_.as<int>(), sizeof(int) * K);
+  ops_.cp_pinv_ragged(G_.as<double>(), N_, tab, W_.data(), rows, cc_P_.data(), cc_flag_.as<int>());
   {
     FactorRef f = fref(m, cc_P_.data());
     f.ptr += (size_t)cA * f.ld;
-    ops_.scan_contract(pl.lay->ptr, V_.dtype, pl.L, pl.J, pl.T, &f, 1, ncols, cc_Y_.ptr, wdt, pl.Lc,
+    ops_.scan_contract(pl.lay->ptr, V_.dtype, pl.L, pl.J, pl.T, &f, 1, ncols, cc_Y_.get(), wdt, pl.Lc,
                        pl.Lc * pl.T, pl.pad);
   }
   ops_.scan_profile_slot(1);
@@ -3196,8 +3085,8 @@ void CpEngine::core_consistency(int only, double *cc_host, double *core_host) {
     size_t core_off = 0;
     for (int b = b0; b < b1; b++) {
       const int Rb = tab.rank(b);
-      double *core = (double *)cc_core_.ptr + core_off;
-      const void *X = (const char *)cc_Y_.ptr + (size_t)(tab.col[b] - cA) * LT * dtype_size(wdt);
+      double *core = cc_core_.as<double>() + core_off;
+      const void *X = cc_Y_.as<char>() + (size_t)(tab.col[b] - cA) * LT * dtype_size(wdt);
       int xdt = wdt;
       int64_t tail = Rb;  // what lies behind the mode being contracted: r_m, then the modes already done
       for (int p = nk - 1; p >= 0; p--) {
@@ -3205,13 +3094,13 @@ void CpEngine::core_consistency(int only, double *cc_host, double *core_host) {
         for (int q = 0; q < p; q++) L *= ext(pl.kept[q]);
         const int km = pl.kept[p];
         FactorRef f = fref(km, cc_P_.data());
-        double *out = p == 0 ? core : (double *)cc_chain_[(nk - 1 - p) & 1].ptr;
+        double *out = p == 0 ? core : cc_chain_[(nk - 1 - p) & 1].as<double>();
         ops_.ttm_keep(X, xdt, L, ext(km), tail, f.ptr + (size_t)tab.col[b] * f.ld, f.ld, Rb, out);
         tail *= Rb;
         X = out;
         xdt = F64;
       }
-      ops_.core_score(core, Rb, N_, cc_flag_ + b, cc_out_ + b);
+      ops_.core_score(core, Rb, N_, cc_flag_.as<int>() + b, cc_out_.as<double>() + b);
       core_off += (size_t)core_entries(b);
     }
   } catch (...) {
@@ -3219,18 +3108,18 @@ void CpEngine::core_consistency(int only, double *cc_host, double *core_host) {
     throw;
   }
   ops_.scan_profile_slot(0);
-  ops_.d2h(cc_host, cc_out_ + b0, sizeof(double) * (b1 - b0));  // the flag travels as the NaN of the score
+  ops_.d2h(cc_host, cc_out_.as<double>() + b0, sizeof(double) * (b1 - b0));  // the flag travels as the NaN of the score
   if (!core_host) return;
   // the device holds the core with its indices in the order (kept modes as stored, then m)
   const int64_t n = core_entries(b0), Rb = tab.rank(b0);
   bool natural = m == N_ - 1;
   for (int q = 0; q < nk; q++) natural = natural && pl.kept[q] == q;
   if (natural) {
-    ops_.d2h(core_host, cc_core_.ptr, sizeof(double) * n);
+    ops_.d2h(core_host, cc_core_.get(), sizeof(double) * n);
     return;
   }
   std::vector<double> tmp((size_t)n);
-  ops_.d2h(tmp.data(), cc_core_.ptr, sizeof(double) * n);
+  ops_.d2h(tmp.data(), cc_core_.get(), sizeof(double) * n);
   int64_t stride[MAX_ORDER];  // of the device's q-th index in the caller's layout
   for (int q = 0; q <= nk; q++) {
     const int mode = q < nk ? pl.kept[q] : m;
@@ -3264,14 +3153,27 @@ void CpEngine::slice_residuals(double *ss_host, double *total_host) {
   int64_t M, K, nout = 0;
   split_sizes(V_, &M, &K);
   for (int i = 0; i < N_; i++) nout += V_.glens[i];
-  if (!Qbuf_) Qbuf_ = (double *)ops_.alloc(sizeof(double) * M * R_);
-  if (!Pbuf_) Pbuf_ = (double *)ops_.alloc(sizeof(double) * K * R_);
-  double *row = (double *)cc_reserve(sl_row_, sizeof(double) * M);
-  double *col = (double *)cc_reserve(sl_col_, sizeof(double) * K);
-  double *out = (double *)cc_reserve(sl_out_, sizeof(double) * (nout + 1));
-  split_krp(ops_, V_, R_, W_.data(), Qbuf_, Pbuf_, &M, &K);
-  ops_.residual_slices(V_.data, V_.dtype, M, K, Qbuf_, Pbuf_, R_, row, col, out + nout, slice_work_cap_, sl_work_.ptr,
-                       sl_work_.cap);
+  if (!Qbuf_) Qbuf_ = DeviceBuffer(ops_, sizeof(double) * M * R_);
+  if (!Pbuf_) Pbuf_ = DeviceBuffer(ops_, sizeof(double) * K * R_);
+  sl_row_.reserve(ops_, sizeof(double) * M);
+  double *row = sl_row_.as<double>();
+  sl_col_.reserve(ops_, sizeof(double) * K);
+  double *col = sl_col_.as<double>();
+  sl_out_.reserve(ops_, sizeof(double) * (nout + 1));
+  double *out = sl_out_.as<double>();
+  split_krp(ops_, V_, R_, W_.data(), Qbuf_.as<double>(), Pbuf_.as<double>(), &M, &K);
+  // the op frees its partial sums' buffer and takes a larger one as it needs (ops.h): handed over for the call,
+  // taken back on every way out
+  size_t work_bytes = sl_work_.size();
+  void *work = sl_work_.release();
+  try {
+    ops_.residual_slices(V_.data, V_.dtype, M, K, Qbuf_.as<double>(), Pbuf_.as<double>(), R_, row, col, out + nout,
+                         slice_work_cap_, work, work_bytes);
+  } catch (...) {
+    sl_work_ = DeviceBuffer(ops_, work, work_bytes);
+    throw;
+  }
+  sl_work_ = DeviceBuffer(ops_, work, work_bytes);
   const int h = N_ / 2;
   int64_t left = 0;
   for (int i = 0; i < h; i++) left += V_.glens[i];
@@ -3292,21 +3194,22 @@ void CpEngine::leverages(double *lev_host) {
   int64_t rows[MAX_ORDER], nout = 0;
   for (int i = 0; i < N_; i++) nout += (rows[i] = V_.glens[i]);
   if (cc_P_.empty()) {  // (the buffers of the core consistency: the same pseudo-inverse factors)
-    cc_P_.assign(N_, nullptr);
-    for (int i = 0; i < N_; i++) cc_P_[i] = (double *)ops_.alloc(sizeof(double) * (size_t)rows[i] * R_);
-    cc_flag_ = (int *)ops_.alloc(sizeof(int));
-    cc_out_ = (double *)ops_.alloc(sizeof(double));
+    cc_P_.resize(N_);
+    for (int i = 0; i < N_; i++) cc_P_.alloc(ops_, i, sizeof(double) * (size_t)rows[i] * R_);
+    cc_flag_ = DeviceBuffer(ops_, sizeof(int));
+    cc_out_ = DeviceBuffer(ops_, sizeof(double));
   }
-  double *out = (double *)cc_reserve(sl_out_, sizeof(double) * (nout + 1));
-  ops_.zero(cc_flag_, sizeof(int));
-  ops_.cp_pinv_ragged(G_, N_, tab, W_.data(), rows, cc_P_.data(), cc_flag_);
+  sl_out_.reserve(ops_, sizeof(double) * (nout + 1));
+  double *out = sl_out_.as<double>();
+  ops_.zero(cc_flag_.as<int>(), sizeof(int));
+  ops_.cp_pinv_ragged(G_.as<double>(), N_, tab, W_.data(), rows, cc_P_.data(), cc_flag_.as<int>());
   int64_t off = 0;
   for (int i = 0; i < N_; i++) {
     ops_.row_dots(cc_P_[i], W_[i], rows[i], R_, rows[i], out + off);
     off += rows[i];
   }
   int bad = 0;
-  ops_.d2h(&bad, cc_flag_, sizeof(int));
+  ops_.d2h(&bad, cc_flag_.as<int>(), sizeof(int));
   ops_.d2h(lev_host, out, sizeof(double) * nout);
   if (bad)  // a Gram without a positive finite pivot: no projector to speak of
     for (int64_t e = 0; e < nout; e++) lev_host[e] = std::numeric_limits<double>::quiet_NaN();
@@ -3345,9 +3248,11 @@ void CpEngine::congruence(CpEngine &b, int skip_mode, std::vector<double> &out) 
   sa.cols = R_;
   sb.cols = b.R_;
   const size_t n = (size_t)R_ * b.R_ + (size_t)R_ + (size_t)b.R_;
-  double *dev = (double *)cc_reserve(fms_out_, sizeof(double) * n);
+  fms_out_.reserve(ops_, sizeof(double) * n);
+  double *dev = fms_out_.as<double>();
   const size_t wbytes = ops_.factor_congruence_work(N_, sa, sb);
-  void *work = wbytes ? cc_reserve(fms_work_, wbytes) : nullptr;
+  if (wbytes) fms_work_.reserve(ops_, wbytes);
+  void *work = wbytes ? fms_work_.get() : nullptr;
   ops_.factor_congruence(N_, sa, sb, mask, work, dev, dev + (size_t)R_ * b.R_, dev + (size_t)R_ * b.R_ + R_);
   out.resize(n);
   ops_.d2h(out.data(), dev, sizeof(double) * n);
@@ -3389,7 +3294,7 @@ int64_t CpEngine::tree_node(const std::string &key, double *out_host) {
   for (auto &n : nodes_) n.valid = false;
   compute_node(idx);
   const Node &n = nodes_[idx];
-  if (out_host) ops_.d2h(out_host, n.buf, sizeof(double) * (size_t)n.elems * R_);
+  if (out_host) ops_.d2h(out_host, n.buf.as<double>(), sizeof(double) * (size_t)n.elems * R_);
   return n.elems * R_;
 }
 void CpEngine::mttkrp(int mode, double *M_host) {
@@ -3398,29 +3303,29 @@ void CpEngine::mttkrp(int mode, double *M_host) {
   const Node &lf = nodes_[leaf_[mode]];
   const int64_t s = V_.glens[mode];
   if (!dist_) {
-    ops_.d2h(M_host, lf.buf, sizeof(double) * s * R_);
+    ops_.d2h(M_host, lf.buf.as<double>(), sizeof(double) * s * R_);
     return;
   }
   const int64_t blk = block_rows(s, P_);
   if (mode == 0) {
-    ops_.zero(sendbuf_, sizeof(double) * blk * P_ * R_);
+    ops_.zero(sendbuf_.as<double>(), sizeof(double) * blk * P_ * R_);
     // place the owner's complete rows into its block, then sum (other blocks are zero)
-    double *mine = sendbuf_ + (size_t)rank_ * blk * R_;
+    double *mine = sendbuf_.as<double>() + (size_t)rank_ * blk * R_;
     for (int r = 0; r < R_; r++)
-      ops_.d2d(mine + (size_t)r * blk, lf.buf + (size_t)r * ext(0), sizeof(double) * ext(0));
+      ops_.d2d(mine + (size_t)r * blk, lf.buf.as<double>() + (size_t)r * ext(0), sizeof(double) * ext(0));
   } else {
-    ops_.pack_blocks(lf.buf, s, s, R_, blk, P_, sendbuf_);
+    ops_.pack_blocks(lf.buf.as<double>(), s, s, R_, blk, P_, sendbuf_.as<double>());
   }
-  comm_.allreduce_sum(sendbuf_, blk * P_ * R_);
-  double *nat = (double *)ops_.alloc(sizeof(double) * s * R_);
-  ops_.unpack_blocks(sendbuf_, s, s, R_, blk, P_, nat);
+  comm_.allreduce_sum(sendbuf_.as<double>(), blk * P_ * R_);
+  DeviceBuffer natbuf(ops_, sizeof(double) * s * R_);
+  double *nat = natbuf.as<double>();
+  ops_.unpack_blocks(sendbuf_.as<double>(), s, s, R_, blk, P_, nat);
   ops_.d2h(M_host, nat, sizeof(double) * s * R_);
-  ops_.free(nat);
 }
 void CpEngine::gram_system(int mode, double lambda, double *S_host, double *Sinv_host) {
-  ops_.gram_system(G_, N_, mode, R_, lambda, S_, Sinv_);
-  ops_.d2h(S_host, S_, sizeof(double) * R_ * R_);
-  ops_.d2h(Sinv_host, Sinv_, sizeof(double) * R_ * R_);
+  ops_.gram_system(G_.as<double>(), N_, mode, R_, lambda, S_.as<double>(), Sinv_.as<double>());
+  ops_.d2h(S_host, S_.as<double>(), sizeof(double) * R_ * R_);
+  ops_.d2h(Sinv_host, Sinv_.as<double>(), sizeof(double) * R_ * R_);
 }
 
 // ---------------------------------------------------------------------------- PP operators
@@ -3532,15 +3437,12 @@ void *CpEngine::pp_buffer(const std::string &seq, size_t bytes) {
       }
     }
   }
-  PPBuf &b = pp_pool_[key];
-  if (b.cap < bytes) {
-    ops_.free(b.buf);
-    b.buf = nullptr;
-    b.cap = 0;
-    b.buf = big_alloc(bytes);
-    b.cap = bytes;
+  DeviceBuffer &b = pp_pool_[key];
+  if (b.size() < bytes) {
+    b.reset();
+    b = big_alloc(bytes);
   }
-  return b.buf;
+  return b.get();
 }
 static std::string all_but(int N, int i, int j = -1) {
   std::string s;
@@ -3604,8 +3506,7 @@ void CpEngine::pp_build_all() {
   // one per level saves the hipMalloc / hipFree of every phase)
   const size_t keep = (size_t)2 << 30;
   for (auto it = pp_pool_.begin(); it != pp_pool_.end();) {
-    if (it->first[0] == '#' && it->second.cap > keep) {
-      ops_.free(it->second.buf);
+    if (it->first[0] == '#' && it->second.size() > keep) {
       it = pp_pool_.erase(it);
     } else {
       ++it;
@@ -3697,10 +3598,10 @@ void CpEngine::sweep_pp(double lambda, double ratio) {
   if (nonneg()) throw Unsupported("ppals: a non-negative session has no pairwise-perturbation sweep");
   if (any_nonfree()) throw Unsupported("ppals: a session with constrained modes has no pairwise-perturbation sweep");
   ms_invalidate();  // PP moves the factors without touching the multi-sweep cache
-  if (!Mbuf_) Mbuf_ = (double *)ops_.alloc(sizeof(double) * (size_t)maxs_ * R_);
+  if (!Mbuf_) Mbuf_ = DeviceBuffer(ops_, sizeof(double) * (size_t)maxs_ * R_);
   if (!pp_norms_) {
-    pp_norms_ = (double *)ops_.alloc(sizeof(double) * 2 * MAX_ORDER);
-    ops_.zero(pp_norms_, sizeof(double) * 2 * MAX_ORDER);
+    pp_norms_ = DeviceBuffer(ops_, sizeof(double) * 2 * MAX_ORDER);
+    ops_.zero(pp_norms_.as<double>(), sizeof(double) * 2 * MAX_ORDER);
   }
   bool norm_fused = false;
   for (int i = 0; i < N_; i++) {
@@ -3722,14 +3623,14 @@ void CpEngine::sweep_pp(double lambda, double ratio) {
     }
     // (S and S^-1 of this mode depend on the other modes' Grams only: a back end may prepare
     // them on the side of the correction's launch)
-    ops_.arm_gram_system(G_, N_, i, R_, lambda, S_, Sinv_);
-    ops_.pp_correct((const double *)M0.buf, si, R_, terms, nt, Mbuf_);
+    ops_.arm_gram_system(G_.as<double>(), N_, i, R_, lambda, S_.as<double>(), Sinv_.as<double>());
+    ops_.pp_correct((const double *)M0.buf, si, R_, terms, nt, Mbuf_.as<double>());
     if (i == N_ - 1 && !dist_) {  // Normalize at the tail of the sweep's last update launch
       int64_t rows[MAX_ORDER];
       for (int q = 0; q < N_; q++) rows[q] = V_.glens[q];
-      norm_fused = ops_.arm_normalize(W_.data(), rows, N_, R_, G_, i, pp_norms_ + 1);
+      norm_fused = ops_.arm_normalize(W_.data(), rows, N_, R_, G_.as<double>(), i, pp_norms_.as<double>() + 1);
     }
-    mode_update(i, Mbuf_, si, lambda, true, ratio);
+    mode_update(i, Mbuf_.as<double>(), si, lambda, true, ratio);
   }
   if (!norm_fused) {
     pp_norms_live_ = !dist_;
@@ -3782,8 +3683,8 @@ ModeNorms CpEngine::read_norms(bool dt_phase) {
   int64_t n[MAX_ORDER];
   for (int i = 0; i < N_; i++) n[i] = V_.glens[i] * R_;
   ops_.diff_norms(W_.data(), dt_phase ? Wprev_.data() : nullptr, n, N_, dt_phase, dW_.data(),
-                  dt_phase, scal_);
-  return ModeNorms(ops_, scal_, N_);
+                  dt_phase, scal_.as<double>());
+  return ModeNorms(ops_, scal_.as<double>(), N_);
 }
 
 void CpEngine::dt_sub(RunReport &rep, const CpOpts &o, double &projnorm, int &iter) {
@@ -3817,8 +3718,8 @@ void CpEngine::pp_sub(RunReport &rep, const CpOpts &o, double &projnorm, int &it
     int num_dw_break = 0;
     if (!o.bench) {
       // dW as the exact phase left it, later as the launches of the previous approximate sweep did
-      const bool fused = iter != init_iter && !dist_ && pp_norms_;
-      const ModeNorms m = fused ? ModeNorms(ops_, pp_norms_, N_) : read_norms(false);
+      const bool fused = iter != init_iter && !dist_ && pp_norms_.as<double>();
+      const ModeNorms m = fused ? ModeNorms(ops_, pp_norms_.as<double>(), N_) : read_norms(false);
       num_dw_break = m.count(o.tol_init, true);
     }
     if ((iter - init_iter) % 15 == 0 || num_dw_break > 0) {
@@ -3883,17 +3784,17 @@ void CpEngine::pp_partupdate_sub(RunReport &rep, const CpOpts &o, double &projno
       if (dist_ && i != 0) {
         // dM_i is a partial sum over this rank's rows of the sharded mode: complete a copy of it.
         // (Mm_i was completed in place by the all-reduce inside its own mode update.)
-        ops_.d2d(sendbuf_, dM_[i], sizeof(double) * ext(i) * R_);
-        comm_.allreduce_sum(sendbuf_, ext(i) * R_);
-        ops_.sumsq(sendbuf_, ext(i) * R_, scal_ + 2 * i);
+        ops_.d2d(sendbuf_.as<double>(), dM_[i], sizeof(double) * ext(i) * R_);
+        comm_.allreduce_sum(sendbuf_.as<double>(), ext(i) * R_);
+        ops_.sumsq(sendbuf_.as<double>(), ext(i) * R_, scal_.as<double>() + 2 * i);
       } else {
-        ops_.sumsq(dM_[i], ext(i) * R_, scal_ + 2 * i);
+        ops_.sumsq(dM_[i], ext(i) * R_, scal_.as<double>() + 2 * i);
       }
-      ops_.sumsq(Mm_[i], ext(i) * R_, scal_ + 2 * i + 1);
+      ops_.sumsq(Mm_[i], ext(i) * R_, scal_.as<double>() + 2 * i + 1);
     }
     // the sharded mode holds complete ROWS: its two sums of squares add up over the ranks
-    if (dist_) comm_.allreduce_sum(scal_, 2);
-    const ModeNorms m(ops_, scal_, N_);  // ||dM_i||, ||M_i||
+    if (dist_) comm_.allreduce_sum(scal_.as<double>(), 2);
+    const ModeNorms m(ops_, scal_.as<double>(), N_);  // ||dM_i||, ||M_i||
     for (int i = 0; i < N_; i++) relpert[i] = m.d[i] / m.w[i];
     normalize();
     grad_from_sweep_ = true;
@@ -3919,11 +3820,11 @@ int CpEngine::run_pp_common(const CpOpts &o, int *iters, bool partupdate) {
   if (partupdate && rank_ == 0 && o.verbose) std::cout << "alsCP_PP_partupdate starts. " << std::endl;
   for (int i = 0; i < N_; i++) {
     size_t n = sizeof(double) * V_.glens[i] * R_;
-    if (!Wprev_[i]) Wprev_[i] = (double *)ops_.alloc(n);
-    if (!Winit_[i]) Winit_[i] = (double *)ops_.alloc(n);
-    if (!dW_[i]) dW_[i] = (double *)ops_.alloc(n);
-    if (partupdate && !dM_[i]) dM_[i] = (double *)ops_.alloc(n);
-    if (partupdate && !Mm_[i]) Mm_[i] = (double *)ops_.alloc(n);
+    if (!Wprev_[i]) Wprev_.alloc(ops_, i, n);
+    if (!Winit_[i]) Winit_.alloc(ops_, i, n);
+    if (!dW_[i]) dW_.alloc(ops_, i, n);
+    if (partupdate && !dM_[i]) dM_.alloc(ops_, i, n);
+    if (partupdate && !Mm_[i]) Mm_.alloc(ops_, i, n);
     ops_.zero(dW_[i], n);
   }
   RunReport rep(o, rank_ == 0, V_.glens[0], "gradnorm");

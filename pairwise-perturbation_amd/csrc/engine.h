@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "device_buffer.h"
 #include "ops.h"
 
 namespace ppals {
@@ -386,7 +387,7 @@ class CpEngine {
     int lo, hi;
     int parent = -1;   // index into nodes_, -1: parent is the root
     int slo, shi;      // sibling range
-    double *buf = nullptr;
+    DeviceBuffer buf;
     int64_t elems = 0;  // without the rank index
     bool valid = false;
   };
@@ -395,26 +396,21 @@ class CpEngine {
     int dt = F64;            // level-1 operators are kept in the tensor's own precision
     int64_t elems = 0;
     std::vector<int> modes;  // remaining modes in STORAGE order (first fastest)
-    bool owned = true;       // false: borrowed from the multi-sweep cache (never freed here)
+    bool owned = true;       // true: buf lies in pp_pool_; false: borrowed from the multi-sweep cache
     const double *scale = nullptr;  // pending Normalize factor of a borrowed tensor (device scalar)
   };
   // grow-only pool of the PP operator buffers: a PP phase re-uses the buffers of the previous one
   // instead of allocating / freeing ~1 GB of operators around every phase. Keyed by operator for
   // what the approximate sweeps read, by LEVEL ("#1", "#2", ...) for the scaffolding above it
-  struct PPBuf {
-    void *buf = nullptr;
-    size_t cap = 0;
-  };
-  std::map<std::string, PPBuf> pp_pool_;
+  std::map<std::string, DeviceBuffer> pp_pool_;
   void *pp_buffer(const std::string &seq, size_t bytes);
   bool pp_norms_live_ = false;  // Normalize is asked for ||W_i||^2 (inside sweep_pp)
-  double *pp_norms_ = nullptr;  // [2N]: ||dW_i||^2, ||W_i||^2 left by the fused PP mode updates
+  DeviceBuffer pp_norms_;  // [2N]: ||dW_i||^2, ||W_i||^2 left by the fused PP mode updates
 
   // a cached intermediate of the multi-sweep schedule: modes in storage order (first fastest),
   // rank index last; `scale` (device scalar) is the Normalize factor still owed to its contents
   struct RTensor {
-    void *buf = nullptr;
-    size_t cap = 0;  // bytes
+    void *buf = nullptr;  // a view: into own / tmp_own of its MsNode, a placement block or an lr_cache_
     int dt = F64;
     std::vector<int> modes;
     unsigned contracted = 0;
@@ -426,12 +422,13 @@ class CpEngine {
     int lo, hi, parent, slo, shi;  // ranges over positions of the step's cyclic mode list
     RTensor t;
     std::vector<RTensor> tmp;
+    DeviceBuffer own;                   // the storage of t
+    std::vector<DeviceBuffer> tmp_own;  // ... and of tmp[k]
   };
   void ms_build_tree(int lo, int hi, int parent);
   void ms_start_step(int root);
   void ms_compute(int idx);
-  void ms_reserve(RTensor &t, size_t bytes);
-  void ms_contract(const RTensor &src, int mode, RTensor &dst, const double *in_scale);
+  void ms_contract(const RTensor &src, int mode, RTensor &dst, DeviceBuffer &own, const double *in_scale);
   void sweep_msdt(double lambda);
   void ms_invalidate() { ms_root_ = -1; }
   int schedule_ = 1;  // 1: multi-sweep dimension tree (default), 0: the reference's two-node tree
@@ -442,7 +439,7 @@ class CpEngine {
   // (extent 3 at R = 10: X is 3.3 x the tensor — the reference's coil-100 / time-lapse shapes). The root
   // set is slid back past them (ms_next_root); the cost model prices both (ms_schedule_cost).
   int test_blocks_ = 0;            // PPALS_TEST_BLOCKED_UPDATE (test hook, see mode_update)
-  double *test_blkbuf_ = nullptr;
+  DeviceBuffer test_blkbuf_;
   unsigned ms_excl_ = 0;
   bool ms_set_excluded(int first, int k, unsigned excl) const;
   int ms_next_root(int i, int k, unsigned excl) const;  // first mode of the root set that serves update i, -1: none
@@ -489,10 +486,9 @@ class CpEngine {
   PlaceExplore ms_place_[MAX_ORDER];
   void ms_place_collect(PlaceExplore &ex);
   int ms_place_pick(PlaceExplore &ex);
-  void *ms_X_base_ = nullptr;
-  void *ms_X_alt_ = nullptr;  // the second candidate block (nullptr: none / released)
+  DeviceBuffer ms_X_base_;
+  DeviceBuffer ms_X_alt_;  // the second candidate block, as large as the first (empty: none / released)
   void ms_place_release_unchosen();
-  size_t ms_X_cap_ = 0;
   int64_t pp_builds_ = 0;
   double pp_build_s_ = 0;
   bool pp_build_timed_ = false;
@@ -500,7 +496,7 @@ class CpEngine {
   size_t ms_X_slack() const;
   static double place_min_bytes();
   size_t ms_X_bytes(int first, int k) const;
-  void *big_alloc(size_t bytes);  // gives optional resident layouts back when the device is full
+  DeviceBuffer big_alloc(size_t bytes);  // gives optional resident layouts back when the device is full
   std::vector<MsNode> ms_nodes_;
   // ---- low-rank-update optimizers of the class API (CPDTLROptimizer / CPMSDTLROptimizer,
   // src/optimizer/cp_dt_lr_optimizer.cxx, cp_msdt_lr_optimizer.cxx; randomsvd = 0). The first
@@ -510,21 +506,20 @@ class CpEngine {
   void lr_step_begin(int left, bool reuse, int r);
   void lr_mode_update(int i, double lambda, int r, const double *base);
   void lr_release();
-  void *lr_cache_[MAX_ORDER] = {nullptr};
+  DeviceBuffer lr_cache_[MAX_ORDER];
   bool lr_have_[MAX_ORDER] = {false};
   bool lr_random_ = false;        // randomized_svd in the rank-r update (common.cxx:691-709)
   uint64_t lr_random_calls_ = 0;  // blocks of R*r draws consumed in this run
   RTensor lr_desc_[MAX_ORDER];
   void *ms_X_override_ = nullptr;  // ms_start_step writes the first-level intermediate here
-  double *lr_X_ = nullptr, *lr_Us_ = nullptr, *lr_G2_ = nullptr, *lr_small_ = nullptr;
-  double *lr_T_ = nullptr;
-  size_t lr_T_cap_ = 0;
+  DeviceBuffer lr_X_, lr_Us_, lr_G2_, lr_small_;
+  DeviceBuffer lr_T_;  // (grow-only)
 
 
   std::vector<int> ms_order_;  // the N-k modes of the step in update order
   std::vector<int> ms_leaf_;   // node index of each list position
-  double *ms_scales_ = nullptr;  // one pending-Normalize scalar per cached tensor (<= 32)
-  const double *ms_scale_of(const RTensor &t) const { return t.pending ? ms_scales_ + t.slot : nullptr; }
+  DeviceBuffer ms_scales_;  // one pending-Normalize scalar per cached tensor (<= 32)
+  const double *ms_scale_of(const RTensor &t) const { return t.pending ? ms_scales_.as<double>() + t.slot : nullptr; }
 
   int64_t ext(int m) const { return m == 0 ? V_.llens[0] : V_.glens[m]; }
   FactorRef fref(int m, double *const *W) const;
@@ -586,39 +581,32 @@ class CpEngine {
   // (K_ x s_mode bytes), bit b set for a start that holds something out, the scores shaped like W_[mode]
   int hold_mode_ = -1;
   std::vector<uint8_t> hold_keep_;
-  uint8_t *hold_keep_dev_ = nullptr;
+  DeviceBuffer hold_keep_dev_;
   unsigned hold_mask_ = 0;
-  double *hold_scores_ = nullptr;
+  DeviceBuffer hold_scores_;
   int64_t hold_rows_ = 0;  // the extent the two device buffers were allocated for
   void hold_apply(unsigned starts);  // Ops::cp_hold_rows on the starts of hold_mask_ & starts
   bool dist_ = false;  // take the collective code paths (P_ > 1, or PPALS_FORCE_COMM=1 for tests)
-  std::vector<double *> W_, gradW_, Wprev_, Winit_, dW_, dM_, Mm_;
-  double *G_ = nullptr;       // N Gram matrices, R*R each
-  double *S_ = nullptr, *Sinv_ = nullptr;
-  double *gradsq_ = nullptr;  // per-mode local sum of grad^2 (device)
-  double *scal_ = nullptr;    // small device scalar scratch (>= 4*MAX_ORDER)
-  double *sendbuf_ = nullptr, *recvbuf_ = nullptr, *gatherbuf_ = nullptr;
-  double *Mbuf_ = nullptr;    // PP: M_i^0 + corrections
-  double *Qbuf_ = nullptr, *Pbuf_ = nullptr;  // residual KRP operands
-  double *xq_ = nullptr, *xp_ = nullptr;      // model export KRP operands (grow-only, kept)
-  int64_t xq_cap_ = 0, xp_cap_ = 0;
+  DeviceBufferTable W_, gradW_, Wprev_, Winit_, dW_, dM_, Mm_;
+  DeviceBuffer G_;            // N Gram matrices, R*R each
+  DeviceBuffer S_, Sinv_;
+  DeviceBuffer gradsq_;  // per-mode local sum of grad^2 (device)
+  DeviceBuffer scal_;    // small device scalar scratch (>= 4*MAX_ORDER)
+  DeviceBuffer sendbuf_, recvbuf_, gatherbuf_;
+  DeviceBuffer Mbuf_;    // PP: M_i^0 + corrections
+  DeviceBuffer Qbuf_, Pbuf_;  // residual KRP operands
+  DeviceBuffer xq_, xp_;      // model export KRP operands (grow-only, kept)
   int residual_form_ = RESIDUAL_FUSED;        // PPALS_MODEL_RESIDUAL
   // core_consistency: the pseudo-inverse factors (laid out like W_), the per-start flag and score, the
   // first contraction Y, the two chain buffers and the cores (all grow-only, kept for the next call)
-  std::vector<double *> cc_P_;
-  int *cc_flag_ = nullptr;
-  double *cc_out_ = nullptr;
-  struct GrowBuf {
-    void *ptr = nullptr;
-    size_t cap = 0;
-  };
-  GrowBuf cc_Y_, cc_chain_[2], cc_core_;
+  DeviceBufferTable cc_P_;
+  DeviceBuffer cc_flag_, cc_out_;
+  DeviceBuffer cc_Y_, cc_chain_[2], cc_core_;
   // slice_residuals / leverages: the two marginals, the folded result, the partial sums of the pass
-  GrowBuf sl_row_, sl_col_, sl_out_, sl_work_;
+  DeviceBuffer sl_row_, sl_col_, sl_out_, sl_work_;
   size_t slice_work_cap_ = (size_t)256 << 20;  // of the back end's partial sums (PPALS_TEST_SLICE_WORK_BYTES)
-  GrowBuf fms_out_, fms_work_;  // congruence: Phi | w_a | w_b, and the back end's partial sums
+  DeviceBuffer fms_out_, fms_work_;  // congruence: Phi | w_a | w_b, and the back end's partial sums
   StartTable start_table() const;  // tab_, or the one start of an ordinary session
-  void *cc_reserve(GrowBuf &b, size_t bytes);
   // Resident storage orders of the local tensor that the scans may read. [0] is the tensor itself.
   // [1] (if built) lists the right-half modes first, so that contractions of left-half modes are
   // row-contiguous suffix scans too. When the tensor's column strides are not multiples of 128 B
@@ -628,12 +616,11 @@ class CpEngine {
   // at a position >= q of a padded layout reads 128-B aligned columns, and the scan writes its
   // result compact (RowPad), so nothing else knows about the padding.
   struct Layout {
-    void *ptr = nullptr;
+    void *ptr = nullptr;      // the tensor itself, or own
+    DeviceBuffer own;         // the copy (empty: [0])
     std::vector<int> order;   // modes, fastest first
     int q = 0;                // leading modes in the padded block (0: not padded)
     int64_t blk = 0, ld = 0;  // real / stored elements of that block
-    bool owned = false;
-    size_t bytes = 0;         // of an owned layout
   };
   std::vector<Layout> lay_;
   // Packed twins of unpadded fp32 layouts (engine.cpp, packed_for): one per (layout, scan shape)
@@ -642,7 +629,7 @@ class CpEngine {
     int layout = 0;             // index into lay_
     const void *src = nullptr;  // that layout's elements
     int64_t L = 0, J = 0, T = 0;
-    void *data = nullptr, *bases = nullptr, *esc = nullptr;
+    DeviceBuffer data, bases, esc;
     int format = 0;             // PACK_FMT28 / PACK_FMT26 (0: no copy)
     int64_t escapes = 0;        // blocks that need an escape plane in format 26, as surveyed
     size_t esc_room = 0;        // bytes behind esc

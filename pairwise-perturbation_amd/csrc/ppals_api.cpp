@@ -40,6 +40,7 @@ struct ppals_ctx {
 struct ppals_tensor {
   ppals_ctx *ctx;
   TensorDesc d;
+  DeviceBuffer data;        // owns d.data (empty in a dead handle)
   uint64_t generation = 1;  // bumped by every fill / upload; sessions rebuild what they derived
   uint64_t prep_epoch = 0;  // bumped by center / shift / scale / rescale (TensorDesc::prep_epoch)
 };
@@ -64,8 +65,8 @@ struct ppals_parafac2 {
   int R;
   ppals_tensor *Y;
   ppals_cp *cp;
-  double *P, *Q, *T, *out;  // I x R x K twice, R x R x K, 3 doubles
-  int *status;              // K
+  DeviceBuffer P, Q, T, out;  // I x R x K twice, R x R x K, 3 doubles
+  DeviceBuffer status;        // K ints
 };
 
 #define API_BEGIN try {
@@ -115,14 +116,12 @@ int ppals_ctx_create(ppals_ctx **out, int device) {
   API_END(PPALS_ERR_NO_DEVICE)
 }
 static void p2_free_buffers(ppals_parafac2 *p) {
-  for (void *b : {(void *)p->P, (void *)p->Q, (void *)p->T, (void *)p->out, (void *)p->status}) {
+  for (DeviceBuffer *b : {&p->P, &p->Q, &p->T, &p->out, &p->status}) {
     try {
-      p->ctx->ops->free(b);
+      b->reset();
     } catch (...) {
     }
   }
-  p->P = p->Q = p->T = p->out = nullptr;
-  p->status = nullptr;
 }
 void ppals_ctx_destroy(ppals_ctx *ctx) {
   if (!ctx) return;
@@ -147,7 +146,7 @@ void ppals_ctx_destroy(ppals_ctx *ctx) {
   }
   for (ppals_tensor *t : ctx->tensors) {
     try {
-      ctx->ops->free(t->d.data);
+      t->data.reset();
     } catch (...) {
     }
     t->d.data = nullptr;
@@ -220,6 +219,7 @@ int ppals_tensor_create(ppals_ctx *ctx, int order, const int64_t *global_lens, i
     g_err = "ppals_tensor_create: " + err;
     return PPALS_ERR_ARG;
   }
+  t->data = DeviceBuffer(*ctx->ops, t->d.data, (size_t)t->d.nloc * dtype_size(dtype));
   t->d.generation = &t->generation;
   t->d.prep_epoch = &t->prep_epoch;
   ctx->tensors.insert(t.get());
@@ -231,7 +231,7 @@ void ppals_tensor_destroy(ppals_tensor *t) {
   if (!t) return;
   if (t->ctx) {
     try {
-      t->ctx->ops->free(t->d.data);
+      t->data.reset();
     } catch (...) {
     }
     t->ctx->tensors.erase(t);
@@ -377,11 +377,10 @@ int ppals_tensor_center(ppals_tensor *t, int mode, double *offsets, int where, v
     ops.release_stream(stream);
     return PPALS_OK;
   }
-  double *tmp = (double *)ops.alloc(sizeof(double) * s.L * s.T);
+  DeviceBuffer tmp(ops, sizeof(double) * s.L * s.T);
   prep_bump(t);
-  tensor_center(ops, t->d, mode, tmp);
-  ops.d2h(offsets, tmp, sizeof(double) * s.L * s.T);
-  ops.free(tmp);
+  tensor_center(ops, t->d, mode, tmp.as<double>());
+  ops.d2h(offsets, tmp.as<double>(), sizeof(double) * s.L * s.T);
   return PPALS_OK;
   API_END(PPALS_ERR_HIP)
 }
@@ -404,11 +403,11 @@ int ppals_tensor_shift(ppals_tensor *t, int mode, const double *offsets, int whe
     ops.release_stream(stream);
     return PPALS_OK;
   }
-  double *tmp = (double *)ops.alloc(sizeof(double) * s.L * s.T);
-  ops.h2d(tmp, offsets, sizeof(double) * s.L * s.T);
+  DeviceBuffer tmp(ops, sizeof(double) * s.L * s.T);
+  ops.h2d(tmp.as<double>(), offsets, sizeof(double) * s.L * s.T);
   prep_bump(t);
-  tensor_shift(ops, t->d, mode, tmp, alpha);
-  ops.free(tmp);  // (waits for the launch: the host buffer has been consumed long before)
+  tensor_shift(ops, t->d, mode, tmp.as<double>(), alpha);
+  tmp.reset();  // (waits for the launch: the host buffer has been consumed long before)
   return PPALS_OK;
   API_END(PPALS_ERR_HIP)
 }
@@ -1173,13 +1172,13 @@ int ppals_parafac2_create(ppals_ctx *ctx, int64_t I, int64_t J, int64_t K, int R
   ppals_parafac2 *q = p.release();
   try {
     const size_t n = sizeof(double) * (size_t)I * R * K;
-    q->P = (double *)ctx->ops->alloc(n);
-    q->Q = (double *)ctx->ops->alloc(n);
-    q->T = (double *)ctx->ops->alloc(sizeof(double) * (size_t)R * R * K);
-    q->out = (double *)ctx->ops->alloc(sizeof(double) * 3);
-    q->status = (int *)ctx->ops->alloc(sizeof(int) * (size_t)K);
-    ctx->ops->zero(q->status, sizeof(int) * (size_t)K);
-    ctx->ops->parafac2_init(q->P, I, R, K);
+    q->P = DeviceBuffer(*ctx->ops, n);
+    q->Q = DeviceBuffer(*ctx->ops, n);
+    q->T = DeviceBuffer(*ctx->ops, sizeof(double) * (size_t)R * R * K);
+    q->out = DeviceBuffer(*ctx->ops, sizeof(double) * 3);
+    q->status = DeviceBuffer(*ctx->ops, sizeof(int) * (size_t)K);
+    ctx->ops->zero(q->status.get(), sizeof(int) * (size_t)K);
+    ctx->ops->parafac2_init(q->P.as<double>(), I, R, K);
   } catch (...) {
     ppals_parafac2_destroy(q);
     throw;
@@ -1227,19 +1226,19 @@ static int p2_check_step(ppals_parafac2 *p, const char *fn, const void *data, in
   st->I = p->I, st->J = p->J, st->K = p->K, st->R = p->R;
   st->X = data, st->vdt = dtype, st->s1 = a.stride[1], st->s2 = a.stride[2];
   st->B = e.factor_device(0), st->A = e.factor_device(1), st->C = e.factor_device(2);
-  st->Q = p->Q, st->P = p->P, st->T = p->T, st->status = p->status;
+  st->Q = p->Q.as<double>(), st->P = p->P.as<double>(), st->T = p->T.as<double>(), st->status = p->status.as<int>();
   st->min_ratio = PPALS_ORTHO_MIN_RATIO;
   st->Y = p->Y->d.data, st->dt = p->Y->d.dtype;
   return PPALS_OK;
 }
 static void p2_step(ppals_parafac2 *p, Ops::Parafac2Step st, void *stream, double *lost_sq, int *failed) {
   const bool want = lost_sq || failed;
-  st.out = want ? p->out : nullptr;
+  st.out = want ? p->out.as<double>() : nullptr;
   p->Y->generation++;  // the contents change with these launches: the session rebuilds what it derived
   p->ctx->ops->parafac2_step(st, stream);
   if (!want) return;
   double o[3];
-  p->ctx->ops->d2h(o, p->out, sizeof(o));
+  p->ctx->ops->d2h(o, p->out.as<double>(), sizeof(o));
   if (lost_sq) *lost_sq = o[0] - o[1];
   if (failed) *failed = (int)o[2];
 }
@@ -1280,13 +1279,13 @@ int ppals_parafac2_run(ppals_parafac2 *p, const void *data, int dtype, const int
 int ppals_parafac2_projections(ppals_parafac2 *p, double *P_host) {
   if (!p || !p->ctx || !P_host) return fail(PPALS_ERR_ARG, "ppals_parafac2_projections: NULL argument or dead handle");
   API_BEGIN
-  p->ctx->ops->d2h(P_host, p->P, sizeof(double) * (size_t)p->I * p->R * p->K);
+  p->ctx->ops->d2h(P_host, p->P.as<double>(), sizeof(double) * (size_t)p->I * p->R * p->K);
   return PPALS_OK;
   API_END(PPALS_ERR_HIP)
 }
 int ppals_parafac2_projections_device(ppals_parafac2 *p, const double **P) {
   if (!p || !p->ctx || !P) return fail(PPALS_ERR_ARG, "ppals_parafac2_projections_device: NULL argument or dead handle");
-  *P = p->P;
+  *P = p->P.as<double>();
   return PPALS_OK;
 }
 

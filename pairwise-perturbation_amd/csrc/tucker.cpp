@@ -31,24 +31,25 @@ TuckerEngine::TuckerEngine(Ops &ops, Comm &comm, const TensorDesc &V, const int 
     for (int i = 0; i < N_ && i < MAX_ORDER; i++)
       if (V_.glens[i] > 64) ops_.eig_lazy(eig_base_ + i, true);
   int64_t maxs = 0;
+  W_.resize(N_);
   for (int i = 0; i < N_; i++) {
     if (ranks[i] <= 0 || ranks[i] > V_.glens[i])
       throw std::runtime_error("ppals: Tucker rank out of range");
     r_.push_back(ranks[i]);
     ncore_ *= ranks[i];
     maxs = std::max(maxs, V_.glens[i]);
-    W_.push_back((double *)ops_.alloc(sizeof(double) * V_.glens[i] * ranks[i]));
-    ops_.zero(W_.back(), sizeof(double) * V_.glens[i] * ranks[i]);
+    W_.alloc(ops_, i, sizeof(double) * V_.glens[i] * ranks[i]);
+    ops_.zero(W_[i], sizeof(double) * V_.glens[i] * ranks[i]);
   }
-  core_ = (double *)ops_.alloc(sizeof(double) * ncore_);
-  core_prev_ = (double *)ops_.alloc(sizeof(double) * ncore_);
-  ops_.zero(core_, sizeof(double) * ncore_);
-  ops_.zero(core_prev_, sizeof(double) * ncore_);
-  G_ = (double *)ops_.alloc(sizeof(double) * maxs * maxs);
+  core_ = DeviceBuffer(ops_, sizeof(double) * ncore_);
+  core_prev_ = DeviceBuffer(ops_, sizeof(double) * ncore_);
+  ops_.zero(core_.as<double>(), sizeof(double) * ncore_);
+  ops_.zero(core_prev_.as<double>(), sizeof(double) * ncore_);
+  G_ = DeviceBuffer(ops_, sizeof(double) * maxs * maxs);
   if (const char *e = std::getenv("PPALS_TUCKER_THIN")) thin_enabled_ = std::atoi(e) != 0;
-  scal_ = (double *)ops_.alloc(sizeof(double) * 64);
+  scal_ = DeviceBuffer(ops_, sizeof(double) * 64);
   yend_elems_ = ncore_ / r_[N_ - 1] * V_.glens[N_ - 1];
-  Yend_ = (double *)ops_.alloc(sizeof(double) * yend_elems_);
+  Yend_ = DeviceBuffer(ops_, sizeof(double) * yend_elems_);
   build_tree(0, N_ - 1, -1);
   leaf_.assign(N_, -1);
   for (size_t k = 0; k < nodes_.size(); k++)
@@ -62,16 +63,16 @@ TuckerEngine::TuckerEngine(Ops &ops, Comm &comm, const TensorDesc &V, const int 
     int64_t rows = 1, cols = 1;
     for (int m = 0; m <= mid; m++) rows *= ext(m);
     for (int m = mid + 1; m < N_; m++) cols *= ext(m);
-    VT_ = ops_.try_alloc((size_t)rows * cols * dtype_size(V_.dtype));
-    if (VT_) ops_.transpose2d(V_.data, V_.dtype, rows, cols, VT_);
+    VT_ = DeviceBuffer::try_alloc(ops_, (size_t)rows * cols * dtype_size(V_.dtype));
+    if (VT_) ops_.transpose2d(V_.data, V_.dtype, rows, cols, VT_.get());
     // the third rotation [1 2 | 0] for the order-3 multi-sweep schedule (tucker.h), room permitting
     const char *chain = std::getenv("PPALS_TUCKER_CHAIN");
-    if (N_ == 3 && !dist_ && VT_ && !(chain && std::string(chain) == "tree")) {
+    if (N_ == 3 && !dist_ && VT_.get() && !(chain && std::string(chain) == "tree")) {
       const size_t bytes = (size_t)V_.nloc * dtype_size(V_.dtype);
       const size_t avail = ops_.mem_available();
-      if (avail == (size_t)-1 || (double)avail > 2.0 * (double)bytes + 2e9) VT2_ = ops_.try_alloc(bytes);
+      if (avail == (size_t)-1 || (double)avail > 2.0 * (double)bytes + 2e9) VT2_ = DeviceBuffer::try_alloc(ops_, bytes);
       if (VT2_) {
-        ops_.transpose2d(V_.data, V_.dtype, ext(0), ext(1) * ext(2), VT2_);
+        ops_.transpose2d(V_.data, V_.dtype, ext(0), ext(1) * ext(2), VT2_.get());
         ms3_ = true;
       }
     }
@@ -103,35 +104,28 @@ double *TuckerEngine::ms3_leaf(int i, int64_t *T) {
   if (ms3_root_ < 0 || ms3_root_ == i || ms3_left_ <= 0) {
     // root = the mode updated last before i: serves i and the mode after it
     const int r = (i + 2) % 3;
-    const void *lay = r == 2 ? V_.data : (r == 1 ? VT_ : VT2_);  // storage order (r+1, r+2, r)
+    const void *lay = r == 2 ? V_.data : (r == 1 ? VT_.get() : VT2_.get());  // storage order (r+1, r+2, r)
     const int64_t d0 = ext((r + 1) % 3), d1 = ext((r + 2) % 3);
     const size_t need = dtype_size(V_.dtype) * (size_t)(d0 * d1 * r_[r]);
-    if (ms3_cap_ < need) {
-      ops_.free(ms3_X_);
-      ms3_X_ = ops_.alloc(need);
-      ms3_cap_ = need;
-    }
+    ms3_X_.reserve(ops_, need);
     FactorRef f;
     f.ptr = wptr(r);
     f.rows = ext(r);
     f.ld = V_.glens[r];
-    ops_.scan_contract(lay, V_.dtype, d0 * d1, ext(r), 1, &f, 1, r_[r], ms3_X_, V_.dtype, d0 * d1 * r_[r], d0 * d1);
+    ops_.scan_contract(lay, V_.dtype, d0 * d1, ext(r), 1, &f, 1, r_[r], ms3_X_.get(), V_.dtype, d0 * d1 * r_[r], d0 * d1);
     ms3_root_ = r;
     ms3_left_ = 2;
   }
   const int r = ms3_root_, m0 = (r + 1) % 3, m1 = (r + 2) % 3;  // X[s_m0, s_m1, rank_r]
   const int64_t d0 = ext(m0), d1 = ext(m1);
   const int64_t elems = (int64_t)V_.glens[i] * (i == m0 ? r_[m1] : r_[m0]) * r_[r];
-  if (ms3_Ycap_[i] < elems) {
-    ops_.free(ms3_Y_[i]);
-    ms3_Y_[i] = (double *)ops_.alloc(sizeof(double) * elems);
-    ms3_Ycap_[i] = elems;
-  }
+  ms3_Y_[i].reserve(ops_, sizeof(double) * elems);
   if (i == m0) {  // keep the first mode in front, contract the second: [s_m0 | rank_m1, rank_r]
-    ops_.ttm_keep(ms3_X_, V_.dtype, d0, d1, r_[r], wptr(m1), V_.glens[m1], r_[m1], ms3_Y_[i]);
+    ops_.ttm_keep(ms3_X_.get(), V_.dtype, d0, d1, r_[r], wptr(m1), V_.glens[m1], r_[m1], ms3_Y_[i].as<double>());
     *T = (int64_t)r_[m1] * r_[r];
   } else {        // contract the leading mode, the second one comes to the front: [s_m1 | rank_m0, rank_r]
-    if (!ops_.ttm_lead_front(ms3_X_, V_.dtype, d0, d1, r_[r], wptr(m0), V_.glens[m0], r_[m0], ms3_Y_[i])) {
+    if (!ops_.ttm_lead_front(ms3_X_.get(), V_.dtype, d0, d1, r_[r], wptr(m0), V_.glens[m0], r_[m0],
+        ms3_Y_[i].as<double>())) {
       ms3_ = false;
       ms3_invalidate();
       return nullptr;
@@ -142,7 +136,7 @@ double *TuckerEngine::ms3_leaf(int i, int64_t *T) {
   // other < root
   ms3_perm_ = (i == m0 ? m1 : m0) > r;
   ms3_left_--;
-  return ms3_Y_[i];
+  return ms3_Y_[i].as<double>();
 }
 
 // see CpEngine::check_tensor_generation: the tensor handle stays writable while sessions exist
@@ -154,9 +148,9 @@ void TuckerEngine::check_tensor_generation() {
     int64_t rows = 1, cols = 1;
     for (int m = 0; m <= mid; m++) rows *= ext(m);
     for (int m = mid + 1; m < N_; m++) cols *= ext(m);
-    ops_.transpose2d(V_.data, V_.dtype, rows, cols, VT_);
+    ops_.transpose2d(V_.data, V_.dtype, rows, cols, VT_.get());
   }
-  if (VT2_) ops_.transpose2d(V_.data, V_.dtype, ext(0), ext(1) * ext(2), VT2_);
+  if (VT2_) ops_.transpose2d(V_.data, V_.dtype, ext(0), ext(1) * ext(2), VT2_.get());
   ms3_invalidate();
   for (auto &n : nodes_) n.valid = false;
   pp_clear();
@@ -171,32 +165,6 @@ TuckerEngine::~TuckerEngine() {
     ops_.eig_session_free(eig_base_);
   } catch (...) {
   }
-  for (auto p : W_) ops_.free(p);
-  for (auto p : Wsave_) ops_.free(p);
-  for (auto &n : nodes_) ops_.free(n.buf);
-  ops_.free(core_);
-  ops_.free(core_prev_);
-  ops_.free(Yend_);
-  ops_.free(G_);
-  ops_.free(thin_);
-  ops_.free(scal_);
-  ops_.free(Yfull_);
-  ops_.free(gather_);
-  ops_.free(Ytmp_);
-  ops_.free(Yacc_);
-  ops_.free(chain_[0]);
-  ops_.free(chain_[1]);
-  ops_.free(xwt_);
-  ops_.free(xz_[0]);
-  ops_.free(xz_[1]);
-  ops_.free(VT_);
-  ops_.free(VT2_);
-  ops_.free(ms3_X_);
-  for (auto p : ms3_Y_) ops_.free(p);
-  for (auto p : Wprev_) ops_.free(p);
-  for (auto p : Winit_) ops_.free(p);
-  for (auto p : dW_) ops_.free(p);
-  pp_clear();
 }
 
 void TuckerEngine::build_tree(int lo, int hi, int parent) {
@@ -211,7 +179,7 @@ void TuckerEngine::build_tree(int lo, int hi, int parent) {
     n.parent = parent;
     n.slo = ranges[1 - c][0];
     n.shi = ranges[1 - c][1];
-    nodes_.push_back(n);
+    nodes_.push_back(std::move(n));
     idx[c] = (int)nodes_.size() - 1;
   }
   build_tree(lo, mid, idx[0]);
@@ -234,7 +202,7 @@ void TuckerEngine::compute_left_half_on_vt(Node &n) {
   std::vector<int64_t> dims;              // extents in VT storage order
   for (int m = nl; m < N_; m++) dims.push_back(ext(m));
   for (int m = 0; m < nl; m++) dims.push_back(ext(m));
-  const void *cur = VT_;
+  const void *cur = VT_.get();
   int cur_dt = V_.dtype;
   int pp_slot = 0;
   // A LEAF (one mode on the right: order 3) keeps the chain's own order [s_mode | left ranks]: that
@@ -243,11 +211,7 @@ void TuckerEngine::compute_left_half_on_vt(Node &n) {
   const bool front_leaf = (nr == 1) && !dist_;
   int64_t node_elems_total = 1;
   for (int m = 0; m < N_; m++) node_elems_total *= (m >= nl ? ext(m) : r_[m]);
-  if (front_leaf && n.cap < node_elems_total) {
-    ops_.free(n.buf);
-    n.buf = (double *)ops_.alloc(sizeof(double) * node_elems_total);
-    n.cap = node_elems_total;
-  }
+  if (front_leaf) n.buf.reserve(ops_, sizeof(double) * node_elems_total);
   for (int m = n.shi; m >= 0; m--) {
     const int p = nr + m;  // storage position of mode m
     int64_t L = 1, T = 1;
@@ -258,14 +222,10 @@ void TuckerEngine::compute_left_half_on_vt(Node &n) {
     const size_t need = dtype_size(dst_dt) * (size_t)(L * r_[m] * T);
     void *dst;
     if (last && front_leaf) {
-      dst = n.buf;
+      dst = n.buf.as<double>();
     } else {
-      if (chain_cap_[pp_slot] < need) {
-        ops_.free(chain_[pp_slot]);
-        chain_[pp_slot] = ops_.alloc(need);
-        chain_cap_[pp_slot] = need;
-      }
-      dst = chain_[pp_slot];
+      chain_[pp_slot].reserve(ops_, need);
+      dst = chain_[pp_slot].get();
       pp_slot ^= 1;
     }
     FactorRef f;
@@ -274,7 +234,7 @@ void TuckerEngine::compute_left_half_on_vt(Node &n) {
     f.ld = V_.glens[m];
     // (the step that reads the tensor is a scan; a later one reads a small intermediate and writes
     // fp64: the back end may run it as one batched GEMM, Ops::ttm_keep)
-    if (cur != VT_ && dst_dt == F64)
+    if (cur != VT_.get() && dst_dt == F64)
       ops_.ttm_keep(cur, cur_dt, L, dims[p], T, f.ptr, f.ld, r_[m], (double *)dst);
     else
       ops_.scan_contract(cur, cur_dt, L, dims[p], T, &f, 1, r_[m], dst, dst_dt, L * r_[m], L);
@@ -290,12 +250,8 @@ void TuckerEngine::compute_left_half_on_vt(Node &n) {
   int64_t rows = 1, cols = 1;
   for (int q = 0; q < nr; q++) rows *= dims[q];
   for (int q = nr; q < N_; q++) cols *= dims[q];
-  if (n.cap < rows * cols) {
-    ops_.free(n.buf);
-    n.buf = (double *)ops_.alloc(sizeof(double) * rows * cols);
-    n.cap = rows * cols;
-  }
-  ops_.transpose2d(cur, F64, rows, cols, n.buf);
+  n.buf.reserve(ops_, sizeof(double) * rows * cols);
+  ops_.transpose2d(cur, F64, rows, cols, n.buf.as<double>());
   n.valid = true;
 }
 
@@ -304,7 +260,7 @@ void TuckerEngine::compute_node(int idx) {
   Node &n = nodes_[idx];
   if (n.valid) return;
   // (the sharded leaf of mode 0 keeps its own blocked layout: not this route)
-  if (n.parent < 0 && n.slo == 0 && n.shi < N_ - 1 && VT_ && !(dist_ && n.lo == 0 && n.hi == 0)) {
+  if (n.parent < 0 && n.slo == 0 && n.shi < N_ - 1 && VT_.get() && !(dist_ && n.lo == 0 && n.hi == 0)) {
     compute_left_half_on_vt(n);
     return;
   }
@@ -319,12 +275,9 @@ void TuckerEngine::compute_node(int idx) {
       int64_t T = 1;
       for (int m = 2; m < N_; m++) T *= r_[m];
       const int64_t elems = (int64_t)ext(1) * r_[0] * T;
-      if (n.cap < elems) {
-        ops_.free(n.buf);
-        n.buf = (double *)ops_.alloc(sizeof(double) * elems);
-        n.cap = elems;
-      }
-      if (ops_.ttm_lead_front(p.buf, F64, ext(0), ext(1), T, wptr(0), V_.glens[0], r_[0], n.buf)) {
+      n.buf.reserve(ops_, sizeof(double) * elems);
+      if (ops_.ttm_lead_front(p.buf.as<double>(), F64, ext(0), ext(1), T, wptr(0), V_.glens[0], r_[0],
+          n.buf.as<double>())) {
         n.front = true;
         n.valid = true;
         return;
@@ -342,7 +295,7 @@ void TuckerEngine::compute_node(int idx) {
     compute_node(n.parent);
     const Node &p = nodes_[n.parent];
     for (int m = 0; m < N_; m++) dims[m] = (m >= p.lo && m <= p.hi) ? ext(m) : r_[m];
-    src = p.buf;
+    src = p.buf.as<double>();
     dt = F64;
   }
   // contract the sibling's modes one at a time (als_Tucker.cxx:216-227). The intermediates of the
@@ -383,23 +336,15 @@ void TuckerEngine::compute_node(int idx) {
     void *dst;
     int dst_dt;
     if (last) {
-      if (n.cap < out_elems) {
-        ops_.free(n.buf);
-        n.buf = (double *)ops_.alloc(sizeof(double) * out_elems);
-        n.cap = out_elems;
-      }
-      dst = n.buf;
+      n.buf.reserve(ops_, sizeof(double) * out_elems);
+      dst = n.buf.as<double>();
       dst_dt = F64;
       if (leaf0_blocked) ops_.zero(dst, sizeof(double) * out_elems);
     } else {
       dst_dt = V_.dtype;
       const size_t need = dtype_size(dst_dt) * (size_t)out_elems;
-      if (chain_cap_[pp_slot] < need) {
-        ops_.free(chain_[pp_slot]);
-        chain_[pp_slot] = ops_.alloc(need);
-        chain_cap_[pp_slot] = need;
-      }
-      dst = chain_[pp_slot];
+      chain_[pp_slot].reserve(ops_, need);
+      dst = chain_[pp_slot].get();
       pp_slot ^= 1;
     }
     FactorRef f;
@@ -429,20 +374,12 @@ double *TuckerEngine::complete_leaf(int i, double *Yloc, int64_t elems_local) {
   const int64_t s0 = V_.glens[0], blk = block_rows(s0, P_);
   int64_t rest = 1;
   for (int m = 1; m < N_; m++) rest *= r_[m];
-  if (gather_cap_ < blk * rest * P_) {
-    ops_.free(gather_);
-    gather_ = (double *)ops_.alloc(sizeof(double) * blk * rest * P_);
-    gather_cap_ = blk * rest * P_;
-  }
-  if (yfull_cap_ < s0 * rest) {
-    ops_.free(Yfull_);
-    Yfull_ = (double *)ops_.alloc(sizeof(double) * s0 * rest);
-    yfull_cap_ = s0 * rest;
-  }
-  ops_.d2d(gather_ + (size_t)rank_ * blk * rest, Yloc, sizeof(double) * blk * rest);
-  comm_.allgather(gather_ + (size_t)rank_ * blk * rest, gather_, blk * rest);
-  ops_.unpack_blocks(gather_, s0, s0, (int)rest, blk, P_, Yfull_);
-  return Yfull_;
+  gather_.reserve(ops_, sizeof(double) * blk * rest * P_);
+  Yfull_.reserve(ops_, sizeof(double) * s0 * rest);
+  ops_.d2d(gather_.as<double>() + (size_t)rank_ * blk * rest, Yloc, sizeof(double) * blk * rest);
+  comm_.allgather(gather_.as<double>() + (size_t)rank_ * blk * rest, gather_.as<double>(), blk * rest);
+  ops_.unpack_blocks(gather_.as<double>(), s0, s0, (int)rest, blk, P_, Yfull_.as<double>());
+  return Yfull_.as<double>();
 }
 
 // TTMc (als_Tucker.cxx:76-110): chain of mode products, skipping `skip`
@@ -459,12 +396,8 @@ double *TuckerEngine::ttmc_chain(int skip, int64_t *elems) {
     for (int q = 0; q < m; q++) L *= dims[q];
     for (int q = m + 1; q < N_; q++) T *= dims[q];
     const size_t need = sizeof(double) * (size_t)(L * r_[m] * T);
-    if (chain_cap_[pp_slot] < need) {
-      ops_.free(chain_[pp_slot]);
-      chain_[pp_slot] = ops_.alloc(need);
-      chain_cap_[pp_slot] = need;
-    }
-    double *dst = (double *)chain_[pp_slot];
+    chain_[pp_slot].reserve(ops_, need);
+    double *dst = chain_[pp_slot].as<double>();
     pp_slot ^= 1;
     ops_.ttm_keep(cur, cur_dt, L, dims[m], T, wptr(m), V_.glens[m], r_[m], dst);
     prev = dst;
@@ -498,14 +431,14 @@ void TuckerEngine::ensure_core() {
   const int64_t Lc = ncore_ / r_[N_ - 1], sN = V_.glens[N_ - 1];
   const int rN = r_[N_ - 1];
   if (yend_T_ == 1) {  // the tree's order [ranks before | s_{N-1}]
-    ops_.ttm_keep(yend_src_, F64, Lc, sN, 1, W_[N_ - 1], sN, rN, core_);
+    ops_.ttm_keep(yend_src_, F64, Lc, sN, 1, W_[N_ - 1], sN, rN, core_.as<double>());
   } else {
     // the last leaf kept the mode in front, [s_{N-1} | ranks]: core^T first, then its order
-    double *tmp = (double *)ops_.alloc(sizeof(double) * ncore_);
-    ops_.ttm_keep(yend_src_, F64, 1, sN, Lc, W_[N_ - 1], sN, rN, tmp);  // [r_{N-1}, ranks before]
-    ops_.transpose2d(tmp, F64, rN, Lc, core_);
+    DeviceBuffer tmp(ops_, sizeof(double) * ncore_);
+    ops_.ttm_keep(yend_src_, F64, 1, sN, Lc, W_[N_ - 1], sN, rN, tmp.as<double>());  // [r_{N-1}, ranks before]
+    ops_.transpose2d(tmp.as<double>(), F64, rN, Lc, core_.as<double>());
     ops_.sync();
-    ops_.free(tmp);
+    tmp.reset();
   }
 }
 
@@ -514,7 +447,7 @@ void TuckerEngine::compute_core_full() {
   int64_t e;
   double *Y = ttmc_chain(-1, &e);
   if (dist_) comm_.allreduce_sum(Y, ncore_);
-  ops_.d2d(core_, Y, sizeof(double) * ncore_);
+  ops_.d2d(core_.as<double>(), Y, sizeof(double) * ncore_);
 }
 
 // Eigenvectors on demand. A plain HOOI sweep lets the back end return ANY orthonormal basis of a
@@ -532,11 +465,11 @@ void TuckerEngine::finalize_rotations() {
     int64_t L = 1, T = 1;
     for (int q = 0; q < i; q++) L *= r_[q];
     for (int q = i + 1; q < N_; q++) T *= r_[q];
-    double *tmp = (double *)ops_.alloc(sizeof(double) * ncore_);
-    ops_.ttm_keep(core_, F64, L, r, T, Y, r, r, tmp);
-    ops_.d2d(core_, tmp, sizeof(double) * ncore_);
+    DeviceBuffer tmp(ops_, sizeof(double) * ncore_);
+    ops_.ttm_keep(core_.as<double>(), F64, L, r, T, Y, r, r, tmp.as<double>());
+    ops_.d2d(core_.as<double>(), tmp.as<double>(), sizeof(double) * ncore_);
     ops_.sync();
-    ops_.free(tmp);
+    tmp.reset();
     ops_.eig_rotation_done(eig_base_ + i);
     ms3_invalidate();  // (the multi-sweep intermediate may carry this mode's rank index in the old basis)
   }
@@ -566,7 +499,7 @@ void TuckerEngine::set_core(const double *core) {
   finalize_rotations();
   if (core) {
     core_owed_ = false;
-    ops_.h2d(core_, core, sizeof(double) * ncore_);
+    ops_.h2d(core_.as<double>(), core, sizeof(double) * ncore_);
   } else
     compute_core_full();
 }
@@ -580,7 +513,7 @@ void TuckerEngine::get_factors(double *Wflat, double *core) {
       w += n;
     }
   }
-  if (core) ops_.d2h(core, core_, sizeof(double) * ncore_);
+  if (core) ops_.d2h(core, core_.as<double>(), sizeof(double) * ncore_);
 }
 
 // The model through a view: f = the view's unit-stride mode (its smallest stride),
@@ -624,7 +557,7 @@ void TuckerEngine::impute(const ViewArgs &a, const void *mask, void *stream, dou
     // (a slab's sum stays in a device slot of its own until a batch of slots is read in one copy: the host
     // does not wait between slabs, and adds the sums in slab order)
     constexpr int kSlots = 48;
-    double *slot = scal_ + 8;
+    double *slot = scal_.as<double>() + 8;
     int used = 0;
     auto drain = [&] {
       double h[kSlots];
@@ -644,9 +577,9 @@ void TuckerEngine::impute(const ViewArgs &a, const void *mask, void *stream, dou
   }
   if (!observed_sq) return;
   if (dist_) {
-    ops_.h2d(scal_ + 8, &sq, sizeof(double));
-    comm_.allreduce_sum(scal_ + 8, 1);
-    ops_.d2h(&sq, scal_ + 8, sizeof(double));
+    ops_.h2d(scal_.as<double>() + 8, &sq, sizeof(double));
+    comm_.allreduce_sum(scal_.as<double>() + 8, 1);
+    ops_.d2h(&sq, scal_.as<double>() + 8, sizeof(double));
   }
   *observed_sq = sq;
 }
@@ -687,14 +620,10 @@ void TuckerEngine::model_slabs(const ModelBox &bx, int f, int s, const SlabRun &
   // W_m^T (r_m x s_m) of the chain's modes, at offsets in mode order (mode f's slot stays unused)
   int64_t nwt = 0;
   for (int m = 0; m < N_; m++) nwt += V_.glens[m] * r_[m];
-  if (nwt > xwt_cap_) {
-    ops_.free(xwt_);
-    xwt_ = (double *)ops_.alloc(sizeof(double) * nwt);
-    xwt_cap_ = nwt;
-  }
+  xwt_.reserve(ops_, sizeof(double) * nwt);
   int64_t off = 0;
   for (int m = 0; m < N_; off += V_.glens[m] * r_[m], m++)
-    if (m != f) ops_.transpose2d(W_[m], F64, V_.glens[m], r_[m], xwt_ + off);
+    if (m != f) ops_.transpose2d(W_[m], F64, V_.glens[m], r_[m], xwt_.as<double>() + off);
   // the largest intermediate of the chain per row of the slab mode, and the slab that fits
   constexpr int64_t budget = int64_t(1) << 25;  // doubles per buffer (256 MB)
   std::vector<int64_t> dims(r_.begin(), r_.end());
@@ -707,13 +636,8 @@ void TuckerEngine::model_slabs(const ModelBox &bx, int f, int s, const SlabRun &
   }
   const int64_t ns = s >= 0 ? bx.len[s] : 1;
   const int64_t cs = std::max<int64_t>(1, std::min(ns, budget / unit));
-  if (unit * cs > xz_cap_) {
-    ops_.free(xz_[0]);
-    ops_.free(xz_[1]);
-    xz_[0] = (double *)ops_.alloc(sizeof(double) * unit * cs);
-    xz_[1] = (double *)ops_.alloc(sizeof(double) * unit * cs);
-    xz_cap_ = unit * cs;
-  }
+  xz_[0].reserve(ops_, sizeof(double) * unit * cs);
+  xz_[1].reserve(ops_, sizeof(double) * unit * cs);
   for (int64_t c = 0; c < ns; c += cs) {
     ModelBox sb = bx;
     if (s >= 0) {
@@ -729,16 +653,16 @@ void TuckerEngine::model_slabs(const ModelBox &bx, int f, int s, const SlabRun &
 void TuckerEngine::export_slab(const ModelBox &bx, int f, const std::vector<int> &chain, const SlabRun &run) {
   std::vector<int64_t> dims(r_.begin(), r_.end()), wtoff(N_, 0);
   for (int m = 1; m < N_; m++) wtoff[m] = wtoff[m - 1] + V_.glens[m - 1] * r_[m - 1];
-  const double *cur = core_;
+  const double *cur = core_.as<double>();
   int pi = 0;
   for (int m : chain) {  // expansion of mode m: out[l, a, t] = sum_k cur[l, k, t] * W_m[lo_m + a, k]
     int64_t L = 1, T = 1;
     for (int q = 0; q < m; q++) L *= dims[q];
     for (int q = m + 1; q < N_; q++) T *= dims[q];
-    ops_.ttm_keep(cur, F64, L, r_[m], T, xwt_ + wtoff[m] + r_[m] * bx.lo[m], r_[m], (int)bx.len[m],
-                  xz_[pi]);
+    ops_.ttm_keep(cur, F64, L, r_[m], T, xwt_.as<double>() + wtoff[m] + r_[m] * bx.lo[m], r_[m], (int)bx.len[m],
+                  xz_[pi].as<double>());
     dims[m] = bx.len[m];
-    cur = xz_[pi];
+    cur = xz_[pi].as<double>();
     pi ^= 1;
   }
   // Z = cur: [modes before f | r_f | modes after f]; P[b, k] with b over the modes other than f
@@ -771,27 +695,26 @@ void TuckerEngine::hosvd() {
       const int64_t s0 = V_.glens[0], blk = block_rows(s0, P_);
       const size_t esz = dtype_size(V_.dtype);
       const int64_t chunk_bytes = ((blk * T * (int64_t)esz + 7) / 8) * 8;
-      char *stage = (char *)ops_.alloc((size_t)chunk_bytes * P_);
-      void *full = ops_.alloc((size_t)s0 * T * esz);
+      DeviceBuffer stage_buf(ops_, (size_t)chunk_bytes * P_), full_buf(ops_, (size_t)s0 * T * esz);
+      char *stage = stage_buf.as<char>();
+      void *full = full_buf.get();
       ops_.zero(stage, (size_t)chunk_bytes * P_);
       ops_.d2d(stage + (size_t)rank_ * chunk_bytes, V_.data, (size_t)V_.nloc * esz);
       comm_.allgather((const double *)(stage + (size_t)rank_ * chunk_bytes), (double *)stage,
                       chunk_bytes / 8);
       ops_.unpack_shards(stage, V_.dtype, s0, T, blk, P_, chunk_bytes, full);
-      ops_.unfold_gram(full, V_.dtype, 1, s0, T, G_);
+      ops_.unfold_gram(full, V_.dtype, 1, s0, T, G_.as<double>());
       ops_.sync();
-      ops_.free(stage);
-      ops_.free(full);
     } else {
-      ops_.unfold_gram(V_.data, V_.dtype, L, V_.glens[i], T, G_);
-      if (dist_) comm_.allreduce_sum(G_, V_.glens[i] * V_.glens[i]);
+      ops_.unfold_gram(V_.data, V_.dtype, L, V_.glens[i], T, G_.as<double>());
+      if (dist_) comm_.allreduce_sum(G_.as<double>(), V_.glens[i] * V_.glens[i]);
     }
     // (slots 8.. : a cold start of their own — the Gram of the full unfolding has little to do
     // with the one the first HOOI sweep will see in slot i)
-    ops_.top_eigvecs_warm(G_, V_.glens[i], r_[i], W_[i], eig_base_ + MAX_ORDER + i);
+    ops_.top_eigvecs_warm(G_.as<double>(), V_.glens[i], r_[i], W_[i], eig_base_ + MAX_ORDER + i);
   }
   compute_core_full();
-  ops_.d2d(core_prev_, core_, sizeof(double) * ncore_);
+  ops_.d2d(core_prev_.as<double>(), core_.as<double>(), sizeof(double) * ncore_);
   ops_.sync();
 }
 
@@ -807,26 +730,22 @@ void TuckerEngine::factor_update(int i, const double *Y, int64_t L, int64_t T) {
   const int64_t s = V_.glens[i], c = L * T;
   if (thin_enabled_ && c < s && r_[i] <= c) {
     const int64_t need = s * c + c * r_[i];
-    if (thin_cap_ < need) {
-      ops_.free(thin_);
-      thin_ = (double *)ops_.alloc(sizeof(double) * need);
-      thin_cap_ = need;
-    }
+    thin_.reserve(ops_, sizeof(double) * need);
     const double *Ym = Y;  // [s, c] with the mode fastest
     if (L > 1) {
-      ops_.transpose_batched(Y, F64, L, s, T, thin_);
-      Ym = thin_;
+      ops_.transpose_batched(Y, F64, L, s, T, thin_.as<double>());
+      Ym = thin_.as<double>();
     }
-    double *Vr = thin_ + s * c;
-    ops_.unfold_gram(Ym, F64, s, c, 1, G_);  // c x c (c < s: fits G_)
+    double *Vr = thin_.as<double>() + s * c;
+    ops_.unfold_gram(Ym, F64, s, c, 1, G_.as<double>());  // c x c (c < s: fits G_.as<double>())
     // (a slot of its own: the c x c problem and the s x s fallback below are different sequences)
-    ops_.top_eigvecs_warm(G_, c, r_[i], Vr, eig_base_ + 2 * MAX_ORDER + i);
+    ops_.top_eigvecs_warm(G_.as<double>(), c, r_[i], Vr, eig_base_ + 2 * MAX_ORDER + i);
     ops_.ttm_keep(Ym, F64, s, c, 1, Vr, c, r_[i], W_[i]);
     if (ops_.orthonormalize(W_[i], s, r_[i])) return;
   }
   // (a slot that defers its checks keeps the Gram itself: they are finished on a second stream)
   double *G = ops_.eig_gram(eig_base_ + i, s);
-  if (!G) G = G_;
+  if (!G) G = G_.as<double>();
   ops_.unfold_gram(Y, F64, L, s, T, G);
   ops_.top_eigvecs_warm(G, s, r_[i], W_[i], eig_base_ + i);
 }
@@ -835,7 +754,7 @@ void TuckerEngine::sweep_dt() { sweep_body(nullptr); }
 
 // one HOOI sweep; align_ref != nullptr: column signs aligned with that factor set after every
 // eigen-step (alsTucker_DT_sub, als_Tucker.cxx:632-643)
-void TuckerEngine::sweep_body(const std::vector<double *> *align_ref) {
+void TuckerEngine::sweep_body(const DeviceBufferTable *align_ref) {
   check_prep_epoch();
   const bool may_defer = defer_enabled_ && align_ref == nullptr && !dist_;
   if (!may_defer) settle_all();
@@ -846,7 +765,7 @@ void TuckerEngine::sweep_body(const std::vector<double *> *align_ref) {
   }
 }
 
-void TuckerEngine::mode_step(int i, const std::vector<double *> *align_ref, bool may_defer) {
+void TuckerEngine::mode_step(int i, const DeviceBufferTable *align_ref, bool may_defer) {
   int64_t L = 1, T = 1;
   double *Y = ms3_ ? ms3_leaf(i, &T) : nullptr;
   const bool from_ms3 = Y != nullptr;
@@ -860,14 +779,14 @@ void TuckerEngine::mode_step(int i, const std::vector<double *> *align_ref, bool
       T = L * T;
       L = 1;
     }
-    Y = complete_leaf(i, lf.buf, L * V_.glens[i] * T);
+    Y = complete_leaf(i, lf.buf.as<double>(), L * V_.glens[i] * T);
   }
   if (i == N_ - 1) {  // als_Tucker.cxx:395
     yend_T_ = T;
     // (one GPU: the leaf's own buffer stays as it is until this mode is stepped again — no copy)
     if (dist_) {
-      ops_.d2d(Yend_, Y, sizeof(double) * yend_elems_);
-      yend_src_ = Yend_;
+      ops_.d2d(Yend_.as<double>(), Y, sizeof(double) * yend_elems_);
+      yend_src_ = Yend_.as<double>();
     } else {
       // (a multi-sweep leaf with its rank indices in descending mode order: the core is recomputed from
       // the tensor when somebody asks for it)
@@ -878,9 +797,9 @@ void TuckerEngine::mode_step(int i, const std::vector<double *> *align_ref, bool
   ops_.eig_defer(eig_base_ + i, may_defer);
   if (may_defer) {
     // the step writes the new factor into the spare buffer; the one it replaces stays intact
-    if (Wsave_.empty()) Wsave_.assign(N_, nullptr);
-    if (!Wsave_[i]) Wsave_[i] = (double *)ops_.alloc(sizeof(double) * V_.glens[i] * r_[i]);
-    std::swap(W_[i], Wsave_[i]);
+    if (Wsave_.empty()) Wsave_.resize(N_);
+    if (!Wsave_[i]) Wsave_.alloc(ops_, i, sizeof(double) * V_.glens[i] * r_[i]);
+    W_.swap_entry(i, Wsave_);
   }
   factor_update(i, Y, L, T);  // K12
   ops_.eig_defer(eig_base_ + i, false);
@@ -930,7 +849,7 @@ void TuckerEngine::rollback_and_redo() {
   for (size_t k = 0; k < steps.size(); k++) {
     const int j = steps[k];
     if (k > 0) ops_.eig_verify(eig_base_ + j, true);
-    std::swap(W_[j], Wsave_[j]);
+    W_.swap_entry(j, Wsave_);
     ops_.eig_rotation_done(eig_base_ + j);  // (the rotation owed belonged to the discarded factor)
   }
   for (int j : steps) {
@@ -948,18 +867,18 @@ void TuckerEngine::rollback_and_redo() {
 bool TuckerEngine::agree(bool local) {
   if (!dist_) return local;
   double x = local ? 1.0 : 0.0, y = 0;
-  ops_.h2d(scal_ + 3, &x, sizeof(double));
-  comm_.allreduce_sum(scal_ + 3, 1);
-  ops_.d2h(&y, scal_ + 3, sizeof(double));
+  ops_.h2d(scal_.as<double>() + 3, &x, sizeof(double));
+  comm_.allreduce_sum(scal_.as<double>() + 3, 1);
+  ops_.d2h(&y, scal_.as<double>() + 3, sizeof(double));
   return y > 0.0;
 }
 
 double TuckerEngine::core_norm() {
   ensure_core();
-  ops_.sumsq(core_, ncore_, scal_);
-  ops_.sumsq(core_prev_, ncore_, scal_ + 1);
+  ops_.sumsq(core_.as<double>(), ncore_, scal_.as<double>());
+  ops_.sumsq(core_prev_.as<double>(), ncore_, scal_.as<double>() + 1);
   double h[2];
-  ops_.d2h(h, scal_, sizeof(double) * 2);
+  ops_.d2h(h, scal_.as<double>(), sizeof(double) * 2);
   return std::fabs(std::sqrt(h[0]) - std::sqrt(h[1]));
 }
 
@@ -969,8 +888,8 @@ double TuckerEngine::residual() {
   ensure_core();
   std::vector<int64_t> dims(N_);
   for (int m = 0; m < N_; m++) dims[m] = r_[m];
-  const double *cur = core_;
-  double *prev = nullptr;
+  const double *cur = core_.as<double>();
+  DeviceBuffer prev;
   for (int m = 0; m < N_ - 1; m++) {
     int64_t L = 1, T = 1;
     for (int q = 0; q < m; q++) L *= dims[q];
@@ -983,30 +902,28 @@ double TuckerEngine::residual() {
     ops_.d2h(Wh.data(), W_[m], sizeof(double) * sg * rk);
     for (int64_t a = 0; a < s; a++)  // local rows of the sharded mode only
       for (int k = 0; k < rk; k++) WT[k + (size_t)rk * a] = Wh[(a + r0) + sg * k];
-    double *WTd = (double *)ops_.alloc(sizeof(double) * s * rk);
-    ops_.h2d(WTd, WT.data(), sizeof(double) * s * rk);
-    double *dst = (double *)ops_.alloc(sizeof(double) * L * s * T);
-    ops_.ttm_keep(cur, F64, L, rk, T, WTd, rk, (int)s, dst);
-    ops_.free(WTd);
-    if (prev) ops_.free(prev);
-    prev = dst;
-    cur = dst;
+    DeviceBuffer WTd(ops_, sizeof(double) * s * rk);
+    ops_.h2d(WTd.as<double>(), WT.data(), sizeof(double) * s * rk);
+    DeviceBuffer dst(ops_, sizeof(double) * L * s * T);
+    ops_.ttm_keep(cur, F64, L, rk, T, WTd.as<double>(), rk, (int)s, dst.as<double>());
+    WTd.reset();
+    prev = std::move(dst);
+    cur = prev.as<double>();
     dims[m] = s;
   }
   int64_t M = 1;
   for (int m = 0; m < N_ - 1; m++) M *= ext(m);
-  ops_.residual_sq(V_.data, V_.dtype, M, V_.glens[N_ - 1], cur, W_[N_ - 1], r_[N_ - 1], scal_ + 2);
-  if (dist_) comm_.allreduce_sum(scal_ + 2, 1);
+  ops_.residual_sq(V_.data, V_.dtype, M, V_.glens[N_ - 1], cur, W_[N_ - 1], r_[N_ - 1], scal_.as<double>() + 2);
+  if (dist_) comm_.allreduce_sum(scal_.as<double>() + 2, 1);
   double h = 0;
-  ops_.d2h(&h, scal_ + 2, sizeof(double));
-  if (prev) ops_.free(prev);
+  ops_.d2h(&h, scal_.as<double>() + 2, sizeof(double));
   return std::sqrt(h);
 }
 
 int TuckerEngine::run_dt(const CpOpts &o, int *iters) {
   RunReport rep(o, rank_ == 0, V_.glens[0], "diffnorm");
   ensure_core();
-  ops_.d2d(core_prev_, core_, sizeof(double) * ncore_);  // Tensor<> core_prev(core)
+  ops_.d2d(core_prev_.as<double>(), core_.as<double>(), sizeof(double) * ncore_);  // Tensor<> core_prev(core)
   double diffnorm = 1000;
   int iter;
   for (iter = 0; iter <= o.maxiter; iter++) {
@@ -1050,7 +967,7 @@ const TuckerEngine::PPOp &TuckerEngine::pp_get(const std::string &args) {
   } else {
     const PPOp &par = pp_get(args.substr(0, args.size() - 1));
     op.dims = par.dims;
-    src = par.buf;
+    src = par.buf.as<double>();
     dt = F64;
   }
   int64_t L = 1, T = 1;
@@ -1059,32 +976,20 @@ const TuckerEngine::PPOp &TuckerEngine::pp_get(const std::string &args) {
   const int64_t J = op.dims[mode];
   op.dims[mode] = r_[mode];
   op.elems = L * r_[mode] * T;
-  op.buf = (double *)ops_.alloc(sizeof(double) * op.elems);
-  ops_.ttm_keep(src, dt, L, J, T, wptr(mode), V_.glens[mode], r_[mode], op.buf);
-  pp_[args] = op;
-  return pp_[args];
+  op.buf = DeviceBuffer(ops_, sizeof(double) * op.elems);
+  ops_.ttm_keep(src, dt, L, J, T, wptr(mode), V_.glens[mode], r_[mode], op.buf.as<double>());
+  return pp_[args] = std::move(op);
 }
-void TuckerEngine::pp_clear() {
-  for (auto &kv : pp_) ops_.free(kv.second.buf);
-  pp_.clear();
-}
+void TuckerEngine::pp_clear() { pp_.clear(); }
 
 // one approximate sweep (als_Tucker.cxx:824-891): Y_i = Y_i^0 + sum_{j != i} T_ij x_j dW_j
 void TuckerEngine::sweep_pp() {
   ms3_invalidate();  // (PP moves the factors without touching the multi-sweep intermediate)
   for (int i = 0; i < N_; i++) {
     const PPOp &Y0 = pp_get(tk_all_but(N_, i));
-    if (yacc_cap_ < Y0.elems) {
-      ops_.free(Yacc_);
-      Yacc_ = (double *)ops_.alloc(sizeof(double) * Y0.elems);
-      yacc_cap_ = Y0.elems;
-    }
-    if (ytmp_cap_ < Y0.elems) {
-      ops_.free(Ytmp_);
-      Ytmp_ = (double *)ops_.alloc(sizeof(double) * Y0.elems);
-      ytmp_cap_ = Y0.elems;
-    }
-    ops_.d2d(Yacc_, Y0.buf, sizeof(double) * Y0.elems);
+    Yacc_.reserve(ops_, sizeof(double) * Y0.elems);
+    Ytmp_.reserve(ops_, sizeof(double) * Y0.elems);
+    ops_.d2d(Yacc_.as<double>(), Y0.buf.as<double>(), sizeof(double) * Y0.elems);
     for (int ii = 0; ii < N_; ii++) {
       if (ii == i) continue;
       const PPOp &Tp = pp_get(tk_all_but(N_, std::min(i, ii), std::max(i, ii)));
@@ -1093,30 +998,26 @@ void TuckerEngine::sweep_pp() {
       for (int q = ii + 1; q < N_; q++) T *= Tp.dims[q];
       // sharded mode: the local rows of dW_0 (the operator keeps the local extent of mode 0)
       const double *dwp = dW_[ii] + (ii == 0 ? V_.row0 : 0);
-      ops_.ttm_keep(Tp.buf, F64, L, ext(ii), T, dwp, V_.glens[ii], r_[ii], Ytmp_);
-      ops_.add_inplace(Yacc_, Ytmp_, Y0.elems);
+      ops_.ttm_keep(Tp.buf.as<double>(), F64, L, ext(ii), T, dwp, V_.glens[ii], r_[ii], Ytmp_.as<double>());
+      ops_.add_inplace(Yacc_.as<double>(), Ytmp_.as<double>(), Y0.elems);
     }
     int64_t L = 1, T = 1;
     for (int q = 0; q < i; q++) L *= r_[q];
     for (int q = i + 1; q < N_; q++) T *= r_[q];
-    double *Y = Yacc_;
+    double *Y = Yacc_.as<double>();
     if (dist_) {
       // same completion as the exact sweep: partial sums are all-reduced, the rows of the sharded
       // mode gathered (from a copy padded to the uniform block height)
       if (i == 0) {
         const int64_t blk = block_rows(V_.glens[0], P_);
-        if (ytmp_cap_ < blk * T) {
-          ops_.free(Ytmp_);
-          Ytmp_ = (double *)ops_.alloc(sizeof(double) * blk * T);
-          ytmp_cap_ = blk * T;
-        }
-        ops_.pack_blocks(Yacc_, ext(0), ext(0), (int)T, blk, 1, Ytmp_);
-        Y = complete_leaf(0, Ytmp_, blk * T);
+        Ytmp_.reserve(ops_, sizeof(double) * blk * T);
+        ops_.pack_blocks(Yacc_.as<double>(), ext(0), ext(0), (int)T, blk, 1, Ytmp_.as<double>());
+        Y = complete_leaf(0, Ytmp_.as<double>(), blk * T);
       } else {
-        Y = complete_leaf(i, Yacc_, Y0.elems);
+        Y = complete_leaf(i, Yacc_.as<double>(), Y0.elems);
       }
     }
-    if (i == N_ - 1) ops_.d2d(Yend_, Y, sizeof(double) * yend_elems_);
+    if (i == N_ - 1) ops_.d2d(Yend_.as<double>(), Y, sizeof(double) * yend_elems_);
     // (the PP phase differences the eigenvectors one by one: never "any basis of the subspace",
     // whatever the slot's last exact sweep allowed — pp_bench enters here without a dt_sub)
     ops_.eig_lazy(eig_base_ + i, false);
@@ -1124,12 +1025,12 @@ void TuckerEngine::sweep_pp() {
     ops_.sign_align(W_[i], Winit_[i], V_.glens[i], r_[i]);  // als_Tucker.cxx:874-885
     double *A[1] = {W_[i]}, *B[1] = {Winit_[i]}, *D[1] = {dW_[i]};
     int64_t n[1] = {V_.glens[i] * r_[i]};
-    ops_.diff_norms(A, B, n, 1, 1, D, 0, scal_ + 4);  // dW = W - W_init (als_Tucker.cxx:887)
+    ops_.diff_norms(A, B, n, 1, 1, D, 0, scal_.as<double>() + 4);  // dW = W - W_init (als_Tucker.cxx:887)
   }
   int64_t L = ncore_ / r_[N_ - 1];
   core_owed_ = false;
-  ops_.ttm_keep(Yend_, F64, L, V_.glens[N_ - 1], 1, W_[N_ - 1], V_.glens[N_ - 1], r_[N_ - 1],
-                core_);
+  ops_.ttm_keep(Yend_.as<double>(), F64, L, V_.glens[N_ - 1], 1, W_[N_ - 1], V_.glens[N_ - 1], r_[N_ - 1],
+                core_.as<double>());
 }
 
 // print block (als_Tucker.cxx:288-338 / :521-564 / :764-822); bench: pp_bench's timings instead of
@@ -1153,7 +1054,7 @@ bool TuckerEngine::print_block(RunReport &rep, const CpOpts &o, int iter, int pp
   if (agree(diffnorm < o.tol || rep.elapsed() > o.timelimit ||
             (stop_at_maxiter && iter == o.maxiter)))
     return true;
-  ops_.d2d(core_prev_, core_, sizeof(double) * ncore_);
+  ops_.d2d(core_prev_.as<double>(), core_.as<double>(), sizeof(double) * ncore_);
   return false;
 }
 
@@ -1161,8 +1062,8 @@ ModeNorms TuckerEngine::read_norms(bool dt_phase) {
   int64_t n[MAX_ORDER];
   for (int i = 0; i < N_; i++) n[i] = V_.glens[i] * r_[i];
   ops_.diff_norms(W_.data(), dt_phase ? Wprev_.data() : nullptr, n, N_, dt_phase, dW_.data(),
-                  dt_phase, scal_ + 8);
-  return ModeNorms(ops_, scal_ + 8, N_);
+                  dt_phase, scal_.as<double>() + 8);
+  return ModeNorms(ops_, scal_.as<double>() + 8, N_);
 }
 
 // alsTucker_DT_sub (als_Tucker.cxx:476-669)
@@ -1212,17 +1113,20 @@ int TuckerEngine::run_pp(const CpOpts &o, int *iters) {
   finalize_rotations();  // the PP phases difference the eigenvectors themselves
   for (int i = 0; i < N_; i++) ops_.eig_lazy(eig_base_ + i, false);
   if (Wprev_.empty()) {
-    for (int i = 0; i < N_; i++) {
-      size_t n = sizeof(double) * V_.glens[i] * r_[i];
-      Wprev_.push_back((double *)ops_.alloc(n));
-      Winit_.push_back((double *)ops_.alloc(n));
-      dW_.push_back((double *)ops_.alloc(n));
-    }
+    Wprev_.resize(N_);
+    Winit_.resize(N_);
+    dW_.resize(N_);
+  }
+  for (int i = 0; i < N_; i++) {
+    size_t n = sizeof(double) * V_.glens[i] * r_[i];
+    if (!Wprev_[i]) Wprev_.alloc(ops_, i, n);
+    if (!Winit_[i]) Winit_.alloc(ops_, i, n);
+    if (!dW_[i]) dW_.alloc(ops_, i, n);
   }
   for (int i = 0; i < N_; i++) ops_.zero(dW_[i], sizeof(double) * V_.glens[i] * r_[i]);
   RunReport rep(o, rank_ == 0, V_.glens[0], "diffnorm");
   int iter = 0;
-  ops_.d2d(core_prev_, core_, sizeof(double) * ncore_);  // Tensor<> core_prev(core)
+  ops_.d2d(core_prev_.as<double>(), core_.as<double>(), sizeof(double) * ncore_);  // Tensor<> core_prev(core)
   double diffnorm = 10.;
   double tol_init = o.tol_init;
   while (diffnorm > o.tol && iter <= o.maxiter) {

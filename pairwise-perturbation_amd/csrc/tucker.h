@@ -40,8 +40,7 @@ class TuckerEngine {
  private:
   struct Node {
     int lo, hi, parent, slo, shi;
-    double *buf = nullptr;
-    int64_t cap = 0;
+    DeviceBuffer buf;  // (grow-only)
     bool valid = false;
     bool front = false;  // a leaf stored [s_mode | ranks of the other modes] instead of the tree's order
   };
@@ -72,8 +71,8 @@ class TuckerEngine {
   TensorDesc V_;
   int N_;
   std::vector<int> r_;
-  std::vector<double *> W_;
-  double *core_ = nullptr, *core_prev_ = nullptr, *Yend_ = nullptr, *G_ = nullptr, *scal_ = nullptr;
+  DeviceBufferTable W_;
+  DeviceBuffer core_, core_prev_, Yend_, G_, scal_;
   int64_t ncore_ = 1, yend_elems_ = 0;
   std::vector<Node> nodes_;
   std::vector<int> leaf_;
@@ -82,20 +81,19 @@ class TuckerEngine {
   bool dist_ = false;
   // pairwise perturbation (als_Tucker.cxx:426-962)
   struct PPOp {
-    double *buf = nullptr;
+    DeviceBuffer buf;
     int64_t elems = 0;
     std::vector<int64_t> dims;
   };
   std::map<std::string, PPOp> pp_;
-  std::vector<double *> Wprev_, Winit_, dW_;
-  double *Ytmp_ = nullptr, *Yacc_ = nullptr;
-  double *thin_ = nullptr;  // [s_i x (L*T) unfolding | (L*T) x r_i right vectors] of the thin route
-  int64_t thin_cap_ = 0;
+  DeviceBufferTable Wprev_, Winit_, dW_;
+  DeviceBuffer Ytmp_, Yacc_;  // (grow-only, as thin_, Yfull_, gather_, chain_, ms3_X_, ms3_Y_, xwt_ and xz_)
+  DeviceBuffer thin_;  // [s_i x (L*T) unfolding | (L*T) x r_i right vectors] of the thin route
   int eig_base_ = 0;  // block of warm-start slots drawn from the back end (Ops::eig_session_new)
   void finalize_rotations();
   void drop_rotations();
   bool thin_enabled_ = true;  // PPALS_TUCKER_THIN=0: always the s_i x s_i Gram (A/B, tests)
-  void *VT_ = nullptr;  // second resident layout [(right modes), (left modes)], nullptr: not held
+  DeviceBuffer VT_;  // second resident layout [(right modes), (left modes)], empty: not held
   // Order 3, one GPU: the multi-sweep dimension tree (as the CP engine's, cp_msdt_optimizer.cxx:172-207).
   // ONE first-level intermediate X_r = V x_r W_r serves the TWO mode updates that follow mode r's, then
   // the root moves on to the mode updated last: 3 tensor scans per 2 HOOI sweeps instead of 4, the same
@@ -106,13 +104,11 @@ class TuckerEngine {
   // 2 x the tensor + 2 GB free at creation); X_r is kept in the TENSOR's precision, so with fp32 storage
   // the two schedules agree to ~1e-7 (X_r rounded like the tensor), with fp64 storage to rounding.
   bool ms3_ = false;
-  void *VT2_ = nullptr;
-  void *ms3_X_ = nullptr;
-  size_t ms3_cap_ = 0;
+  DeviceBuffer VT2_;
+  DeviceBuffer ms3_X_;
   int ms3_root_ = -1, ms3_left_ = 0;
   bool ms3_perm_ = false;  // the leaf just served has its two rank indices in descending mode order
-  double *ms3_Y_[3] = {nullptr, nullptr, nullptr};
-  int64_t ms3_Ycap_[3] = {0, 0, 0};
+  DeviceBuffer ms3_Y_[3];
   double *ms3_leaf(int i, int64_t *T);
   void ms3_invalidate() {
     ms3_root_ = -1;
@@ -127,14 +123,12 @@ class TuckerEngine {
   uint64_t prep_epoch_ = 0;
   bool ms3_created_ = false;
   void check_prep_epoch();
-  void *chain_[2] = {nullptr, nullptr};  // ping-pong scratch of the mode-product chains
-  size_t chain_cap_[2] = {0, 0};
-  int64_t ytmp_cap_ = 0, yacc_cap_ = 0;
+  DeviceBuffer chain_[2];  // ping-pong scratch of the mode-product chains
   const PPOp &pp_get(const std::string &args);
   void pp_clear();
-  void sweep_body(const std::vector<double *> *align_ref);
+  void sweep_body(const DeviceBufferTable *align_ref);
   // one mode of a HOOI sweep: leaf tensor, eigen-step, (last mode) the core
-  void mode_step(int i, const std::vector<double *> *align_ref, bool may_defer);
+  void mode_step(int i, const DeviceBufferTable *align_ref, bool may_defer);
   // Deferred acceptance of eigen-steps (Ops::eig_defer / eig_verify): inside plain sweeps the host
   // does not wait for a step's checks — it enqueues ahead of the device — and asks for them when it
   // comes back to the mode (or before anything is published: print blocks, get_factors, the PP
@@ -142,7 +136,7 @@ class TuckerEngine {
   // the factor the latest step of mode m replaced. A step that was NOT accepted: every factor
   // stepped since goes back to what it was and those steps are repeated, checked one by one.
   std::vector<int> defer_log_;
-  std::vector<double *> Wsave_;
+  DeviceBufferTable Wsave_;
   bool defer_enabled_ = true;  // (the back end decides per slot: PPALS_EIG_DEFER=0 switches every deferral off)
   int defer_rollbacks_ = 0;
   void settle_mode(int i);  // before mode i is stepped again
@@ -160,11 +154,9 @@ class TuckerEngine {
   void model_slabs(const ModelBox &bx, int f, int s, const SlabRun &run);
   void export_slab(const ModelBox &bx, int f, const std::vector<int> &chain, const SlabRun &run);
   // (kept for the session's next export: freeing them would wait for the device)
-  double *xwt_ = nullptr, *xz_[2] = {nullptr, nullptr};
+  DeviceBuffer xwt_, xz_[2];
   int residual_form_ = RESIDUAL_FUSED;  // PPALS_MODEL_RESIDUAL
-  int64_t xwt_cap_ = 0, xz_cap_ = 0;
-  double *Yfull_ = nullptr, *gather_ = nullptr;
-  int64_t yfull_cap_ = 0, gather_cap_ = 0;
+  DeviceBuffer Yfull_, gather_;
 };
 
 }  // namespace ppals

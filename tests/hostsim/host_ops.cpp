@@ -81,13 +81,22 @@ void jacobi_eig(int n, std::vector<double> &A, std::vector<double> &w, std::vect
   for (int i = 0; i < n; i++) w[i] = A[i + (size_t)n * i];
 }
 
+// Allocation-failure injection (tests/hostsim/lifetime_main.cpp): armed at k > 0, the k-th allocation from now fails —
+// alloc throws, try_alloc returns nullptr — once; then it is disarmed again. 0: disarmed, nothing changes.
+long g_fail_alloc_countdown = 0;
+bool fail_this_alloc() { return g_fail_alloc_countdown > 0 && --g_fail_alloc_countdown == 0; }
+
 class HostOps : public Ops {
  public:
   HostOps() {
     if (const char *e = std::getenv("PPALS_HOSTSIM_DEFER")) sim_defer_ = std::atoi(e);
     if (const char *e = std::getenv("PPALS_HOSTSIM_DEFER_FAIL")) sim_fail_every_ = std::atoi(e);
   }
-  void *alloc(size_t bytes) override { return std::calloc(1, bytes ? bytes : 8); }
+  void *alloc(size_t bytes) override {
+    if (fail_this_alloc()) throw std::runtime_error("hostsim: injected allocation failure");
+    return std::calloc(1, bytes ? bytes : 8);
+  }
+  void *try_alloc(size_t bytes) override { return fail_this_alloc() ? nullptr : std::calloc(1, bytes ? bytes : 8); }
   void free(void *p) override { std::free(p); }
   void h2d(void *d, const void *s, size_t n) override { std::memcpy(d, s, n); }
   void d2h(void *d, const void *s, size_t n) override { std::memcpy(d, s, n); }
@@ -574,3 +583,9 @@ Comm *backend_make_comm(Ops *, int rank, int nranks, const void *uid128) {
 }
 
 }  // namespace ppals
+
+// the injection's two hooks (not part of the C ABI: no ppals_ prefix)
+extern "C" {
+void hostsim_fail_alloc_after(long k) { ppals::g_fail_alloc_countdown = k > 0 ? k : 0; }
+long hostsim_fail_alloc_countdown(void) { return ppals::g_fail_alloc_countdown; }  // > 0: armed and not fired yet
+}
