@@ -954,6 +954,56 @@ int ppals_npls_predict(const ppals_npls *m, ppals_tensor *Xnew, int ncomp, doubl
  * (W: L T C, S: I x C). Column c has the bits of that column computed alone. Refusals as above (C < 1 too). */
 int ppals_tensor_contract_mode(ppals_tensor *t, int mode, const double *U, int C, double *Z);
 int ppals_tensor_slice_inner(ppals_tensor *t, int mode, const double *W, int C, double *S);
+/* The same two passes for U or W of many columns: arguments, host pointers, layouts and refusals are those of the
+ * two calls above, the message starts with the new name. The columns travel together, up to 64 a read of the
+ * tensor, and products and sums run on the fp64 matrix cores wherever that was measured not to lose to the two
+ * passes above (L == 1 with I >= 32 and more than 4 columns; L >= 16 with more than 32 columns for the contraction,
+ * more than 8 for the slice inner product); otherwise the call goes through those. Results are DETERMINISTIC (two calls
+ * give the same bits, every sum runs in an order fixed by the storage type, L, I, T and the number of columns, no
+ * atomics) and WITHIN THE SAME ERROR BOUNDS as the narrow calls, but they are NOT BIT-EQUAL to them, and a column
+ * need not have the bits of that column computed alone. */
+int ppals_tensor_contract_columns(ppals_tensor *t, int mode, const double *U, int C, double *Z);
+int ppals_tensor_slice_inner_columns(ppals_tensor *t, int mode, const double *W, int C, double *S);
+
+/* ---- N-PLS cross-validation (leave-segments-out; `ncrossreg` of the N-way toolbox) ----
+ * segment[i] in [0, S) names the segment of sample i. For every segment s the model is fitted on all samples
+ * OUTSIDE s, with exactly the conventions of the fit above (the start of q, the rank-one rule and its start, the
+ * signs, the triangular inner relation, the stops, the status bits), and predicts the samples of s:
+ *   Ycv[i, :, f]   (I x M x F, column-major) the prediction of sample i from the first f + 1 components of the fit
+ *                  without segment[i];
+ *   press[f, m]    (F x M, column-major, may be NULL) = sum_i (Ycv[i, m, f] - Y[i, m])^2;
+ *   fitted[s]      (S, may be NULL) the components the fit without s reached; a fit that ends early (zero or
+ *                  non-finite Z) repeats its last prediction in its later columns of Ycv, and with no component
+ *                  they hold the training mean of Y (0 if center == 0);
+ *   status[s, f]   (S x F, column-major, may be NULL) the status bits of component f of the fit without s, 0 where
+ *                  none was fitted;
+ *   x_passes       (may be NULL) the shared passes over X: 2 F ceil(S / G) when no fit ends early (a pass of up
+ *                  to 64 columns is one read of X on the wide routes; where the rule of the _columns calls sends
+ *                  it through the narrow passes it reads X once per 4 columns).
+ * center == 1: every fit centres X across the sample mode and Y on ITS OWN training samples, and the training mean
+ * of Y is added back to the predictions; the caller passes the tensor as it is (one already centred by the centring
+ * call gives the same result up to rounding). center == 0: nothing is centred.
+ *
+ * The tensor is NEVER WRITTEN OR COPIED, no reduced or re-centred tensor is formed, no generation moves and live
+ * sessions are undisturbed: a fit leaves a segment out by zeroing its rows in the columns of Y_res that are
+ * contracted with X; the columns of Y_res sum to zero over the training samples, so the contraction with the
+ * centred tensor is the contraction with X; the centred scores are the raw scores less their training mean; and the
+ * raw scores of the held-out samples come out of the same pass as the training scores. The fits run in groups of G
+ * that share every pass, G the largest count with G M <= 64 columns and G (M + 2) fp64 slices within 2 GiB: one
+ * contraction of G M columns and one slice inner product of G columns per component, through the passes of
+ * the two _columns calls above; the rest is small work per fit and host arithmetic. Deterministic: the same
+ * state gives the same bits.
+ *
+ * Refusals come before anything is launched or allocated, the message starts with "ppals_npls_crossval: ":
+ * PPALS_ERR_ARG for NULL or dead handles, NULL Y, segment or Ycv, `mode` outside [0, N), M < 1, F < 1, S < 2 or
+ * S > I, a label outside [0, S) or an empty segment, F larger than (the smallest training set) - center, center
+ * other than 0 or 1, a non-finite Y, bad options (as the fit defines them); PPALS_ERR_UNSUPPORTED for a context of
+ * more than one rank. */
+int ppals_npls_crossval(ppals_tensor *X, int mode, const double *Y, int M, int F,
+                        const int32_t *segment /* I entries in [0, S) */, int S, int center /* 0 or 1 */,
+                        const ppals_npls_opts *opts /* or NULL */, double *Ycv /* I x M x F, column-major */,
+                        double *press /* F x M, may be NULL */, int *fitted /* S, may be NULL */,
+                        int *status /* S x F, may be NULL */, int64_t *x_passes /* may be NULL */);
 
 /* ---- Tucker with missing entries (TensorLy's tucker(mask=...)): imputation and an EM driver ----
  * The contracts of ppals_cp_impute_device / ppals_cp_em with a Tucker session in the CP session's place:

@@ -616,6 +616,247 @@ void npls_predict(Ops &ops, const NplsModel &m, const TensorDesc &Xnew, int ncom
     }
 }
 
+void tensor_contract_columns(Ops &ops, const TensorDesc &V, int mode, const double *U_host, int C, double *Z_host) {
+  const PrepShape s = prep_shape(V, mode);
+  DeviceBuffer U = doubles(ops, s.J * C), Z = doubles(ops, s.L * s.T * C);
+  ops.h2d(U.as<double>(), U_host, sizeof(double) * (size_t)(s.J * C));
+  ops.npls_contract_wide(V.data, V.dtype, s.L, s.J, s.T, U.as<double>(), C, Z.as<double>());
+  ops.d2h(Z_host, Z.as<double>(), sizeof(double) * (size_t)(s.L * s.T * C));
+}
+void tensor_slice_inner_columns(Ops &ops, const TensorDesc &V, int mode, const double *W_host, int C, double *S_host) {
+  const PrepShape s = prep_shape(V, mode);
+  DeviceBuffer W = doubles(ops, s.L * s.T * C), S = doubles(ops, s.J * C);
+  ops.h2d(W.as<double>(), W_host, sizeof(double) * (size_t)(s.L * s.T * C));
+  ops.npls_slice_inner_wide(V.data, V.dtype, s.L, s.J, s.T, W.as<double>(), C, S.as<double>());
+  ops.d2h(S_host, S.as<double>(), sizeof(double) * (size_t)(s.J * C));
+}
+
+int npls_crossval_group(int64_t LT, int M, int S) {
+  int64_t G = std::max<int64_t>(1, kNplsCvColumns / M);
+  G = std::min(G, std::max<int64_t>(1, kNplsCvBytes / ((int64_t)sizeof(double) * LT * (M + 2))));
+  return (int)std::min<int64_t>(G, S);
+}
+
+namespace {
+// one resampled fit of a cross-validation: everything on the host, the rows of its own segment zero in Yres and
+// Ttr, so that every sum over the I samples is a sum over the training samples
+struct NplsCvFit {
+  int seg = 0, nf = 0;
+  bool live = true;
+  int64_t ntrain = 0;
+  std::vector<char> held;                     // I: 1 for the samples of the segment
+  std::vector<double> ymean, Yc, Yres;        // M; I x M, centred on the training samples, held-out rows zero (twice)
+  std::vector<double> Tall, Ttr, Uy, Q, B, wall, q, pred;  // Tall: the scores of all I samples; pred: I x M so far
+};
+// steps 2-4 of npls_fit for one fit: q, Z = sum_m q_m Z_m, its rank-one weights (w on the host, wdev on the device,
+// W = their outer product in dW), iterated over q. false: Z is zero or not finite.
+bool npls_cv_weights(Ops &ops, const NplsDims &d, int M, int64_t I, const NplsOpts &o, const std::vector<double> &Yres,
+                     double *dZm, double *dZ, double *dW, double *dq, double *dS, double *dE, double *w, double *wdev,
+                     std::vector<double> &q, int *status_out) {
+  const int64_t LT = d.LT;
+  int best = 0;
+  double bestss = -1;
+  for (int c = 0; c < M; c++) {
+    const double ss = dotn(&Yres[(size_t)I * c], &Yres[(size_t)I * c], I);
+    if (ss > bestss) {
+      bestss = ss;
+      best = c;
+    }
+  }
+  std::fill(q.begin(), q.end(), 0.0);
+  q[(size_t)best] = 1.0;
+  std::vector<double> qn((size_t)M);
+  int status = 0;
+  for (int round = 0;; round++) {
+    const double *Zp = dZm;
+    if (M > 1) {
+      ops.h2d(dq, q.data(), sizeof(double) * (size_t)M);
+      ops.npls_contract(dZm, F64, LT, M, 1, dq, 1, dZ);
+      Zp = dZ;
+    }
+    bool capped = false;
+    if (!npls_rank_one(ops, d, Zp, o, w, wdev, dW, dS, dE, &capped)) return false;
+    status = (status & ~1) | (capped ? 1 : 0);
+    npls_outer(ops, d, wdev, -1, dW);
+    ops.npls_slice_inner(dZm, F64, LT, M, 1, dW, 1, dS);
+    ops.d2h(qn.data(), dS, sizeof(double) * (size_t)M);
+    if (!normalise(qn.data(), M)) return false;
+    double moved = 0;
+    for (int c = 0; c < M; c++) moved = std::max(moved, std::fabs(qn[(size_t)c] - q[(size_t)c]));
+    q = qn;
+    if (M == 1 || moved <= o.inner_tol) break;
+    if (round + 1 >= o.inner_max) {
+      status |= 2;
+      break;
+    }
+  }
+  *status_out = status;
+  return true;
+}
+}  // namespace
+
+void npls_crossval(Ops &ops, const TensorDesc &X, int mode, const double *Y, int M, int F, const int32_t *segment, int S,
+                   int center, const NplsOpts &o, double *Ycv, double *press, int *fitted, int *status,
+                   int64_t *x_passes) {
+  const PrepShape s = prep_shape(X, mode);
+  const int64_t I = s.J;
+  const NplsDims d(X.order, X.llens, mode);
+  const int64_t LT = d.LT;
+  const int G = npls_crossval_group(LT, M, S);
+  int64_t passes = 0;
+  if (status) std::fill(status, status + (size_t)S * F, 0);
+  DeviceBuffer dY = doubles(ops, I * M * G), dZm = doubles(ops, LT * M * G), dW = doubles(ops, LT * G), dZ = doubles(ops, LT);
+  DeviceBuffer dwall = doubles(ops, d.sum * F * G), dE = doubles(ops, d.sum), dq = doubles(ops, M);
+  DeviceBuffer dS = doubles(ops, std::max<int64_t>(std::max<int64_t>(I * G, M), std::max<int64_t>(d.sum, 2)));
+  std::vector<double> Yh((size_t)I * M * G), Sh((size_t)I * G);
+  for (int s0 = 0; s0 < S; s0 += G) {
+    const int ng = std::min(G, S - s0);
+    std::vector<NplsCvFit> fits((size_t)ng);
+    for (int j = 0; j < ng; j++) {
+      NplsCvFit &ft = fits[(size_t)j];
+      ft.seg = s0 + j;
+      ft.held.assign((size_t)I, 0);
+      for (int64_t i = 0; i < I; i++) ft.held[(size_t)i] = segment[i] == ft.seg;
+      for (int64_t i = 0; i < I; i++) ft.ntrain += !ft.held[(size_t)i];
+      ft.ymean.assign((size_t)M, 0.0);
+      ft.Yc.assign((size_t)I * M, 0.0);
+      for (int c = 0; c < M; c++) {
+        double sum = 0;
+        if (center) {
+          for (int64_t i = 0; i < I; i++)
+            if (!ft.held[(size_t)i]) sum += Y[i + I * c];
+          ft.ymean[(size_t)c] = sum / (double)ft.ntrain;
+        }
+        for (int64_t i = 0; i < I; i++)
+          if (!ft.held[(size_t)i]) ft.Yc[(size_t)(i + I * c)] = Y[i + I * c] - ft.ymean[(size_t)c];
+      }
+      ft.Yres = ft.Yc;
+      ft.Tall.assign((size_t)I * F, 0.0);
+      ft.Ttr.assign((size_t)I * F, 0.0);
+      ft.Uy.assign((size_t)I * F, 0.0);
+      ft.Q.assign((size_t)M * F, 0.0);
+      ft.B.assign((size_t)F * F, 0.0);
+      ft.wall.assign((size_t)d.sum * F, 0.0);
+      ft.q.assign((size_t)M, 0.0);
+      ft.pred.assign((size_t)I * M, 0.0);
+      for (int c = 0; c < M; c++)
+        for (int64_t i = 0; i < I; i++) ft.pred[(size_t)(i + I * c)] = ft.ymean[(size_t)c];
+    }
+    for (int f = 0; f < F; f++) {
+      bool any = false;
+      for (const NplsCvFit &ft : fits) any = any || ft.live;
+      if (any) {
+        // 1. the Z_m of every live fit in one pass: the columns of an ended fit are zero
+        for (int j = 0; j < ng; j++) {
+          const NplsCvFit &ft = fits[(size_t)j];
+          if (ft.live)
+            std::copy(ft.Yres.begin(), ft.Yres.end(), Yh.begin() + (size_t)I * M * j);
+          else
+            std::fill(Yh.begin() + (size_t)I * M * j, Yh.begin() + (size_t)I * M * (j + 1), 0.0);
+        }
+        ops.h2d(dY.as<double>(), Yh.data(), sizeof(double) * (size_t)I * M * ng);
+        ops.npls_contract_wide(X.data, X.dtype, s.L, I, s.T, dY.as<double>(), ng * M, dZm.as<double>());
+        passes += (ng * M + kNplsCvColumns - 1) / kNplsCvColumns;
+        // 2. per fit: the corrections for the components so far, q and the rank-one weights
+        for (int j = 0; j < ng; j++) {
+          NplsCvFit &ft = fits[(size_t)j];
+          double *Wj = dW.as<double>() + LT * j;
+          if (ft.live) {
+            double *Zmj = dZm.as<double>() + LT * M * j, *wallj = dwall.as<double>() + d.sum * F * j;
+            for (int g = 0; g < f; g++)
+              for (int c = 0; c < M; c++) {
+                const double coef = dotn(&ft.Ttr[(size_t)I * g], &ft.Yres[(size_t)I * c], I);
+                const double *w[MAX_ORDER];
+                for (int k = 0; k < d.K; k++) w[k] = wallj + g * d.sum + d.off[k];
+                if (coef != 0) ops.npls_outer_axpy(Zmj + LT * c, d.ext, d.K, w, -coef);
+              }
+            int st = 0;
+            ft.live = npls_cv_weights(ops, d, M, I, o, ft.Yres, Zmj, dZ.as<double>(), Wj, dq.as<double>(), dS.as<double>(),
+                                      dE.as<double>(), &ft.wall[(size_t)d.sum * f], wallj + d.sum * f, ft.q, &st);
+            if (ft.live && status) status[ft.seg + (size_t)S * f] = st;
+          }
+          if (!ft.live) ops.zero(Wj, sizeof(double) * (size_t)LT);
+        }
+        // 3. the raw scores of all I samples for every fit in one pass
+        ops.npls_slice_inner_wide(X.data, X.dtype, s.L, I, s.T, dW.as<double>(), ng, dS.as<double>());
+        passes += (ng + kNplsCvColumns - 1) / kNplsCvColumns;
+        ops.d2h(Sh.data(), dS.as<double>(), sizeof(double) * (size_t)I * ng);
+      }
+      // 4. on the host: centred scores, the inner relation over the training samples, the held-out predictions
+      for (int j = 0; j < ng; j++) {
+        NplsCvFit &ft = fits[(size_t)j];
+        if (ft.live) {
+          const double *raw = &Sh[(size_t)I * j];
+          double mean = 0;
+          if (center) {
+            for (int64_t i = 0; i < I; i++)
+              if (!ft.held[(size_t)i]) mean += raw[i];
+            mean /= (double)ft.ntrain;
+          }
+          double *t = &ft.Tall[(size_t)I * f];
+          for (int64_t i = 0; i < I; i++) t[i] = raw[i] - mean;
+          for (int g = 0; g < f; g++) {
+            const double ww = npls_ww(d, ft.wall.data(), g, f);
+            for (int64_t i = 0; i < I; i++) t[i] -= ft.Tall[(size_t)(i + I * g)] * ww;
+          }
+          for (int64_t i = 0; i < I; i++) ft.Ttr[(size_t)(i + I * f)] = ft.held[(size_t)i] ? 0.0 : t[i];
+          for (int c = 0; c < M; c++) ft.Q[(size_t)(c + M * f)] = ft.q[(size_t)c];
+          for (int64_t i = 0; i < I; i++) {
+            double u = 0;
+            for (int c = 0; c < M; c++) u += ft.Yres[(size_t)(i + I * c)] * ft.q[(size_t)c];
+            ft.Uy[(size_t)(i + I * f)] = u;
+          }
+          const int n = f + 1;
+          std::vector<double> Gm((size_t)n * n), b((size_t)n);
+          for (int g = 0; g < n; g++) {
+            for (int h = 0; h < n; h++) Gm[g + (size_t)n * h] = dotn(&ft.Ttr[(size_t)I * g], &ft.Ttr[(size_t)I * h], I);
+            b[(size_t)g] = dotn(&ft.Ttr[(size_t)I * g], &ft.Uy[(size_t)I * f], I);
+          }
+          solve_small(Gm, b, n);
+          for (int g = 0; g < n; g++) ft.B[g + (size_t)F * f] = b[(size_t)g];
+          ft.Yres = ft.Yc;
+          for (int h = 0; h < n; h++)
+            for (int g = 0; g <= h; g++) {
+              const double bgh = ft.B[g + (size_t)F * h];
+              if (bgh == 0) continue;
+              for (int c = 0; c < M; c++) {
+                const double bq = bgh * ft.Q[(size_t)(c + M * h)];
+                for (int64_t i = 0; i < I; i++) ft.Yres[(size_t)(i + I * c)] -= ft.Ttr[(size_t)(i + I * g)] * bq;
+              }
+            }
+          for (int g = 0; g < n; g++) {
+            const double bgf = ft.B[g + (size_t)F * f];
+            if (bgf == 0) continue;
+            for (int c = 0; c < M; c++) {
+              const double bq = bgf * ft.Q[(size_t)(c + M * f)];
+              for (int64_t i = 0; i < I; i++)
+                if (ft.held[(size_t)i]) ft.pred[(size_t)(i + I * c)] += ft.Tall[(size_t)(i + I * g)] * bq;
+            }
+          }
+          ft.nf = f + 1;
+        }
+        // (an ended fit repeats its last prediction)
+        for (int c = 0; c < M; c++)
+          for (int64_t i = 0; i < I; i++)
+            if (ft.held[(size_t)i]) Ycv[i + I * (c + (int64_t)M * f)] = ft.pred[(size_t)(i + I * c)];
+      }
+    }
+    if (fitted)
+      for (const NplsCvFit &ft : fits) fitted[ft.seg] = ft.nf;
+  }
+  if (press)
+    for (int f = 0; f < F; f++)
+      for (int c = 0; c < M; c++) {
+        double p = 0;
+        for (int64_t i = 0; i < I; i++) {
+          const double e = Ycv[i + I * (c + (int64_t)M * f)] - Y[i + I * c];
+          p += e * e;
+        }
+        press[f + (size_t)F * c] = p;
+      }
+  if (x_passes) *x_passes = passes;
+}
+
 // ============================================================================ CpEngine
 // total columns of a session: nstarts * R, or the sum of the starts' own ranks
 static int total_columns(int R, int nstarts, const int *ranks) {

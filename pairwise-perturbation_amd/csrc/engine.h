@@ -130,6 +130,20 @@ void npls_fit(Ops &ops, const TensorDesc &X, int mode, const double *Y, int M, i
               NplsModel *out);
 // Yhat: Inew x M from the first ncomp components; Tnew: Inew x ncomp (may be nullptr)
 void npls_predict(Ops &ops, const NplsModel &m, const TensorDesc &Xnew, int ncomp, double *Yhat, double *Tnew);
+// The two passes through Ops::npls_contract_wide / npls_slice_inner_wide (ppals_tensor_contract_columns /
+// _slice_inner_columns): the layouts of the calls above, deterministic, not bit-equal to them.
+void tensor_contract_columns(Ops &ops, const TensorDesc &V, int mode, const double *U_host, int C, double *Z_host);
+void tensor_slice_inner_columns(Ops &ops, const TensorDesc &V, int mode, const double *W_host, int C, double *S_host);
+// Leave-segments-out cross-validation of N-PLS (ppals_npls_crossval; DESIGN.md §3, "Cross-validation"): the S
+// resampled fits run in groups of G that share every pass over X. G is the largest count with G M <= kNplsCvColumns
+// columns (what one read of X carries in the wide ops) and a working set of G (M + 2) fp64 slices within kNplsCvBytes.
+constexpr int kNplsCvColumns = 64;
+constexpr int64_t kNplsCvBytes = (int64_t)2 << 30;
+int npls_crossval_group(int64_t LT, int M, int S);
+// segment: I labels in [0, S); Ycv: I x M x F; press: F x M, fitted: S, status: S x F, x_passes (each may be nullptr)
+void npls_crossval(Ops &ops, const TensorDesc &X, int mode, const double *Y, int M, int F, const int32_t *segment, int S,
+                   int center, const NplsOpts &o, double *Ycv, double *press, int *fitted, int *status,
+                   int64_t *x_passes);
 
 struct CpOpts {
   double tol = 0, timelimit = 5e3;

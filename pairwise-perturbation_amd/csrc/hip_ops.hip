@@ -35,6 +35,7 @@
 #include "kernels_bf16.hip.h"
 #include "kernels_prep.hip.h"
 #include "kernels_npls.hip.h"
+#include "kernels_npls_wide.hip.h"
 
 namespace ppals {
 #define HIP_CHECK(expr)                                                                       \
@@ -1149,6 +1150,123 @@ class HipOps : public Ops {
       npls_si_typed((const bf16s *)X, L, I, T, W, C, S);
     else
       npls_si_typed((const double *)X, L, I, T, W, C, S);
+    prof_end();
+  }
+
+  // ------------------------------------------------------------------ N-PLS, wide columns (kernels_npls_wide.hip.h)
+  // The route rule, a plain formula on (L, I, T, C) ("Cross-validation"), the thresholds from
+  // profiles/npls_cv_bench.md (a wide route is taken only where it did not lose to the narrow chunks):
+  //   L == 1:      `wide.lead` for C > NPLS_CW and I >= 32 (below that a chunk of the contraction, or half a tile of
+  //                output rows, is mostly padding: I = 3 lost), both ops;
+  //   L >= 16:     `wide.rows` for C > 32 (contract: the narrow rows walk holds 0.67 of the HBM peak with four columns
+  //                and wins up to C = 16) and for C > 8 (slice_inner);
+  //   otherwise:   `narrow`, the ops above in their chunks of NPLS_CW.
+  // A launch carries up to 64 columns in nt tiles of 16, C > 64 goes in chunks of 64. Where the output tiles alone
+  // leave the device short of work the contracted index is split over grid.y into ns pieces (4 chunks of 32 each at
+  // least, the partial sums of a launch within 64 MB) and k_npls_fold adds the pieces in split order.
+  static bool npls_wide_geometry(bool contract, int64_t L, int64_t I, int C) {
+    if (L == 1) return C > NPLS_CW && I >= 32;
+    return L >= 16 && C > (contract ? 32 : 8);
+  }
+  int64_t npls_wide_ns(int64_t blocks, int64_t units, int64_t rows, int nc) {
+    int64_t ns = std::max<int64_t>(1, (4 * (int64_t)ncu_ + blocks - 1) / blocks);
+    ns = std::min(ns, std::max<int64_t>(1, units / 4));
+    ns = std::min(ns, std::max<int64_t>(1, ((int64_t)64 << 20) / (8 * rows * nc)));
+    return std::min<int64_t>(ns, 65535);
+  }
+  template <typename TX>
+  void npls_wide_rows_launch(int nt, dim3 grid, const TX *X, int64_t s1, int64_t s2, int64_t n, int64_t K, const double *B,
+                             int nc, int64_t tiles, double *out, int64_t cstride, int64_t sstride) {
+    auto k = nt == 1 ? k_npls_wide_rows<TX, 1> : nt == 2 ? k_npls_wide_rows<TX, 2> : nt == 3 ? k_npls_wide_rows<TX, 3>
+                                                                                              : k_npls_wide_rows<TX, 4>;
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, st_, X, s1, s2, n, K, B, nc, tiles, out, cstride, sstride);
+  }
+  template <typename TX>
+  void npls_wide_cols_launch(int nt, dim3 grid, const TX *X, int64_t s1, int64_t s2, int64_t n, int64_t K, int64_t slabs,
+                             const double *B, int nc, double *out, int64_t cstride, int64_t sstride) {
+    auto k = nt == 1 ? k_npls_wide_cols<TX, 1> : nt == 2 ? k_npls_wide_cols<TX, 2> : nt == 3 ? k_npls_wide_cols<TX, 3>
+                                                                                              : k_npls_wide_cols<TX, 4>;
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, st_, X, s1, s2, n, K, slabs, B, nc, out, cstride, sstride);
+  }
+  template <typename TX>
+  void npls_contract_wide_typed(const TX *X, int64_t L, int64_t I, int64_t T, const double *U, int C, double *Z) {
+    const int64_t LT = L * T;
+    for (int c0 = 0; c0 < C; c0 += NPLS_WIDE_COLS) {
+      const int nc = std::min(NPLS_WIDE_COLS, C - c0), nt = (nc + 15) / 16;
+      const double *Uc = U + I * c0;
+      double *Zc = Z + LT * c0;
+      if (L > 1) {
+        const int64_t tiles = (L + NPLS_WT - 1) / NPLS_WT;
+        if (tiles * T > 0x7fffffff) throw Unsupported("ppals: the wide contraction supports at most 2^31 - 1 row tiles");
+        route("npls.contract.%s.wide.rows nt=%d", sname<TX>(), nt);
+        npls_wide_rows_launch<TX>(nt, dim3((unsigned)(tiles * T)), X, L, L * I, L, I, Uc, nc, tiles, Zc, LT, 0);
+      } else {
+        const int64_t blocks = (T + NPLS_WT - 1) / NPLS_WT, units = (I + NPLS_WCH - 1) / NPLS_WCH;
+        if (blocks > 0x7fffffff) throw Unsupported("ppals: the wide contraction supports at most 2^31 - 1 row tiles");
+        const int64_t ns = npls_wide_ns(blocks, units, T, nc);
+        double *out = ns > 1 ? (double *)ensure(ws_part_, ws_part_sz_, sizeof(double) * (size_t)ns * nc * T) : Zc;
+        route("npls.contract.%s.wide.lead nt=%d ns=%lld", sname<TX>(), nt, (long long)ns);
+        npls_wide_cols_launch<TX>(nt, dim3((unsigned)blocks, (unsigned)ns), X, I, 0, T, I, 1, Uc, nc, out, T,
+                                  ns > 1 ? nc * T : 0);
+        if (ns > 1)
+          hipLaunchKernelGGL(k_npls_fold, dim3(grid_for(T, 256)), dim3(256), 0, st_, out, (int)ns, nc, (int64_t)1, T, nc, Zc);
+      }
+    }
+    HIP_CHECK(hipGetLastError());
+  }
+  template <typename TX>
+  void npls_si_wide_typed(const TX *X, int64_t L, int64_t I, int64_t T, const double *W, int C, double *S) {
+    const int64_t LT = L * T, blocks = (I + NPLS_WT - 1) / NPLS_WT;
+    if (blocks > 0x7fffffff) throw Unsupported("ppals: the wide slice_inner supports at most 2^31 - 1 row tiles");
+    for (int c0 = 0; c0 < C; c0 += NPLS_WIDE_COLS) {
+      const int nc = std::min(NPLS_WIDE_COLS, C - c0), nt = (nc + 15) / 16;
+      const double *Wc = W + LT * c0;
+      double *Sc = S + I * c0;
+      const int64_t units = L > 1 ? (L + NPLS_WCH - 1) / NPLS_WCH * T : (T + NPLS_WCH - 1) / NPLS_WCH;
+      const int64_t ns = npls_wide_ns(blocks, units, I, nc);
+      double *out = ns > 1 ? (double *)ensure(ws_part_, ws_part_sz_, sizeof(double) * (size_t)ns * nc * I) : Sc;
+      const int64_t sstride = ns > 1 ? nc * I : 0;
+      const dim3 grid((unsigned)blocks, (unsigned)ns);
+      if (L > 1) {
+        route("npls.slice_inner.%s.wide.rows nt=%d ns=%lld", sname<TX>(), nt, (long long)ns);
+        npls_wide_cols_launch<TX>(nt, grid, X, L, L * I, I, L, T, Wc, nc, out, I, sstride);
+      } else {
+        route("npls.slice_inner.%s.wide.lead nt=%d ns=%lld", sname<TX>(), nt, (long long)ns);
+        npls_wide_rows_launch<TX>(nt, grid, X, I, 0, I, T, Wc, nc, blocks, out, I, sstride);
+      }
+      if (ns > 1)
+        hipLaunchKernelGGL(k_npls_fold, dim3(grid_for(I, 256)), dim3(256), 0, st_, out, (int)ns, nc, (int64_t)1, I, nc, Sc);
+    }
+    HIP_CHECK(hipGetLastError());
+  }
+  void npls_contract_wide(const void *X, int dt, int64_t L, int64_t I, int64_t T, const double *U, int C, double *Z) override {
+    if (!npls_wide_geometry(true, L, I, C) || L * T <= 0 || I <= 0) {
+      route("npls.contract.%s.wide.narrow", dt == F32 ? "f32" : dt == BF16 ? "bf16" : "f64");
+      npls_contract(X, dt, L, I, T, U, C, Z);
+      return;
+    }
+    prof_begin(0, (double)L * I * T * dtype_size(dt) * ((C + NPLS_WIDE_COLS - 1) / NPLS_WIDE_COLS));
+    if (dt == F32)
+      npls_contract_wide_typed((const float *)X, L, I, T, U, C, Z);
+    else if (dt == BF16)
+      npls_contract_wide_typed((const bf16s *)X, L, I, T, U, C, Z);
+    else
+      npls_contract_wide_typed((const double *)X, L, I, T, U, C, Z);
+    prof_end();
+  }
+  void npls_slice_inner_wide(const void *X, int dt, int64_t L, int64_t I, int64_t T, const double *W, int C, double *S) override {
+    if (!npls_wide_geometry(false, L, I, C) || L * T <= 0 || I <= 0) {
+      route("npls.slice_inner.%s.wide.narrow", dt == F32 ? "f32" : dt == BF16 ? "bf16" : "f64");
+      npls_slice_inner(X, dt, L, I, T, W, C, S);
+      return;
+    }
+    prof_begin(0, (double)L * I * T * dtype_size(dt) * ((C + NPLS_WIDE_COLS - 1) / NPLS_WIDE_COLS));
+    if (dt == F32)
+      npls_si_wide_typed((const float *)X, L, I, T, W, C, S);
+    else if (dt == BF16)
+      npls_si_wide_typed((const bf16s *)X, L, I, T, W, C, S);
+    else
+      npls_si_wide_typed((const double *)X, L, I, T, W, C, S);
     prof_end();
   }
   void npls_outer_axpy(double *A, const int64_t *ext, int K, const double *const *w, double alpha) override {

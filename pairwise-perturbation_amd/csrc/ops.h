@@ -457,6 +457,16 @@ class Ops {
             s[(size_t)i + (size_t)I * c] += prep_load(h.data(), dt, (size_t)(l + L * (i + I * t))) * w[(size_t)(l + L * t) + LT * c];
     h2d(S, s.data(), sizeof(double) * s.size());
   }
+  // The wide-column forms (ppals_tensor_contract_columns / _slice_inner_columns, ppals_npls_crossval): the meaning
+  // and the layouts of the two ops above for many columns at once. Results are deterministic (two calls give the
+  // same bits) and within the same error bounds, but a column need not have the bits of the narrow op: the product
+  // back end sums on the fp64 matrix cores, 64 columns a read of X. The defaults are the narrow twins.
+  virtual void npls_contract_wide(const void *X, int dt, int64_t L, int64_t I, int64_t T, const double *U, int C, double *Z) {
+    npls_contract(X, dt, L, I, T, U, C, Z);
+  }
+  virtual void npls_slice_inner_wide(const void *X, int dt, int64_t L, int64_t I, int64_t T, const double *W, int C, double *S) {
+    npls_slice_inner(X, dt, L, I, T, W, C, S);
+  }
   virtual void npls_outer_axpy(double *A, const int64_t *ext, int K, const double *const *w, double alpha) {
     if (K < 1 || K > MAX_ORDER) throw Unsupported("ppals: outer_axpy takes 1 to 8 vectors");
     size_t n = 1;

@@ -479,6 +479,79 @@ int ppals_tensor_slice_inner(ppals_tensor *t, int mode, const double *W, int C, 
   return PPALS_OK;
   API_END(PPALS_ERR_HIP)
 }
+int ppals_tensor_contract_columns(ppals_tensor *t, int mode, const double *U, int C, double *Z) {
+  static const char *fn = "ppals_tensor_contract_columns";
+  API_BEGIN
+  const int rc = prep_check(t, mode, fn);
+  if (rc != PPALS_OK) return rc;
+  if (!U || !Z) return fail_fn(PPALS_ERR_ARG, fn, "U or Z is NULL");
+  if (C < 1) return fail_fn(PPALS_ERR_ARG, fn, "C must be at least 1");
+  tensor_contract_columns(*t->ctx->ops, t->d, mode, U, C, Z);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_tensor_slice_inner_columns(ppals_tensor *t, int mode, const double *W, int C, double *S) {
+  static const char *fn = "ppals_tensor_slice_inner_columns";
+  API_BEGIN
+  const int rc = prep_check(t, mode, fn);
+  if (rc != PPALS_OK) return rc;
+  if (!W || !S) return fail_fn(PPALS_ERR_ARG, fn, "W or S is NULL");
+  if (C < 1) return fail_fn(PPALS_ERR_ARG, fn, "C must be at least 1");
+  tensor_slice_inner_columns(*t->ctx->ops, t->d, mode, W, C, S);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+// the options of a fit or a cross-validation, checked; opts == NULL: the defaults
+static int npls_take_opts(const ppals_npls_opts *opts, const char *fn, NplsOpts *o) {
+  if (!opts) return PPALS_OK;
+  o->hopm_tol = opts->hopm_tol;
+  o->hopm_max = opts->hopm_max;
+  o->inner_tol = opts->inner_tol;
+  o->inner_max = opts->inner_max;
+  if (!(o->hopm_tol >= 0) || !(o->inner_tol >= 0)) return fail_fn(PPALS_ERR_ARG, fn, "a tolerance is negative or NaN");
+  if (o->hopm_max < 1 || o->inner_max < 1) return fail_fn(PPALS_ERR_ARG, fn, "hopm_max and inner_max must be at least 1");
+  return PPALS_OK;
+}
+int ppals_npls_crossval(ppals_tensor *X, int mode, const double *Y, int M, int F, const int32_t *segment, int S,
+                        int center, const ppals_npls_opts *opts, double *Ycv, double *press, int *fitted, int *status,
+                        int64_t *x_passes) {
+  static const char *fn = "ppals_npls_crossval";
+  API_BEGIN
+  int rc = prep_check(X, mode, fn);
+  if (rc != PPALS_OK) return rc;
+  if (!Y || !segment || !Ycv) return fail_fn(PPALS_ERR_ARG, fn, "Y, segment or Ycv is NULL");
+  if (X->d.order < 2) return fail_fn(PPALS_ERR_ARG, fn, "the tensor must have at least two modes");
+  if (M < 1) return fail_fn(PPALS_ERR_ARG, fn, "M must be at least 1");
+  if (F < 1) return fail_fn(PPALS_ERR_ARG, fn, "F must be at least 1");
+  if (center != 0 && center != 1) return fail_fn(PPALS_ERR_ARG, fn, "center must be 0 or 1");
+  const int64_t I = X->d.llens[mode];
+  if (S < 2 || S > I)
+    return fail_fn(PPALS_ERR_ARG, fn, ("S = " + std::to_string(S) + " is outside [2, " + std::to_string(I) +
+                                       "], the number of samples").c_str());
+  std::vector<int64_t> count((size_t)S, 0);
+  for (int64_t i = 0; i < I; i++) {
+    if (segment[i] < 0 || segment[i] >= S)
+      return fail_fn(PPALS_ERR_ARG, fn, ("segment[" + std::to_string(i) + "] = " + std::to_string(segment[i]) +
+                                         " is outside [0, " + std::to_string(S) + ")").c_str());
+    count[(size_t)segment[i]]++;
+  }
+  int64_t largest = 0;
+  for (int g = 0; g < S; g++) {
+    if (!count[(size_t)g]) return fail_fn(PPALS_ERR_ARG, fn, ("segment " + std::to_string(g) + " is empty").c_str());
+    largest = std::max(largest, count[(size_t)g]);
+  }
+  if (F > I - largest - center)
+    return fail_fn(PPALS_ERR_ARG, fn, ("F = " + std::to_string(F) + " is larger than " + std::to_string(I - largest - center) +
+                                       ", the smallest training set" + (center ? " less one for the mean" : "")).c_str());
+  NplsOpts o;
+  rc = npls_take_opts(opts, fn, &o);
+  if (rc != PPALS_OK) return rc;
+  rc = npls_check_finite(Y, I * M, fn, "Y");
+  if (rc != PPALS_OK) return rc;
+  npls_crossval(*X->ctx->ops, X->d, mode, Y, M, F, segment, S, center, o, Ycv, press, fitted, status, x_passes);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
 int ppals_npls_fit(ppals_tensor *X, int mode, const double *Y, int M, int F, const ppals_npls_opts *opts,
                    ppals_npls **out) {
   static const char *fn = "ppals_npls_fit";
@@ -494,14 +567,8 @@ int ppals_npls_fit(ppals_tensor *X, int mode, const double *Y, int M, int F, con
     return fail_fn(PPALS_ERR_ARG, fn, ("F = " + std::to_string(F) + " is outside [1, " + std::to_string(I) +
                                        "], the number of samples").c_str());
   NplsOpts o;
-  if (opts) {
-    o.hopm_tol = opts->hopm_tol;
-    o.hopm_max = opts->hopm_max;
-    o.inner_tol = opts->inner_tol;
-    o.inner_max = opts->inner_max;
-    if (!(o.hopm_tol >= 0) || !(o.inner_tol >= 0)) return fail_fn(PPALS_ERR_ARG, fn, "a tolerance is negative or NaN");
-    if (o.hopm_max < 1 || o.inner_max < 1) return fail_fn(PPALS_ERR_ARG, fn, "hopm_max and inner_max must be at least 1");
-  }
+  rc = npls_take_opts(opts, fn, &o);
+  if (rc != PPALS_OK) return rc;
   rc = npls_check_finite(Y, I * M, fn, "Y");
   if (rc != PPALS_OK) return rc;
   std::unique_ptr<ppals_npls> m(new ppals_npls);

@@ -84,6 +84,7 @@ EXPORTS = [
     "ppals_parafac2_run", "ppals_parafac2_projections", "ppals_parafac2_projections_device",
     "ppals_npls_fit", "ppals_npls_destroy", "ppals_npls_dims", "ppals_npls_get", "ppals_npls_predict",
     "ppals_tensor_contract_mode", "ppals_tensor_slice_inner",
+    "ppals_tensor_contract_columns", "ppals_tensor_slice_inner_columns", "ppals_npls_crossval",
 ]
 HOST, DEVICE = 0, 1  # PPALS_HOST / PPALS_DEVICE: where the offsets of Tensor.center / Tensor.shift lie
 MODE_FREE, MODE_NONNEG, MODE_FIXED, MODE_ORTHO = 0, 1, 2, 3  # PPALS_MODE_*
@@ -502,6 +503,28 @@ class Tensor:
         Cn = W2.shape[1]
         S = np.empty((I, Cn), dtype=np.float64, order="F")
         _check(lib().ppals_tensor_slice_inner(self._h, mode, _dp(W2), Cn, _dp(S)))
+        return S
+
+    # ---- the same passes for many columns: up to 64 a read of the tensor, on the fp64 matrix cores; deterministic and
+    # within the same error bounds as the two above, not bit-equal to them ----
+    def contract_columns(self, mode, U):
+        """contract_mode(mode, U) through the wide-column pass"""
+        mode = int(mode)
+        L, I, T, _ = self._prep_shape(mode)
+        U2 = np.asfortranarray(np.asarray(U, dtype=np.float64).reshape(I, -1, order="F"))
+        Cn = U2.shape[1]
+        Z = np.empty(L * T * Cn, dtype=np.float64)
+        _check(lib().ppals_tensor_contract_columns(self._h, mode, _dp(U2), Cn, _dp(Z)))
+        return Z.reshape(self.lens[:mode] + self.lens[mode + 1:] + [Cn], order="F")
+
+    def slice_inner_columns(self, mode, W):
+        """slice_inner(mode, W) through the wide-column pass"""
+        mode = int(mode)
+        L, I, T, _ = self._prep_shape(mode)
+        W2 = np.asfortranarray(np.asarray(W, dtype=np.float64).reshape(L * T, -1, order="F"))
+        Cn = W2.shape[1]
+        S = np.empty((I, Cn), dtype=np.float64, order="F")
+        _check(lib().ppals_tensor_slice_inner_columns(self._h, mode, _dp(W2), Cn, _dp(S)))
         return S
 
     def close(self):
@@ -1238,6 +1261,10 @@ class NPLS:
         self._opts = _NplsOpts(hopm_tol, hopm_max, inner_tol, inner_max)
         self._h = C.c_void_p()
 
+    def _opts_tuple(self):
+        o = self._opts
+        return o.hopm_tol, o.hopm_max, o.inner_tol, o.inner_max
+
     def _get(self, what, shape):
         n = C.c_int64(0)
         _check(lib().ppals_npls_get(self._h, what, None, C.byref(n)))
@@ -1293,6 +1320,51 @@ class NPLS:
 def npls(tensor, Y, ncomp, mode=0, **opts):
     """NPLS(**opts).fit(tensor, Y, ncomp, mode)"""
     return NPLS(**opts).fit(tensor, Y, ncomp, mode)
+
+
+class NplsCrossval:
+    """The record of npls_crossval: Ycv (I x M x F, the prediction of sample i from the first f + 1 components of the
+    fit without its segment), press (F x M), rmsecv = sqrt(press / I), best_ncomp (1-based: the first minimum of PRESS
+    summed over the responses), fitted (S: the components each resampled fit reached), status (S x F), x_passes (how
+    often the tensor was read) and segments (the I labels used)."""
+
+    def __init__(self, Ycv, press, fitted, status, x_passes, segments):
+        self.Ycv, self.press, self.fitted, self.status, self.x_passes, self.segments = Ycv, press, fitted, status, x_passes, segments
+        self.rmsecv = np.sqrt(press / Ycv.shape[0])
+        self.best_ncomp = int(np.argmin(press.sum(axis=1))) + 1
+
+
+def npls_crossval(tensor, Y, ncomp, mode=0, segments=7, center=True, split="interleave", **opts):
+    """Leave-segments-out cross-validation of N-PLS with 1 .. ncomp components on the resident tensor (ppals.h, "N-PLS
+    cross-validation"): all resampled fits share every pass over the tensor, which is neither written nor copied.
+    segments: a count (labels from holdout_segments(I, segments, split)) or an array of I labels in [0, S), S their
+    largest + 1. center: every fit centres X and Y on its own training samples (pass the tensor as it is). opts: those
+    of NPLS. Returns an NplsCrossval."""
+    Yh = _host_matrix(Y)
+    mode = int(mode)
+    I = tensor.lens[mode] if 0 <= mode < len(tensor.lens) else Yh.shape[0]
+    if Yh.shape[0] != I:
+        raise PpalsError(f"Y has {Yh.shape[0]} rows, the sample mode {I}")
+    if np.ndim(segments) == 0:
+        S = int(segments)
+        seg = np.argmin(holdout_segments(I, S, split), axis=0)
+    else:
+        seg = np.asarray(segments).ravel()
+        if seg.size != I:
+            raise PpalsError(f"{seg.size} segment labels for {I} samples")
+        S = int(seg.max()) + 1
+    seg = np.ascontiguousarray(seg, dtype=np.int32)
+    M, F = Yh.shape[1], int(ncomp)
+    o = _NplsOpts(*NPLS(**opts)._opts_tuple())
+    Ycv = np.zeros((I, M, max(F, 0)), dtype=np.float64, order="F")
+    press = np.zeros((max(F, 0), M), dtype=np.float64, order="F")
+    fitted, status = np.zeros(max(S, 0), dtype=np.int32), np.zeros((max(S, 0), max(F, 0)), dtype=np.int32, order="F")
+    passes = C.c_int64(0)
+    _check(lib().ppals_npls_crossval(tensor._h, mode, _dp(Yh), M, F, seg.ctypes.data_as(C.POINTER(C.c_int32)), S,
+                                     int(bool(center)), C.byref(o), _dp(Ycv), _dp(press),
+                                     fitted.ctypes.data_as(C.POINTER(C.c_int)), status.ctypes.data_as(C.POINTER(C.c_int)),
+                                     C.byref(passes)))
+    return NplsCrossval(Ycv, press, fitted.astype(np.int64), status.astype(np.int64), int(passes.value), seg.astype(np.int64))
 
 
 class CPMulti:
