@@ -655,6 +655,46 @@ int ppals_tucker_dt(ppals_tucker *s, const ppals_cp_opts *o, int *iters);
 /* alsTucker_PP (als_Tucker.h:89-91, als_Tucker.cxx:906-962); o->tol_init = -pp_res_tol */
 int ppals_tucker_pp(ppals_tucker *s, const ppals_cp_opts *o, int *iters);
 
+/* ---- Tucker: residual, per-slice residuals and leverages (the influence plot of a Tucker3 model; no
+ * counterpart in the reference) ----
+ * The CP section "per-slice residuals and leverages" for a Tucker session: which samples fit badly, which
+ * samples or variables carry the model. The model is core x_0 W_0 ... x_{N-1} W_{N-1} of exactly the factors
+ * and core ppals_tucker_get_factors would return now (deferred eigen-steps settled, pending rotations
+ * applied), whatever they are: orthonormal factors as every sweep leaves them, or any factors and core given
+ * by ppals_tucker_set_factors / ppals_tucker_set_core.
+ * ss, lev: sum_i s_i doubles, mode 0's s_0 values first, like their CP twins.
+ *   *out     = ||V - model||_F, the figure the drivers print.
+ *   ss_i[x]  = sum over all elements whose i-th index is x of (V - model)^2; V as stored (fp32 / fp64), model,
+ *              differences and sums in fp64 (the products on the fp64 matrix cores). *total (may be NULL) = the
+ *              sum over all elements = ppals_tucker_residual()^2 up to rounding; every mode's ss_i sums to it.
+ *   lev_i[x] = the x-th diagonal entry of the projector onto the column space of W_i: sum_k W_i[x,k]^2 for the
+ *              orthonormal factors every sweep leaves, and for any other factor the same sum over an
+ *              orthonormal basis of its columns (a QR factorisation of a scratch copy). In [0,1], summing to
+ *              r_i. Every rank a session can hold. A session ONE of whose factors is numerically rank
+ *              deficient gets NaN in EVERY entry of lev, and PPALS_OK.
+ * All three are ordered after the work queued on the engine stream and return when the result is on the host.
+ * They change nothing of the session (beyond what ppals_tucker_get_factors changes: the settle) and nothing of
+ * the tensor or its generation: a session that calls them between sweeps continues, bit for bit, like a twin
+ * that called ppals_tucker_get_factors at the same points. The same state gives the same bits on every call
+ * (no floating-point atomics; partial sums are added in an order fixed by the geometry).
+ * Tensor traffic: ppals_tucker_slice_residuals reads the resident tensor exactly ONCE, whatever the order,
+ * extents and ranks, and stores nothing but sums: the pass of ppals_tucker_impute_device's observed residual,
+ * Z = core x_{i != 0} W_i built slab by slab within two 256 MB buffers and V - W_0 Z^T formed tile by tile,
+ * keeping the sums over the rows and the columns of every tile; the column sums are folded onto modes
+ * 1..N-1. Nothing of the tensor's size is allocated. ppals_tucker_leverages never reads the tensor.
+ * Work memory: the session's own, grow-only — the transposed factors and chain buffers the model export
+ * keeps, one slab's marginal and its fold, and the partial sums of the pass, which stay under 256 MB (a
+ * slab's row tiles are walked in several launches where they would not, and folded in tile order, so the cap
+ * changes no bit of the result).
+ * No mask argument, for the reason the CP section gives (after ppals_tucker_impute_device the missing
+ * entries equal the model up to one storage rounding).
+ * Refused before anything is launched or allocated, the message starting with the function's name —
+ * PPALS_ERR_ARG: a NULL session, a NULL out / ss / lev; PPALS_ERR_UNSUPPORTED: a context of more than one
+ * rank (ppals_tucker_slice_residuals and ppals_tucker_leverages; ppals_tucker_residual runs sharded). */
+int ppals_tucker_residual(ppals_tucker *s, double *out);
+int ppals_tucker_slice_residuals(ppals_tucker *s, double *ss, double *total /* may be NULL */);
+int ppals_tucker_leverages(ppals_tucker *s, double *lev);
+
 /* ---- a fitted model and its residual into DEVICE memory (TensorLy's cp_to_tensor / tucker_to_tensor)
  * The view is exactly that of ppals_tensor_export_device: a box of the GLOBAL tensor, strides >= 0 in
  * elements (NULL: dense over the box, first index fastest), destination type F32 or F64; every check

@@ -29,6 +29,7 @@
 #include "kernels_eig.hip.h"
 #include "kernels_io.hip.h"
 #include "kernels_model.hip.h"
+#include "kernels_tucker_slices.hip.h"
 #include "kernels_wls.hip.h"
 #include "kernels_huber.hip.h"
 #include "kernels_parafac2.hip.h"
@@ -186,6 +187,11 @@ class HipOps : public Ops {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, mw_max));
     HIP_CHECK(hipFuncSetAttribute((const void *)k_model_impute_wide<double, true>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, mw_max));
+    const int ts_max = (int)ts_lds_bytes(MW_KMAX);
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_model_slices_wide<float>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, ts_max));
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_model_slices_wide<double>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, ts_max));
     const int wl_max = (int)wl_lds_bytes(WL_KMAX, sizeof(double));
     HIP_CHECK(hipFuncSetAttribute((const void *)k_model_wls<float, float>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, wl_max));
@@ -1434,6 +1440,67 @@ class HipOps : public Ops {
       hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(1024), 0, st_, part, (int)npart, sumsq);
       HIP_CHECK(hipGetLastError());
     }
+  }
+
+  // ------------------------------------------------------------------ a Tucker session's slice sums
+  // Routes (kernels_tucker_slices.hip.h), chosen by K as the imputation chooses: K <= 16 k_model_slices, Q in
+  // registers; 16 < K <= MW_KMAX k_model_slices_wide, Q in LDS; above, k_model_slices again, in chunks of k.
+  // The geometry — ntA row tiles, gy workgroups a tile — follows from the slab alone; the cap only cuts the
+  // row tiles into launches of nt tiles whose partials (8 (nt B + gy 64 nt) bytes) fit, and k_slice_fold adds
+  // every launch's partials onto asq / bsq in tile order, so the cap changes no bit.
+  template <typename TV>
+  void slice_sums_launch(const ModelPlan &mp, const double *Q, const double *P, int K, const TV *V, bool first,
+                         double *asq, double *bsq, size_t cap, void *&work, size_t &work_bytes) {
+    const int64_t A = mp.ga.count, B = mp.gb.count;
+    const bool wide = K > 16 && K <= MW_KMAX;
+    dim3 grid;
+    const int64_t *tab = wide ? mv_tables(mp, &grid, 2 * ts_wgs_per_cu(K)) : mv_tables(mp, &grid);
+    const int64_t *tar = tab + A, *tbr = tab + 2 * A + B;
+    const int64_t ntA = grid.x, gy = grid.y;
+    const int64_t one = B + gy * MV_TILE;  // doubles of partial sums a row tile
+    const int64_t nt = std::max<int64_t>(1, std::min<int64_t>(ntA, (int64_t)(cap / sizeof(double)) / one));
+    const int64_t rp_ld = nt * MV_TILE;
+    const size_t need = sizeof(double) * (size_t)(nt * one);
+    if (need > work_bytes) {  // (the caller's buffer, exactly what is needed: it is held to a cap)
+      free(work);
+      work = nullptr;
+      work_bytes = 0;
+      work = alloc(need);
+      work_bytes = need;
+    }
+    double *rowpart = (double *)work, *colpart = rowpart + gy * rp_ld;
+    route("model_slices:%s,K%d,%s,tiles%lld,gy%lld,launches%lld", tname<TV>(), K,
+          wide ? "lds" : (K <= 16 ? "regs" : "chunks"), (long long)ntA, (long long)gy, (long long)((ntA + nt - 1) / nt));
+    for (int64_t t0 = 0; t0 < ntA; t0 += nt) {
+      const int64_t ntc = std::min(nt, ntA - t0), rows = std::min(A - t0 * MV_TILE, ntc * MV_TILE);
+      const dim3 g((unsigned)ntc, (unsigned)gy);
+      prof_begin(1, (double)rows * (double)B * sizeof(TV));
+      if (wide)
+        hipLaunchKernelGGL((k_model_slices_wide<TV>), g, dim3(256), ts_lds_bytes(K), st_, V, Q, P, K, mp, tar, tbr, t0,
+                           rp_ld, rowpart, colpart);
+      else
+        hipLaunchKernelGGL((k_model_slices<TV>), g, dim3(256), 0, st_, V, Q, P, K, mp, tar, tbr, t0, rp_ld, rowpart,
+                           colpart);
+      prof_end();
+      HIP_CHECK(hipGetLastError());
+      hipLaunchKernelGGL(k_slice_fold, dim3(grid_for(rows + B, 256)), dim3(256), 0, st_, rowpart, gy, rp_ld, rows,
+                         t0 * MV_TILE, first ? 1 : 0, colpart, ntc, B, B, (int64_t)0, t0 == 0 ? 1 : 0, asq, bsq);
+      HIP_CHECK(hipGetLastError());
+    }
+  }
+  void model_slice_sums(const ModelPlan &mp, const double *Q, const double *P, int K, const void *V, int dt,
+                        bool first, double *asq, double *bsq, size_t work_cap_bytes, void *&work,
+                        size_t &work_bytes) override {
+    RoctxRange roctx_("model slice sums");
+    HIP_CHECK(hipSetDevice(dev_));
+    if (mp.ga.count <= 0 || mp.gb.count <= 0) return;
+    if (K < 1) throw std::runtime_error("ppals: model_slice_sums needs K >= 1");
+    if (dt == F32)
+      slice_sums_launch(mp, Q, P, K, (const float *)V, first, asq, bsq, work_cap_bytes, work, work_bytes);
+    else if (dt == F64)
+      slice_sums_launch(mp, Q, P, K, (const double *)V, first, asq, bsq, work_cap_bytes, work, work_bytes);
+    else
+      throw std::runtime_error("ppals: model_slice_sums reads F32 or F64 storage");
   }
 
   // ------------------------------------------------------------------ the weighted step

@@ -1318,6 +1318,61 @@ class Ops {
       for (int64_t x = 0; x < rows; x++) o[(size_t)x] += p[(size_t)(x + ld * r)] * w[(size_t)(x + ld * r)];
     h2d(out, o.data(), sizeof(double) * o.size());
   }
+  // ---- a Tucker session's per-slice residuals (TuckerEngine::slice_residuals; include/ppals.h) ----
+  // One slab of the pass, on a plan as TuckerEngine::impute builds it (group A = mode 0, the shard's fast
+  // side; group B = the other modes in the shard's order; only the plan's SHARD side is read): with
+  //   e(a,b) = V[roff + rA(a) + rB(b)] - sum_{k<K} Q[a + ldq*k] * P[(b % pL) + pLK*(b / pL) + pL*k]
+  // (V as stored, dt F32 / F64; everything else fp64, k ascending)
+  //   asq[a] = (first ? 0 : asq[a]) + sum_b e^2,   bsq[b] = sum_a e^2                      (device, fp64)
+  // from ONE read of the slab of V, nothing else of its size touched. The same inputs give the same bits: no
+  // atomics, partial sums added in an order fixed by the geometry. `work`, `work_bytes` and the cap: the
+  // caller's grow-only buffer of the partial sums, handed over as to residual_slices; the cap cuts the slab's
+  // row tiles into several launches and changes no bit. On the engine stream; the host does not block.
+  // This default is the fp64 host twin (it needs no partial sums and leaves `work` alone), which the host
+  // stand-in runs; the product back end overrides it.
+  virtual void model_slice_sums(const ModelPlan &mp, const double *Q, const double *P, int K, const void *V, int dt,
+                                bool first, double *asq, double *bsq, size_t /*work_cap_bytes*/, void *& /*work*/,
+                                size_t & /*work_bytes*/) {
+    const int64_t A = mp.ga.count, B = mp.gb.count;
+    if (A <= 0 || B <= 0) return;
+    if (dt != F32 && dt != F64) throw std::runtime_error("ppals: model_slice_sums reads F32 or F64 storage");
+    auto offsets = [](const ModelGroup &g) {
+      std::vector<int64_t> o((size_t)g.count);
+      for (int64_t e = 0; e < g.count; e++) {
+        int64_t idx = e, r = 0;
+        for (int m = 0; m < g.n; m++) {
+          r += (idx % g.len[m]) * g.rs[m];
+          idx /= g.len[m];
+        }
+        o[(size_t)e] = r;
+      }
+      return o;
+    };
+    const std::vector<int64_t> ra = offsets(mp.ga), rb = offsets(mp.gb);
+    const int64_t bl = B - 1;
+    const size_t nv = (size_t)(mp.roff + ra.back() + rb.back() + 1), nq = (size_t)((A - 1) + mp.ldq * (K - 1) + 1),
+                 np = (size_t)((bl % mp.pL) + mp.pLK * (bl / mp.pL) + mp.pL * (K - 1) + 1);
+    std::vector<char> raw(nv * dtype_size(dt));
+    std::vector<double> q(nq), p(np), as((size_t)A, 0.0), bs((size_t)B, 0.0);
+    d2h(raw.data(), V, raw.size());
+    d2h(q.data(), Q, sizeof(double) * nq);
+    d2h(p.data(), P, sizeof(double) * np);
+    if (!first) d2h(as.data(), asq, sizeof(double) * as.size());
+    for (int64_t b = 0; b < B; b++) {
+      const int64_t pb = (b % mp.pL) + mp.pLK * (b / mp.pL);
+      for (int64_t a = 0; a < A; a++) {
+        double v = 0;
+        for (int k = 0; k < K; k++) v += q[(size_t)(a + mp.ldq * k)] * p[(size_t)(pb + mp.pL * k)];
+        const size_t e = (size_t)(mp.roff + ra[(size_t)a] + rb[(size_t)b]);
+        const double x = dt == F32 ? (double)((const float *)raw.data())[e] : ((const double *)raw.data())[e];
+        const double d = x - v;
+        as[(size_t)a] += d * d;
+        bs[(size_t)b] += d * d;
+      }
+    }
+    h2d(asq, as.data(), sizeof(double) * as.size());
+    h2d(bsq, bs.data(), sizeof(double) * bs.size());
+  }
   // Where the next scan_contract calls are booked in the launch profile: 0 the tensor scans (the default),
   // 1 the other kernels — for a scan of something that is not the tensor.
   virtual void scan_profile_slot(int /*slot*/) {}

@@ -1916,4 +1916,45 @@ int ppals_tucker_pp(ppals_tucker *s, const ppals_cp_opts *o, int *iters) {
   API_END(PPALS_ERR_HIP)
 }
 
+// ------------------------------------------------------------------ Tucker: residual and influence plot
+// the refusals of the three calls, before anything is launched or allocated (one_rank: the two diagnostics)
+static int check_tucker_influence(ppals_tucker *s, const void *out, const char *fn, const char *outname,
+                                  bool one_rank) {
+  char msg[192];
+  if (!s || !s->eng) {
+    std::snprintf(msg, sizeof(msg), "%s: NULL session", fn);
+    return fail(PPALS_ERR_ARG, msg);
+  }
+  if (!out) {
+    std::snprintf(msg, sizeof(msg), "%s: %s is NULL", fn, outname);
+    return fail(PPALS_ERR_ARG, msg);
+  }
+  if (one_rank && s->ctx->c().size() > 1) {
+    std::snprintf(msg, sizeof(msg), "%s: the influence plot runs on one rank (no sharded form)", fn);
+    return fail(PPALS_ERR_UNSUPPORTED, msg);
+  }
+  return PPALS_OK;
+}
+int ppals_tucker_residual(ppals_tucker *s, double *out) {
+  if (int rc = check_tucker_influence(s, out, "ppals_tucker_residual", "out", false)) return rc;
+  API_BEGIN
+  *out = s->eng->residual_now();
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_tucker_slice_residuals(ppals_tucker *s, double *ss, double *total) {
+  if (int rc = check_tucker_influence(s, ss, "ppals_tucker_slice_residuals", "ss", true)) return rc;
+  API_BEGIN
+  s->eng->slice_residuals(ss, total);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_tucker_leverages(ppals_tucker *s, double *lev) {
+  if (int rc = check_tucker_influence(s, lev, "ppals_tucker_leverages", "lev", true)) return rc;
+  API_BEGIN
+  s->eng->leverages(lev);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+
 }  // extern "C"

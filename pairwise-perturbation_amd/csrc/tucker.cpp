@@ -15,7 +15,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <limits>
 #include <stdexcept>
+#include <string>
 
 namespace ppals {
 
@@ -25,6 +27,7 @@ TuckerEngine::TuckerEngine(Ops &ops, Comm &comm, const TensorDesc &V, const int 
   dist_ = P_ > 1 || (force_comm_path() && !comm.is_self());
   rank_ = comm.rank();
   residual_form_ = residual_form_env();
+  slice_work_cap_ = slice_work_cap_env();
   eig_base_ = ops_.eig_session_new();  // this session's warm-start slots: base + {i, 8 + i, 16 + i}
   // (the back end sets up what lazy eigen-steps need now, not inside the first sweep)
   if (!dist_)
@@ -608,6 +611,100 @@ int TuckerEngine::run_em(const ViewArgs &a, const void *mask, void *stream, cons
   if (iters) *iters = k;
   if (observed_res) *observed_res = std::sqrt(sq);
   return on_tol ? 1 : 0;
+}
+
+// The influence plot (tucker.h). The plan is the imputation's on the box of the whole local
+// shard: f = mode 0 is group A, the slabs are cut along the last mode of extent > 1.
+void TuckerEngine::slice_residuals(double *ss_host, double *total_host) {
+  if (dist_) throw Unsupported("ppals: the per-slice residuals run on one rank");
+  finalize_rotations();  // (as export_model: the factors and core get_factors would return now)
+  ViewArgs a;
+  std::string err;
+  if (!dv_check_args(DV_EXPORT, N_, V_.glens, DV_F64, nullptr, nullptr, nullptr, &a, &err))
+    throw std::runtime_error("ppals: " + err);
+  ModelBox bx;
+  if (!dv_model_box(a, V_.glens, V_.row0, V_.llens[0], &bx)) throw std::logic_error("ppals: empty shard");
+  int s = -1;
+  int64_t nout = 0, off[MAX_ORDER];
+  for (int m = 0; m < N_; m++) {
+    if (m >= 1 && bx.len[m] > 1) s = m;
+    off[m] = nout;
+    nout += V_.glens[m];
+  }
+  sl_out_.reserve(ops_, sizeof(double) * nout);
+  double *out = sl_out_.as<double>();
+  // the op frees its partial sums' buffer and takes a larger one as it needs (ops.h): handed over for the
+  // call, taken back on every way out
+  size_t work_bytes = sl_work_.size();
+  void *work = sl_work_.release();
+  bool first = true;
+  int64_t done = 0;  // rows of the slab mode behind us
+  try {
+    model_slabs(bx, 0, s, [&](const ModelPlan &mp, const double *Q, const double *Z) {
+      int64_t nb = 0;
+      for (int j = 0; j < mp.gb.n; j++) nb += mp.gb.len[j];
+      // (the first slab is the largest: the buffers move there or never, so no later slab waits for a free)
+      sl_col_.reserve(ops_, sizeof(double) * mp.gb.count);
+      sl_fold_.reserve(ops_, sizeof(double) * std::max<int64_t>(nb, 1));
+      double *col = sl_col_.as<double>(), *fold = sl_fold_.as<double>();
+      ops_.model_slice_sums(mp, Q, Z, r_[0], V_.data, V_.dtype, first, out, col, slice_work_cap_, work, work_bytes);
+      if (mp.gb.n > 0) ops_.fold_slice_sums(col, mp.gb.len, mp.gb.n, fold);
+      int64_t fo = 0, slab_len = 0;
+      for (int j = 0; j < mp.gb.n; j++) {
+        const int m = mp.gb.mode[j];
+        const int64_t len = mp.gb.len[j];
+        double *dst = out + off[m] + (m == s ? done : 0);
+        if (m == s || first)
+          ops_.d2d(dst, fold + fo, sizeof(double) * len);
+        else
+          ops_.add_inplace(dst, fold + fo, len);
+        if (m == s) slab_len = len;
+        fo += len;
+      }
+      done += slab_len;
+      first = false;
+    });
+  } catch (...) {
+    sl_work_ = DeviceBuffer(ops_, work, work_bytes);
+    throw;
+  }
+  sl_work_ = DeviceBuffer(ops_, work, work_bytes);
+  ops_.d2h(ss_host, out, sizeof(double) * nout);
+  if (total_host) {
+    double t = 0;
+    for (int64_t x = 0; x < V_.glens[0]; x++) t += ss_host[x];
+    *total_host = t;
+  }
+}
+
+void TuckerEngine::leverages(double *lev_host) {
+  if (dist_) throw Unsupported("ppals: the leverages run on one rank");
+  finalize_rotations();
+  int64_t nout = 0, most = 0;
+  for (int i = 0; i < N_; i++) {
+    nout += V_.glens[i];
+    most = std::max(most, V_.glens[i] * r_[i]);
+  }
+  sl_out_.reserve(ops_, sizeof(double) * nout);
+  sl_q_.reserve(ops_, sizeof(double) * most);
+  double *out = sl_out_.as<double>(), *Qs = sl_q_.as<double>();
+  bool bad = false;
+  int64_t off = 0;
+  for (int i = 0; i < N_ && !bad; i++) {
+    const int64_t rows = V_.glens[i];
+    ops_.d2d(Qs, W_[i], sizeof(double) * rows * r_[i]);
+    if (!ops_.orthonormalize(Qs, rows, r_[i]))
+      bad = true;  // rank deficient: no projector to speak of
+    else
+      ops_.row_dots(Qs, Qs, rows, r_[i], rows, out + off);
+    off += rows;
+  }
+  if (bad) {
+    ops_.sync();
+    for (int64_t e = 0; e < nout; e++) lev_host[e] = std::numeric_limits<double>::quiet_NaN();
+    return;
+  }
+  ops_.d2h(lev_host, out, sizeof(double) * nout);
 }
 
 // The slabs of box bx for fast mode f, cut along mode s (-1: none): the transposed factors, the chain

@@ -33,6 +33,24 @@ class TuckerEngine {
   // stop rules and the last impute on the way out as CpEngine::run_em. Returns 1 if it stopped on tol.
   int run_em(const ViewArgs &a, const void *mask, void *stream, const CpOpts &o, int inner_sweeps, int *iters,
              double *observed_res);
+  // ||V - core x_i W_i||_F of the factors and core get_factors would return now (ppals_tucker_residual)
+  double residual_now() {
+    finalize_rotations();
+    return residual();
+  }
+  // The influence plot of a Tucker session (ppals_tucker_slice_residuals / _leverages; one rank). Both settle
+  // the rotations as export_model does, change nothing else of the session and nothing of the tensor.
+  //   slice_residuals: ss_i[x] = the sum of (V - core x_j W_j)^2 over the slice x of mode i, all modes from
+  //     ONE pass over the tensor: the slabs of impute (model_slabs: Z = core x_{i != 0} W_i within the chain
+  //     buffers), per slab Ops::model_slice_sums — the sums over b onto ss_0 in slab order, the sums over a
+  //     folded onto modes 1..N-1 (Ops::fold_slice_sums): the slab mode's entries at the slab's offset, the
+  //     other modes' added in slab order. total = the sum of ss_0 in index order. The host does not wait
+  //     between slabs.
+  //   leverages: lev_i[x] = the x-th diagonal entry of the projector onto the columns of W_i = the row sums of
+  //     squares of an orthonormal basis of them (Ops::orthonormalize on a scratch copy, Ops::row_dots); NaN in
+  //     every entry when ONE factor is rank deficient. Never reads the tensor.
+  void slice_residuals(double *ss_host, double *total_host);
+  void leverages(double *lev_host);
   const TensorDesc &tensor() const { return V_; }
   int run_dt(const CpOpts &o, int *iters);  // alsTucker_DT, als_Tucker.cxx:240-424
   int run_pp(const CpOpts &o, int *iters);  // alsTucker_PP, als_Tucker.cxx:906-962
@@ -155,6 +173,10 @@ class TuckerEngine {
   void export_slab(const ModelBox &bx, int f, const std::vector<int> &chain, const SlabRun &run);
   // (kept for the session's next export: freeing them would wait for the device)
   DeviceBuffer xwt_, xz_[2];
+  // slice_residuals / leverages (grow-only): the slab's marginal over b, its fold, the N result vectors, the
+  // back end's partial sums, the scratch copy of a factor
+  DeviceBuffer sl_col_, sl_fold_, sl_out_, sl_work_, sl_q_;
+  size_t slice_work_cap_ = (size_t)256 << 20;  // of the partial sums (PPALS_TEST_SLICE_WORK_BYTES)
   int residual_form_ = RESIDUAL_FUSED;  // PPALS_MODEL_RESIDUAL
   DeviceBuffer Yfull_, gather_;
 };

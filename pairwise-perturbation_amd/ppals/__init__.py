@@ -71,6 +71,7 @@ EXPORTS = [
     "ppals_match_columns", "ppals_cp_congruence", "ppals_cp_fms", "ppals_cp_multi_congruence",
     "ppals_cp_multi_fms", "ppals_cp_multi_fms_between",
     "ppals_cp_slice_residuals", "ppals_cp_leverages",
+    "ppals_tucker_residual", "ppals_tucker_slice_residuals", "ppals_tucker_leverages",
     "ppals_cp_multi_set_holdout", "ppals_cp_multi_get_holdout", "ppals_cp_multi_heldout_scores",
     "ppals_cp_multi_take_predicted",
     "ppals_cp_set_mode_constraints", "ppals_cp_get_mode_constraints",
@@ -1648,6 +1649,40 @@ class Tucker(_ModelExport, _Impute):
         it = C.c_int(0)
         rc = _check(lib().ppals_tucker_pp(self._h, C.byref(o), C.byref(it)))
         return rc, it.value
+
+    def residual(self):
+        """||V - core x_i W_i||_F of the factors and core get_factors would return now (ppals_tucker_residual)"""
+        out = C.c_double(0)
+        _check(lib().ppals_tucker_residual(self._h, C.byref(out)))
+        return out.value
+
+    _per_mode = CP._per_mode
+
+    def slice_residuals(self, return_total=False):
+        """the residual side of the influence plot (ppals_tucker_slice_residuals): a list of N vectors, entry x
+        of vector i the sum of (V - model)^2 over the slice x of mode i — one pass over the tensor, nothing
+        materialised. return_total: (list, total), total = residual()**2 up to rounding. Changes nothing of
+        the session beyond the settle of get_factors."""
+        out = np.empty(sum(self.lens))
+        total = C.c_double(0)
+        _check(lib().ppals_tucker_slice_residuals(self._h, _dp(out), C.byref(total)))
+        ss = self._per_mode(out)
+        return (ss, total.value) if return_total else ss
+
+    def leverages(self):
+        """the leverage side (ppals_tucker_leverages): a list of N vectors, entry x of vector i the x-th
+        diagonal entry of the projector onto the columns of W_i (the row's sum of squares for the orthonormal
+        factors a sweep leaves); all NaN when a factor is rank deficient. Never reads the tensor."""
+        out = np.empty(sum(self.lens))
+        _check(lib().ppals_tucker_leverages(self._h, _dp(out)))
+        return self._per_mode(out)
+
+    def explained(self):
+        """core**2 / ||V||**2, shaped like the core: the share of the tensor's variation each core entry
+        explains. Meaningful for ORTHONORMAL factors (what hosvd and every sweep leave): the entries then sum
+        to 1 - residual()**2 / ||V||**2. A host helper on get_factors."""
+        core = self.get_factors()[1]
+        return core ** 2 / self.V.norm() ** 2
 
     def close(self):
         if self._h:
