@@ -929,10 +929,50 @@ int ppals_parafac2_step_device(ppals_parafac2 *p, const void *data, int dtype, c
  * ppals_cp_wls (NULL o, inner_sweeps < 1, rel_change < 0 or NaN, o->maxiter < 0) and of the step. */
 int ppals_parafac2_run(ppals_parafac2 *p, const void *data, int dtype, const int64_t *strides, void *stream,
                        const ppals_cp_opts *o, int inner_sweeps, double rel_change, int *iters, double *res);
-/* The projections: P_host receives I R K doubles, P_k column-major at I R k; the device pointer (same layout)
+/* The projections: P_host receives I R K doubles, P_k column-major at I R k (a ragged object, below: R N doubles,
+ * P_k with leading dimension rows[k] at R o_k — for equal rows the same layout); the device pointer (same layout)
  * stays the object's and is valid until ppals_parafac2_destroy; it is written by work on the engine stream. */
 int ppals_parafac2_projections(ppals_parafac2 *p, double *P_host);
 int ppals_parafac2_projections_device(ppals_parafac2 *p, const double **P);
+
+/* ---- PARAFAC2 on slices of unequal length (batch processes of different duration, runs cut at different points) ----
+ * Slice k is rows[k] x J; N = sum_k rows[k], o_k = sum_{l<k} rows[l]. The model, the compressed tensor Y (R x J x K),
+ * the inner session, the loss identity and the driver are those above; only P_k (rows[k] x R) differs in size.
+ * The object owns Y, the session, P and the step's scratch of R N doubles each (P_k column-major with leading
+ * dimension rows[k] at R o_k), T, the outputs and the small device tables of the step (rows, row offsets, the
+ * map from row tiles to slices, the view of the last step). A step on zero-padded slices of equal length gives
+ * the same fit but reads the padding twice and holds max_k rows[k] K rows.
+ *
+ * ppals_parafac2_create_ragged: refused before anything is allocated — PPALS_ERR_ARG for NULL rows, K < 1 or
+ * J < 1, R outside [2, 64], R > J, a rows[k] < R (the message names the first such k), a bad dtype;
+ * PPALS_ERR_UNSUPPORTED as ppals_parafac2_create. The initial state is that of ppals_parafac2_create: every P_k the
+ * first R identity columns. ppals_parafac2_cp, _tensor, _destroy and _projections_device serve both kinds of
+ * object; ppals_parafac2_step_device and ppals_parafac2_run refuse a ragged object, and the two entry points below
+ * an equal-length one, with PPALS_ERR_ARG. */
+int ppals_parafac2_create_ragged(ppals_ctx *ctx, int64_t K, const int64_t *rows /* K */, int64_t J, int R,
+                                 int storage_dtype, ppals_parafac2 **out);
+/* The slice lengths, for both kinds of object (an equal-length object answers I for every slice), and their sum. */
+int ppals_parafac2_rows(ppals_parafac2 *p, int64_t *rows /* K */, int64_t *total /* may be NULL */);
+/* The step of ppals_parafac2_step_device on a ragged object. X_k[i, j] = data[offsets[k] + i + col_strides[k] j],
+ * in elements, unit stride in i. offsets == NULL: the slices packed one after another, offsets[k] = J o_k;
+ * col_strides == NULL: col_strides[k] = rows[k]. The stacked N x J column-major matrix is offsets[k] = o_k,
+ * col_strides[k] = N. Padded slices and gaps are fine; the step only reads, so spans that overlap are not refused.
+ * PPALS_ERR_ARG, before any launch, copy or allocation: an equal-length object, NULL data, a dtype other than
+ * PPALS_F32 / PPALS_F64, a pointer not aligned to its element size or not device memory, an offsets[k] < 0, a
+ * col_strides[k] < rows[k], a union of the slices' spans that does not lie inside the pointer's allocation, mode 0
+ * of the inner session not PPALS_MODE_FREE. Semantics, *lost_sq, *failed, the ordering against `stream` and "the
+ * host does not block when both outputs are NULL" are those of ppals_parafac2_step_device, with one exception: the
+ * offsets and strides travel to the device when they differ from the last step's, and that copy waits for the
+ * engine stream. The sums run in the orders of the equal-length step: equal rows on the dense layout give its
+ * bits. The number of launches does not depend on K, the rows, J or R. */
+int ppals_parafac2_step_ragged_device(ppals_parafac2 *p, const void *data, int dtype,
+                                      const int64_t *offsets /* K, or NULL */,
+                                      const int64_t *col_strides /* K, or NULL */, void *stream,
+                                      double *lost_sq /* may be NULL */, int *failed /* may be NULL */);
+/* The driver of ppals_parafac2_run on the ragged step: the same looks, stop rules, return codes and errors. */
+int ppals_parafac2_run_ragged(ppals_parafac2 *p, const void *data, int dtype, const int64_t *offsets,
+                              const int64_t *col_strides, void *stream, const ppals_cp_opts *o, int inner_sweeps,
+                              double rel_change, int *iters, double *res);
 
 /* ---- N-PLS regression (multilinear PLS: Bro, J. Chemometrics 10 (1996) 47-61; `npls` of the N-way toolbox) ----
  * X is a resident tensor of any order N >= 2, `mode` its sample mode with I = lens[mode] samples; Y is I x M on

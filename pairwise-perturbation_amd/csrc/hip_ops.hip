@@ -226,7 +226,11 @@ class HipOps : public Ops {
     HIP_CHECK(hipFuncSetAttribute((const void *)k_shape_columns, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)kShapeLdsBytes));
     HIP_CHECK(hipFuncSetAttribute((const void *)k_p2_polar, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    const void *p2_wide[] = {(const void *)k_p2_project<float, 4>, (const void *)k_p2_project<double, 4>};
+    HIP_CHECK(hipFuncSetAttribute((const void *)k_p2_polar_ragged, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  96 * 1024));
+    const void *p2_wide[] = {(const void *)k_p2_project<float, 4>, (const void *)k_p2_project<double, 4>,
+                             (const void *)k_p2_project_ragged<float, 4>,
+                             (const void *)k_p2_project_ragged<double, 4>};
     for (const void *k : p2_wide)  // (R > 48: 72 KB at R = 64; every other instantiation stays below 64 KB)
       HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p2_project_lds(64)));
   }
@@ -1717,6 +1721,66 @@ class HipOps : public Ops {
     });
     HIP_CHECK(hipGetLastError());
     release_stream(caller_stream);  // and the caller may change the view after the reads
+    if (s.out) {
+      hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(1024), 0, st_, part, (int)npart, s.out);
+      hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(1024), 0, st_, part + npart, (int)npart, s.out + 1);
+      hipLaunchKernelGGL(k_p2_failed, dim3(1), dim3(1024), 0, st_, s.status, s.K, s.out + 2);
+      HIP_CHECK(hipGetLastError());
+    }
+  }
+
+  // the ragged step: the same seven launches, the first pass and the apply over the row tiles of all slices
+  void parafac2_init_ragged(const Parafac2Ragged &s) override {
+    HIP_CHECK(hipSetDevice(dev_));
+    if (s.tiles < 1 || s.tiles > 0x7fffffff) throw std::runtime_error("ppals: parafac2_init_ragged: too many tiles");
+    hipLaunchKernelGGL(k_p2_init_ragged, dim3((unsigned)s.tiles), dim3(256), 0, st_, s.P, s.rows, s.roff, s.tile0,
+                       s.tile_slice, s.R);
+    HIP_CHECK(hipGetLastError());
+  }
+  template <typename TX, int NT>
+  void p2_launch_ragged(const Parafac2Ragged &s, int tj, double *part) {
+    const TX *X = (const TX *)s.X;
+    hipLaunchKernelGGL((k_p2_project_ragged<TX, NT>), dim3((unsigned)s.tiles), dim3(256), p2_project_lds(s.R), st_, X,
+                       s.rows, s.roff, s.tile0, s.tile_slice, s.xoff, s.xcs, s.J, s.R, s.A, s.B, s.C, s.K, s.Q);
+    const size_t lds_polar = sizeof(double) * (2 * (size_t)s.R * (s.R + 1) + 64 + 18) + sizeof(int) * 64;
+    hipLaunchKernelGGL(k_p2_polar_ragged, dim3((unsigned)s.K), dim3(1024), lds_polar, st_, s.Q, s.rows, s.roff, s.R,
+                       s.min_ratio, s.T, s.status);
+    hipLaunchKernelGGL(k_p2_apply_ragged, dim3((unsigned)s.tiles), dim3(256),
+                       sizeof(double) * ((size_t)s.R * s.R + 64 * (size_t)s.R), st_, s.Q, s.T, s.status, s.rows, s.roff,
+                       s.tile0, s.tile_slice, s.R, s.P);
+    if (s.dt == F32)
+      hipLaunchKernelGGL((k_p2_compress_ragged<TX, float, NT>), dim3((unsigned)(tj * s.K)), dim3(256),
+                         p2_compress_lds(s.R), st_, X, s.rows, s.roff, s.xoff, s.xcs, s.J, s.R, s.P, tj, (float *)s.Y,
+                         part);
+    else
+      hipLaunchKernelGGL((k_p2_compress_ragged<TX, double, NT>), dim3((unsigned)(tj * s.K)), dim3(256),
+                         p2_compress_lds(s.R), st_, X, s.rows, s.roff, s.xoff, s.xcs, s.J, s.R, s.P, tj, (double *)s.Y,
+                         part);
+  }
+  void parafac2_step_ragged(const Parafac2Ragged &s, void *caller_stream) override {
+    HIP_CHECK(hipSetDevice(dev_));
+    if (s.R < 2 || s.R > 64 || s.J < s.R || s.K < 1 || s.tiles < s.K)
+      throw std::runtime_error("ppals: parafac2_step_ragged needs 2 <= R <= min(64, J), K >= 1 and rows[k] >= 1");
+    if ((s.dt != F32 && s.dt != F64) || (s.vdt != DV_F32 && s.vdt != DV_F64))
+      throw std::runtime_error("ppals: parafac2_step_ragged stores F32 or F64 and reads an F32 or F64 view");
+    const int64_t tj = (s.J + P2_TILE - 1) / P2_TILE;
+    if (s.tiles > 0x7fffffff || tj * s.K > 0x3fffffff)
+      throw std::runtime_error("ppals: parafac2_step_ragged: too many tiles");
+    const int64_t npart = tj * s.K;
+    double *part = (double *)ensure(ws_part_, ws_part_sz_, sizeof(double) * 2 * npart);
+    const int nt = (s.R + 15) / 16;
+    route("parafac2.step_ragged.%s.%s R=%d nt=%d tiles=%d,%d lds=%zu,%zu", s.dt == F32 ? "f32" : "f64",
+          s.vdt == DV_F32 ? "f32" : "f64", s.R, nt, (int)s.tiles, (int)(tj * s.K), p2_project_lds(s.R),
+          p2_compress_lds(s.R));
+    join_stream(caller_stream);
+    dispatch<1, 2, 3, 4>(nt, [&](auto NT) {
+      if (s.vdt == DV_F32)
+        p2_launch_ragged<float, NT()>(s, (int)tj, part);
+      else
+        p2_launch_ragged<double, NT()>(s, (int)tj, part);
+    });
+    HIP_CHECK(hipGetLastError());
+    release_stream(caller_stream);
     if (s.out) {
       hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(1024), 0, st_, part, (int)npart, s.out);
       hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(1024), 0, st_, part + npart, (int)npart, s.out + 1);

@@ -5,6 +5,11 @@
 //   k_p2_apply      P_k = Q_k T_k where status[k] is 1
 //   k_p2_compress   Y_k = P_k^T X_k                        one pass over X, contraction over i
 //   k_p2_failed     the number of slices whose status is 0
+// The ragged twins (k_p2_*_ragged, Ops::parafac2_step_ragged) run the same bodies on slices of unequal length:
+// slice k has rows[k] rows, X_k[i, j] = X[xoff[k] + i + xcs[k] j], Q_k and P_k are column-major with leading
+// dimension rows[k] at R roff[k], roff the prefix sum of rows. The grid of pass 1 and of the apply is the total
+// number of row tiles, the slice slowest; a workgroup reads its slice from tile_slice[blockIdx.x] and its tile
+// within the slice from tile0[slice], once, before its first chunk (one value per workgroup: scalar loads).
 // The two passes over X widen its elements to fp64 and contract on v_mfma_f64_16x16x4_f64 with the operand
 // maps of kernels_model.hip.h / kernels_fms.hip.h: A operand a[m = lane & 15][k = lane >> 4], B operand
 // b[k = lane >> 4][n = lane & 15], D at (m = (lane >> 4) + 4 reg, n = lane & 15). The rank is padded to
@@ -38,14 +43,14 @@ __host__ __device__ inline size_t p2_compress_lds(int R) {
 // rows [16 w, 16 w + 16) of the tile and NT accumulators G[16 rows][16 t ..]; X is read once, 64 consecutive i per
 // wave load. The epilogue multiplies the
 // 64 x R tile of G = X_k A by Mk = diag(C[k, :]) B^T (Mk[r][s] = C[k, r] B[s, r]) from LDS and stores
-// Q[i + I s + I R k].
+// Qk[i + I s] (k_p2_project: Qk = Q + I R k). The body serves both kernels; k, i0, Xk, s1 and I are one value
+// per workgroup.
 // dynamic LDS (p2_project_lds): Xs[32][80] | As[32][80], then G[64][16 NT + 1] in their place | Mk[R][R]
 template <typename TX, int NT>
-__global__ __launch_bounds__(256) void k_p2_project(const TX *__restrict__ X, int64_t s1, int64_t s2, int64_t I,
-                                                    int64_t J, int R, const double *__restrict__ A,
-                                                    const double *__restrict__ B, const double *__restrict__ C,
-                                                    int64_t K, int tiles, double *__restrict__ Q) {
-  extern __shared__ __attribute__((aligned(16))) double lds_p2[];
+__device__ __forceinline__ void p2_project_body(const TX *__restrict__ Xk, int64_t s1, int64_t I, int64_t J, int R,
+                                                const double *__restrict__ A, const double *__restrict__ B,
+                                                const double *__restrict__ C, int64_t K, int64_t k, int64_t i0,
+                                                double *__restrict__ Qk, double *lds_p2) {
   constexpr int RP = 16 * NT;
   const size_t stage = 2 * (size_t)P2_CH * P2_LDX, gsz = (size_t)P2_TILE * (RP + 1);
   double *Xs = lds_p2;
@@ -53,8 +58,6 @@ __global__ __launch_bounds__(256) void k_p2_project(const TX *__restrict__ X, in
   double *Gs = lds_p2;
   double *Mk = lds_p2 + (stage > gsz ? stage : gsz);
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, g4 = lane >> 4;
-  const int64_t k = blockIdx.x / tiles, i0 = (int64_t)(blockIdx.x % tiles) * P2_TILE;
-  const TX *__restrict__ Xk = X + s2 * k;
   for (int e = tid; e < R * R; e += 256) {
     const int r = e % R, s = e / R;
     Mk[e] = C[k + K * r] * B[s + (int64_t)R * r];
@@ -92,7 +95,6 @@ __global__ __launch_bounds__(256) void k_p2_project(const TX *__restrict__ X, in
     for (int reg = 0; reg < 4; reg++) Gs[(16 * wave + g4 + 4 * reg) * (RP + 1) + 16 * t + l16] = acc[t][reg];
   __syncthreads();
   if (xi < I) {
-    double *__restrict__ Qk = Q + I * (int64_t)R * k;
     for (int s = wave; s < R; s += 4) {
       const double *mk = Mk + (size_t)R * s;
       double v = 0;
@@ -100,6 +102,26 @@ __global__ __launch_bounds__(256) void k_p2_project(const TX *__restrict__ X, in
       Qk[xi + I * s] = v;
     }
   }
+}
+template <typename TX, int NT>
+__global__ __launch_bounds__(256) void k_p2_project(const TX *__restrict__ X, int64_t s1, int64_t s2, int64_t I,
+                                                    int64_t J, int R, const double *__restrict__ A,
+                                                    const double *__restrict__ B, const double *__restrict__ C,
+                                                    int64_t K, int tiles, double *__restrict__ Q) {
+  extern __shared__ __attribute__((aligned(16))) double lds_p2[];
+  const int64_t k = blockIdx.x / tiles, i0 = (int64_t)(blockIdx.x % tiles) * P2_TILE;
+  p2_project_body<TX, NT>(X + s2 * k, s1, I, J, R, A, B, C, K, k, i0, Q + I * (int64_t)R * k, lds_p2);
+}
+// the ragged twin: grid = the total number of row tiles
+template <typename TX, int NT>
+__global__ __launch_bounds__(256) void k_p2_project_ragged(
+    const TX *__restrict__ X, const int64_t *__restrict__ rows, const int64_t *__restrict__ roff,
+    const int *__restrict__ tile0, const int *__restrict__ tile_slice, const int64_t *__restrict__ xoff,
+    const int64_t *__restrict__ xcs, int64_t J, int R, const double *__restrict__ A, const double *__restrict__ B,
+    const double *__restrict__ C, int64_t K, double *__restrict__ Q) {
+  extern __shared__ __attribute__((aligned(16))) double lds_p2[];
+  const int64_t k = tile_slice[blockIdx.x], i0 = (int64_t)((int)blockIdx.x - tile0[k]) * P2_TILE;
+  p2_project_body<TX, NT>(X + xoff[k], xcs[k], rows[k], J, R, A, B, C, K, k, i0, Q + (int64_t)R * roff[k], lds_p2);
 }
 
 // The slice polar factors: workgroup k runs polar_factor_body on Q_k (I rows, leading dimension I) and writes
@@ -110,30 +132,54 @@ __global__ __launch_bounds__(1024) void k_p2_polar(const double *__restrict__ Q,
   const int64_t k = blockIdx.x;
   polar_factor_body(Q + I * (int64_t)R * k, I, I, R, min_ratio, T + (int64_t)R * R * k, status + k, lds);
 }
+__global__ __launch_bounds__(1024) void k_p2_polar_ragged(const double *__restrict__ Q,
+                                                          const int64_t *__restrict__ rows,
+                                                          const int64_t *__restrict__ roff, int R, double min_ratio,
+                                                          double *__restrict__ T, int *__restrict__ status) {
+  extern __shared__ double lds[];
+  const int64_t k = blockIdx.x, I = rows[k];
+  polar_factor_body(Q + (int64_t)R * roff[k], I, I, R, min_ratio, T + (int64_t)R * R * k, status + k, lds);
+}
 
 // P_k = Q_k T_k for the slices whose status is 1; grid ceil(I / 64) x K as k_p2_project, 256 threads, a thread one
 // row and every fourth column. dynamic LDS: T[R][R] | Q tile [R][64]
-__global__ __launch_bounds__(256) void k_p2_apply(const double *__restrict__ Q, const double *__restrict__ T,
-                                                  const int *__restrict__ status, int64_t I, int R, int tiles,
-                                                  double *__restrict__ P) {
-  extern __shared__ double lds[];
-  const int64_t k = blockIdx.x / tiles;
-  if (!status[k]) return;  // (one value per slice: uniform over the workgroup)
+__device__ __forceinline__ void p2_apply_body(const double *__restrict__ Qk, const double *__restrict__ Tk,
+                                              int64_t I, int R, int64_t i0, double *__restrict__ Pk, double *lds) {
   double *sT = lds, *sQ = lds + R * R;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int64_t x = (int64_t)(blockIdx.x % tiles) * 64 + lane;
-  const double *__restrict__ Qk = Q + I * (int64_t)R * k;
-  for (int e = tid; e < R * R; e += 256) sT[e] = T[(int64_t)R * R * k + e];
+  const int64_t x = i0 + lane;
+  for (int e = tid; e < R * R; e += 256) sT[e] = Tk[e];
   for (int q = wave; q < R; q += 4) sQ[q * 64 + lane] = x < I ? Qk[x + I * q] : 0.0;
   __syncthreads();
   if (x >= I) return;
-  double *__restrict__ Pk = P + I * (int64_t)R * k;
   for (int s = wave; s < R; s += 4) {
     const double *tc = sT + R * s;
     double v = 0;
     for (int q = 0; q < R; q++) v += sQ[q * 64 + lane] * tc[q];
     Pk[x + I * s] = v;
   }
+}
+__global__ __launch_bounds__(256) void k_p2_apply(const double *__restrict__ Q, const double *__restrict__ T,
+                                                  const int *__restrict__ status, int64_t I, int R, int tiles,
+                                                  double *__restrict__ P) {
+  extern __shared__ double lds[];
+  const int64_t k = blockIdx.x / tiles;
+  if (!status[k]) return;  // (one value per slice: uniform over the workgroup)
+  p2_apply_body(Q + I * (int64_t)R * k, T + (int64_t)R * R * k, I, R, (int64_t)(blockIdx.x % tiles) * 64,
+                P + I * (int64_t)R * k, lds);
+}
+__global__ __launch_bounds__(256) void k_p2_apply_ragged(const double *__restrict__ Q, const double *__restrict__ T,
+                                                         const int *__restrict__ status,
+                                                         const int64_t *__restrict__ rows,
+                                                         const int64_t *__restrict__ roff,
+                                                         const int *__restrict__ tile0,
+                                                         const int *__restrict__ tile_slice, int R,
+                                                         double *__restrict__ P) {
+  extern __shared__ double lds[];
+  const int64_t k = tile_slice[blockIdx.x];
+  if (!status[k]) return;
+  const int64_t o = (int64_t)R * roff[k];
+  p2_apply_body(Q + o, T + (int64_t)R * R * k, rows[k], R, (int64_t)((int)blockIdx.x - tile0[k]) * 64, P + o, lds);
 }
 
 // Pass 2. Grid ceil(J / 64) x K (`tiles` column tiles per slice, the slice slowest), 256 threads. Wave w owns the
@@ -143,18 +189,14 @@ __global__ __launch_bounds__(256) void k_p2_apply(const double *__restrict__ Q, 
 // and of the fp64 Y entries it holds; part[g] and part[gridDim.x + g], g = blockIdx.x, are the workgroup's sums.
 // dynamic LDS (p2_compress_lds): Xs[64][36] | Ps[16 NT][36] | 17 doubles of block_sum
 template <typename TX, typename TY, int NT>
-__global__ __launch_bounds__(256) void k_p2_compress(const TX *__restrict__ X, int64_t s1, int64_t s2, int64_t I,
-                                                     int64_t J, int R, const double *__restrict__ P, int tiles,
-                                                     TY *__restrict__ Y, double *__restrict__ part) {
-  extern __shared__ __attribute__((aligned(16))) double lds_p2[];
+__device__ __forceinline__ void p2_compress_body(const TX *__restrict__ Xk, int64_t s1, int64_t I, int64_t J, int R,
+                                                 const double *__restrict__ Pk, int64_t k, int64_t j0,
+                                                 TY *__restrict__ Y, double *__restrict__ part, double *lds_p2) {
   constexpr int RP = 16 * NT;
   double *Xs = lds_p2;
   double *Ps = Xs + P2_TILE * P2_LDC;
   double *red = Ps + RP * P2_LDC;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l16 = lane & 15, g4 = lane >> 4;
-  const int64_t k = blockIdx.x / tiles, j0 = (int64_t)(blockIdx.x % tiles) * P2_TILE;
-  const TX *__restrict__ Xk = X + s2 * k;
-  const double *__restrict__ Pk = P + I * (int64_t)R * k;
   f64x4 acc[NT];
 #pragma unroll
   for (int t = 0; t < NT; t++) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
@@ -203,6 +245,27 @@ __global__ __launch_bounds__(256) void k_p2_compress(const TX *__restrict__ X, i
     part[(int64_t)gridDim.x + blockIdx.x] = sy;
   }
 }
+template <typename TX, typename TY, int NT>
+__global__ __launch_bounds__(256) void k_p2_compress(const TX *__restrict__ X, int64_t s1, int64_t s2, int64_t I,
+                                                     int64_t J, int R, const double *__restrict__ P, int tiles,
+                                                     TY *__restrict__ Y, double *__restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) double lds_p2[];
+  const int64_t k = blockIdx.x / tiles, j0 = (int64_t)(blockIdx.x % tiles) * P2_TILE;
+  p2_compress_body<TX, TY, NT>(X + s2 * k, s1, I, J, R, P + I * (int64_t)R * k, k, j0, Y, part, lds_p2);
+}
+// the ragged twin: the same grid, the contraction of slice k runs to rows[k]
+template <typename TX, typename TY, int NT>
+__global__ __launch_bounds__(256) void k_p2_compress_ragged(const TX *__restrict__ X,
+                                                            const int64_t *__restrict__ rows,
+                                                            const int64_t *__restrict__ roff,
+                                                            const int64_t *__restrict__ xoff,
+                                                            const int64_t *__restrict__ xcs, int64_t J, int R,
+                                                            const double *__restrict__ P, int tiles,
+                                                            TY *__restrict__ Y, double *__restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) double lds_p2[];
+  const int64_t k = blockIdx.x / tiles, j0 = (int64_t)(blockIdx.x % tiles) * P2_TILE;
+  p2_compress_body<TX, TY, NT>(X + xoff[k], xcs[k], rows[k], J, R, P + (int64_t)R * roff[k], k, j0, Y, part, lds_p2);
+}
 
 // the number of slices that kept their projection, as a double beside the two sums
 __global__ __launch_bounds__(1024) void k_p2_failed(const int *__restrict__ status, int64_t K,
@@ -221,6 +284,19 @@ __global__ void k_p2_init(double *__restrict__ P, int64_t I, int R, int64_t K) {
     const int64_t i = e % I, r = (e / I) % R;
     P[e] = i == r ? 1.0 : 0.0;
   }
+}
+
+// the same in every rows[k] x R slice of a ragged P: grid = the total number of row tiles, 256 threads
+__global__ __launch_bounds__(256) void k_p2_init_ragged(double *__restrict__ P, const int64_t *__restrict__ rows,
+                                                        const int64_t *__restrict__ roff,
+                                                        const int *__restrict__ tile0,
+                                                        const int *__restrict__ tile_slice, int R) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t k = tile_slice[blockIdx.x], I = rows[k];
+  const int64_t x = (int64_t)((int)blockIdx.x - tile0[k]) * 64 + lane;
+  if (x >= I) return;
+  double *__restrict__ Pk = P + (int64_t)R * roff[k];
+  for (int s = wave; s < R; s += 4) Pk[x + I * s] = x == s ? 1.0 : 0.0;
 }
 
 }  // namespace ppals

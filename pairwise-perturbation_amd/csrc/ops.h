@@ -328,6 +328,38 @@ class Ops {
   virtual void parafac2_step(const Parafac2Step & /*s*/, void * /*caller_stream*/) {
     throw Unsupported("ppals: this back end has no device views");
   }
+  // The same step on K slices of unequal length (ppals_parafac2_*_ragged): slice k is rows[k] x J with
+  // rows[k] >= R, X_k[i, j] = X[xoff[k] + i + xcs[k] j]. With roff[k] = sum_{l<k} rows[l] and N = roff[K],
+  // Q_k and P_k are column-major with leading dimension rows[k] at Q + R roff[k] and P + R roff[k] (R N doubles
+  // each); T, status, Y and out are those of parafac2_step. The tables are DEVICE arrays the caller fills once:
+  // rows, roff, xoff, xcs of K int64 each; tile0[k] = sum_{l<k} ceil(rows[l] / 64), K ints; tile_slice[t] = the
+  // slice of row tile t, `tiles` = tile0[K] ints. The first pass and the apply run one workgroup per row tile, the
+  // slice slowest, so the number of launches (seven) depends on nothing. The summation orders are those of
+  // parafac2_step: equal rows on the dense layout give its bits. parafac2_init_ragged writes the first R identity
+  // columns into every P_k.
+  struct Parafac2Ragged {
+    int64_t J = 0, K = 0;
+    int R = 0;
+    int64_t tiles = 0;  // row tiles over all slices
+    const int64_t *rows = nullptr, *roff = nullptr;
+    const int *tile0 = nullptr, *tile_slice = nullptr;
+    const void *X = nullptr;
+    int vdt = 0;  // DV_F32 or DV_F64
+    const int64_t *xoff = nullptr, *xcs = nullptr;
+    const double *B = nullptr, *A = nullptr, *C = nullptr;
+    double *Q = nullptr, *P = nullptr, *T = nullptr;
+    int *status = nullptr;
+    double min_ratio = 0;
+    void *Y = nullptr;
+    int dt = 0;
+    double *out = nullptr;
+  };
+  virtual void parafac2_init_ragged(const Parafac2Ragged & /*s*/) {
+    throw Unsupported("ppals: this back end has no device views");
+  }
+  virtual void parafac2_step_ragged(const Parafac2Ragged & /*s*/, void * /*caller_stream*/) {
+    throw Unsupported("ppals: this back end has no device views");
+  }
 
   // Order work on the engine stream against a caller's stream, as copy_view does it: join_stream makes the
   // work queued on the engine stream from now on wait for what `caller_stream` holds so far, release_stream

@@ -67,6 +67,14 @@ struct ppals_parafac2 {
   ppals_cp *cp;
   DeviceBuffer P, Q, T, out;  // I x R x K twice, R x R x K, 3 doubles
   DeviceBuffer status;        // K ints
+  // slices of unequal length (ppals_parafac2_create_ragged): I is 0, slice k has rows[k] rows, roff is their
+  // prefix sum (K + 1 entries, roff[K] = N), P and Q hold R N doubles with P_k at R roff[k]
+  bool ragged = false;
+  std::vector<int64_t> rows, roff;
+  int64_t tiles = 0;             // sum of ceil(rows[k] / 64)
+  DeviceBuffer tab;              // rows[K] | roff[K] (int64), then tile0[K] | tile_slice[tiles] (int)
+  DeviceBuffer xv;               // the view of the last step: offsets[K] | col_strides[K] (int64)
+  std::vector<int64_t> xv_host;  // what xv holds (empty before the first step)
 };
 
 #define API_BEGIN try {
@@ -116,7 +124,7 @@ int ppals_ctx_create(ppals_ctx **out, int device) {
   API_END(PPALS_ERR_NO_DEVICE)
 }
 static void p2_free_buffers(ppals_parafac2 *p) {
-  for (DeviceBuffer *b : {&p->P, &p->Q, &p->T, &p->out, &p->status}) {
+  for (DeviceBuffer *b : {&p->P, &p->Q, &p->T, &p->out, &p->status, &p->tab, &p->xv}) {
     try {
       b->reset();
     } catch (...) {
@@ -1194,14 +1202,8 @@ int ppals_cp_abs_residual_quantile(ppals_cp *s, const void *data, const void *we
 }
 
 // ------------------------------------------------------------------ PARAFAC2
-int ppals_parafac2_create(ppals_ctx *ctx, int64_t I, int64_t J, int64_t K, int R, int storage_dtype,
-                          ppals_parafac2 **out) {
-  const char *fn = "ppals_parafac2_create";
-  if (!ctx || !out) return fail_fn(PPALS_ERR_ARG, fn, "NULL argument");
-  *out = nullptr;
-  if (I < 1 || J < 1 || K < 1) return fail_fn(PPALS_ERR_ARG, fn, "the extents I, J, K must be positive");
-  if (R < 2 || R > 64) return fail_fn(PPALS_ERR_ARG, fn, "the rank must lie in [2, 64]");
-  if (R > I || R > J) return fail_fn(PPALS_ERR_ARG, fn, "the rank must not exceed min(I, J)");
+// the refusals both kinds of object share, after the extents: dtype, BF16, more than one rank
+static int p2_check_create(ppals_ctx *ctx, const char *fn, int storage_dtype) {
   if (storage_dtype != PPALS_F32 && storage_dtype != PPALS_F64 && storage_dtype != PPALS_BF16)
     return fail_fn(PPALS_ERR_ARG, fn, "bad storage dtype");
   if (storage_dtype == PPALS_BF16)
@@ -1212,11 +1214,12 @@ int ppals_parafac2_create(ppals_ctx *ctx, int64_t I, int64_t J, int64_t K, int R
     return fail_fn(PPALS_ERR_UNSUPPORTED, fn,
                    "a context of more than one rank is not supported (the compressed tensor's leading mode is the "
                    "rank R and cannot be sharded usefully)");
-  API_BEGIN
-  ctx->ops->parafac2_check();  // a back end without device views refuses here, nothing allocated
-  std::unique_ptr<ppals_parafac2> p(new ppals_parafac2());
-  p->ctx = ctx;
-  p->I = I, p->J = J, p->K = K, p->R = R;
+  return PPALS_OK;
+}
+// Y, the inner session and its initial factors; on failure nothing is left behind
+static int p2_create_inner(ppals_ctx *ctx, ppals_parafac2 *p, int storage_dtype) {
+  const int R = p->R;
+  const int64_t J = p->J, K = p->K;
   const int64_t lens[3] = {R, J, K};
   int rc = ppals_tensor_create(ctx, 3, lens, storage_dtype, &p->Y);
   if (rc == PPALS_OK) {
@@ -1233,18 +1236,50 @@ int ppals_parafac2_create(ppals_ctx *ctx, int64_t I, int64_t J, int64_t K, int R
   if (rc != PPALS_OK) {
     ppals_cp_destroy(p->cp);
     ppals_tensor_destroy(p->Y);
-    return rc;
   }
+  return rc;
+}
+// the buffers every object has but P and Q: T, out, status (zeroed)
+static void p2_alloc_small(ppals_ctx *ctx, ppals_parafac2 *q) {
+  q->T = DeviceBuffer(*ctx->ops, sizeof(double) * (size_t)q->R * q->R * q->K);
+  q->out = DeviceBuffer(*ctx->ops, sizeof(double) * 3);
+  q->status = DeviceBuffer(*ctx->ops, sizeof(int) * (size_t)q->K);
+  ctx->ops->zero(q->status.get(), sizeof(int) * (size_t)q->K);
+}
+// the ragged step's description but for the view and `out`
+static void p2_ragged_desc(ppals_parafac2 *p, Ops::Parafac2Ragged *out) {
+  Ops::Parafac2Ragged s;
+  s.J = p->J, s.K = p->K, s.R = p->R, s.tiles = p->tiles;
+  s.rows = p->tab.as<int64_t>(), s.roff = s.rows + p->K;
+  s.tile0 = (const int *)(s.roff + p->K), s.tile_slice = s.tile0 + p->K;
+  s.xoff = p->xv.as<int64_t>(), s.xcs = s.xoff + p->K;
+  s.Q = p->Q.as<double>(), s.P = p->P.as<double>(), s.T = p->T.as<double>(), s.status = p->status.as<int>();
+  s.min_ratio = PPALS_ORTHO_MIN_RATIO;
+  s.Y = p->Y->d.data, s.dt = p->Y->d.dtype;
+  *out = s;
+}
+int ppals_parafac2_create(ppals_ctx *ctx, int64_t I, int64_t J, int64_t K, int R, int storage_dtype,
+                          ppals_parafac2 **out) {
+  const char *fn = "ppals_parafac2_create";
+  if (!ctx || !out) return fail_fn(PPALS_ERR_ARG, fn, "NULL argument");
+  *out = nullptr;
+  if (I < 1 || J < 1 || K < 1) return fail_fn(PPALS_ERR_ARG, fn, "the extents I, J, K must be positive");
+  if (R < 2 || R > 64) return fail_fn(PPALS_ERR_ARG, fn, "the rank must lie in [2, 64]");
+  if (R > I || R > J) return fail_fn(PPALS_ERR_ARG, fn, "the rank must not exceed min(I, J)");
+  if (const int rc = p2_check_create(ctx, fn, storage_dtype)) return rc;
+  API_BEGIN
+  ctx->ops->parafac2_check();  // a back end without device views refuses here, nothing allocated
+  std::unique_ptr<ppals_parafac2> p(new ppals_parafac2());
+  p->ctx = ctx;
+  p->I = I, p->J = J, p->K = K, p->R = R;
+  if (const int rc = p2_create_inner(ctx, p.get(), storage_dtype)) return rc;
   ctx->p2s.insert(p.get());  // from here on ppals_parafac2_destroy undoes everything
   ppals_parafac2 *q = p.release();
   try {
     const size_t n = sizeof(double) * (size_t)I * R * K;
     q->P = DeviceBuffer(*ctx->ops, n);
     q->Q = DeviceBuffer(*ctx->ops, n);
-    q->T = DeviceBuffer(*ctx->ops, sizeof(double) * (size_t)R * R * K);
-    q->out = DeviceBuffer(*ctx->ops, sizeof(double) * 3);
-    q->status = DeviceBuffer(*ctx->ops, sizeof(int) * (size_t)K);
-    ctx->ops->zero(q->status.get(), sizeof(int) * (size_t)K);
+    p2_alloc_small(ctx, q);
     ctx->ops->parafac2_init(q->P.as<double>(), I, R, K);
   } catch (...) {
     ppals_parafac2_destroy(q);
@@ -1253,6 +1288,75 @@ int ppals_parafac2_create(ppals_ctx *ctx, int64_t I, int64_t J, int64_t K, int R
   *out = q;
   return PPALS_OK;
   API_END(PPALS_ERR_HIP)
+}
+int ppals_parafac2_create_ragged(ppals_ctx *ctx, int64_t K, const int64_t *rows, int64_t J, int R, int storage_dtype,
+                                 ppals_parafac2 **out) {
+  const char *fn = "ppals_parafac2_create_ragged";
+  if (!ctx || !out) return fail_fn(PPALS_ERR_ARG, fn, "NULL argument");
+  *out = nullptr;
+  if (!rows) return fail_fn(PPALS_ERR_ARG, fn, "rows is NULL");
+  if (K < 1 || J < 1) return fail_fn(PPALS_ERR_ARG, fn, "the number of slices K and the extent J must be positive");
+  if (R < 2 || R > 64) return fail_fn(PPALS_ERR_ARG, fn, "the rank must lie in [2, 64]");
+  if (R > J) return fail_fn(PPALS_ERR_ARG, fn, "the rank must not exceed J");
+  int64_t N = 0, tiles = 0, bytes = 0;
+  for (int64_t k = 0; k < K; k++) {
+    if (rows[k] < R)
+      return fail_fn(PPALS_ERR_ARG, fn,
+                     ("slice " + std::to_string(k) + " has " + std::to_string(rows[k]) +
+                      " rows, fewer than the rank " + std::to_string(R))
+                         .c_str());
+    if (!dv_add(N, rows[k], &N)) return fail_fn(PPALS_ERR_ARG, fn, "the total number of rows overflows int64");
+    tiles += (rows[k] - 1) / 64 + 1;  // (at most N: no overflow)
+  }
+  if (!dv_mul(N, (int64_t)sizeof(double) * R, &bytes))
+    return fail_fn(PPALS_ERR_ARG, fn, "the projections' size overflows int64");
+  if (tiles > 0x7fffffff) return fail_fn(PPALS_ERR_ARG, fn, "too many row tiles (the sum of ceil(rows[k] / 64))");
+  if (const int rc = p2_check_create(ctx, fn, storage_dtype)) return rc;
+  API_BEGIN
+  ctx->ops->parafac2_check();  // a back end without device views refuses here, nothing allocated
+  std::unique_ptr<ppals_parafac2> p(new ppals_parafac2());
+  p->ctx = ctx;
+  p->I = 0, p->J = J, p->K = K, p->R = R;
+  p->ragged = true;
+  p->tiles = tiles;
+  p->rows.assign(rows, rows + K);
+  p->roff.assign((size_t)K + 1, 0);
+  // the device tables as one host image: rows | roff (int64), tile0 | tile_slice (int)
+  std::vector<int64_t> img((size_t)(2 * K) + (size_t)((K + tiles + 1) / 2), 0);
+  int *tile0 = (int *)(img.data() + 2 * K), *tile_slice = tile0 + K;
+  int t = 0;
+  for (int64_t k = 0; k < K; k++) {
+    p->roff[(size_t)k + 1] = p->roff[(size_t)k] + rows[k];
+    img[(size_t)k] = rows[k], img[(size_t)(K + k)] = p->roff[(size_t)k];
+    tile0[k] = t;
+    for (int64_t i = 0; i < rows[k]; i += 64) tile_slice[t++] = (int)k;
+  }
+  if (const int rc = p2_create_inner(ctx, p.get(), storage_dtype)) return rc;
+  ctx->p2s.insert(p.get());  // from here on ppals_parafac2_destroy undoes everything
+  ppals_parafac2 *q = p.release();
+  try {
+    q->P = DeviceBuffer(*ctx->ops, (size_t)bytes);
+    q->Q = DeviceBuffer(*ctx->ops, (size_t)bytes);
+    p2_alloc_small(ctx, q);
+    q->tab = DeviceBuffer(*ctx->ops, sizeof(int64_t) * img.size());
+    q->xv = DeviceBuffer(*ctx->ops, sizeof(int64_t) * 2 * (size_t)K);
+    ctx->ops->h2d(q->tab.get(), img.data(), sizeof(int64_t) * img.size());
+    Ops::Parafac2Ragged d;
+    p2_ragged_desc(q, &d);
+    ctx->ops->parafac2_init_ragged(d);
+  } catch (...) {
+    ppals_parafac2_destroy(q);
+    throw;
+  }
+  *out = q;
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_parafac2_rows(ppals_parafac2 *p, int64_t *rows, int64_t *total) {
+  if (!p || !p->ctx || !rows) return fail(PPALS_ERR_ARG, "ppals_parafac2_rows: NULL argument or dead handle");
+  for (int64_t k = 0; k < p->K; k++) rows[k] = p->ragged ? p->rows[(size_t)k] : p->I;
+  if (total) *total = p->ragged ? p->roff[(size_t)p->K] : p->I * p->K;
+  return PPALS_OK;
 }
 void ppals_parafac2_destroy(ppals_parafac2 *p) {
   if (!p) return;
@@ -1271,6 +1375,10 @@ ppals_tensor *ppals_parafac2_tensor(ppals_parafac2 *p) { return p && p->ctx ? p-
 static int p2_check_step(ppals_parafac2 *p, const char *fn, const void *data, int dtype, const int64_t *strides,
                          Ops::Parafac2Step *st) {
   if (!p || !p->ctx || !p->cp || !p->cp->eng) return fail_fn(PPALS_ERR_ARG, fn, "NULL or dead handle");
+  if (p->ragged)
+    return fail_fn(PPALS_ERR_ARG, fn,
+                   "the object holds slices of unequal length (ppals_parafac2_create_ragged): use "
+                   "ppals_parafac2_step_ragged_device / ppals_parafac2_run_ragged");
   if (!data) return fail_fn(PPALS_ERR_ARG, fn, "the data pointer is NULL");
   if (dtype != PPALS_F32 && dtype != PPALS_F64)
     return fail_fn(PPALS_ERR_ARG, fn, "bad dtype of the data view (PPALS_F32 or PPALS_F64)");
@@ -1343,10 +1451,118 @@ int ppals_parafac2_run(ppals_parafac2 *p, const void *data, int dtype, const int
       to_opts(o), inner_sweeps, rel_change, iters, res);
   API_END(PPALS_ERR_HIP)
 }
+// every check of a ragged step, nothing launched, copied or allocated: on success *xv holds the resolved view
+// (offsets | column strides) and *st is ready but for `out`
+static int p2_check_step_ragged(ppals_parafac2 *p, const char *fn, const void *data, int dtype,
+                                const int64_t *offsets, const int64_t *col_strides, Ops::Parafac2Ragged *st,
+                                std::vector<int64_t> *xv) {
+  if (!p || !p->ctx || !p->cp || !p->cp->eng) return fail_fn(PPALS_ERR_ARG, fn, "NULL or dead handle");
+  if (!p->ragged)
+    return fail_fn(PPALS_ERR_ARG, fn,
+                   "the object holds slices of one length (ppals_parafac2_create): use ppals_parafac2_step_device / "
+                   "ppals_parafac2_run");
+  if (!data) return fail_fn(PPALS_ERR_ARG, fn, "the data pointer is NULL");
+  if (dtype != PPALS_F32 && dtype != PPALS_F64)
+    return fail_fn(PPALS_ERR_ARG, fn, "bad dtype of the data view (PPALS_F32 or PPALS_F64)");
+  if (p->cp->eng->mode_kind(0) != ppals::kModeFree)
+    return fail_fn(PPALS_ERR_ARG, fn, "mode 0 of the inner session (B) must stay PPALS_MODE_FREE");
+  const int64_t K = p->K, J = p->J;
+  xv->resize(2 * (size_t)K);
+  int64_t lo = INT64_MAX, hi = 0;  // the first and the last element any slice reads
+  for (int64_t k = 0; k < K; k++) {
+    const int64_t rows = p->rows[(size_t)k];
+    int64_t off, cs = col_strides ? col_strides[k] : rows, last;
+    if (offsets)
+      off = offsets[k];
+    else if (!dv_mul(J, p->roff[(size_t)k], &off))
+      return fail_fn(PPALS_ERR_ARG, fn, "the packed offsets overflow int64");
+    if (off < 0) return fail_fn(PPALS_ERR_ARG, fn, ("offsets[" + std::to_string(k) + "] is negative").c_str());
+    if (cs < rows)
+      return fail_fn(PPALS_ERR_ARG, fn,
+                     ("col_strides[" + std::to_string(k) + "] = " + std::to_string(cs) + " is less than the slice's " +
+                      std::to_string(rows) + " rows")
+                         .c_str());
+    if (!dv_mul(cs, J - 1, &last) || !dv_add(last, rows - 1, &last) || !dv_add(last, off, &last))
+      return fail_fn(PPALS_ERR_ARG, fn, "the data view's span overflows int64");
+    lo = std::min(lo, off), hi = std::max(hi, last);
+    (*xv)[(size_t)k] = off, (*xv)[(size_t)(K + k)] = cs;
+  }
+  ViewArgs a;  // the union of the slices' spans as one view of hi - lo + 1 elements from data + lo
+  a.order = 1, a.dtype = dtype, a.esize = dv_elem_size(dtype);
+  a.lo[0] = 0, a.len[0] = hi - lo + 1, a.stride[0] = 1;
+  int64_t lo_bytes;
+  if (!dv_mul(a.len[0], a.esize, &a.span) || !dv_mul(lo, a.esize, &lo_bytes))
+    return fail_fn(PPALS_ERR_ARG, fn, "the data view's byte span overflows int64");
+  if ((uintptr_t)data % (uintptr_t)a.esize)
+    return fail_fn(PPALS_ERR_ARG, fn, "the data pointer is not aligned to its element size");
+  const int rc =
+      check_view_ptr(p->ctx, (std::string(fn) + ": the data view: ").c_str(), (const char *)data + lo_bytes, &a);
+  if (rc != PPALS_OK) return rc;
+  const CpEngine &e = *p->cp->eng;
+  p2_ragged_desc(p, st);
+  st->X = data, st->vdt = dtype;
+  st->B = e.factor_device(0), st->A = e.factor_device(1), st->C = e.factor_device(2);
+  return PPALS_OK;
+}
+// the view's tables travel only when they differ from the last step's (h2d is ordered behind that step)
+static void p2_step_ragged(ppals_parafac2 *p, Ops::Parafac2Ragged st, const std::vector<int64_t> &xv, void *stream,
+                           double *lost_sq, int *failed) {
+  if (xv != p->xv_host) {
+    p->xv_host.clear();  // (a failed copy leaves nothing believed)
+    p->ctx->ops->h2d(p->xv.get(), xv.data(), sizeof(int64_t) * xv.size());
+    p->xv_host = xv;
+  }
+  const bool want = lost_sq || failed;
+  st.out = want ? p->out.as<double>() : nullptr;
+  p->Y->generation++;  // the contents change with these launches: the session rebuilds what it derived
+  p->ctx->ops->parafac2_step_ragged(st, stream);
+  if (!want) return;
+  double o[3];
+  p->ctx->ops->d2h(o, p->out.as<double>(), sizeof(o));
+  if (lost_sq) *lost_sq = o[0] - o[1];
+  if (failed) *failed = (int)o[2];
+}
+int ppals_parafac2_step_ragged_device(ppals_parafac2 *p, const void *data, int dtype, const int64_t *offsets,
+                                      const int64_t *col_strides, void *stream, double *lost_sq, int *failed) {
+  API_BEGIN
+  Ops::Parafac2Ragged st;
+  std::vector<int64_t> xv;
+  const int rc = p2_check_step_ragged(p, "ppals_parafac2_step_ragged_device", data, dtype, offsets, col_strides, &st, &xv);
+  if (rc != PPALS_OK) return rc;
+  p2_step_ragged(p, st, xv, stream, lost_sq, failed);
+  return PPALS_OK;
+  API_END(PPALS_ERR_HIP)
+}
+int ppals_parafac2_run_ragged(ppals_parafac2 *p, const void *data, int dtype, const int64_t *offsets,
+                              const int64_t *col_strides, void *stream, const ppals_cp_opts *o, int inner_sweeps,
+                              double rel_change, int *iters, double *res) {
+  API_BEGIN
+  if (!o) return fail(PPALS_ERR_ARG, "ppals_parafac2_run_ragged: NULL options");
+  if (inner_sweeps < 1) return fail(PPALS_ERR_ARG, "ppals_parafac2_run_ragged: inner_sweeps must be at least 1");
+  if (!(rel_change >= 0)) return fail(PPALS_ERR_ARG, "ppals_parafac2_run_ragged: rel_change must not be negative");
+  if (o->maxiter < 0) return fail(PPALS_ERR_ARG, "ppals_parafac2_run_ragged: maxiter must not be negative");
+  Ops::Parafac2Ragged st;
+  std::vector<int64_t> xv;
+  const int rc = p2_check_step_ragged(p, "ppals_parafac2_run_ragged", data, dtype, offsets, col_strides, &st, &xv);
+  if (rc != PPALS_OK) return rc;
+  CpEngine *e = p->cp->eng;
+  return e->run_steps(
+      [&](double *sq) {
+        double lost = 0;
+        p2_step_ragged(p, st, xv, stream, sq ? &lost : nullptr, nullptr);
+        if (sq) {
+          const double r = e->residual();
+          *sq = std::max(lost, 0.0) + r * r;
+        }
+      },
+      to_opts(o), inner_sweeps, rel_change, iters, res);
+  API_END(PPALS_ERR_HIP)
+}
 int ppals_parafac2_projections(ppals_parafac2 *p, double *P_host) {
   if (!p || !p->ctx || !P_host) return fail(PPALS_ERR_ARG, "ppals_parafac2_projections: NULL argument or dead handle");
   API_BEGIN
-  p->ctx->ops->d2h(P_host, p->P.as<double>(), sizeof(double) * (size_t)p->I * p->R * p->K);
+  const size_t n = p->ragged ? (size_t)p->roff[(size_t)p->K] * p->R : (size_t)p->I * p->R * p->K;
+  p->ctx->ops->d2h(P_host, p->P.as<double>(), sizeof(double) * n);
   return PPALS_OK;
   API_END(PPALS_ERR_HIP)
 }

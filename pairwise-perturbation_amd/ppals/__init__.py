@@ -83,6 +83,8 @@ EXPORTS = [
     "ppals_parafac2_create", "ppals_parafac2_destroy", "ppals_parafac2_cp", "ppals_parafac2_tensor",
     "ppals_parafac2_step_device",
     "ppals_parafac2_run", "ppals_parafac2_projections", "ppals_parafac2_projections_device",
+    "ppals_parafac2_create_ragged", "ppals_parafac2_rows", "ppals_parafac2_step_ragged_device",
+    "ppals_parafac2_run_ragged",
     "ppals_npls_fit", "ppals_npls_destroy", "ppals_npls_dims", "ppals_npls_get", "ppals_npls_predict",
     "ppals_tensor_contract_mode", "ppals_tensor_slice_inner",
     "ppals_tensor_contract_columns", "ppals_tensor_slice_inner_columns", "ppals_npls_crossval",
@@ -1109,19 +1111,49 @@ class Parafac2:
     """PARAFAC2 by direct fitting (ppals_parafac2_*): X_k ~ P_k B diag(C[k, :]) A^T for the slices X_k = X[:, :, k]
     of an I x J x K torch tensor on the context's device, P_k^T P_k = I. `.cp` is the rank-R CP session on the
     compressed tensor (R x J x K; factors [B, A, C]): constraints, shapes, schedule and diagnostics are set there;
-    mode 0 (B) must stay free."""
+    mode 0 (B) must stay free.
+
+    Parafac2.ragged(ctx, rows, J, R) is the model on K = len(rows) slices of unequal length, slice k rows[k] x J
+    (`is_ragged`, `I` is None): step_torch / run / loss then take a list of K torch matrices or one flat buffer
+    with offsets and column strides, and projections() / profiles() return lists."""
 
     def __init__(self, ctx, I, J, K, R, dtype=F64):
         self.ctx, self.I, self.J, self.K, self.R, self.dtype = ctx, int(I), int(J), int(K), int(R), dtype
+        self.is_ragged = False
         self._h = C.c_void_p()
         _check(lib().ppals_parafac2_create(ctx._h, C.c_int64(self.I), C.c_int64(self.J), C.c_int64(self.K), self.R,
                                            int(dtype), C.byref(self._h)))
+        self._attach()
+
+    @classmethod
+    def ragged(cls, ctx, rows, J, R, dtype=F64):
+        """ppals_parafac2_create_ragged: slice k is rows[k] x J"""
+        self = cls.__new__(cls)
+        rows = [int(r) for r in rows]
+        self.ctx, self.I, self.J, self.K, self.R, self.dtype = ctx, None, int(J), len(rows), int(R), dtype
+        self.is_ragged = True
+        self._pack = None      # a list input's packed device copy: (key, the tensors, the buffer)
+        self._h = C.c_void_p()
+        _check(lib().ppals_parafac2_create_ragged(ctx._h, C.c_int64(self.K), (C.c_int64 * max(self.K, 1))(*rows),
+                                                  C.c_int64(self.J), self.R, int(dtype), C.byref(self._h)))
+        self._attach()
+        return self
+
+    def _attach(self):
+        ctx, dtype = self.ctx, self.dtype
         lib().ppals_parafac2_cp.restype = C.c_void_p
         self.cp = _BorrowedCP(self, C.c_void_p(lib().ppals_parafac2_cp(self._h)), [self.R, self.J, self.K], self.R)
         lib().ppals_parafac2_tensor.restype = C.c_void_p
         self.Y = _BorrowedTensor(self, C.c_void_p(lib().ppals_parafac2_tensor(self._h)), [self.R, self.J, self.K], dtype)
         self.cp.V = self.Y
         ctx._children.add(self)
+
+    @property
+    def rows(self):
+        """the slice lengths (ppals_parafac2_rows): I for every slice of an equal-length object"""
+        out = (C.c_int64 * self.K)()
+        _check(lib().ppals_parafac2_rows(self._h, out, None))
+        return [int(r) for r in out]
 
     def _view(self, X):
         torch = _torch()
@@ -1143,33 +1175,121 @@ class Parafac2:
                                                 C.byref(failed) if want else None))
         return (float(lost.value), int(failed.value)) if want else None
 
-    def step_torch(self, X, stream=None, want=True):
+    def _i64(self, v):
+        if v is None:
+            return None
+        v = [int(x) for x in v]
+        if len(v) != self.K:
+            raise PpalsError(f"{len(v)} entries for {self.K} slices")
+        return (C.c_int64 * self.K)(*v)
+
+    def step_slices_device(self, ptr, dtype, offsets=None, col_strides=None, stream=0, want=True):
+        """raw ppals_parafac2_step_ragged_device: X_k[i, j] = data[offsets[k] + i + col_strides[k] j] in elements
+        (offsets None: packed one after another; col_strides None: rows[k]). Returns (lost_sq, failed) if want
+        (the call then waits), else None."""
+        lost, failed = C.c_double(0), C.c_int(0)
+        _check(lib().ppals_parafac2_step_ragged_device(self._h, C.c_void_p(int(ptr)), int(dtype), self._i64(offsets),
+                                                       self._i64(col_strides), C.c_void_p(int(stream or 0)),
+                                                       C.byref(lost) if want else None,
+                                                       C.byref(failed) if want else None))
+        return (float(lost.value), int(failed.value)) if want else None
+
+    def _slices_view(self, X, offsets, col_strides, stream):
+        """a ragged object's input as (pointer, dtype code, offsets, col_strides): a flat 1-D torch buffer with its
+        offsets and column strides, or a list of K matrices rows[k] x J, packed (each slice column-major, one after
+        another) into a buffer the object keeps. The buffer is refilled, on `stream`, when the list holds other
+        tensors than last time or one of them has been written to since."""
+        torch = _torch()
+        if not isinstance(X, (list, tuple)):
+            if X.dim() != 1:
+                raise PpalsError(f"a ragged model takes a list of K matrices or a 1-D buffer, not shape {tuple(X.shape)}")
+            if X.stride(0) != 1:
+                raise PpalsError("the flat buffer needs unit stride")
+            self._check_torch(X)
+            return X.data_ptr(), (F64 if X.dtype == torch.float64 else F32), offsets, col_strides
+        if offsets is not None or col_strides is not None:
+            raise PpalsError("offsets and col_strides go with a flat buffer, not with a list of matrices")
+        rows = self.rows
+        if len(X) != self.K:
+            raise PpalsError(f"{len(X)} matrices for {self.K} slices")
+        for k, x in enumerate(X):
+            self._check_torch(x)
+            if tuple(x.shape) != (rows[k], self.J) or x.dtype != X[0].dtype:
+                raise PpalsError(f"slice {k} has shape {tuple(x.shape)} and dtype {x.dtype}, the model "
+                                 f"{(rows[k], self.J)} and the first slice {X[0].dtype}")
+        key = tuple((id(x), x.data_ptr(), x._version) for x in X)
+        if self._pack is None or self._pack[0] != key:
+            buf = self._pack[2] if self._pack is not None and self._pack[2].dtype == X[0].dtype else \
+                torch.empty(sum(rows) * self.J, dtype=X[0].dtype, device=X[0].device)
+            s = stream if stream is not None else torch.cuda.current_stream()
+            with torch.cuda.stream(s if hasattr(s, "cuda_stream") else torch.cuda.ExternalStream(int(s))):
+                o = 0
+                for k, x in enumerate(X):          # column-major rows[k] x J = row-major J x rows[k]
+                    buf[o:o + rows[k] * self.J].view(self.J, rows[k]).copy_(x.t())
+                    o += rows[k] * self.J
+            self._pack = (key, list(X), buf)       # (the tensors stay referenced: their ids stay theirs)
+        buf = self._pack[2]
+        return buf.data_ptr(), (F64 if buf.dtype == torch.float64 else F32), None, None
+
+    def _check_torch(self, X):
+        torch = _torch()
+        if X.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"the torch dtype {X.dtype} of X is not torch.float32 or torch.float64")
+        if X.device.type != "cuda" or X.device.index != self.ctx.device:
+            raise PpalsError(f"the torch tensor is on {X.device}, the context on cuda:{self.ctx.device}")
+
+    def step_torch(self, X, stream=None, want=True, offsets=None, col_strides=None):
         """one projection step from the session's current factors: new P_k where Q_k has a polar factor, Y = P^T X
         into the compressed tensor. X: float32 or float64 with X.stride(0) == 1 (e.g. made by
-        x.permute(2, 1, 0).contiguous().permute(2, 1, 0)). Returns (lost_sq, failed), or None if not want."""
+        x.permute(2, 1, 0).contiguous().permute(2, 1, 0)); on a ragged object a list of K matrices rows[k] x J, or
+        a flat 1-D buffer with `offsets` and `col_strides` (step_slices_device). Returns (lost_sq, failed), or None
+        if not want."""
+        if self.is_ragged:
+            ptr, code, off, cs = self._slices_view(X, offsets, col_strides, stream)
+            return self.step_slices_device(ptr, code, off, cs, Tensor._stream(stream), want)
         ptr, code, st = self._view(X)
         return self.step_device(ptr, code, st, Tensor._stream(stream), want)
 
-    def run(self, X, inner_sweeps=1, rel_change=0.0, stream=None, **opts):
-        """ppals_parafac2_run: repeat { step; inner_sweeps exact sweeps } with the looks and stop rules of
-        CP.run_wls. Returns (rc, iterations, ||X - model||)."""
-        ptr, code, st = self._view(X)
+    def run(self, X, inner_sweeps=1, rel_change=0.0, stream=None, offsets=None, col_strides=None, **opts):
+        """ppals_parafac2_run (ppals_parafac2_run_ragged on a ragged object, X as step_torch takes it): repeat
+        { step; inner_sweeps exact sweeps } with the looks and stop rules of CP.run_wls. Returns
+        (rc, iterations, ||X - model||)."""
         o = _opts(**opts)
         it, res = C.c_int(0), C.c_double(0)
+        if self.is_ragged:
+            ptr, code, off, cs = self._slices_view(X, offsets, col_strides, stream)
+            rc = _check(lib().ppals_parafac2_run_ragged(self._h, C.c_void_p(int(ptr)), int(code), self._i64(off),
+                                                        self._i64(cs), C.c_void_p(int(Tensor._stream(stream) or 0)),
+                                                        C.byref(o), int(inner_sweeps), C.c_double(float(rel_change)),
+                                                        C.byref(it), C.byref(res)))
+            return rc, it.value, res.value
+        ptr, code, st = self._view(X)
         rc = _check(lib().ppals_parafac2_run(self._h, C.c_void_p(int(ptr)), int(code), st,
                                              C.c_void_p(int(Tensor._stream(stream) or 0)), C.byref(o),
                                              int(inner_sweeps), C.c_double(float(rel_change)), C.byref(it),
                                              C.byref(res)))
         return rc, it.value, res.value
 
-    def loss(self, X, stream=None):
+    def loss(self, X, stream=None, offsets=None, col_strides=None):
         """||X - model||^2 of the session's current factors with the P_k that are best for them: takes a step
         (which can only lower the loss), then lost_sq + the inner residual squared"""
-        lost, _ = self.step_torch(X, stream)
+        if self.is_ragged:
+            lost, _ = self.step_torch(X, stream, offsets=offsets, col_strides=col_strides)
+        else:
+            lost, _ = self.step_torch(X, stream)
         return max(lost, 0.0) + self.cp.residual() ** 2
 
     def projections(self):
-        """the P_k as a K x I x R numpy array"""
+        """the P_k as a K x I x R numpy array; of a ragged object as a list of K arrays rows[k] x R"""
+        if self.is_ragged:
+            rows = self.rows
+            flat_p = np.empty(sum(rows) * self.R)
+            _check(lib().ppals_parafac2_projections(self._h, _dp(flat_p)))
+            out, o = [], 0
+            for n in rows:
+                out.append(np.ascontiguousarray(flat_p[o:o + n * self.R].reshape((n, self.R), order="F")))
+                o += n * self.R
+            return out
         out = np.empty((self.I, self.R, self.K), order="F")
         _check(lib().ppals_parafac2_projections(self._h, _dp(out)))
         return np.ascontiguousarray(out.transpose(2, 0, 1))
@@ -1181,8 +1301,11 @@ class Parafac2:
         return C.cast(ptr, C.c_void_p).value
 
     def profiles(self):
-        """the slice profiles P_k B as a K x I x R numpy array"""
-        return self.projections() @ self.cp.get_factors()[0]
+        """the slice profiles P_k B as a K x I x R numpy array; of a ragged object as a list of rows[k] x R arrays"""
+        B = self.cp.get_factors()[0]
+        if self.is_ragged:
+            return [P @ B for P in self.projections()]
+        return self.projections() @ B
 
     def close(self):
         if self._h:
@@ -1190,6 +1313,7 @@ class Parafac2:
             self.Y.close()
             lib().ppals_parafac2_destroy(self._h)
             self._h = C.c_void_p()
+            self._pack = None
 
     def __del__(self):
         try:
@@ -1201,14 +1325,25 @@ class Parafac2:
 def parafac2(X, R, n_iter=100, nonneg_modes=(), inner_sweeps=1, rel_change=0.0, dtype=F64, ctx=None, A0=None):
     """PARAFAC2 of a torch tensor X (I x J x K on a GPU, float32 or float64; mode 0 shifts, mode 2 are the slices).
     nonneg_modes: which of the modes 1 (A) and 2 (C) are non-negative. Looks at the loss at every iteration.
+    X may also be a list or tuple of K torch matrices rows[k] x J, slices of unequal length (Parafac2.ragged).
     Returns a dict: B, A, C, projections (K x I x R), profiles (K x I x R), losses (||X - model||^2 per
-    iteration, the final one last), iterations, rc."""
-    if X.stride(0) != 1:
-        X = X.permute(2, 1, 0).contiguous().permute(2, 1, 0)
+    iteration, the final one last), iterations, rc; for a list input projections and profiles are lists of K
+    arrays rows[k] x R."""
+    slices = isinstance(X, (list, tuple))
+    if slices:
+        X = list(X)
+        dev, (J, K) = X[0].device, (X[0].shape[1], len(X))
+    else:
+        if X.stride(0) != 1:
+            X = X.permute(2, 1, 0).contiguous().permute(2, 1, 0)
+        dev = X.device
     own = ctx is None
-    ctx = ctx or Context(X.device.index or 0)
-    I, J, K = X.shape
-    p2 = Parafac2(ctx, I, J, K, R, dtype)
+    ctx = ctx or Context(dev.index or 0)
+    if slices:
+        p2 = Parafac2.ragged(ctx, [x.shape[0] for x in X], J, R, dtype)
+    else:
+        I, J, K = X.shape
+        p2 = Parafac2(ctx, I, J, K, R, dtype)
     try:
         if A0 is not None:
             p2.cp.set_factors([np.eye(R), np.asarray(A0, dtype=np.float64), np.ones((K, R))])
